@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - frames/sec of the MI355X EfficientPose path at 256x256, batch 16 per GPU, phi 0.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,9 +12,15 @@ One step = one pass of the hot path over one batch of 16 synthetic, HBM-resident
 GPU: the full forward (stem .. heads, one hipGraph replay) + box/translation decode, through
 the C ABI of libhep.so.  --inflight D (default 4) keeps D steps in flight on D HIP streams (D
 sessions): a single forward is a dependent chain of small kernels and leaves most of the
-256 CUs idle; `one_batch_in_flight` reports the strictly sequential number as well.  Weak scaling:
-every rank owns 16 frames, the forward needs no collective (frames are independent); ranks meet
-only at the timing barriers.  Rank 0 prints ONE JSON line.  It also carries
+256 CUs idle.  Weak scaling: every rank owns 16 frames, the forward needs no collective (frames
+are independent); ranks meet only at the timing barriers.
+
+A plain run does only what the headline figure needs: set-up, warm-up, EXACTLY --steps timed steps, and rank 0 prints ONE JSON
+line (`value` frames/s over all ranks, `ms_per_step` the wall time of one timed step, `metric`, `unit`, `higher_is_better`,
+`dtype`, `config`).  --dump-outputs DIR also writes what the last timed step computed (dump_outputs below).
+--full measures everything else as well; the line then also carries
+  one_batch_in_flight  (N=1) the strictly sequential number (one batch in flight): latency of a step
+  single_thread_value  the timed window again, submitted from one thread
   sustained     the same loop run for >= 2 s: frames/s and min / median / max over 10 sub-windows
   fp32          (N=1) the same two figures for an fp32 session - the precision that meets the 0.1 mm ADD bound
                 (no bf16 storage boundary does on the seeded weights)
@@ -30,9 +36,9 @@ only at the timing barriers.  Rank 0 prints ONE JSON line.  It also carries
                 "effnet_b0_512", FP32, batch 1, prep + inference 175 / 40 / 16 ms on the ONNXRuntime CPU / CUDA / TensorRT providers,
                 + 6-8 ms preprocessing): phi 0 at 512x512, fp32, batch 1, called through the C ABI the way the C# host would -
                 p50 / p99 over >= 200 back-to-back calls, the same call paced at 60 Hz, and the model-load time (hep_create).
+The --no-* options trim a --full run.
 The timed loop is fed by one submission thread per stream (joined before the closing barrier; a thread that raises fails the run):
 after a synchronize the first graph launch costs the host ~140 us, and with one Python thread the other streams wait behind it.
-`single_thread_value` is the same loop submitted from one thread.
 Before the --warmup steps every loop keeps the device busy with the same step for --preheat-ms (default 50, reported as `preheat_ms`;
 untimed set-up): an MI355X that has had no work for >= 10 ms runs its next ~20 ms of launches up to 8 % slower
 (tools/exp/window_ramp.py), and session set-up ends with such a gap.  The timed region itself is unchanged: exactly --steps steps
@@ -338,6 +344,28 @@ def launch_profile(sess, B, ms_step, ms_one_batch, traffic_of=None, layers=True)
     return out
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_HEADS = ("regression", "classification", "rotation", "translation_raw", "hand")
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write `arrays` (name -> [batch, anchors, k] array) as path/<name>.npy in float32.  When they exceed `budget`
+    bytes together, every array keeps the same fixed, seeded sample of anchors (sorted, axis 1), so that two builds stay comparable
+    file for file.  Returns the number of anchors written."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    n = next(iter(arrays.values())).shape[1]
+    per_anchor = sum(a.nbytes // n for a in arrays.values())
+    keep = min(n, (budget - 256 * len(arrays)) // per_anchor)          # (256 bytes per .npy header)
+    if keep < n:
+        idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[:, idx]) for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return keep
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -347,6 +375,10 @@ def parse_args(argv=None):
     ap.add_argument("--phi", type=int, default=0)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--precision", default="bf16", choices=PRECISIONS)
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline figure as well (one batch in flight, single-thread "
+                    "submission, sustained, comm, roofline, fp32, latency_b1, cpu_baseline, add_vs_ref); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (the five heads, boxes, "
+                    "translation) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-comm", action="store_true", help="skip the scatter -> preprocess -> forward -> filter -> gather loop")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 (accuracy-bound-meeting) throughput block")
@@ -361,7 +393,10 @@ def parse_args(argv=None):
     ap.add_argument("--inflight", type=int, default=4, help="batches in flight per GPU (sessions on separate HIP streams)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for wiring tests)")
     ap.add_argument("--single-device", action="store_true", help="wiring test: every rank uses cuda:0 (needs --backend gloo)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def visible_gpu_count():
@@ -576,9 +611,15 @@ def main():
     main_loop.run(args.steps)           # EXACTLY --steps steps: submission thread d enqueues steps d, d + D, ... on stream d and is joined here
     torch.cuda.synchronize(dev); hd.barrier()
     elapsed = hd.max_over_ranks(time.perf_counter() - t0, dev)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (step --steps - 1, slot (steps - 1) % D): the handle's five
+        # head buffers and the decoded boxes / translations
+        d = (args.steps - 1) % D
+        heads = [v[:B].cpu().numpy() for v in main_loop.sess[d].output_views()]
+        dump_outputs(args.dump_outputs, dict(zip(DUMP_HEADS, heads), boxes=main_loop.boxes[d].cpu().numpy(), translation=main_loop.trans[d].cpu().numpy()))
     # the same window submitted from ONE thread (what `value` was until round 5): a side figure
     single_elapsed = None
-    if main_loop.pool is not None:
+    if args.full and main_loop.pool is not None:
         main_loop.preheat(args.preheat_ms / 1e3)
         main_loop.timed(args.warmup, threads=False)
         single_elapsed = hd.max_over_ranks(main_loop.timed(args.steps, threads=False), dev)
@@ -586,7 +627,7 @@ def main():
 
     # ---- the same loop for >= sustain_seconds, in 10 sub-windows (a 20-step run is 7 ms: this is the figure to trust) ----
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         per = max(args.steps, int(args.sustain_seconds / 10 / max(elapsed / args.steps, 1e-6)) + 1)
         wins = []
         hd.barrier()
@@ -602,7 +643,7 @@ def main():
     #      gather of step i - 1 overlap the compute of step i (measured at N = 1: 2 / 3 / 4 in flight 36.6k / 42.3k /
     #      46.5k frames/s) ----
     comm = None
-    if not args.no_comm:
+    if args.full and not args.no_comm:
         G = B * world
         M = 100
         frames_u8 = torch.from_numpy(np.random.Generator(np.random.PCG64(7)).integers(0, 256, (G, S, S, 3), dtype=np.uint8)).to(dev) if rank == 0 else None
@@ -692,7 +733,7 @@ def main():
             out["sustained"] = sustained
         if comm is not None:
             out["comm"] = comm
-        if world == 1:
+        if args.full and world == 1:
             # the strictly sequential number (one batch in flight): latency of a step
             k1 = max(50, args.steps // 2)
             main_loop.timed(10, 1)

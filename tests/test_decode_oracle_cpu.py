@@ -6,7 +6,6 @@ lower index)."""
 import math
 
 import numpy as np
-import pytest
 
 from oracle import decode_ref as D
 
@@ -150,29 +149,32 @@ def test_preprocess_image_restatement():
 
 
 def test_min_distances_match_the_compiled_reference():
-    """oracle.min_distances (numpy) against c_min_distances of the reference's own calc_min_distances.h, compiled by
-    oracle/Makefile from where it lies under /root/reference (oracle/_ref/libmindist.so): bit for bit, on clouds with
-    close pairs, duplicates and large offsets; and add_s_metric's subsampling (step = n // 1000 + 1)."""
+    """oracle.min_distances (numpy) against c_min_distances of the reference's own calc_min_distances.h: bit for bit, on
+    clouds with close pairs, duplicates and large offsets; and add_s_metric's subsampling (step = n // 1000 + 1).  The
+    reference's answers are stored in tests/golden/min_distances.npz (tests/golden/make_golden_min_distances.py, from
+    oracle/_ref/libmindist.so, which oracle/Makefile compiles out of the reference's header); where that library has been
+    built, the stored answers are checked against it as well."""
+    import importlib.util
     import os
-    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libmindist.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libmindist.so not built (needs /root/reference: `make -C oracle`)")
-    rng = np.random.Generator(np.random.PCG64(5))
-    for n_g, n_p, scale, off in ((1, 1, 1.0, 0.0), (7, 13, 100.0, 0.0), (500, 500, 130.0, 2.5), (1000, 777, 0.05, 1000.0)):
-        g = (rng.standard_normal((n_g, 3)) * scale + off).astype(np.float32)
-        p = (rng.standard_normal((n_p, 3)) * scale + off).astype(np.float32)
-        if n_p > 10:
-            p[3] = g[min(2, n_g - 1)]                       # an exact hit
-            p[5] = p[4]                                    # duplicates
-        want = D.reference_min_distances(g, p)
+    here = os.path.dirname(os.path.abspath(__file__))
+    spec = importlib.util.spec_from_file_location("mgm", os.path.join(here, "golden", "make_golden_min_distances.py"))
+    mgm = importlib.util.module_from_spec(spec); spec.loader.exec_module(mgm)
+    fx = np.load(os.path.join(here, "golden", "min_distances.npz"))
+    live = os.path.exists(os.path.join(os.path.dirname(here), "oracle", "_ref", "libmindist.so"))
+    clouds, metric = mgm.cases()
+    assert set(fx.files) == {name for name, _, _ in clouds} | {"add_s_metric"}
+    for name, g, p in clouds:
+        want = fx[name]
+        assert want.dtype == np.float32 and want.shape == (g.shape[0],), name
+        if live:
+            assert np.array_equal(D.reference_min_distances(g, p), want), name
         got = D.min_distances(g, p)
-        assert got.dtype == np.float32 and np.array_equal(got, want), (n_g, n_p)
+        assert got.dtype == np.float32 and np.array_equal(got, want), name
     # the metric: 2500 model points -> step 3 -> 834 points per cloud
-    pts = (rng.standard_normal((2500, 3)) * 60).astype(np.float32)
-    Rg, Rp = D.rodrigues(np.array([0.3, -1.2, 0.5])), D.rodrigues(np.array([0.31, -1.18, 0.52]))
-    tg, tp = np.array([10., -20., 600.]), np.array([11., -19., 604.])
-    ok, d = D.add_s_metric(pts, 150.0, Rg, tg, Rp, tp)
-    ref = D.reference_min_distances((pts @ Rg.T + tg)[::3], (pts @ Rp.T + tp)[::3])
+    ok, d = D.add_s_metric(metric[0], 150.0, *metric[1:])
+    ref = fx["add_s_metric"]
+    if live:
+        assert np.array_equal(D.reference_min_distances(*mgm.metric_clouds(*metric)), ref)
     assert len(ref) == 834 and d == float(np.mean(ref)) and ok == (d <= 15.0)
 
 

@@ -1425,11 +1425,11 @@ def test_reference_checkpoint_known_answers(api):
 
 
 def test_bench_line_contract():
-    """`python bench.py` on one GPU prints ONE JSON line with the driver's keys, BASELINE.json's metric, the two extra
+    """`python bench.py --full` on one GPU prints ONE JSON line with the driver's keys, BASELINE.json's metric, the two extra
     objects (`roofline`, `cpu_baseline`) and figures that are consistent with each other."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--sustain-seconds", "0.3"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--sustain-seconds", "0.3"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -1455,6 +1455,44 @@ def test_bench_line_contract():
     f32 = d["fp32"]["roofline"]
     assert f32["kernel"] and 0 < f32["time_weighted_frac"] < 1 and f32["layers_total"] >= 50
     assert "not the parity-tested weight set" in d["comm"]["what"]
+
+
+def test_plain_bench_line_and_dumped_outputs(api, tmp_path):
+    """`python bench.py` without --full: ONE JSON line with the headline keys and none of the --full blocks, exactly --steps timed
+    steps; --dump-outputs writes the last timed step's heads, boxes and translations (float32, <= 64 MB), and they are what a
+    session of the same precision computes for that step's seeded frames (step 6 of 7 runs on slot 6 % 4 = 2)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    base = json.load(open(os.path.join(root, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["n_gpus"] == 1 and abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    assert not {"roofline", "cpu_baseline", "add_vs_ref", "fp32", "comm", "sustained", "one_batch_in_flight", "single_thread_value", "latency_b1"} & set(d)
+    s = api["Session"](api["sd"](0, 0), 0, 256, 16, "bf16")
+    N = s.num_anchors
+    widths = dict(zip(("regression", "classification", "rotation", "translation_raw", "hand"), s.out_width), boxes=4, translation=3)
+    files = sorted(os.listdir(out_dir))
+    assert files == sorted(k + ".npy" for k in widths), files
+    assert sum(os.path.getsize(out_dir / f) for f in files) <= 64_000_000
+    got = {k: np.load(out_dir / (k + ".npy")) for k in widths}
+    for k, w in widths.items():
+        assert got[k].dtype == np.float32 and got[k].shape == (16, N, w), (k, got[k].shape)      # the default workload fits whole
+    rng = np.random.Generator(np.random.PCG64(1000))
+    x = [rng.standard_normal((16, 3, 256, 256)).astype(np.float32) for _ in range(3)][2]
+    _, *heads = s.forward(torch.from_numpy(x).cuda(), want_features=False)
+    cam = torch.tensor([[480, 480, 128, 128, 1000, 1.0]] * 16, dtype=torch.float32).cuda()
+    boxes, trans = s.decode(heads[0], heads[3], cam)
+    want = dict(zip(("regression", "classification", "rotation", "translation_raw", "hand"), heads), boxes=boxes, translation=trans)
+    for k in widths:
+        w = want[k].cpu().numpy()
+        assert np.isfinite(got[k]).all() and np.allclose(got[k], w, rtol=1e-5, atol=1e-5), (k, float(np.abs(got[k] - w).max()))
+    s.close()
 
 
 @pytest.mark.parametrize("precision,env", [("fp32", {}), ("bf16", {"HEP_CHAIN_STREAM": "1"})])
@@ -1512,7 +1550,7 @@ def test_two_gpu_rccl_bench_line():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

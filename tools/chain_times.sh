@@ -3,7 +3,7 @@
 # usage (GPU box): tools/chain_times.sh <kernel substring> [count]
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tr
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-comm --no-fp32 --sustain-seconds 0 --inflight 1 > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-comm --no-fp32 --sustain-seconds 0 --inflight 1 > /dev/null 2>&1
 python3 - "$1" "${2:-8}" <<'PY'
 import csv, glob, sys
 f = glob.glob("/tmp/tr/**/*kernel_trace.csv", recursive=True)[0]

@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r4b
-B="python bench.py --precision fp32 --no-cpu-baseline --no-comm --no-fp32 --no-layers --sustain-seconds 0 --steps 200"
+B="python bench.py --full --precision fp32 --no-cpu-baseline --no-comm --no-fp32 --no-layers --sustain-seconds 0 --steps 200"
 run() { echo "== $1"; env $1 $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['one_batch_in_flight'], d['config']['launches_per_step'])"; }
 run X=1
 run HEP_MBF=none

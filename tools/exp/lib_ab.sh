@@ -3,7 +3,7 @@
 #   tools/exp/lib_ab.sh <libA.so> <libB.so> [rounds] [extra bench.py args, e.g. --precision fp32]
 # prints per run: sustained frames/s (four batches in flight, >= 1 s), the one-batch figure, launches per step; then the medians
 A=$1; B=$2; R=${3:-3}; shift 3 2>/dev/null
-BENCH="python bench.py --no-cpu-baseline --no-comm --no-fp32 --no-layers --no-latency --sustain-seconds 1 --steps 200 $*"
+BENCH="python bench.py --full --no-cpu-baseline --no-comm --no-fp32 --no-layers --no-latency --sustain-seconds 1 --steps 200 $*"
 for i in $(seq $R); do
   for L in "$A" "$B"; do
     HEP_LIB=$PWD/$L $BENCH 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', d['sustained']['value'], d['one_batch_in_flight']['value'], d['config']['launches_per_step'])"
