@@ -351,6 +351,14 @@ struct LossArgs {
   float* losses;                                // [5]: batch means, regression x 50
 };
 void launch_losses(const LossArgs&, hipStream_t);
+// ... and their backward (k_loss_grad.hip): the gradients of the predictions for an upstream gradient of the per-image losses
+struct LossGradArgs {
+  LossArgs f;                                   // the forward's inputs and sizes (per_image / losses unused)
+  const float* u;                               // [B][5] upstream gradient of per_image
+  float* g_cls; float* g_reg; float* g_tr; float* g_hand;   // [B][N][K], [B][N][4], [B][N][R+3], [B][N][H] (each nullable)
+  int32_t* ws;                                  // [B][4] counts (n_c, n_r, n_t, n_h), then [B][N] object anchors of the transformation state
+};
+void launch_losses_backward(const LossGradArgs&, hipStream_t);
 
 void launch_stem(const StemArgs&, hipStream_t);
 int stem_uses_mfma(int cout, int force = -1);      // which of the two stem kernels the plan takes (force: Knobs::stem_mfma, -1 = by width)

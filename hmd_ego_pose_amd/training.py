@@ -5,10 +5,12 @@ the per-batch classification / regression / transformation / hand targets on the
 (generators/utils/compute_overlap.pyx:33-73); here the assignment runs in one kernel (csrc/k_eval.hip,
 hep_anchor_targets_device) and its outputs stay on the device for the losses.
 
-``losses`` is ``batch_iterate`` (pytorch-sandbox/hmdegopose/loss.py:54-99): the forward VALUES of the focal, box, rotation
-(model-point distance), translation and hand losses, one workgroup per image (hep_losses_device).  The reference computes
-them with a Python loop over the batch and per-image gathers; gradients stay with the caller's autograd - training
-through the HIP forward is out of scope (the inference path has no backward).
+``losses`` is ``batch_iterate`` (pytorch-sandbox/hmdegopose/loss.py:54-99): the focal, box, rotation (model-point
+distance), translation and hand losses, one workgroup per image (hep_losses_device).  The reference computes them with a
+Python loop over the batch and per-image gathers.  When a prediction requires grad the outputs carry a ``grad_fn`` whose
+backward is HIP as well (csrc/k_loss_grad.hip, hep_losses_backward_device): the gradients the reference's autograd returns,
+computed on the whole GPU without a host synchronisation.  ``batch_iterate`` is the drop-in with the reference's signature
+and return shape.  Backward through the HIP network forward stays out of scope (the inference path has no backward).
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _capi
 
@@ -58,13 +61,13 @@ def anchor_targets(anchors: torch.Tensor, boxes: Sequence[np.ndarray], labels: S
     return lab, reg, tra, crd
 
 
-def losses(gt_classification: torch.Tensor, classification: torch.Tensor, gt_regression: torch.Tensor, regression: torch.Tensor,
-           gt_transformation: torch.Tensor, transformation: torch.Tensor, gt_hand: Optional[torch.Tensor], hand: Optional[torch.Tensor],
-           model_3d_points, num_rotation_parameter: int = 3):
-    """``batch_iterate`` (hmdegopose/loss.py:54-99) on float32 ROCm tensors laid out as the generator / the network
-    produce them (see include/hep.h: hep_losses_device); ``model_3d_points`` [classes, P, 3] (numpy or tensor).  Returns
-    (losses [5] = classification, regression x 50, rotation, translation, hand - the batch means, per_image [B, 5])."""
-    dev = classification.device
+_PRED_NAMES = ("classification", "regression", "transformation", "hand")
+_MEAN_SCALE = (1.0, 50.0, 1.0, 1.0, 1.0)      # d losses / d per_image[b] = scale / B (regression x 50)
+
+
+def _loss_inputs(gt_classification, classification, gt_regression, regression, gt_transformation, transformation, gt_hand, hand,
+                 model_3d_points, num_rotation_parameter):
+    """Validated, contiguous float32 device tensors and sizes (the contiguous copies are autograd-tracked)."""
     def chk(x, name):
         if x is None:
             return None
@@ -73,24 +76,111 @@ def losses(gt_classification: torch.Tensor, classification: torch.Tensor, gt_reg
         return x.contiguous()
     gc, pc, gr, pr = chk(gt_classification, "gt_classification"), chk(classification, "classification"), chk(gt_regression, "gt_regression"), chk(regression, "regression")
     gt, pt, gh, ph = chk(gt_transformation, "gt_transformation"), chk(transformation, "transformation"), chk(gt_hand, "gt_hand"), chk(hand, "hand")
+    if pc.dim() != 3:
+        raise ValueError("loss inputs do not have the reference's shapes")
     B, N, K = pc.shape
     R = int(num_rotation_parameter)
     if gc.shape != (B, N, K + 1) or gr.shape != (B, N, 5) or pr.shape != (B, N, 4) or gt.shape != (B, N, R + 6) or pt.shape != (B, N, R + 3):
         raise ValueError("loss inputs do not have the reference's shapes")
     H = 0
     if ph is not None:
-        H = int(ph.shape[2])
+        H = int(ph.shape[2]) if ph.dim() == 3 else -1
         if gh is None or gh.shape != (B, N, H + 1) or ph.shape != (B, N, H):
             raise ValueError("gt_hand must be [B, N, H + 1] next to hand [B, N, H]")
     pts = torch.as_tensor(np.asarray(model_3d_points, dtype=np.float32) if not torch.is_tensor(model_3d_points) else model_3d_points,
-                          dtype=torch.float32).to(dev).contiguous()
+                          dtype=torch.float32).to(pc.device).contiguous()
     if pts.dim() != 3 or pts.shape[2] != 3:
         raise ValueError("model_3d_points must be [classes, P, 3]")
+    return (gc, pc, gr, pr, gt, pt, gh, ph, pts), (B, N, K, R, H, int(pts.shape[0]), int(pts.shape[1]))
+
+
+def _losses_forward(t, sizes):
+    gc, pc, gr, pr, gt, pt, gh, ph, pts = t
+    B, N, K, R, H, C, P = sizes
+    dev = pc.device
     per = torch.empty((B, 5), dtype=torch.float32, device=dev)
     out = torch.empty((5,), dtype=torch.float32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     _capi.check(_capi.lib().hep_losses_device(gc.data_ptr(), pc.data_ptr(), gr.data_ptr(), pr.data_ptr(), gt.data_ptr(), pt.data_ptr(),
-                                              _capi.ptr(gh), _capi.ptr(ph), pts.data_ptr(), B, N, K, R, H, int(pts.shape[0]), int(pts.shape[1]),
+                                              _capi.ptr(gh), _capi.ptr(ph), pts.data_ptr(), B, N, K, R, H, C, P,
                                               per.data_ptr(), out.data_ptr(), stream))
     torch.cuda.current_stream(dev).synchronize()      # the contiguous copies above must outlive the launch
     return out, per
+
+
+def losses_backward(t, sizes, grad_per_image, need=(True, True, True, True)):
+    """hep_losses_backward_device on the current stream: the gradients of (classification, regression, transformation,
+    hand) for the upstream gradient ``grad_per_image`` [B, 5] of the per-image losses (None where ``need`` is False or
+    there is no hand).  ``t`` / ``sizes`` as _loss_inputs returns them.  No host synchronisation: every tensor involved is
+    allocated on, and stays alive with respect to, the current stream."""
+    gc, pc, gr, pr, gt, pt, gh, ph, pts = t
+    B, N, K, R, H, C, P = sizes
+    dev = pc.device
+    u = grad_per_image.to(device=dev, dtype=torch.float32).contiguous()
+    if u.shape != (B, 5):
+        raise ValueError("grad_per_image must be [B, 5]")
+    f = lambda on, *shape: torch.empty(shape, dtype=torch.float32, device=dev) if on else None
+    g_cls, g_reg, g_tr = f(need[0], B, N, K), f(need[1], B, N, 4), f(need[2], B, N, R + 3)
+    g_hand = f(need[3] and ph is not None, B, N, H)
+    ws = torch.empty((B * (N + 4),), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().hep_losses_backward_device(gc.data_ptr(), pc.data_ptr(), gr.data_ptr(), pr.data_ptr(), gt.data_ptr(), pt.data_ptr(),
+                                                       _capi.ptr(gh), _capi.ptr(ph), pts.data_ptr(), B, N, K, R, H, C, P, u.data_ptr(),
+                                                       _capi.ptr(g_cls), _capi.ptr(g_reg), _capi.ptr(g_tr), _capi.ptr(g_hand),
+                                                       ws.data_ptr(), stream))
+    return g_cls, g_reg, g_tr, g_hand
+
+
+class _Losses(torch.autograd.Function):
+    """losses() with a HIP backward; inputs are _loss_inputs' tensors, gradients flow to the four predictions only."""
+
+    @staticmethod
+    def forward(ctx, gc, pc, gr, pr, gt, pt, gh, ph, pts, sizes):
+        out, per = _losses_forward((gc, pc, gr, pr, gt, pt, gh, ph, pts), sizes)
+        ctx.save_for_backward(gc, pc, gr, pr, gt, pt, gh, ph, pts)
+        ctx.sizes = sizes
+        return out, per
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_per):
+        t = ctx.saved_tensors
+        B = ctx.sizes[0]
+        dev = t[1].device
+        u = torch.zeros((B, 5), dtype=torch.float32, device=dev)
+        if g_per is not None:
+            u = u + g_per
+        if g_out is not None:
+            u = u + (g_out * torch.tensor(_MEAN_SCALE, dtype=torch.float32, device=dev) / B)[None]
+        nig = ctx.needs_input_grad
+        g_cls, g_reg, g_tr, g_hand = losses_backward(t, ctx.sizes, u, (nig[1], nig[3], nig[5], nig[7]))
+        return None, g_cls, None, g_reg, None, g_tr, None, g_hand, None, None
+
+
+def losses(gt_classification: torch.Tensor, classification: torch.Tensor, gt_regression: torch.Tensor, regression: torch.Tensor,
+           gt_transformation: torch.Tensor, transformation: torch.Tensor, gt_hand: Optional[torch.Tensor], hand: Optional[torch.Tensor],
+           model_3d_points, num_rotation_parameter: int = 3):
+    """``batch_iterate`` (hmdegopose/loss.py:54-99) on float32 ROCm tensors laid out as the generator / the network
+    produce them (see include/hep.h: hep_losses_device); ``model_3d_points`` [classes, P, 3] (numpy or tensor).  Returns
+    (losses [5] = classification, regression x 50, rotation, translation, hand - the batch means, per_image [B, 5]).
+    When grad mode is on and a prediction (classification / regression / transformation / hand) requires grad, both
+    outputs carry a ``grad_fn`` whose backward is hep_losses_backward_device; the targets and the model points get no
+    gradient.  The values are the same either way."""
+    t, sizes = _loss_inputs(gt_classification, classification, gt_regression, regression, gt_transformation, transformation, gt_hand,
+                            hand, model_3d_points, num_rotation_parameter)
+    if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (t[1], t[3], t[5], t[7])):
+        return _Losses.apply(*t, sizes)
+    return _losses_forward(t, sizes)
+
+
+def batch_iterate(gt_classification, classification, gt_regression, regression, gt_transformation, transformation, gt_hand, hand,
+                  model_3d_points, num_rotation_parameter):
+    """Drop-in for the reference's ``hmdegopose.loss.batch_iterate`` (loss.py:54-99), differentiable: returns the five
+    losses (classification, regression x 50, rotation, translation, hand) as tensors of shape [1], like the reference.
+    The predictions must be float32 ROCm tensors (any strides); targets on the host are moved to their device;
+    ``model_3d_points`` may be numpy."""
+    dev = classification.device
+    mv = lambda x: None if x is None else (x if x.is_cuda else x.to(dev)).to(torch.float32)
+    out, _per = losses(mv(gt_classification), classification, mv(gt_regression), regression, mv(gt_transformation), transformation,
+                       mv(gt_hand), hand, model_3d_points, num_rotation_parameter)
+    return tuple(out[k:k + 1] for k in range(5))

@@ -23,6 +23,7 @@
  *                                 (C# twin Program.cs:472-627)
  *   hep_anchor_targets_device  <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
+ *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
  *   hep_pose_errors / _device  <- check_6d_pose_add / check_6d_pose_add_s, pytorch-sandbox/eval/common.py:682-746 with
  *                                 c_min_distances, pytorch-sandbox/generators/utils/calc_min_distances.h:24-35 (the
  *                                 metric arithmetic of evaluate.py's loop, eval/common.py:866-1121)
@@ -200,12 +201,31 @@ int hep_anchor_targets_device(const float* anchors, int num_anchors, const doubl
  * (rotation, translation, is_symmetric, class index, anchor state), transformation [batch][N][num_rotation+3] =
  * cat(rotation head, decoded translation) (train.py:49), gt_hand [batch][N][num_hand+1], hand [batch][N][num_hand],
  * model_points [num_model_classes][num_points][3] (num_points <= 2048).  Outputs: per_image [batch][5] and losses [5] =
- * (classification, regression, rotation, translation, hand), the batch means.  Backward stays with the caller's
- * autograd (the reference's optimiser loop, train.py:88-342, is out of scope). */
+ * (classification, regression, rotation, translation, hand), the batch means.  The gradients are
+ * hep_losses_backward_device below (the reference's optimiser loop, train.py:88-342, stays with the caller). */
 int hep_losses_device(const float* gt_classification, const float* classification, const float* gt_regression, const float* regression,
                       const float* gt_transformation, const float* transformation, const float* gt_hand, const float* hand,
                       const float* model_points, int batch, int num_anchors, int num_classes, int num_rotation, int num_hand,
                       int num_model_classes, int num_points, float* per_image, float* losses, void* stream);
+
+/* Backward of hep_losses_device: what the reference's autograd returns for batch_iterate.  Same inputs, sizes and
+ * argument rules as hep_losses_device; grad_per_image [batch][5] is the upstream gradient of per_image (fold the
+ * gradient of the batch means in first: grad_per_image[b][k] += grad_losses[k] * (k == 1 ? 50 : 1) / batch).  Outputs
+ * (each may be NULL: that tensor is skipped; grad_hand needs hand): grad_classification [batch][N][num_classes],
+ * grad_regression [batch][N][4], grad_transformation [batch][N][num_rotation+3] (rotation, then translation),
+ * grad_hand [batch][N][num_hand].  Every element of a given output is written (zeros included): uninitialised memory
+ * is fine.  workspace: int32 scratch of batch * (num_anchors + 4) entries on the device (per-image counts and the
+ * compacted object anchors), owned by the caller and busy until the launches on `stream` end.  Asynchronous on
+ * `stream`, no host synchronisation and no allocation; bit-reproducible (fixed reduction order, no float atomics).
+ * Edges follow torch: the classification clamp passes the gradient at its bounds (inclusive), smooth-L1 gives 0 at a
+ * zero residual, the translation gradient is 0 in an image without object anchors (whose translation loss is NaN).
+ * An object anchor whose predicted or target rotation vector is exactly zero (no rotation axis; its forward distance
+ * is NaN and the image's rotation loss 0) gets a rotation gradient of 0; the reference's autograd returns NaN there. */
+int hep_losses_backward_device(const float* gt_classification, const float* classification, const float* gt_regression, const float* regression,
+                               const float* gt_transformation, const float* transformation, const float* gt_hand, const float* hand,
+                               const float* model_points, int batch, int num_anchors, int num_classes, int num_rotation, int num_hand,
+                               int num_model_classes, int num_points, const float* grad_per_image, float* grad_classification,
+                               float* grad_regression, float* grad_transformation, float* grad_hand, int32_t* workspace, void* stream);
 
 /* preprocess_image (reference generators/colibri_common.py:622-656): device uint8 RGB [batch, height, width, 3] ->
  * device float32 [batch, size, size, 3]: resize by scale = size / max(height, width) (8-bit bilinear, OpenCV
