@@ -12,6 +12,9 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name in ("HMDEgoPose", "TrainModelWithLoss", "Session"):
         from . import model
         return getattr(model, name)
+    if name == "TrainableHeads":
+        from .heads import TrainableHeads
+        return TrainableHeads
     if name == "InflightPool":
         from .pipeline import InflightPool
         return InflightPool

@@ -49,6 +49,11 @@ SYMBOLS = {
     "hep_anchor_targets_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_double, c_double, _FP, _FP, _FP, _FP, c_void_p]),
     "hep_losses_device": (c_int, [_FP] * 9 + [c_int] * 7 + [_FP, _FP, c_void_p]),
     "hep_losses_backward_device": (c_int, [_FP] * 9 + [c_int] * 7 + [_FP] * 6 + [c_void_p]),
+    "hep_heads_param_count": (c_int64, [c_int, c_int]),
+    "hep_heads_param_layout": (c_int, [c_int, c_int, POINTER(c_int64), c_int]),
+    "hep_heads_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "hep_heads_forward_device": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_void_p]),
+    "hep_heads_backward_device": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, c_int, _FP, POINTER(_FP), c_void_p, c_size_t, c_void_p]),
     "hep_debug_tensor_count": (c_int, [_P]),
     "hep_debug_tensor_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int64)]),
     "hep_debug_tensor": (c_int, [_P, c_char_p, c_int, _FP, c_size_t]),

@@ -705,6 +705,72 @@ int hep_losses_backward_device(const float* gt_classification, const float* clas
   return 0;
 } HEP_CATCH_INT
 
+// ---- training side: the five head nets, forward and backward (k_head_grad.hip) ----
+int64_t hep_heads_param_count(int phi, int num_classes) try {
+  HGPlan p; const char* why = "";
+  if (int rc = heads_plan(phi, num_classes, 0, 0, &p, &why)) return fail(rc, why);
+  return p.nparams;
+} HEP_CATCH_INT
+
+int hep_heads_param_layout(int phi, int num_classes, int64_t* offsets, int capacity) try {
+  HGPlan p; const char* why = "";
+  if (int rc = heads_plan(phi, num_classes, 0, 0, &p, &why)) return fail(rc, why);
+  const int W = p.g.W, D = p.g.D, count = HG_NETS * (3 * D + 5 * D * 4) + HG_SLOTS * 3;
+  if (!offsets) return count;
+  if (capacity < count) return fail(HEP_ERR_INVALID, "hep_heads_param_layout: capacity is smaller than the number of head tensors");
+  int k = 0;
+  for (int n = 0; n < HG_NETS; n++) {
+    for (int i = 0; i < D; i++) {
+      const int64_t c = p.p_conv[n] + (int64_t)i * (9 * W + W * W + W);
+      offsets[k++] = c; offsets[k++] = c + 9 * W; offsets[k++] = c + 9 * W + (int64_t)W * W;
+    }
+    for (int j = 0; j < 5 * D * 4; j++) offsets[k++] = p.p_bn[n] + (int64_t)j * W;
+    for (int h = 0; h < HG_SLOTS; h++)
+      if (p.net[h] == n) { offsets[k++] = p.p_hdr[h]; offsets[k++] = p.p_hdr[h] + 9 * W; offsets[k++] = p.p_hdr[h] + 9 * W + (int64_t)p.C[h] * W; }
+  }
+  return count;
+} HEP_CATCH_INT
+
+int64_t hep_heads_workspace_bytes(int phi, int num_classes, int size, int batch) try {
+  HGPlan p; const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, "heads: size must be a multiple of 128 in [128, 2048]");
+  if (int rc = heads_plan(phi, num_classes, size, batch, &p, &why)) return fail(rc, why);
+  return p.ws_floats * (int64_t)sizeof(float);
+} HEP_CATCH_INT
+
+static int heads_check(int phi, int num_classes, int size, int batch, const void* workspace, size_t workspace_bytes, HGPlan* p) {
+  const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, "heads: size must be a multiple of 128 in [128, 2048]");
+  if (int rc = heads_plan(phi, num_classes, size, batch, p, &why)) return fail(rc, why);
+  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "heads: the workspace must be 16-byte aligned");
+  if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "heads: the workspace is smaller than hep_heads_workspace_bytes");
+  return 0;
+}
+
+int hep_heads_forward_device(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
+                             float* const outs[5], void* workspace, size_t workspace_bytes, void* stream) try {
+  if (!params || !feats || !outs || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 5; i++) if (!feats[i] || !outs[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  HGPlan p;
+  if (int rc = heads_check(phi, num_classes, size, batch, workspace, workspace_bytes, &p)) return rc;
+  launch_heads_forward(p, params, feats, outs, (float*)workspace, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_heads_backward_device(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
+                              float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream) try {
+  if (!params || !grad_outs || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 5; i++) if (!grad_outs[i] || (grad_feats && !grad_feats[i])) return fail(HEP_ERR_INVALID, "bad argument");
+  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  HGPlan p;
+  if (int rc = heads_check(phi, num_classes, size, batch, workspace, workspace_bytes, &p)) return rc;
+  launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, (float*)workspace, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

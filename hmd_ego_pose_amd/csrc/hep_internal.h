@@ -360,6 +360,35 @@ struct LossGradArgs {
 };
 void launch_losses_backward(const LossGradArgs&, hipStream_t);
 
+// ---- training side: forward and backward of the five head nets (k_head_grad.hip) ----
+// Activations live as fp32 rows [R][W]: the pixels of level 0 (all images), then level 1, ...; R = batch * sum(s_l^2).
+#define HG_SLOTS 6           // header separable convs: regressor, classifier, rotation, translation xy, translation z, hand
+#define HG_NETS 5
+#define HG_TILE_ROWS 32      // rows of one column-reduction tile (a tile never crosses a level)
+#define HG_MAX_SLABS 32      // split-K slabs of the weight-gradient products
+struct HGGeom {
+  int B, W, D, R, S;         // batch, width, head depth, rows, pixels per image over the five levels
+  int s[5];                  // side of each level
+  int pixoff[6];             // pixels per image in front of each level
+  int rowoff[6];             // rows in front of each level (= B * pixoff)
+  int tileoff[6];            // column-reduction tiles in front of each level
+  int ntiles, nslab, slab_rows;
+};
+struct HGPlan {
+  HGGeom g;
+  int num_classes;
+  int C[HG_SLOTS], ld[HG_SLOTS];                        // header channels (9 * values per anchor) and their row pitch (C rounded up to 4)
+  int net[HG_SLOTS], K[HG_SLOTS], kh[HG_SLOTS], koff[HG_SLOTS];   // owning net; values per anchor of the net's output, of this header, first column
+  int64_t p_conv[HG_NETS], p_bn[HG_NETS], p_hdr[HG_SLOTS], nparams;   // float offsets into the flat parameter buffer
+  int64_t o_x0, o_x, o_u, o_z, o_uh, o_cl, o_do[HG_SLOTS], o_g1, o_g2, o_pw[HG_SLOTS], o_pdw[HG_SLOTS], o_pbh[HG_SLOTS],
+      o_pg[2], o_pb[2], o_pbi[2], ws_floats;            // float offsets into the workspace
+};
+// fills the plan; returns 0, or a negative HEP_ERR_* with a reason in *why (a static string)
+int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why);
+void launch_heads_forward(const HGPlan&, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t);
+void launch_heads_backward(const HGPlan&, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
+                           float* ws, hipStream_t);
+
 void launch_stem(const StemArgs&, hipStream_t);
 int stem_uses_mfma(int cout, int force = -1);      // which of the two stem kernels the plan takes (force: Knobs::stem_mfma, -1 = by width)
 void launch_pw(const PwArgs&, hipStream_t);

@@ -1,0 +1,579 @@
+// k_head_grad.hip - training forward and backward of the five head nets (regressor, classifier, rotation_net,
+// translation_net, hand_net; reference efficientdet/model.py:361-417, hmdegopose/model.py:55-228 with
+// num_iteration_steps == 0) on gfx950, fp32.  The function is the inference function: BatchNorm uses the RUNNING
+// statistics in forward and backward (frozen-statistics fine-tuning); gamma and beta get gradients.
+//
+// Own kernels and plain layouts (nothing of the inference plan is shared): the parameters are one flat buffer in the
+// reference's shapes and state_dict order, activations are rows [R][W] (pixels of level 0 for every image, then level
+// 1, ...; W channels contiguous), so one launch covers the five levels, and blockIdx.y covers the five nets (or the six
+// header convs).  Per layer   x -> u = depthwise3x3(x) -> z = u . Wp^T + b -> a = bn_level(z) -> x' = swish(a).
+//
+//   forward   rows_from_nchw; per layer dw_fwd + gemm<LAYER> (stores z and x'); headers dw_fwd + gemm<HEADER>
+//             (stores into the [B][N][K] outputs, classifier through a sigmoid, its logits kept)
+//   backward  hdr_gather (cotangents -> rows, header-bias partials); gemm<DATA> (d u = d z . Wp); gemm<WGRAD>
+//             (d Wp = d z^T . u, pixels as K, split into slabs); dw_bwd (depthwise weight partials, depthwise data
+//             gradient = the 3x3 with mirrored taps, then swish' and BatchNorm of the layer below: d z, gamma / beta /
+//             bias partials); reduce (second pass over slabs and tiles); per layer the same four; feats_grad at the end.
+// The pointwise products are v_mfma_f32_16x16x4_f32, four independent accumulators per wave.  Every reduction over
+// pixels, images and levels is partial sums in a fixed order (a thread walks the rows of its tile; a slab is one MFMA
+// chain) plus a second pass that adds the partials in a fixed order in double: bit-reproducible, no float atomics.
+#include "hep.h"
+#include "hep_dev.h"
+#include "hep_internal.h"
+
+#define HG_THREADS 256
+#define HG_BM 64
+#define HG_BN 64
+#define HG_BK 16
+#define HG_LDS_PITCH 80      // floats: rows of a k-step land 16 banks apart (conflict-free fragment reads)
+#define HG_BN_EPS 1e-3f
+
+typedef float hg_f32x4 __attribute__((ext_vector_type(4)));
+
+static const int kFpnWidth[8] = {64, 88, 112, 160, 224, 288, 384, 384};
+static const int kHeadDepth[8] = {3, 3, 3, 4, 4, 4, 5, 5};
+
+__device__ __forceinline__ int hg_level(const HGGeom& g, int r) {
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < 5; i++) l += (r >= g.rowoff[i]);
+  return l;
+}
+__device__ __forceinline__ float hg_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// ------------------------------------------------------------------------------------------------------------------
+struct HGPtr5 { const float* in[5]; float* out[5]; };
+
+// feats[l] NCHW [B][W][s][s] -> rows [R][W]
+__global__ __launch_bounds__(HG_THREADS) void hg_rows_from_nchw_kernel(HGGeom g, HGPtr5 f, float* __restrict__ x0) {
+  const int64_t idx = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+  if (idx >= (int64_t)g.R * g.W) return;
+  const int r = (int)(idx / g.W), c = (int)(idx % g.W);
+  const int l = hg_level(g, r), ss = g.s[l] * g.s[l], q = r - g.rowoff[l], b = q / ss, pix = q % ss;
+  x0[idx] = f.in[l][((int64_t)b * g.W + c) * ss + pix];
+}
+
+// grad_feats[l] NCHW = sum over the five nets (in net order) of the rows d x_0[net]
+__global__ __launch_bounds__(HG_THREADS) void hg_feats_grad_kernel(HGGeom g, HGPtr5 f, const float* __restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x, rw = (int64_t)g.R * g.W;
+  if (idx >= rw) return;
+  const int r = (int)(idx / g.W), c = (int)(idx % g.W);
+  const int l = hg_level(g, r), ss = g.s[l] * g.s[l], q = r - g.rowoff[l], b = q / ss, pix = q % ss;
+  float v = dx[idx];
+#pragma unroll
+  for (int n = 1; n < HG_NETS; n++) v += dx[n * rw + idx];
+  f.out[l][((int64_t)b * g.W + c) * ss + pix] = v;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct HGDwArgs {
+  HGGeom g;
+  const float* src[HG_SLOTS]; const float* w[HG_SLOTS]; float* dst[HG_SLOTS];     // rows, [W][1][3][3], rows
+};
+
+// The 3 x 3 window of rows around row r = pixel (y, x) of an s x s level, zeros outside the map.  A thread that walks
+// consecutive rows keeps it in registers: one new column (three loads) per step instead of nine, all nine at the start of an
+// image row.
+__device__ __forceinline__ void hg_win_col(float (&v)[3][3], const int j, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
+  const int xx = x + j - 1;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const int yy = y + i - 1;
+    v[i][j] = (yy >= 0 && yy < s && xx >= 0 && xx < s) ? p[(int64_t)(r + (i - 1) * s + (j - 1)) * W + c] : 0.0f;
+  }
+}
+__device__ __forceinline__ void hg_win_step(float (&v)[3][3], bool fresh, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
+  if (fresh) {
+    hg_win_col(v, 0, p, r, y, x, s, W, c);
+    hg_win_col(v, 1, p, r, y, x, s, W, c);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { v[i][0] = v[i][1]; v[i][1] = v[i][2]; }
+  }
+  hg_win_col(v, 2, p, r, y, x, s, W, c);
+}
+
+// depthwise 3x3 SAME (zero padding 1) on rows; blockIdx.y = slot; a thread = (HG_DW_ROWS consecutive rows, channel)
+#define HG_DW_ROWS 4
+__global__ __launch_bounds__(HG_THREADS) void hg_dw_fwd_kernel(HGDwArgs a) {
+  const HGGeom& g = a.g;
+  const int slot = blockIdx.y, W = g.W;
+  const int64_t idx = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+  const int ra = (int)(idx / W) * HG_DW_ROWS, c = (int)(idx % W);
+  if (ra >= g.R) return;
+  const int rb = min(g.R, ra + HG_DW_ROWS);
+  const float* __restrict__ src = a.src[slot];
+  float w[9], v[3][3];
+#pragma unroll
+  for (int tp = 0; tp < 9; tp++) w[tp] = a.w[slot][c * 9 + tp];
+  for (int r = ra; r < rb; r++) {
+    const int l = hg_level(g, r), s = g.s[l], pix = (r - g.rowoff[l]) % (s * s), y = pix / s, x = pix % s;
+    hg_win_step(v, r == ra || x == 0, src, r, y, x, s, W, c);
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc = fmaf(w[i * 3 + j], v[i][j], acc);
+    a.dst[slot][(int64_t)r * W + c] = acc;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+enum { HG_LAYER = 0, HG_HEADER = 1, HG_DATA = 2, HG_WGRAD = 3 };
+struct HGGemmArgs {
+  HGGeom g;
+  int ntmax, bn_lstride;
+  const float* A[HG_SLOTS]; const float* Bm[HG_SLOTS]; float* C[HG_SLOTS]; float* C2[HG_SLOTS];
+  const float* bias[HG_SLOTS]; const float* bn[HG_SLOTS];
+  int I[HG_SLOTS], J[HG_SLOTS], K[HG_SLOTS], Kb[HG_SLOTS], lda[HG_SLOTS], ldb[HG_SLOTS], ldc[HG_SLOTS];
+  int hK[HG_SLOTS], hkh[HG_SLOTS], hoff[HG_SLOTS], sigmoid[HG_SLOTS];
+};
+
+// C[i][j] = sum_k A(i,k) B(k,j), 64 x 64 per workgroup, wave w owns rows 16w..16w+15 and four 16-column accumulators.
+//   LAYER   A = u rows (k contiguous), B = Wp [J][K] (k contiguous); z = C + bias -> C, swish(bn_level(z)) -> C2
+//   HEADER  the same product; C + bias (sigmoid for the classifier) -> the [B][N][K] output C2, the logits -> C (nullable)
+//   DATA    A = d z rows (k contiguous, pitch lda = K, padding columns zero), B = Wp [Kb][J] (j contiguous) -> C rows
+//   WGRAD   A = d z rows read as (k = row, i = column), B = u rows (k = row); rows [z * slab_rows, ...) -> C[z][I][J]
+template <int MODE> __global__ __launch_bounds__(HG_THREADS) void hg_gemm_kernel(HGGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[HG_BK][HG_LDS_PITCH];
+  __shared__ __attribute__((aligned(16))) float Bs[HG_BK][HG_LDS_PITCH];
+  const HGGeom& g = a.g;
+  const int slot = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int I = a.I[slot], J = a.J[slot];
+  const int i0 = (int)(blockIdx.x / a.ntmax) * HG_BM, j0 = (int)(blockIdx.x % a.ntmax) * HG_BN;
+  if (i0 >= I || j0 >= J) return;                          // uniform over the workgroup
+  int k_begin = 0, k_end = a.K[slot];
+  if (MODE == HG_WGRAD) { k_begin = blockIdx.z * g.slab_rows; k_end = min(g.R, k_begin + g.slab_rows); }
+  const float* __restrict__ A = a.A[slot];
+  const float* __restrict__ Bm = a.Bm[slot];
+  const int lda = a.lda[slot], ldb = a.ldb[slot];
+  const int kb_end = MODE == HG_DATA ? a.Kb[slot] : k_end;
+  hg_f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) acc[j] = hg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int k0 = k_begin; k0 < k_end; k0 += HG_BK) {
+    float4 va = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vb = va;
+    if (MODE != HG_WGRAD) {                                 // k contiguous: thread = (row i, four k)
+      const int i = lane, kq = wv * 4;
+      if (i0 + i < I && k0 + kq < k_end) va = *reinterpret_cast<const float4*>(A + (int64_t)(i0 + i) * lda + k0 + kq);
+      As[kq + 0][i] = va.x; As[kq + 1][i] = va.y; As[kq + 2][i] = va.z; As[kq + 3][i] = va.w;
+    } else {                                                // i contiguous: thread = (k, four i)
+      const int k = t >> 4, q = (t & 15) * 4;
+      if (k0 + k < k_end && i0 + q < I) va = *reinterpret_cast<const float4*>(A + (int64_t)(k0 + k) * lda + i0 + q);
+      *reinterpret_cast<float4*>(&As[k][q]) = va;
+    }
+    if (MODE == HG_LAYER || MODE == HG_HEADER) {
+      const int j = lane, kq = wv * 4;
+      if (j0 + j < J && k0 + kq < k_end) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(j0 + j) * ldb + k0 + kq);
+      Bs[kq + 0][j] = vb.x; Bs[kq + 1][j] = vb.y; Bs[kq + 2][j] = vb.z; Bs[kq + 3][j] = vb.w;
+    } else {
+      const int k = t >> 4, q = (t & 15) * 4;
+      if (k0 + k < kb_end && j0 + q < J) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(k0 + k) * ldb + j0 + q);
+      *reinterpret_cast<float4*>(&Bs[k][q]) = vb;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < HG_BK / 4; kk++) {
+      const float av = As[kk * 4 + (lane >> 4)][wv * 16 + (lane & 15)];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float bv = Bs[kk * 4 + (lane >> 4)][j * 16 + (lane & 15)];
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // accumulator element (reg): row 4 * (lane >> 4) + reg, column lane & 15
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int n = j0 + j * 16 + (lane & 15);
+    if (n >= J) continue;
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) {
+      const int m = i0 + wv * 16 + (lane >> 4) * 4 + reg;
+      if (m >= I) continue;
+      const float v = acc[j][reg];
+      if (MODE == HG_LAYER) {
+        const int l = hg_level(g, m);
+        const float* __restrict__ bn = a.bn[slot] + (int64_t)l * a.bn_lstride;
+        const float z = v + a.bias[slot][n];
+        const float rstd = 1.0f / sqrtf(bn[3 * g.W + n] + HG_BN_EPS);
+        const float act = (z - bn[2 * g.W + n]) * rstd * bn[n] + bn[g.W + n];
+        a.C[slot][(int64_t)m * g.W + n] = z;
+        a.C2[slot][(int64_t)m * g.W + n] = act * hg_sigmoid(act);
+      } else if (MODE == HG_HEADER) {
+        const int l = hg_level(g, m), ss = g.s[l] * g.s[l], q = m - g.rowoff[l], b = q / ss, pix = q % ss;
+        const int K = a.hK[slot], kh = a.hkh[slot], an = n / kh, jj = n % kh;
+        const float z = v + a.bias[slot][n];
+        if (a.C[slot]) a.C[slot][(int64_t)m * a.ldc[slot] + n] = z;
+        a.C2[slot][((int64_t)b * g.S * 9 + (int64_t)(g.pixoff[l] + pix) * 9 + an) * K + a.hoff[slot] + jj] = a.sigmoid[slot] ? hg_sigmoid(z) : z;
+      } else if (MODE == HG_DATA) {
+        a.C[slot][(int64_t)m * a.ldc[slot] + n] = v;
+      } else {
+        a.C[slot][((int64_t)blockIdx.z * I + m) * J + n] = v;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct HGGatherArgs {
+  HGGeom g;
+  const float* gout[HG_SLOTS]; const float* logits[HG_SLOTS];   // [B][N][K] cotangent of the net's output; classifier logits rows (else NULL)
+  float* dz[HG_SLOTS]; float* pbias[HG_SLOTS];                   // rows [R][ld] (padding columns zero); [tile][ld]
+  int C[HG_SLOTS], ld[HG_SLOTS], hK[HG_SLOTS], hkh[HG_SLOTS], hoff[HG_SLOTS];
+};
+
+// header cotangents as rows + the per-tile partial sums of the header bias gradient; thread = (tile, column), blockIdx.y = slot
+__global__ __launch_bounds__(HG_THREADS) void hg_hdr_gather_kernel(HGGatherArgs a) {
+  const HGGeom& g = a.g;
+  const int slot = blockIdx.y, ld = a.ld[slot];
+  const int64_t gid = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+  if (gid >= (int64_t)g.ntiles * ld) return;
+  const int tile = (int)(gid / ld), c = (int)(gid % ld);
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < 5; i++) l += (tile >= g.tileoff[i]);
+  const int r0 = g.rowoff[l] + (tile - g.tileoff[l]) * HG_TILE_ROWS, r1 = min(g.rowoff[l + 1], r0 + HG_TILE_ROWS);
+  const int ss = g.s[l] * g.s[l], K = a.hK[slot], kh = a.hkh[slot], an = c / kh, jj = c % kh;
+  const bool real = c < a.C[slot];
+  float sum = 0.0f;
+  for (int r = r0; r < r1; r++) {
+    float v = 0.0f;
+    if (real) {
+      const int q = r - g.rowoff[l], b = q / ss, pix = q % ss;
+      v = a.gout[slot][((int64_t)b * g.S * 9 + (int64_t)(g.pixoff[l] + pix) * 9 + an) * K + a.hoff[slot] + jj];
+      if (a.logits[slot]) { const float y = hg_sigmoid(a.logits[slot][(int64_t)r * ld + c]); v *= y * (1.0f - y); }
+    }
+    a.dz[slot][(int64_t)r * ld + c] = v;
+    sum += v;
+  }
+  a.pbias[slot][(int64_t)tile * ld + c] = sum;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct HGDwBwdArgs {
+  HGGeom g;
+  int bn_lstride;
+  int nsrc[HG_NETS];
+  const float* G[HG_NETS][2]; const float* w[HG_NETS][2]; float* pdw[HG_NETS][2];   // d u rows, depthwise weights, [tile][W * 9] partials
+  const float* X[HG_NETS];                        // the depthwise convs' input rows
+  const float* Zprev[HG_NETS]; const float* bnprev[HG_NETS];   // pre-BatchNorm rows and BatchNorm (level 0) of the layer below; NULL at layer 0
+  float* out[HG_NETS];                            // d z of the layer below, or d x_0 at layer 0
+  float* pgamma[HG_NETS]; float* pbeta[HG_NETS]; float* pbias[HG_NETS];   // [tile][W]
+};
+
+// One thread = (tile, channel), blockIdx.y = net; it walks the rows of its tile in order:
+//   depthwise weight gradient  pdw[tap] += d u[r] * x[neighbour(r, tap)]
+//   depthwise data gradient    d x[r]    = sum_tap w[8 - tap] * d u[neighbour(r, tap)]   (summed over the net's headers)
+//   below                      d a = d x * swish'(a), a = bn(z);  d gamma += d a * zhat;  d beta += d a;  d z = d a * gamma * rstd;  d bias += d z
+__global__ __launch_bounds__(HG_THREADS) void hg_dw_bwd_kernel(HGDwBwdArgs a) {
+  const HGGeom& g = a.g;
+  const int net = blockIdx.y, W = g.W;
+  const int64_t gid = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+  if (gid >= (int64_t)g.ntiles * W) return;
+  const int tile = (int)(gid / W), c = (int)(gid % W);
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < 5; i++) l += (tile >= g.tileoff[i]);
+  const int r0 = g.rowoff[l] + (tile - g.tileoff[l]) * HG_TILE_ROWS, r1 = min(g.rowoff[l + 1], r0 + HG_TILE_ROWS);
+  const int s = g.s[l], ss = s * s, nsrc = a.nsrc[net];
+  const float* __restrict__ X = a.X[net];
+  float wt[2][9], aw[2][9];
+#pragma unroll
+  for (int k = 0; k < 2; k++)
+#pragma unroll
+    for (int tp = 0; tp < 9; tp++) { wt[k][tp] = k < nsrc ? a.w[net][k][c * 9 + tp] : 0.0f; aw[k][tp] = 0.0f; }
+  const float* __restrict__ Z = a.Zprev[net];
+  float gamma = 0.0f, beta = 0.0f, mean = 0.0f, rstd = 0.0f;
+  if (Z) {
+    const float* __restrict__ bn = a.bnprev[net] + (int64_t)l * a.bn_lstride;
+    gamma = bn[c]; beta = bn[W + c]; mean = bn[2 * W + c]; rstd = 1.0f / sqrtf(bn[3 * W + c] + HG_BN_EPS);
+  }
+  float ag = 0.0f, ab = 0.0f, abias = 0.0f;
+  float xw[3][3], gw[2][3][3];
+  for (int r = r0; r < r1; r++) {
+    const int pix = (r - g.rowoff[l]) % ss, y = pix / s, x = pix % s;
+    const bool fresh = r == r0 || x == 0;
+    hg_win_step(xw, fresh, X, r, y, x, s, W, c);
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+      if (k < nsrc) hg_win_step(gw[k], fresh, a.G[net][k], r, y, x, s, W, c);
+    float dx = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+      if (k < nsrc) {
+        const float gk = gw[k][1][1];
+#pragma unroll
+        for (int tp = 0; tp < 9; tp++) {
+          aw[k][tp] = fmaf(gk, xw[tp / 3][tp % 3], aw[k][tp]);
+          dx = fmaf(wt[k][8 - tp], gw[k][tp / 3][tp % 3], dx);
+        }
+      }
+    if (Z) {
+      const float zh = (Z[(int64_t)r * W + c] - mean) * rstd, act = zh * gamma + beta, sg = hg_sigmoid(act);
+      const float da = dx * (sg * (1.0f + act * (1.0f - sg)));
+      const float dz = da * gamma * rstd;
+      ag = fmaf(da, zh, ag); ab += da; abias += dz;
+      a.out[net][(int64_t)r * W + c] = dz;
+    } else if (a.out[net]) {
+      a.out[net][(int64_t)r * W + c] = dx;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2; k++)
+    if (k < nsrc)
+#pragma unroll
+      for (int tp = 0; tp < 9; tp++) a.pdw[net][k][((int64_t)tile * W + c) * 9 + tp] = aw[k][tp];
+  if (Z) {
+    a.pgamma[net][(int64_t)tile * W + c] = ag; a.pbeta[net][(int64_t)tile * W + c] = ab; a.pbias[net][(int64_t)tile * W + c] = abias;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct HGReduceArgs {
+  HGGeom g;
+  int bn_lstride;
+  const float* pw[HG_SLOTS]; float* dW[HG_SLOTS]; int Cout[HG_SLOTS], I[HG_SLOTS];        // [slab][I][W] -> [Cout][W]
+  const float* pdw[HG_SLOTS]; float* ddw[HG_SLOTS];                                       // [tile][W * 9] -> [W * 9]
+  const float* pbias[HG_SLOTS]; float* dbias[HG_SLOTS]; int ldb[HG_SLOTS];                // [tile][ldb] -> [Cout]
+  const float* pgamma[HG_SLOTS]; const float* pbeta[HG_SLOTS]; float* dbn[HG_SLOTS];      // [tile][W] -> per level gamma, beta, 0, 0 (NULL: none)
+};
+
+// second pass: every gradient element is the sum of its partials, added in double in a FIXED order: 16 threads share an
+// element, thread j adds the partials j, j + 16, ... in index order, then thread 0 adds the 16 sums in order 0..15 and
+// rounds once.  A workgroup = 16 consecutive elements x 16 such threads (64-byte reads of a partial row).
+// blockIdx.y = slot, blockIdx.z = kind (0 pointwise weight, 1 depthwise weight, 2 bias, 3 BatchNorm of the five levels)
+#define HG_RED_E 16
+#define HG_RED_K 16
+static_assert(HG_RED_E * HG_RED_K == HG_THREADS, "one reduce workgroup = 16 elements x 16 partial lanes");
+__global__ __launch_bounds__(HG_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
+  __shared__ double part[HG_RED_K][HG_RED_E + 1];
+  const HGGeom& g = a.g;
+  const int slot = blockIdx.y, kind = blockIdx.z, W = g.W, el = threadIdx.x % HG_RED_E, kl = threadIdx.x / HG_RED_E;
+  const int64_t e = (int64_t)blockIdx.x * HG_RED_E + el;
+  const float* __restrict__ src = nullptr;      // partial k of this element: src[k * stride]
+  float* dst = nullptr;
+  int64_t stride = 0;
+  int k0 = 0, k1 = 0;
+  if (kind == 0) {
+    if (a.dW[slot] && e < (int64_t)a.Cout[slot] * W) { src = a.pw[slot] + e; stride = (int64_t)a.I[slot] * W; k1 = g.nslab; dst = a.dW[slot] + e; }
+  } else if (kind == 1) {
+    if (a.ddw[slot] && e < (int64_t)W * 9) { src = a.pdw[slot] + e; stride = (int64_t)W * 9; k1 = g.ntiles; dst = a.ddw[slot] + e; }
+  } else if (kind == 2) {
+    if (a.dbias[slot] && e < a.Cout[slot]) { src = a.pbias[slot] + e; stride = a.ldb[slot]; k1 = g.ntiles; dst = a.dbias[slot] + e; }
+  } else if (a.dbn[slot] && e < (int64_t)5 * 4 * W) {
+    const int l = (int)(e / (4 * W)), which = (int)(e / W) % 4, c = (int)(e % W);
+    dst = a.dbn[slot] + (int64_t)l * a.bn_lstride + which * W + c;
+    if (which < 2) { src = (which == 0 ? a.pgamma[slot] : a.pbeta[slot]) + c; stride = W; k0 = g.tileoff[l]; k1 = g.tileoff[l + 1]; }
+  }
+  double s = 0.0;
+  if (src)
+    for (int k = k0 + kl; k < k1; k += HG_RED_K) s += (double)src[k * stride];
+  part[kl][el] = s;
+  __syncthreads();
+  if (kl == 0 && dst) {
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < HG_RED_K; j++) t += part[j][el];
+    *dst = (float)t;                              // (running statistics: no partials, zero)
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host side
+int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why) {
+  if (phi < 0 || phi > 7) { *why = "heads: phi must be in 0..7 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
+  if (num_classes < 1 || num_classes > 63) { *why = "heads: num_classes must be in 1..63"; return HEP_ERR_UNSUPPORTED; }
+  HGGeom& g = p->g;
+  g.W = kFpnWidth[phi]; g.D = kHeadDepth[phi];
+  p->num_classes = num_classes;
+  const int W = g.W, D = g.D;
+  const int vals[HG_SLOTS] = {4, num_classes, 3, 2, 1, 63};
+  const int nets[HG_SLOTS] = {0, 1, 2, 3, 3, 4}, Ks[HG_SLOTS] = {4, num_classes, 3, 3, 3, 63}, offs[HG_SLOTS] = {0, 0, 0, 0, 2, 0};
+  for (int h = 0; h < HG_SLOTS; h++) {
+    p->C[h] = 9 * vals[h]; p->ld[h] = (p->C[h] + 3) / 4 * 4; p->net[h] = nets[h]; p->K[h] = Ks[h]; p->kh[h] = vals[h]; p->koff[h] = offs[h];
+  }
+  // flat parameters: the reference's state_dict order restricted to the heads (regressor, classifier, rotation_net,
+  // translation_net, hand_net), num_batches_tracked left out
+  int64_t o = 0;
+  for (int n = 0; n < HG_NETS; n++) {
+    p->p_conv[n] = o; o += (int64_t)D * (9 * W + W * W + W);
+    p->p_bn[n] = o; o += (int64_t)5 * D * 4 * W;
+    for (int h = 0; h < HG_SLOTS; h++)
+      if (nets[h] == n) { p->p_hdr[h] = o; o += 9 * W + (int64_t)p->C[h] * W + p->C[h]; }
+  }
+  p->nparams = o;
+  if (size == 0 && batch == 0) return 0;                   // layout only
+  if (size < 128 || size > 2048 || size % 128 != 0) { *why = "heads: size must be a multiple of 128 in [128, 2048]"; return HEP_ERR_UNSUPPORTED; }
+  if (batch < 1) { *why = "heads: batch must be at least 1"; return HEP_ERR_UNSUPPORTED; }
+  g.B = batch;
+  int S = 0, tiles = 0;
+  for (int l = 0; l < 5; l++) {
+    g.s[l] = (size + (8 << l) - 1) / (8 << l);
+    g.pixoff[l] = S; S += g.s[l] * g.s[l];
+  }
+  g.pixoff[5] = S; g.S = S;
+  if ((int64_t)batch * S > (1 << 22)) { *why = "heads: batch * pixels exceeds 4 Mi rows"; return HEP_ERR_UNSUPPORTED; }
+  g.R = batch * S;
+  for (int l = 0; l < 6; l++) g.rowoff[l] = batch * g.pixoff[l];
+  for (int l = 0; l < 5; l++) { g.tileoff[l] = tiles; tiles += (batch * g.s[l] * g.s[l] + HG_TILE_ROWS - 1) / HG_TILE_ROWS; }
+  g.tileoff[5] = tiles; g.ntiles = tiles;
+  g.nslab = g.R / 512; if (g.nslab < 1) g.nslab = 1; if (g.nslab > HG_MAX_SLABS) g.nslab = HG_MAX_SLABS;
+  g.slab_rows = ((g.R + g.nslab - 1) / g.nslab + HG_BK - 1) / HG_BK * HG_BK;
+  g.nslab = (g.R + g.slab_rows - 1) / g.slab_rows;
+  const int64_t RW = (int64_t)g.R * W;
+  int64_t w = 0;
+  auto take = [&](int64_t n) { const int64_t at = w; w += (n + 3) / 4 * 4; return at; };
+  p->o_x0 = take(RW); p->o_x = take(D * HG_NETS * RW); p->o_u = take(D * HG_NETS * RW); p->o_z = take(D * HG_NETS * RW);
+  p->o_uh = take(HG_SLOTS * RW); p->o_cl = take((int64_t)g.R * p->ld[1]);
+  for (int h = 0; h < HG_SLOTS; h++) p->o_do[h] = take((int64_t)g.R * p->ld[h]);
+  p->o_g1 = take(HG_SLOTS * RW); p->o_g2 = take(HG_NETS * RW);
+  for (int h = 0; h < HG_SLOTS; h++) p->o_pw[h] = take((int64_t)g.nslab * (p->ld[h] > W ? p->ld[h] : W) * W);
+  for (int h = 0; h < HG_SLOTS; h++) p->o_pdw[h] = take((int64_t)tiles * W * 9);
+  for (int h = 0; h < HG_SLOTS; h++) p->o_pbh[h] = take((int64_t)tiles * p->ld[h]);
+  for (int k = 0; k < 2; k++) { p->o_pg[k] = take((int64_t)HG_NETS * tiles * W); p->o_pb[k] = take((int64_t)HG_NETS * tiles * W); p->o_pbi[k] = take((int64_t)HG_NETS * tiles * W); }
+  p->ws_floats = w;
+  return 0;
+}
+
+static inline unsigned hg_blocks(int64_t n) { return (unsigned)((n + HG_THREADS - 1) / HG_THREADS); }
+static inline int64_t hg_conv_stride(const HGGeom& g) { return (int64_t)9 * g.W + (int64_t)g.W * g.W + g.W; }
+
+void launch_heads_forward(const HGPlan& p, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t st) {
+  const HGGeom& g = p.g;
+  const int W = g.W, D = g.D;
+  const int64_t RW = (int64_t)g.R * W;
+  HGPtr5 f{};
+  for (int l = 0; l < 5; l++) f.in[l] = feats[l];
+  hipLaunchKernelGGL(hg_rows_from_nchw_kernel, dim3(hg_blocks(RW)), dim3(HG_THREADS), 0, st, g, f, ws + p.o_x0);
+  const int mt = (g.R + HG_BM - 1) / HG_BM;
+  const int64_t dw_threads = (int64_t)((g.R + HG_DW_ROWS - 1) / HG_DW_ROWS) * W;
+  for (int i = 0; i < D; i++) {
+    HGDwArgs d{}; d.g = g;
+    HGGemmArgs m{}; m.g = g; m.ntmax = (W + HG_BN - 1) / HG_BN; m.bn_lstride = D * 4 * W;
+    for (int n = 0; n < HG_NETS; n++) {
+      const float* conv = params + p.p_conv[n] + i * hg_conv_stride(g);
+      d.src[n] = i == 0 ? ws + p.o_x0 : ws + p.o_x + ((int64_t)(i - 1) * HG_NETS + n) * RW;
+      d.w[n] = conv;
+      d.dst[n] = ws + p.o_u + ((int64_t)i * HG_NETS + n) * RW;
+      m.A[n] = d.dst[n]; m.Bm[n] = conv + 9 * W; m.bias[n] = conv + 9 * W + (int64_t)W * W;
+      m.bn[n] = params + p.p_bn[n] + (int64_t)i * 4 * W;
+      m.C[n] = ws + p.o_z + ((int64_t)i * HG_NETS + n) * RW;
+      m.C2[n] = ws + p.o_x + ((int64_t)i * HG_NETS + n) * RW;
+      m.I[n] = g.R; m.J[n] = W; m.K[n] = W; m.lda[n] = W; m.ldb[n] = W; m.ldc[n] = W;
+    }
+    hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(hg_blocks(dw_threads), HG_NETS), dim3(HG_THREADS), 0, st, d);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_LAYER>, dim3(mt * m.ntmax, HG_NETS), dim3(HG_THREADS), 0, st, m);
+  }
+  HGDwArgs d{}; d.g = g;
+  HGGemmArgs m{}; m.g = g; m.ntmax = 1;
+  for (int h = 0; h < HG_SLOTS; h++) {
+    const float* hdr = params + p.p_hdr[h];
+    d.src[h] = ws + p.o_x + ((int64_t)(D - 1) * HG_NETS + p.net[h]) * RW;
+    d.w[h] = hdr;
+    d.dst[h] = ws + p.o_uh + (int64_t)h * RW;
+    m.A[h] = d.dst[h]; m.Bm[h] = hdr + 9 * W; m.bias[h] = hdr + 9 * W + (int64_t)p.C[h] * W;
+    m.C[h] = h == 1 ? ws + p.o_cl : nullptr; m.C2[h] = outs[p.net[h]];
+    m.I[h] = g.R; m.J[h] = p.C[h]; m.K[h] = W; m.lda[h] = W; m.ldb[h] = W; m.ldc[h] = p.ld[h];
+    m.hK[h] = p.K[h]; m.hkh[h] = p.kh[h]; m.hoff[h] = p.koff[h]; m.sigmoid[h] = h == 1;
+    const int nt = (p.C[h] + HG_BN - 1) / HG_BN;
+    if (nt > m.ntmax) m.ntmax = nt;
+  }
+  hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(hg_blocks(dw_threads), HG_SLOTS), dim3(HG_THREADS), 0, st, d);
+  hipLaunchKernelGGL(hg_gemm_kernel<HG_HEADER>, dim3(mt * m.ntmax, HG_SLOTS), dim3(HG_THREADS), 0, st, m);
+}
+
+void launch_heads_backward(const HGPlan& p, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
+                           float* ws, hipStream_t st) {
+  const HGGeom& g = p.g;
+  const int W = g.W, D = g.D, T = g.ntiles;
+  const int64_t RW = (int64_t)g.R * W, TW = (int64_t)T * W;
+  const int mt = (g.R + HG_BM - 1) / HG_BM, bn_lstride = D * 4 * W;
+  const unsigned col_blocks = hg_blocks(TW);
+  // ---- header stage ----
+  {
+    HGGatherArgs ga{}; ga.g = g;
+    HGGemmArgs md{}; md.g = g; md.ntmax = (W + HG_BN - 1) / HG_BN;
+    HGGemmArgs mw{}; mw.g = g; mw.ntmax = md.ntmax;
+    HGDwBwdArgs db{}; db.g = g; db.bn_lstride = bn_lstride;
+    HGReduceArgs rd{}; rd.g = g; rd.bn_lstride = bn_lstride;
+    int ldmax = 0, itmax = 1;
+    int64_t emax = (int64_t)W * 9;
+    for (int h = 0; h < HG_SLOTS; h++) {
+      const float* hdr = params + p.p_hdr[h];
+      float* ghdr = grad_params + p.p_hdr[h];
+      const int n = p.net[h];
+      ga.gout[h] = grad_outs[n]; ga.logits[h] = h == 1 ? ws + p.o_cl : nullptr;
+      ga.dz[h] = ws + p.o_do[h]; ga.pbias[h] = ws + p.o_pbh[h];
+      ga.C[h] = p.C[h]; ga.ld[h] = p.ld[h]; ga.hK[h] = p.K[h]; ga.hkh[h] = p.kh[h]; ga.hoff[h] = p.koff[h];
+      if (p.ld[h] > ldmax) ldmax = p.ld[h];
+      md.A[h] = ga.dz[h]; md.Bm[h] = hdr + 9 * W; md.C[h] = ws + p.o_g1 + (int64_t)h * RW;
+      md.I[h] = g.R; md.J[h] = W; md.K[h] = p.ld[h]; md.Kb[h] = p.C[h]; md.lda[h] = p.ld[h]; md.ldb[h] = W; md.ldc[h] = W;
+      mw.A[h] = ga.dz[h]; mw.Bm[h] = ws + p.o_uh + (int64_t)h * RW; mw.C[h] = ws + p.o_pw[h];
+      mw.I[h] = p.ld[h]; mw.J[h] = W; mw.lda[h] = p.ld[h]; mw.ldb[h] = W;
+      const int it = (p.ld[h] + HG_BM - 1) / HG_BM;
+      if (it > itmax) itmax = it;
+      const int k = db.nsrc[n]++;
+      db.G[n][k] = md.C[h]; db.w[n][k] = hdr; db.pdw[n][k] = ws + p.o_pdw[h];
+      rd.pw[h] = mw.C[h]; rd.dW[h] = ghdr + 9 * W; rd.Cout[h] = p.C[h]; rd.I[h] = p.ld[h];
+      rd.pdw[h] = ws + p.o_pdw[h]; rd.ddw[h] = ghdr;
+      rd.pbias[h] = ga.pbias[h]; rd.dbias[h] = ghdr + 9 * W + (int64_t)p.C[h] * W; rd.ldb[h] = p.ld[h];
+      if ((int64_t)p.C[h] * W > emax) emax = (int64_t)p.C[h] * W;
+    }
+    for (int n = 0; n < HG_NETS; n++) {
+      db.X[n] = ws + p.o_x + ((int64_t)(D - 1) * HG_NETS + n) * RW;
+      db.Zprev[n] = ws + p.o_z + ((int64_t)(D - 1) * HG_NETS + n) * RW;
+      db.bnprev[n] = params + p.p_bn[n] + (int64_t)(D - 1) * 4 * W;
+      db.out[n] = ws + p.o_g2 + (int64_t)n * RW;
+      const int par = (D - 1) & 1;
+      db.pgamma[n] = ws + p.o_pg[par] + n * TW; db.pbeta[n] = ws + p.o_pb[par] + n * TW; db.pbias[n] = ws + p.o_pbi[par] + n * TW;
+    }
+    hipLaunchKernelGGL(hg_hdr_gather_kernel, dim3(hg_blocks((int64_t)T * ldmax), HG_SLOTS), dim3(HG_THREADS), 0, st, ga);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_SLOTS), dim3(HG_THREADS), 0, st, md);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(itmax * mw.ntmax, HG_SLOTS, g.nslab), dim3(HG_THREADS), 0, st, mw);
+    hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(HG_THREADS), 0, st, db);
+    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)((emax + HG_RED_E - 1) / HG_RED_E), HG_SLOTS, 3), dim3(HG_THREADS), 0, st, rd);
+  }
+  // ---- the layers, top down ----
+  for (int i = D - 1; i >= 0; i--) {
+    HGGemmArgs md{}; md.g = g; md.ntmax = (W + HG_BN - 1) / HG_BN;
+    HGGemmArgs mw{}; mw.g = g; mw.ntmax = md.ntmax;
+    HGDwBwdArgs db{}; db.g = g; db.bn_lstride = bn_lstride;
+    HGReduceArgs rd{}; rd.g = g; rd.bn_lstride = bn_lstride;
+    for (int n = 0; n < HG_NETS; n++) {
+      const float* conv = params + p.p_conv[n] + i * hg_conv_stride(g);
+      float* gconv = grad_params + p.p_conv[n] + i * hg_conv_stride(g);
+      const float* dz = ws + p.o_g2 + (int64_t)n * RW;
+      md.A[n] = dz; md.Bm[n] = conv + 9 * W; md.C[n] = ws + p.o_g1 + (int64_t)n * RW;
+      md.I[n] = g.R; md.J[n] = W; md.K[n] = W; md.Kb[n] = W; md.lda[n] = W; md.ldb[n] = W; md.ldc[n] = W;
+      mw.A[n] = dz; mw.Bm[n] = ws + p.o_u + ((int64_t)i * HG_NETS + n) * RW; mw.C[n] = ws + p.o_pw[n];
+      mw.I[n] = W; mw.J[n] = W; mw.lda[n] = W; mw.ldb[n] = W;
+      db.nsrc[n] = 1; db.G[n][0] = md.C[n]; db.w[n][0] = conv; db.pdw[n][0] = ws + p.o_pdw[n];
+      db.X[n] = i == 0 ? ws + p.o_x0 : ws + p.o_x + ((int64_t)(i - 1) * HG_NETS + n) * RW;
+      const int par = i & 1, below = (i - 1) & 1;
+      if (i > 0) {
+        db.Zprev[n] = ws + p.o_z + ((int64_t)(i - 1) * HG_NETS + n) * RW;
+        db.bnprev[n] = params + p.p_bn[n] + (int64_t)(i - 1) * 4 * W;
+        db.out[n] = ws + p.o_g2 + (int64_t)n * RW;
+        db.pgamma[n] = ws + p.o_pg[below] + n * TW; db.pbeta[n] = ws + p.o_pb[below] + n * TW; db.pbias[n] = ws + p.o_pbi[below] + n * TW;
+      } else {
+        db.out[n] = grad_feats ? ws + p.o_g2 + (int64_t)n * RW : nullptr;
+      }
+      rd.pw[n] = mw.C[n]; rd.dW[n] = gconv + 9 * W; rd.Cout[n] = W; rd.I[n] = W;
+      rd.pdw[n] = ws + p.o_pdw[n]; rd.ddw[n] = gconv;
+      rd.pbias[n] = ws + p.o_pbi[par] + n * TW; rd.dbias[n] = gconv + 9 * W + (int64_t)W * W; rd.ldb[n] = W;
+      rd.pgamma[n] = ws + p.o_pg[par] + n * TW; rd.pbeta[n] = ws + p.o_pb[par] + n * TW;
+      rd.dbn[n] = grad_params + p.p_bn[n] + (int64_t)i * 4 * W;
+    }
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_NETS), dim3(HG_THREADS), 0, st, md);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(md.ntmax * mw.ntmax, HG_NETS, g.nslab), dim3(HG_THREADS), 0, st, mw);
+    hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(HG_THREADS), 0, st, db);
+    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)W * W + HG_RED_E - 1) / HG_RED_E), HG_NETS, 4), dim3(HG_THREADS), 0, st, rd);
+  }
+  if (grad_feats) {
+    HGPtr5 f{};
+    for (int l = 0; l < 5; l++) f.out[l] = grad_feats[l];
+    hipLaunchKernelGGL(hg_feats_grad_kernel, dim3(hg_blocks(RW)), dim3(HG_THREADS), 0, st, g, f, ws + p.o_g2);
+  }
+}

@@ -1,0 +1,186 @@
+"""Trainable pose heads: the five head nets (regressor, classifier, rotation_net, translation_net, hand_net) with a HIP
+forward AND backward (csrc/k_head_grad.hip: hep_heads_forward_device / hep_heads_backward_device).
+
+The heads are what the reference added to EfficientDet and what one re-fits when the tracked instrument changes.  With
+them trainable the whole fitting loop stays on the GPU: run the inference path once over a dataset and keep the five
+BiFPN maps (``feats``, the first value ``HMDEgoPose.forward`` returns), then per step
+
+    HIP targets (training.anchor_targets) -> HIP heads forward (TrainableHeads) -> training.format_translation ->
+    HIP losses (training.losses) -> HIP loss backward -> HIP heads backward -> a stock torch.optim step
+
+and finally ``export_to(model)`` copies the fitted heads back into the ``HMDEgoPose`` drop-in.
+
+BatchNorm: RUNNING statistics in every mode (``train()`` and ``eval()`` compute the same function), in forward and
+backward - frozen-statistics fine-tuning, the reference's ``freeze_bn`` (backbone.py:99).  That is the gradient of the
+function the inference path computes, so "train here, serve here" is consistent: ``gamma`` and ``beta`` get gradients,
+``running_mean`` / ``running_var`` never change.  Batch-statistics BatchNorm (``model.train()`` in the reference's
+train.py:162) is out of scope, and so are the backward through BiFPN / backbone and bf16 training.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import List, Sequence, Tuple
+
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+
+from . import _capi
+from .arch import HEAD_NAMES, NUM_ANCHORS, get_arch, level_sizes, param_spec
+
+
+def head_spec(compound_coef: int, num_classes: int = 1) -> List[Tuple[str, tuple]]:
+    """The head subset of ``param_spec`` (key, shape), in the reference's state_dict order."""
+    return [(k, s) for k, s in param_spec(compound_coef, num_classes) if k.split(".", 1)[0] in HEAD_NAMES]
+
+
+def flat_keys(compound_coef: int, num_classes: int = 1) -> List[Tuple[str, tuple]]:
+    """The tensors of the flat fp32 parameter buffer of hep_heads_*_device, in buffer order: ``head_spec`` without the
+    int64 ``num_batches_tracked`` counters."""
+    return [(k, s) for k, s in head_spec(compound_coef, num_classes) if not k.endswith("num_batches_tracked")]
+
+
+def _numel(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def _ptrs(tensors):
+    return None if tensors is None else _capi.ptr_array(list(tensors))
+
+
+def heads_forward(flat: torch.Tensor, feats: Sequence[torch.Tensor], compound_coef: int, num_classes: int, size: int):
+    """hep_heads_forward_device on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order),
+    ``feats``: five contiguous float32 NCHW maps.  Returns (outs, workspace): the five [B, N, K] outputs and the workspace
+    that hep_heads_backward_device needs.  No host synchronisation."""
+    dev, B = flat.device, int(feats[0].shape[0])
+    N = NUM_ANCHORS * sum(s * s for s in level_sizes(size))
+    l = _capi.lib()
+    nbytes = _capi.check(l.hep_heads_workspace_bytes(compound_coef, num_classes, size, B))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    outs = tuple(torch.empty((B, N, k), dtype=torch.float32, device=dev) for k in (4, num_classes, 3, 3, 63))
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(l.hep_heads_forward_device(flat.data_ptr(), _ptrs(feats), compound_coef, num_classes, size, B, _ptrs(outs),
+                                           ws.data_ptr(), nbytes, stream))
+    return outs, ws
+
+
+def heads_backward(flat: torch.Tensor, grad_outs: Sequence[torch.Tensor], ws: torch.Tensor, compound_coef: int, num_classes: int,
+                   size: int, feat_shapes=None):
+    """hep_heads_backward_device on the current stream, after ``heads_forward`` with the same ``flat`` and ``ws``.
+    Returns (grad_flat, grad_feats): the parameter gradients in the layout of ``flat`` (running statistics zero) and the
+    five map gradients (None when ``feat_shapes`` is None: the ABI then gets NULL and skips them)."""
+    dev, B = flat.device, int(grad_outs[0].shape[0])
+    g_flat = torch.empty_like(flat)
+    g_feats = None if feat_shapes is None else tuple(torch.empty(tuple(s), dtype=torch.float32, device=dev) for s in feat_shapes)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _capi.check(_capi.lib().hep_heads_backward_device(flat.data_ptr(), _ptrs(grad_outs), compound_coef, num_classes, size, B,
+                                                      g_flat.data_ptr(), _ptrs(g_feats), ws.data_ptr(), ws.numel(), stream))
+    return g_flat, g_feats
+
+
+class _Heads(torch.autograd.Function):
+    """The two ABI calls as one differentiable function of (flat parameters, five maps)."""
+
+    @staticmethod
+    def forward(ctx, flat, phi, num_classes, size, *feats):
+        outs, ws = heads_forward(flat, feats, phi, num_classes, size)
+        ctx.save_for_backward(flat, ws)
+        ctx.cfg = (phi, num_classes, size, [tuple(f.shape) for f in feats])
+        return outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grad_outs):
+        flat, ws = ctx.saved_tensors
+        phi, num_classes, size, shapes = ctx.cfg
+        N = NUM_ANCHORS * sum(s * s for s in level_sizes(size))
+        B = shapes[0][0]
+        gs = [torch.zeros((B, N, k), dtype=torch.float32, device=flat.device) if g is None else g.to(torch.float32).contiguous()
+              for g, k in zip(grad_outs, (4, num_classes, 3, 3, 63))]
+        want_feats = any(ctx.needs_input_grad[4:])
+        g_flat, g_feats = heads_backward(flat, gs, ws, phi, num_classes, size, shapes if want_feats else None)
+        return (g_flat if ctx.needs_input_grad[0] else None, None, None, None, *(g_feats if want_feats else (None,) * 5))
+
+
+class TrainableHeads(nn.Module):
+    """The five head nets as an ``nn.Module`` whose parameters and buffers carry exactly the reference's head keys
+    (``regressor.conv_list.0.depthwise_conv.conv.weight`` ... ``hand_net.bn_list.4.2.running_var``), so that
+    ``load_state_dict(model.state_dict(), strict=False)`` fills it.  ``forward(feats)`` takes the 5-tuple of BiFPN maps
+    that ``HMDEgoPose.forward`` returns first and gives (regression, classification, rotation, translation_raw, hand) with
+    a ``grad_fn``: HIP forward and HIP backward, gradients to the parameters and, where they require grad, to the maps.
+    Runs on a ROCm device only (no CPU fallback).  BatchNorm uses the running statistics in EVERY mode, ``train()``
+    included (see the module docstring); they receive no gradient and never change."""
+
+    def __init__(self, compound_coef: int = 0, num_classes: int = 1):
+        super().__init__()
+        from .model import _attach
+        self.compound_coef = int(compound_coef)
+        self.num_classes = int(num_classes)
+        self.arch = get_arch(self.compound_coef)
+        for key, shape in head_spec(self.compound_coef, self.num_classes):
+            _attach(self, key, shape)
+        self._flat_keys = [k for k, _ in flat_keys(self.compound_coef, self.num_classes)]
+
+    @classmethod
+    def from_model(cls, model) -> "TrainableHeads":
+        """Heads with the tensors of an ``HMDEgoPose`` (or any module with the reference's keys), on the model's device."""
+        h = cls(model.compound_coef, model.num_classes)
+        sd = model.state_dict()
+        missing = [k for k, _ in head_spec(h.compound_coef, h.num_classes) if k not in sd]
+        if missing:
+            raise KeyError(f"the model's state_dict lacks head tensors, e.g. {missing[0]}")
+        h.load_state_dict(sd, strict=False)
+        return h.to(next(iter(sd.values())).device)
+
+    def export_to(self, model):
+        """Copy every head tensor into ``model`` (an ``HMDEgoPose``) and drop its packed device weights."""
+        own, dst = self.state_dict(), model.state_dict()
+        with torch.no_grad():
+            for k, v in own.items():
+                dst[k].copy_(v)
+        model.invalidate()
+        return model
+
+    def flat_parameters(self) -> torch.Tensor:
+        """The flat fp32 buffer of hep_heads_*_device (autograd-tracked: its gradient splits back onto the parameters)."""
+        tensors = dict(self.named_parameters())
+        tensors.update(dict(self.named_buffers()))
+        return torch.cat([tensors[k].reshape(-1) for k in self._flat_keys])
+
+    def _check_feats(self, feats):
+        if len(feats) != 5:
+            raise ValueError("feats must be the five BiFPN maps P3..P7")
+        f0 = feats[0]
+        if f0.dim() != 4:
+            raise ValueError("feats[0] must be [B, W, s, s]")
+        B, W, side = int(f0.shape[0]), self.arch.fpn_w, int(f0.shape[2])
+        size = side * 8
+        if size < 128 or size % 128 != 0:
+            raise ValueError(f"feats[0] has side {side}: the input size must be a multiple of 128 (side a multiple of 16)")
+        for l, (f, s) in enumerate(zip(feats, level_sizes(size))):
+            if tuple(f.shape) != (B, W, s, s):
+                raise ValueError(f"feats[{l}] has shape {tuple(f.shape)}, expected {(B, W, s, s)} (phi {self.compound_coef}, size {size})")
+            if not f.is_cuda or f.dtype != torch.float32:
+                raise ValueError(f"feats[{l}] must be a float32 ROCm tensor")
+        return size
+
+    def forward(self, feats):
+        feats = tuple(feats)
+        size = self._check_feats(feats)
+        flat = self.flat_parameters()
+        if flat.device != feats[0].device:
+            raise ValueError("the heads and the maps live on different devices: move the module with .to(device)")
+        return _Heads.apply(flat, self.compound_coef, self.num_classes, size, *(f.contiguous() for f in feats))
+
+
+def param_layout(compound_coef: int, num_classes: int = 1):
+    """(total floats, [offset of every ``flat_keys`` tensor]) as the library reports them."""
+    l = _capi.lib()
+    total = _capi.check(l.hep_heads_param_count(compound_coef, num_classes))
+    n = _capi.check(l.hep_heads_param_layout(compound_coef, num_classes, None, 0))
+    arr = (ctypes.c_int64 * n)()
+    _capi.check(l.hep_heads_param_layout(compound_coef, num_classes, arr, n))
+    return int(total), [int(v) for v in arr]

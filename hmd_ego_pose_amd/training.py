@@ -10,7 +10,9 @@ distance), translation and hand losses, one workgroup per image (hep_losses_devi
 Python loop over the batch and per-image gathers.  When a prediction requires grad the outputs carry a ``grad_fn`` whose
 backward is HIP as well (csrc/k_loss_grad.hip, hep_losses_backward_device): the gradients the reference's autograd returns,
 computed on the whole GPU without a host synchronisation.  ``batch_iterate`` is the drop-in with the reference's signature
-and return shape.  Backward through the HIP network forward stays out of scope (the inference path has no backward).
+and return shape.  The five head nets under these losses are trainable as well (``heads.TrainableHeads``: HIP forward and
+backward, csrc/k_head_grad.hip); ``format_translation`` is the differentiable step between them (the losses take the DECODED
+translation, train.py:39,49).  Backward through BiFPN and the backbone stays out of scope (the inference path has no backward).
 """
 from __future__ import annotations
 
@@ -59,6 +61,44 @@ def anchor_targets(anchors: torch.Tensor, boxes: Sequence[np.ndarray], labels: S
                                                       float(positive_overlap), lab.data_ptr(), reg.data_ptr(), tra.data_ptr(), _capi.ptr(crd), stream))
     torch.cuda.current_stream(dev).synchronize()      # the staging tensors above must outlive the launch
     return lab, reg, tra, crd
+
+
+_T_ANCHORS = {}
+
+
+def translation_anchors(size: int) -> torch.Tensor:
+    """The translation anchors [N, 3] = (cx, cy, stride) of a square input (hep_anchors, host code), float32 on the CPU."""
+    size = int(size)
+    if size not in _T_ANCHORS:
+        l = _capi.lib()
+        n = _capi.check(l.hep_anchors(size, None, None))
+        a = np.empty((n, 4), np.float32); t = np.empty((n, 3), np.float32)
+        _capi.check(l.hep_anchors(size, a.ctypes.data, t.ctypes.data))
+        _T_ANCHORS[size] = torch.from_numpy(t)
+    return _T_ANCHORS[size]
+
+
+def format_translation(translation_raw: torch.Tensor, camera: torch.Tensor, size: int) -> torch.Tensor:
+    """``format_translation`` (hmdegopose/loss.py:30-51: RegressTranslation layers.py:142-166, CalculateTxTy :203-249) as
+    plain differentiable torch ops: the translation half of ``torch.ops.hep.decode`` with a ``grad_fn``.
+    translation_raw [B, N, 3] (any device and float dtype), camera [B, 6] = fx, fy, px, py, tz_scale, image_scale, ``size``
+    the square input side the anchors are built for.  Returns (tx, ty, tz) [B, N, 3].  Elementwise, not a hot path."""
+    if translation_raw.dim() != 3 or translation_raw.shape[2] != 3:
+        raise ValueError("translation_raw must be [B, N, 3]")
+    ta = translation_anchors(size).to(device=translation_raw.device, dtype=translation_raw.dtype)
+    if ta.shape[0] != translation_raw.shape[1]:
+        raise ValueError(f"translation_raw has {translation_raw.shape[1]} anchors, size {size} has {ta.shape[0]}")
+    cam = camera.to(device=translation_raw.device, dtype=translation_raw.dtype)
+    if cam.shape != (translation_raw.shape[0], 6):
+        raise ValueError("camera must be [B, 6]")
+    stride = ta[None, :, 2]
+    x = ta[None, :, 0] + translation_raw[..., 0] * stride
+    y = ta[None, :, 1] + translation_raw[..., 1] * stride
+    fx, fy, px, py, tzs, isc = (cam[:, i:i + 1] for i in range(6))
+    x = x / isc - px
+    y = y / isc - py
+    tz = translation_raw[..., 2] * tzs
+    return torch.stack((x * tz / fx, y * tz / fy, tz), dim=-1)
 
 
 _PRED_NAMES = ("classification", "regression", "transformation", "hand")

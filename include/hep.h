@@ -24,6 +24,7 @@
  *   hep_anchor_targets_device  <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
+ *   hep_heads_forward_device / hep_heads_backward_device <- the five head nets under those losses, trainable
  *   hep_pose_errors / _device  <- check_6d_pose_add / check_6d_pose_add_s, pytorch-sandbox/eval/common.py:682-746 with
  *                                 c_min_distances, pytorch-sandbox/generators/utils/calc_min_distances.h:24-35 (the
  *                                 metric arithmetic of evaluate.py's loop, eval/common.py:866-1121)
@@ -226,6 +227,34 @@ int hep_losses_backward_device(const float* gt_classification, const float* clas
                                const float* model_points, int batch, int num_anchors, int num_classes, int num_rotation, int num_hand,
                                int num_model_classes, int num_points, const float* grad_per_image, float* grad_classification,
                                float* grad_regression, float* grad_transformation, float* grad_hand, int32_t* workspace, void* stream);
+
+/* The five head nets (regressor, classifier, rotation_net, translation_net, hand_net) as a TRAINABLE function of the five
+ * BiFPN maps: forward and backward in HIP (csrc/k_head_grad.hip), so that the heads can be fitted on the device behind
+ * hep_losses_device / hep_losses_backward_device.  Stateless: plain pointers and sizes, asynchronous on `stream`, no
+ * allocation, no host synchronisation, argument checks before any HIP call, bit-reproducible (no float atomics).
+ * BatchNorm uses its RUNNING statistics in forward and backward (the function the inference path computes; the
+ * reference's freeze_bn): gamma and beta get gradients, the statistics never change.  Batch-statistics BatchNorm is out
+ * of scope.
+ *
+ * params: ONE flat fp32 device buffer (16-byte aligned) holding the head tensors in the reference's shapes and
+ * state_dict order (regressor, classifier, rotation_net, translation_net, hand_net; per net conv_list.{i}.{depthwise
+ * [W,1,3,3], pointwise [W,W,1,1], bias [W]}, bn_list.{level}.{i}.{weight, bias, running_mean, running_var},
+ * then the header conv(s)); num_batches_tracked is not part of it.  hep_heads_param_count returns its length in
+ * floats; hep_heads_param_layout writes the offset of every tensor in that order (offsets == NULL: returns how many).
+ * feats[l]: the five maps, fp32 NCHW [batch][W][s_l][s_l] as hep_run_device exports them.  outs[k]: [batch][N][K_k] in
+ * the inference layout (regression, classification post-sigmoid, rotation, translation raw, hand).
+ * workspace: hep_heads_workspace_bytes bytes on the device, 16-byte aligned, owned by the caller.  The forward leaves
+ * in it what the backward needs: hand the SAME workspace (untouched) and the same params to hep_heads_backward_device.
+ * grad_outs[k]: cotangents [batch][N][K_k].  grad_params: same layout as params, every element written (running
+ * statistics: zero).  grad_feats: five NCHW buffers, or NULL to skip the map gradients.
+ * Supported: phi 0..7, num_classes 1..63, size a multiple of 128 in [128, 2048], batch >= 1 (HEP_ERR_UNSUPPORTED otherwise). */
+int64_t hep_heads_param_count(int phi, int num_classes);
+int hep_heads_param_layout(int phi, int num_classes, int64_t* offsets, int capacity);
+int64_t hep_heads_workspace_bytes(int phi, int num_classes, int size, int batch);
+int hep_heads_forward_device(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
+                             float* const outs[5], void* workspace, size_t workspace_bytes, void* stream);
+int hep_heads_backward_device(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
+                              float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream);
 
 /* preprocess_image (reference generators/colibri_common.py:622-656): device uint8 RGB [batch, height, width, 3] ->
  * device float32 [batch, size, size, 3]: resize by scale = size / max(height, width) (8-bit bilinear, OpenCV

@@ -1,0 +1,307 @@
+"""GPU (MI355X): the trainable pose heads - hep_heads_forward_device / hep_heads_backward_device (csrc/k_head_grad.hip)
+behind hmd_ego_pose_amd.heads.TrainableHeads.
+
+Forward: against the fp32 inference session on the session's OWN maps, FP32_HEAD_TOL (5e-4, tests/test_gpu_parity.py).
+Backward: every parameter gradient and every map gradient against the oracle's float64 autograd on the same inputs, per
+tensor e = max |g_hip - g_64| / max |g_64|.  The bound is measured, not fixed: the test runs the same oracle autograd in
+float32 on the CPU (torch, one thread), takes ITS worst e over the tensors of the case, and allows the device 4 x that, floor
+2e-6 (both are float32 evaluations of the same sums in different orders; the device adds split-K slabs and its own exp).
+
+Measured on MI355X (worst e over all 218 / 283 gradient tensors: device | float32 torch on the CPU | bound):
+  phi0_s256_b2     1.3e-6 | 1.6e-6 | 6.5e-6        phi0_s384_b1   1.4e-6 | 1.7e-6 | 6.9e-6
+  phi0_s128_b2_k3  1.6e-6 | 1.4e-6 | 5.7e-6        phi3_s128_b1   2.0e-6 | 2.1e-6 | 8.4e-6
+(NOTEBOOK.md section 12); the tests print the values they reach.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from hmd_ego_pose_amd import seeded_state_dict
+from tests import _head_grad as H
+from tests._loss_grad import TRAIN_WEIGHTS
+from tests._util import CAMS, seeded_input
+from tests.test_head_grads_cpu import check_against_golden
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+FP32_HEAD_TOL = 5e-4            # the project's bound for fp32 heads on the device's own inputs (tests/test_gpu_parity.py)
+BOUND_FACTOR, BOUND_FLOOR = 4.0, 2e-6
+# tag -> (phi, num_classes, size, batch, seed): the backward cases.  The first is the one the bound's reasoning was measured
+# on; 384 has a 3 x 3 top level, 128 a 1 x 1 one; phi 3 is width 160 (n-tiles that are not full), depth 4.
+BACKWARD_CASES = {
+    "phi0_s256_b2": (0, 1, 256, 2, 0),
+    "phi0_s128_b2_k3": (0, 3, 128, 2, 0),
+    "phi0_s384_b1": (0, 1, 384, 1, 0),
+    "phi3_s128_b1": (3, 1, 128, 1, 0),
+}
+
+
+def _heads(phi, classes, seed):
+    from hmd_ego_pose_amd import TrainableHeads
+    h = TrainableHeads(phi, classes)
+    h.load_state_dict(seeded_state_dict(phi, seed, num_classes=classes), strict=False)
+    return h.cuda()
+
+
+def _inputs(phi, classes, size, batch, seed):
+    return H.seeded_maps(phi, size, batch, seed + 1), H.seeded_cotangents(classes, size, batch, seed + 2)
+
+
+def _device_grads(h, feats, cots, feats_grad=True):
+    """Through autograd: ({key: float32 numpy}, [five map gradients] or None, outs)."""
+    h.zero_grad(set_to_none=True)
+    f = [torch.from_numpy(a).cuda().requires_grad_(feats_grad) for a in feats]
+    outs = h(f)
+    sum((o * torch.from_numpy(c).cuda()).sum() for o, c in zip(outs, cots)).backward()
+    torch.cuda.synchronize()
+    grads = {k: p.grad.cpu().numpy() for k, p in h.named_parameters()}
+    return grads, ([a.grad.cpu().numpy() for a in f] if feats_grad else None), [o.detach() for o in outs]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(phi, classes, size, batch, seed):
+    """(float64 grads, float64 map grads, worst relative error of the float32 CPU evaluation, the bound for the device)."""
+    sd = seeded_state_dict(phi, seed, num_classes=classes)
+    feats, cots = _inputs(phi, classes, size, batch, seed)
+    _o, g64, f64 = H.oracle_grads(sd, feats, cots, phi, classes, torch.float64)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        _o32, g32, f32 = H.oracle_grads(sd, feats, cots, phi, classes, torch.float32)
+    finally:
+        torch.set_num_threads(threads)
+    e32 = max([H.rel_err(g32[k].numpy(), g64[k].numpy()) for k in g64] + [H.rel_err(a.numpy(), b.numpy()) for a, b in zip(f32, f64)])
+    return g64, f64, e32, max(BOUND_FACTOR * e32, BOUND_FLOOR)
+
+
+def _worst(got, gfeats, g64, f64):
+    errs = {k: H.rel_err(got[k], g64[k].numpy()) for k in g64}
+    errs.update({f"feat.{l}": H.rel_err(a, b.numpy()) for l, (a, b) in enumerate(zip(gfeats, f64))})
+    k = max(errs, key=errs.get)
+    return errs, k
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("phi,classes,size,batch", [(0, 1, 256, 2), (0, 1, 256, 16), (0, 1, 128, 2), (0, 1, 384, 2), (3, 1, 512, 1), (0, 3, 256, 2)])
+def test_forward_matches_the_inference_session_on_its_own_maps(phi, classes, size, batch):
+    from hmd_ego_pose_amd import TrainableHeads
+    from hmd_ego_pose_amd.model import HMDEgoPose
+    m = HMDEgoPose({"iter": 0}, num_classes=classes, compound_coef=phi, onnx_export=True, input_sizes=[size] * 9)
+    m.load_state_dict(seeded_state_dict(phi, 0, num_classes=classes), strict=True)
+    m = m.cuda().eval()
+    x = torch.from_numpy(seeded_input((batch, 3, size, size), 0)).cuda()
+    feats, *want = m(x)
+    h = TrainableHeads.from_model(m)
+    assert next(h.parameters()).is_cuda
+    for training_mode in (False, True):                      # running statistics in every mode
+        got = h.train(training_mode)(feats)
+        torch.cuda.synchronize()
+        errs = []
+        for name, g, w in zip(H.OUT_NAMES, got, want):
+            assert g.shape == w.shape and g.grad_fn is not None and torch.isfinite(g).all(), name
+            errs.append((g.detach() - w).abs().max().item() / max(1.0, w.abs().max().item()))
+        print(f"phi {phi} k{classes} @ {size} b{batch}: heads forward against the session, per output {['%.2e' % e for e in errs]}")
+        assert max(errs) <= FP32_HEAD_TOL, errs
+    with torch.no_grad():
+        assert all(torch.equal(a, b.detach()) for a, b in zip(h(feats), got))
+
+
+@pytest.mark.parametrize("tag", list(BACKWARD_CASES))
+def test_backward_matches_float64_autograd_of_the_oracle(tag):
+    phi, classes, size, batch, seed = BACKWARD_CASES[tag]
+    g64, f64, e32, bound = _oracle(phi, classes, size, batch, seed)
+    feats, cots = _inputs(phi, classes, size, batch, seed)
+    h = _heads(phi, classes, seed)
+    got, gfeats, _ = _device_grads(h, feats, cots)
+    assert set(got) == set(g64) and len(got) == sum(1 for k, _ in H.head_keys(phi, classes) if H.trainable(k))
+    errs, k = _worst(got, gfeats, g64, f64)
+    scale = min(float(np.abs(v.numpy()).max()) for v in list(g64.values()) + list(f64))
+    print(f"{tag}: {len(errs)} gradient tensors, device worst {errs[k]:.3e} ({k}); float32 torch on the CPU worst {e32:.3e}; bound {bound:.3e}; "
+          f"smallest tensor scale {scale:.3g}")
+    bad = {n: e for n, e in errs.items() if not e <= bound}
+    assert not bad, (tag, bound, bad)
+
+
+@pytest.mark.parametrize("tag", list(H.GOLDEN_CASES))
+def test_device_gradients_hold_the_reference_golden_slices(tag):
+    """The real reference's autograd (tests/golden/head_grads.npz) against the device, same bound; the scale of each tensor is
+    the largest element of the oracle's float64 gradient."""
+    phi, classes, size, batch, seed = H.GOLDEN_CASES[tag]
+    g64, f64, e32, bound = _oracle(phi, classes, size, batch, seed)
+    z = np.load(os.path.join(HERE, "golden", "head_grads.npz"))
+    names = H.golden_names(phi, classes)
+    feats, cots = _inputs(phi, classes, size, batch, seed)
+    got, gfeats, outs = _device_grads(_heads(phi, classes, seed), feats, cots)
+    worst = 0.0
+    for k, g in got.items():
+        worst = max(worst, check_against_golden(z, tag, names, "param." + k, g, bound, scale=float(np.abs(g64[k].numpy()).max())))
+    for l, g in enumerate(gfeats):
+        worst = max(worst, check_against_golden(z, tag, names, f"feat.{l}", g, bound, scale=float(np.abs(f64[l].numpy()).max())))
+    for n, o in zip(H.OUT_NAMES, outs):
+        check_against_golden(z, tag, names, f"out.{n}", o.cpu().numpy(), FP32_HEAD_TOL, scale=max(1.0, float(o.abs().max())))
+    print(f"{tag}: device against the reference's golden slices, worst {worst:.3e} (bound {bound:.3e}, float32 torch {e32:.3e})")
+
+
+def test_shared_conv_gradients_are_the_sum_over_levels_and_statistics_get_zero():
+    tag = "phi0_s128_b2_k3"
+    phi, classes, size, batch, seed = BACKWARD_CASES[tag]
+    _g64, _f64, _e32, bound = _oracle(phi, classes, size, batch, seed)
+    feats, cots = _inputs(phi, classes, size, batch, seed)
+    h = _heads(phi, classes, seed)
+    full, _, _ = _device_grads(h, feats, cots)
+    from hmd_ego_pose_amd.arch import level_sizes
+    edges = np.cumsum([0] + [9 * s * s for s in level_sizes(size)])
+    parts = []
+    for l in range(5):
+        masked = [np.zeros_like(c) for c in cots]
+        for mc, c in zip(masked, cots):
+            mc[:, edges[l]:edges[l + 1]] = c[:, edges[l]:edges[l + 1]]
+        g, _, _ = _device_grads(h, feats, masked)
+        parts.append(g)
+        for k, v in g.items():                               # a level's BatchNorm sees that level's cotangent only
+            if "bn_list" in k and f"bn_list.{l}." not in k:
+                assert not v.any(), (l, k)
+    worst = 0.0
+    for k, v in full.items():
+        if "bn_list" in k:
+            continue
+        s = sum(p[k].astype(np.float64) for p in parts)
+        worst = max(worst, H.rel_err(s, v))
+        assert H.rel_err(s, v) <= bound, (k, H.rel_err(s, v), bound)
+    print(f"{tag}: conv_list / header gradients against the sum of five single-level runs, worst {worst:.3e} (bound {bound:.3e})")
+    assert all(b.grad is None for b in h.buffers())
+
+
+def test_backward_is_deterministic_and_the_abi_equals_the_autograd_path():
+    from hmd_ego_pose_amd import heads as HD
+    phi, classes, size, batch, seed = 0, 1, 256, 2, 0
+    feats, cots = _inputs(phi, classes, size, batch, seed)
+    h = _heads(phi, classes, seed)
+    a, fa, _ = _device_grads(h, feats, cots)
+    b, fb, _ = _device_grads(h, feats, cots)
+    assert all(np.array_equal(a[k], b[k]) for k in a) and all(np.array_equal(x, y) for x, y in zip(fa, fb))
+    c, none, _ = _device_grads(h, feats, cots, feats_grad=False)          # NULL grad_feats
+    assert none is None and all(np.array_equal(a[k], c[k]) for k in a)
+    # the two entry points called directly, the gradient buffer poisoned first
+    flat = h.flat_parameters().detach()
+    f = [torch.from_numpy(x).cuda() for x in feats]
+    g = [torch.from_numpy(x).cuda() for x in cots]
+    outs, ws = HD.heads_forward(flat, f, phi, classes, size)
+    l = HD._capi.lib()
+    g_flat = torch.full_like(flat, float("nan"))
+    g_feats = [torch.full_like(x, float("nan")) for x in f]
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = l.hep_heads_backward_device(flat.data_ptr(), HD._capi.ptr_array(g), phi, classes, size, batch, g_flat.data_ptr(),
+                                     HD._capi.ptr_array(g_feats), ws.data_ptr(), ws.numel(), stream)
+    assert rc == 0, l.hep_last_error()
+    torch.cuda.synchronize()
+    total, offsets = HD.param_layout(phi, classes)
+    assert total == flat.numel()
+    host = g_flat.cpu().numpy()
+    assert np.isfinite(host).all()
+    for (k, shape), off in zip(HD.flat_keys(phi, classes), offsets):
+        v = host[off:off + int(np.prod(shape))].reshape(shape)
+        if H.trainable(k):
+            assert np.array_equal(v, a[k]), k
+        else:
+            assert not v.any(), k                                          # running statistics: exactly zero
+    assert all(np.array_equal(x.cpu().numpy(), y) for x, y in zip(g_feats, fa))
+    # a workspace one float short is refused before anything is launched
+    assert l.hep_heads_backward_device(flat.data_ptr(), HD._capi.ptr_array(g), phi, classes, size, batch, g_flat.data_ptr(), None,
+                                       ws.data_ptr(), ws.numel() - 4, stream) == -1
+
+
+def test_ten_sgd_steps_on_the_device_lower_the_training_loss_and_export_serves_them():
+    """feats of a session -> TrainableHeads -> format_translation -> training.losses on training.anchor_targets -> backward
+    -> torch.optim.SGD; the weighted total of the reference's train.py:61-68 falls, and the exported heads serve."""
+    from hmd_ego_pose_amd import HMDEgoPose, TrainableHeads, _capi, training
+    phi, size, B = 0, 256, 2
+    m = HMDEgoPose({"iter": 0}, num_classes=1, compound_coef=phi, onnx_export=True, input_sizes=[size] * 9)
+    m.load_state_dict(seeded_state_dict(phi, 4), strict=True)
+    m = m.cuda().eval()
+    x = torch.from_numpy(seeded_input((B, 3, size, size), 31)).cuda()
+    cam = torch.from_numpy(np.stack([CAMS[0]] * B)).cuda()
+    feats = m(x)[0]
+    n = _capi.lib().hep_anchors(size, None, None)
+    anchors = np.empty((n, 4), np.float32); t_anchors = np.empty((n, 3), np.float32)
+    assert _capi.lib().hep_anchors(size, anchors.ctypes.data, t_anchors.ctypes.data) == n
+    rng = np.random.Generator(np.random.PCG64(8))
+    boxes = [np.array([[48., 48., 176., 176.]]), np.array([[16., 16., 80., 80.], [112., 112., 240., 240.]])]
+    labels = [np.zeros((len(b),), np.int32) for b in boxes]
+    tr = [np.concatenate([rng.uniform(-1, 1, (len(b), 3)), rng.standard_normal((len(b), 3)) * 100 + [0, 0, 600], np.zeros((len(b), 2))], 1).astype(np.float32) for b in boxes]
+    co = [rng.standard_normal((len(b), 63)).astype(np.float32) * 50 for b in boxes]
+    lab, reg_t, tra_t, crd_t = training.anchor_targets(torch.from_numpy(anchors).cuda(), boxes, labels, tr, co, [(size, size)] * B, 1)
+    assert (tra_t[..., -1] == 1).sum(1).min().item() > 0, "every image needs an object anchor"
+    pts = (rng.standard_normal((1, 300, 3)) * 30).astype(np.float32)
+    weights = torch.tensor(TRAIN_WEIGHTS, device="cuda")
+
+    def total(heads):
+        outs = heads(feats)
+        reg, cls, rot, trn_raw, hand = outs
+        trn = training.format_translation(trn_raw, cam, size)
+        out, _per = training.losses(lab, cls, reg_t, reg, tra_t, torch.cat((rot, trn), dim=2), crd_t, hand, pts, 3)
+        return (out * weights).sum(), all(bool(torch.isfinite(o).all()) for o in outs)
+
+    def steps(lr, count):
+        heads = TrainableHeads.from_model(m).train()
+        opt = torch.optim.SGD(heads.parameters(), lr=lr)
+        values, finite = [], True
+        for _ in range(count):
+            opt.zero_grad(set_to_none=True)
+            loss, ok = total(heads)
+            loss.backward()
+            opt.step()
+            values.append(float(loss.detach()))
+            finite &= ok
+        with torch.no_grad():
+            loss, ok = total(heads)
+        return heads, values + [float(loss)], finite and ok
+
+    # The learning rate: halved from 1e-3 until it is small enough.  "Small enough" is more than "the first step lowers the
+    # loss": the rotation term (x 100, model points of 30 units) gives parameter gradients of ~1e3, so at 1e-3 .. 6e-5 the first
+    # step still lowers the total but the rotation net diverges to NaN within five steps - and batch_iterate reports a NaN
+    # rotation loss as 0, which reads as a lower total (measured: 9167 -> 2686 with a NaN rotation head).  So the run must
+    # also keep every head output finite and no later step may raise the total.
+    lr = 1e-3
+    while True:
+        heads, values, finite = steps(lr, 10)
+        print(f"lr {lr:g}: finite {finite}, weighted total over ten SGD steps {['%.6g' % t for t in values]}")
+        assert np.isfinite(values[0]), values
+        if finite and all(b < a for a, b in zip(values, values[1:])):
+            break
+        lr /= 2
+        assert lr > 1e-7, "no learning rate down to 1e-7 gives ten descending steps: the gradient is not a descent direction"
+    assert np.isfinite(values).all() and values[-1] < values[0], values
+    before = {k: v.clone() for k, v in heads.state_dict().items() if "running" in k}
+    assert all(torch.equal(v, m.state_dict()[k]) for k, v in before.items())          # running statistics never change
+    with torch.no_grad():
+        want = heads(feats)
+    heads.export_to(m)
+    got = m(x)
+    assert all(torch.equal(a, b) for a, b in zip(got[0], feats))                       # the maps do not depend on the heads
+    for name, g, w in zip(H.OUT_NAMES, got[1:], want):
+        err = (g - w).abs().max().item() / max(1.0, w.abs().max().item())
+        assert err <= FP32_HEAD_TOL, (name, err)
+
+
+def test_map_shapes_are_validated_before_the_abi_sees_a_pointer():
+    h = _heads(0, 1, 0)
+    good = [torch.zeros((2, 64, s, s), device="cuda") for s in (32, 16, 8, 4, 2)]
+    assert h(good)[0].shape == (2, 9 * 1364, 4)
+    for l, shape in ((1, (2, 64, 15, 16)), (4, (2, 64, 1, 1)), (2, (2, 88, 8, 8)), (0, (1, 64, 32, 32)), (3, (2, 64, 4))):
+        bad = list(good)
+        bad[l] = torch.zeros(shape, device="cuda")
+        with pytest.raises(ValueError):
+            h(bad)
+    with pytest.raises(ValueError):
+        h(good[:4])
+    with pytest.raises(ValueError):
+        h([g.double() for g in good])
+    with pytest.raises(ValueError):
+        h([torch.zeros((2, 64, s, s), device="cuda") for s in (25, 13, 7, 4, 2)])      # size 200
+    with pytest.raises(ValueError):
+        h([g.cpu() for g in good])

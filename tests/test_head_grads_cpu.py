@@ -1,0 +1,176 @@
+"""CPU side of the trainable pose heads (hmd_ego_pose_amd/heads.py, hep_heads_*_device, training.format_translation).
+
+The oracle's autograd through ``oracle.efficientpose_ref.head`` is pinned to the REAL reference's autograd
+(tests/golden/head_grads.npz, made by tests/golden/make_golden_head_grads.py), so the GPU tests may compare dense device
+gradients against the oracle.  Bound of that pin: the golden values are a float32 evaluation (torch CPU, one thread), the
+oracle here runs in float64, so what remains is the reference's own float32 error.  Every gradient element is a sum of at
+most batch * pixels = 682 products per level (the golden cases) behind D + 1 layers; the float32 evaluation measured against
+float64 is at most 1.8e-6 of the tensor's largest element (218 tensors, phi 0 @ 256 batch 2), and 1e-5 - 84 float32 epsilons -
+is that with a margin of five for the other cases.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from hmd_ego_pose_amd import _capi, param_spec, seeded_state_dict
+from hmd_ego_pose_amd.arch import HEAD_NAMES
+from tests import _head_grad as H
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REF_F32_TOL = 1e-5
+
+
+def check_against_golden(z, tag, names, name, got, tol, scale=None):
+    """The committed digest of ``name``: strided slice within tol * scale (scale: the largest element where the caller knows
+    it, else the larger of the slice's largest element and the tensor's mean magnitude), sum and abs-sum within tol * abs-sum."""
+    shape, (s, sa), sl = H.golden_entry(z, tag, names, name)
+    a = np.ascontiguousarray(np.asarray(got, dtype=np.float64)).reshape(-1)
+    assert list(np.shape(got)) == shape, (name, np.shape(got), shape)
+    mine = a[::H.digest_stride(a.size)]
+    if scale is None:
+        scale = max(float(np.abs(sl).max()), float(sa) / a.size)
+    err = float(np.abs(mine - sl.astype(np.float64)).max())
+    assert err <= tol * scale + 1e-30, f"{tag} {name}: slice error {err:.3e} > {tol:g} * {scale:.3e}"
+    assert abs(a.sum() - s) <= tol * sa + 1e-30 and abs(np.abs(a).sum() - sa) <= tol * sa + 1e-30, (tag, name, a.sum(), s, sa)
+    return err / scale if scale > 0 else 0.0
+
+
+@pytest.mark.parametrize("tag", list(H.GOLDEN_CASES))
+def test_oracle_autograd_reproduces_the_reference(tag):
+    """float64 autograd through oracle.efficientpose_ref.head == the real reference's autograd (eval-mode BatchNorm) on every
+    head output, every map gradient and every trainable head tensor."""
+    phi, classes, size, batch, seed = H.GOLDEN_CASES[tag]
+    z = np.load(os.path.join(HERE, "golden", "head_grads.npz"))
+    sd = seeded_state_dict(phi, seed, num_classes=classes)
+    outs, grads, gfeats = H.oracle_grads(sd, H.seeded_maps(phi, size, batch, seed + 1), H.seeded_cotangents(classes, size, batch, seed + 2),
+                                         phi, classes, torch.float64)
+    names = H.golden_names(phi, classes)
+    assert len(names) == len(z[f"{tag}/sums"]) == 10 + len(grads)
+    worst = 0.0
+    for n, o in zip(H.OUT_NAMES, outs):
+        worst = max(worst, check_against_golden(z, tag, names, f"out.{n}", o.numpy(), REF_F32_TOL))
+    for l, g in enumerate(gfeats):
+        worst = max(worst, check_against_golden(z, tag, names, f"feat.{l}", g.numpy(), REF_F32_TOL))
+    for k, g in grads.items():
+        worst = max(worst, check_against_golden(z, tag, names, "param." + k, g.numpy(), REF_F32_TOL))
+    print(f"{tag}: oracle float64 against the reference's float32 autograd, worst slice error / scale {worst:.2e}")
+
+
+@pytest.mark.parametrize("phi", [0, 3, 6])
+@pytest.mark.parametrize("classes", [1, 3])
+def test_trainable_heads_carry_the_reference_head_keys(phi, classes):
+    from hmd_ego_pose_amd import TrainableHeads
+    want = [(k, tuple(s)) for k, s in param_spec(phi, classes) if k.split(".", 1)[0] in HEAD_NAMES]
+    h = TrainableHeads(phi, classes)
+    got = [(k, tuple(v.shape)) for k, v in h.state_dict().items()]
+    assert sorted(got) == sorted(want) and len(got) == len(want)
+    params = dict(h.named_parameters())
+    for k, _ in want:
+        leaf = k.rsplit(".", 1)[1]
+        assert (k in params) == (leaf in ("weight", "bias")), k              # running statistics and counters are buffers
+    assert sum(p.numel() for p in params.values()) == sum(int(np.prod(s)) for k, s in H.head_keys(phi, classes) if H.trainable(k))
+
+
+def test_from_model_and_export_round_trip_bit_exactly():
+    from hmd_ego_pose_amd import HMDEgoPose, TrainableHeads
+    torch.manual_seed(3)
+    m = HMDEgoPose({"iter": 0}, num_classes=3, compound_coef=0)
+    m.reset_parameters(seed=5)
+    h = TrainableHeads.from_model(m)
+    sd = m.state_dict()
+    for k, v in h.state_dict().items():
+        assert torch.equal(v, sd[k]) and v.data_ptr() != sd[k].data_ptr(), k
+    with torch.no_grad():
+        for p in h.parameters():
+            p.add_(torch.randn_like(p))
+        for name, b in h.named_buffers():
+            if b.dtype == torch.float32:
+                b.add_(torch.rand_like(b))
+    before = {k: v.clone() for k, v in m.state_dict().items()}
+    assert h.export_to(m) is m
+    after, own = m.state_dict(), h.state_dict()
+    for k, v in after.items():
+        assert torch.equal(v, own[k] if k in own else before[k]), k
+    assert not torch.equal(after["hand_net.conv_list.0.pointwise_conv.conv.weight"], before["hand_net.conv_list.0.pointwise_conv.conv.weight"])
+    with pytest.raises(KeyError):
+        TrainableHeads.from_model(type("M", (), {"compound_coef": 0, "num_classes": 1, "state_dict": lambda self: {"regressor.x": torch.zeros(1)}})())
+
+
+def test_param_count_and_layout_follow_param_spec():
+    from hmd_ego_pose_amd.heads import flat_keys, param_layout
+    for phi, classes, trainable in ((0, 1, 127386), (3, 1, 691866), (6, 3, None)):
+        keys = flat_keys(phi, classes)
+        n_train = sum(int(np.prod(s)) for k, s in keys if H.trainable(k))
+        n_stats = sum(int(np.prod(s)) for k, s in keys if not H.trainable(k))
+        if trainable is not None:
+            assert n_train == trainable
+        total, offsets = param_layout(phi, classes)
+        assert total == n_train + n_stats == _capi.lib().hep_heads_param_count(phi, classes)
+        assert offsets == list(np.cumsum([0] + [int(np.prod(s)) for _, s in keys])[:-1])
+
+
+def test_heads_abi_refuses_bad_arguments_before_any_hip_call():
+    """HEP_ERR_INVALID = -1 for NULL pointers / a short or misaligned workspace, HEP_ERR_UNSUPPORTED = -4 with a reason for
+    phi 8, size 200, batch 0, num_classes 64; all of it on a machine without a device."""
+    l = _capi.lib()
+    for name in ("hep_heads_param_count", "hep_heads_param_layout", "hep_heads_workspace_bytes", "hep_heads_forward_device",
+                 "hep_heads_backward_device"):
+        assert hasattr(l, name), name
+    need = l.hep_heads_workspace_bytes(0, 1, 256, 2)
+    assert need > 0 and need % 16 == 0
+    assert l.hep_heads_workspace_bytes(0, 1, 256, 4) > need
+    buf = np.zeros(64, np.float32)
+    a = (buf.ctypes.data + 15) // 16 * 16                       # a non-NULL, 16-byte aligned host address: never dereferenced
+    five = (ctypes.c_void_p * 5)(*([a] * 5))
+    holed = (ctypes.c_void_p * 5)(a, a, None, a, a)
+    fwd = lambda params=a, feats=five, phi=0, k=1, size=256, batch=2, outs=five, ws=a, nbytes=need: \
+        l.hep_heads_forward_device(params, feats, phi, k, size, batch, outs, ws, nbytes, None)
+    bwd = lambda params=a, gouts=five, phi=0, k=1, size=256, batch=2, gparams=a, gfeats=None, ws=a, nbytes=need: \
+        l.hep_heads_backward_device(params, gouts, phi, k, size, batch, gparams, gfeats, ws, nbytes, None)
+    for f in (fwd, bwd):
+        assert f(params=None) == -1 and f(ws=None) == -1
+        assert f(phi=8) == -4 and b"phi" in l.hep_last_error()
+        assert f(phi=-1) == -4
+        assert f(size=200) == -4 and b"multiple of 128" in l.hep_last_error()
+        assert f(size=0) == -4
+        assert f(batch=0) == -4 and b"batch" in l.hep_last_error()
+        assert f(k=64) == -4 and b"num_classes" in l.hep_last_error()
+        assert f(k=0) == -4
+        assert f(nbytes=need - 4) == -1 and b"workspace" in l.hep_last_error()
+        assert f(ws=a + 4) == -1 and f(params=a + 4) == -1
+    assert fwd(feats=None) == -1 and fwd(outs=None) == -1 and fwd(feats=holed) == -1 and fwd(outs=holed) == -1
+    assert bwd(gouts=None) == -1 and bwd(gparams=None) == -1 and bwd(gouts=holed) == -1 and bwd(gfeats=holed) == -1
+    assert l.hep_heads_param_count(8, 1) == -4 and l.hep_heads_param_count(0, 64) == -4
+    assert l.hep_heads_workspace_bytes(0, 1, 200, 1) == -4 and l.hep_heads_workspace_bytes(0, 1, 256, 0) == -4
+    assert l.hep_heads_workspace_bytes(0, 1, 0, 0) == -4
+    n = l.hep_heads_param_layout(0, 1, None, 0)
+    assert n == 5 * (3 * 3 + 5 * 3 * 4) + 6 * 3
+    assert l.hep_heads_param_layout(0, 1, (ctypes.c_int64 * 4)(), 4) == -1
+
+
+def test_format_translation_matches_the_decode_oracle_and_is_differentiable():
+    from hmd_ego_pose_amd.training import format_translation
+    from oracle import decode_ref as D
+    from tests._util import CAMS
+    size = 256
+    _anchors, t_anchors = D.anchors_for_size(size)
+    rng = np.random.Generator(np.random.PCG64(7))
+    raw = rng.standard_normal((2, t_anchors.shape[0], 3)).astype(np.float32)
+    got = format_translation(torch.from_numpy(raw), torch.from_numpy(CAMS), size)
+    want = D.decode_translation(t_anchors, raw, CAMS)
+    assert got.dtype == torch.float32 and got.shape == want.shape
+    np.testing.assert_allclose(got.numpy(), want, rtol=1e-6, atol=1e-4)       # same float32 formula, torch against numpy
+    with pytest.raises(ValueError):
+        format_translation(torch.from_numpy(raw[:, :100]), torch.from_numpy(CAMS), size)
+    with pytest.raises(ValueError):
+        format_translation(torch.from_numpy(raw), torch.from_numpy(CAMS[:1]), size)
+    # autograd in float64 on a few anchors of a small input (the function is elementwise)
+    small = 128
+    n = D.anchors_for_size(small)[1].shape[0]
+    r64 = torch.from_numpy(rng.standard_normal((2, n, 3))).requires_grad_(True)
+    cam64 = torch.from_numpy(CAMS.astype(np.float64))
+    pick = torch.from_numpy(rng.choice(2 * n * 3, size=40, replace=False))
+    assert torch.autograd.gradcheck(lambda r: format_translation(r, cam64, small).reshape(-1)[pick], (r64,), eps=1e-6, atol=1e-6, rtol=1e-5)
