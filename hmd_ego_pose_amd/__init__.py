@@ -15,6 +15,9 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name == "TrainableHeads":
         from .heads import TrainableHeads
         return TrainableHeads
+    if name in ("TrainableNeck", "backbone_taps"):
+        from . import neck
+        return getattr(neck, name)
     if name == "InflightPool":
         from .pipeline import InflightPool
         return InflightPool

@@ -771,6 +771,99 @@ int hep_heads_backward_device(const float* params, const float* const grad_outs[
   return 0;
 } HEP_CATCH_INT
 
+// ---- training side: the BiFPN neck, forward and backward (k_neck_grad.hip) ----
+int64_t hep_neck_param_count(int phi) try {
+  NGPlan p; const char* why = "";
+  if (int rc = neck_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
+  return p.nparams;
+} HEP_CATCH_INT
+
+int hep_neck_param_layout(int phi, int64_t* offsets, int capacity) try {
+  NGPlan p; const char* why = "";
+  if (int rc = neck_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
+  const int W = p.W, count = p.cells * (8 + NG_NODES * 7) + NG_LATERALS * 6;
+  if (!offsets) return count;
+  if (capacity < count) return fail(HEP_ERR_INVALID, "hep_neck_param_layout: capacity is smaller than the number of neck tensors");
+  static const int fusion[8] = {2, 2, 2, 2, 3, 3, 3, 2};
+  int k = 0;
+  for (int r = 0; r < p.cells; r++) {
+    int64_t o = p.p_cell[r];
+    for (int f = 0; f < 8; f++) { offsets[k++] = o; o += fusion[f]; }
+    for (int j = 0; j < NG_NODES; j++) {
+      offsets[k++] = o; o += 9 * W;
+      offsets[k++] = o; o += (int64_t)W * W;
+      for (int t = 0; t < 5; t++) { offsets[k++] = o; o += W; }
+    }
+    if (r == 0)
+      for (int i = 0; i < NG_LATERALS; i++) {
+        o = p.p_lat[i];
+        offsets[k++] = o; o += (i + 1 < NG_LATERALS ? p.p_lat[i + 1] : p.p_cell[1]) - p.p_lat[i] - 5 * W;
+        for (int t = 0; t < 5; t++) { offsets[k++] = o; o += W; }
+      }
+  }
+  return count;
+} HEP_CATCH_INT
+
+static const char* kNeckSize = "neck: size must be a multiple of 128 in [128, 2048]";
+int64_t hep_neck_workspace_bytes(int phi, int size, int batch) try {
+  NGPlan p; const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
+  if (int rc = neck_plan(phi, size, batch, &p, &why)) return fail(rc, why);
+  return p.ws_floats * (int64_t)sizeof(float);
+} HEP_CATCH_INT
+
+static int neck_check(int phi, int size, int batch, const void* workspace, size_t workspace_bytes, NGPlan* p) {
+  const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
+  if (int rc = neck_plan(phi, size, batch, p, &why)) return fail(rc, why);
+  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "neck: the workspace must be 16-byte aligned");
+  if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "neck: the workspace is smaller than hep_neck_workspace_bytes");
+  return 0;
+}
+
+int hep_neck_forward_device(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                            void* workspace, size_t workspace_bytes, void* stream) try {
+  if (!params || !taps || !feats || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; i++) if (!taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 5; i++) if (!feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  NGPlan p;
+  if (int rc = neck_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
+  launch_neck_forward(p, params, taps, feats, (float*)workspace, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_neck_backward_device(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
+                             float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream) try {
+  if (!params || !grad_feats || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 5; i++) if (!grad_feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; i++) if (grad_taps && !grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  NGPlan p;
+  if (int rc = neck_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
+  launch_neck_backward(p, grad_feats, grad_params, grad_taps, (float*)workspace, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_neck_stage_count(int phi) try {
+  NGPlan p; const char* why = "";
+  if (int rc = neck_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
+  return neck_stage_count(p);
+} HEP_CATCH_INT
+
+int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes) try {
+  NGPlan p; const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
+  if (int rc = neck_plan(phi, size, batch, &p, &why)) return fail(rc, why);
+  static thread_local char buf[32];
+  int level = 0; int64_t off = 0;
+  if (neck_stage(p, i, buf, &level, &off)) return fail(HEP_ERR_INVALID, "bad stage index");
+  if (name) *name = buf;
+  if (dims) { dims[0] = p.B; dims[1] = p.s[level]; dims[2] = p.s[level]; dims[3] = p.W; }
+  if (offset_bytes) *offset_bytes = off * (int64_t)sizeof(float);
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

@@ -389,6 +389,33 @@ void launch_heads_forward(const HGPlan&, const float* params, const float* const
 void launch_heads_backward(const HGPlan&, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
                            float* ws, hipStream_t);
 
+// ---- training side: forward and backward of the BiFPN neck (k_neck_grad.hip) ----
+// Every map is fp32 rows [B * s_l * s_l][C] in a buffer of its own; the parameters are read from an aligned copy in the workspace.
+#define NG_NODES 8           // conv6_up conv5_up conv4_up conv3_up conv4_down conv5_down conv6_down conv7_down
+#define NG_LATERALS 6        // cell 0: p5_down_channel p4_down_channel p3_down_channel p5_to_p6 p4_down_channel_2 p5_down_channel_2
+#define NG_MAX_CELLS 8
+#define NG_FUSION_FLOATS 19  // the eight fusion vectors in front of every cell
+#define NG_TILE_ROWS 8       // rows of one column-reduction tile: short serial walks, the maps are small (32 measured 3 x slower in gather / dw_bwd)
+#define NG_MAX_SLABS 32      // split-K slabs of the weight-gradient products
+#define NG_MAX_CONTRIB 4     // consumers of one map
+struct NGPlan {
+  int phi, W, cells, B;
+  int tapc[3];                                          // channels of the taps P3, P4, P5
+  int s[5], R[5], ntiles[5], slab_rows[5], nslab[5];    // per level: side, rows, column-reduction tiles, weight-gradient slabs
+  int64_t p_cell[NG_MAX_CELLS + 1], p_lat[NG_LATERALS], nparams;   // float offsets into the flat parameter buffer
+  // float offsets into the workspace: the aligned parameter copy of each cell; tap rows; lateral z / y; cell 0's pooled P6 / P7
+  // and their argmax bytes; per node s, u, z, y (+ argmax bytes of the pool it reads); temporaries of the backward
+  int64_t o_pp[NG_MAX_CELLS], o_tap[3], o_lz[NG_LATERALS], o_ly[NG_LATERALS], o_p6, o_p7, o_am6, o_am7;
+  int64_t o_s[NG_MAX_CELLS][NG_NODES], o_u[NG_MAX_CELLS][NG_NODES], o_z[NG_MAX_CELLS][NG_NODES], o_y[NG_MAX_CELLS][NG_NODES], o_am[NG_MAX_CELLS][NG_NODES];
+  int64_t o_x, o_dz, o_du, o_ds[2][NG_NODES], o_g6, o_g7, o_pw, o_pdw, o_pb[3], o_pf[3], o_dtap[NG_LATERALS], ws_floats;
+};
+// fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
+int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why);
+int neck_stage_count(const NGPlan&);
+int neck_stage(const NGPlan&, int i, char name[32], int* level, int64_t* offset_floats);
+void launch_neck_forward(const NGPlan&, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t);
+void launch_neck_backward(const NGPlan&, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t);
+
 void launch_stem(const StemArgs&, hipStream_t);
 int stem_uses_mfma(int cout, int force = -1);      // which of the two stem kernels the plan takes (force: Knobs::stem_mfma, -1 = by width)
 void launch_pw(const PwArgs&, hipStream_t);

@@ -1,0 +1,723 @@
+// k_neck_grad.hip - training forward and backward of the BiFPN neck (all fpn_cells cells of bifpn.{r}; reference
+// efficientdet/model.py:194-266, fast-attention fusion, phi 0..5) on gfx950, fp32, as a function of (its parameters, the
+// three backbone taps P3 / P4 / P5).  The function is the inference function: BatchNorm uses the RUNNING statistics in
+// forward and backward; gamma and beta get gradients, the statistics get zero.
+//
+// Own kernels and plain layouts, as k_head_grad.hip has: every map is rows [B * s * s][C], channels contiguous, one buffer
+// per map.  The flat parameter buffer starts every cell with 19 fusion scalars, so no tensor behind them is 16-byte aligned:
+// the forward first copies each cell to workspace[4 * k + 1], which puts every conv / BatchNorm tensor on a 16-byte boundary
+// for the GEMMs' float4 loads; forward and backward read the parameters from that copy.
+//
+//   node      s = sum_i w_i * src_i (src: same-size map | nearest x2 of the level above | maxpool_same of the level below),
+//             w = relu(p) / (sum relu(p) + 1e-4);  x = swish(s);  u = depthwise3x3(x);  z = u . Wp^T + b;  y = bn(z)
+//   forward   pack; rows_from_nchw (taps); 6 lateral gemm<FWD>; 2 pools; per node fuse_fwd (stores s, x and the pool's
+//             argmax bytes), dw_fwd, gemm<FWD> (stores z and y); nchw_from_rows (the five maps)
+//   backward  per node, last cell first, within a cell 7d 6d 5d 4d 3u 4u 5u 6u:
+//             gather (the gradient of the node's OUTPUT map in gather form: every destination element adds, in a fixed
+//             order, the cotangent and w_i * d s of each consumer - same element | its 2 x 2 children | the at most four pool
+//             windows that contain it and whose argmax it is - then BatchNorm: d z, gamma / beta / bias partials);
+//             gemm<DATA> (d u = d z . Wp); gemm<WGRAD> (d Wp = d z^T . u, pixels as K, split into slabs); dw_bwd (depthwise
+//             weight partials, d x = the 3x3 with mirrored taps, d s = d x * swish'(s), the partials of <d s, src_i>);
+//             reduce (second pass over slabs and tiles); fusion (the dot products' second pass, the Jacobian of the
+//             normalisation and the relu gate).  Then the laterals of cell 0 (gather, WGRAD, DATA, reduce) and the taps.
+// Max-pool routing: zero padding is one column right and one row at the bottom (pooled sides are even); a window's gradient
+// goes to the FIRST maximal element in row-major order of the padded window (strict > while scanning), padding included -
+// a padding argmax matches no real element, so that window's gradient is dropped.
+// The pointwise products are v_mfma_f32_16x16x4_f32 (the tile scheme of k_head_grad.hip).  Every reduction is partial sums
+// in a fixed order plus a fixed-order second pass in double: bit-reproducible, no float atomics.
+#include <cstdio>
+
+#include "hep.h"
+#include "hep_dev.h"
+#include "hep_internal.h"
+
+#define NG_THREADS 256
+#define NG_BM 64
+#define NG_BN 64
+#define NG_BK 16
+#define NG_LDS_PITCH 80      // floats: rows of a k-step land 16 banks apart (conflict-free fragment reads)
+#define NG_BN_EPS 1e-3f
+#define NG_FUSION_EPS 1e-4f
+#define NG_DW_ROWS 4
+
+typedef float ng_f32x4 __attribute__((ext_vector_type(4)));
+enum { NG_SAME = 0, NG_UP = 1, NG_POOL = 2 };
+
+static const int kNeckWidth[6] = {64, 88, 112, 160, 224, 288};
+static const int kNeckCells[6] = {3, 4, 5, 6, 7, 7};
+static const int kNeckTaps[6][3] = {{40, 112, 320}, {40, 112, 320}, {48, 120, 352}, {48, 136, 384}, {56, 160, 448}, {64, 176, 512}};
+// nodes in state_dict order: conv6_up conv5_up conv4_up conv3_up conv4_down conv5_down conv6_down conv7_down
+static const int kNodeLevel[NG_NODES] = {3, 2, 1, 0, 1, 2, 3, 4};
+static const int kNodeNsrc[NG_NODES] = {2, 2, 2, 2, 3, 3, 3, 2};
+static const int kNodeFw[NG_NODES] = {0, 2, 4, 6, 8, 11, 14, 17};       // offset of the node's fusion vector in the cell
+// source maps of a node: 0..4 the cell's inputs P3..P7, 5 / 6 the second P4 / P5 input (cell 0: *_down_channel_2), 8 + j node j
+static const int kNodeSrc[NG_NODES][3] = {{3, 4, -1}, {2, 8, -1}, {1, 9, -1}, {0, 10, -1}, {5, 10, 11}, {6, 9, 12}, {3, 8, 13}, {4, 14, -1}};
+static const int kNodeMode[NG_NODES][3] = {{NG_SAME, NG_UP, 0}, {NG_SAME, NG_UP, 0}, {NG_SAME, NG_UP, 0}, {NG_SAME, NG_UP, 0},
+                                           {NG_SAME, NG_SAME, NG_POOL}, {NG_SAME, NG_SAME, NG_POOL}, {NG_SAME, NG_SAME, NG_POOL}, {NG_SAME, NG_POOL, 0}};
+static const int kOutNode[5] = {3, 4, 5, 6, 7};                           // the node whose output is the cell's P3..P7
+// laterals in state_dict order: p5_down_channel p4_down_channel p3_down_channel p5_to_p6 p4_down_channel_2 p5_down_channel_2
+static const int kLatTap[NG_LATERALS] = {2, 1, 0, 2, 1, 2};
+static const int kLatCode[NG_LATERALS] = {2, 1, 0, -1, 5, 6};             // the cell-0 input it is (-1: p6_pre, pooled into P6)
+
+__device__ __forceinline__ float ng_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// w_i = relu(p_i) / (sum_k relu(p_k) + 1e-4); p == NULL: 1 (a pool that is not a fusion source)
+__device__ __forceinline__ float ng_fusion_weight(const float* __restrict__ p, int n, int i) {
+  if (!p) return 1.0f;
+  float sum = 0.0f;
+  for (int k = 0; k < n; k++) sum += fmaxf(p[k], 0.0f);
+  return fmaxf(p[i], 0.0f) / (sum + NG_FUSION_EPS);
+}
+
+// maxpool_same(3, 2) window of output (oy, ox) over a map of even side sf: the first maximum in row-major order of the
+// padded window (zeros right / below), its position 0..8 in *arg
+__device__ __forceinline__ float ng_pool_window(const float* __restrict__ p, int b, int sf, int oy, int ox, int W, int c, int* arg) {
+  float best = 0.0f;
+  int at = 0;
+#pragma unroll
+  for (int k = 0; k < 9; k++) {
+    const int yy = 2 * oy + k / 3, xx = 2 * ox + k % 3;
+    const float v = (yy < sf && xx < sf) ? p[((int64_t)(b * sf + yy) * sf + xx) * W + c] : 0.0f;
+    if (k == 0 || v > best) { best = v; at = k; }
+  }
+  *arg = at;
+  return best;
+}
+// the pooled value again, from the stored argmax
+__device__ __forceinline__ float ng_pool_value(const float* __restrict__ p, const uint8_t* __restrict__ am, int b, int sf, int oy, int ox, int W, int c) {
+  const int so = sf >> 1, k = am[((int64_t)(b * so + oy) * so + ox) * W + c];
+  const int yy = 2 * oy + k / 3, xx = 2 * ox + k % 3;
+  return (yy < sf && xx < sf) ? p[((int64_t)(b * sf + yy) * sf + xx) * W + c] : 0.0f;
+}
+
+struct NGSrc { const float* p; const uint8_t* am; int mode; };
+// source value of a node element (b, y, x, c) of side s, r its row; the pool's argmax comes from the forward
+__device__ __forceinline__ float ng_src_value(const NGSrc& q, int r, int b, int y, int x, int s, int W, int c) {
+  if (q.mode == NG_SAME) return q.p[(int64_t)r * W + c];
+  if (q.mode == NG_UP) { const int sh = s >> 1; return q.p[((int64_t)(b * sh + (y >> 1)) * sh + (x >> 1)) * W + c]; }
+  return ng_pool_value(q.p, q.am, b, 2 * s, y, x, W, c);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct NGPackArgs { int cells; int64_t src[NG_MAX_CELLS + 1], dst[NG_MAX_CELLS]; };
+// the flat parameters, cell by cell, to their 16-byte friendly place in the workspace
+__global__ __launch_bounds__(NG_THREADS) void ng_pack_kernel(NGPackArgs a, const float* __restrict__ params, float* __restrict__ ws) {
+  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  if (idx >= a.src[a.cells]) return;
+  int r = 0;
+  for (int i = 1; i < a.cells; i++) r += (idx >= a.src[i]);
+  ws[a.dst[r] + (idx - a.src[r])] = params[idx];
+}
+
+// NCHW [B][C][s][s] -> rows [B * s * s][C]
+__global__ __launch_bounds__(NG_THREADS) void ng_rows_from_nchw_kernel(int B, int C, int ss, const float* __restrict__ in, float* __restrict__ rows) {
+  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  if (idx >= (int64_t)B * ss * C) return;
+  const int r = (int)(idx / C), c = (int)(idx % C), b = r / ss, pix = r % ss;
+  rows[idx] = in[((int64_t)b * C + c) * ss + pix];
+}
+// rows -> NCHW, summing up to three row buffers in their order (the taps collect the data gradients of their laterals)
+struct NGRows3 { const float* p[3]; int n; };
+__global__ __launch_bounds__(NG_THREADS) void ng_nchw_from_rows_kernel(int B, int C, int ss, NGRows3 rows, float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  if (idx >= (int64_t)B * ss * C) return;
+  const int r = (int)(idx / C), c = (int)(idx % C), b = r / ss, pix = r % ss;
+  float v = rows.p[0][idx];
+  for (int i = 1; i < rows.n; i++) v += rows.p[i][idx];
+  out[((int64_t)b * C + c) * ss + pix] = v;
+}
+
+// maxpool_same of a map of side sf (cell 0: p6_in = pool(p5_to_p6(P5)), p7_in = pool(p6_in)): values and argmax bytes
+__global__ __launch_bounds__(NG_THREADS) void ng_pool_fwd_kernel(int B, int sf, int W, const float* __restrict__ in, float* __restrict__ out, uint8_t* __restrict__ am) {
+  const int so = sf >> 1;
+  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  if (idx >= (int64_t)B * so * so * W) return;
+  const int r = (int)(idx / W), c = (int)(idx % W), b = r / (so * so), pix = r % (so * so);
+  int arg;
+  out[idx] = ng_pool_window(in, b, sf, pix / so, pix % so, W, c, &arg);
+  am[idx] = (uint8_t)arg;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct NGFuseArgs {
+  int B, s, W, n;
+  NGSrc src[3]; uint8_t* am_out;      // am_out: where the pool source (if any) leaves its argmax
+  const float* fw;                    // the node's fusion vector p
+  float* S; float* X;                 // the pre-activation sum (kept for the backward) and swish of it (the depthwise input)
+};
+__global__ __launch_bounds__(NG_THREADS) void ng_fuse_fwd_kernel(NGFuseArgs a) {
+  const int W = a.W, s = a.s, ss = s * s;
+  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  if (idx >= (int64_t)a.B * ss * W) return;
+  const int r = (int)(idx / W), c = (int)(idx % W), b = r / ss, pix = r % ss, y = pix / s, x = pix % s;
+  float acc = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+    if (i < a.n) {
+      float v;
+      if (a.src[i].mode == NG_POOL) {
+        int arg;
+        v = ng_pool_window(a.src[i].p, b, 2 * s, y, x, W, c, &arg);
+        a.am_out[idx] = (uint8_t)arg;
+      } else {
+        v = ng_src_value(a.src[i], r, b, y, x, s, W, c);
+      }
+      const float w = ng_fusion_weight(a.fw, a.n, i);
+      acc = i == 0 ? w * v : acc + w * v;
+    }
+  a.S[idx] = acc;
+  a.X[idx] = acc * ng_sigmoid(acc);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The 3 x 3 window of rows around row r = pixel (y, x) of an s x s map, zeros outside.  A thread that walks consecutive
+// rows keeps it in registers (one new column per step).  SW: the stored map is the pre-activation, the window holds swish of it.
+template <bool SW> __device__ __forceinline__ void ng_win_col(float (&v)[3][3], const int j, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
+  const int xx = x + j - 1;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const int yy = y + i - 1;
+    float t = (yy >= 0 && yy < s && xx >= 0 && xx < s) ? p[(int64_t)(r + (i - 1) * s + (j - 1)) * W + c] : 0.0f;
+    if (SW) t = t * ng_sigmoid(t);
+    v[i][j] = t;
+  }
+}
+template <bool SW> __device__ __forceinline__ void ng_win_step(float (&v)[3][3], bool fresh, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
+  if (fresh) {
+    ng_win_col<SW>(v, 0, p, r, y, x, s, W, c);
+    ng_win_col<SW>(v, 1, p, r, y, x, s, W, c);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { v[i][0] = v[i][1]; v[i][1] = v[i][2]; }
+  }
+  ng_win_col<SW>(v, 2, p, r, y, x, s, W, c);
+}
+
+// depthwise 3x3 SAME on the rows of one map; a thread = (NG_DW_ROWS consecutive rows, channel)
+__global__ __launch_bounds__(NG_THREADS) void ng_dw_fwd_kernel(int R, int s, int W, const float* __restrict__ src, const float* __restrict__ wdw, float* __restrict__ dst) {
+  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  const int ra = (int)(idx / W) * NG_DW_ROWS, c = (int)(idx % W);
+  if (ra >= R) return;
+  const int rb = min(R, ra + NG_DW_ROWS), ss = s * s;
+  float w[9], v[3][3];
+#pragma unroll
+  for (int tp = 0; tp < 9; tp++) w[tp] = wdw[c * 9 + tp];
+  for (int r = ra; r < rb; r++) {
+    const int pix = r % ss, y = pix / s, x = pix % s;
+    ng_win_step<false>(v, r == ra || x == 0, src, r, y, x, s, W, c);
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) acc = fmaf(w[i * 3 + j], v[i][j], acc);
+    dst[(int64_t)r * W + c] = acc;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+enum { NG_FWD = 0, NG_DATA = 1, NG_WGRAD = 2 };
+struct NGGemmArgs {
+  const float* A; const float* Bm; float* C; float* C2;
+  const float* bias; const float* bn;          // FWD: [J]; gamma, beta, mean, var [4][J]
+  int I, J, K, lda, ldb, ldc, ntn, slab_rows;
+};
+// C[i][j] = sum_k A(i,k) B(k,j), 64 x 64 per workgroup, wave w owns rows 16w..16w+15 and four 16-column accumulators.
+//   FWD     A = u rows (k contiguous), B = Wp [J][K] (k contiguous); z = C + bias -> C, bn(z) -> C2
+//   DATA    A = d z rows (k contiguous), B = Wp [K][J] (j contiguous) -> C rows
+//   WGRAD   A = d z rows read as (k = row, i = column), B = u rows (k = row); rows [z * slab_rows, ...) of K -> C[z][I][J]
+template <int MODE> __global__ __launch_bounds__(NG_THREADS) void ng_gemm_kernel(NGGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[NG_BK][NG_LDS_PITCH];
+  __shared__ __attribute__((aligned(16))) float Bs[NG_BK][NG_LDS_PITCH];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int I = a.I, J = a.J;
+  const int i0 = (int)(blockIdx.x / a.ntn) * NG_BM, j0 = (int)(blockIdx.x % a.ntn) * NG_BN;
+  if (i0 >= I || j0 >= J) return;                          // uniform over the workgroup
+  int k_begin = 0, k_end = a.K;
+  if (MODE == NG_WGRAD) { k_begin = blockIdx.z * a.slab_rows; k_end = min(a.K, k_begin + a.slab_rows); }
+  const float* __restrict__ A = a.A;
+  const float* __restrict__ Bm = a.Bm;
+  const int lda = a.lda, ldb = a.ldb;
+  ng_f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) acc[j] = ng_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int k0 = k_begin; k0 < k_end; k0 += NG_BK) {
+    float4 va = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vb = va;
+    if (MODE != NG_WGRAD) {                                 // k contiguous: thread = (row i, four k)
+      const int i = lane, kq = wv * 4;
+      if (i0 + i < I && k0 + kq < k_end) va = *reinterpret_cast<const float4*>(A + (int64_t)(i0 + i) * lda + k0 + kq);
+      As[kq + 0][i] = va.x; As[kq + 1][i] = va.y; As[kq + 2][i] = va.z; As[kq + 3][i] = va.w;
+    } else {                                                // i contiguous: thread = (k, four i)
+      const int k = t >> 4, q = (t & 15) * 4;
+      if (k0 + k < k_end && i0 + q < I) va = *reinterpret_cast<const float4*>(A + (int64_t)(k0 + k) * lda + i0 + q);
+      *reinterpret_cast<float4*>(&As[k][q]) = va;
+    }
+    if (MODE == NG_FWD) {
+      const int j = lane, kq = wv * 4;
+      if (j0 + j < J && k0 + kq < k_end) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(j0 + j) * ldb + k0 + kq);
+      Bs[kq + 0][j] = vb.x; Bs[kq + 1][j] = vb.y; Bs[kq + 2][j] = vb.z; Bs[kq + 3][j] = vb.w;
+    } else {
+      const int k = t >> 4, q = (t & 15) * 4;
+      if (k0 + k < k_end && j0 + q < J) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(k0 + k) * ldb + j0 + q);
+      *reinterpret_cast<float4*>(&Bs[k][q]) = vb;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < NG_BK / 4; kk++) {
+      const float av = As[kk * 4 + (lane >> 4)][wv * 16 + (lane & 15)];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const float bv = Bs[kk * 4 + (lane >> 4)][j * 16 + (lane & 15)];
+        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // accumulator element (reg): row 4 * (lane >> 4) + reg, column lane & 15
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int n = j0 + j * 16 + (lane & 15);
+    if (n >= J) continue;
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) {
+      const int m = i0 + wv * 16 + (lane >> 4) * 4 + reg;
+      if (m >= I) continue;
+      const float v = acc[j][reg];
+      if (MODE == NG_FWD) {
+        const float z = v + a.bias[n];
+        const float rstd = 1.0f / sqrtf(a.bn[3 * J + n] + NG_BN_EPS);
+        a.C[(int64_t)m * a.ldc + n] = z;
+        a.C2[(int64_t)m * a.ldc + n] = (z - a.bn[2 * J + n]) * rstd * a.bn[n] + a.bn[J + n];
+      } else if (MODE == NG_DATA) {
+        a.C[(int64_t)m * a.ldc + n] = v;
+      } else {
+        a.C[((int64_t)blockIdx.z * I + m) * J + n] = v;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// One consumer of a map: the node whose source i it is (d s rows of that node, its fusion vector), or a plain pool
+// (fw NULL: weight 1, g = the gradient of the pooled map).  mode as the FORWARD saw it from the consumer.
+struct NGContrib { const float* g; const float* fw; const uint8_t* am; int n, idx, mode; };
+struct NGGatherArgs {
+  int B, s, W, R, nc;
+  NGContrib c[NG_MAX_CONTRIB];
+  const float* cot;                       // NCHW cotangent of this map (the last cell's outputs), or NULL
+  const float* Z; const float* bn;        // the map's pre-BatchNorm rows and gamma, beta, mean, var; NULL: a pooled map, no BatchNorm
+  float* out;                             // d z rows (or the map's gradient rows)
+  float* pgamma; float* pbeta; float* pbias;   // [tile][W]
+};
+// Gradient of one map in gather form + the BatchNorm that produced it.  One thread = (tile of NG_TILE_ROWS rows, channel).
+__global__ __launch_bounds__(NG_THREADS) void ng_gather_kernel(NGGatherArgs a) {
+  const int W = a.W, s = a.s, ss = s * s;
+  const int64_t gid = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  const int tile = (int)(gid / W), c = (int)(gid % W);
+  const int r0 = tile * NG_TILE_ROWS, r1 = min(a.R, r0 + NG_TILE_ROWS);
+  if (r0 >= a.R) return;
+  float wt[NG_MAX_CONTRIB];
+#pragma unroll
+  for (int i = 0; i < NG_MAX_CONTRIB; i++) wt[i] = i < a.nc ? ng_fusion_weight(a.c[i].fw, a.c[i].n, a.c[i].idx) : 0.0f;
+  float gamma = 0.0f, mean = 0.0f, rstd = 0.0f;
+  if (a.bn) { gamma = a.bn[c]; mean = a.bn[2 * W + c]; rstd = 1.0f / sqrtf(a.bn[3 * W + c] + NG_BN_EPS); }
+  float ag = 0.0f, ab = 0.0f, abias = 0.0f;
+  for (int r = r0; r < r1; r++) {
+    const int b = r / ss, pix = r % ss, y = pix / s, x = pix % s;
+    float g = a.cot ? a.cot[((int64_t)b * W + c) * ss + pix] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < NG_MAX_CONTRIB; i++)
+      if (i < a.nc) {
+        const float* __restrict__ G = a.c[i].g;
+        float v = 0.0f;
+        if (a.c[i].mode == NG_SAME) {
+          v = G[(int64_t)r * W + c];
+        } else if (a.c[i].mode == NG_UP) {                  // the consumer is the finer level: the 2 x 2 children of (y, x)
+          const int sf = 2 * s;
+#pragma unroll
+          for (int d = 0; d < 4; d++) v += G[((int64_t)(b * sf + 2 * y + (d >> 1)) * sf + 2 * x + (d & 1)) * W + c];
+        } else {                                            // the consumer is the coarser level: the windows that contain (y, x)
+          const int so = s >> 1;
+          const uint8_t* __restrict__ am = a.c[i].am;
+          for (int oy = (y >> 1) - ((y & 1) == 0 && y >= 2); oy <= (y >> 1); oy++)
+            for (int ox = (x >> 1) - ((x & 1) == 0 && x >= 2); ox <= (x >> 1); ox++) {
+              const int64_t o = ((int64_t)(b * so + oy) * so + ox) * W + c;
+              if (am[o] == (y - 2 * oy) * 3 + (x - 2 * ox)) v += G[o];
+            }
+        }
+        g = fmaf(wt[i], v, g);
+      }
+    if (a.bn) {
+      const float zh = (a.Z[(int64_t)r * W + c] - mean) * rstd, dz = g * gamma * rstd;
+      ag = fmaf(g, zh, ag); ab += g; abias += dz;
+      a.out[(int64_t)r * W + c] = dz;
+    } else {
+      a.out[(int64_t)r * W + c] = g;
+    }
+  }
+  if (a.bn) {
+    a.pgamma[(int64_t)tile * W + c] = ag; a.pbeta[(int64_t)tile * W + c] = ab; a.pbias[(int64_t)tile * W + c] = abias;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct NGDwBwdArgs {
+  int B, s, W, R, n;
+  const float* G; const float* S; const float* w;     // d u rows, the node's pre-activation rows, depthwise weights [W][1][3][3]
+  NGSrc src[3];
+  float* DS;                                          // d s rows
+  float* pdw; double* pf[3];                          // [tile][W * 9]; per source one double per workgroup (these dot products cancel heavily)
+};
+// One thread = (tile of NG_TILE_ROWS rows, channel); it walks the rows of its tile in order:
+//   depthwise weight gradient  pdw[tap] += d u[r] * x[neighbour(r, tap)],  x = swish(s)
+//   depthwise data gradient    d x[r]    = sum_tap w[8 - tap] * d u[neighbour(r, tap)]
+//   fusion                     d s = d x * swish'(s);  pf[i] += d s * src_i   (exact products, added in double)
+__global__ __launch_bounds__(NG_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
+  __shared__ double red[3][NG_THREADS];
+  const int W = a.W, s = a.s, ss = s * s, t = threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * NG_THREADS + t;
+  const int tile = (int)(gid / W), c = (int)(gid % W);
+  const int r0 = tile * NG_TILE_ROWS, r1 = min(a.R, r0 + NG_TILE_ROWS);
+  double af[3] = {0.0, 0.0, 0.0};
+  if (r0 < a.R) {
+    float wt[9], aw[9];
+#pragma unroll
+    for (int tp = 0; tp < 9; tp++) { wt[tp] = a.w[c * 9 + tp]; aw[tp] = 0.0f; }
+    float xw[3][3], gw[3][3];
+    for (int r = r0; r < r1; r++) {
+      const int b = r / ss, pix = r % ss, y = pix / s, x = pix % s;
+      const bool fresh = r == r0 || x == 0;
+      ng_win_step<true>(xw, fresh, a.S, r, y, x, s, W, c);
+      ng_win_step<false>(gw, fresh, a.G, r, y, x, s, W, c);
+      const float gk = gw[1][1];
+      float dx = 0.0f;
+#pragma unroll
+      for (int tp = 0; tp < 9; tp++) {
+        aw[tp] = fmaf(gk, xw[tp / 3][tp % 3], aw[tp]);
+        dx = fmaf(wt[8 - tp], gw[tp / 3][tp % 3], dx);
+      }
+      const float sv = a.S[(int64_t)r * W + c], sg = ng_sigmoid(sv);
+      const float ds = dx * (sg * (1.0f + sv * (1.0f - sg)));
+      a.DS[(int64_t)r * W + c] = ds;
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+        if (i < a.n) af[i] = fma((double)ds, (double)ng_src_value(a.src[i], r, b, y, x, s, W, c), af[i]);
+    }
+#pragma unroll
+    for (int tp = 0; tp < 9; tp++) a.pdw[((int64_t)tile * W + c) * 9 + tp] = aw[tp];
+  }
+  // the workgroup's share of <d s, src_i>: a fixed-order tree over its 256 threads, one double per source and workgroup
+#pragma unroll
+  for (int i = 0; i < 3; i++) red[i][t] = af[i];
+  __syncthreads();
+  for (int h = NG_THREADS / 2; h > 0; h >>= 1) {
+    if (t < h) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) red[i][t] += red[i][t + h];
+    }
+    __syncthreads();
+  }
+  if (t == 0)
+    for (int i = 0; i < a.n; i++) a.pf[i][blockIdx.x] = red[i][0];
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// second pass: element e of job j = the sum of its partials src[e + k * stride], k < nparts, added in double in a FIXED
+// order: 16 threads share an element, thread j adds the partials j, j + 16, ... in index order, then thread 0 adds the 16
+// sums in order 0..15 and rounds once (the scheme of hg_reduce_kernel).  src == NULL: the element is zero (running statistics).
+#define NG_RED_E 16
+#define NG_RED_K 16
+#define NG_RED_JOBS 6
+struct NGRedJob { const float* src; float* dst; int64_t count, stride; int nparts; };
+struct NGReduceArgs { NGRedJob j[NG_RED_JOBS]; };
+static_assert(NG_RED_E * NG_RED_K == NG_THREADS, "one reduce workgroup = 16 elements x 16 partial lanes");
+__global__ __launch_bounds__(NG_THREADS) void ng_reduce_kernel(NGReduceArgs a) {
+  __shared__ double part[NG_RED_K][NG_RED_E + 1];
+  const NGRedJob& job = a.j[blockIdx.y];
+  const int el = threadIdx.x % NG_RED_E, kl = threadIdx.x / NG_RED_E;
+  const int64_t e = (int64_t)blockIdx.x * NG_RED_E + el;
+  if ((int64_t)blockIdx.x * NG_RED_E >= job.count) return;  // uniform over the workgroup
+  const bool live = e < job.count;
+  double s = 0.0;
+  if (live && job.src)
+    for (int k = kl; k < job.nparts; k += NG_RED_K) s += (double)job.src[e + k * job.stride];
+  part[kl][el] = s;
+  __syncthreads();
+  if (kl == 0 && live) {
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < NG_RED_K; j++) t += part[j][el];
+    job.dst[e] = (float)t;
+  }
+}
+
+// The fusion vector's gradient: a_i = <d s, src_i> = the sum of the workgroup sums pf[i][0 .. count) (thread t adds t, t + 256, ... in double,
+// thread 0 adds the 256 sums in order), then with r = relu(p), D = sum r + 1e-4, w = r / D:
+//   d L / d p_j = (a_j - sum_i a_i w_i) / D  where p_j > 0, else exactly 0.
+struct NGFusionArgs { const double* pf[3]; int n; int64_t count; const float* p; float* dp; };
+__global__ __launch_bounds__(NG_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
+  __shared__ double part[3][NG_THREADS];
+  for (int i = 0; i < a.n; i++) {
+    double s = 0.0;
+    for (int64_t k = threadIdx.x; k < a.count; k += NG_THREADS) s += a.pf[i][k];
+    part[i][threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double dot[3] = {0.0, 0.0, 0.0}, D = (double)NG_FUSION_EPS, mix = 0.0;
+  for (int i = 0; i < a.n; i++) {
+    for (int k = 0; k < NG_THREADS; k++) dot[i] += part[i][k];
+    D += (double)fmaxf(a.p[i], 0.0f);
+  }
+  for (int i = 0; i < a.n; i++) mix += dot[i] * ((double)fmaxf(a.p[i], 0.0f) / D);
+  for (int i = 0; i < a.n; i++) a.dp[i] = a.p[i] > 0.0f ? (float)((dot[i] - mix) / D) : 0.0f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host side
+static inline int64_t ng_node_stride(int W) { return (int64_t)9 * W + (int64_t)W * W + W + 4 * W; }
+static inline int64_t ng_lat_stride(int W, int K) { return (int64_t)W * K + W + 4 * W; }
+static inline unsigned ng_blocks(int64_t n) { return (unsigned)((n + NG_THREADS - 1) / NG_THREADS); }
+
+int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why) {
+  if (phi == 6 || phi == 7) { *why = "neck: phi 6 and 7 fuse by plain sums at width 384 (no fast attention): not supported, phi must be in 0..5"; return HEP_ERR_UNSUPPORTED; }
+  if (phi < 0 || phi > 5) { *why = "neck: phi must be in 0..5 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
+  const int W = kNeckWidth[phi];
+  p->phi = phi; p->W = W; p->cells = kNeckCells[phi];
+  for (int t = 0; t < 3; t++) p->tapc[t] = kNeckTaps[phi][t];
+  int64_t o = 0;
+  for (int r = 0; r < p->cells; r++) {
+    p->p_cell[r] = o; o += NG_FUSION_FLOATS + NG_NODES * ng_node_stride(W);
+    if (r == 0)
+      for (int i = 0; i < NG_LATERALS; i++) { p->p_lat[i] = o; o += ng_lat_stride(W, p->tapc[kLatTap[i]]); }
+  }
+  p->p_cell[p->cells] = o;
+  p->nparams = o;
+  if (size == 0 && batch == 0) return 0;                   // layout only
+  if (size < 128 || size > 2048 || size % 128 != 0) { *why = "neck: size must be a multiple of 128 in [128, 2048]"; return HEP_ERR_UNSUPPORTED; }
+  if (batch < 1) { *why = "neck: batch must be at least 1"; return HEP_ERR_UNSUPPORTED; }
+  if ((int64_t)batch * (size / 8) * (size / 8) > (1 << 22)) { *why = "neck: batch * pixels exceeds 4 Mi rows"; return HEP_ERR_UNSUPPORTED; }
+  p->B = batch;
+  for (int l = 0; l < 5; l++) {
+    p->s[l] = size / (8 << l); p->R[l] = batch * p->s[l] * p->s[l];
+    p->ntiles[l] = (p->R[l] + NG_TILE_ROWS - 1) / NG_TILE_ROWS;
+    int ns = p->R[l] / 512; if (ns < 1) ns = 1; if (ns > NG_MAX_SLABS) ns = NG_MAX_SLABS;
+    p->slab_rows[l] = ((p->R[l] + ns - 1) / ns + NG_BK - 1) / NG_BK * NG_BK;
+    p->nslab[l] = (p->R[l] + p->slab_rows[l] - 1) / p->slab_rows[l];
+  }
+  int64_t w = 0;
+  auto take = [&](int64_t n) { const int64_t at = w; w += (n + 3) / 4 * 4; return at; };
+  for (int r = 0; r < p->cells; r++) p->o_pp[r] = take(p->p_cell[r + 1] - p->p_cell[r] + 4) + 1;   // + 19 fusion floats = 16-byte aligned
+  for (int t = 0; t < 3; t++) p->o_tap[t] = take((int64_t)p->R[t] * p->tapc[t]);
+  for (int i = 0; i < NG_LATERALS; i++) { p->o_lz[i] = take((int64_t)p->R[kLatTap[i]] * W); p->o_ly[i] = take((int64_t)p->R[kLatTap[i]] * W); }
+  p->o_p6 = take((int64_t)p->R[3] * W); p->o_p7 = take((int64_t)p->R[4] * W);
+  p->o_am6 = take(((int64_t)p->R[3] * W + 3) / 4); p->o_am7 = take(((int64_t)p->R[4] * W + 3) / 4);
+  for (int r = 0; r < p->cells; r++)
+    for (int j = 0; j < NG_NODES; j++) {
+      const int64_t n = (int64_t)p->R[kNodeLevel[j]] * W;
+      p->o_s[r][j] = take(n); p->o_u[r][j] = take(n); p->o_z[r][j] = take(n); p->o_y[r][j] = take(n);
+      p->o_am[r][j] = j >= 4 ? take((n + 3) / 4) : 0;      // the down-path nodes pool the level below
+    }
+  const int64_t n0 = (int64_t)p->R[0] * W;
+  p->o_x = take(n0); p->o_dz = take(n0); p->o_du = take(n0);
+  for (int k = 0; k < 2; k++)
+    for (int j = 0; j < NG_NODES; j++) p->o_ds[k][j] = take((int64_t)p->R[kNodeLevel[j]] * W);
+  p->o_g6 = take((int64_t)p->R[3] * W); p->o_g7 = take((int64_t)p->R[4] * W);
+  int kmax = W;
+  for (int t = 0; t < 3; t++) if (p->tapc[t] > kmax) kmax = p->tapc[t];
+  p->o_pw = take((int64_t)NG_MAX_SLABS * W * kmax);
+  p->o_pdw = take((int64_t)p->ntiles[0] * W * 9);
+  for (int k = 0; k < 3; k++) { p->o_pb[k] = take((int64_t)p->ntiles[0] * W); p->o_pf[k] = take((int64_t)2 * p->ntiles[0] * W); }
+  for (int i = 0; i < NG_LATERALS; i++) p->o_dtap[i] = take((int64_t)p->R[kLatTap[i]] * p->tapc[kLatTap[i]]);
+  p->ws_floats = w;
+  return 0;
+}
+
+int neck_stage_count(const NGPlan& p) { return 2 + 5 * p.cells; }
+// stage i: 0 p6_pre (the p5_to_p6 lateral's output), 1 bifpn0_p6_in, then bifpn{r}_p{3..7}
+int neck_stage(const NGPlan& p, int i, char name[32], int* level, int64_t* offset_floats) {
+  if (i < 0 || i >= neck_stage_count(p)) return -1;
+  if (i == 0) { snprintf(name, 32, "p6_pre"); *level = 2; *offset_floats = p.o_ly[3]; return 0; }
+  if (i == 1) { snprintf(name, 32, "bifpn0_p6_in"); *level = 3; *offset_floats = p.o_p6; return 0; }
+  const int r = (i - 2) / 5, l = (i - 2) % 5;
+  snprintf(name, 32, "bifpn%d_p%d", r, l + 3);
+  *level = l; *offset_floats = p.o_y[r][kOutNode[l]];
+  return 0;
+}
+
+namespace {
+// the maps a cell's nodes read, by source code (kNodeSrc)
+const float* ng_map(const NGPlan& p, const float* ws, int cell, int code) {
+  if (code >= 8) return ws + p.o_y[cell][code - 8];
+  if (cell > 0) return ws + p.o_y[cell - 1][kOutNode[code == 5 ? 1 : code == 6 ? 2 : code]];
+  switch (code) {
+    case 0: return ws + p.o_ly[2];
+    case 1: return ws + p.o_ly[1];
+    case 2: return ws + p.o_ly[0];
+    case 3: return ws + p.o_p6;
+    case 4: return ws + p.o_p7;
+    case 5: return ws + p.o_ly[4];
+    default: return ws + p.o_ly[5];
+  }
+}
+inline const float* ng_node_params(const NGPlan& p, const float* ws, int cell, int j) { return ws + p.o_pp[cell] + NG_FUSION_FLOATS + j * ng_node_stride(p.W); }
+inline const float* ng_lat_params(const NGPlan& p, const float* ws, int i) { return ws + p.o_pp[0] + (p.p_lat[i] - p.p_cell[0]); }
+inline uint8_t* ng_bytes(float* ws, int64_t off) { return reinterpret_cast<uint8_t*>(ws + off); }
+
+void ng_node_sources(const NGPlan& p, float* ws, int cell, int j, NGSrc src[3]) {
+  for (int i = 0; i < kNodeNsrc[j]; i++) {
+    src[i].p = ng_map(p, ws, cell, kNodeSrc[j][i]);
+    src[i].mode = kNodeMode[j][i];
+    src[i].am = src[i].mode == NG_POOL ? ng_bytes(ws, p.o_am[cell][j]) : nullptr;
+  }
+}
+
+void ng_gemm(int mode, const NGGemmArgs& m, int nslab, hipStream_t st) {
+  const int ntm = (m.I + NG_BM - 1) / NG_BM;
+  if (mode == NG_FWD) hipLaunchKernelGGL(ng_gemm_kernel<NG_FWD>, dim3(ntm * m.ntn), dim3(NG_THREADS), 0, st, m);
+  else if (mode == NG_DATA) hipLaunchKernelGGL(ng_gemm_kernel<NG_DATA>, dim3(ntm * m.ntn), dim3(NG_THREADS), 0, st, m);
+  else hipLaunchKernelGGL(ng_gemm_kernel<NG_WGRAD>, dim3(ntm * m.ntn, 1, nslab), dim3(NG_THREADS), 0, st, m);
+}
+
+// consumers of the map `code` among the nodes of `cell`, in node order
+void ng_collect(const NGPlan& p, float* ws, int cell, int code, NGGatherArgs* ga) {
+  for (int j = 0; j < NG_NODES; j++)
+    for (int i = 0; i < kNodeNsrc[j]; i++) {
+      int sc = kNodeSrc[j][i];
+      if (cell > 0 && sc == 5) sc = 1;
+      if (cell > 0 && sc == 6) sc = 2;
+      if (sc != code) continue;
+      NGContrib& c = ga->c[ga->nc++];
+      c.g = ws + p.o_ds[cell & 1][j]; c.fw = ws + p.o_pp[cell] + kNodeFw[j]; c.n = kNodeNsrc[j]; c.idx = i; c.mode = kNodeMode[j][i];
+      c.am = c.mode == NG_POOL ? ng_bytes(ws, p.o_am[cell][j]) : nullptr;
+    }
+}
+void ng_collect_pool(float* g, uint8_t* am, NGGatherArgs* ga) {
+  NGContrib& c = ga->c[ga->nc++];
+  c.g = g; c.fw = nullptr; c.am = am; c.n = 0; c.idx = 0; c.mode = NG_POOL;
+}
+
+// BatchNorm partials [tile][W] -> gamma, beta, zeros for the statistics, and the conv bias
+void ng_bn_jobs(const NGPlan& p, float* ws, int level, float* dbias, float* dbn, NGReduceArgs* rd, int at) {
+  const int W = p.W, T = p.ntiles[level];
+  rd->j[at + 0] = NGRedJob{ws + p.o_pb[0], dbn, W, W, T};
+  rd->j[at + 1] = NGRedJob{ws + p.o_pb[1], dbn + W, W, W, T};
+  rd->j[at + 2] = NGRedJob{nullptr, dbn + 2 * W, 2 * W, 0, 0};
+  rd->j[at + 3] = NGRedJob{ws + p.o_pb[2], dbias, W, W, T};
+}
+}  // namespace
+
+void launch_neck_forward(const NGPlan& p, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t st) {
+  const int W = p.W, B = p.B;
+  NGPackArgs pk{}; pk.cells = p.cells;
+  for (int r = 0; r < p.cells; r++) { pk.src[r] = p.p_cell[r]; pk.dst[r] = p.o_pp[r]; }
+  pk.src[p.cells] = p.nparams;
+  hipLaunchKernelGGL(ng_pack_kernel, dim3(ng_blocks(p.nparams)), dim3(NG_THREADS), 0, st, pk, params, ws);
+  for (int t = 0; t < 3; t++)
+    hipLaunchKernelGGL(ng_rows_from_nchw_kernel, dim3(ng_blocks((int64_t)p.R[t] * p.tapc[t])), dim3(NG_THREADS), 0, st, B, p.tapc[t], p.s[t] * p.s[t], taps[t], ws + p.o_tap[t]);
+  for (int i = 0; i < NG_LATERALS; i++) {
+    const int t = kLatTap[i], K = p.tapc[t];
+    const float* lp = ng_lat_params(p, ws, i);
+    NGGemmArgs m{}; m.A = ws + p.o_tap[t]; m.Bm = lp; m.bias = lp + (int64_t)W * K; m.bn = lp + (int64_t)W * K + W;
+    m.C = ws + p.o_lz[i]; m.C2 = ws + p.o_ly[i]; m.I = p.R[t]; m.J = W; m.K = K; m.lda = K; m.ldb = K; m.ldc = W; m.ntn = (W + NG_BN - 1) / NG_BN;
+    ng_gemm(NG_FWD, m, 1, st);
+  }
+  hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(ng_blocks((int64_t)p.R[3] * W)), dim3(NG_THREADS), 0, st, B, p.s[2], W, (const float*)(ws + p.o_ly[3]), ws + p.o_p6, ng_bytes(ws, p.o_am6));
+  hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(ng_blocks((int64_t)p.R[4] * W)), dim3(NG_THREADS), 0, st, B, p.s[3], W, (const float*)(ws + p.o_p6), ws + p.o_p7, ng_bytes(ws, p.o_am7));
+  for (int r = 0; r < p.cells; r++)
+    for (int j = 0; j < NG_NODES; j++) {
+      const int l = kNodeLevel[j], R = p.R[l];
+      const float* np = ng_node_params(p, ws, r, j);
+      NGFuseArgs f{}; f.B = B; f.s = p.s[l]; f.W = W; f.n = kNodeNsrc[j];
+      ng_node_sources(p, ws, r, j, f.src);
+      f.am_out = j >= 4 ? ng_bytes(ws, p.o_am[r][j]) : nullptr;
+      f.fw = ws + p.o_pp[r] + kNodeFw[j]; f.S = ws + p.o_s[r][j]; f.X = ws + p.o_x;
+      hipLaunchKernelGGL(ng_fuse_fwd_kernel, dim3(ng_blocks((int64_t)R * W)), dim3(NG_THREADS), 0, st, f);
+      hipLaunchKernelGGL(ng_dw_fwd_kernel, dim3(ng_blocks((int64_t)((R + NG_DW_ROWS - 1) / NG_DW_ROWS) * W)), dim3(NG_THREADS), 0, st, R, p.s[l], W,
+                         (const float*)(ws + p.o_x), np, ws + p.o_u[r][j]);
+      NGGemmArgs m{}; m.A = ws + p.o_u[r][j]; m.Bm = np + 9 * W; m.bias = np + 9 * W + (int64_t)W * W; m.bn = m.bias + W;
+      m.C = ws + p.o_z[r][j]; m.C2 = ws + p.o_y[r][j]; m.I = R; m.J = W; m.K = W; m.lda = W; m.ldb = W; m.ldc = W; m.ntn = (W + NG_BN - 1) / NG_BN;
+      ng_gemm(NG_FWD, m, 1, st);
+    }
+  for (int l = 0; l < 5; l++) {
+    NGRows3 rows{}; rows.p[0] = ws + p.o_y[p.cells - 1][kOutNode[l]]; rows.n = 1;
+    hipLaunchKernelGGL(ng_nchw_from_rows_kernel, dim3(ng_blocks((int64_t)p.R[l] * W)), dim3(NG_THREADS), 0, st, B, W, p.s[l] * p.s[l], rows, feats[l]);
+  }
+}
+
+void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t st) {
+  const int W = p.W, B = p.B, ntn = (W + NG_BN - 1) / NG_BN;
+  auto gather = [&](NGGatherArgs& ga, int l) {
+    ga.B = B; ga.s = p.s[l]; ga.W = W; ga.R = p.R[l];
+    ga.pgamma = ws + p.o_pb[0]; ga.pbeta = ws + p.o_pb[1]; ga.pbias = ws + p.o_pb[2];
+    hipLaunchKernelGGL(ng_gather_kernel, dim3(ng_blocks((int64_t)p.ntiles[l] * W)), dim3(NG_THREADS), 0, st, ga);
+  };
+  for (int r = p.cells - 1; r >= 0; r--) {
+    float* gcell = grad_params + p.p_cell[r];
+    for (int j = NG_NODES - 1; j >= 0; j--) {               // 7d 6d 5d 4d 3u 4u 5u 6u: every consumer of a map before the map
+      const int l = kNodeLevel[j], R = p.R[l], T = p.ntiles[l];
+      const float* np = ng_node_params(p, ws, r, j);
+      float* gn = gcell + NG_FUSION_FLOATS + j * ng_node_stride(W);
+      // the node's output map: its consumers in this cell, then in the next one (or the cotangent)
+      NGGatherArgs ga{};
+      int out_level = -1;
+      for (int k = 0; k < 5; k++) if (kOutNode[k] == j) out_level = k;
+      if (out_level >= 0 && r == p.cells - 1) ga.cot = grad_feats[out_level];
+      ng_collect(p, ws, r, 8 + j, &ga);
+      if (out_level >= 0 && r + 1 < p.cells) ng_collect(p, ws, r + 1, out_level, &ga);
+      ga.Z = ws + p.o_z[r][j]; ga.bn = np + 9 * W + (int64_t)W * W + W; ga.out = ws + p.o_dz;
+      gather(ga, l);
+      NGGemmArgs md{}; md.A = ws + p.o_dz; md.Bm = np + 9 * W; md.C = ws + p.o_du; md.I = R; md.J = W; md.K = W; md.lda = W; md.ldb = W; md.ldc = W; md.ntn = ntn;
+      ng_gemm(NG_DATA, md, 1, st);
+      NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_u[r][j]; mw.C = ws + p.o_pw; mw.I = W; mw.J = W; mw.K = R; mw.lda = W; mw.ldb = W; mw.ntn = ntn;
+      mw.slab_rows = p.slab_rows[l];
+      ng_gemm(NG_WGRAD, mw, p.nslab[l], st);
+      NGDwBwdArgs db{}; db.B = B; db.s = p.s[l]; db.W = W; db.R = R; db.n = kNodeNsrc[j];
+      db.G = ws + p.o_du; db.S = ws + p.o_s[r][j]; db.w = np; db.DS = ws + p.o_ds[r & 1][j]; db.pdw = ws + p.o_pdw;
+      ng_node_sources(p, ws, r, j, db.src);
+      for (int i = 0; i < 3; i++) db.pf[i] = reinterpret_cast<double*>(ws + p.o_pf[i]);
+      hipLaunchKernelGGL(ng_dw_bwd_kernel, dim3(ng_blocks((int64_t)T * W)), dim3(NG_THREADS), 0, st, db);
+      NGReduceArgs rd{};
+      rd.j[0] = NGRedJob{ws + p.o_pw, gn + 9 * W, (int64_t)W * W, (int64_t)W * W, p.nslab[l]};
+      rd.j[1] = NGRedJob{ws + p.o_pdw, gn, (int64_t)W * 9, (int64_t)W * 9, T};
+      ng_bn_jobs(p, ws, l, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, &rd, 2);
+      hipLaunchKernelGGL(ng_reduce_kernel, dim3((unsigned)(((int64_t)W * W + NG_RED_E - 1) / NG_RED_E), NG_RED_JOBS), dim3(NG_THREADS), 0, st, rd);
+      NGFusionArgs fa{}; fa.n = kNodeNsrc[j]; fa.count = ng_blocks((int64_t)T * W); fa.p = ws + p.o_pp[r] + kNodeFw[j]; fa.dp = gcell + kNodeFw[j];
+      for (int i = 0; i < 3; i++) fa.pf[i] = reinterpret_cast<const double*>(ws + p.o_pf[i]);
+      hipLaunchKernelGGL(ng_fusion_kernel, dim3(1), dim3(NG_THREADS), 0, st, fa);
+    }
+  }
+  // cell 0's own inputs.  p7_in and p6_in are pooled maps (no parameters): their gradients feed the pool below them.
+  {
+    NGGatherArgs g7{}; ng_collect(p, ws, 0, 4, &g7); g7.out = ws + p.o_g7; gather(g7, 4);
+    NGGatherArgs g6{}; ng_collect(p, ws, 0, 3, &g6); ng_collect_pool(ws + p.o_g7, ng_bytes(ws, p.o_am7), &g6); g6.out = ws + p.o_g6; gather(g6, 3);
+  }
+  for (int i = 0; i < NG_LATERALS; i++) {
+    const int t = kLatTap[i], K = p.tapc[t], R = p.R[t];
+    const float* lp = ng_lat_params(p, ws, i);
+    float* gl = grad_params + p.p_lat[i];
+    NGGatherArgs ga{};
+    if (kLatCode[i] >= 0) ng_collect(p, ws, 0, kLatCode[i], &ga);
+    else ng_collect_pool(ws + p.o_g6, ng_bytes(ws, p.o_am6), &ga);
+    ga.Z = ws + p.o_lz[i]; ga.bn = lp + (int64_t)W * K + W; ga.out = ws + p.o_dz;
+    gather(ga, t);
+    NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_tap[t]; mw.C = ws + p.o_pw; mw.I = W; mw.J = K; mw.K = R; mw.lda = W; mw.ldb = K;
+    mw.ntn = (K + NG_BN - 1) / NG_BN; mw.slab_rows = p.slab_rows[t];
+    ng_gemm(NG_WGRAD, mw, p.nslab[t], st);
+    if (grad_taps) {
+      NGGemmArgs md{}; md.A = ws + p.o_dz; md.Bm = lp; md.C = ws + p.o_dtap[i]; md.I = R; md.J = K; md.K = W; md.lda = W; md.ldb = K; md.ldc = K;
+      md.ntn = (K + NG_BN - 1) / NG_BN;
+      ng_gemm(NG_DATA, md, 1, st);
+    }
+    NGReduceArgs rd{};
+    rd.j[0] = NGRedJob{ws + p.o_pw, gl, (int64_t)W * K, (int64_t)W * K, p.nslab[t]};
+    rd.j[1] = NGRedJob{nullptr, nullptr, 0, 0, 0};
+    ng_bn_jobs(p, ws, t, gl + (int64_t)W * K, gl + (int64_t)W * K + W, &rd, 2);
+    hipLaunchKernelGGL(ng_reduce_kernel, dim3((unsigned)(((int64_t)W * K + NG_RED_E - 1) / NG_RED_E), NG_RED_JOBS), dim3(NG_THREADS), 0, st, rd);
+  }
+  if (grad_taps)
+    for (int t = 0; t < 3; t++) {
+      NGRows3 rows{};
+      for (int i = 0; i < NG_LATERALS; i++) if (kLatTap[i] == t) rows.p[rows.n++] = ws + p.o_dtap[i];
+      hipLaunchKernelGGL(ng_nchw_from_rows_kernel, dim3(ng_blocks((int64_t)p.R[t] * p.tapc[t])), dim3(NG_THREADS), 0, st, B, p.tapc[t], p.s[t] * p.s[t], rows, grad_taps[t]);
+    }
+}

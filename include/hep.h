@@ -25,6 +25,7 @@
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
  *   hep_heads_forward_device / hep_heads_backward_device <- the five head nets under those losses, trainable
+ *   hep_neck_forward_device / hep_neck_backward_device <- the BiFPN neck in front of them, trainable
  *   hep_pose_errors / _device  <- check_6d_pose_add / check_6d_pose_add_s, pytorch-sandbox/eval/common.py:682-746 with
  *                                 c_min_distances, pytorch-sandbox/generators/utils/calc_min_distances.h:24-35 (the
  *                                 metric arithmetic of evaluate.py's loop, eval/common.py:866-1121)
@@ -229,7 +230,7 @@ int hep_losses_backward_device(const float* gt_classification, const float* clas
                                float* grad_regression, float* grad_transformation, float* grad_hand, int32_t* workspace, void* stream);
 
 /* The five head nets (regressor, classifier, rotation_net, translation_net, hand_net) as a TRAINABLE function of the five
- * BiFPN maps: forward and backward in HIP (csrc/k_head_grad.hip), so that the heads can be fitted on the device behind
+ * BiFPN maps: forward and backward in HIP (csrc/k_head_grad.hip; the neck in front of them: hep_neck_*), so that the heads can be fitted on the device behind
  * hep_losses_device / hep_losses_backward_device.  Stateless: plain pointers and sizes, asynchronous on `stream`, no
  * allocation, no host synchronisation, argument checks before any HIP call, bit-reproducible (no float atomics).
  * BatchNorm uses its RUNNING statistics in forward and backward (the function the inference path computes; the
@@ -255,6 +256,41 @@ int hep_heads_forward_device(const float* params, const float* const feats[5], i
                              float* const outs[5], void* workspace, size_t workspace_bytes, void* stream);
 int hep_heads_backward_device(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
                               float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream);
+
+/* The BiFPN neck (every cell of bifpn.{r}; reference efficientdet/model.py:194-266) as a TRAINABLE function of its parameters
+ * and the three backbone taps P3 / P4 / P5: forward and backward in HIP (csrc/k_neck_grad.hip).  Same conventions as the
+ * hep_heads_* group: stateless, asynchronous on `stream`, no allocation, no host synchronisation, argument checks before any
+ * HIP call, bit-reproducible (no float atomics), BatchNorm with its RUNNING statistics in forward and backward (gamma and beta
+ * get gradients, the statistics get exactly zero).  Fast-attention fusion w = relu(p) / (sum relu(p) + 1e-4); relu'(p) = 0 for
+ * p <= 0.  Max-pool gradients go to the FIRST maximal element in row-major order of the zero-padded 3 x 3 window (padding:
+ * one column right, one row below).  The backward through the backbone is out of scope (the taps are inputs; grad_taps
+ * gives their gradient).
+ *
+ * params: ONE flat fp32 device buffer (16-byte aligned) with every bifpn.* tensor in the reference's shapes and state_dict
+ * order, num_batches_tracked left out (per cell the eight fusion vectors p6_w1 .. p7_w2, then per node depthwise [W,1,3,3],
+ * pointwise [W,W,1,1], bias [W], bn weight / bias / running_mean / running_var; cell 0 ends with its six lateral convs:
+ * weight [W,C,1,1], bias, BatchNorm).  hep_neck_param_count: its length in floats; hep_neck_param_layout: the offset of every
+ * tensor in that order (offsets == NULL: returns how many).
+ * taps[t]: fp32 NCHW [batch][tap_channels[t]][s][s], s = size/8, size/16, size/32.  feats[l]: fp32 NCHW [batch][W][s_l][s_l],
+ * the layout hep_heads_forward_device takes.  workspace: hep_neck_workspace_bytes bytes, 16-byte aligned, owned by the caller;
+ * the forward leaves in it what the backward needs (an aligned copy of params included): hand the SAME workspace, untouched, to
+ * hep_neck_backward_device.  grad_feats[l]: cotangents of the five maps.  grad_params: layout of params, every element
+ * written.  grad_taps: three NCHW buffers, or NULL to skip the tap gradients.
+ * Supported: phi 0..5 (phi 6 / 7 fuse by plain sums: HEP_ERR_UNSUPPORTED), size a multiple of 128 in [128, 2048], batch >= 1.
+ *
+ * hep_neck_stage_*: introspection for tests.  Stage i names an fp32 tensor the forward leaves in the workspace at
+ * offset_bytes, laid out NHWC: dims = {batch, s, s, W}, channels contiguous.  Names: "p6_pre" (the p5_to_p6 lateral's
+ * output, pooled into P6 of cell 0), "bifpn0_p6_in" (that pool's result, pooled again into P7), and "bifpn{r}_p3" ..
+ * "bifpn{r}_p7", the outputs of cell r (p3 .. p6 are pooled by the cell's down path).  *name points to thread-local storage. */
+int64_t hep_neck_param_count(int phi);
+int hep_neck_param_layout(int phi, int64_t* offsets, int capacity);
+int64_t hep_neck_workspace_bytes(int phi, int size, int batch);
+int hep_neck_forward_device(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                            void* workspace, size_t workspace_bytes, void* stream);
+int hep_neck_backward_device(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
+                             float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream);
+int hep_neck_stage_count(int phi);
+int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes);
 
 /* preprocess_image (reference generators/colibri_common.py:622-656): device uint8 RGB [batch, height, width, 3] ->
  * device float32 [batch, size, size, 3]: resize by scale = size / max(height, width) (8-bit bilinear, OpenCV
