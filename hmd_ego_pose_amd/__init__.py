@@ -18,6 +18,9 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name in ("TrainableNeck", "backbone_taps"):
         from . import neck
         return getattr(neck, name)
+    if name == "TrainableBackbone":
+        from .backbone import TrainableBackbone
+        return TrainableBackbone
     if name == "InflightPool":
         from .pipeline import InflightPool
         return InflightPool

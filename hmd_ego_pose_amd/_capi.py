@@ -61,6 +61,13 @@ SYMBOLS = {
     "hep_neck_backward_device": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, _FP, POINTER(_FP), c_void_p, c_size_t, c_void_p]),
     "hep_neck_stage_count": (c_int, [c_int]),
     "hep_neck_stage_info": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
+    "hep_backbone_param_count": (c_int64, [c_int]),
+    "hep_backbone_param_layout": (c_int, [c_int, POINTER(c_int64), c_int]),
+    "hep_backbone_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "hep_backbone_forward_device": (c_int, [_FP, _FP, _FP, c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_void_p]),
+    "hep_backbone_backward_device": (c_int, [_FP, POINTER(_FP), _FP, c_int, c_int, c_int, _FP, _FP, c_void_p, c_size_t, c_void_p]),
+    "hep_backbone_stage_count": (c_int, [c_int]),
+    "hep_backbone_stage_info": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
     "hep_debug_tensor_count": (c_int, [_P]),
     "hep_debug_tensor_info": (c_int, [_P, c_int, POINTER(c_char_p), POINTER(c_int64)]),
     "hep_debug_tensor": (c_int, [_P, c_char_p, c_int, _FP, c_size_t]),

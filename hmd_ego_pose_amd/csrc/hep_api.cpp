@@ -864,6 +864,81 @@ int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, 
   return 0;
 } HEP_CATCH_INT
 
+// ---- training side: the EfficientNet trunk, forward and backward (k_backbone_grad.hip) ----
+int64_t hep_backbone_param_count(int phi) try {
+  BGPlan p; const char* why = "";
+  if (int rc = backbone_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
+  return p.nparams;
+} HEP_CATCH_INT
+
+int hep_backbone_param_layout(int phi, int64_t* offsets, int capacity) try {
+  BGPlan p; const char* why = "";
+  if (int rc = backbone_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
+  const int count = backbone_tensor_count(p);
+  if (!offsets) return count;
+  if (capacity < count) return fail(HEP_ERR_INVALID, "hep_backbone_param_layout: capacity is smaller than the number of backbone tensors");
+  backbone_tensor_offsets(p, offsets);
+  return count;
+} HEP_CATCH_INT
+
+static const char* kBackboneSize = "backbone: size must be a multiple of 128 in [128, 2048]";
+int64_t hep_backbone_workspace_bytes(int phi, int size, int batch) try {
+  BGPlan p; const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
+  if (int rc = backbone_plan(phi, size, batch, &p, &why)) return fail(rc, why);
+  return p.ws_floats * (int64_t)sizeof(float);
+} HEP_CATCH_INT
+
+static int backbone_check(int phi, int size, int batch, const void* workspace, size_t workspace_bytes, BGPlan* p) {
+  const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
+  if (int rc = backbone_plan(phi, size, batch, p, &why)) return fail(rc, why);
+  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "backbone: the workspace must be 16-byte aligned");
+  if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "backbone: the workspace is smaller than hep_backbone_workspace_bytes");
+  return 0;
+}
+
+int hep_backbone_forward_device(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
+                                void* workspace, size_t workspace_bytes, void* stream) try {
+  if (!params || !image || !taps || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; i++) if (!taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  static thread_local BGPlan p;
+  if (int rc = backbone_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
+  launch_backbone_forward(p, params, image, branch_scale, taps, (float*)workspace, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_backbone_backward_device(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
+                                 float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, void* stream) try {
+  if (!params || !grad_taps || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; i++) if (!grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  static thread_local BGPlan p;
+  if (int rc = backbone_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
+  launch_backbone_backward(p, grad_taps, branch_scale, grad_params, grad_image, (float*)workspace, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_backbone_stage_count(int phi) try {
+  static thread_local BGPlan p; const char* why = "";
+  if (int rc = backbone_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
+  return backbone_stage_count(p);
+} HEP_CATCH_INT
+
+int hep_backbone_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes) try {
+  static thread_local BGPlan p; const char* why = "";
+  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
+  if (int rc = backbone_plan(phi, size, batch, &p, &why)) return fail(rc, why);
+  static thread_local char buf[32];
+  int side = 0, channels = 0; int64_t off = 0;
+  if (backbone_stage(p, i, buf, &side, &channels, &off)) return fail(HEP_ERR_INVALID, "bad stage index");
+  if (name) *name = buf;
+  if (dims) { dims[0] = p.B; dims[1] = side; dims[2] = side; dims[3] = channels; }
+  if (offset_bytes) *offset_bytes = off * (int64_t)sizeof(float);
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

@@ -416,6 +416,40 @@ int neck_stage(const NGPlan&, int i, char name[32], int* level, int64_t* offset_
 void launch_neck_forward(const NGPlan&, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t);
 void launch_neck_backward(const NGPlan&, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t);
 
+// ---- training side: forward and backward of the EfficientNet trunk (k_backbone_grad.hip) ----
+// Every map is fp32 rows [B * s * s][C] in a buffer of its own; the parameters are read from an aligned copy in the workspace.
+#define BG_MAX_BLOCKS 48     // phi 6 / 7 have 45 MBConv blocks
+#define BG_MAX_SEGMENTS (2 * BG_MAX_BLOCKS + 1)   // aligned parameter copies: the stem, per block [expand .. se_expand bias] and [project, bn2]
+#define BG_MAX_SLABS 256     // split-K slabs of the weight-gradient products (up to 16 * 128 * 128 rows at phi 0 / 256 / batch 16)
+#define BG_MAX_CEXP 3456     // widest expanded map (phi 6 / 7) and squeeze width: the squeeze-excite kernels keep one image's vectors in LDS
+#define BG_MAX_SE 144
+struct BGBlock {
+  int cin, cexp, k, stride, se, cout, expand, skip;
+  int s_in, s_out, R_in, R_out;
+  // float offsets into the flat parameter buffer (p_first: the block's first tensor, p_end: one past its last)
+  int64_t p_first, p_w0, p_bn0, p_dw, p_bn1, p_wr, p_br, p_we, p_be, p_w2, p_bn2, p_end;
+  // float offsets into the workspace: the two aligned parameter copies; what the forward keeps (conv outputs z0 z1 z2, swish(bn0(z0)),
+  // the gated map, the block's output, per image the squeezed means, the reduce FC's output and the gate)
+  int64_t q_a, q_b, o_z0, o_a0, o_z1, o_xg, o_z2, o_y, o_m, o_r, o_g;
+};
+struct BGPlan {
+  int phi, nblocks, stem, B, size, s0, R0;
+  int taps[3], tapc[3];                                 // blocks whose outputs are P3, P4, P5 and their channels
+  int64_t p_stem, p_bn_stem, nparams;
+  BGBlock b[BG_MAX_BLOCKS];
+  // workspace: stem parameters, the image, the stem's conv output and activation; temporaries of forward (a1) and backward
+  int64_t q_stem, o_img, o_zs, o_as, o_a1, o_dy[2], o_dz2, o_dxg, o_da0, o_dx, o_pw, o_pcol[2], o_pdw, o_pse, o_dl, o_dr, o_dm, ws_floats;
+};
+// fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
+int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why);
+int backbone_tensor_count(const BGPlan&);
+void backbone_tensor_offsets(const BGPlan&, int64_t* offsets);
+int backbone_stage_count(const BGPlan&);
+int backbone_stage(const BGPlan&, int i, char name[32], int* side, int* channels, int64_t* offset_floats);
+void launch_backbone_forward(const BGPlan&, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t);
+void launch_backbone_backward(const BGPlan&, const float* const grad_taps[3], const float* branch_scale, float* grad_params, float* grad_image, float* ws,
+                              hipStream_t);
+
 void launch_stem(const StemArgs&, hipStream_t);
 int stem_uses_mfma(int cout, int force = -1);      // which of the two stem kernels the plan takes (force: Knobs::stem_mfma, -1 = by width)
 void launch_pw(const PwArgs&, hipStream_t);

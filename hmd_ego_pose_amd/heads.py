@@ -14,8 +14,8 @@ BatchNorm: RUNNING statistics in every mode (``train()`` and ``eval()`` compute 
 backward - frozen-statistics fine-tuning, the reference's ``freeze_bn`` (backbone.py:99).  That is the gradient of the
 function the inference path computes, so "train here, serve here" is consistent: ``gamma`` and ``beta`` get gradients,
 ``running_mean`` / ``running_var`` never change.  Batch-statistics BatchNorm (``model.train()`` in the reference's
-train.py:162) is out of scope, and so are the backward through the backbone and bf16 training (the BiFPN in front of the
-heads is trainable too: ``hmd_ego_pose_amd.neck.TrainableNeck``).
+train.py:162) is out of scope, and so is bf16 training (the BiFPN and the backbone in front of the heads are trainable too:
+``hmd_ego_pose_amd.neck.TrainableNeck``, ``hmd_ego_pose_amd.backbone.TrainableBackbone``).
 """
 from __future__ import annotations
 

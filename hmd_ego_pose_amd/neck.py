@@ -13,9 +13,9 @@ and ``export_to(model)`` copies the fitted tensors back into the ``HMDEgoPose`` 
 The rules are those of ``hmd_ego_pose_amd.heads``: BatchNorm uses its RUNNING statistics in every mode, forward and backward
 (``gamma`` / ``beta`` get gradients, ``running_mean`` / ``running_var`` never change); fast-attention fusion
 ``w = relu(p) / (sum relu(p) + 1e-4)`` with ``relu'(p) = 0`` for ``p <= 0``; a max-pool window sends its gradient to its first
-maximal element in row-major order of the zero-padded window.  phi 6 and 7 (plain-sum fusion) are refused.  Out of scope:
-the backward through the backbone (the taps are inputs; their gradient is available when they require grad),
-batch-statistics BatchNorm and bf16 training.
+maximal element in row-major order of the zero-padded window.  phi 6 and 7 (plain-sum fusion) are refused.  The taps are
+inputs; their gradient is available when they require grad, which is how ``hmd_ego_pose_amd.backbone.TrainableBackbone`` chains
+in front of the neck.  Out of scope: batch-statistics BatchNorm and bf16 training.
 """
 from __future__ import annotations
 

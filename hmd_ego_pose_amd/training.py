@@ -12,7 +12,9 @@ backward is HIP as well (csrc/k_loss_grad.hip, hep_losses_backward_device): the 
 computed on the whole GPU without a host synchronisation.  ``batch_iterate`` is the drop-in with the reference's signature
 and return shape.  The five head nets under these losses are trainable as well (``heads.TrainableHeads``: HIP forward and
 backward, csrc/k_head_grad.hip); ``format_translation`` is the differentiable step between them (the losses take the DECODED
-translation, train.py:39,49).  Backward through BiFPN and the backbone stays out of scope (the inference path has no backward).
+translation, train.py:39,49).  The BiFPN (``neck.TrainableNeck``) and the EfficientNet trunk (``backbone.TrainableBackbone``) in
+front of them have a HIP forward and backward of their own as well, so image -> backbone -> neck -> heads -> losses is differentiable
+end to end on the project's kernels.
 """
 from __future__ import annotations
 

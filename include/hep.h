@@ -26,6 +26,7 @@
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
  *   hep_heads_forward_device / hep_heads_backward_device <- the five head nets under those losses, trainable
  *   hep_neck_forward_device / hep_neck_backward_device <- the BiFPN neck in front of them, trainable
+ *   hep_backbone_forward_device / hep_backbone_backward_device <- the EfficientNet trunk in front of the neck, trainable
  *   hep_pose_errors / _device  <- check_6d_pose_add / check_6d_pose_add_s, pytorch-sandbox/eval/common.py:682-746 with
  *                                 c_min_distances, pytorch-sandbox/generators/utils/calc_min_distances.h:24-35 (the
  *                                 metric arithmetic of evaluate.py's loop, eval/common.py:866-1121)
@@ -263,8 +264,8 @@ int hep_heads_backward_device(const float* params, const float* const grad_outs[
  * HIP call, bit-reproducible (no float atomics), BatchNorm with its RUNNING statistics in forward and backward (gamma and beta
  * get gradients, the statistics get exactly zero).  Fast-attention fusion w = relu(p) / (sum relu(p) + 1e-4); relu'(p) = 0 for
  * p <= 0.  Max-pool gradients go to the FIRST maximal element in row-major order of the zero-padded 3 x 3 window (padding:
- * one column right, one row below).  The backward through the backbone is out of scope (the taps are inputs; grad_taps
- * gives their gradient).
+ * one column right, one row below).  The taps are inputs; grad_taps gives their gradient (what hep_backbone_backward_device
+ * takes).
  *
  * params: ONE flat fp32 device buffer (16-byte aligned) with every bifpn.* tensor in the reference's shapes and state_dict
  * order, num_batches_tracked left out (per cell the eight fusion vectors p6_w1 .. p7_w2, then per node depthwise [W,1,3,3],
@@ -291,6 +292,43 @@ int hep_neck_backward_device(const float* params, const float* const grad_feats[
                              float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream);
 int hep_neck_stage_count(int phi);
 int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes);
+
+/* The EfficientNet trunk (backbone_net.model.*: stem conv + BN + swish and every MBConv block - expand 1x1, depthwise k3 / k5 at
+ * stride 1 / 2 with TF-SAME padding, squeeze-excite, project 1x1, skip add; reference efficientnet/model.py:69-104,
+ * efficientdet/model.py:436-458) as a TRAINABLE function image [batch][3][size][size] -> (P3, P4, P5): forward and backward in
+ * HIP (csrc/k_backbone_grad.hip).  Same conventions as the hep_neck_* group: stateless, asynchronous on `stream`, no
+ * allocation, no host synchronisation, argument checks before any HIP call, bit-reproducible (no float atomics), BatchNorm
+ * with its RUNNING statistics in forward and backward (gamma and beta get gradients, the statistics get exactly zero).
+ *
+ * Drop-connect (efficientnet/utils.py:85-94) enters as data.  branch_scale: fp32 [blocks][batch] on the device, or NULL for
+ * all ones; a block that adds its input computes y = bn2(project) * branch_scale[block][image] + input, the other blocks
+ * ignore their row.  Hand the same table (or NULL) to forward and backward.
+ *
+ * params: ONE flat fp32 device buffer (16-byte aligned) with every float backbone_net.* tensor in the reference's shapes and
+ * state_dict order, num_batches_tracked left out (_conv_stem weight [stem,3,3,3], _bn0 weight / bias / running_mean /
+ * running_var, then per block [_expand_conv [cexp,cin,1,1], _bn0], _depthwise_conv [cexp,1,k,k], _bn1, _se_reduce weight
+ * [se,cexp,1,1] and bias, _se_expand weight [cexp,se,1,1] and bias, _project_conv [cout,cexp,1,1], _bn2).
+ * hep_backbone_param_count: its length in floats; hep_backbone_param_layout: the offset of every tensor in that order
+ * (offsets == NULL: returns how many).
+ * image: fp32 NCHW, contiguous.  taps[t]: fp32 NCHW [batch][tap_channels[t]][s][s], s = size/8, size/16, size/32: what
+ * hep_neck_forward_device takes.  workspace: hep_backbone_workspace_bytes bytes, 16-byte aligned, owned by the caller; the
+ * forward leaves in it what the backward needs (aligned copies of params and of the image included): hand the SAME workspace,
+ * untouched, to hep_backbone_backward_device.  grad_taps[t]: cotangents of the three taps.  grad_params: layout of params,
+ * every element written.  grad_image: an NCHW buffer like image, or NULL to skip the image gradient.
+ * Supported: phi 0..7, size a multiple of 128 in [128, 2048], batch >= 1 (HEP_ERR_UNSUPPORTED otherwise).
+ *
+ * hep_backbone_stage_*: introspection for tests.  Stage i names an fp32 tensor the forward leaves in the workspace at
+ * offset_bytes, laid out NHWC: dims = {batch, s, s, C}, channels contiguous.  Names: "stem" (after BN and swish) and
+ * "block{i}", the output of MBConv block i.  *name points to thread-local storage. */
+int64_t hep_backbone_param_count(int phi);
+int hep_backbone_param_layout(int phi, int64_t* offsets, int capacity);
+int64_t hep_backbone_workspace_bytes(int phi, int size, int batch);
+int hep_backbone_forward_device(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch,
+                                float* const taps[3], void* workspace, size_t workspace_bytes, void* stream);
+int hep_backbone_backward_device(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
+                                 float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, void* stream);
+int hep_backbone_stage_count(int phi);
+int hep_backbone_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes);
 
 /* preprocess_image (reference generators/colibri_common.py:622-656): device uint8 RGB [batch, height, width, 3] ->
  * device float32 [batch, size, size, 3]: resize by scale = size / max(height, width) (8-bit bilinear, OpenCV
