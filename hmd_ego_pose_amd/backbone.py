@@ -20,14 +20,12 @@ batch-statistics BatchNorm and bf16 training.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Optional, Tuple
 
 import torch
-from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _capi
+from . import _capi, _trainable
 from .arch import get_arch, param_spec
 
 PREFIX = "backbone_net."
@@ -42,7 +40,7 @@ def backbone_spec(compound_coef: int) -> List[Tuple[str, tuple]]:
 def flat_keys(compound_coef: int) -> List[Tuple[str, tuple]]:
     """The tensors of the flat fp32 parameter buffer of hep_backbone_*_device, in buffer order: ``backbone_spec`` without the
     int64 ``num_batches_tracked`` counters."""
-    return [(k, s) for k, s in backbone_spec(compound_coef) if not k.endswith("num_batches_tracked")]
+    return _trainable.without_counters(backbone_spec(compound_coef))
 
 
 def _check_size(size: int):
@@ -85,25 +83,12 @@ def backbone_backward(flat: torch.Tensor, grad_taps, ws: torch.Tensor, compound_
 def stage_views(ws: torch.Tensor, compound_coef: int, size: int, batch: int) -> Dict[str, torch.Tensor]:
     """name -> float32 view [B, s, s, C] (NHWC) of every tensor hep_backbone_stage_info names in the workspace of a forward:
     ``stem`` and ``block{i}``, the names of ``Session.stage``."""
-    l = _capi.lib()
-    out = {}
-    for i in range(_capi.check(l.hep_backbone_stage_count(compound_coef))):
-        nm = ctypes.c_char_p(); dims = (ctypes.c_int64 * 4)(); off = ctypes.c_int64()
-        _capi.check(l.hep_backbone_stage_info(compound_coef, size, batch, i, ctypes.byref(nm), dims, ctypes.byref(off)))
-        shape = tuple(int(d) for d in dims)
-        n = shape[0] * shape[1] * shape[2] * shape[3]
-        out[nm.value.decode()] = ws[off.value:off.value + 4 * n].view(torch.float32).view(shape)
-    return out
+    return _trainable.stage_views("backbone", ws, compound_coef, size, batch)
 
 
 def param_layout(compound_coef: int):
     """(total floats, [offset of every ``flat_keys`` tensor]) as the library reports them."""
-    l = _capi.lib()
-    total = _capi.check(l.hep_backbone_param_count(compound_coef))
-    n = _capi.check(l.hep_backbone_param_layout(compound_coef, None, 0))
-    arr = (ctypes.c_int64 * n)()
-    _capi.check(l.hep_backbone_param_layout(compound_coef, arr, n))
-    return int(total), [int(v) for v in arr]
+    return _trainable.param_layout("backbone", compound_coef)
 
 
 def draw_branch_scale(compound_coef: int, rate: float, batch: int, device) -> Optional[torch.Tensor]:
@@ -141,13 +126,12 @@ class _Backbone(torch.autograd.Function):
     def backward(ctx, *grad_taps):
         flat, ws, *rest = ctx.saved_tensors
         phi, size, shapes = ctx.cfg
-        gs = [torch.zeros(s, dtype=torch.float32, device=flat.device) if g is None else g.to(torch.float32).contiguous()
-              for g, s in zip(grad_taps, shapes)]
+        gs = _trainable.cotangents(grad_taps, shapes, flat.device)
         g_flat, g_img = backbone_backward(flat, gs, ws, phi, size, rest[0] if rest else None, want_image=ctx.needs_input_grad[1])
         return (g_flat if ctx.needs_input_grad[0] else None, g_img, None, None)
 
 
-class TrainableBackbone(nn.Module):
+class TrainableBackbone(_trainable.TrainablePart):
     """The EfficientNet trunk as an ``nn.Module`` whose parameters and buffers carry exactly the reference's ``backbone_net.*``
     keys, so that ``load_state_dict(model.state_dict(), strict=False)`` fills it.  ``forward(x)`` takes a float32 ROCm image
     batch [B, 3, S, S] (S a multiple of 128 in [128, 2048]) and gives the taps (P3, P4, P5) as float32 NCHW with a ``grad_fn``:
@@ -157,41 +141,14 @@ class TrainableBackbone(nn.Module):
     0.0) is the reference's global rate: non-zero and in ``train()``, every forward draws fresh branch scales
     (``draw_branch_scale``); otherwise the module is deterministic."""
 
+    NOUN, spec = "backbone", staticmethod(backbone_spec)
+
     def __init__(self, compound_coef: int = 0, drop_connect_rate: float = 0.0):
         super().__init__()
-        from .model import _attach
         self.compound_coef = int(compound_coef)
         self.arch = get_arch(self.compound_coef)
         self.drop_connect_rate = float(drop_connect_rate)
-        for key, shape in backbone_spec(self.compound_coef):
-            _attach(self, key, shape)
-        self._flat_keys = [k for k, _ in flat_keys(self.compound_coef)]
-
-    @classmethod
-    def from_model(cls, model) -> "TrainableBackbone":
-        """A trunk with the tensors of an ``HMDEgoPose`` (or any module with the reference's keys), on the model's device."""
-        n = cls(model.compound_coef)
-        sd = model.state_dict()
-        missing = [k for k, _ in backbone_spec(n.compound_coef) if k not in sd]
-        if missing:
-            raise KeyError(f"the model's state_dict lacks backbone tensors, e.g. {missing[0]}")
-        n.load_state_dict(sd, strict=False)
-        return n.to(next(iter(sd.values())).device)
-
-    def export_to(self, model):
-        """Copy every ``backbone_net.*`` tensor into ``model`` (an ``HMDEgoPose``) and drop its packed device weights."""
-        own, dst = self.state_dict(), model.state_dict()
-        with torch.no_grad():
-            for k, v in own.items():
-                dst[k].copy_(v)
-        model.invalidate()
-        return model
-
-    def flat_parameters(self) -> torch.Tensor:
-        """The flat fp32 buffer of hep_backbone_*_device (autograd-tracked: its gradient splits back onto the parameters)."""
-        tensors = dict(self.named_parameters())
-        tensors.update(dict(self.named_buffers()))
-        return torch.cat([tensors[k].reshape(-1) for k in self._flat_keys])
+        self._attach_spec(self.compound_coef)
 
     def draw_branch_scale(self, batch: int, device) -> Optional[torch.Tensor]:
         """The branch scales ``forward`` would draw now: None unless ``drop_connect_rate`` is non-zero and the module trains."""

@@ -5,8 +5,8 @@
 // zero.  Drop-connect enters as data: branch_scale[block][image] multiplies the residual branch of the blocks that add their
 // input (NULL: every scale is 1).
 //
-// Own kernels and plain layouts, as k_neck_grad.hip has: every map is rows [B * s * s][C], channels contiguous, one buffer per
-// map.  The squeeze-excite biases have 4, 6, 10, ... floats, so the tensors behind them are not 16-byte aligned in the flat
+// Plain layouts, as k_neck_grad.hip has (the GEMM tile and the reduce are grad_dev.h's): every map is rows [B * s * s][C],
+// channels contiguous, one buffer per map.  The squeeze-excite biases have 4, 6, 10, ... floats, so the tensors behind them are not 16-byte aligned in the flat
 // parameter buffer: the forward first copies the stem, every block up to its se_expand bias and every block's project conv +
 // bn2 to 16-byte aligned places in the workspace (the GEMMs' float4 loads); forward and backward read that copy.
 //
@@ -21,54 +21,36 @@
 //             act_bwd (d a1 = d xg * g + d m / ss, swish', bn1: d z1 in place), dw_wgrad (per-tile partials), dw_dgrad (gather
 //             form), reduce; [act_bwd (bn0: d z0), gemm<WGRAD> (d W0), gemm<DATA> (d x), reduce].  Then the stem: act_bwd,
 //             stem_wgrad, reduce, and stem_dgrad when the image gradient is requested.
-// The pointwise products are v_mfma_f32_16x16x4_f32 (the tile scheme of k_neck_grad.hip, copied so that the neck's and the
-// heads' kernels stay untouched).  Every reduction is partial sums in a fixed order plus a fixed-order second pass in double:
-// bit-reproducible, no float atomics.
+// The pointwise products are v_mfma_f32_16x16x4_f32 (gd_gemm_tile of grad_dev.h).  Every reduction is partial sums in a
+// fixed order plus a fixed-order second pass in double (gd_reduce_kernel): bit-reproducible, no float atomics.
 #include <cstdio>
 
 #include "hep.h"
-#include "hep_dev.h"
+#include "grad_dev.h"
 #include "hep_host.h"
 #include "hep_internal.h"
 
-#define BG_THREADS 256
-#define BG_BM 64
-#define BG_BN 64
-#define BG_BK 16
-#define BG_LDS_PITCH 80      // floats: rows of a k-step land 16 banks apart (conflict-free fragment reads)
-#define BG_BN_EPS 1e-3f
-
-typedef float bg_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bg_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
-__device__ __forceinline__ float bg_swish_grad(float v) { const float sg = bg_sigmoid(v); return sg * (1.0f + v * (1.0f - sg)); }
-
-// BatchNorm with running statistics: bn = gamma, beta, mean, var [4][C]
-struct BGBn { float gamma, beta, mean, rstd; };
-__device__ __forceinline__ BGBn bg_bn_load(const float* __restrict__ bn, int C, int c) {
-  return BGBn{bn[c], bn[C + c], bn[2 * C + c], 1.0f / sqrtf(bn[3 * C + c] + BG_BN_EPS)};
-}
-__device__ __forceinline__ float bg_bn_apply(const BGBn& q, float z) { return fmaf((z - q.mean) * q.rstd, q.gamma, q.beta); }
+#define BG_RED_JOBS 4        // reduce jobs of one launch: a weight, gamma, beta, statistics
 
 // ------------------------------------------------------------------------------------------------------------------
 struct BGPackArgs { int64_t src[BG_MAX_SEGMENTS], dst[BG_MAX_SEGMENTS], len[BG_MAX_SEGMENTS]; };
 // segment blockIdx.y of the flat parameters to its 16-byte aligned place in the workspace
-__global__ __launch_bounds__(BG_THREADS) void bg_pack_kernel(BGPackArgs a, const float* __restrict__ params, float* __restrict__ ws) {
+__global__ __launch_bounds__(GD_THREADS) void bg_pack_kernel(BGPackArgs a, const float* __restrict__ params, float* __restrict__ ws) {
   const int sgm = blockIdx.y;
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= a.len[sgm]) return;
   ws[a.dst[sgm] + idx] = params[a.src[sgm] + idx];
 }
 
 // the image, kept for the stem's weight gradient
-__global__ __launch_bounds__(BG_THREADS) void bg_copy_kernel(int64_t n, const float* __restrict__ src, float* __restrict__ dst) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void bg_copy_kernel(int64_t n, const float* __restrict__ src, float* __restrict__ dst) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx < n) dst[idx] = src[idx];
 }
 
 // rows [B * ss][C] -> NCHW [B][C][ss]
-__global__ __launch_bounds__(BG_THREADS) void bg_nchw_from_rows_kernel(int B, int C, int ss, const float* __restrict__ rows, float* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void bg_nchw_from_rows_kernel(int B, int C, int ss, const float* __restrict__ rows, float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * ss * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / ss, pix = r % ss;
   out[((int64_t)b * C + c) * ss + pix] = rows[idx];
@@ -76,10 +58,10 @@ __global__ __launch_bounds__(BG_THREADS) void bg_nchw_from_rows_kernel(int B, in
 
 // ------------------------------------------------------------------------------------------------------------------
 // stem: 3 x 3 stride 2 over the NCHW image of even side S, TF-SAME = no padding before, one row / column after
-__global__ __launch_bounds__(BG_THREADS) void bg_stem_fwd_kernel(int B, int S, int C, const float* __restrict__ img, const float* __restrict__ w,
+__global__ __launch_bounds__(GD_THREADS) void bg_stem_fwd_kernel(int B, int S, int C, const float* __restrict__ img, const float* __restrict__ w,
                                                                  const float* __restrict__ bn, float* __restrict__ Z, float* __restrict__ A) {
   const int s = S >> 1;
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * s * s * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / (s * s), pix = r % (s * s), oy = pix / s, ox = pix % s;
   float acc = 0.0f;
@@ -92,16 +74,16 @@ __global__ __launch_bounds__(BG_THREADS) void bg_stem_fwd_kernel(int B, int S, i
         const int y = 2 * oy + i, x = 2 * ox + j;
         if (y < S && x < S) acc = fmaf(w[c * 27 + ci * 9 + i * 3 + j], img[((int64_t)(b * 3 + ci) * S + y) * S + x], acc);
       }
-  const float v = bg_bn_apply(bg_bn_load(bn, C, c), acc);
+  const float v = gd_bn_apply(gd_bn_load(bn, C, c), acc);
   Z[idx] = acc;
-  A[idx] = v * bg_sigmoid(v);
+  A[idx] = v * gd_sigmoid(v);
 }
 
 // d W[c][ci][i][j] partials: one thread = (tile of output rows, channel)
-__global__ __launch_bounds__(BG_THREADS) void bg_stem_wgrad_kernel(int B, int S, int C, int R, int tile_rows, const float* __restrict__ dZ,
+__global__ __launch_bounds__(GD_THREADS) void bg_stem_wgrad_kernel(int B, int S, int C, int R, int tile_rows, const float* __restrict__ dZ,
                                                                    const float* __restrict__ img, float* __restrict__ part) {
   const int s = S >> 1, ss = s * s;
-  const int64_t gid = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int tile = (int)(gid / C), c = (int)(gid % C);
   const int r0 = tile * tile_rows, r1 = min(R, r0 + tile_rows);
   if (r0 >= R) return;
@@ -126,10 +108,10 @@ __global__ __launch_bounds__(BG_THREADS) void bg_stem_wgrad_kernel(int B, int S,
 }
 
 // image gradient in gather form: every image element adds the outputs whose window holds it, (i, j, channel) in order
-__global__ __launch_bounds__(BG_THREADS) void bg_stem_dgrad_kernel(int B, int S, int C, const float* __restrict__ dZ, const float* __restrict__ w,
+__global__ __launch_bounds__(GD_THREADS) void bg_stem_dgrad_kernel(int B, int S, int C, const float* __restrict__ dZ, const float* __restrict__ w,
                                                                    float* __restrict__ dimg) {
   const int s = S >> 1;
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * 3 * S * S) return;
   const int x = (int)(idx % S), y = (int)((idx / S) % S), ci = (int)((idx / ((int64_t)S * S)) % 3), b = (int)(idx / ((int64_t)3 * S * S));
   float acc = 0.0f;
@@ -148,10 +130,10 @@ __global__ __launch_bounds__(BG_THREADS) void bg_stem_dgrad_kernel(int B, int S,
 
 // ------------------------------------------------------------------------------------------------------------------
 // depthwise K x K, stride 1 / 2, TF-SAME (pad rows / columns before; the rest falls after), fused with bn1 + swish
-template <int K> __global__ __launch_bounds__(BG_THREADS) void bg_dw_fwd_kernel(int B, int si, int so, int stride, int pad, int C, const float* __restrict__ X,
+template <int K> __global__ __launch_bounds__(GD_THREADS) void bg_dw_fwd_kernel(int B, int si, int so, int stride, int pad, int C, const float* __restrict__ X,
                                                                                 const float* __restrict__ w, const float* __restrict__ bn,
                                                                                 float* __restrict__ Z, float* __restrict__ A) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * so * so * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / (so * so), pix = r % (so * so), oy = pix / so, ox = pix % so;
   float acc = 0.0f;
@@ -166,16 +148,16 @@ template <int K> __global__ __launch_bounds__(BG_THREADS) void bg_dw_fwd_kernel(
       acc = fmaf(w[c * K * K + i * K + j], X[((int64_t)(b * si + y) * si + x) * C + c], acc);
     }
   }
-  const float v = bg_bn_apply(bg_bn_load(bn, C, c), acc);
+  const float v = gd_bn_apply(gd_bn_load(bn, C, c), acc);
   Z[idx] = acc;
-  A[idx] = v * bg_sigmoid(v);
+  A[idx] = v * gd_sigmoid(v);
 }
 
 // depthwise weight gradient: K * K sums per channel over all output pixels; one thread = (tile of output rows, channel)
-template <int K> __global__ __launch_bounds__(BG_THREADS) void bg_dw_wgrad_kernel(int si, int so, int stride, int pad, int C, int R, int tile_rows,
+template <int K> __global__ __launch_bounds__(GD_THREADS) void bg_dw_wgrad_kernel(int si, int so, int stride, int pad, int C, int R, int tile_rows,
                                                                                   const float* __restrict__ dZ, const float* __restrict__ X, float* __restrict__ part) {
   const int ss = so * so;
-  const int64_t gid = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int tile = (int)(gid / C), c = (int)(gid % C);
   const int r0 = tile * tile_rows, r1 = min(R, r0 + tile_rows);
   if (r0 >= R) return;
@@ -202,9 +184,9 @@ template <int K> __global__ __launch_bounds__(BG_THREADS) void bg_dw_wgrad_kerne
 }
 
 // depthwise data gradient in gather form: input (y, x) belongs to the window of output o at tap i where o * stride = y + pad - i
-template <int K> __global__ __launch_bounds__(BG_THREADS) void bg_dw_dgrad_kernel(int B, int si, int so, int stride, int pad, int C, const float* __restrict__ dZ,
+template <int K> __global__ __launch_bounds__(GD_THREADS) void bg_dw_dgrad_kernel(int B, int si, int so, int stride, int pad, int C, const float* __restrict__ dZ,
                                                                                   const float* __restrict__ w, float* __restrict__ dX) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * si * si * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / (si * si), pix = r % (si * si), y = pix / si, x = pix % si;
   float acc = 0.0f;
@@ -224,22 +206,22 @@ template <int K> __global__ __launch_bounds__(BG_THREADS) void bg_dw_dgrad_kerne
 
 // ------------------------------------------------------------------------------------------------------------------
 // squeeze-excite.  Per (image, chunk of rows, channel) sums in row order; FWD: of a1, else of d xg * a1 with a1 = swish(bn1(z1))
-template <bool FWD> __global__ __launch_bounds__(BG_THREADS) void bg_se_sum_kernel(int B, int ss, int C, int nchunk, int chunk_rows, const float* __restrict__ A,
+template <bool FWD> __global__ __launch_bounds__(GD_THREADS) void bg_se_sum_kernel(int B, int ss, int C, int nchunk, int chunk_rows, const float* __restrict__ A,
                                                                                    const float* __restrict__ Z, const float* __restrict__ bn, float* __restrict__ part) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * nchunk * C) return;
   const int c = (int)(idx % C), q = (int)((idx / C) % nchunk), b = (int)(idx / ((int64_t)C * nchunk));
   const int r0 = q * chunk_rows, r1 = min(ss, r0 + chunk_rows);
-  BGBn n{};
-  if (!FWD) n = bg_bn_load(bn, C, c);
+  GDBn n{};
+  if (!FWD) n = gd_bn_load(bn, C, c);
   float s = 0.0f;
   for (int r = r0; r < r1; r++) {
     const int64_t at = ((int64_t)b * ss + r) * C + c;
     if (FWD) {
       s += A[at];
     } else {
-      const float v = bg_bn_apply(n, Z[at]);
-      s = fmaf(A[at], v * bg_sigmoid(v), s);
+      const float v = gd_bn_apply(n, Z[at]);
+      s = fmaf(A[at], v * gd_sigmoid(v), s);
     }
   }
   part[idx] = s;
@@ -253,13 +235,13 @@ __device__ __forceinline__ float bg_wave_sum(float a) {
 }
 
 // one workgroup per image: the means (second pass over the chunks in double), the two small FCs (VALU), the gate
-__global__ __launch_bounds__(BG_THREADS) void bg_se_fc_kernel(int ss, int C, int se, int nchunk, const float* __restrict__ part, const float* __restrict__ wr,
+__global__ __launch_bounds__(GD_THREADS) void bg_se_fc_kernel(int ss, int C, int se, int nchunk, const float* __restrict__ part, const float* __restrict__ wr,
                                                               const float* __restrict__ br, const float* __restrict__ we, const float* __restrict__ be,
                                                               float* __restrict__ M, float* __restrict__ Rr, float* __restrict__ G) {
   __shared__ float sm[BG_MAX_CEXP];
   __shared__ float sh[BG_MAX_SE];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  for (int c = t; c < C; c += BG_THREADS) {
+  for (int c = t; c < C; c += GD_THREADS) {
     double s = 0.0;
     for (int q = 0; q < nchunk; q++) s += (double)part[((int64_t)b * nchunk + q) * C + c];
     const float m = (float)(s / (double)ss);
@@ -267,39 +249,39 @@ __global__ __launch_bounds__(BG_THREADS) void bg_se_fc_kernel(int ss, int C, int
     M[(int64_t)b * C + c] = m;
   }
   __syncthreads();
-  for (int j = wv; j < se; j += BG_THREADS / 64) {
+  for (int j = wv; j < se; j += GD_THREADS / 64) {
     float a = 0.0f;
     for (int c = lane; c < C; c += 64) a = fmaf(wr[(int64_t)j * C + c], sm[c], a);
     a = bg_wave_sum(a);
     if (lane == 0) {
       const float r = a + br[j];
       Rr[b * se + j] = r;
-      sh[j] = r * bg_sigmoid(r);
+      sh[j] = r * gd_sigmoid(r);
     }
   }
   __syncthreads();
-  for (int c = t; c < C; c += BG_THREADS) {
+  for (int c = t; c < C; c += GD_THREADS) {
     float l = be[c];
     for (int j = 0; j < se; j++) l = fmaf(we[(int64_t)c * se + j], sh[j], l);
-    G[(int64_t)b * C + c] = bg_sigmoid(l);
+    G[(int64_t)b * C + c] = gd_sigmoid(l);
   }
 }
 
-__global__ __launch_bounds__(BG_THREADS) void bg_gate_kernel(int64_t total, int ss, int C, const float* __restrict__ A, const float* __restrict__ G, float* __restrict__ XG) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void bg_gate_kernel(int64_t total, int ss, int C, const float* __restrict__ A, const float* __restrict__ G, float* __restrict__ XG) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= total) return;
   const int r = (int)(idx / C), c = (int)(idx % C);
   XG[idx] = A[idx] * G[(int64_t)(r / ss) * C + c];
 }
 
 // one workgroup per image: d l = (sum d xg * a1) * g (1 - g), d r = (We^T d l) * swish'(r), d m / ss = (Wr^T d r) / ss
-__global__ __launch_bounds__(BG_THREADS) void bg_se_bwd_kernel(int ss, int C, int se, int nchunk, const float* __restrict__ part, const float* __restrict__ wr,
+__global__ __launch_bounds__(GD_THREADS) void bg_se_bwd_kernel(int ss, int C, int se, int nchunk, const float* __restrict__ part, const float* __restrict__ wr,
                                                                const float* __restrict__ we, const float* __restrict__ Rr, const float* __restrict__ G,
                                                                float* __restrict__ DL, float* __restrict__ DR, float* __restrict__ DM) {
   __shared__ float sdl[BG_MAX_CEXP];
   __shared__ float sdr[BG_MAX_SE];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  for (int c = t; c < C; c += BG_THREADS) {
+  for (int c = t; c < C; c += GD_THREADS) {
     double s = 0.0;
     for (int q = 0; q < nchunk; q++) s += (double)part[((int64_t)b * nchunk + q) * C + c];
     const float g = G[(int64_t)b * C + c], dl = (float)s * (g * (1.0f - g));
@@ -307,19 +289,19 @@ __global__ __launch_bounds__(BG_THREADS) void bg_se_bwd_kernel(int ss, int C, in
     DL[(int64_t)b * C + c] = dl;
   }
   __syncthreads();
-  for (int j = wv; j < se; j += BG_THREADS / 64) {
+  for (int j = wv; j < se; j += GD_THREADS / 64) {
     float a = 0.0f;
     for (int c = lane; c < C; c += 64) a = fmaf(we[(int64_t)c * se + j], sdl[c], a);
     a = bg_wave_sum(a);
     if (lane == 0) {
-      const float dr = a * bg_swish_grad(Rr[b * se + j]);
+      const float dr = a * gd_swish_grad(Rr[b * se + j]);
       sdr[j] = dr;
       DR[b * se + j] = dr;
     }
   }
   __syncthreads();
   const float inv = 1.0f / (float)ss;
-  for (int c = t; c < C; c += BG_THREADS) {
+  for (int c = t; c < C; c += GD_THREADS) {
     float a = 0.0f;
     for (int j = 0; j < se; j++) a = fmaf(wr[(int64_t)j * C + c], sdr[j], a);
     DM[(int64_t)b * C + c] = a * inv;
@@ -328,9 +310,9 @@ __global__ __launch_bounds__(BG_THREADS) void bg_se_bwd_kernel(int ss, int C, in
 
 // the four squeeze-excite tensors' gradients (se_reduce weight [se][C], bias [se], se_expand weight [C][se], bias [C], contiguous
 // in that order): sums over the images in order, in double
-__global__ __launch_bounds__(BG_THREADS) void bg_se_wgrad_kernel(int B, int C, int se, const float* __restrict__ M, const float* __restrict__ Rr,
+__global__ __launch_bounds__(GD_THREADS) void bg_se_wgrad_kernel(int B, int C, int se, const float* __restrict__ M, const float* __restrict__ Rr,
                                                                  const float* __restrict__ DL, const float* __restrict__ DR, float* __restrict__ dst) {
-  const int64_t idx = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int64_t n0 = (int64_t)se * C, n1 = n0 + se, n2 = n1 + (int64_t)C * se, n3 = n2 + C;
   if (idx >= n3) return;
   double s = 0.0;
@@ -344,7 +326,7 @@ __global__ __launch_bounds__(BG_THREADS) void bg_se_wgrad_kernel(int B, int C, i
     const int c = (int)((idx - n1) / se), j = (int)((idx - n1) % se);
     for (int b = 0; b < B; b++) {
       const float r = Rr[b * se + j];
-      s += (double)(DL[(int64_t)b * C + c] * (r * bg_sigmoid(r)));
+      s += (double)(DL[(int64_t)b * C + c] * (r * gd_sigmoid(r)));
     }
   } else {
     const int c = (int)(idx - n2);
@@ -366,82 +348,35 @@ struct BGGemmArgs {
 //   FWD     A = x rows (k contiguous), B = W [J][K] (k contiguous); z = C -> C, act: swish(bn(z)) -> C2, else bn(z) * scale + res -> C2
 //   DATA    A = d z rows (k contiguous), B = W [K][J] (j contiguous, W un-transposed) -> C rows
 //   WGRAD   A = d z rows read as (k = row, i = column), B = x rows (k = row); rows [z * slab_rows, ...) of K -> C[z][I][J]
-template <int MODE> __global__ __launch_bounds__(BG_THREADS) void bg_gemm_kernel(BGGemmArgs a) {
-  __shared__ __attribute__((aligned(16))) float As[BG_BK][BG_LDS_PITCH];
-  __shared__ __attribute__((aligned(16))) float Bs[BG_BK][BG_LDS_PITCH];
+template <int MODE> __global__ __launch_bounds__(GD_THREADS) void bg_gemm_kernel(BGGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[GD_BK][GD_LDS_PITCH];
+  __shared__ __attribute__((aligned(16))) float Bs[GD_BK][GD_LDS_PITCH];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int I = a.I, J = a.J;
-  const int i0 = (int)(blockIdx.x / a.ntn) * BG_BM, j0 = (int)(blockIdx.x % a.ntn) * BG_BN;
+  const int i0 = (int)(blockIdx.x / a.ntn) * GD_BM, j0 = (int)(blockIdx.x % a.ntn) * GD_BN;
   if (i0 >= I || j0 >= J) return;                          // uniform over the workgroup
   int k_begin = 0, k_end = a.K;
   if (MODE == BG_WGRAD) { k_begin = blockIdx.z * a.slab_rows; k_end = min(a.K, k_begin + a.slab_rows); }
-  const float* __restrict__ A = a.A;
-  const float* __restrict__ Bm = a.Bm;
-  const int lda = a.lda, ldb = a.ldb;
-  bg_f32x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) acc[j] = bg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  for (int k0 = k_begin; k0 < k_end; k0 += BG_BK) {
-    float4 va = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vb = va;
-    if (MODE != BG_WGRAD) {                                 // k contiguous: thread = (row i, four k)
-      const int i = lane, kq = wv * 4;
-      if (i0 + i < I && k0 + kq < k_end) va = *reinterpret_cast<const float4*>(A + (int64_t)(i0 + i) * lda + k0 + kq);
-      As[kq + 0][i] = va.x; As[kq + 1][i] = va.y; As[kq + 2][i] = va.z; As[kq + 3][i] = va.w;
-    } else {                                                // i contiguous: thread = (k, four i)
-      const int k = t >> 4, q = (t & 15) * 4;
-      if (k0 + k < k_end && i0 + q < I) va = *reinterpret_cast<const float4*>(A + (int64_t)(k0 + k) * lda + i0 + q);
-      *reinterpret_cast<float4*>(&As[k][q]) = va;
-    }
+  f32x4 acc[4];
+  gd_gemm_tile<MODE == BG_WGRAD ? GD_ROW_CONTIG : GD_K_CONTIG, MODE == BG_FWD ? GD_K_CONTIG : GD_ROW_CONTIG>(
+      As, Bs, acc, a.A, a.lda, a.Bm, a.ldb, i0, I, j0, J, k_begin, k_end, k_end, t, lane, wv);
+  gd_acc_visit(acc, i0, I, j0, J, lane, wv, [=](int m, int n, float v, const GDBn& q) {
     if (MODE == BG_FWD) {
-      const int j = lane, kq = wv * 4;
-      if (j0 + j < J && k0 + kq < k_end) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(j0 + j) * ldb + k0 + kq);
-      Bs[kq + 0][j] = vb.x; Bs[kq + 1][j] = vb.y; Bs[kq + 2][j] = vb.z; Bs[kq + 3][j] = vb.w;
+      const int64_t at = (int64_t)m * a.ldc + n;
+      float y = gd_bn_apply(q, v);
+      if (a.act) {
+        y = y * gd_sigmoid(y);
+      } else if (a.res) {
+        y = fmaf(y, a.scale ? a.scale[m / a.ss] : 1.0f, a.res[at]);
+      }
+      a.C[at] = v;
+      a.C2[at] = y;
+    } else if (MODE == BG_DATA) {
+      a.C[(int64_t)m * a.ldc + n] = v;
     } else {
-      const int k = t >> 4, q = (t & 15) * 4;
-      if (k0 + k < k_end && j0 + q < J) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(k0 + k) * ldb + j0 + q);
-      *reinterpret_cast<float4*>(&Bs[k][q]) = vb;
+      a.C[((int64_t)blockIdx.z * I + m) * J + n] = v;
     }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < BG_BK / 4; kk++) {
-      const float av = As[kk * 4 + (lane >> 4)][wv * 16 + (lane & 15)];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float bv = Bs[kk * 4 + (lane >> 4)][j * 16 + (lane & 15)];
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // accumulator element (reg): row 4 * (lane >> 4) + reg, column lane & 15
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int n = j0 + j * 16 + (lane & 15);
-    if (n >= J) continue;
-    BGBn q{};
-    if (MODE == BG_FWD) q = bg_bn_load(a.bn, J, n);
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      const int m = i0 + wv * 16 + (lane >> 4) * 4 + reg;
-      if (m >= I) continue;
-      const float v = acc[j][reg];
-      if (MODE == BG_FWD) {
-        const int64_t at = (int64_t)m * a.ldc + n;
-        float y = bg_bn_apply(q, v);
-        if (a.act) {
-          y = y * bg_sigmoid(y);
-        } else if (a.res) {
-          y = fmaf(y, a.scale ? a.scale[m / a.ss] : 1.0f, a.res[at]);
-        }
-        a.C[at] = v;
-        a.C2[at] = y;
-      } else if (MODE == BG_DATA) {
-        a.C[(int64_t)m * a.ldc + n] = v;
-      } else {
-        a.C[((int64_t)blockIdx.z * I + m) * J + n] = v;
-      }
-    }
-  }
+  }, [=](int n) { return MODE == BG_FWD ? gd_bn_load(a.bn, J, n) : GDBn{}; });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -454,13 +389,13 @@ struct BGOutArgs {
   const float* Z; const float* bn;
   float* dY; float* dZ; float* pgamma; float* pbeta;
 };
-__global__ __launch_bounds__(BG_THREADS) void bg_out_bwd_kernel(BGOutArgs a) {
+__global__ __launch_bounds__(GD_THREADS) void bg_out_bwd_kernel(BGOutArgs a) {
   const int C = a.C, ss = a.ss;
-  const int64_t gid = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int tile = (int)(gid / C), c = (int)(gid % C);
   const int r0 = tile * a.tile_rows, r1 = min(a.R, r0 + a.tile_rows);
   if (r0 >= a.R) return;
-  const BGBn q = bg_bn_load(a.bn, C, c);
+  const GDBn q = gd_bn_load(a.bn, C, c);
   float ag = 0.0f, ab = 0.0f;
   for (int r = r0; r < r1; r++) {
     const int b = r / ss, pix = r % ss;
@@ -486,20 +421,20 @@ struct BGActArgs {
   float* G; const float* Z; const float* bn; const float* gate; const float* dmean;
   float* pgamma; float* pbeta;
 };
-__global__ __launch_bounds__(BG_THREADS) void bg_act_bwd_kernel(BGActArgs a) {
+__global__ __launch_bounds__(GD_THREADS) void bg_act_bwd_kernel(BGActArgs a) {
   const int C = a.C, ss = a.ss;
-  const int64_t gid = (int64_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int tile = (int)(gid / C), c = (int)(gid % C);
   const int r0 = tile * a.tile_rows, r1 = min(a.R, r0 + a.tile_rows);
   if (r0 >= a.R) return;
-  const BGBn q = bg_bn_load(a.bn, C, c);
+  const GDBn q = gd_bn_load(a.bn, C, c);
   float ag = 0.0f, ab = 0.0f;
   for (int r = r0; r < r1; r++) {
     const int64_t at = (int64_t)r * C + c;
     float g = a.G[at];
     if (a.gate) { const int64_t bc = (int64_t)(r / ss) * C + c; g = fmaf(g, a.gate[bc], a.dmean[bc]); }
     const float zh = (a.Z[at] - q.mean) * q.rstd, v = fmaf(zh, q.gamma, q.beta);
-    const float dv = g * bg_swish_grad(v);
+    const float dv = g * gd_swish_grad(v);
     ag = fmaf(dv, zh, ag);
     ab += dv;
     a.G[at] = dv * q.gamma * q.rstd;
@@ -509,45 +444,10 @@ __global__ __launch_bounds__(BG_THREADS) void bg_act_bwd_kernel(BGActArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// second pass: element e of job j = the sum of its partials src[e + k * stride], k < nparts, added in double in a FIXED
-// order: 16 threads share an element, thread j adds the partials j, j + 16, ... in index order, then thread 0 adds the 16
-// sums in order 0..15 and rounds once (the scheme of ng_reduce_kernel).  src == NULL: the element is zero (running statistics).
-#define BG_RED_E 16
-#define BG_RED_K 16
-#define BG_RED_JOBS 4
-struct BGRedJob { const float* src; float* dst; int64_t count, stride; int nparts; };
-struct BGReduceArgs { BGRedJob j[BG_RED_JOBS]; };
-static_assert(BG_RED_E * BG_RED_K == BG_THREADS, "one reduce workgroup = 16 elements x 16 partial lanes");
-__global__ __launch_bounds__(BG_THREADS) void bg_reduce_kernel(BGReduceArgs a) {
-  __shared__ double part[BG_RED_K][BG_RED_E + 1];
-  const BGRedJob& job = a.j[blockIdx.y];
-  const int el = threadIdx.x % BG_RED_E, kl = threadIdx.x / BG_RED_E;
-  const int64_t e = (int64_t)blockIdx.x * BG_RED_E + el;
-  if ((int64_t)blockIdx.x * BG_RED_E >= job.count) return;  // uniform over the workgroup
-  const bool live = e < job.count;
-  double s = 0.0;
-  if (live && job.src)
-    for (int k = kl; k < job.nparts; k += BG_RED_K) s += (double)job.src[e + k * job.stride];
-  part[kl][el] = s;
-  __syncthreads();
-  if (kl == 0 && live) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < BG_RED_K; j++) t += part[j][el];
-    job.dst[e] = (float)t;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
 // host side
-static inline unsigned bg_blocks(int64_t n) { return (unsigned)((n + BG_THREADS - 1) / BG_THREADS); }
 static inline int bg_tile_rows(int R) { return R <= 4096 ? 8 : R <= 65536 ? 32 : 64; }
 static inline int bg_ntiles(int R) { const int tr = bg_tile_rows(R); return (R + tr - 1) / tr; }
-static inline void bg_slabs(int R, int* slab_rows, int* nslab) {
-  int ns = R / 512; if (ns < 1) ns = 1; if (ns > BG_MAX_SLABS) ns = BG_MAX_SLABS;
-  *slab_rows = ((R + ns - 1) / ns + BG_BK - 1) / BG_BK * BG_BK;
-  *nslab = (R + *slab_rows - 1) / *slab_rows;
-}
+static inline void bg_slabs(int R, int* slab_rows, int* nslab) { gd_slabs(R, BG_MAX_SLABS, slab_rows, nslab); }
 static inline void bg_chunks(int ss, int* chunk_rows, int* nchunk) {
   int nc = (ss + 31) / 32; if (nc > 128) nc = 128;
   *chunk_rows = (ss + nc - 1) / nc;
@@ -664,24 +564,24 @@ inline const float* bg_pa(const BGPlan& p, const float* ws, int i, int64_t flat)
 inline const float* bg_pb(const BGPlan& p, const float* ws, int i, int64_t flat) { return ws + p.b[i].q_b + (flat - p.b[i].p_w2); }
 
 void bg_gemm(int mode, BGGemmArgs m, int nslab, hipStream_t st) {
-  const int ntm = (m.I + BG_BM - 1) / BG_BM;
-  m.ntn = (m.J + BG_BN - 1) / BG_BN;
-  if (mode == BG_FWD) hipLaunchKernelGGL(bg_gemm_kernel<BG_FWD>, dim3(ntm * m.ntn), dim3(BG_THREADS), 0, st, m);
-  else if (mode == BG_DATA) hipLaunchKernelGGL(bg_gemm_kernel<BG_DATA>, dim3(ntm * m.ntn), dim3(BG_THREADS), 0, st, m);
-  else hipLaunchKernelGGL(bg_gemm_kernel<BG_WGRAD>, dim3(ntm * m.ntn, 1, nslab), dim3(BG_THREADS), 0, st, m);
+  const int ntm = (m.I + GD_BM - 1) / GD_BM;
+  m.ntn = (m.J + GD_BN - 1) / GD_BN;
+  if (mode == BG_FWD) hipLaunchKernelGGL(bg_gemm_kernel<BG_FWD>, dim3(ntm * m.ntn), dim3(GD_THREADS), 0, st, m);
+  else if (mode == BG_DATA) hipLaunchKernelGGL(bg_gemm_kernel<BG_DATA>, dim3(ntm * m.ntn), dim3(GD_THREADS), 0, st, m);
+  else hipLaunchKernelGGL(bg_gemm_kernel<BG_WGRAD>, dim3(ntm * m.ntn, 1, nslab), dim3(GD_THREADS), 0, st, m);
 }
 
-void bg_reduce(const BGReduceArgs& rd, hipStream_t st) {
+void bg_reduce(const GDReduceArgs<BG_RED_JOBS>& rd, hipStream_t st) {
   int64_t most = 1;
   for (int j = 0; j < BG_RED_JOBS; j++) most = std::max(most, rd.j[j].count);
-  hipLaunchKernelGGL(bg_reduce_kernel, dim3((unsigned)((most + BG_RED_E - 1) / BG_RED_E), BG_RED_JOBS), dim3(BG_THREADS), 0, st, rd);
+  hipLaunchKernelGGL(gd_reduce_kernel<BG_RED_JOBS>, dim3((unsigned)((most + GD_RED_E - 1) / GD_RED_E), BG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
 }
 // BatchNorm column partials [tile][C] -> gamma, beta, zeros for the statistics
-void bg_bn_jobs(const BGPlan& p, float* ws, int R, int C, float* dbn, BGReduceArgs* rd, int at) {
+void bg_bn_jobs(const BGPlan& p, float* ws, int R, int C, float* dbn, GDReduceArgs<BG_RED_JOBS>* rd, int at) {
   const int T = bg_ntiles(R);
-  rd->j[at + 0] = BGRedJob{ws + p.o_pcol[0], dbn, C, C, T};
-  rd->j[at + 1] = BGRedJob{ws + p.o_pcol[1], dbn + C, C, C, T};
-  rd->j[at + 2] = BGRedJob{nullptr, dbn + 2 * C, 2 * C, 0, 0};
+  rd->j[at + 0] = GDRedJob{ws + p.o_pcol[0], dbn, C, C, T};
+  rd->j[at + 1] = GDRedJob{ws + p.o_pcol[1], dbn + C, C, C, T};
+  rd->j[at + 2] = GDRedJob{nullptr, dbn + 2 * C, 2 * C, 0, 0};
 }
 }  // namespace
 
@@ -697,12 +597,12 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
       pk.src[n] = b.p_first; pk.dst[n] = b.q_a; pk.len[n] = b.p_w2 - b.p_first; most = std::max(most, pk.len[n]); n++;
       pk.src[n] = b.p_w2; pk.dst[n] = b.q_b; pk.len[n] = b.p_end - b.p_w2; most = std::max(most, pk.len[n]); n++;
     }
-    hipLaunchKernelGGL(bg_pack_kernel, dim3(bg_blocks(most), n), dim3(BG_THREADS), 0, st, pk, params, ws);
+    hipLaunchKernelGGL(bg_pack_kernel, dim3(gd_blocks(most), n), dim3(GD_THREADS), 0, st, pk, params, ws);
   }
   const float* ps = ws + p.q_stem;
   const int64_t nimg = (int64_t)B * 3 * p.size * p.size;
-  hipLaunchKernelGGL(bg_copy_kernel, dim3(bg_blocks(nimg)), dim3(BG_THREADS), 0, st, nimg, image, ws + p.o_img);
-  hipLaunchKernelGGL(bg_stem_fwd_kernel, dim3(bg_blocks((int64_t)p.R0 * p.stem)), dim3(BG_THREADS), 0, st, B, p.size, p.stem, image, ps,
+  hipLaunchKernelGGL(bg_copy_kernel, dim3(gd_blocks(nimg)), dim3(GD_THREADS), 0, st, nimg, image, ws + p.o_img);
+  hipLaunchKernelGGL(bg_stem_fwd_kernel, dim3(gd_blocks((int64_t)p.R0 * p.stem)), dim3(GD_THREADS), 0, st, B, p.size, p.stem, image, ps,
                      ps + (p.p_bn_stem - p.p_stem), ws + p.o_zs, ws + p.o_as);
   const float* x = ws + p.o_as;
   for (int i = 0; i < p.nblocks; i++) {
@@ -717,18 +617,18 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
     }
     const int64_t nmid = (int64_t)b.R_out * b.cexp;
     if (b.k == 3)
-      hipLaunchKernelGGL(bg_dw_fwd_kernel<3>, dim3(bg_blocks(nmid)), dim3(BG_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, dwin,
+      hipLaunchKernelGGL(bg_dw_fwd_kernel<3>, dim3(gd_blocks(nmid)), dim3(GD_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, dwin,
                          bg_pa(p, ws, i, b.p_dw), bg_pa(p, ws, i, b.p_bn1), ws + b.o_z1, ws + p.o_a1);
     else
-      hipLaunchKernelGGL(bg_dw_fwd_kernel<5>, dim3(bg_blocks(nmid)), dim3(BG_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, dwin,
+      hipLaunchKernelGGL(bg_dw_fwd_kernel<5>, dim3(gd_blocks(nmid)), dim3(GD_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, dwin,
                          bg_pa(p, ws, i, b.p_dw), bg_pa(p, ws, i, b.p_bn1), ws + b.o_z1, ws + p.o_a1);
     int cr, nc;
     bg_chunks(ss, &cr, &nc);
-    hipLaunchKernelGGL(bg_se_sum_kernel<true>, dim3(bg_blocks((int64_t)B * nc * b.cexp)), dim3(BG_THREADS), 0, st, B, ss, b.cexp, nc, cr,
+    hipLaunchKernelGGL(bg_se_sum_kernel<true>, dim3(gd_blocks((int64_t)B * nc * b.cexp)), dim3(GD_THREADS), 0, st, B, ss, b.cexp, nc, cr,
                        (const float*)(ws + p.o_a1), (const float*)nullptr, (const float*)nullptr, ws + p.o_pse);
-    hipLaunchKernelGGL(bg_se_fc_kernel, dim3(B), dim3(BG_THREADS), 0, st, ss, b.cexp, b.se, nc, (const float*)(ws + p.o_pse), bg_pa(p, ws, i, b.p_wr),
+    hipLaunchKernelGGL(bg_se_fc_kernel, dim3(B), dim3(GD_THREADS), 0, st, ss, b.cexp, b.se, nc, (const float*)(ws + p.o_pse), bg_pa(p, ws, i, b.p_wr),
                        bg_pa(p, ws, i, b.p_br), bg_pa(p, ws, i, b.p_we), bg_pa(p, ws, i, b.p_be), ws + b.o_m, ws + b.o_r, ws + b.o_g);
-    hipLaunchKernelGGL(bg_gate_kernel, dim3(bg_blocks(nmid)), dim3(BG_THREADS), 0, st, nmid, ss, b.cexp, (const float*)(ws + p.o_a1),
+    hipLaunchKernelGGL(bg_gate_kernel, dim3(gd_blocks(nmid)), dim3(GD_THREADS), 0, st, nmid, ss, b.cexp, (const float*)(ws + p.o_a1),
                        (const float*)(ws + b.o_g), ws + b.o_xg);
     BGGemmArgs m{}; m.A = ws + b.o_xg; m.Bm = bg_pb(p, ws, i, b.p_w2); m.bn = bg_pb(p, ws, i, b.p_bn2); m.C = ws + b.o_z2; m.C2 = ws + b.o_y;
     m.I = b.R_out; m.J = b.cout; m.K = b.cexp; m.lda = b.cexp; m.ldb = b.cexp; m.ldc = b.cout; m.act = 0; m.ss = ss;
@@ -738,7 +638,7 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
   }
   for (int t = 0; t < 3; t++) {
     const BGBlock& b = p.b[p.taps[t]];
-    hipLaunchKernelGGL(bg_nchw_from_rows_kernel, dim3(bg_blocks((int64_t)b.R_out * b.cout)), dim3(BG_THREADS), 0, st, B, b.cout, b.s_out * b.s_out,
+    hipLaunchKernelGGL(bg_nchw_from_rows_kernel, dim3(gd_blocks((int64_t)b.R_out * b.cout)), dim3(GD_THREADS), 0, st, B, b.cout, b.s_out * b.s_out,
                        (const float*)(ws + b.o_y), taps[t]);
   }
 }
@@ -758,7 +658,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     for (int t = 0; t < 3; t++) if (p.taps[t] == i) oa.cot = grad_taps[t];
     if (b.skip && branch_scale) oa.scale = branch_scale + (int64_t)i * B;
     oa.Z = ws + b.o_z2; oa.bn = bg_pb(p, ws, i, b.p_bn2); oa.dY = ws + p.o_dy[i & 1]; oa.dZ = ws + p.o_dz2; oa.pgamma = pg; oa.pbeta = pb;
-    hipLaunchKernelGGL(bg_out_bwd_kernel, dim3(bg_blocks((int64_t)bg_ntiles(b.R_out) * b.cout)), dim3(BG_THREADS), 0, st, oa);
+    hipLaunchKernelGGL(bg_out_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cout)), dim3(GD_THREADS), 0, st, oa);
     // project conv
     BGGemmArgs md{}; md.A = ws + p.o_dz2; md.Bm = bg_pb(p, ws, i, b.p_w2); md.C = ws + p.o_dxg; md.I = b.R_out; md.J = b.cexp; md.K = b.cout;
     md.lda = b.cout; md.ldb = b.cexp; md.ldc = b.cexp;
@@ -769,43 +669,43 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     mw.slab_rows = sr;
     bg_gemm(BG_WGRAD, mw, ns, st);
     {
-      BGReduceArgs rd{};
-      rd.j[0] = BGRedJob{ws + p.o_pw, grad_params + b.p_w2, (int64_t)b.cout * b.cexp, (int64_t)b.cout * b.cexp, ns};
+      GDReduceArgs<BG_RED_JOBS> rd{};
+      rd.j[0] = GDRedJob{ws + p.o_pw, grad_params + b.p_w2, (int64_t)b.cout * b.cexp, (int64_t)b.cout * b.cexp, ns};
       bg_bn_jobs(p, ws, b.R_out, b.cout, grad_params + b.p_bn2, &rd, 1);
       bg_reduce(rd, st);
     }
     // squeeze-excite
     int cr, nc;
     bg_chunks(ss, &cr, &nc);
-    hipLaunchKernelGGL(bg_se_sum_kernel<false>, dim3(bg_blocks((int64_t)B * nc * b.cexp)), dim3(BG_THREADS), 0, st, B, ss, b.cexp, nc, cr,
+    hipLaunchKernelGGL(bg_se_sum_kernel<false>, dim3(gd_blocks((int64_t)B * nc * b.cexp)), dim3(GD_THREADS), 0, st, B, ss, b.cexp, nc, cr,
                        (const float*)(ws + p.o_dxg), (const float*)(ws + b.o_z1), bg_pa(p, ws, i, b.p_bn1), ws + p.o_pse);
-    hipLaunchKernelGGL(bg_se_bwd_kernel, dim3(B), dim3(BG_THREADS), 0, st, ss, b.cexp, b.se, nc, (const float*)(ws + p.o_pse), bg_pa(p, ws, i, b.p_wr),
+    hipLaunchKernelGGL(bg_se_bwd_kernel, dim3(B), dim3(GD_THREADS), 0, st, ss, b.cexp, b.se, nc, (const float*)(ws + p.o_pse), bg_pa(p, ws, i, b.p_wr),
                        bg_pa(p, ws, i, b.p_we), (const float*)(ws + b.o_r), (const float*)(ws + b.o_g), ws + p.o_dl, ws + p.o_dr, ws + p.o_dm);
-    hipLaunchKernelGGL(bg_se_wgrad_kernel, dim3(bg_blocks(b.p_w2 - b.p_wr)), dim3(BG_THREADS), 0, st, B, b.cexp, b.se, (const float*)(ws + b.o_m),
+    hipLaunchKernelGGL(bg_se_wgrad_kernel, dim3(gd_blocks(b.p_w2 - b.p_wr)), dim3(GD_THREADS), 0, st, B, b.cexp, b.se, (const float*)(ws + b.o_m),
                        (const float*)(ws + b.o_r), (const float*)(ws + p.o_dl), (const float*)(ws + p.o_dr), grad_params + b.p_wr);
     // gate, swish, bn1: d z1 in place of d xg
     BGActArgs aa{}; aa.ss = ss; aa.C = b.cexp; aa.R = b.R_out; aa.tile_rows = bg_tile_rows(b.R_out);
     aa.G = ws + p.o_dxg; aa.Z = ws + b.o_z1; aa.bn = bg_pa(p, ws, i, b.p_bn1); aa.gate = ws + b.o_g; aa.dmean = ws + p.o_dm; aa.pgamma = pg; aa.pbeta = pb;
-    hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(bg_blocks((int64_t)bg_ntiles(b.R_out) * b.cexp)), dim3(BG_THREADS), 0, st, aa);
+    hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cexp)), dim3(GD_THREADS), 0, st, aa);
     // depthwise
     const float* dwin = b.expand ? ws + b.o_a0 : x;
     float* ddw = b.expand ? ws + p.o_da0 : ws + p.o_dx;
-    const unsigned gw = bg_blocks((int64_t)bg_ntiles(b.R_out) * b.cexp), gd = bg_blocks((int64_t)b.R_in * b.cexp);
+    const unsigned gw = gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cexp), gd = gd_blocks((int64_t)b.R_in * b.cexp);
     if (b.k == 3) {
-      hipLaunchKernelGGL(bg_dw_wgrad_kernel<3>, dim3(gw), dim3(BG_THREADS), 0, st, b.s_in, b.s_out, b.stride, pad, b.cexp, b.R_out, bg_tile_rows(b.R_out),
+      hipLaunchKernelGGL(bg_dw_wgrad_kernel<3>, dim3(gw), dim3(GD_THREADS), 0, st, b.s_in, b.s_out, b.stride, pad, b.cexp, b.R_out, bg_tile_rows(b.R_out),
                          (const float*)(ws + p.o_dxg), dwin, ws + p.o_pdw);
-      hipLaunchKernelGGL(bg_dw_dgrad_kernel<3>, dim3(gd), dim3(BG_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, (const float*)(ws + p.o_dxg),
+      hipLaunchKernelGGL(bg_dw_dgrad_kernel<3>, dim3(gd), dim3(GD_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, (const float*)(ws + p.o_dxg),
                          bg_pa(p, ws, i, b.p_dw), ddw);
     } else {
-      hipLaunchKernelGGL(bg_dw_wgrad_kernel<5>, dim3(gw), dim3(BG_THREADS), 0, st, b.s_in, b.s_out, b.stride, pad, b.cexp, b.R_out, bg_tile_rows(b.R_out),
+      hipLaunchKernelGGL(bg_dw_wgrad_kernel<5>, dim3(gw), dim3(GD_THREADS), 0, st, b.s_in, b.s_out, b.stride, pad, b.cexp, b.R_out, bg_tile_rows(b.R_out),
                          (const float*)(ws + p.o_dxg), dwin, ws + p.o_pdw);
-      hipLaunchKernelGGL(bg_dw_dgrad_kernel<5>, dim3(gd), dim3(BG_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, (const float*)(ws + p.o_dxg),
+      hipLaunchKernelGGL(bg_dw_dgrad_kernel<5>, dim3(gd), dim3(GD_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, (const float*)(ws + p.o_dxg),
                          bg_pa(p, ws, i, b.p_dw), ddw);
     }
     {
-      BGReduceArgs rd{};
+      GDReduceArgs<BG_RED_JOBS> rd{};
       const int64_t n = (int64_t)b.cexp * b.k * b.k;
-      rd.j[0] = BGRedJob{ws + p.o_pdw, grad_params + b.p_dw, n, n, bg_ntiles(b.R_out)};
+      rd.j[0] = GDRedJob{ws + p.o_pdw, grad_params + b.p_dw, n, n, bg_ntiles(b.R_out)};
       bg_bn_jobs(p, ws, b.R_out, b.cexp, grad_params + b.p_bn1, &rd, 1);
       bg_reduce(rd, st);
     }
@@ -813,7 +713,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     if (b.expand) {
       BGActArgs ea{}; ea.ss = b.s_in * b.s_in; ea.C = b.cexp; ea.R = b.R_in; ea.tile_rows = bg_tile_rows(b.R_in);
       ea.G = ws + p.o_da0; ea.Z = ws + b.o_z0; ea.bn = bg_pa(p, ws, i, b.p_bn0); ea.pgamma = pg; ea.pbeta = pb;
-      hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(bg_blocks((int64_t)bg_ntiles(b.R_in) * b.cexp)), dim3(BG_THREADS), 0, st, ea);
+      hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_in) * b.cexp)), dim3(GD_THREADS), 0, st, ea);
       bg_slabs(b.R_in, &sr, &ns);
       BGGemmArgs ew{}; ew.A = ws + p.o_da0; ew.Bm = x; ew.C = ws + p.o_pw; ew.I = b.cexp; ew.J = b.cin; ew.K = b.R_in; ew.lda = b.cexp; ew.ldb = b.cin;
       ew.slab_rows = sr;
@@ -821,8 +721,8 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
       BGGemmArgs ed{}; ed.A = ws + p.o_da0; ed.Bm = bg_pa(p, ws, i, b.p_w0); ed.C = ws + p.o_dx; ed.I = b.R_in; ed.J = b.cin; ed.K = b.cexp;
       ed.lda = b.cexp; ed.ldb = b.cin; ed.ldc = b.cin;
       bg_gemm(BG_DATA, ed, 1, st);
-      BGReduceArgs rd{};
-      rd.j[0] = BGRedJob{ws + p.o_pw, grad_params + b.p_w0, (int64_t)b.cexp * b.cin, (int64_t)b.cexp * b.cin, ns};
+      GDReduceArgs<BG_RED_JOBS> rd{};
+      rd.j[0] = GDRedJob{ws + p.o_pw, grad_params + b.p_w0, (int64_t)b.cexp * b.cin, (int64_t)b.cexp * b.cin, ns};
       bg_bn_jobs(p, ws, b.R_in, b.cexp, grad_params + b.p_bn0, &rd, 1);
       bg_reduce(rd, st);
     }
@@ -831,14 +731,14 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
   const float* ps = ws + p.q_stem;
   BGActArgs sa{}; sa.ss = p.s0 * p.s0; sa.C = p.stem; sa.R = p.R0; sa.tile_rows = bg_tile_rows(p.R0);
   sa.G = ws + p.o_dx; sa.Z = ws + p.o_zs; sa.bn = ps + (p.p_bn_stem - p.p_stem); sa.pgamma = pg; sa.pbeta = pb;
-  hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(bg_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(BG_THREADS), 0, st, sa);
-  hipLaunchKernelGGL(bg_stem_wgrad_kernel, dim3(bg_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(BG_THREADS), 0, st, B, p.size, p.stem, p.R0,
+  hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(GD_THREADS), 0, st, sa);
+  hipLaunchKernelGGL(bg_stem_wgrad_kernel, dim3(gd_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(GD_THREADS), 0, st, B, p.size, p.stem, p.R0,
                      bg_tile_rows(p.R0), (const float*)(ws + p.o_dx), (const float*)(ws + p.o_img), ws + p.o_pdw);
-  BGReduceArgs rd{};
-  rd.j[0] = BGRedJob{ws + p.o_pdw, grad_params + p.p_stem, (int64_t)p.stem * 27, (int64_t)p.stem * 27, bg_ntiles(p.R0)};
+  GDReduceArgs<BG_RED_JOBS> rd{};
+  rd.j[0] = GDRedJob{ws + p.o_pdw, grad_params + p.p_stem, (int64_t)p.stem * 27, (int64_t)p.stem * 27, bg_ntiles(p.R0)};
   bg_bn_jobs(p, ws, p.R0, p.stem, grad_params + p.p_bn_stem, &rd, 1);
   bg_reduce(rd, st);
   if (grad_image)
-    hipLaunchKernelGGL(bg_stem_dgrad_kernel, dim3(bg_blocks((int64_t)B * 3 * p.size * p.size)), dim3(BG_THREADS), 0, st, B, p.size, p.stem,
+    hipLaunchKernelGGL(bg_stem_dgrad_kernel, dim3(gd_blocks((int64_t)B * 3 * p.size * p.size)), dim3(GD_THREADS), 0, st, B, p.size, p.stem,
                        (const float*)(ws + p.o_dx), ps, grad_image);
 }

@@ -3,10 +3,11 @@
 // num_iteration_steps == 0) on gfx950, fp32.  The function is the inference function: BatchNorm uses the RUNNING
 // statistics in forward and backward (frozen-statistics fine-tuning); gamma and beta get gradients.
 //
-// Own kernels and plain layouts (nothing of the inference plan is shared): the parameters are one flat buffer in the
-// reference's shapes and state_dict order, activations are rows [R][W] (pixels of level 0 for every image, then level
-// 1, ...; W channels contiguous), so one launch covers the five levels, and blockIdx.y covers the five nets (or the six
-// header convs).  Per layer   x -> u = depthwise3x3(x) -> z = u . Wp^T + b -> a = bn_level(z) -> x' = swish(a).
+// Plain layouts, none of the inference plan's (the GEMM tile, the 3 x 3 window and the reduce core are grad_dev.h's, shared
+// with the neck and the backbone): the parameters are one flat buffer in the reference's shapes and state_dict order,
+// activations are rows [R][W] (pixels of level 0 for every image, then level 1, ...; W channels contiguous), so one
+// launch covers the five levels, and blockIdx.y covers the five nets (or the six header convs).
+// Per layer   x -> u = depthwise3x3(x) -> z = u . Wp^T + b -> a = bn_level(z) -> x' = swish(a).
 //
 //   forward   rows_from_nchw; per layer dw_fwd + gemm<LAYER> (stores z and x'); headers dw_fwd + gemm<HEADER>
 //             (stores into the [B][N][K] outputs, classifier through a sigmoid, its logits kept)
@@ -18,17 +19,8 @@
 // pixels, images and levels is partial sums in a fixed order (a thread walks the rows of its tile; a slab is one MFMA
 // chain) plus a second pass that adds the partials in a fixed order in double: bit-reproducible, no float atomics.
 #include "hep.h"
-#include "hep_dev.h"
+#include "grad_dev.h"
 #include "hep_internal.h"
-
-#define HG_THREADS 256
-#define HG_BM 64
-#define HG_BN 64
-#define HG_BK 16
-#define HG_LDS_PITCH 80      // floats: rows of a k-step land 16 banks apart (conflict-free fragment reads)
-#define HG_BN_EPS 1e-3f
-
-typedef float hg_f32x4 __attribute__((ext_vector_type(4)));
 
 static const int kFpnWidth[8] = {64, 88, 112, 160, 224, 288, 384, 384};
 static const int kHeadDepth[8] = {3, 3, 3, 4, 4, 4, 5, 5};
@@ -39,14 +31,13 @@ __device__ __forceinline__ int hg_level(const HGGeom& g, int r) {
   for (int i = 1; i < 5; i++) l += (r >= g.rowoff[i]);
   return l;
 }
-__device__ __forceinline__ float hg_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // ------------------------------------------------------------------------------------------------------------------
 struct HGPtr5 { const float* in[5]; float* out[5]; };
 
 // feats[l] NCHW [B][W][s][s] -> rows [R][W]
-__global__ __launch_bounds__(HG_THREADS) void hg_rows_from_nchw_kernel(HGGeom g, HGPtr5 f, float* __restrict__ x0) {
-  const int64_t idx = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void hg_rows_from_nchw_kernel(HGGeom g, HGPtr5 f, float* __restrict__ x0) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)g.R * g.W) return;
   const int r = (int)(idx / g.W), c = (int)(idx % g.W);
   const int l = hg_level(g, r), ss = g.s[l] * g.s[l], q = r - g.rowoff[l], b = q / ss, pix = q % ss;
@@ -54,8 +45,8 @@ __global__ __launch_bounds__(HG_THREADS) void hg_rows_from_nchw_kernel(HGGeom g,
 }
 
 // grad_feats[l] NCHW = sum over the five nets (in net order) of the rows d x_0[net]
-__global__ __launch_bounds__(HG_THREADS) void hg_feats_grad_kernel(HGGeom g, HGPtr5 f, const float* __restrict__ dx) {
-  const int64_t idx = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x, rw = (int64_t)g.R * g.W;
+__global__ __launch_bounds__(GD_THREADS) void hg_feats_grad_kernel(HGGeom g, HGPtr5 f, const float* __restrict__ dx) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x, rw = (int64_t)g.R * g.W;
   if (idx >= rw) return;
   const int r = (int)(idx / g.W), c = (int)(idx % g.W);
   const int l = hg_level(g, r), ss = g.s[l] * g.s[l], q = r - g.rowoff[l], b = q / ss, pix = q % ss;
@@ -71,50 +62,21 @@ struct HGDwArgs {
   const float* src[HG_SLOTS]; const float* w[HG_SLOTS]; float* dst[HG_SLOTS];     // rows, [W][1][3][3], rows
 };
 
-// The 3 x 3 window of rows around row r = pixel (y, x) of an s x s level, zeros outside the map.  A thread that walks
-// consecutive rows keeps it in registers: one new column (three loads) per step instead of nine, all nine at the start of an
-// image row.
-__device__ __forceinline__ void hg_win_col(float (&v)[3][3], const int j, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
-  const int xx = x + j - 1;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const int yy = y + i - 1;
-    v[i][j] = (yy >= 0 && yy < s && xx >= 0 && xx < s) ? p[(int64_t)(r + (i - 1) * s + (j - 1)) * W + c] : 0.0f;
-  }
-}
-__device__ __forceinline__ void hg_win_step(float (&v)[3][3], bool fresh, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
-  if (fresh) {
-    hg_win_col(v, 0, p, r, y, x, s, W, c);
-    hg_win_col(v, 1, p, r, y, x, s, W, c);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 3; i++) { v[i][0] = v[i][1]; v[i][1] = v[i][2]; }
-  }
-  hg_win_col(v, 2, p, r, y, x, s, W, c);
-}
-
-// depthwise 3x3 SAME (zero padding 1) on rows; blockIdx.y = slot; a thread = (HG_DW_ROWS consecutive rows, channel)
-#define HG_DW_ROWS 4
-__global__ __launch_bounds__(HG_THREADS) void hg_dw_fwd_kernel(HGDwArgs a) {
+// depthwise 3x3 SAME (zero padding 1) on rows; blockIdx.y = slot; a thread = (GD_DW_ROWS consecutive rows, channel)
+__global__ __launch_bounds__(GD_THREADS) void hg_dw_fwd_kernel(HGDwArgs a) {
   const HGGeom& g = a.g;
   const int slot = blockIdx.y, W = g.W;
-  const int64_t idx = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
-  const int ra = (int)(idx / W) * HG_DW_ROWS, c = (int)(idx % W);
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
+  const int ra = (int)(idx / W) * GD_DW_ROWS, c = (int)(idx % W);
   if (ra >= g.R) return;
-  const int rb = min(g.R, ra + HG_DW_ROWS);
+  const int rb = min(g.R, ra + GD_DW_ROWS);
   const float* __restrict__ src = a.src[slot];
   float w[9], v[3][3];
-#pragma unroll
-  for (int tp = 0; tp < 9; tp++) w[tp] = a.w[slot][c * 9 + tp];
+  gd_dw_taps(w, a.w[slot], c);
   for (int r = ra; r < rb; r++) {
     const int l = hg_level(g, r), s = g.s[l], pix = (r - g.rowoff[l]) % (s * s), y = pix / s, x = pix % s;
-    hg_win_step(v, r == ra || x == 0, src, r, y, x, s, W, c);
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) acc = fmaf(w[i * 3 + j], v[i][j], acc);
-    a.dst[slot][(int64_t)r * W + c] = acc;
+    gd_win_step<false>(v, r == ra || x == 0, src, r, y, x, s, W, c);
+    a.dst[slot][(int64_t)r * W + c] = gd_dw_dot(w, v);
   }
 }
 
@@ -134,86 +96,46 @@ struct HGGemmArgs {
 //   HEADER  the same product; C + bias (sigmoid for the classifier) -> the [B][N][K] output C2, the logits -> C (nullable)
 //   DATA    A = d z rows (k contiguous, pitch lda = K, padding columns zero), B = Wp [Kb][J] (j contiguous) -> C rows
 //   WGRAD   A = d z rows read as (k = row, i = column), B = u rows (k = row); rows [z * slab_rows, ...) -> C[z][I][J]
-template <int MODE> __global__ __launch_bounds__(HG_THREADS) void hg_gemm_kernel(HGGemmArgs a) {
-  __shared__ __attribute__((aligned(16))) float As[HG_BK][HG_LDS_PITCH];
-  __shared__ __attribute__((aligned(16))) float Bs[HG_BK][HG_LDS_PITCH];
+template <int MODE> __global__ __launch_bounds__(GD_THREADS) void hg_gemm_kernel(HGGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[GD_BK][GD_LDS_PITCH];
+  __shared__ __attribute__((aligned(16))) float Bs[GD_BK][GD_LDS_PITCH];
   const HGGeom& g = a.g;
   const int slot = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int I = a.I[slot], J = a.J[slot];
-  const int i0 = (int)(blockIdx.x / a.ntmax) * HG_BM, j0 = (int)(blockIdx.x % a.ntmax) * HG_BN;
+  const int i0 = (int)(blockIdx.x / a.ntmax) * GD_BM, j0 = (int)(blockIdx.x % a.ntmax) * GD_BN;
   if (i0 >= I || j0 >= J) return;                          // uniform over the workgroup
   int k_begin = 0, k_end = a.K[slot];
   if (MODE == HG_WGRAD) { k_begin = blockIdx.z * g.slab_rows; k_end = min(g.R, k_begin + g.slab_rows); }
-  const float* __restrict__ A = a.A[slot];
-  const float* __restrict__ Bm = a.Bm[slot];
-  const int lda = a.lda[slot], ldb = a.ldb[slot];
   const int kb_end = MODE == HG_DATA ? a.Kb[slot] : k_end;
-  hg_f32x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) acc[j] = hg_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  for (int k0 = k_begin; k0 < k_end; k0 += HG_BK) {
-    float4 va = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vb = va;
-    if (MODE != HG_WGRAD) {                                 // k contiguous: thread = (row i, four k)
-      const int i = lane, kq = wv * 4;
-      if (i0 + i < I && k0 + kq < k_end) va = *reinterpret_cast<const float4*>(A + (int64_t)(i0 + i) * lda + k0 + kq);
-      As[kq + 0][i] = va.x; As[kq + 1][i] = va.y; As[kq + 2][i] = va.z; As[kq + 3][i] = va.w;
-    } else {                                                // i contiguous: thread = (k, four i)
-      const int k = t >> 4, q = (t & 15) * 4;
-      if (k0 + k < k_end && i0 + q < I) va = *reinterpret_cast<const float4*>(A + (int64_t)(k0 + k) * lda + i0 + q);
-      *reinterpret_cast<float4*>(&As[k][q]) = va;
-    }
-    if (MODE == HG_LAYER || MODE == HG_HEADER) {
-      const int j = lane, kq = wv * 4;
-      if (j0 + j < J && k0 + kq < k_end) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(j0 + j) * ldb + k0 + kq);
-      Bs[kq + 0][j] = vb.x; Bs[kq + 1][j] = vb.y; Bs[kq + 2][j] = vb.z; Bs[kq + 3][j] = vb.w;
+  f32x4 acc[4];
+  gd_gemm_tile<MODE == HG_WGRAD ? GD_ROW_CONTIG : GD_K_CONTIG, MODE == HG_LAYER || MODE == HG_HEADER ? GD_K_CONTIG : GD_ROW_CONTIG>(
+      As, Bs, acc, a.A[slot], a.lda[slot], a.Bm[slot], a.ldb[slot], i0, I, j0, J, k_begin, k_end, kb_end, t, lane, wv);
+  // the slot's arguments by value: an epilogue that captured the whole argument struct would keep a private copy of it
+  float* const C = a.C[slot];
+  float* const C2 = a.C2[slot];
+  const float* const bias = a.bias[slot];
+  const float* const bn = a.bn[slot];
+  const int ldc = a.ldc[slot], bn_lstride = a.bn_lstride, K = a.hK[slot], kh = a.hkh[slot], hoff = a.hoff[slot], sig = a.sigmoid[slot];
+  gd_acc_visit(acc, i0, I, j0, J, lane, wv, [=, &g](int m, int n, float v) {
+    if (MODE == HG_LAYER) {
+      const int l = hg_level(g, m);
+      const GDBn q = gd_bn_load(bn + (int64_t)l * bn_lstride, g.W, n);
+      const float z = v + bias[n];
+      const float act = gd_bn_apply(q, z);
+      C[(int64_t)m * g.W + n] = z;
+      C2[(int64_t)m * g.W + n] = act * gd_sigmoid(act);
+    } else if (MODE == HG_HEADER) {
+      const int l = hg_level(g, m), ss = g.s[l] * g.s[l], q = m - g.rowoff[l], b = q / ss, pix = q % ss;
+      const int an = n / kh, jj = n % kh;
+      const float z = v + bias[n];
+      if (C) C[(int64_t)m * ldc + n] = z;
+      C2[((int64_t)b * g.S * 9 + (int64_t)(g.pixoff[l] + pix) * 9 + an) * K + hoff + jj] = sig ? gd_sigmoid(z) : z;
+    } else if (MODE == HG_DATA) {
+      C[(int64_t)m * ldc + n] = v;
     } else {
-      const int k = t >> 4, q = (t & 15) * 4;
-      if (k0 + k < kb_end && j0 + q < J) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(k0 + k) * ldb + j0 + q);
-      *reinterpret_cast<float4*>(&Bs[k][q]) = vb;
+      C[((int64_t)blockIdx.z * I + m) * J + n] = v;
     }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < HG_BK / 4; kk++) {
-      const float av = As[kk * 4 + (lane >> 4)][wv * 16 + (lane & 15)];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float bv = Bs[kk * 4 + (lane >> 4)][j * 16 + (lane & 15)];
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // accumulator element (reg): row 4 * (lane >> 4) + reg, column lane & 15
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int n = j0 + j * 16 + (lane & 15);
-    if (n >= J) continue;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      const int m = i0 + wv * 16 + (lane >> 4) * 4 + reg;
-      if (m >= I) continue;
-      const float v = acc[j][reg];
-      if (MODE == HG_LAYER) {
-        const int l = hg_level(g, m);
-        const float* __restrict__ bn = a.bn[slot] + (int64_t)l * a.bn_lstride;
-        const float z = v + a.bias[slot][n];
-        const float rstd = 1.0f / sqrtf(bn[3 * g.W + n] + HG_BN_EPS);
-        const float act = (z - bn[2 * g.W + n]) * rstd * bn[n] + bn[g.W + n];
-        a.C[slot][(int64_t)m * g.W + n] = z;
-        a.C2[slot][(int64_t)m * g.W + n] = act * hg_sigmoid(act);
-      } else if (MODE == HG_HEADER) {
-        const int l = hg_level(g, m), ss = g.s[l] * g.s[l], q = m - g.rowoff[l], b = q / ss, pix = q % ss;
-        const int K = a.hK[slot], kh = a.hkh[slot], an = n / kh, jj = n % kh;
-        const float z = v + a.bias[slot][n];
-        if (a.C[slot]) a.C[slot][(int64_t)m * a.ldc[slot] + n] = z;
-        a.C2[slot][((int64_t)b * g.S * 9 + (int64_t)(g.pixoff[l] + pix) * 9 + an) * K + a.hoff[slot] + jj] = a.sigmoid[slot] ? hg_sigmoid(z) : z;
-      } else if (MODE == HG_DATA) {
-        a.C[slot][(int64_t)m * a.ldc[slot] + n] = v;
-      } else {
-        a.C[slot][((int64_t)blockIdx.z * I + m) * J + n] = v;
-      }
-    }
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -225,10 +147,10 @@ struct HGGatherArgs {
 };
 
 // header cotangents as rows + the per-tile partial sums of the header bias gradient; thread = (tile, column), blockIdx.y = slot
-__global__ __launch_bounds__(HG_THREADS) void hg_hdr_gather_kernel(HGGatherArgs a) {
+__global__ __launch_bounds__(GD_THREADS) void hg_hdr_gather_kernel(HGGatherArgs a) {
   const HGGeom& g = a.g;
   const int slot = blockIdx.y, ld = a.ld[slot];
-  const int64_t gid = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (gid >= (int64_t)g.ntiles * ld) return;
   const int tile = (int)(gid / ld), c = (int)(gid % ld);
   int l = 0;
@@ -243,7 +165,7 @@ __global__ __launch_bounds__(HG_THREADS) void hg_hdr_gather_kernel(HGGatherArgs 
     if (real) {
       const int q = r - g.rowoff[l], b = q / ss, pix = q % ss;
       v = a.gout[slot][((int64_t)b * g.S * 9 + (int64_t)(g.pixoff[l] + pix) * 9 + an) * K + a.hoff[slot] + jj];
-      if (a.logits[slot]) { const float y = hg_sigmoid(a.logits[slot][(int64_t)r * ld + c]); v *= y * (1.0f - y); }
+      if (a.logits[slot]) { const float y = gd_sigmoid(a.logits[slot][(int64_t)r * ld + c]); v *= y * (1.0f - y); }
     }
     a.dz[slot][(int64_t)r * ld + c] = v;
     sum += v;
@@ -267,10 +189,10 @@ struct HGDwBwdArgs {
 //   depthwise weight gradient  pdw[tap] += d u[r] * x[neighbour(r, tap)]
 //   depthwise data gradient    d x[r]    = sum_tap w[8 - tap] * d u[neighbour(r, tap)]   (summed over the net's headers)
 //   below                      d a = d x * swish'(a), a = bn(z);  d gamma += d a * zhat;  d beta += d a;  d z = d a * gamma * rstd;  d bias += d z
-__global__ __launch_bounds__(HG_THREADS) void hg_dw_bwd_kernel(HGDwBwdArgs a) {
+__global__ __launch_bounds__(GD_THREADS) void hg_dw_bwd_kernel(HGDwBwdArgs a) {
   const HGGeom& g = a.g;
   const int net = blockIdx.y, W = g.W;
-  const int64_t gid = (int64_t)blockIdx.x * HG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (gid >= (int64_t)g.ntiles * W) return;
   const int tile = (int)(gid / W), c = (int)(gid % W);
   int l = 0;
@@ -285,20 +207,17 @@ __global__ __launch_bounds__(HG_THREADS) void hg_dw_bwd_kernel(HGDwBwdArgs a) {
 #pragma unroll
     for (int tp = 0; tp < 9; tp++) { wt[k][tp] = k < nsrc ? a.w[net][k][c * 9 + tp] : 0.0f; aw[k][tp] = 0.0f; }
   const float* __restrict__ Z = a.Zprev[net];
-  float gamma = 0.0f, beta = 0.0f, mean = 0.0f, rstd = 0.0f;
-  if (Z) {
-    const float* __restrict__ bn = a.bnprev[net] + (int64_t)l * a.bn_lstride;
-    gamma = bn[c]; beta = bn[W + c]; mean = bn[2 * W + c]; rstd = 1.0f / sqrtf(bn[3 * W + c] + HG_BN_EPS);
-  }
+  GDBn q{};
+  if (Z) q = gd_bn_load(a.bnprev[net] + (int64_t)l * a.bn_lstride, W, c);
   float ag = 0.0f, ab = 0.0f, abias = 0.0f;
   float xw[3][3], gw[2][3][3];
   for (int r = r0; r < r1; r++) {
     const int pix = (r - g.rowoff[l]) % ss, y = pix / s, x = pix % s;
     const bool fresh = r == r0 || x == 0;
-    hg_win_step(xw, fresh, X, r, y, x, s, W, c);
+    gd_win_step<false>(xw, fresh, X, r, y, x, s, W, c);
 #pragma unroll
     for (int k = 0; k < 2; k++)
-      if (k < nsrc) hg_win_step(gw[k], fresh, a.G[net][k], r, y, x, s, W, c);
+      if (k < nsrc) gd_win_step<false>(gw[k], fresh, a.G[net][k], r, y, x, s, W, c);
     float dx = 0.0f;
 #pragma unroll
     for (int k = 0; k < 2; k++)
@@ -311,9 +230,9 @@ __global__ __launch_bounds__(HG_THREADS) void hg_dw_bwd_kernel(HGDwBwdArgs a) {
         }
       }
     if (Z) {
-      const float zh = (Z[(int64_t)r * W + c] - mean) * rstd, act = zh * gamma + beta, sg = hg_sigmoid(act);
-      const float da = dx * (sg * (1.0f + act * (1.0f - sg)));
-      const float dz = da * gamma * rstd;
+      const float zh = (Z[(int64_t)r * W + c] - q.mean) * q.rstd, act = zh * q.gamma + q.beta;
+      const float da = dx * gd_swish_grad(act);
+      const float dz = da * q.gamma * q.rstd;
       ag = fmaf(da, zh, ag); ab += da; abias += dz;
       a.out[net][(int64_t)r * W + c] = dz;
     } else if (a.out[net]) {
@@ -340,18 +259,12 @@ struct HGReduceArgs {
   const float* pgamma[HG_SLOTS]; const float* pbeta[HG_SLOTS]; float* dbn[HG_SLOTS];      // [tile][W] -> per level gamma, beta, 0, 0 (NULL: none)
 };
 
-// second pass: every gradient element is the sum of its partials, added in double in a FIXED order: 16 threads share an
-// element, thread j adds the partials j, j + 16, ... in index order, then thread 0 adds the 16 sums in order 0..15 and
-// rounds once.  A workgroup = 16 consecutive elements x 16 such threads (64-byte reads of a partial row).
+// second pass (gd_reduce_core): a workgroup = 16 consecutive elements, 64-byte reads of a partial row.
 // blockIdx.y = slot, blockIdx.z = kind (0 pointwise weight, 1 depthwise weight, 2 bias, 3 BatchNorm of the five levels)
-#define HG_RED_E 16
-#define HG_RED_K 16
-static_assert(HG_RED_E * HG_RED_K == HG_THREADS, "one reduce workgroup = 16 elements x 16 partial lanes");
-__global__ __launch_bounds__(HG_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
-  __shared__ double part[HG_RED_K][HG_RED_E + 1];
+__global__ __launch_bounds__(GD_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
   const HGGeom& g = a.g;
-  const int slot = blockIdx.y, kind = blockIdx.z, W = g.W, el = threadIdx.x % HG_RED_E, kl = threadIdx.x / HG_RED_E;
-  const int64_t e = (int64_t)blockIdx.x * HG_RED_E + el;
+  const int slot = blockIdx.y, kind = blockIdx.z, W = g.W, el = threadIdx.x % GD_RED_E, kl = threadIdx.x / GD_RED_E;
+  const int64_t e = (int64_t)blockIdx.x * GD_RED_E + el;
   const float* __restrict__ src = nullptr;      // partial k of this element: src[k * stride]
   float* dst = nullptr;
   int64_t stride = 0;
@@ -367,17 +280,8 @@ __global__ __launch_bounds__(HG_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
     dst = a.dbn[slot] + (int64_t)l * a.bn_lstride + which * W + c;
     if (which < 2) { src = (which == 0 ? a.pgamma[slot] : a.pbeta[slot]) + c; stride = W; k0 = g.tileoff[l]; k1 = g.tileoff[l + 1]; }
   }
-  double s = 0.0;
-  if (src)
-    for (int k = k0 + kl; k < k1; k += HG_RED_K) s += (double)src[k * stride];
-  part[kl][el] = s;
-  __syncthreads();
-  if (kl == 0 && dst) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < HG_RED_K; j++) t += part[j][el];
-    *dst = (float)t;                              // (running statistics: no partials, zero)
-  }
+  const float v = gd_reduce_core(src, stride, k0, k1, el, kl);
+  if (kl == 0 && dst) *dst = v;                    // (running statistics: no partials, zero)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -419,9 +323,7 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
   for (int l = 0; l < 6; l++) g.rowoff[l] = batch * g.pixoff[l];
   for (int l = 0; l < 5; l++) { g.tileoff[l] = tiles; tiles += (batch * g.s[l] * g.s[l] + HG_TILE_ROWS - 1) / HG_TILE_ROWS; }
   g.tileoff[5] = tiles; g.ntiles = tiles;
-  g.nslab = g.R / 512; if (g.nslab < 1) g.nslab = 1; if (g.nslab > HG_MAX_SLABS) g.nslab = HG_MAX_SLABS;
-  g.slab_rows = ((g.R + g.nslab - 1) / g.nslab + HG_BK - 1) / HG_BK * HG_BK;
-  g.nslab = (g.R + g.slab_rows - 1) / g.slab_rows;
+  gd_slabs(g.R, HG_MAX_SLABS, &g.slab_rows, &g.nslab);
   const int64_t RW = (int64_t)g.R * W;
   int64_t w = 0;
   auto take = [&](int64_t n) { const int64_t at = w; w += (n + 3) / 4 * 4; return at; };
@@ -437,7 +339,6 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
   return 0;
 }
 
-static inline unsigned hg_blocks(int64_t n) { return (unsigned)((n + HG_THREADS - 1) / HG_THREADS); }
 static inline int64_t hg_conv_stride(const HGGeom& g) { return (int64_t)9 * g.W + (int64_t)g.W * g.W + g.W; }
 
 void launch_heads_forward(const HGPlan& p, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t st) {
@@ -446,12 +347,12 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
   const int64_t RW = (int64_t)g.R * W;
   HGPtr5 f{};
   for (int l = 0; l < 5; l++) f.in[l] = feats[l];
-  hipLaunchKernelGGL(hg_rows_from_nchw_kernel, dim3(hg_blocks(RW)), dim3(HG_THREADS), 0, st, g, f, ws + p.o_x0);
-  const int mt = (g.R + HG_BM - 1) / HG_BM;
-  const int64_t dw_threads = (int64_t)((g.R + HG_DW_ROWS - 1) / HG_DW_ROWS) * W;
+  hipLaunchKernelGGL(hg_rows_from_nchw_kernel, dim3(gd_blocks(RW)), dim3(GD_THREADS), 0, st, g, f, ws + p.o_x0);
+  const int mt = (g.R + GD_BM - 1) / GD_BM;
+  const int64_t dw_threads = (int64_t)((g.R + GD_DW_ROWS - 1) / GD_DW_ROWS) * W;
   for (int i = 0; i < D; i++) {
     HGDwArgs d{}; d.g = g;
-    HGGemmArgs m{}; m.g = g; m.ntmax = (W + HG_BN - 1) / HG_BN; m.bn_lstride = D * 4 * W;
+    HGGemmArgs m{}; m.g = g; m.ntmax = (W + GD_BN - 1) / GD_BN; m.bn_lstride = D * 4 * W;
     for (int n = 0; n < HG_NETS; n++) {
       const float* conv = params + p.p_conv[n] + i * hg_conv_stride(g);
       d.src[n] = i == 0 ? ws + p.o_x0 : ws + p.o_x + ((int64_t)(i - 1) * HG_NETS + n) * RW;
@@ -463,8 +364,8 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
       m.C2[n] = ws + p.o_x + ((int64_t)i * HG_NETS + n) * RW;
       m.I[n] = g.R; m.J[n] = W; m.K[n] = W; m.lda[n] = W; m.ldb[n] = W; m.ldc[n] = W;
     }
-    hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(hg_blocks(dw_threads), HG_NETS), dim3(HG_THREADS), 0, st, d);
-    hipLaunchKernelGGL(hg_gemm_kernel<HG_LAYER>, dim3(mt * m.ntmax, HG_NETS), dim3(HG_THREADS), 0, st, m);
+    hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(gd_blocks(dw_threads), HG_NETS), dim3(GD_THREADS), 0, st, d);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_LAYER>, dim3(mt * m.ntmax, HG_NETS), dim3(GD_THREADS), 0, st, m);
   }
   HGDwArgs d{}; d.g = g;
   HGGemmArgs m{}; m.g = g; m.ntmax = 1;
@@ -477,11 +378,11 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
     m.C[h] = h == 1 ? ws + p.o_cl : nullptr; m.C2[h] = outs[p.net[h]];
     m.I[h] = g.R; m.J[h] = p.C[h]; m.K[h] = W; m.lda[h] = W; m.ldb[h] = W; m.ldc[h] = p.ld[h];
     m.hK[h] = p.K[h]; m.hkh[h] = p.kh[h]; m.hoff[h] = p.koff[h]; m.sigmoid[h] = h == 1;
-    const int nt = (p.C[h] + HG_BN - 1) / HG_BN;
+    const int nt = (p.C[h] + GD_BN - 1) / GD_BN;
     if (nt > m.ntmax) m.ntmax = nt;
   }
-  hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(hg_blocks(dw_threads), HG_SLOTS), dim3(HG_THREADS), 0, st, d);
-  hipLaunchKernelGGL(hg_gemm_kernel<HG_HEADER>, dim3(mt * m.ntmax, HG_SLOTS), dim3(HG_THREADS), 0, st, m);
+  hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(gd_blocks(dw_threads), HG_SLOTS), dim3(GD_THREADS), 0, st, d);
+  hipLaunchKernelGGL(hg_gemm_kernel<HG_HEADER>, dim3(mt * m.ntmax, HG_SLOTS), dim3(GD_THREADS), 0, st, m);
 }
 
 void launch_heads_backward(const HGPlan& p, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
@@ -489,12 +390,12 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
   const HGGeom& g = p.g;
   const int W = g.W, D = g.D, T = g.ntiles;
   const int64_t RW = (int64_t)g.R * W, TW = (int64_t)T * W;
-  const int mt = (g.R + HG_BM - 1) / HG_BM, bn_lstride = D * 4 * W;
-  const unsigned col_blocks = hg_blocks(TW);
+  const int mt = (g.R + GD_BM - 1) / GD_BM, bn_lstride = D * 4 * W;
+  const unsigned col_blocks = gd_blocks(TW);
   // ---- header stage ----
   {
     HGGatherArgs ga{}; ga.g = g;
-    HGGemmArgs md{}; md.g = g; md.ntmax = (W + HG_BN - 1) / HG_BN;
+    HGGemmArgs md{}; md.g = g; md.ntmax = (W + GD_BN - 1) / GD_BN;
     HGGemmArgs mw{}; mw.g = g; mw.ntmax = md.ntmax;
     HGDwBwdArgs db{}; db.g = g; db.bn_lstride = bn_lstride;
     HGReduceArgs rd{}; rd.g = g; rd.bn_lstride = bn_lstride;
@@ -512,7 +413,7 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
       md.I[h] = g.R; md.J[h] = W; md.K[h] = p.ld[h]; md.Kb[h] = p.C[h]; md.lda[h] = p.ld[h]; md.ldb[h] = W; md.ldc[h] = W;
       mw.A[h] = ga.dz[h]; mw.Bm[h] = ws + p.o_uh + (int64_t)h * RW; mw.C[h] = ws + p.o_pw[h];
       mw.I[h] = p.ld[h]; mw.J[h] = W; mw.lda[h] = p.ld[h]; mw.ldb[h] = W;
-      const int it = (p.ld[h] + HG_BM - 1) / HG_BM;
+      const int it = (p.ld[h] + GD_BM - 1) / GD_BM;
       if (it > itmax) itmax = it;
       const int k = db.nsrc[n]++;
       db.G[n][k] = md.C[h]; db.w[n][k] = hdr; db.pdw[n][k] = ws + p.o_pdw[h];
@@ -529,15 +430,15 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
       const int par = (D - 1) & 1;
       db.pgamma[n] = ws + p.o_pg[par] + n * TW; db.pbeta[n] = ws + p.o_pb[par] + n * TW; db.pbias[n] = ws + p.o_pbi[par] + n * TW;
     }
-    hipLaunchKernelGGL(hg_hdr_gather_kernel, dim3(hg_blocks((int64_t)T * ldmax), HG_SLOTS), dim3(HG_THREADS), 0, st, ga);
-    hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_SLOTS), dim3(HG_THREADS), 0, st, md);
-    hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(itmax * mw.ntmax, HG_SLOTS, g.nslab), dim3(HG_THREADS), 0, st, mw);
-    hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(HG_THREADS), 0, st, db);
-    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)((emax + HG_RED_E - 1) / HG_RED_E), HG_SLOTS, 3), dim3(HG_THREADS), 0, st, rd);
+    hipLaunchKernelGGL(hg_hdr_gather_kernel, dim3(gd_blocks((int64_t)T * ldmax), HG_SLOTS), dim3(GD_THREADS), 0, st, ga);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_SLOTS), dim3(GD_THREADS), 0, st, md);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(itmax * mw.ntmax, HG_SLOTS, g.nslab), dim3(GD_THREADS), 0, st, mw);
+    hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(GD_THREADS), 0, st, db);
+    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)((emax + GD_RED_E - 1) / GD_RED_E), HG_SLOTS, 3), dim3(GD_THREADS), 0, st, rd);
   }
   // ---- the layers, top down ----
   for (int i = D - 1; i >= 0; i--) {
-    HGGemmArgs md{}; md.g = g; md.ntmax = (W + HG_BN - 1) / HG_BN;
+    HGGemmArgs md{}; md.g = g; md.ntmax = (W + GD_BN - 1) / GD_BN;
     HGGemmArgs mw{}; mw.g = g; mw.ntmax = md.ntmax;
     HGDwBwdArgs db{}; db.g = g; db.bn_lstride = bn_lstride;
     HGReduceArgs rd{}; rd.g = g; rd.bn_lstride = bn_lstride;
@@ -566,14 +467,14 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
       rd.pgamma[n] = ws + p.o_pg[par] + n * TW; rd.pbeta[n] = ws + p.o_pb[par] + n * TW;
       rd.dbn[n] = grad_params + p.p_bn[n] + (int64_t)i * 4 * W;
     }
-    hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_NETS), dim3(HG_THREADS), 0, st, md);
-    hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(md.ntmax * mw.ntmax, HG_NETS, g.nslab), dim3(HG_THREADS), 0, st, mw);
-    hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(HG_THREADS), 0, st, db);
-    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)W * W + HG_RED_E - 1) / HG_RED_E), HG_NETS, 4), dim3(HG_THREADS), 0, st, rd);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_NETS), dim3(GD_THREADS), 0, st, md);
+    hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(md.ntmax * mw.ntmax, HG_NETS, g.nslab), dim3(GD_THREADS), 0, st, mw);
+    hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(GD_THREADS), 0, st, db);
+    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)W * W + GD_RED_E - 1) / GD_RED_E), HG_NETS, 4), dim3(GD_THREADS), 0, st, rd);
   }
   if (grad_feats) {
     HGPtr5 f{};
     for (int l = 0; l < 5; l++) f.out[l] = grad_feats[l];
-    hipLaunchKernelGGL(hg_feats_grad_kernel, dim3(hg_blocks(RW)), dim3(HG_THREADS), 0, st, g, f, ws + p.o_g2);
+    hipLaunchKernelGGL(hg_feats_grad_kernel, dim3(gd_blocks(RW)), dim3(GD_THREADS), 0, st, g, f, ws + p.o_g2);
   }
 }

@@ -3,8 +3,8 @@
 // three backbone taps P3 / P4 / P5).  The function is the inference function: BatchNorm uses the RUNNING statistics in
 // forward and backward; gamma and beta get gradients, the statistics get zero.
 //
-// Own kernels and plain layouts, as k_head_grad.hip has: every map is rows [B * s * s][C], channels contiguous, one buffer
-// per map.  The flat parameter buffer starts every cell with 19 fusion scalars, so no tensor behind them is 16-byte aligned:
+// Plain layouts, as k_head_grad.hip has (the GEMM tile, the 3 x 3 window and the reduce are grad_dev.h's): every map is
+// rows [B * s * s][C], channels contiguous, one buffer per map.  The flat parameter buffer starts every cell with 19 fusion scalars, so no tensor behind them is 16-byte aligned:
 // the forward first copies each cell to workspace[4 * k + 1], which puts every conv / BatchNorm tensor on a 16-byte boundary
 // for the GEMMs' float4 loads; forward and backward read the parameters from that copy.
 //
@@ -23,24 +23,17 @@
 // Max-pool routing: zero padding is one column right and one row at the bottom (pooled sides are even); a window's gradient
 // goes to the FIRST maximal element in row-major order of the padded window (strict > while scanning), padding included -
 // a padding argmax matches no real element, so that window's gradient is dropped.
-// The pointwise products are v_mfma_f32_16x16x4_f32 (the tile scheme of k_head_grad.hip).  Every reduction is partial sums
-// in a fixed order plus a fixed-order second pass in double: bit-reproducible, no float atomics.
+// The pointwise products are v_mfma_f32_16x16x4_f32 (gd_gemm_tile of grad_dev.h).  Every reduction is partial sums in a
+// fixed order plus a fixed-order second pass in double (gd_reduce_kernel): bit-reproducible, no float atomics.
 #include <cstdio>
 
 #include "hep.h"
-#include "hep_dev.h"
+#include "grad_dev.h"
 #include "hep_internal.h"
 
-#define NG_THREADS 256
-#define NG_BM 64
-#define NG_BN 64
-#define NG_BK 16
-#define NG_LDS_PITCH 80      // floats: rows of a k-step land 16 banks apart (conflict-free fragment reads)
-#define NG_BN_EPS 1e-3f
 #define NG_FUSION_EPS 1e-4f
-#define NG_DW_ROWS 4
+#define NG_RED_JOBS 6        // reduce jobs of one launch: pointwise weight, depthwise weight, gamma, beta, statistics, bias
 
-typedef float ng_f32x4 __attribute__((ext_vector_type(4)));
 enum { NG_SAME = 0, NG_UP = 1, NG_POOL = 2 };
 
 static const int kNeckWidth[6] = {64, 88, 112, 160, 224, 288};
@@ -58,8 +51,6 @@ static const int kOutNode[5] = {3, 4, 5, 6, 7};                           // the
 // laterals in state_dict order: p5_down_channel p4_down_channel p3_down_channel p5_to_p6 p4_down_channel_2 p5_down_channel_2
 static const int kLatTap[NG_LATERALS] = {2, 1, 0, 2, 1, 2};
 static const int kLatCode[NG_LATERALS] = {2, 1, 0, -1, 5, 6};             // the cell-0 input it is (-1: p6_pre, pooled into P6)
-
-__device__ __forceinline__ float ng_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // w_i = relu(p_i) / (sum_k relu(p_k) + 1e-4); p == NULL: 1 (a pool that is not a fusion source)
 __device__ __forceinline__ float ng_fusion_weight(const float* __restrict__ p, int n, int i) {
@@ -101,8 +92,8 @@ __device__ __forceinline__ float ng_src_value(const NGSrc& q, int r, int b, int 
 // ------------------------------------------------------------------------------------------------------------------
 struct NGPackArgs { int cells; int64_t src[NG_MAX_CELLS + 1], dst[NG_MAX_CELLS]; };
 // the flat parameters, cell by cell, to their 16-byte friendly place in the workspace
-__global__ __launch_bounds__(NG_THREADS) void ng_pack_kernel(NGPackArgs a, const float* __restrict__ params, float* __restrict__ ws) {
-  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void ng_pack_kernel(NGPackArgs a, const float* __restrict__ params, float* __restrict__ ws) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= a.src[a.cells]) return;
   int r = 0;
   for (int i = 1; i < a.cells; i++) r += (idx >= a.src[i]);
@@ -110,16 +101,16 @@ __global__ __launch_bounds__(NG_THREADS) void ng_pack_kernel(NGPackArgs a, const
 }
 
 // NCHW [B][C][s][s] -> rows [B * s * s][C]
-__global__ __launch_bounds__(NG_THREADS) void ng_rows_from_nchw_kernel(int B, int C, int ss, const float* __restrict__ in, float* __restrict__ rows) {
-  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void ng_rows_from_nchw_kernel(int B, int C, int ss, const float* __restrict__ in, float* __restrict__ rows) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * ss * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / ss, pix = r % ss;
   rows[idx] = in[((int64_t)b * C + c) * ss + pix];
 }
 // rows -> NCHW, summing up to three row buffers in their order (the taps collect the data gradients of their laterals)
 struct NGRows3 { const float* p[3]; int n; };
-__global__ __launch_bounds__(NG_THREADS) void ng_nchw_from_rows_kernel(int B, int C, int ss, NGRows3 rows, float* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(GD_THREADS) void ng_nchw_from_rows_kernel(int B, int C, int ss, NGRows3 rows, float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * ss * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / ss, pix = r % ss;
   float v = rows.p[0][idx];
@@ -128,9 +119,9 @@ __global__ __launch_bounds__(NG_THREADS) void ng_nchw_from_rows_kernel(int B, in
 }
 
 // maxpool_same of a map of side sf (cell 0: p6_in = pool(p5_to_p6(P5)), p7_in = pool(p6_in)): values and argmax bytes
-__global__ __launch_bounds__(NG_THREADS) void ng_pool_fwd_kernel(int B, int sf, int W, const float* __restrict__ in, float* __restrict__ out, uint8_t* __restrict__ am) {
+__global__ __launch_bounds__(GD_THREADS) void ng_pool_fwd_kernel(int B, int sf, int W, const float* __restrict__ in, float* __restrict__ out, uint8_t* __restrict__ am) {
   const int so = sf >> 1;
-  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * so * so * W) return;
   const int r = (int)(idx / W), c = (int)(idx % W), b = r / (so * so), pix = r % (so * so);
   int arg;
@@ -145,9 +136,9 @@ struct NGFuseArgs {
   const float* fw;                    // the node's fusion vector p
   float* S; float* X;                 // the pre-activation sum (kept for the backward) and swish of it (the depthwise input)
 };
-__global__ __launch_bounds__(NG_THREADS) void ng_fuse_fwd_kernel(NGFuseArgs a) {
+__global__ __launch_bounds__(GD_THREADS) void ng_fuse_fwd_kernel(NGFuseArgs a) {
   const int W = a.W, s = a.s, ss = s * s;
-  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)a.B * ss * W) return;
   const int r = (int)(idx / W), c = (int)(idx % W), b = r / ss, pix = r % ss, y = pix / s, x = pix % s;
   float acc = 0.0f;
@@ -166,51 +157,22 @@ __global__ __launch_bounds__(NG_THREADS) void ng_fuse_fwd_kernel(NGFuseArgs a) {
       acc = i == 0 ? w * v : acc + w * v;
     }
   a.S[idx] = acc;
-  a.X[idx] = acc * ng_sigmoid(acc);
+  a.X[idx] = acc * gd_sigmoid(acc);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The 3 x 3 window of rows around row r = pixel (y, x) of an s x s map, zeros outside.  A thread that walks consecutive
-// rows keeps it in registers (one new column per step).  SW: the stored map is the pre-activation, the window holds swish of it.
-template <bool SW> __device__ __forceinline__ void ng_win_col(float (&v)[3][3], const int j, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
-  const int xx = x + j - 1;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const int yy = y + i - 1;
-    float t = (yy >= 0 && yy < s && xx >= 0 && xx < s) ? p[(int64_t)(r + (i - 1) * s + (j - 1)) * W + c] : 0.0f;
-    if (SW) t = t * ng_sigmoid(t);
-    v[i][j] = t;
-  }
-}
-template <bool SW> __device__ __forceinline__ void ng_win_step(float (&v)[3][3], bool fresh, const float* __restrict__ p, int r, int y, int x, int s, int W, int c) {
-  if (fresh) {
-    ng_win_col<SW>(v, 0, p, r, y, x, s, W, c);
-    ng_win_col<SW>(v, 1, p, r, y, x, s, W, c);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 3; i++) { v[i][0] = v[i][1]; v[i][1] = v[i][2]; }
-  }
-  ng_win_col<SW>(v, 2, p, r, y, x, s, W, c);
-}
-
-// depthwise 3x3 SAME on the rows of one map; a thread = (NG_DW_ROWS consecutive rows, channel)
-__global__ __launch_bounds__(NG_THREADS) void ng_dw_fwd_kernel(int R, int s, int W, const float* __restrict__ src, const float* __restrict__ wdw, float* __restrict__ dst) {
-  const int64_t idx = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
-  const int ra = (int)(idx / W) * NG_DW_ROWS, c = (int)(idx % W);
+// depthwise 3x3 SAME on the rows of one map; a thread = (GD_DW_ROWS consecutive rows, channel)
+__global__ __launch_bounds__(GD_THREADS) void ng_dw_fwd_kernel(int R, int s, int W, const float* __restrict__ src, const float* __restrict__ wdw, float* __restrict__ dst) {
+  const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
+  const int ra = (int)(idx / W) * GD_DW_ROWS, c = (int)(idx % W);
   if (ra >= R) return;
-  const int rb = min(R, ra + NG_DW_ROWS), ss = s * s;
+  const int rb = min(R, ra + GD_DW_ROWS), ss = s * s;
   float w[9], v[3][3];
-#pragma unroll
-  for (int tp = 0; tp < 9; tp++) w[tp] = wdw[c * 9 + tp];
+  gd_dw_taps(w, wdw, c);
   for (int r = ra; r < rb; r++) {
     const int pix = r % ss, y = pix / s, x = pix % s;
-    ng_win_step<false>(v, r == ra || x == 0, src, r, y, x, s, W, c);
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) acc = fmaf(w[i * 3 + j], v[i][j], acc);
-    dst[(int64_t)r * W + c] = acc;
+    gd_win_step<false>(v, r == ra || x == 0, src, r, y, x, s, W, c);
+    dst[(int64_t)r * W + c] = gd_dw_dot(w, v);
   }
 }
 
@@ -225,75 +187,29 @@ struct NGGemmArgs {
 //   FWD     A = u rows (k contiguous), B = Wp [J][K] (k contiguous); z = C + bias -> C, bn(z) -> C2
 //   DATA    A = d z rows (k contiguous), B = Wp [K][J] (j contiguous) -> C rows
 //   WGRAD   A = d z rows read as (k = row, i = column), B = u rows (k = row); rows [z * slab_rows, ...) of K -> C[z][I][J]
-template <int MODE> __global__ __launch_bounds__(NG_THREADS) void ng_gemm_kernel(NGGemmArgs a) {
-  __shared__ __attribute__((aligned(16))) float As[NG_BK][NG_LDS_PITCH];
-  __shared__ __attribute__((aligned(16))) float Bs[NG_BK][NG_LDS_PITCH];
+template <int MODE> __global__ __launch_bounds__(GD_THREADS) void ng_gemm_kernel(NGGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) float As[GD_BK][GD_LDS_PITCH];
+  __shared__ __attribute__((aligned(16))) float Bs[GD_BK][GD_LDS_PITCH];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int I = a.I, J = a.J;
-  const int i0 = (int)(blockIdx.x / a.ntn) * NG_BM, j0 = (int)(blockIdx.x % a.ntn) * NG_BN;
+  const int i0 = (int)(blockIdx.x / a.ntn) * GD_BM, j0 = (int)(blockIdx.x % a.ntn) * GD_BN;
   if (i0 >= I || j0 >= J) return;                          // uniform over the workgroup
   int k_begin = 0, k_end = a.K;
   if (MODE == NG_WGRAD) { k_begin = blockIdx.z * a.slab_rows; k_end = min(a.K, k_begin + a.slab_rows); }
-  const float* __restrict__ A = a.A;
-  const float* __restrict__ Bm = a.Bm;
-  const int lda = a.lda, ldb = a.ldb;
-  ng_f32x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) acc[j] = ng_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  for (int k0 = k_begin; k0 < k_end; k0 += NG_BK) {
-    float4 va = make_float4(0.0f, 0.0f, 0.0f, 0.0f), vb = va;
-    if (MODE != NG_WGRAD) {                                 // k contiguous: thread = (row i, four k)
-      const int i = lane, kq = wv * 4;
-      if (i0 + i < I && k0 + kq < k_end) va = *reinterpret_cast<const float4*>(A + (int64_t)(i0 + i) * lda + k0 + kq);
-      As[kq + 0][i] = va.x; As[kq + 1][i] = va.y; As[kq + 2][i] = va.z; As[kq + 3][i] = va.w;
-    } else {                                                // i contiguous: thread = (k, four i)
-      const int k = t >> 4, q = (t & 15) * 4;
-      if (k0 + k < k_end && i0 + q < I) va = *reinterpret_cast<const float4*>(A + (int64_t)(k0 + k) * lda + i0 + q);
-      *reinterpret_cast<float4*>(&As[k][q]) = va;
-    }
+  f32x4 acc[4];
+  gd_gemm_tile<MODE == NG_WGRAD ? GD_ROW_CONTIG : GD_K_CONTIG, MODE == NG_FWD ? GD_K_CONTIG : GD_ROW_CONTIG>(
+      As, Bs, acc, a.A, a.lda, a.Bm, a.ldb, i0, I, j0, J, k_begin, k_end, k_end, t, lane, wv);
+  gd_acc_visit(acc, i0, I, j0, J, lane, wv, [=](int m, int n, float v, const GDBn& q) {
     if (MODE == NG_FWD) {
-      const int j = lane, kq = wv * 4;
-      if (j0 + j < J && k0 + kq < k_end) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(j0 + j) * ldb + k0 + kq);
-      Bs[kq + 0][j] = vb.x; Bs[kq + 1][j] = vb.y; Bs[kq + 2][j] = vb.z; Bs[kq + 3][j] = vb.w;
+      const float z = v + a.bias[n];
+      a.C[(int64_t)m * a.ldc + n] = z;
+      a.C2[(int64_t)m * a.ldc + n] = gd_bn_apply(q, z);
+    } else if (MODE == NG_DATA) {
+      a.C[(int64_t)m * a.ldc + n] = v;
     } else {
-      const int k = t >> 4, q = (t & 15) * 4;
-      if (k0 + k < k_end && j0 + q < J) vb = *reinterpret_cast<const float4*>(Bm + (int64_t)(k0 + k) * ldb + j0 + q);
-      *reinterpret_cast<float4*>(&Bs[k][q]) = vb;
+      a.C[((int64_t)blockIdx.z * I + m) * J + n] = v;
     }
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < NG_BK / 4; kk++) {
-      const float av = As[kk * 4 + (lane >> 4)][wv * 16 + (lane & 15)];
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float bv = Bs[kk * 4 + (lane >> 4)][j * 16 + (lane & 15)];
-        acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  // accumulator element (reg): row 4 * (lane >> 4) + reg, column lane & 15
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const int n = j0 + j * 16 + (lane & 15);
-    if (n >= J) continue;
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      const int m = i0 + wv * 16 + (lane >> 4) * 4 + reg;
-      if (m >= I) continue;
-      const float v = acc[j][reg];
-      if (MODE == NG_FWD) {
-        const float z = v + a.bias[n];
-        const float rstd = 1.0f / sqrtf(a.bn[3 * J + n] + NG_BN_EPS);
-        a.C[(int64_t)m * a.ldc + n] = z;
-        a.C2[(int64_t)m * a.ldc + n] = (z - a.bn[2 * J + n]) * rstd * a.bn[n] + a.bn[J + n];
-      } else if (MODE == NG_DATA) {
-        a.C[(int64_t)m * a.ldc + n] = v;
-      } else {
-        a.C[((int64_t)blockIdx.z * I + m) * J + n] = v;
-      }
-    }
-  }
+  }, [=](int n) { return MODE == NG_FWD ? gd_bn_load(a.bn, J, n) : GDBn{}; });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -309,17 +225,17 @@ struct NGGatherArgs {
   float* pgamma; float* pbeta; float* pbias;   // [tile][W]
 };
 // Gradient of one map in gather form + the BatchNorm that produced it.  One thread = (tile of NG_TILE_ROWS rows, channel).
-__global__ __launch_bounds__(NG_THREADS) void ng_gather_kernel(NGGatherArgs a) {
+__global__ __launch_bounds__(GD_THREADS) void ng_gather_kernel(NGGatherArgs a) {
   const int W = a.W, s = a.s, ss = s * s;
-  const int64_t gid = (int64_t)blockIdx.x * NG_THREADS + threadIdx.x;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int tile = (int)(gid / W), c = (int)(gid % W);
   const int r0 = tile * NG_TILE_ROWS, r1 = min(a.R, r0 + NG_TILE_ROWS);
   if (r0 >= a.R) return;
   float wt[NG_MAX_CONTRIB];
 #pragma unroll
   for (int i = 0; i < NG_MAX_CONTRIB; i++) wt[i] = i < a.nc ? ng_fusion_weight(a.c[i].fw, a.c[i].n, a.c[i].idx) : 0.0f;
-  float gamma = 0.0f, mean = 0.0f, rstd = 0.0f;
-  if (a.bn) { gamma = a.bn[c]; mean = a.bn[2 * W + c]; rstd = 1.0f / sqrtf(a.bn[3 * W + c] + NG_BN_EPS); }
+  float gamma = 0.0f, mean = 0.0f, rstd = 0.0f;      // (no beta here, so not gd_bn_load)
+  if (a.bn) { gamma = a.bn[c]; mean = a.bn[2 * W + c]; rstd = 1.0f / sqrtf(a.bn[3 * W + c] + GD_BN_EPS); }
   float ag = 0.0f, ab = 0.0f, abias = 0.0f;
   for (int r = r0; r < r1; r++) {
     const int b = r / ss, pix = r % ss, y = pix / s, x = pix % s;
@@ -371,10 +287,10 @@ struct NGDwBwdArgs {
 //   depthwise weight gradient  pdw[tap] += d u[r] * x[neighbour(r, tap)],  x = swish(s)
 //   depthwise data gradient    d x[r]    = sum_tap w[8 - tap] * d u[neighbour(r, tap)]
 //   fusion                     d s = d x * swish'(s);  pf[i] += d s * src_i   (exact products, added in double)
-__global__ __launch_bounds__(NG_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
-  __shared__ double red[3][NG_THREADS];
+__global__ __launch_bounds__(GD_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
+  __shared__ double red[3][GD_THREADS];
   const int W = a.W, s = a.s, ss = s * s, t = threadIdx.x;
-  const int64_t gid = (int64_t)blockIdx.x * NG_THREADS + t;
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + t;
   const int tile = (int)(gid / W), c = (int)(gid % W);
   const int r0 = tile * NG_TILE_ROWS, r1 = min(a.R, r0 + NG_TILE_ROWS);
   double af[3] = {0.0, 0.0, 0.0};
@@ -386,8 +302,8 @@ __global__ __launch_bounds__(NG_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
     for (int r = r0; r < r1; r++) {
       const int b = r / ss, pix = r % ss, y = pix / s, x = pix % s;
       const bool fresh = r == r0 || x == 0;
-      ng_win_step<true>(xw, fresh, a.S, r, y, x, s, W, c);
-      ng_win_step<false>(gw, fresh, a.G, r, y, x, s, W, c);
+      gd_win_step<true>(xw, fresh, a.S, r, y, x, s, W, c);
+      gd_win_step<false>(gw, fresh, a.G, r, y, x, s, W, c);
       const float gk = gw[1][1];
       float dx = 0.0f;
 #pragma unroll
@@ -395,8 +311,7 @@ __global__ __launch_bounds__(NG_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
         aw[tp] = fmaf(gk, xw[tp / 3][tp % 3], aw[tp]);
         dx = fmaf(wt[8 - tp], gw[tp / 3][tp % 3], dx);
       }
-      const float sv = a.S[(int64_t)r * W + c], sg = ng_sigmoid(sv);
-      const float ds = dx * (sg * (1.0f + sv * (1.0f - sg)));
+      const float ds = dx * gd_swish_grad(a.S[(int64_t)r * W + c]);
       a.DS[(int64_t)r * W + c] = ds;
 #pragma unroll
       for (int i = 0; i < 3; i++)
@@ -409,7 +324,7 @@ __global__ __launch_bounds__(NG_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
 #pragma unroll
   for (int i = 0; i < 3; i++) red[i][t] = af[i];
   __syncthreads();
-  for (int h = NG_THREADS / 2; h > 0; h >>= 1) {
+  for (int h = GD_THREADS / 2; h > 0; h >>= 1) {
     if (t < h) {
 #pragma unroll
       for (int i = 0; i < 3; i++) red[i][t] += red[i][t + h];
@@ -421,51 +336,22 @@ __global__ __launch_bounds__(NG_THREADS) void ng_dw_bwd_kernel(NGDwBwdArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// second pass: element e of job j = the sum of its partials src[e + k * stride], k < nparts, added in double in a FIXED
-// order: 16 threads share an element, thread j adds the partials j, j + 16, ... in index order, then thread 0 adds the 16
-// sums in order 0..15 and rounds once (the scheme of hg_reduce_kernel).  src == NULL: the element is zero (running statistics).
-#define NG_RED_E 16
-#define NG_RED_K 16
-#define NG_RED_JOBS 6
-struct NGRedJob { const float* src; float* dst; int64_t count, stride; int nparts; };
-struct NGReduceArgs { NGRedJob j[NG_RED_JOBS]; };
-static_assert(NG_RED_E * NG_RED_K == NG_THREADS, "one reduce workgroup = 16 elements x 16 partial lanes");
-__global__ __launch_bounds__(NG_THREADS) void ng_reduce_kernel(NGReduceArgs a) {
-  __shared__ double part[NG_RED_K][NG_RED_E + 1];
-  const NGRedJob& job = a.j[blockIdx.y];
-  const int el = threadIdx.x % NG_RED_E, kl = threadIdx.x / NG_RED_E;
-  const int64_t e = (int64_t)blockIdx.x * NG_RED_E + el;
-  if ((int64_t)blockIdx.x * NG_RED_E >= job.count) return;  // uniform over the workgroup
-  const bool live = e < job.count;
-  double s = 0.0;
-  if (live && job.src)
-    for (int k = kl; k < job.nparts; k += NG_RED_K) s += (double)job.src[e + k * job.stride];
-  part[kl][el] = s;
-  __syncthreads();
-  if (kl == 0 && live) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < NG_RED_K; j++) t += part[j][el];
-    job.dst[e] = (float)t;
-  }
-}
-
 // The fusion vector's gradient: a_i = <d s, src_i> = the sum of the workgroup sums pf[i][0 .. count) (thread t adds t, t + 256, ... in double,
 // thread 0 adds the 256 sums in order), then with r = relu(p), D = sum r + 1e-4, w = r / D:
 //   d L / d p_j = (a_j - sum_i a_i w_i) / D  where p_j > 0, else exactly 0.
 struct NGFusionArgs { const double* pf[3]; int n; int64_t count; const float* p; float* dp; };
-__global__ __launch_bounds__(NG_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
-  __shared__ double part[3][NG_THREADS];
+__global__ __launch_bounds__(GD_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
+  __shared__ double part[3][GD_THREADS];
   for (int i = 0; i < a.n; i++) {
     double s = 0.0;
-    for (int64_t k = threadIdx.x; k < a.count; k += NG_THREADS) s += a.pf[i][k];
+    for (int64_t k = threadIdx.x; k < a.count; k += GD_THREADS) s += a.pf[i][k];
     part[i][threadIdx.x] = s;
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
   double dot[3] = {0.0, 0.0, 0.0}, D = (double)NG_FUSION_EPS, mix = 0.0;
   for (int i = 0; i < a.n; i++) {
-    for (int k = 0; k < NG_THREADS; k++) dot[i] += part[i][k];
+    for (int k = 0; k < GD_THREADS; k++) dot[i] += part[i][k];
     D += (double)fmaxf(a.p[i], 0.0f);
   }
   for (int i = 0; i < a.n; i++) mix += dot[i] * ((double)fmaxf(a.p[i], 0.0f) / D);
@@ -476,7 +362,6 @@ __global__ __launch_bounds__(NG_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
 // host side
 static inline int64_t ng_node_stride(int W) { return (int64_t)9 * W + (int64_t)W * W + W + 4 * W; }
 static inline int64_t ng_lat_stride(int W, int K) { return (int64_t)W * K + W + 4 * W; }
-static inline unsigned ng_blocks(int64_t n) { return (unsigned)((n + NG_THREADS - 1) / NG_THREADS); }
 
 int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why) {
   if (phi == 6 || phi == 7) { *why = "neck: phi 6 and 7 fuse by plain sums at width 384 (no fast attention): not supported, phi must be in 0..5"; return HEP_ERR_UNSUPPORTED; }
@@ -500,9 +385,7 @@ int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why) {
   for (int l = 0; l < 5; l++) {
     p->s[l] = size / (8 << l); p->R[l] = batch * p->s[l] * p->s[l];
     p->ntiles[l] = (p->R[l] + NG_TILE_ROWS - 1) / NG_TILE_ROWS;
-    int ns = p->R[l] / 512; if (ns < 1) ns = 1; if (ns > NG_MAX_SLABS) ns = NG_MAX_SLABS;
-    p->slab_rows[l] = ((p->R[l] + ns - 1) / ns + NG_BK - 1) / NG_BK * NG_BK;
-    p->nslab[l] = (p->R[l] + p->slab_rows[l] - 1) / p->slab_rows[l];
+    gd_slabs(p->R[l], NG_MAX_SLABS, &p->slab_rows[l], &p->nslab[l]);
   }
   int64_t w = 0;
   auto take = [&](int64_t n) { const int64_t at = w; w += (n + 3) / 4 * 4; return at; };
@@ -572,10 +455,10 @@ void ng_node_sources(const NGPlan& p, float* ws, int cell, int j, NGSrc src[3]) 
 }
 
 void ng_gemm(int mode, const NGGemmArgs& m, int nslab, hipStream_t st) {
-  const int ntm = (m.I + NG_BM - 1) / NG_BM;
-  if (mode == NG_FWD) hipLaunchKernelGGL(ng_gemm_kernel<NG_FWD>, dim3(ntm * m.ntn), dim3(NG_THREADS), 0, st, m);
-  else if (mode == NG_DATA) hipLaunchKernelGGL(ng_gemm_kernel<NG_DATA>, dim3(ntm * m.ntn), dim3(NG_THREADS), 0, st, m);
-  else hipLaunchKernelGGL(ng_gemm_kernel<NG_WGRAD>, dim3(ntm * m.ntn, 1, nslab), dim3(NG_THREADS), 0, st, m);
+  const int ntm = (m.I + GD_BM - 1) / GD_BM;
+  if (mode == NG_FWD) hipLaunchKernelGGL(ng_gemm_kernel<NG_FWD>, dim3(ntm * m.ntn), dim3(GD_THREADS), 0, st, m);
+  else if (mode == NG_DATA) hipLaunchKernelGGL(ng_gemm_kernel<NG_DATA>, dim3(ntm * m.ntn), dim3(GD_THREADS), 0, st, m);
+  else hipLaunchKernelGGL(ng_gemm_kernel<NG_WGRAD>, dim3(ntm * m.ntn, 1, nslab), dim3(GD_THREADS), 0, st, m);
 }
 
 // consumers of the map `code` among the nodes of `cell`, in node order
@@ -597,12 +480,12 @@ void ng_collect_pool(float* g, uint8_t* am, NGGatherArgs* ga) {
 }
 
 // BatchNorm partials [tile][W] -> gamma, beta, zeros for the statistics, and the conv bias
-void ng_bn_jobs(const NGPlan& p, float* ws, int level, float* dbias, float* dbn, NGReduceArgs* rd, int at) {
+void ng_bn_jobs(const NGPlan& p, float* ws, int level, float* dbias, float* dbn, GDReduceArgs<NG_RED_JOBS>* rd, int at) {
   const int W = p.W, T = p.ntiles[level];
-  rd->j[at + 0] = NGRedJob{ws + p.o_pb[0], dbn, W, W, T};
-  rd->j[at + 1] = NGRedJob{ws + p.o_pb[1], dbn + W, W, W, T};
-  rd->j[at + 2] = NGRedJob{nullptr, dbn + 2 * W, 2 * W, 0, 0};
-  rd->j[at + 3] = NGRedJob{ws + p.o_pb[2], dbias, W, W, T};
+  rd->j[at + 0] = GDRedJob{ws + p.o_pb[0], dbn, W, W, T};
+  rd->j[at + 1] = GDRedJob{ws + p.o_pb[1], dbn + W, W, W, T};
+  rd->j[at + 2] = GDRedJob{nullptr, dbn + 2 * W, 2 * W, 0, 0};
+  rd->j[at + 3] = GDRedJob{ws + p.o_pb[2], dbias, W, W, T};
 }
 }  // namespace
 
@@ -611,18 +494,18 @@ void launch_neck_forward(const NGPlan& p, const float* params, const float* cons
   NGPackArgs pk{}; pk.cells = p.cells;
   for (int r = 0; r < p.cells; r++) { pk.src[r] = p.p_cell[r]; pk.dst[r] = p.o_pp[r]; }
   pk.src[p.cells] = p.nparams;
-  hipLaunchKernelGGL(ng_pack_kernel, dim3(ng_blocks(p.nparams)), dim3(NG_THREADS), 0, st, pk, params, ws);
+  hipLaunchKernelGGL(ng_pack_kernel, dim3(gd_blocks(p.nparams)), dim3(GD_THREADS), 0, st, pk, params, ws);
   for (int t = 0; t < 3; t++)
-    hipLaunchKernelGGL(ng_rows_from_nchw_kernel, dim3(ng_blocks((int64_t)p.R[t] * p.tapc[t])), dim3(NG_THREADS), 0, st, B, p.tapc[t], p.s[t] * p.s[t], taps[t], ws + p.o_tap[t]);
+    hipLaunchKernelGGL(ng_rows_from_nchw_kernel, dim3(gd_blocks((int64_t)p.R[t] * p.tapc[t])), dim3(GD_THREADS), 0, st, B, p.tapc[t], p.s[t] * p.s[t], taps[t], ws + p.o_tap[t]);
   for (int i = 0; i < NG_LATERALS; i++) {
     const int t = kLatTap[i], K = p.tapc[t];
     const float* lp = ng_lat_params(p, ws, i);
     NGGemmArgs m{}; m.A = ws + p.o_tap[t]; m.Bm = lp; m.bias = lp + (int64_t)W * K; m.bn = lp + (int64_t)W * K + W;
-    m.C = ws + p.o_lz[i]; m.C2 = ws + p.o_ly[i]; m.I = p.R[t]; m.J = W; m.K = K; m.lda = K; m.ldb = K; m.ldc = W; m.ntn = (W + NG_BN - 1) / NG_BN;
+    m.C = ws + p.o_lz[i]; m.C2 = ws + p.o_ly[i]; m.I = p.R[t]; m.J = W; m.K = K; m.lda = K; m.ldb = K; m.ldc = W; m.ntn = (W + GD_BN - 1) / GD_BN;
     ng_gemm(NG_FWD, m, 1, st);
   }
-  hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(ng_blocks((int64_t)p.R[3] * W)), dim3(NG_THREADS), 0, st, B, p.s[2], W, (const float*)(ws + p.o_ly[3]), ws + p.o_p6, ng_bytes(ws, p.o_am6));
-  hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(ng_blocks((int64_t)p.R[4] * W)), dim3(NG_THREADS), 0, st, B, p.s[3], W, (const float*)(ws + p.o_p6), ws + p.o_p7, ng_bytes(ws, p.o_am7));
+  hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(gd_blocks((int64_t)p.R[3] * W)), dim3(GD_THREADS), 0, st, B, p.s[2], W, (const float*)(ws + p.o_ly[3]), ws + p.o_p6, ng_bytes(ws, p.o_am6));
+  hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(gd_blocks((int64_t)p.R[4] * W)), dim3(GD_THREADS), 0, st, B, p.s[3], W, (const float*)(ws + p.o_p6), ws + p.o_p7, ng_bytes(ws, p.o_am7));
   for (int r = 0; r < p.cells; r++)
     for (int j = 0; j < NG_NODES; j++) {
       const int l = kNodeLevel[j], R = p.R[l];
@@ -631,25 +514,25 @@ void launch_neck_forward(const NGPlan& p, const float* params, const float* cons
       ng_node_sources(p, ws, r, j, f.src);
       f.am_out = j >= 4 ? ng_bytes(ws, p.o_am[r][j]) : nullptr;
       f.fw = ws + p.o_pp[r] + kNodeFw[j]; f.S = ws + p.o_s[r][j]; f.X = ws + p.o_x;
-      hipLaunchKernelGGL(ng_fuse_fwd_kernel, dim3(ng_blocks((int64_t)R * W)), dim3(NG_THREADS), 0, st, f);
-      hipLaunchKernelGGL(ng_dw_fwd_kernel, dim3(ng_blocks((int64_t)((R + NG_DW_ROWS - 1) / NG_DW_ROWS) * W)), dim3(NG_THREADS), 0, st, R, p.s[l], W,
+      hipLaunchKernelGGL(ng_fuse_fwd_kernel, dim3(gd_blocks((int64_t)R * W)), dim3(GD_THREADS), 0, st, f);
+      hipLaunchKernelGGL(ng_dw_fwd_kernel, dim3(gd_blocks((int64_t)((R + GD_DW_ROWS - 1) / GD_DW_ROWS) * W)), dim3(GD_THREADS), 0, st, R, p.s[l], W,
                          (const float*)(ws + p.o_x), np, ws + p.o_u[r][j]);
       NGGemmArgs m{}; m.A = ws + p.o_u[r][j]; m.Bm = np + 9 * W; m.bias = np + 9 * W + (int64_t)W * W; m.bn = m.bias + W;
-      m.C = ws + p.o_z[r][j]; m.C2 = ws + p.o_y[r][j]; m.I = R; m.J = W; m.K = W; m.lda = W; m.ldb = W; m.ldc = W; m.ntn = (W + NG_BN - 1) / NG_BN;
+      m.C = ws + p.o_z[r][j]; m.C2 = ws + p.o_y[r][j]; m.I = R; m.J = W; m.K = W; m.lda = W; m.ldb = W; m.ldc = W; m.ntn = (W + GD_BN - 1) / GD_BN;
       ng_gemm(NG_FWD, m, 1, st);
     }
   for (int l = 0; l < 5; l++) {
     NGRows3 rows{}; rows.p[0] = ws + p.o_y[p.cells - 1][kOutNode[l]]; rows.n = 1;
-    hipLaunchKernelGGL(ng_nchw_from_rows_kernel, dim3(ng_blocks((int64_t)p.R[l] * W)), dim3(NG_THREADS), 0, st, B, W, p.s[l] * p.s[l], rows, feats[l]);
+    hipLaunchKernelGGL(ng_nchw_from_rows_kernel, dim3(gd_blocks((int64_t)p.R[l] * W)), dim3(GD_THREADS), 0, st, B, W, p.s[l] * p.s[l], rows, feats[l]);
   }
 }
 
 void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t st) {
-  const int W = p.W, B = p.B, ntn = (W + NG_BN - 1) / NG_BN;
+  const int W = p.W, B = p.B, ntn = (W + GD_BN - 1) / GD_BN;
   auto gather = [&](NGGatherArgs& ga, int l) {
     ga.B = B; ga.s = p.s[l]; ga.W = W; ga.R = p.R[l];
     ga.pgamma = ws + p.o_pb[0]; ga.pbeta = ws + p.o_pb[1]; ga.pbias = ws + p.o_pb[2];
-    hipLaunchKernelGGL(ng_gather_kernel, dim3(ng_blocks((int64_t)p.ntiles[l] * W)), dim3(NG_THREADS), 0, st, ga);
+    hipLaunchKernelGGL(ng_gather_kernel, dim3(gd_blocks((int64_t)p.ntiles[l] * W)), dim3(GD_THREADS), 0, st, ga);
   };
   for (int r = p.cells - 1; r >= 0; r--) {
     float* gcell = grad_params + p.p_cell[r];
@@ -675,15 +558,15 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
       db.G = ws + p.o_du; db.S = ws + p.o_s[r][j]; db.w = np; db.DS = ws + p.o_ds[r & 1][j]; db.pdw = ws + p.o_pdw;
       ng_node_sources(p, ws, r, j, db.src);
       for (int i = 0; i < 3; i++) db.pf[i] = reinterpret_cast<double*>(ws + p.o_pf[i]);
-      hipLaunchKernelGGL(ng_dw_bwd_kernel, dim3(ng_blocks((int64_t)T * W)), dim3(NG_THREADS), 0, st, db);
-      NGReduceArgs rd{};
-      rd.j[0] = NGRedJob{ws + p.o_pw, gn + 9 * W, (int64_t)W * W, (int64_t)W * W, p.nslab[l]};
-      rd.j[1] = NGRedJob{ws + p.o_pdw, gn, (int64_t)W * 9, (int64_t)W * 9, T};
+      hipLaunchKernelGGL(ng_dw_bwd_kernel, dim3(gd_blocks((int64_t)T * W)), dim3(GD_THREADS), 0, st, db);
+      GDReduceArgs<NG_RED_JOBS> rd{};
+      rd.j[0] = GDRedJob{ws + p.o_pw, gn + 9 * W, (int64_t)W * W, (int64_t)W * W, p.nslab[l]};
+      rd.j[1] = GDRedJob{ws + p.o_pdw, gn, (int64_t)W * 9, (int64_t)W * 9, T};
       ng_bn_jobs(p, ws, l, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, &rd, 2);
-      hipLaunchKernelGGL(ng_reduce_kernel, dim3((unsigned)(((int64_t)W * W + NG_RED_E - 1) / NG_RED_E), NG_RED_JOBS), dim3(NG_THREADS), 0, st, rd);
-      NGFusionArgs fa{}; fa.n = kNodeNsrc[j]; fa.count = ng_blocks((int64_t)T * W); fa.p = ws + p.o_pp[r] + kNodeFw[j]; fa.dp = gcell + kNodeFw[j];
+      hipLaunchKernelGGL(gd_reduce_kernel<NG_RED_JOBS>, dim3((unsigned)(((int64_t)W * W + GD_RED_E - 1) / GD_RED_E), NG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
+      NGFusionArgs fa{}; fa.n = kNodeNsrc[j]; fa.count = gd_blocks((int64_t)T * W); fa.p = ws + p.o_pp[r] + kNodeFw[j]; fa.dp = gcell + kNodeFw[j];
       for (int i = 0; i < 3; i++) fa.pf[i] = reinterpret_cast<const double*>(ws + p.o_pf[i]);
-      hipLaunchKernelGGL(ng_fusion_kernel, dim3(1), dim3(NG_THREADS), 0, st, fa);
+      hipLaunchKernelGGL(ng_fusion_kernel, dim3(1), dim3(GD_THREADS), 0, st, fa);
     }
   }
   // cell 0's own inputs.  p7_in and p6_in are pooled maps (no parameters): their gradients feed the pool below them.
@@ -701,23 +584,23 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
     ga.Z = ws + p.o_lz[i]; ga.bn = lp + (int64_t)W * K + W; ga.out = ws + p.o_dz;
     gather(ga, t);
     NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_tap[t]; mw.C = ws + p.o_pw; mw.I = W; mw.J = K; mw.K = R; mw.lda = W; mw.ldb = K;
-    mw.ntn = (K + NG_BN - 1) / NG_BN; mw.slab_rows = p.slab_rows[t];
+    mw.ntn = (K + GD_BN - 1) / GD_BN; mw.slab_rows = p.slab_rows[t];
     ng_gemm(NG_WGRAD, mw, p.nslab[t], st);
     if (grad_taps) {
       NGGemmArgs md{}; md.A = ws + p.o_dz; md.Bm = lp; md.C = ws + p.o_dtap[i]; md.I = R; md.J = K; md.K = W; md.lda = W; md.ldb = K; md.ldc = K;
-      md.ntn = (K + NG_BN - 1) / NG_BN;
+      md.ntn = (K + GD_BN - 1) / GD_BN;
       ng_gemm(NG_DATA, md, 1, st);
     }
-    NGReduceArgs rd{};
-    rd.j[0] = NGRedJob{ws + p.o_pw, gl, (int64_t)W * K, (int64_t)W * K, p.nslab[t]};
-    rd.j[1] = NGRedJob{nullptr, nullptr, 0, 0, 0};
+    GDReduceArgs<NG_RED_JOBS> rd{};
+    rd.j[0] = GDRedJob{ws + p.o_pw, gl, (int64_t)W * K, (int64_t)W * K, p.nslab[t]};
+    rd.j[1] = GDRedJob{nullptr, nullptr, 0, 0, 0};
     ng_bn_jobs(p, ws, t, gl + (int64_t)W * K, gl + (int64_t)W * K + W, &rd, 2);
-    hipLaunchKernelGGL(ng_reduce_kernel, dim3((unsigned)(((int64_t)W * K + NG_RED_E - 1) / NG_RED_E), NG_RED_JOBS), dim3(NG_THREADS), 0, st, rd);
+    hipLaunchKernelGGL(gd_reduce_kernel<NG_RED_JOBS>, dim3((unsigned)(((int64_t)W * K + GD_RED_E - 1) / GD_RED_E), NG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
   }
   if (grad_taps)
     for (int t = 0; t < 3; t++) {
       NGRows3 rows{};
       for (int i = 0; i < NG_LATERALS; i++) if (kLatTap[i] == t) rows.p[rows.n++] = ws + p.o_dtap[i];
-      hipLaunchKernelGGL(ng_nchw_from_rows_kernel, dim3(ng_blocks((int64_t)p.R[t] * p.tapc[t])), dim3(NG_THREADS), 0, st, B, p.tapc[t], p.s[t] * p.s[t], rows, grad_taps[t]);
+      hipLaunchKernelGGL(ng_nchw_from_rows_kernel, dim3(gd_blocks((int64_t)p.R[t] * p.tapc[t])), dim3(GD_THREADS), 0, st, B, p.tapc[t], p.s[t] * p.s[t], rows, grad_taps[t]);
     }
 }

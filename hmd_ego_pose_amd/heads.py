@@ -19,14 +19,13 @@ train.py:162) is out of scope, and so is bf16 training (the BiFPN and the backbo
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Sequence, Tuple
 
 import torch
-from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _capi
+from . import _capi, _trainable
+from ._trainable import ptrs as _ptrs
 from .arch import HEAD_NAMES, NUM_ANCHORS, get_arch, level_sizes, param_spec
 
 
@@ -38,18 +37,7 @@ def head_spec(compound_coef: int, num_classes: int = 1) -> List[Tuple[str, tuple
 def flat_keys(compound_coef: int, num_classes: int = 1) -> List[Tuple[str, tuple]]:
     """The tensors of the flat fp32 parameter buffer of hep_heads_*_device, in buffer order: ``head_spec`` without the
     int64 ``num_batches_tracked`` counters."""
-    return [(k, s) for k, s in head_spec(compound_coef, num_classes) if not k.endswith("num_batches_tracked")]
-
-
-def _numel(shape) -> int:
-    n = 1
-    for d in shape:
-        n *= int(d)
-    return n
-
-
-def _ptrs(tensors):
-    return None if tensors is None else _capi.ptr_array(list(tensors))
+    return _trainable.without_counters(head_spec(compound_coef, num_classes))
 
 
 def heads_forward(flat: torch.Tensor, feats: Sequence[torch.Tensor], compound_coef: int, num_classes: int, size: int):
@@ -99,14 +87,13 @@ class _Heads(torch.autograd.Function):
         phi, num_classes, size, shapes = ctx.cfg
         N = NUM_ANCHORS * sum(s * s for s in level_sizes(size))
         B = shapes[0][0]
-        gs = [torch.zeros((B, N, k), dtype=torch.float32, device=flat.device) if g is None else g.to(torch.float32).contiguous()
-              for g, k in zip(grad_outs, (4, num_classes, 3, 3, 63))]
+        gs = _trainable.cotangents(grad_outs, [(B, N, k) for k in (4, num_classes, 3, 3, 63)], flat.device)
         want_feats = any(ctx.needs_input_grad[4:])
         g_flat, g_feats = heads_backward(flat, gs, ws, phi, num_classes, size, shapes if want_feats else None)
         return (g_flat if ctx.needs_input_grad[0] else None, None, None, None, *(g_feats if want_feats else (None,) * 5))
 
 
-class TrainableHeads(nn.Module):
+class TrainableHeads(_trainable.TrainablePart):
     """The five head nets as an ``nn.Module`` whose parameters and buffers carry exactly the reference's head keys
     (``regressor.conv_list.0.depthwise_conv.conv.weight`` ... ``hand_net.bn_list.4.2.running_var``), so that
     ``load_state_dict(model.state_dict(), strict=False)`` fills it.  ``forward(feats)`` takes the 5-tuple of BiFPN maps
@@ -115,41 +102,18 @@ class TrainableHeads(nn.Module):
     Runs on a ROCm device only (no CPU fallback).  BatchNorm uses the running statistics in EVERY mode, ``train()``
     included (see the module docstring); they receive no gradient and never change."""
 
+    NOUN, spec = "head", staticmethod(head_spec)
+
     def __init__(self, compound_coef: int = 0, num_classes: int = 1):
         super().__init__()
-        from .model import _attach
         self.compound_coef = int(compound_coef)
         self.num_classes = int(num_classes)
         self.arch = get_arch(self.compound_coef)
-        for key, shape in head_spec(self.compound_coef, self.num_classes):
-            _attach(self, key, shape)
-        self._flat_keys = [k for k, _ in flat_keys(self.compound_coef, self.num_classes)]
+        self._attach_spec(self.compound_coef, self.num_classes)
 
     @classmethod
-    def from_model(cls, model) -> "TrainableHeads":
-        """Heads with the tensors of an ``HMDEgoPose`` (or any module with the reference's keys), on the model's device."""
-        h = cls(model.compound_coef, model.num_classes)
-        sd = model.state_dict()
-        missing = [k for k, _ in head_spec(h.compound_coef, h.num_classes) if k not in sd]
-        if missing:
-            raise KeyError(f"the model's state_dict lacks head tensors, e.g. {missing[0]}")
-        h.load_state_dict(sd, strict=False)
-        return h.to(next(iter(sd.values())).device)
-
-    def export_to(self, model):
-        """Copy every head tensor into ``model`` (an ``HMDEgoPose``) and drop its packed device weights."""
-        own, dst = self.state_dict(), model.state_dict()
-        with torch.no_grad():
-            for k, v in own.items():
-                dst[k].copy_(v)
-        model.invalidate()
-        return model
-
-    def flat_parameters(self) -> torch.Tensor:
-        """The flat fp32 buffer of hep_heads_*_device (autograd-tracked: its gradient splits back onto the parameters)."""
-        tensors = dict(self.named_parameters())
-        tensors.update(dict(self.named_buffers()))
-        return torch.cat([tensors[k].reshape(-1) for k in self._flat_keys])
+    def _model_cfg(cls, model):
+        return (model.compound_coef, model.num_classes)
 
     def _check_feats(self, feats):
         if len(feats) != 5:
@@ -179,9 +143,4 @@ class TrainableHeads(nn.Module):
 
 def param_layout(compound_coef: int, num_classes: int = 1):
     """(total floats, [offset of every ``flat_keys`` tensor]) as the library reports them."""
-    l = _capi.lib()
-    total = _capi.check(l.hep_heads_param_count(compound_coef, num_classes))
-    n = _capi.check(l.hep_heads_param_layout(compound_coef, num_classes, None, 0))
-    arr = (ctypes.c_int64 * n)()
-    _capi.check(l.hep_heads_param_layout(compound_coef, num_classes, arr, n))
-    return int(total), [int(v) for v in arr]
+    return _trainable.param_layout("heads", compound_coef, num_classes)

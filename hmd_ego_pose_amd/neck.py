@@ -19,14 +19,13 @@ in front of the neck.  Out of scope: batch-statistics BatchNorm and bf16 trainin
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, List, Sequence, Tuple
 
 import torch
-from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _capi
+from . import _capi, _trainable
+from ._trainable import ptrs as _ptrs
 from .arch import get_arch, level_sizes, param_spec
 
 
@@ -46,11 +45,7 @@ def neck_spec(compound_coef: int) -> List[Tuple[str, tuple]]:
 def flat_keys(compound_coef: int) -> List[Tuple[str, tuple]]:
     """The tensors of the flat fp32 parameter buffer of hep_neck_*_device, in buffer order: ``neck_spec`` without the int64
     ``num_batches_tracked`` counters."""
-    return [(k, s) for k, s in neck_spec(compound_coef) if not k.endswith("num_batches_tracked")]
-
-
-def _ptrs(tensors):
-    return None if tensors is None else _capi.ptr_array(list(tensors))
+    return _trainable.without_counters(neck_spec(compound_coef))
 
 
 def neck_forward(flat: torch.Tensor, taps: Sequence[torch.Tensor], compound_coef: int, size: int):
@@ -83,15 +78,7 @@ def neck_backward(flat: torch.Tensor, grad_feats: Sequence[torch.Tensor], ws: to
 
 def stage_views(ws: torch.Tensor, compound_coef: int, size: int, batch: int) -> Dict[str, torch.Tensor]:
     """name -> float32 view [B, s, s, W] (NHWC) of every tensor hep_neck_stage_info names in the workspace of a forward."""
-    l = _capi.lib()
-    out = {}
-    for i in range(_capi.check(l.hep_neck_stage_count(compound_coef))):
-        nm = ctypes.c_char_p(); dims = (ctypes.c_int64 * 4)(); off = ctypes.c_int64()
-        _capi.check(l.hep_neck_stage_info(compound_coef, size, batch, i, ctypes.byref(nm), dims, ctypes.byref(off)))
-        shape = tuple(int(d) for d in dims)
-        n = shape[0] * shape[1] * shape[2] * shape[3]
-        out[nm.value.decode()] = ws[off.value:off.value + 4 * n].view(torch.float32).view(shape)
-    return out
+    return _trainable.stage_views("neck", ws, compound_coef, size, batch)
 
 
 class _Neck(torch.autograd.Function):
@@ -109,14 +96,13 @@ class _Neck(torch.autograd.Function):
     def backward(ctx, *grad_feats):
         flat, ws = ctx.saved_tensors
         phi, size, tap_shapes, feat_shapes = ctx.cfg
-        gs = [torch.zeros(s, dtype=torch.float32, device=flat.device) if g is None else g.to(torch.float32).contiguous()
-              for g, s in zip(grad_feats, feat_shapes)]
+        gs = _trainable.cotangents(grad_feats, feat_shapes, flat.device)
         want_taps = any(ctx.needs_input_grad[3:])
         g_flat, g_taps = neck_backward(flat, gs, ws, phi, size, tap_shapes if want_taps else None)
         return (g_flat if ctx.needs_input_grad[0] else None, None, None, *(g_taps if want_taps else (None,) * 3))
 
 
-class TrainableNeck(nn.Module):
+class TrainableNeck(_trainable.TrainablePart):
     """The BiFPN neck as an ``nn.Module`` whose parameters and buffers carry exactly the reference's ``bifpn.*`` keys, so that
     ``load_state_dict(model.state_dict(), strict=False)`` fills it.  ``forward(taps)`` takes the three backbone taps
     (P3, P4, P5: float32 NCHW, ``backbone_taps``) and gives the 5-tuple of maps ``TrainableHeads`` takes, with a ``grad_fn``:
@@ -124,41 +110,14 @@ class TrainableNeck(nn.Module):
     device only (no CPU fallback).  BatchNorm uses the running statistics in EVERY mode, ``train()`` included; they receive
     no gradient and never change."""
 
+    NOUN, spec = "BiFPN", staticmethod(neck_spec)
+
     def __init__(self, compound_coef: int = 0):
         super().__init__()
-        from .model import _attach
         self.compound_coef = int(compound_coef)
         _check_phi(self.compound_coef)
         self.arch = get_arch(self.compound_coef)
-        for key, shape in neck_spec(self.compound_coef):
-            _attach(self, key, shape)
-        self._flat_keys = [k for k, _ in flat_keys(self.compound_coef)]
-
-    @classmethod
-    def from_model(cls, model) -> "TrainableNeck":
-        """A neck with the tensors of an ``HMDEgoPose`` (or any module with the reference's keys), on the model's device."""
-        n = cls(model.compound_coef)
-        sd = model.state_dict()
-        missing = [k for k, _ in neck_spec(n.compound_coef) if k not in sd]
-        if missing:
-            raise KeyError(f"the model's state_dict lacks BiFPN tensors, e.g. {missing[0]}")
-        n.load_state_dict(sd, strict=False)
-        return n.to(next(iter(sd.values())).device)
-
-    def export_to(self, model):
-        """Copy every ``bifpn.*`` tensor into ``model`` (an ``HMDEgoPose``) and drop its packed device weights."""
-        own, dst = self.state_dict(), model.state_dict()
-        with torch.no_grad():
-            for k, v in own.items():
-                dst[k].copy_(v)
-        model.invalidate()
-        return model
-
-    def flat_parameters(self) -> torch.Tensor:
-        """The flat fp32 buffer of hep_neck_*_device (autograd-tracked: its gradient splits back onto the parameters)."""
-        tensors = dict(self.named_parameters())
-        tensors.update(dict(self.named_buffers()))
-        return torch.cat([tensors[k].reshape(-1) for k in self._flat_keys])
+        self._attach_spec(self.compound_coef)
 
     def _check_taps(self, taps) -> int:
         if len(taps) != 3:
@@ -189,12 +148,7 @@ class TrainableNeck(nn.Module):
 
 def param_layout(compound_coef: int):
     """(total floats, [offset of every ``flat_keys`` tensor]) as the library reports them."""
-    l = _capi.lib()
-    total = _capi.check(l.hep_neck_param_count(compound_coef))
-    n = _capi.check(l.hep_neck_param_layout(compound_coef, None, 0))
-    arr = (ctypes.c_int64 * n)()
-    _capi.check(l.hep_neck_param_layout(compound_coef, arr, n))
-    return int(total), [int(v) for v in arr]
+    return _trainable.param_layout("neck", compound_coef)
 
 
 def backbone_taps(model, x: torch.Tensor):

@@ -5,7 +5,9 @@ Shapes: phi 0 @ 256 batch 16 and phi 3 @ 512 batch 8 (the benchmarked inference 
 and cotangents.  Rows (milliseconds, median of --reps timed repetitions after --warmup):
   hip fwd            heads.heads_forward (hep_heads_forward_device; the workspace is allocated by torch's caching allocator)
   hip bwd            heads.heads_backward on that workspace (hep_heads_backward_device, parameter and map gradients)
-  hip fwd+bwd        TrainableHeads(feats) + backward through autograd (adds the flat-parameter cat and its split)
+  hip fwd+bwd        the two back to back (the row tools/neck_grad_time.py and tools/backbone_grad_time.py call the same)
+  hip fwd+bwd (autograd)  TrainableHeads(feats) + backward through autograd (adds the flat-parameter cat of 363 tensors and its
+                     split; at phi 0 the row is 2 .. 4 ms around 1 ms of kernels, so presumably bound by that host work)
   torch fwd / fwd+bwd  stock PyTorch-ROCm autograd through oracle.efficientpose_ref.head on the same device and inputs:
                      the baseline (the same function as ~1000 small launches), not the code under test
 and the launch counts of the two HIP entry points.
@@ -57,6 +59,10 @@ def one_shape(phi, size, batch, reps, warmup):
 
     fg = [f.clone().requires_grad_(True) for f in feats]
 
+    def hip_abi():
+        _o, w = HD.heads_forward(flat, feats, phi, classes, size)
+        HD.heads_backward(flat, cots, w, phi, classes, size, shapes)
+
     def hip_fb():
         h.zero_grad(set_to_none=True)
         for f in fg:
@@ -81,6 +87,7 @@ def one_shape(phi, size, batch, reps, warmup):
     rows = {
         "hip fwd": timed(lambda: HD.heads_forward(flat, feats, phi, classes, size), reps, warmup),
         "hip bwd": timed(lambda: HD.heads_backward(flat, cots, ws, phi, classes, size, shapes), reps, warmup),
+        "hip fwd+bwd": timed(hip_abi, reps, warmup),
         "hip fwd+bwd (autograd)": timed(hip_fb, reps, warmup),
         "torch fwd": timed(torch_f, reps, warmup),
         "torch fwd+bwd (autograd)": timed(torch_fb, reps, warmup),
