@@ -357,8 +357,9 @@ class HMDEgoPose(nn.Module):
     def reset_parameters(self, seed: int = 0):
         from .weights import seeded_state_dict
         with torch.no_grad():
+            own = self.state_dict()      # once: building it per key made the constructor quadratic in the key count (20 s at phi 4)
             for k, v in seeded_state_dict(self.compound_coef, seed, num_classes=self.num_classes).items():
-                self.state_dict()[k].copy_(v)
+                own[k].copy_(v)
 
     def invalidate(self):
         """Drop the packed device weights; they are rebuilt on the next forward.  Called after

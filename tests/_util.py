@@ -1,5 +1,6 @@
 """Shared helpers for the tests: seeded inputs (same recipe as tests/golden/make_golden.py)
 and golden-digest comparison."""
+import functools
 import json
 import os
 
@@ -31,6 +32,14 @@ def seeded_input(shape, seed, kind="normal"):
     return a.astype(np.float32)
 
 
+@functools.lru_cache(maxsize=8)
+def seeded_state_dict_once(phi, seed=0, num_classes=1):
+    """hmd_ego_pose_amd.seeded_state_dict, kept for the next caller: at phi 5 one call draws 34 M values (1 to 2 s) and a
+    gradient case needs the same weights for the module, both oracle evaluations and its checks.  Read-only for every caller."""
+    from hmd_ego_pose_amd import seeded_state_dict
+    return seeded_state_dict(phi, seed, num_classes=num_classes)
+
+
 def golden_meta():
     with open(os.path.join(GOLDEN, "golden_meta.json")) as f:
         return json.load(f)
@@ -47,6 +56,58 @@ def strides_for(size, key, batch=1):
     if key.startswith("trace_"):
         return (16139 if big else 1009) if size == 256 else (131071 if big else 8191)
     return (1543 if big else 97) if size == 256 else (6353 if big else 397)
+
+
+ARCH_DIGEST_PHI = (1, 2, 4, 5, 6, 7)     # the phi without a net_*.npz of their own: forward digests in tests/golden/arch_all_phi.npz
+ARCH_DIGEST_SIZE = 128
+
+
+def arch_digest_stride(key, n):
+    """Slice stride of tests/golden/arch_all_phi.npz (size 128, batch 1): ``strides_for`` where that keeps at least 16 samples
+    of the n elements, else 7 (the top-level maps and taps hold a few hundred elements)."""
+    s = strides_for(ARCH_DIGEST_SIZE, key, 1)
+    return s if n >= 16 * s else 7
+
+
+def golden_arch():
+    """(meta of tests/golden/arch_all_phi.json, the slices of arch_all_phi.npz): tests/golden/make_golden_arch.py."""
+    with open(os.path.join(GOLDEN, "arch_all_phi.json")) as f:
+        return json.load(f), np.load(os.path.join(GOLDEN, "arch_all_phi.npz"))
+
+
+GUARD_BYTES = 1 << 20
+GUARD_PATTERN = 0x5AC3A53C               # as a float 2.75e16: nothing a kernel computes here
+
+
+class GuardedWorkspace:
+    """An exact-size, 16-byte aligned workspace window inside a larger device buffer of the test's own, GUARD_BYTES of guard on
+    each side.  The window starts out as NaN (a read of scratch that nothing wrote poisons the result), the guards as a fixed
+    bit pattern; ``changed()`` lists the guards a kernel wrote into.  The guards are this buffer's memory, so an overrun of
+    up to GUARD_BYTES is seen as a changed byte and touches nothing else."""
+
+    def __init__(self, nbytes, device):
+        import torch
+        assert nbytes > 0 and nbytes % 16 == 0
+        self.buf = torch.empty((GUARD_BYTES + nbytes + GUARD_BYTES + 16,), dtype=torch.uint8, device=device)
+        lo = (-self.buf.data_ptr()) % 16
+        self.nbytes = nbytes
+        self.below = self.buf[lo:lo + GUARD_BYTES].view(torch.int32)
+        self.window = self.buf[lo + GUARD_BYTES:lo + GUARD_BYTES + nbytes]
+        self.above = self.buf[lo + GUARD_BYTES + nbytes:lo + 2 * GUARD_BYTES + nbytes].view(torch.int32)
+        self.below.fill_(GUARD_PATTERN)
+        self.above.fill_(GUARD_PATTERN)
+        self.window.view(torch.float32).fill_(float("nan"))
+        self.ptr = self.window.data_ptr()
+        assert self.ptr % 16 == 0 and self.above.data_ptr() == self.ptr + nbytes and self.below.data_ptr() + GUARD_BYTES == self.ptr
+
+    def changed(self):
+        """[(which guard, changed 32-bit words, byte offset of the first from the guard's start)]; empty when both are intact."""
+        out = []
+        for name, g in (("below", self.below), ("above", self.above)):
+            bad = (g != GUARD_PATTERN).nonzero()
+            if bad.numel():
+                out.append((name, int(bad.numel()), 4 * int(bad[0])))
+        return out
 
 
 def check_digest(name, arr, info, ref_slice, stride, atol, rtol=0.0):

@@ -17,8 +17,20 @@ Measured on MI355X (device | float32 torch on the CPU | bound; NOTEBOOK.md secti
   phi0_s384_b1        2.37e-6 | 1.87e-6 | 7.47e-6   4.95e-6 | 4.29e-6 | 1.72e-5   1.27e-5 | 8.97e-6 | 3.59e-5   1.14e-5 | 6.73e-6 | 2.69e-5
   phi3_s128_b1        1.23e-6 | 8.49e-7 | 3.40e-6   2.40e-6 | 1.59e-6 | 6.36e-6   6.00e-6 | 3.41e-6 | 1.37e-5   5.94e-6 | 4.02e-6 | 1.61e-5
   drop-connect case   1.78e-6 | 1.30e-6 | 5.21e-6   3.15e-6 | 3.34e-6 | 1.34e-5   5.24e-6 | 5.09e-6 | 2.03e-5   5.43e-6 | 5.78e-6 | 2.31e-5
-Forward against the session (worst stage): phi 0 @ 256 b2 2.2e-6, b16 2.6e-6, phi 0 @ 128 2.5e-6, phi 0 @ 384 2.7e-6, phi 3 @ 512 3.1e-6
-(bound 1e-3).
+  phi1_s128_b1        2.90e-6 | 2.21e-6 | 8.85e-6   7.47e-6 | 4.61e-6 | 1.85e-5   1.22e-5 | 2.28e-5 | 9.10e-5   1.80e-5 | 2.29e-5 | 9.14e-5
+  phi2_s128_b1        1.57e-6 | 1.16e-6 | 4.62e-6   4.63e-6 | 2.05e-6 | 8.18e-6   1.19e-5 | 1.51e-5 | 6.04e-5   1.20e-5 | 1.52e-5 | 6.09e-5
+  phi4_s128_b1        1.93e-6 | 1.01e-6 | 4.04e-6   7.22e-6 | 4.88e-6 | 1.95e-5   1.78e-5 | 1.15e-5 | 4.59e-5   2.80e-5 | 1.15e-5 | 4.61e-5
+  phi5_s128_b1        2.43e-6 | 1.69e-6 | 6.77e-6   9.88e-6 | 6.23e-6 | 2.49e-5   2.19e-5 | 1.61e-5 | 6.45e-5   2.29e-5 | 1.61e-5 | 6.45e-5
+  phi6_s128_b1        1.92e-6 | 8.80e-7 | 3.52e-6   5.59e-6 | 3.80e-6 | 1.52e-5   1.49e-5 | 7.07e-6 | 2.83e-5   1.50e-5 | 6.97e-6 | 2.79e-5
+  phi0_s128_b7        1.98e-6 | 1.27e-6 | 5.07e-6   3.36e-6 | 2.60e-6 | 1.04e-5   5.65e-6 | 8.48e-6 | 3.39e-5   6.65e-6 | 8.09e-6 | 3.24e-5
+  phi0_s256_b9        2.45e-6 | 1.54e-6 | 6.15e-6   3.82e-6 | 3.27e-6 | 1.31e-5   7.69e-6 | 1.01e-5 | 4.05e-5   9.05e-6 | 9.56e-6 | 3.82e-5
+(the last seven: NOTEBOOK.md section 16; smallest max |g64| over the tensors of a case 0.61 .. 27, never zero; nearest to its bound:
+BatchNorm / SE biases at phi 4, 0.61 of it.)
+Forward against the session (worst stage): phi 0 @ 256 b2 2.2e-6, b16 2.6e-6, phi 0 @ 128 2.5e-6, phi 0 @ 384 2.7e-6, phi 3 @ 512 3.1e-6,
+phi 1 / 2 / 4 / 5 / 6 @ 128 3.0e-6 / 2.0e-6 / 2.5e-6 / 3.2e-6 / 2.4e-6 (bound 1e-3).
+test_workspace_and_gradient_writes_stay_inside_their_buffers runs every case once more through the ABI on an exact-size workspace
+between two guards: a write past either end of the workspace changes a guard word (a write past one scratch array INTO the next
+one does not - that shows only as a wrong gradient in the comparison above).
 """
 import functools
 import os
@@ -27,10 +39,10 @@ import numpy as np
 import pytest
 import torch
 
-from hmd_ego_pose_amd import seeded_state_dict
 from tests import _backbone_grad as G
 from tests._loss_grad import TRAIN_WEIGHTS
-from tests._util import CAMS, seeded_input
+from tests._util import CAMS, GuardedWorkspace, seeded_input
+from tests._util import seeded_state_dict_once as seeded_state_dict      # the same weights serve module, oracles and checks
 from tests.test_head_grads_cpu import check_against_golden
 
 pytestmark = pytest.mark.gpu
@@ -46,7 +58,17 @@ BACKWARD_CASES = {              # tag -> (phi, size, batch, weight seed)
     "phi0_s384_b1": (0, 384, 1, 0),
     "phi3_s128_b1": (3, 128, 1, 0),
     G.DROP_TAG: G.DROP_CASE,    # with the scale table stored in the golden archive
+    # EfficientNet-B1, B2, B4, B5, B6: their own channel, squeeze and tap widths; B6 sits on BG_MAX_CEXP = 3456 and BG_MAX_SE = 144,
+    # the sizes of the LDS arrays of the squeeze-excite kernels (phi 7 is B6 as well: tests/test_host_cpu.py)
+    "phi1_s128_b1": (1, 128, 1, 0),
+    "phi2_s128_b1": (2, 128, 1, 0),
+    "phi4_s128_b1": (4, 128, 1, 0),
+    "phi5_s128_b1": (5, 128, 1, 0),
+    "phi6_s128_b1": (6, 128, 1, 0),
+    "phi0_s128_b7": (0, 128, 7, 0),             # odd batch in the per-image SE sums; a 1792-row stage: 3 slabs of 608, the last 576
+    "phi0_s256_b9": (0, 256, 9, 0),             # R0 = 147456: capped at BG_MAX_SLABS = 256 slabs of 576; bg_tile_rows 64; 128 SE chunks
 }
+LARGEST_NEW = ("phi0_s256_b9",)                 # where the smallest gradient scale must be non-zero: no tensor passes by being all zero
 
 
 def _backbone(phi, seed):
@@ -95,7 +117,8 @@ def _bound(c, grp):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("phi,size,batch", [(0, 256, 2), (0, 256, 16), (0, 128, 2), (0, 384, 2), (3, 512, 1)])
+@pytest.mark.parametrize("phi,size,batch", [(0, 256, 2), (0, 256, 16), (0, 128, 2), (0, 384, 2), (3, 512, 1),
+                                            (1, 128, 1), (2, 128, 1), (4, 128, 1), (5, 128, 1), (6, 128, 1)])
 def test_forward_matches_the_inference_session_stage_by_stage(phi, size, batch):
     from hmd_ego_pose_amd import _capi
     from hmd_ego_pose_amd import backbone as BB
@@ -142,6 +165,11 @@ def test_forward_and_backward_match_float64_autograd(tag):
     phi = BACKWARD_CASES[tag][0]
     assert set(c["grads"]) == set(c["g64"]) == {k for k, _ in G.backbone_keys(phi) if G.trainable(k)}
     dev = G.group_errors(c["taps"], c["gimage"], c["grads"], c["t64"], c["i64"], c["g64"])
+    scales = {k: float(v.abs().max()) for k, v in c["g64"].items()}
+    smallest = min(scales, key=scales.get)
+    print(f"{tag}: smallest tensor scale {scales[smallest]:.3g} ({smallest})")
+    if tag in LARGEST_NEW:
+        assert scales[smallest] > 0.0, (tag, smallest)
     bad = {}
     for grp in G.GROUPS:
         e, bound = dev[grp], _bound(c, grp)
@@ -213,6 +241,48 @@ def test_structure_determinism_and_the_abi_equal_the_autograd_path():
     ones = torch.ones((len(bb.arch.blocks), batch), device="cuda")
     e, ie, te = _device(bb, image, cots, scales=ones)
     assert all(np.array_equal(a[k], e[k]) for k in a) and np.array_equal(c["gimage"], ie) and all(np.array_equal(x, y) for x, y in zip(c["taps"], te))
+
+
+@pytest.mark.parametrize("tag", list(BACKWARD_CASES))
+def test_workspace_and_gradient_writes_stay_inside_their_buffers(tag):
+    """The plan sizes its scratch by maxima over blocks (m_pw, m_col, m_pdw, m_pse, ...); which block sets a maximum changes with
+    phi, size and batch.  One forward and one backward through the ABI on a workspace window of exactly
+    hep_backbone_workspace_bytes between two guards (tests/_util.py::GuardedWorkspace), every output and gradient buffer NaN
+    first: the guards keep their pattern, every value is finite, running statistics get exactly zero, all of it equal to the
+    autograd path bit for bit."""
+    from hmd_ego_pose_amd import backbone as BB
+    phi, size, batch, seed = BACKWARD_CASES[tag]
+    c = _case(tag)
+    a = c["grads"]
+    flat = c["bb"].flat_parameters().detach()
+    x = torch.from_numpy(c["image"]).cuda()
+    g = [torch.from_numpy(t).cuda() for t in c["cots"]]
+    scales = None if c["scales"] is None else c["scales"].to(device="cuda", dtype=torch.float32).contiguous()
+    l = BB._capi.lib()
+    nbytes = BB._capi.check(l.hep_backbone_workspace_bytes(phi, size, batch))
+    gw = GuardedWorkspace(nbytes, flat.device)
+    taps = [torch.full(t.shape, float("nan"), device="cuda") for t in c["taps"]]
+    g_flat = torch.full_like(flat, float("nan"))
+    g_img = torch.full_like(x, float("nan"))
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = l.hep_backbone_forward_device(flat.data_ptr(), x.data_ptr(), BB._capi.ptr(scales), phi, size, batch, BB._capi.ptr_array(taps), gw.ptr, nbytes, stream)
+    assert rc == 0, l.hep_last_error()
+    rc = l.hep_backbone_backward_device(flat.data_ptr(), BB._capi.ptr_array(g), BB._capi.ptr(scales), phi, size, batch, g_flat.data_ptr(),
+                                        g_img.data_ptr(), gw.ptr, nbytes, stream)
+    assert rc == 0, l.hep_last_error()
+    torch.cuda.synchronize()
+    assert gw.changed() == [], (tag, nbytes, gw.changed())
+    host = g_flat.cpu().numpy()
+    assert np.isfinite(host).all() and bool(torch.isfinite(g_img).all()) and all(bool(torch.isfinite(t).all()) for t in taps)
+    total, offsets = BB.param_layout(phi)
+    assert total == flat.numel()
+    for (k, shape), off in zip(BB.flat_keys(phi), offsets):
+        v = host[off:off + int(np.prod(shape))].reshape(shape)
+        if G.trainable(k):
+            assert np.array_equal(v, a[k]), k
+        else:
+            assert not v.any(), k                                          # running statistics: exactly zero
+    assert np.array_equal(g_img.cpu().numpy(), c["gimage"]) and all(np.array_equal(t.cpu().numpy(), y) for t, y in zip(taps, c["taps"]))
 
 
 def test_parameter_gradients_are_linear_in_the_cotangents():

@@ -10,7 +10,16 @@ float32 on the CPU (torch, one thread), takes ITS worst e over the tensors of th
 Measured on MI355X (worst e over all 218 / 283 gradient tensors: device | float32 torch on the CPU | bound):
   phi0_s256_b2     1.3e-6 | 1.6e-6 | 6.5e-6        phi0_s384_b1   1.4e-6 | 1.7e-6 | 6.9e-6
   phi0_s128_b2_k3  1.6e-6 | 1.4e-6 | 5.7e-6        phi3_s128_b1   2.0e-6 | 2.1e-6 | 8.4e-6
-(NOTEBOOK.md section 12); the tests print the values they reach.
+(NOTEBOOK.md section 12); the tests print the values they reach.  The cases that reach every other width, the widest
+classifier, an odd batch and the slab cap (348 tensors at depth 5; NOTEBOOK.md section 16):
+  phi1_s128_b1     1.5e-6 | 1.1e-6 | 4.6e-6        phi2_s128_b1   1.6e-6 | 1.6e-6 | 6.4e-6
+  phi4_s128_b1     2.4e-6 | 2.2e-6 | 8.6e-6        phi5_s128_b1   2.9e-6 | 2.0e-6 | 7.9e-6
+  phi6_s128_b1     1.8e-6 | 1.8e-6 | 7.1e-6        phi0_s128_b1_k63  1.5e-6 | 1.2e-6 | 4.8e-6
+  phi0_s128_b7     1.4e-6 | 2.0e-6 | 7.8e-6        phi0_s256_b13  1.5e-6 | 4.2e-6 | 1.7e-5   (32 slabs of 560 rows, the last 372)
+Smallest max |g64| over the tensors of a case: 2.8e-5 (phi 6) .. 0.76 (phi0_s256_b13), never zero.
+test_workspace_and_gradient_writes_stay_inside_their_buffers runs every case once more through the ABI on an exact-size workspace
+between two guards: a write past either end of the workspace changes a guard word (a write past one scratch array INTO the next
+one does not - that shows only as a wrong gradient in the comparison above).
 """
 import functools
 import os
@@ -19,10 +28,10 @@ import numpy as np
 import pytest
 import torch
 
-from hmd_ego_pose_amd import seeded_state_dict
 from tests import _head_grad as H
 from tests._loss_grad import TRAIN_WEIGHTS
-from tests._util import CAMS, seeded_input
+from tests._util import CAMS, GuardedWorkspace, seeded_input
+from tests._util import seeded_state_dict_once as seeded_state_dict      # the same weights serve module, oracles and checks
 from tests.test_head_grads_cpu import check_against_golden
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +46,18 @@ BACKWARD_CASES = {
     "phi0_s128_b2_k3": (0, 3, 128, 2, 0),
     "phi0_s384_b1": (0, 1, 384, 1, 0),
     "phi3_s128_b1": (3, 1, 128, 1, 0),
+    # every remaining width: 88 (a k-tail of 8 in the 16-wide k-step, a last n-tile of 24), 112, 224 (3.5 tiles), 288 (4.5 tiles),
+    # 384 with depth 5; phi 7 has the shapes of phi 6 (tests/test_host_cpu.py)
+    "phi1_s128_b1": (1, 1, 128, 1, 0),
+    "phi2_s128_b1": (2, 1, 128, 1, 0),
+    "phi4_s128_b1": (4, 1, 128, 1, 0),
+    "phi5_s128_b1": (5, 1, 128, 1, 0),
+    "phi6_s128_b1": (6, 1, 128, 1, 0),
+    "phi0_s128_b1_k63": (0, 63, 128, 1, 0),     # classifier header 567 columns (ld 568): nine n-tiles, sigmoid backward across tiles
+    "phi0_s128_b7": (0, 1, 128, 7, 0),          # odd batch: 7 and 28 rows at the top levels; R = 2387: 4 slabs of 608, the last 563
+    "phi0_s256_b13": (0, 1, 256, 13, 0),        # R = 17732: capped at HG_MAX_SLABS = 32 slabs of 560, the last 372
 }
+LARGEST_NEW = ("phi0_s256_b13",)                # where the smallest gradient scale must be non-zero: no tensor passes by being all zero
 
 
 def _heads(phi, classes, seed):
@@ -86,7 +106,8 @@ def _worst(got, gfeats, g64, f64):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("phi,classes,size,batch", [(0, 1, 256, 2), (0, 1, 256, 16), (0, 1, 128, 2), (0, 1, 384, 2), (3, 1, 512, 1), (0, 3, 256, 2)])
+@pytest.mark.parametrize("phi,classes,size,batch", [(0, 1, 256, 2), (0, 1, 256, 16), (0, 1, 128, 2), (0, 1, 384, 2), (3, 1, 512, 1), (0, 3, 256, 2),
+                                                    (1, 1, 128, 1), (2, 1, 128, 1), (4, 1, 128, 1), (5, 1, 128, 1), (6, 1, 128, 1)])
 def test_forward_matches_the_inference_session_on_its_own_maps(phi, classes, size, batch):
     from hmd_ego_pose_amd import TrainableHeads
     from hmd_ego_pose_amd.model import HMDEgoPose
@@ -122,6 +143,8 @@ def test_backward_matches_float64_autograd_of_the_oracle(tag):
     scale = min(float(np.abs(v.numpy()).max()) for v in list(g64.values()) + list(f64))
     print(f"{tag}: {len(errs)} gradient tensors, device worst {errs[k]:.3e} ({k}); float32 torch on the CPU worst {e32:.3e}; bound {bound:.3e}; "
           f"smallest tensor scale {scale:.3g}")
+    if tag in LARGEST_NEW:
+        assert scale > 0.0, tag
     bad = {n: e for n, e in errs.items() if not e <= bound}
     assert not bad, (tag, bound, bad)
 
@@ -213,6 +236,48 @@ def test_backward_is_deterministic_and_the_abi_equals_the_autograd_path():
     # a workspace one float short is refused before anything is launched
     assert l.hep_heads_backward_device(flat.data_ptr(), HD._capi.ptr_array(g), phi, classes, size, batch, g_flat.data_ptr(), None,
                                        ws.data_ptr(), ws.numel() - 4, stream) == -1
+
+
+@pytest.mark.parametrize("tag", list(BACKWARD_CASES))
+def test_workspace_and_gradient_writes_stay_inside_their_buffers(tag):
+    """The plan sizes its scratch by maxima over levels and nets; which one sets a maximum changes with phi, size, batch and
+    class count.  One forward and one backward through the ABI on a workspace window of exactly hep_heads_workspace_bytes
+    between two guards (tests/_util.py::GuardedWorkspace), every output and gradient buffer NaN first: the guards keep their
+    pattern, every value is finite, running statistics get exactly zero, all of it equal to the autograd path bit for bit."""
+    from hmd_ego_pose_amd import heads as HD
+    phi, classes, size, batch, seed = BACKWARD_CASES[tag]
+    feats, cots = _inputs(phi, classes, size, batch, seed)
+    h = _heads(phi, classes, seed)
+    a, fa, outs_a = _device_grads(h, feats, cots)
+    flat = h.flat_parameters().detach()
+    f = [torch.from_numpy(x).cuda() for x in feats]
+    g = [torch.from_numpy(x).cuda() for x in cots]
+    l = HD._capi.lib()
+    nbytes = HD._capi.check(l.hep_heads_workspace_bytes(phi, classes, size, batch))
+    gw = GuardedWorkspace(nbytes, flat.device)
+    outs = [torch.full_like(o, float("nan")) for o in outs_a]
+    g_flat = torch.full_like(flat, float("nan"))
+    g_feats = [torch.full_like(x, float("nan")) for x in f]
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = l.hep_heads_forward_device(flat.data_ptr(), HD._capi.ptr_array(f), phi, classes, size, batch, HD._capi.ptr_array(outs), gw.ptr, nbytes, stream)
+    assert rc == 0, l.hep_last_error()
+    rc = l.hep_heads_backward_device(flat.data_ptr(), HD._capi.ptr_array(g), phi, classes, size, batch, g_flat.data_ptr(),
+                                     HD._capi.ptr_array(g_feats), gw.ptr, nbytes, stream)
+    assert rc == 0, l.hep_last_error()
+    torch.cuda.synchronize()
+    assert gw.changed() == [], (tag, nbytes, gw.changed())
+    host = g_flat.cpu().numpy()
+    assert np.isfinite(host).all() and all(bool(torch.isfinite(x).all()) for x in g_feats + outs)
+    total, offsets = HD.param_layout(phi, classes)
+    assert total == flat.numel()
+    for (k, shape), off in zip(HD.flat_keys(phi, classes), offsets):
+        v = host[off:off + int(np.prod(shape))].reshape(shape)
+        if H.trainable(k):
+            assert np.array_equal(v, a[k]), k
+        else:
+            assert not v.any(), k                                          # running statistics: exactly zero
+    assert all(np.array_equal(x.cpu().numpy(), y) for x, y in zip(g_feats, fa))
+    assert all(torch.equal(x, y) for x, y in zip(outs, outs_a))
 
 
 def test_ten_sgd_steps_on_the_device_lower_the_training_loss_and_export_serves_them():

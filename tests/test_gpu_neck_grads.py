@@ -16,8 +16,22 @@ Measured on MI355X (device | float32 torch on the CPU | bound; NOTEBOOK.md secti
   phi0_s128_b2   5.82e-7 | 5.52e-7 | 2.21e-6   6.92e-7 | 7.41e-7 | 2.96e-6   1.75e-6 | 1.72e-6 | 6.87e-6   1.43e-6 | 6.60e-7 | 2.64e-6
   phi0_s384_b1   1.27e-6 | 1.14e-6 | 4.56e-6   1.57e-6 | 1.50e-6 | 5.99e-6   2.54e-6 | 3.29e-6 | 1.32e-5   1.87e-6 | 1.76e-6 | 7.04e-6
   phi3_s128_b1   3.81e-7 | 4.36e-7 | 2.00e-6   1.24e-6 | 1.31e-6 | 5.25e-6   2.09e-6 | 2.79e-6 | 1.12e-5   4.81e-7 | 2.58e-7 | 2.00e-6
-Legitimacy slack 0 and no window routed unlike the float64 oracle's own in all four cases.  Forward against the session (worst map):
-phi 0 @ 256 b2 4.4e-6, b16 2.9e-6, phi 0 @ 128 1.0e-6, phi 0 @ 384 2.6e-6, phi 3 @ 512 7.8e-6 (bound 1e-3).
+  phi1_s128_b1   1.15e-6 | 1.19e-6 | 4.76e-6   9.41e-7 | 9.75e-7 | 3.90e-6   1.91e-6 | 1.94e-6 | 7.77e-6   7.38e-7 | 2.09e-6 | 8.37e-6
+  phi2_s128_b1   9.22e-7 | 9.87e-7 | 3.95e-6   1.21e-6 | 1.20e-6 | 4.81e-6   2.16e-6 | 2.14e-6 | 8.55e-6   3.93e-7 | 4.20e-7 | 2.00e-6
+  phi4_s128_b1   6.54e-7 | 6.04e-7 | 2.42e-6   1.44e-6 | 1.05e-6 | 4.19e-6   2.70e-6 | 2.67e-6 | 1.07e-5   1.05e-6 | 3.64e-7 | 2.00e-6
+  phi5_s128_b1   9.49e-7 | 6.58e-7 | 2.63e-6   1.32e-6 | 1.05e-6 | 4.20e-6   2.75e-6 | 2.05e-6 | 8.20e-6   1.98e-6 | 1.14e-6 | 4.54e-6
+  phi0_s128_b7   5.64e-7 | 5.67e-7 | 2.27e-6   6.55e-7 | 6.57e-7 | 2.63e-6   2.14e-6 | 3.29e-6 | 1.32e-5   1.65e-6 | 1.11e-6 | 4.43e-6
+  phi0_s256_b17  7.79e-7 | 7.51e-7 | 3.00e-6   8.75e-7 | 7.95e-7 | 3.18e-6   1.27e-6 | 6.53e-6 | 2.61e-5   5.18e-7 | 5.94e-7 | 2.38e-6
+The last six (NOTEBOOK.md section 16) use weight seed 4: with seed 0, at every phi, two relu-dead fusion entries leave the whole
+p5_down_channel lateral and conv6_up of cell 2 with a gradient that is identically zero, so those tensors pass by being zero;
+with seed 4 every convolution, lateral and BatchNorm tensor has a gradient (smallest max |g64| 0.03 .. 14) and the test asserts it.
+Legitimacy slack 0 and no window routed unlike the float64 oracle's own in the first four cases and in five of the new ones; one
+window each at phi5_s128_b1 (slack 4.3e-8) and phi0_s256_b17 (1.7e-8), no window excluded.  Forward against the session (worst map):
+phi 0 @ 256 b2 4.4e-6, b16 2.9e-6, phi 0 @ 128 1.0e-6, phi 0 @ 384 2.6e-6, phi 3 @ 512 7.8e-6, phi 1 / 2 / 4 / 5 @ 128 1.7e-6 / 8.9e-7 /
+6.1e-7 / 1.2e-6 (bound 1e-3).
+test_workspace_and_gradient_writes_stay_inside_their_buffers runs every case once more through the ABI on an exact-size workspace
+between two guards: a write past either end of the workspace changes a guard word (a write past one scratch array INTO the next
+one does not - that shows only as a wrong gradient in the comparison above).
 """
 import functools
 import os
@@ -26,10 +40,10 @@ import numpy as np
 import pytest
 import torch
 
-from hmd_ego_pose_amd import seeded_state_dict
 from tests import _neck_grad as N
 from tests._loss_grad import TRAIN_WEIGHTS
-from tests._util import CAMS, seeded_input
+from tests._util import CAMS, GuardedWorkspace, seeded_input
+from tests._util import seeded_state_dict_once as seeded_state_dict      # the same weights serve module, oracles and checks
 from tests.test_head_grads_cpu import check_against_golden
 
 pytestmark = pytest.mark.gpu
@@ -44,7 +58,18 @@ BACKWARD_CASES = {              # tag -> (phi, size, batch, weight seed)
     "phi0_s128_b2": (0, 128, 2, 0),
     "phi0_s384_b1": (0, 384, 1, 0),
     "phi3_s128_b1": (3, 128, 1, 0),
+    # every remaining width (88, 112, 224, 288) with 4 / 5 / 7 / 7 cells; the lateral products run over the tap channels of B1..B5.
+    # Weight seed LIVE_SEED: with seed 0 the fusion entries bifpn.0.p5_w1[0] and bifpn.2.p6_w1[0] are relu-dead at every phi (the
+    # seeded weights are keyed by tensor name), so the whole p5_down_channel lateral and conv6_up of cell 2 have a zero gradient
+    # and pass by being zero; seed 4 leaves no convolution, lateral or BatchNorm tensor without a gradient at phi 0..5.
+    "phi1_s128_b1": (1, 128, 1, 4),
+    "phi2_s128_b1": (2, 128, 1, 4),
+    "phi4_s128_b1": (4, 128, 1, 4),
+    "phi5_s128_b1": (5, 128, 1, 4),
+    "phi0_s128_b7": (0, 128, 7, 4),             # odd batch: R[0] = 1792, 3 slabs of 608, the last 576; 7 rows at P7
+    "phi0_s256_b17": (0, 256, 17, 4),           # R[0] = 17408: capped at NG_MAX_SLABS = 32 slabs of 544
 }
+LIVE_SEED = 4                                   # the cases where the smallest gradient scale is asserted non-zero
 
 
 def _neck(phi, seed):
@@ -100,7 +125,8 @@ def _case(tag):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("phi,size,batch", [(0, 256, 2), (0, 256, 16), (0, 128, 2), (0, 384, 2), (3, 512, 1)])
+@pytest.mark.parametrize("phi,size,batch", [(0, 256, 2), (0, 256, 16), (0, 128, 2), (0, 384, 2), (3, 512, 1),
+                                            (1, 128, 1), (2, 128, 1), (4, 128, 1), (5, 128, 1)])
 def test_forward_matches_the_inference_session_on_its_own_taps(phi, size, batch):
     from hmd_ego_pose_amd.model import HMDEgoPose
     from hmd_ego_pose_amd.neck import TrainableNeck, backbone_taps
@@ -132,7 +158,14 @@ def test_forward_and_backward_match_float64_autograd_with_the_devices_routing(ta
         assert slack <= LEGIT * max(1.0, scale), (name, slack, scale)
     flips = sum(int((a != b).sum()) for a, b in zip(c["argmax"], c["pool"].own))
     dev = N.group_errors(c["maps"], c["gtaps"], c["grads"], c["m64"], c["t64"], c["g64"])
-    print(f"{tag}: worst legitimacy slack {max(c['pool'].slack):.3e}; windows routed unlike the float64 oracle's own {flips}")
+    # no tensor passes by being all zero: every trainable tensor that is not a fusion weight has a non-zero float64 gradient
+    # (a fusion weight the seed left at or below zero is relu-dead: its gradient IS zero, asserted exactly below)
+    scales = {k: float(v.abs().max()) for k, v in c["g64"].items() if not N.is_fusion(k)}
+    smallest = min(scales, key=scales.get)
+    print(f"{tag}: worst legitimacy slack {max(c['pool'].slack):.3e}; windows routed unlike the float64 oracle's own {flips}; "
+          f"smallest tensor scale {scales[smallest]:.3g} ({smallest})")
+    if BACKWARD_CASES[tag][3] == LIVE_SEED:
+        assert scales[smallest] > 0.0, (tag, smallest)
     bad = {}
     for grp, e in dev.items():
         bound = max(BOUND_FACTOR * c["e32"][grp], BOUND_FLOOR)
@@ -140,9 +173,10 @@ def test_forward_and_backward_match_float64_autograd_with_the_devices_routing(ta
         if not e <= bound:
             bad[grp] = (e, bound)
     assert not bad, (tag, bad)
+    sd = seeded_state_dict(phi, BACKWARD_CASES[tag][3])
     for k, v in c["g64"].items():                            # dead fusion entries: exactly zero
         if N.is_fusion(k):
-            p = seeded_state_dict(phi, 0)[k].numpy()
+            p = sd[k].numpy()
             assert not c["grads"][k][p <= 0].any(), k
 
 
@@ -215,6 +249,48 @@ def test_structure_determinism_and_the_abi_equal_the_autograd_path():
     assert all(np.array_equal(t.cpu().numpy(), y) for t, y in zip(g_taps, c["gtaps"]))
     assert l.hep_neck_backward_device(flat.data_ptr(), NK._capi.ptr_array(g), phi, size, batch, g_flat.data_ptr(), None,
                                       ws.data_ptr(), ws.numel() - 4, stream) == -1
+
+
+@pytest.mark.parametrize("tag", list(BACKWARD_CASES))
+def test_workspace_and_gradient_writes_stay_inside_their_buffers(tag):
+    """The plan sizes its scratch by maxima over levels and laterals (o_pw = NG_MAX_SLABS * W * kmax, ...); which one sets a
+    maximum changes with phi, size and batch.  One forward and one backward through the ABI on a workspace window of exactly
+    hep_neck_workspace_bytes between two guards (tests/_util.py::GuardedWorkspace), every output and gradient buffer NaN first:
+    the guards keep their pattern, every value is finite, running statistics get exactly zero, all of it equal to the autograd
+    path bit for bit."""
+    from hmd_ego_pose_amd import neck as NK
+    phi, size, batch, seed = BACKWARD_CASES[tag]
+    c = _case(tag)
+    a = c["grads"]
+    flat = c["neck"].flat_parameters().detach()
+    x = [torch.from_numpy(t).cuda() for t in c["taps"]]
+    g = [torch.from_numpy(t).cuda() for t in c["cots"]]
+    l = NK._capi.lib()
+    nbytes = NK._capi.check(l.hep_neck_workspace_bytes(phi, size, batch))
+    gw = GuardedWorkspace(nbytes, flat.device)
+    maps = [torch.full(m.shape, float("nan"), device="cuda") for m in c["maps"]]
+    g_flat = torch.full_like(flat, float("nan"))
+    g_taps = [torch.full_like(t, float("nan")) for t in x]
+    stream = torch.cuda.current_stream().cuda_stream
+    rc = l.hep_neck_forward_device(flat.data_ptr(), NK._capi.ptr_array(x), phi, size, batch, NK._capi.ptr_array(maps), gw.ptr, nbytes, stream)
+    assert rc == 0, l.hep_last_error()
+    rc = l.hep_neck_backward_device(flat.data_ptr(), NK._capi.ptr_array(g), phi, size, batch, g_flat.data_ptr(), NK._capi.ptr_array(g_taps),
+                                    gw.ptr, nbytes, stream)
+    assert rc == 0, l.hep_last_error()
+    torch.cuda.synchronize()
+    assert gw.changed() == [], (tag, nbytes, gw.changed())
+    host = g_flat.cpu().numpy()
+    assert np.isfinite(host).all() and all(bool(torch.isfinite(t).all()) for t in g_taps + maps)
+    total, offsets = NK.param_layout(phi)
+    assert total == flat.numel()
+    for (k, shape), off in zip(NK.flat_keys(phi), offsets):
+        v = host[off:off + int(np.prod(shape))].reshape(shape)
+        if N.trainable(k):
+            assert np.array_equal(v, a[k]), k
+        else:
+            assert not v.any(), k                                          # running statistics: exactly zero
+    assert all(np.array_equal(t.cpu().numpy(), y) for t, y in zip(g_taps, c["gtaps"]))
+    assert all(np.array_equal(m.cpu().numpy(), y) for m, y in zip(maps, c["maps"]))
 
 
 def test_parameter_gradients_are_linear_in_the_cotangents():

@@ -101,7 +101,9 @@ def test_from_model_and_export_round_trip_bit_exactly():
 
 def test_param_count_and_layout_follow_param_spec():
     from hmd_ego_pose_amd.heads import flat_keys, param_layout
-    for phi, classes, trainable in ((0, 1, 127386), (3, 1, 691866), (6, 3, None)):
+    known = {(0, 1): 127386, (3, 1): 691866}
+    for phi, classes in [(phi, 1) for phi in range(8)] + [(6, 3), (0, 63)]:      # every phi the ABI accepts; class counts
+        trainable = known.get((phi, classes))
         keys = flat_keys(phi, classes)
         n_train = sum(int(np.prod(s)) for k, s in keys if H.trainable(k))
         n_stats = sum(int(np.prod(s)) for k, s in keys if not H.trainable(k))

@@ -14,7 +14,7 @@ import torch
 from hmd_ego_pose_amd import _capi
 from hmd_ego_pose_amd.arch import get_arch, level_sizes, num_anchors_total, param_spec, same_pad
 from hmd_ego_pose_amd.weights import load_pack, pack_bytes, seeded_state_dict, strip_checkpoint_prefix
-from tests._util import golden_meta
+from tests._util import golden_arch, golden_meta
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -24,6 +24,94 @@ def test_param_spec_matches_reference_state_dict(phi):
     spec = param_spec(phi)
     assert hashlib.sha256(repr(spec).encode()).hexdigest() == golden_meta()[f"keys_phi{phi}_sha256"]
     assert len(spec) == {0: 1048, 3: 1618}[phi]
+
+
+@pytest.mark.parametrize("phi", range(8))
+def test_param_spec_hashes_to_the_reference_at_every_phi(phi):
+    """tests/golden/arch_all_phi.json (make_golden_arch.py): the sha256 of the real reference's [(key, shape)] state_dict list,
+    one class, at every supported phi; no phi had to be left out (the reference constructs all eight without fetching)."""
+    meta, _ = golden_arch()
+    assert meta["left_out"] == [] and len(meta["phi"]) == 8
+    spec = param_spec(phi)
+    assert len(spec) == meta["phi"][phi]["key_count"]
+    assert hashlib.sha256(repr(spec).encode()).hexdigest() == meta["phi"][phi]["keys_sha256"]
+    if phi in (0, 3):                                             # the two pins agree where both exist
+        assert meta["phi"][phi]["keys_sha256"] == golden_meta()[f"keys_phi{phi}_sha256"]
+
+
+@pytest.mark.parametrize("phi", range(8))
+def test_block_table_taps_and_widths_equal_the_reference_modules_at_every_phi(phi):
+    """get_arch(phi) and the oracle's block_table(phi) against the settings read from the constructed reference module, field
+    by field: kernel size, stride, expand ratio, input / output filters, squeeze width, whether the block adds its input; stem
+    width, tapped blocks, tap channels; BiFPN width, cell count, head depth, attention."""
+    from oracle import efficientpose_ref as R
+    ref = golden_arch()[0]["phi"][phi]
+    a, table = get_arch(phi), R.block_table(phi)
+    assert len(a.blocks) == len(table) == len(ref["blocks"])
+    for i, (b, t, (k, stride, e, cin, cout, se, adds)) in enumerate(zip(a.blocks, table, ref["blocks"])):
+        assert (b.k, b.stride, b.cin, b.cout, b.se, b.skip, b.expand, b.cexp) == (k, stride, cin, cout, se, bool(adds), e != 1, cin * e), (phi, i)
+        assert (t["k"], t["s"], t["e"], t["cin"], t["cout"], t["skip"]) == (k, stride, e, cin, cout, bool(adds)), (phi, i)
+    assert (a.stem, list(a.taps), list(a.tap_channels)) == (ref["stem"], ref["taps"], ref["tap_channels"])
+    assert (a.fpn_w, a.fpn_cells, a.head_depth, a.attention) == (ref["fpn_w"], ref["fpn_cells"], ref["head_depth"], ref["attention"])
+    assert (R._FPN_REPEATS[phi], R._HEAD_DEPTH[phi]) == (ref["fpn_cells"], ref["head_depth"])
+    # the oracle's loop taps what enters a stride-2 block and the last output: the same blocks
+    tapped = [i - 1 for i, t in enumerate(table) if t["s"] == 2] + [len(table) - 1]
+    assert tapped[-3:] == ref["taps"]
+    # the sizes of the LDS arrays of the squeeze-excite kernels hold the widest block of every supported backbone; B6 fills them
+    assert max(b.cexp for b in a.blocks) <= 3456 and max(b.se for b in a.blocks) <= 144
+    if phi >= 6:
+        assert max(b.cexp for b in a.blocks) == 3456 and max(b.se for b in a.blocks) == 144
+
+
+def _stages(part, phi, size, batch):
+    l = _capi.lib()
+    out = []
+    for i in range(getattr(l, f"hep_{part}_stage_count")(phi)):
+        nm = ctypes.c_char_p(); dims = (ctypes.c_int64 * 4)(); off = ctypes.c_int64()
+        assert getattr(l, f"hep_{part}_stage_info")(phi, size, batch, i, ctypes.byref(nm), dims, ctypes.byref(off)) == 0
+        out.append((nm.value.decode(), tuple(int(d) for d in dims), int(off.value)))
+    return out
+
+
+def test_phi7_is_phi6_for_the_backbone_and_the_heads():
+    """_BACKBONE_OF_PHI maps phi 6 and 7 both to EfficientNet-B6 and both have heads of width 384, depth 5: layout, workspace
+    bytes and the stage list are equal, so phi 7 adds no kernel shape beyond phi 6 (which the GPU gradient tests run)."""
+    from hmd_ego_pose_amd import backbone as BB, heads as HD
+    l = _capi.lib()
+    assert get_arch(7).blocks == get_arch(6).blocks and BB.flat_keys(7) == BB.flat_keys(6)
+    assert BB.param_layout(7) == BB.param_layout(6)
+    assert _stages("backbone", 7, 128, 1) == _stages("backbone", 6, 128, 1) and len(_stages("backbone", 6, 128, 1)) == 46
+    for classes in (1, 3):
+        assert HD.flat_keys(7, classes) == HD.flat_keys(6, classes) and HD.param_layout(7, classes) == HD.param_layout(6, classes)
+    for size, batch in ((128, 1), (256, 3), (384, 2)):
+        assert l.hep_backbone_workspace_bytes(7, size, batch) == l.hep_backbone_workspace_bytes(6, size, batch) > 0
+        assert l.hep_heads_workspace_bytes(7, 1, size, batch) == l.hep_heads_workspace_bytes(6, 1, size, batch) > 0
+
+
+def test_module_constructs_with_the_seeded_weights_at_the_deepest_phi():
+    """HMDEgoPose.__init__ fills its 2314 tensors at phi 7 from seeded_state_dict(phi, 0) through reset_parameters, each
+    key copied once (the constructor used to rebuild its state_dict per key: 20 s at phi 4, which is what the
+    per-phi forward tests on the GPU spent their time on)."""
+    from hmd_ego_pose_amd import HMDEgoPose
+    m = HMDEgoPose({"iter": 0}, num_classes=1, compound_coef=7, onnx_export=True, input_sizes=[128] * 9)
+    own = m.state_dict()
+    assert [(k, tuple(v.shape)) for k, v in own.items()] == param_spec(7)
+    assert all(torch.equal(v, own[k]) for k, v in seeded_state_dict(7, 0).items())
+
+
+def test_guarded_workspace_reports_a_write_one_word_outside_the_window():
+    """The helper of the GPU tests' workspace checks (tests/_util.py), on host memory: intact guards read as no change; one
+    word written right below or right above the exact-size window is reported with its position."""
+    from tests._util import GUARD_BYTES, GuardedWorkspace
+    gw = GuardedWorkspace(4096, "cpu")
+    assert gw.changed() == [] and gw.window.numel() == 4096 and bool(torch.isnan(gw.window.view(torch.float32)).all())
+    gw.window.view(torch.float32).zero_()                         # writes inside the window are not the guards' business
+    assert gw.changed() == []
+    edge = gw.buf[gw.window.storage_offset() + 4096:gw.window.storage_offset() + 4100].view(torch.float32)
+    edge.fill_(1.0)                                               # the first float past the end
+    assert gw.changed() == [("above", 1, 0)]
+    gw.buf[gw.window.storage_offset() - 4:gw.window.storage_offset()].view(torch.float32).fill_(0.0)
+    assert gw.changed() == [("below", 1, GUARD_BYTES - 4), ("above", 1, 0)]
 
 
 def test_arch_tables_phi0_phi3():
