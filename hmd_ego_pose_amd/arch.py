@@ -3,7 +3,7 @@
 Host-side description of *what* the network is for a compound coefficient
 ``phi``: the MBConv block list, BiFPN width/repeats, head depth, pyramid
 geometry and the ordered parameter inventory (names + shapes) that the
-reference's ``state_dict`` uses.  ``csrc/hep_model.cpp`` holds the same tables
+reference's ``state_dict`` uses.  ``csrc/hep_arch.cpp`` holds the same tables
 in C++ (the C-ABI library is self-contained); ``tests/test_host_cpu.py`` checks
 this table against the golden key list captured from the reference, and the GPU
 parity tests exercise the C++ copy.

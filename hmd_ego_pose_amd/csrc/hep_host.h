@@ -1,4 +1,5 @@
-// hep_host.h - host-side model description, weight pack and execution plan of libhep.so.
+// hep_host.h - host-side model description (hep_arch.cpp), weight pack (hep_pack.cpp) and execution plan (hep_plan.cpp,
+// realised by hep_session.cpp) of libhep.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,7 +41,7 @@ struct Pack {
 struct TensorDesc {
   std::string name;
   int H, W, C; bool f32;            // NHWC; f32 forces fp32 storage (head outputs, SE buffers)
-  size_t bytes_per_image; size_t offset;
+  size_t bytes_per_image; size_t offset = 0;
   int first_op = -1, last_op = -1;
   int C_logical = 0;                // channels the layer has when the allocation is padded (0: C); frag: stored in the project GEMM's fragment
   bool frag = false;                // order (k_pw_impl.h FRAG: 16-byte units [m / 16][k-step][lane]) instead of NHWC - hep_debug_tensor undoes both
@@ -63,6 +64,7 @@ struct Op {
 
 struct Session {
   Arch arch; int size, max_batch, dtype, device; unsigned flags;
+  int cu_count = 256;               // compute units of `device` (build_session asks; the alt build's planner sizes a grouped launch by it)
   Knobs knobs;                      // the plan knobs of the environment this session was created in (hep_knobs.h)
   // The batch is cut into `lanes` contiguous slices of lane_batch frames; every lane owns an arena and a
   // patched copy of the plan, and the captured hipGraph runs the lanes as parallel branches: the

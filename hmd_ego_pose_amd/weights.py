@@ -4,7 +4,7 @@ version-stable seeded initialiser, and the ``HEPW`` container the C-ABI reads.
 The container is deliberately dumb: the reference's own ``state_dict`` tensors
 by their own names, fp32, nothing folded.  BatchNorm folding, fusion-weight
 normalisation, NHWC/GEMM layouts and bf16 conversion happen inside
-``libhep.so`` at ``hep_create`` time (csrc/hep_model.cpp), so a checkpoint
+``libhep.so`` at ``hep_create`` time (csrc/hep_pack.cpp, csrc/hep_plan.cpp), so a checkpoint
 converted once serves every dtype and the C# host never needs Python.
 
 Reference behaviour restated:
