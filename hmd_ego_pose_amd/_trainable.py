@@ -53,11 +53,42 @@ def stage_views(part: str, ws: torch.Tensor, compound_coef: int, size: int, batc
     return out
 
 
+BN_RUNNING, BN_BATCH = 0, 1        # HEP_BN_RUNNING, HEP_BN_BATCH of include/hep.h
+BN_MODES = {"running": BN_RUNNING, "batch": BN_BATCH}
+BN_MOMENTUM = 0.01                 # every nn.BatchNorm2d of the reference (efficientnet/model.py, efficientdet/model.py, hmdegopose/model.py)
+
+
 class TrainablePart(nn.Module):
     """Base of the three trainable parts.  A subclass sets ``spec`` and ``NOUN``, calls ``_attach_spec`` in its ``__init__``
-    and adds its own ``forward``."""
+    and adds its own ``forward``.  ``batch_norm``: "running" (every mode evaluates BatchNorm with the running statistics) or
+    "batch" (``train()`` mode normalises with the statistics of the batch and moves the running statistics, as
+    ``nn.BatchNorm2d`` does; ``eval()`` is the running-statistics function)."""
     NOUN = ""     # "head" | "BiFPN" | "backbone": what from_model's error calls the part's tensors
     spec = None   # staticmethod(*cfg) -> [(key, shape)]: the part's subset of ``param_spec``, in state_dict order
+
+    def _set_batch_norm(self, batch_norm):
+        if batch_norm not in BN_MODES:
+            raise ValueError(f"batch_norm must be 'running' or 'batch', not {batch_norm!r}")
+        self.batch_norm = batch_norm
+
+    def _bn_mode(self) -> int:
+        """The BatchNorm mode of this call: batch statistics only in ``train()`` mode of a ``batch_norm="batch"`` part."""
+        return BN_BATCH if self.batch_norm == "batch" and self.training else BN_RUNNING
+
+    def _store_statistics(self, stats: torch.Tensor):
+        """After a batch-statistics forward: ``stats`` (layout of ``flat_parameters``, its running_mean / running_var elements
+        new) into the buffers in place, and every ``num_batches_tracked`` up by one."""
+        buffers = dict(self.named_buffers())
+        tensors = dict(self.named_parameters())
+        tensors.update(buffers)
+        dst, src = [], []
+        for k, v in zip(self._flat_keys, stats.split([tensors[k].numel() for k in self._flat_keys])):
+            if k.endswith(("running_mean", "running_var")):
+                dst.append(buffers[k]); src.append(v.view_as(buffers[k]))
+        counters = [b for k, b in buffers.items() if k.endswith("num_batches_tracked")]
+        with torch.no_grad():
+            torch._foreach_copy_(dst, src)
+            torch._foreach_add_(counters, 1)
 
     def _attach_spec(self, *cfg):
         """Register the part's parameters and buffers under the reference's keys; ``cfg``: the arguments of ``spec``."""
@@ -74,9 +105,10 @@ class TrainablePart(nn.Module):
         return (model.compound_coef,)
 
     @classmethod
-    def from_model(cls, model):
-        """This part with the tensors of an ``HMDEgoPose`` (or any module with the reference's keys), on the model's device."""
-        m = cls(*cls._model_cfg(model))
+    def from_model(cls, model, **kwargs):
+        """This part with the tensors of an ``HMDEgoPose`` (or any module with the reference's keys), on the model's device.
+        ``kwargs``: further constructor arguments (``batch_norm=...``)."""
+        m = cls(*cls._model_cfg(model), **kwargs)
         sd = model.state_dict()
         missing = [k for k in m._spec_keys if k not in sd]
         if missing:

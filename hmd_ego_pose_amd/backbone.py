@@ -10,13 +10,15 @@ With the trunk trainable the reference's whole ``train.py`` step stays on the GP
 
 and ``export_to(model)`` copies the fitted tensors back into the ``HMDEgoPose`` drop-in.
 
-The rules are those of ``hmd_ego_pose_amd.heads`` and ``hmd_ego_pose_amd.neck``: fp32 only; BatchNorm uses its RUNNING
+The rules are those of ``hmd_ego_pose_amd.heads`` and ``hmd_ego_pose_amd.neck``: fp32 only; by default BatchNorm uses its RUNNING
 statistics in every mode, forward and backward (``weight`` / ``bias`` get gradients, ``running_mean`` / ``running_var`` get
-exactly zero and never change).  Drop-connect (efficientnet/utils.py:85-94 with the rate of efficientdet/model.py:447-449), the
+exactly zero and never change); ``batch_norm="batch"`` makes ``train()`` mode the reference's ``model.train()``: the stem's
+BatchNorm and every block's ``_bn0`` / ``_bn1`` / ``_bn2`` normalise with the statistics of their map's ``B * s * s`` pixels and
+move their running statistics (momentum 0.01), ``eval()`` stays the running-statistics function bit for bit.  Drop-connect (efficientnet/utils.py:85-94 with the rate of efficientdet/model.py:447-449), the
 only stochastic op on the path, enters the kernels as DATA: a per-block, per-image scale of the residual branch,
 ``y = bn2(project) * scale[i][b] + input``, used only where the block adds its input.  The module draws the scales itself only
 when ``drop_connect_rate`` is non-zero AND it is in ``train()``; the default rate 0.0 makes it deterministic.  Out of scope:
-batch-statistics BatchNorm and bf16 training.
+sync-BN across GPUs and bf16 training.
 """
 from __future__ import annotations
 
@@ -48,35 +50,37 @@ def _check_size(size: int):
         raise ValueError(f"input size {size}: the trainable backbone takes a multiple of 128 in [128, 2048]")
 
 
-def backbone_forward(flat: torch.Tensor, image: torch.Tensor, compound_coef: int, branch_scale: Optional[torch.Tensor] = None):
-    """hep_backbone_forward_device on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order), ``image``:
+def backbone_forward(flat: torch.Tensor, image: torch.Tensor, compound_coef: int, branch_scale: Optional[torch.Tensor] = None,
+                     bn_mode: int = _trainable.BN_RUNNING, momentum: float = _trainable.BN_MOMENTUM, stats: Optional[torch.Tensor] = None):
+    """hep_backbone_forward_device_bn on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order), ``image``:
     contiguous float32 NCHW [B, 3, S, S], ``branch_scale``: float32 [blocks, B] on the same device or None (all ones).
-    Returns (taps, workspace): P3, P4, P5 as float32 NCHW and the workspace hep_backbone_backward_device needs.  No host
-    synchronisation."""
+    Returns (taps, workspace): P3, P4, P5 as float32 NCHW and the workspace hep_backbone_backward_device_bn needs (same
+    ``bn_mode``).  ``stats`` (batch statistics): a buffer like ``flat`` whose running_mean / running_var elements receive the
+    updated statistics.  No host synchronisation."""
     a = get_arch(compound_coef)
     dev, B, size = flat.device, int(image.shape[0]), int(image.shape[-1])
     _check_size(size)
     l = _capi.lib()
-    nbytes = _capi.check(l.hep_backbone_workspace_bytes(compound_coef, size, B))
+    nbytes = _capi.check(l.hep_backbone_workspace_bytes_bn(compound_coef, size, B, bn_mode))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     taps = tuple(torch.empty((B, c, size // (8 << t), size // (8 << t)), dtype=torch.float32, device=dev) for t, c in enumerate(a.tap_channels))
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(l.hep_backbone_forward_device(flat.data_ptr(), image.data_ptr(), _capi.ptr(branch_scale), compound_coef, size, B,
-                                              _capi.ptr_array(list(taps)), ws.data_ptr(), nbytes, stream))
+    _capi.check(l.hep_backbone_forward_device_bn(flat.data_ptr(), image.data_ptr(), _capi.ptr(branch_scale), compound_coef, size, B,
+                                                 _capi.ptr_array(list(taps)), ws.data_ptr(), nbytes, bn_mode, momentum, _capi.ptr(stats), stream))
     return taps, ws
 
 
 def backbone_backward(flat: torch.Tensor, grad_taps, ws: torch.Tensor, compound_coef: int, size: int,
-                      branch_scale: Optional[torch.Tensor] = None, want_image: bool = False):
-    """hep_backbone_backward_device on the current stream, after ``backbone_forward`` with the same ``flat``, ``branch_scale``
-    and ``ws``.  Returns (grad_flat, grad_image): the parameter gradients in the layout of ``flat`` (running statistics zero)
+                      branch_scale: Optional[torch.Tensor] = None, want_image: bool = False, bn_mode: int = _trainable.BN_RUNNING):
+    """hep_backbone_backward_device_bn on the current stream, after ``backbone_forward`` with the same ``flat``, ``branch_scale``,
+    ``ws`` and ``bn_mode``.  Returns (grad_flat, grad_image): the parameter gradients in the layout of ``flat`` (running statistics zero)
     and the image gradient (None unless ``want_image``: the ABI then gets NULL and skips it)."""
     dev, B = flat.device, int(grad_taps[0].shape[0])
     g_flat = torch.empty_like(flat)
     g_img = torch.empty((B, 3, size, size), dtype=torch.float32, device=dev) if want_image else None
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(_capi.lib().hep_backbone_backward_device(flat.data_ptr(), _capi.ptr_array(list(grad_taps)), _capi.ptr(branch_scale), compound_coef,
-                                                         size, B, g_flat.data_ptr(), _capi.ptr(g_img), ws.data_ptr(), ws.numel(), stream))
+    _capi.check(_capi.lib().hep_backbone_backward_device_bn(flat.data_ptr(), _capi.ptr_array(list(grad_taps)), _capi.ptr(branch_scale), compound_coef,
+                                                            size, B, g_flat.data_ptr(), _capi.ptr(g_img), ws.data_ptr(), ws.numel(), bn_mode, stream))
     return g_flat, g_img
 
 
@@ -115,20 +119,20 @@ class _Backbone(torch.autograd.Function):
     """The two ABI calls as one differentiable function of (flat parameters, image); the branch scales are data."""
 
     @staticmethod
-    def forward(ctx, flat, image, phi, scale):
-        taps, ws = backbone_forward(flat, image, phi, scale)
+    def forward(ctx, flat, image, phi, scale, bn_mode, stats):
+        taps, ws = backbone_forward(flat, image, phi, scale, bn_mode, stats=stats)
         ctx.save_for_backward(flat, ws, *(() if scale is None else (scale,)))
-        ctx.cfg = (phi, int(image.shape[-1]), [tuple(t.shape) for t in taps])
+        ctx.cfg = (phi, int(image.shape[-1]), [tuple(t.shape) for t in taps], bn_mode)
         return taps
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grad_taps):
         flat, ws, *rest = ctx.saved_tensors
-        phi, size, shapes = ctx.cfg
+        phi, size, shapes, bn_mode = ctx.cfg
         gs = _trainable.cotangents(grad_taps, shapes, flat.device)
-        g_flat, g_img = backbone_backward(flat, gs, ws, phi, size, rest[0] if rest else None, want_image=ctx.needs_input_grad[1])
-        return (g_flat if ctx.needs_input_grad[0] else None, g_img, None, None)
+        g_flat, g_img = backbone_backward(flat, gs, ws, phi, size, rest[0] if rest else None, want_image=ctx.needs_input_grad[1], bn_mode=bn_mode)
+        return (g_flat if ctx.needs_input_grad[0] else None, g_img, None, None, None, None)
 
 
 class TrainableBackbone(_trainable.TrainablePart):
@@ -136,15 +140,17 @@ class TrainableBackbone(_trainable.TrainablePart):
     keys, so that ``load_state_dict(model.state_dict(), strict=False)`` fills it.  ``forward(x)`` takes a float32 ROCm image
     batch [B, 3, S, S] (S a multiple of 128 in [128, 2048]) and gives the taps (P3, P4, P5) as float32 NCHW with a ``grad_fn``:
     HIP forward and HIP backward, gradients to every parameter and, where it requires grad, to the image.  ``TrainableNeck``
-    and ``TrainableHeads`` chain behind it.  Runs on a ROCm device only (no CPU fallback).  BatchNorm uses the running
-    statistics in EVERY mode, ``train()`` included; they receive no gradient and never change.  ``drop_connect_rate`` (default
+    and ``TrainableHeads`` chain behind it.  Runs on a ROCm device only (no CPU fallback).  ``batch_norm="running"`` (the default):
+    BatchNorm uses the running statistics in EVERY mode, ``train()`` included; they receive no gradient and never change.
+    ``batch_norm="batch"``: batch statistics in ``train()`` mode, the running statistics move.  ``drop_connect_rate`` (default
     0.0) is the reference's global rate: non-zero and in ``train()``, every forward draws fresh branch scales
     (``draw_branch_scale``); otherwise the module is deterministic."""
 
     NOUN, spec = "backbone", staticmethod(backbone_spec)
 
-    def __init__(self, compound_coef: int = 0, drop_connect_rate: float = 0.0):
+    def __init__(self, compound_coef: int = 0, drop_connect_rate: float = 0.0, batch_norm: str = "running"):
         super().__init__()
+        self._set_batch_norm(batch_norm)
         self.compound_coef = int(compound_coef)
         self.arch = get_arch(self.compound_coef)
         self.drop_connect_rate = float(drop_connect_rate)
@@ -179,4 +185,9 @@ class TrainableBackbone(_trainable.TrainablePart):
             if tuple(branch_scale.shape) != (len(self.arch.blocks), B):
                 raise ValueError(f"branch_scale has shape {tuple(branch_scale.shape)}, expected {(len(self.arch.blocks), B)}")
             branch_scale = branch_scale.detach().to(device=x.device, dtype=torch.float32).contiguous()
-        return _Backbone.apply(flat, x.contiguous(), self.compound_coef, branch_scale)
+        bn_mode = self._bn_mode()
+        stats = torch.empty_like(flat) if bn_mode == _trainable.BN_BATCH else None
+        taps = _Backbone.apply(flat, x.contiguous(), self.compound_coef, branch_scale, bn_mode, stats)
+        if stats is not None:
+            self._store_statistics(stats)
+        return taps

@@ -1,7 +1,7 @@
 // grad_dev.h - the building blocks shared by the training kernels (k_head_grad.hip, k_neck_grad.hip, k_backbone_grad.hip):
 // the fp32 MFMA GEMM tile and its accumulator walk, the rolling 3 x 3 window of the depthwise convs, the fixed-order
-// second-pass reduce, and the small pieces around them (sigmoid, swish', the running-statistics BatchNorm load, block and
-// split-K slab counts).  Each kernel keeps its own argument struct and epilogue in its own file.  The f32x4 accumulator
+// second-pass reduce, the batch-statistics BatchNorm passes, and the small pieces around them (sigmoid, swish', the BatchNorm
+// table load, block and split-K slab counts).  Each kernel keeps its own argument struct and epilogue in its own file.  The f32x4 accumulator
 // type is hep_dev.h's.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -148,7 +148,8 @@ __device__ __forceinline__ float gd_dw_dot(const float (&w)[9], const float (&v)
 #define GD_RED_E 16
 #define GD_RED_K 16
 static_assert(GD_RED_E * GD_RED_K == GD_THREADS, "one reduce workgroup = 16 elements x 16 partial lanes");
-__device__ __forceinline__ float gd_reduce_core(const float* __restrict__ src, int64_t stride, int k0, int k1, int el, int kl) {
+// gd_reduce_core_d: the same walk over partials of type T (float or double), the sum before its rounding.
+template <class T> __device__ __forceinline__ double gd_reduce_core_d(const T* __restrict__ src, int64_t stride, int k0, int k1, int el, int kl) {
   __shared__ double part[GD_RED_K][GD_RED_E + 1];
   double s = 0.0;
   if (src)
@@ -160,7 +161,10 @@ __device__ __forceinline__ float gd_reduce_core(const float* __restrict__ src, i
 #pragma unroll
     for (int j = 0; j < GD_RED_K; j++) t += part[j][el];
   }
-  return (float)t;
+  return t;
+}
+__device__ __forceinline__ float gd_reduce_core(const float* __restrict__ src, int64_t stride, int k0, int k1, int el, int kl) {
+  return (float)gd_reduce_core_d(src, stride, k0, k1, el, kl);
 }
 
 // A list of reduce jobs in one launch (blockIdx.y = job): element e of a job = the sum of src[e + k * stride], k < nparts.
@@ -178,6 +182,102 @@ template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_reduce_ker
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Batch-statistics BatchNorm (F.batch_norm(training=True)), shared by the three parts.  One job = one BatchNorm = the rows
+// [R][C] of its pre-BatchNorm map z (R = the rows it sees: batch * s * s; in the heads one level); blockIdx.y = job.
+//   forward   the producing epilogue stores z only;  stats (per (row tile, channel) the sums of z and z^2, in double, a thread
+//             walks its tile in row order);  finish (fixed-order second pass, mean and biased variance in double, the EFFECTIVE
+//             table gamma, beta, mean, var [4][C] in the layout gd_bn_load reads, the running-statistics update);  apply (z -> a)
+//   backward  every consumer reads the effective table instead of the parameters: that gives x^ and d a, the "frozen"
+//             d z = d a gamma rstd and the partials of d beta = sum d a, d gamma = sum d a x^;  once their reduce has run, dz adds
+//             - gamma rstd (d beta + x^ d gamma) / R in place, before any product reads d z.
+// The variance is (sum z^2 - mean sum z) / R of double sums: no float32 cancellation.
+struct GDBnJob {
+  const float* z;        // pre-BatchNorm rows [R][C]
+  const float* bn;       // the parameters' gamma, beta, running_mean, running_var [4][C]
+  float* eff;            // the effective table [4][C] (workspace)
+  float* stats;          // this BatchNorm's [4][C] in the statistics output: rows 2 and 3 get the new running statistics, rows 0 and 1
+                         // stay untouched; NULL: no update
+  double* part;          // [tiles][C][2]
+  float* io;             // apply: the output rows;  dz: the d z rows, corrected in place
+  const float* dbn;      // dz: the reduced d gamma, d beta [2][C]
+  const float* res; const float* scale;   // apply GD_BN_SCALE_SKIP: the rows to add, the per-image scale of bn(z) (NULL: 1); images of ss rows
+  int R, C, ss;
+};
+template <int NJOBS> struct GDBnArgs { GDBnJob j[NJOBS]; int tile_rows; float momentum; };
+
+// thread = (row tile, channel): channels contiguous, a wave reads 256 consecutive bytes of every row
+template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_stats_kernel(GDBnArgs<NJOBS> a) {
+  const GDBnJob& j = a.j[blockIdx.y];
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
+  const int tile = (int)(gid / j.C), c = (int)(gid % j.C);
+  const int64_t r0 = (int64_t)tile * a.tile_rows;
+  if (r0 >= j.R) return;
+  const int r1 = (int)min((int64_t)j.R, r0 + a.tile_rows);
+  double s = 0.0, q = 0.0;
+  for (int r = (int)r0; r < r1; r++) {
+    const double v = (double)j.z[(int64_t)r * j.C + c];
+    s += v; q = fma(v, v, q);
+  }
+  j.part[((int64_t)tile * j.C + c) * 2] = s;
+  j.part[((int64_t)tile * j.C + c) * 2 + 1] = q;
+}
+
+// workgroup = 16 channels x 16 partial lanes (gd_reduce_core_d, twice)
+template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_finish_kernel(GDBnArgs<NJOBS> a) {
+  const GDBnJob& j = a.j[blockIdx.y];
+  const int el = threadIdx.x % GD_RED_E, kl = threadIdx.x / GD_RED_E, C = j.C;
+  if ((int)blockIdx.x * GD_RED_E >= C) return;              // uniform over the workgroup
+  const int c = blockIdx.x * GD_RED_E + el;
+  const bool live = c < C;
+  const int tiles = (j.R + a.tile_rows - 1) / a.tile_rows;
+  const double s = gd_reduce_core_d(live ? j.part + 2 * c : nullptr, (int64_t)2 * C, 0, tiles, el, kl);
+  __syncthreads();                                          // the first sum is read before the second reuses the staging array
+  const double q = gd_reduce_core_d(live ? j.part + 2 * c + 1 : nullptr, (int64_t)2 * C, 0, tiles, el, kl);
+  if (kl != 0 || !live) return;
+  const double n = (double)j.R, mean = s / n, var = fmax((q - mean * s) / n, 0.0);
+  j.eff[c] = j.bn[c]; j.eff[C + c] = j.bn[C + c]; j.eff[2 * C + c] = (float)mean; j.eff[3 * C + c] = (float)var;
+  if (j.stats) {
+    const double m = (double)a.momentum;
+    j.stats[2 * C + c] = (float)((1.0 - m) * (double)j.bn[2 * C + c] + m * mean);
+    j.stats[3 * C + c] = (float)((1.0 - m) * (double)j.bn[3 * C + c] + m * (var * n / (n - 1.0)));
+  }
+}
+
+// a = bn(z) with the effective table, then nothing | swish(a) | a * scale[image] + res; thread = (GD_DW_ROWS consecutive rows, channel)
+enum { GD_BN_PLAIN = 0, GD_BN_SWISH = 1, GD_BN_SCALE_SKIP = 2 };
+template <int NJOBS, int EPI> __global__ __launch_bounds__(GD_THREADS) void gd_bn_apply_kernel(GDBnArgs<NJOBS> a) {
+  const GDBnJob& j = a.j[blockIdx.y];
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
+  const int64_t ra = gid / j.C * GD_DW_ROWS;
+  const int c = (int)(gid % j.C);
+  if (ra >= j.R) return;
+  const int rb = (int)min((int64_t)j.R, ra + GD_DW_ROWS);
+  const GDBn q = gd_bn_load(j.eff, j.C, c);
+  for (int r = (int)ra; r < rb; r++) {
+    float act = gd_bn_apply(q, j.z[(int64_t)r * j.C + c]);
+    if (EPI == GD_BN_SWISH) act = act * gd_sigmoid(act);
+    if (EPI == GD_BN_SCALE_SKIP) act = fmaf(act, j.scale ? j.scale[r / j.ss] : 1.0f, j.res[(int64_t)r * j.C + c]);
+    j.io[(int64_t)r * j.C + c] = act;
+  }
+}
+
+// d z -= gamma rstd (d beta + x^ d gamma) / R; thread = (GD_DW_ROWS consecutive rows, channel)
+template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_dz_kernel(GDBnArgs<NJOBS> a) {
+  const GDBnJob& j = a.j[blockIdx.y];
+  const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
+  const int64_t ra = gid / j.C * GD_DW_ROWS;
+  const int c = (int)(gid % j.C);
+  if (ra >= j.R) return;
+  const int rb = (int)min((int64_t)j.R, ra + GD_DW_ROWS);
+  const GDBn q = gd_bn_load(j.eff, j.C, c);
+  const float dg = j.dbn[c], db = j.dbn[j.C + c], k = q.gamma * q.rstd / (float)j.R;
+  for (int r = (int)ra; r < rb; r++) {
+    const float zh = (j.z[(int64_t)r * j.C + c] - q.mean) * q.rstd;
+    j.io[(int64_t)r * j.C + c] = fmaf(-k, fmaf(zh, dg, db), j.io[(int64_t)r * j.C + c]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // host side
 static inline unsigned gd_blocks(int64_t n) { return (unsigned)((n + GD_THREADS - 1) / GD_THREADS); }
 // split-K of a weight-gradient product over R rows: about 512 rows per slab, at most max_slabs, slabs a multiple of GD_BK
@@ -185,4 +285,18 @@ static inline void gd_slabs(int R, int max_slabs, int* slab_rows, int* nslab) {
   int ns = R / 512; if (ns < 1) ns = 1; if (ns > max_slabs) ns = max_slabs;
   *slab_rows = ((R + ns - 1) / ns + GD_BK - 1) / GD_BK * GD_BK;
   *nslab = (R + *slab_rows - 1) / *slab_rows;
+}
+// the batch-statistics launches over NJOBS BatchNorms whose largest map has max_rows rows and max_c channels
+template <int NJOBS> static inline void gd_bn_forward(const GDBnArgs<NJOBS>& a, int max_rows, int max_c, int epi, hipStream_t st) {
+  const int64_t tiles = (max_rows + a.tile_rows - 1) / a.tile_rows, quads = (max_rows + GD_DW_ROWS - 1) / GD_DW_ROWS;
+  hipLaunchKernelGGL(gd_bn_stats_kernel<NJOBS>, dim3(gd_blocks(tiles * max_c), NJOBS), dim3(GD_THREADS), 0, st, a);
+  hipLaunchKernelGGL(gd_bn_finish_kernel<NJOBS>, dim3((unsigned)((max_c + GD_RED_E - 1) / GD_RED_E), NJOBS), dim3(GD_THREADS), 0, st, a);
+  const dim3 grid(gd_blocks(quads * max_c), NJOBS);
+  if (epi == GD_BN_SWISH) hipLaunchKernelGGL((gd_bn_apply_kernel<NJOBS, GD_BN_SWISH>), grid, dim3(GD_THREADS), 0, st, a);
+  else if (epi == GD_BN_SCALE_SKIP) hipLaunchKernelGGL((gd_bn_apply_kernel<NJOBS, GD_BN_SCALE_SKIP>), grid, dim3(GD_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((gd_bn_apply_kernel<NJOBS, GD_BN_PLAIN>), grid, dim3(GD_THREADS), 0, st, a);
+}
+template <int NJOBS> static inline void gd_bn_dz(const GDBnArgs<NJOBS>& a, int max_rows, int max_c, hipStream_t st) {
+  const int64_t quads = (max_rows + GD_DW_ROWS - 1) / GD_DW_ROWS;
+  hipLaunchKernelGGL(gd_bn_dz_kernel<NJOBS>, dim3(gd_blocks(quads * max_c), NJOBS), dim3(GD_THREADS), 0, st, a);
 }

@@ -731,44 +731,62 @@ int hep_heads_param_layout(int phi, int num_classes, int64_t* offsets, int capac
   return count;
 } HEP_CATCH_INT
 
-int64_t hep_heads_workspace_bytes(int phi, int num_classes, int size, int batch) try {
+int64_t hep_heads_workspace_bytes_bn(int phi, int num_classes, int size, int batch, int bn_mode) try {
   HGPlan p; const char* why = "";
   if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, "heads: size must be a multiple of 128 in [128, 2048]");
-  if (int rc = heads_plan(phi, num_classes, size, batch, &p, &why)) return fail(rc, why);
+  if (int rc = heads_plan(phi, num_classes, size, batch, &p, &why, bn_mode)) return fail(rc, why);
   return p.ws_floats * (int64_t)sizeof(float);
 } HEP_CATCH_INT
 
-static int heads_check(int phi, int num_classes, int size, int batch, const void* workspace, size_t workspace_bytes, HGPlan* p) {
+int64_t hep_heads_workspace_bytes(int phi, int num_classes, int size, int batch) try {
+  return hep_heads_workspace_bytes_bn(phi, num_classes, size, batch, HEP_BN_RUNNING);
+} HEP_CATCH_INT
+
+static int heads_check(int phi, int num_classes, int size, int batch, int bn_mode, const void* workspace, size_t workspace_bytes, HGPlan* p) {
   const char* why = "";
   if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, "heads: size must be a multiple of 128 in [128, 2048]");
-  if (int rc = heads_plan(phi, num_classes, size, batch, p, &why)) return fail(rc, why);
+  if (int rc = heads_plan(phi, num_classes, size, batch, p, &why, bn_mode)) return fail(rc, why);
   if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "heads: the workspace must be 16-byte aligned");
   if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "heads: the workspace is smaller than hep_heads_workspace_bytes");
   return 0;
 }
 
-int hep_heads_forward_device(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
-                             float* const outs[5], void* workspace, size_t workspace_bytes, void* stream) try {
+int hep_heads_forward_device_bn(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
+                                float* const outs[5], void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out,
+                                void* stream) try {
   if (!params || !feats || !outs || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
   for (int i = 0; i < 5; i++) if (!feats[i] || !outs[i]) return fail(HEP_ERR_INVALID, "bad argument");
   if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, "heads: the BatchNorm momentum must be in [0, 1]");
   HGPlan p;
-  if (int rc = heads_check(phi, num_classes, size, batch, workspace, workspace_bytes, &p)) return rc;
-  launch_heads_forward(p, params, feats, outs, (float*)workspace, (hipStream_t)stream);
+  if (int rc = heads_check(phi, num_classes, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
+  launch_heads_forward(p, params, feats, outs, (float*)workspace, (hipStream_t)stream, momentum, stats_out);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_heads_forward_device(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
+                             float* const outs[5], void* workspace, size_t workspace_bytes, void* stream) try {
+  return hep_heads_forward_device_bn(params, feats, phi, num_classes, size, batch, outs, workspace, workspace_bytes, HEP_BN_RUNNING, 0.0f, nullptr, stream);
+} HEP_CATCH_INT
+
+int hep_heads_backward_device_bn(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
+                                 float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, int bn_mode,
+                                 void* stream) try {
+  if (!params || !grad_outs || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 5; i++) if (!grad_outs[i] || (grad_feats && !grad_feats[i])) return fail(HEP_ERR_INVALID, "bad argument");
+  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  HGPlan p;
+  if (int rc = heads_check(phi, num_classes, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
+  launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, (float*)workspace, (hipStream_t)stream);
   HIPRET(hipGetLastError());
   return 0;
 } HEP_CATCH_INT
 
 int hep_heads_backward_device(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
                               float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream) try {
-  if (!params || !grad_outs || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 5; i++) if (!grad_outs[i] || (grad_feats && !grad_feats[i])) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
-  HGPlan p;
-  if (int rc = heads_check(phi, num_classes, size, batch, workspace, workspace_bytes, &p)) return rc;
-  launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, (float*)workspace, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
+  return hep_heads_backward_device_bn(params, grad_outs, phi, num_classes, size, batch, grad_params, grad_feats, workspace, workspace_bytes,
+                                      HEP_BN_RUNNING, stream);
 } HEP_CATCH_INT
 
 // ---- training side: the BiFPN neck, forward and backward (k_neck_grad.hip) ----
@@ -805,44 +823,57 @@ int hep_neck_param_layout(int phi, int64_t* offsets, int capacity) try {
 } HEP_CATCH_INT
 
 static const char* kNeckSize = "neck: size must be a multiple of 128 in [128, 2048]";
-int64_t hep_neck_workspace_bytes(int phi, int size, int batch) try {
+int64_t hep_neck_workspace_bytes_bn(int phi, int size, int batch, int bn_mode) try {
   NGPlan p; const char* why = "";
   if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
-  if (int rc = neck_plan(phi, size, batch, &p, &why)) return fail(rc, why);
+  if (int rc = neck_plan(phi, size, batch, &p, &why, bn_mode)) return fail(rc, why);
   return p.ws_floats * (int64_t)sizeof(float);
 } HEP_CATCH_INT
 
-static int neck_check(int phi, int size, int batch, const void* workspace, size_t workspace_bytes, NGPlan* p) {
+int64_t hep_neck_workspace_bytes(int phi, int size, int batch) try { return hep_neck_workspace_bytes_bn(phi, size, batch, HEP_BN_RUNNING); } HEP_CATCH_INT
+
+static int neck_check(int phi, int size, int batch, int bn_mode, const void* workspace, size_t workspace_bytes, NGPlan* p) {
   const char* why = "";
   if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
-  if (int rc = neck_plan(phi, size, batch, p, &why)) return fail(rc, why);
+  if (int rc = neck_plan(phi, size, batch, p, &why, bn_mode)) return fail(rc, why);
   if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "neck: the workspace must be 16-byte aligned");
   if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "neck: the workspace is smaller than hep_neck_workspace_bytes");
   return 0;
 }
 
-int hep_neck_forward_device(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
-                            void* workspace, size_t workspace_bytes, void* stream) try {
+int hep_neck_forward_device_bn(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                               void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out, void* stream) try {
   if (!params || !taps || !feats || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
   for (int i = 0; i < 3; i++) if (!taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
   for (int i = 0; i < 5; i++) if (!feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, "neck: the BatchNorm momentum must be in [0, 1]");
   NGPlan p;
-  if (int rc = neck_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
-  launch_neck_forward(p, params, taps, feats, (float*)workspace, (hipStream_t)stream);
+  if (int rc = neck_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
+  launch_neck_forward(p, params, taps, feats, (float*)workspace, (hipStream_t)stream, momentum, stats_out);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_neck_forward_device(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                            void* workspace, size_t workspace_bytes, void* stream) try {
+  return hep_neck_forward_device_bn(params, taps, phi, size, batch, feats, workspace, workspace_bytes, HEP_BN_RUNNING, 0.0f, nullptr, stream);
+} HEP_CATCH_INT
+
+int hep_neck_backward_device_bn(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
+                                float* const grad_taps[3], void* workspace, size_t workspace_bytes, int bn_mode, void* stream) try {
+  if (!params || !grad_feats || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 5; i++) if (!grad_feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; i++) if (grad_taps && !grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  NGPlan p;
+  if (int rc = neck_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
+  launch_neck_backward(p, grad_feats, grad_params, grad_taps, (float*)workspace, (hipStream_t)stream);
   HIPRET(hipGetLastError());
   return 0;
 } HEP_CATCH_INT
 
 int hep_neck_backward_device(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
                              float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream) try {
-  if (!params || !grad_feats || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 5; i++) if (!grad_feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 3; i++) if (grad_taps && !grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  NGPlan p;
-  if (int rc = neck_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
-  launch_neck_backward(p, grad_feats, grad_params, grad_taps, (float*)workspace, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
+  return hep_neck_backward_device_bn(params, grad_feats, phi, size, batch, grad_params, grad_taps, workspace, workspace_bytes, HEP_BN_RUNNING, stream);
 } HEP_CATCH_INT
 
 int hep_neck_stage_count(int phi) try {
@@ -882,42 +913,56 @@ int hep_backbone_param_layout(int phi, int64_t* offsets, int capacity) try {
 } HEP_CATCH_INT
 
 static const char* kBackboneSize = "backbone: size must be a multiple of 128 in [128, 2048]";
-int64_t hep_backbone_workspace_bytes(int phi, int size, int batch) try {
+int64_t hep_backbone_workspace_bytes_bn(int phi, int size, int batch, int bn_mode) try {
   BGPlan p; const char* why = "";
   if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
-  if (int rc = backbone_plan(phi, size, batch, &p, &why)) return fail(rc, why);
+  if (int rc = backbone_plan(phi, size, batch, &p, &why, bn_mode)) return fail(rc, why);
   return p.ws_floats * (int64_t)sizeof(float);
 } HEP_CATCH_INT
 
-static int backbone_check(int phi, int size, int batch, const void* workspace, size_t workspace_bytes, BGPlan* p) {
+int64_t hep_backbone_workspace_bytes(int phi, int size, int batch) try { return hep_backbone_workspace_bytes_bn(phi, size, batch, HEP_BN_RUNNING); } HEP_CATCH_INT
+
+static int backbone_check(int phi, int size, int batch, int bn_mode, const void* workspace, size_t workspace_bytes, BGPlan* p) {
   const char* why = "";
   if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
-  if (int rc = backbone_plan(phi, size, batch, p, &why)) return fail(rc, why);
+  if (int rc = backbone_plan(phi, size, batch, p, &why, bn_mode)) return fail(rc, why);
   if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "backbone: the workspace must be 16-byte aligned");
   if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "backbone: the workspace is smaller than hep_backbone_workspace_bytes");
   return 0;
 }
 
-int hep_backbone_forward_device(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
-                                void* workspace, size_t workspace_bytes, void* stream) try {
+int hep_backbone_forward_device_bn(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
+                                   void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out, void* stream) try {
   if (!params || !image || !taps || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
   for (int i = 0; i < 3; i++) if (!taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, "backbone: the BatchNorm momentum must be in [0, 1]");
   static thread_local BGPlan p;
-  if (int rc = backbone_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
-  launch_backbone_forward(p, params, image, branch_scale, taps, (float*)workspace, (hipStream_t)stream);
+  if (int rc = backbone_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
+  launch_backbone_forward(p, params, image, branch_scale, taps, (float*)workspace, (hipStream_t)stream, momentum, stats_out);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_backbone_forward_device(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
+                                void* workspace, size_t workspace_bytes, void* stream) try {
+  return hep_backbone_forward_device_bn(params, image, branch_scale, phi, size, batch, taps, workspace, workspace_bytes, HEP_BN_RUNNING, 0.0f, nullptr, stream);
+} HEP_CATCH_INT
+
+int hep_backbone_backward_device_bn(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
+                                    float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, int bn_mode, void* stream) try {
+  if (!params || !grad_taps || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
+  for (int i = 0; i < 3; i++) if (!grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
+  static thread_local BGPlan p;
+  if (int rc = backbone_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
+  launch_backbone_backward(p, grad_taps, branch_scale, grad_params, grad_image, (float*)workspace, (hipStream_t)stream);
   HIPRET(hipGetLastError());
   return 0;
 } HEP_CATCH_INT
 
 int hep_backbone_backward_device(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
                                  float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, void* stream) try {
-  if (!params || !grad_taps || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 3; i++) if (!grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  static thread_local BGPlan p;
-  if (int rc = backbone_check(phi, size, batch, workspace, workspace_bytes, &p)) return rc;
-  launch_backbone_backward(p, grad_taps, branch_scale, grad_params, grad_image, (float*)workspace, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
+  return hep_backbone_backward_device_bn(params, grad_taps, branch_scale, phi, size, batch, grad_params, grad_image, workspace, workspace_bytes,
+                                         HEP_BN_RUNNING, stream);
 } HEP_CATCH_INT
 
 int hep_backbone_stage_count(int phi) try {

@@ -382,10 +382,14 @@ struct HGPlan {
   int64_t p_conv[HG_NETS], p_bn[HG_NETS], p_hdr[HG_SLOTS], nparams;   // float offsets into the flat parameter buffer
   int64_t o_x0, o_x, o_u, o_z, o_uh, o_cl, o_do[HG_SLOTS], o_g1, o_g2, o_pw[HG_SLOTS], o_pdw[HG_SLOTS], o_pbh[HG_SLOTS],
       o_pg[2], o_pb[2], o_pbi[2], ws_floats;            // float offsets into the workspace
+  int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
+  int64_t o_bne, o_bnp;                                 // ... its effective tables (layout of p_bn per net) and the statistics partials
 };
 // fills the plan; returns 0, or a negative HEP_ERR_* with a reason in *why (a static string)
-int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why);
-void launch_heads_forward(const HGPlan&, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t);
+int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode = 0);
+// momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
+void launch_heads_forward(const HGPlan&, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t,
+                          float momentum = 0.0f, float* stats_out = nullptr);
 void launch_heads_backward(const HGPlan&, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
                            float* ws, hipStream_t);
 
@@ -408,12 +412,16 @@ struct NGPlan {
   int64_t o_pp[NG_MAX_CELLS], o_tap[3], o_lz[NG_LATERALS], o_ly[NG_LATERALS], o_p6, o_p7, o_am6, o_am7;
   int64_t o_s[NG_MAX_CELLS][NG_NODES], o_u[NG_MAX_CELLS][NG_NODES], o_z[NG_MAX_CELLS][NG_NODES], o_y[NG_MAX_CELLS][NG_NODES], o_am[NG_MAX_CELLS][NG_NODES];
   int64_t o_x, o_dz, o_du, o_ds[2][NG_NODES], o_g6, o_g7, o_pw, o_pdw, o_pb[3], o_pf[3], o_dtap[NG_LATERALS], ws_floats;
+  int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
+  int64_t o_bne, o_bnp;                                 // ... an effective table per BatchNorm (laterals, then cell by cell); the statistics partials
 };
 // fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
-int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why);
+int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why, int bn_mode = 0);
 int neck_stage_count(const NGPlan&);
 int neck_stage(const NGPlan&, int i, char name[32], int* level, int64_t* offset_floats);
-void launch_neck_forward(const NGPlan&, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t);
+// momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
+void launch_neck_forward(const NGPlan&, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t,
+                         float momentum = 0.0f, float* stats_out = nullptr);
 void launch_neck_backward(const NGPlan&, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t);
 
 // ---- training side: forward and backward of the EfficientNet trunk (k_backbone_grad.hip) ----
@@ -431,6 +439,7 @@ struct BGBlock {
   // float offsets into the workspace: the two aligned parameter copies; what the forward keeps (conv outputs z0 z1 z2, swish(bn0(z0)),
   // the gated map, the block's output, per image the squeezed means, the reduce FC's output and the gate)
   int64_t q_a, q_b, o_z0, o_a0, o_z1, o_xg, o_z2, o_y, o_m, o_r, o_g;
+  int64_t o_e0, o_e1, o_e2;                             // batch statistics: the effective tables of bn0, bn1, bn2
 };
 struct BGPlan {
   int phi, nblocks, stem, B, size, s0, R0;
@@ -439,14 +448,18 @@ struct BGPlan {
   BGBlock b[BG_MAX_BLOCKS];
   // workspace: stem parameters, the image, the stem's conv output and activation; temporaries of forward (a1) and backward
   int64_t q_stem, o_img, o_zs, o_as, o_a1, o_dy[2], o_dz2, o_dxg, o_da0, o_dx, o_pw, o_pcol[2], o_pdw, o_pse, o_dl, o_dr, o_dm, ws_floats;
+  int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
+  int64_t o_es, o_bnp;                                  // ... the stem's effective table; the statistics partials
 };
 // fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
-int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why);
+int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why, int bn_mode = 0);
 int backbone_tensor_count(const BGPlan&);
 void backbone_tensor_offsets(const BGPlan&, int64_t* offsets);
 int backbone_stage_count(const BGPlan&);
 int backbone_stage(const BGPlan&, int i, char name[32], int* side, int* channels, int64_t* offset_floats);
-void launch_backbone_forward(const BGPlan&, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t);
+// momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
+void launch_backbone_forward(const BGPlan&, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t,
+                             float momentum = 0.0f, float* stats_out = nullptr);
 void launch_backbone_backward(const BGPlan&, const float* const grad_taps[3], const float* branch_scale, float* grad_params, float* grad_image, float* ws,
                               hipStream_t);
 

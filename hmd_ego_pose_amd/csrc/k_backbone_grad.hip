@@ -1,8 +1,11 @@
 // k_backbone_grad.hip - training forward and backward of the EfficientNet trunk (backbone_net.model.*: stem conv + BN + swish
 // and every MBConv block; reference efficientnet/model.py:69-104, efficientdet/model.py:436-458) on gfx950, fp32, as a function
-// of (its parameters, the image [B,3,S,S]) with the three taps P3 / P4 / P5 as outputs.  The function is the inference
+// of (its parameters, the image [B,3,S,S]) with the three taps P3 / P4 / P5 as outputs.  By default the function is the inference
 // function: BatchNorm uses the RUNNING statistics in forward and backward; gamma and beta get gradients, the statistics get
-// zero.  Drop-connect enters as data: branch_scale[block][image] multiplies the residual branch of the blocks that add their
+// zero.  HEP_BN_BATCH: the stem's BatchNorm and every bn0 / bn1 / bn2 normalise with the statistics of their map's rows (the shared
+// passes of grad_dev.h): stem, gemm<FWD> and dw_fwd store z only, then statistics / finish / apply (swish; none; * branch_scale +
+// skip for bn2); in the backward the gamma / beta reduce and the d z correction follow out_bwd / act_bwd, ahead of whatever reads
+// d z.  Drop-connect enters as data: branch_scale[block][image] multiplies the residual branch of the blocks that add their
 // input (NULL: every scale is 1).
 //
 // Plain layouts, as k_neck_grad.hip has (the GEMM tile and the reduce are grad_dev.h's): every map is rows [B * s * s][C],
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(GD_THREADS) void bg_nchw_from_rows_kernel(int B, in
 // ------------------------------------------------------------------------------------------------------------------
 // stem: 3 x 3 stride 2 over the NCHW image of even side S, TF-SAME = no padding before, one row / column after
 __global__ __launch_bounds__(GD_THREADS) void bg_stem_fwd_kernel(int B, int S, int C, const float* __restrict__ img, const float* __restrict__ w,
-                                                                 const float* __restrict__ bn, float* __restrict__ Z, float* __restrict__ A) {
+                                                                 const float* __restrict__ bn, float* __restrict__ Z, float* __restrict__ A, int z_only) {
   const int s = S >> 1;
   const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * s * s * C) return;
@@ -74,8 +77,9 @@ __global__ __launch_bounds__(GD_THREADS) void bg_stem_fwd_kernel(int B, int S, i
         const int y = 2 * oy + i, x = 2 * ox + j;
         if (y < S && x < S) acc = fmaf(w[c * 27 + ci * 9 + i * 3 + j], img[((int64_t)(b * 3 + ci) * S + y) * S + x], acc);
       }
-  const float v = gd_bn_apply(gd_bn_load(bn, C, c), acc);
   Z[idx] = acc;
+  if (z_only) return;                                      // batch statistics: the BatchNorm passes of grad_dev.h make A
+  const float v = gd_bn_apply(gd_bn_load(bn, C, c), acc);
   A[idx] = v * gd_sigmoid(v);
 }
 
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(GD_THREADS) void bg_stem_dgrad_kernel(int B, int S,
 // depthwise K x K, stride 1 / 2, TF-SAME (pad rows / columns before; the rest falls after), fused with bn1 + swish
 template <int K> __global__ __launch_bounds__(GD_THREADS) void bg_dw_fwd_kernel(int B, int si, int so, int stride, int pad, int C, const float* __restrict__ X,
                                                                                 const float* __restrict__ w, const float* __restrict__ bn,
-                                                                                float* __restrict__ Z, float* __restrict__ A) {
+                                                                                float* __restrict__ Z, float* __restrict__ A, int z_only) {
   const int64_t idx = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   if (idx >= (int64_t)B * so * so * C) return;
   const int r = (int)(idx / C), c = (int)(idx % C), b = r / (so * so), pix = r % (so * so), oy = pix / so, ox = pix % so;
@@ -148,8 +152,9 @@ template <int K> __global__ __launch_bounds__(GD_THREADS) void bg_dw_fwd_kernel(
       acc = fmaf(w[c * K * K + i * K + j], X[((int64_t)(b * si + y) * si + x) * C + c], acc);
     }
   }
-  const float v = gd_bn_apply(gd_bn_load(bn, C, c), acc);
   Z[idx] = acc;
+  if (z_only) return;                                      // batch statistics: the BatchNorm passes of grad_dev.h make A
+  const float v = gd_bn_apply(gd_bn_load(bn, C, c), acc);
   A[idx] = v * gd_sigmoid(v);
 }
 
@@ -342,6 +347,7 @@ struct BGGemmArgs {
   const float* bn;                               // FWD: gamma, beta, mean, var [4][J]
   const float* res; const float* scale;          // FWD without act: the block's input rows to add (or NULL), the per-image branch scale (or NULL)
   int I, J, K, lda, ldb, ldc, ntn, slab_rows, act, ss;
+  int z_only;                                    // FWD with batch statistics: store z, the BatchNorm passes of grad_dev.h make C2
 };
 // C[i][j] = sum_k A(i,k) B(k,j), 64 x 64 per workgroup, wave w owns rows 16w..16w+15 and four 16-column accumulators; edge
 // tiles are masked at the loads and at the stores (channel counts are multiples of 8, not of 64).
@@ -363,14 +369,16 @@ template <int MODE> __global__ __launch_bounds__(GD_THREADS) void bg_gemm_kernel
   gd_acc_visit(acc, i0, I, j0, J, lane, wv, [=](int m, int n, float v, const GDBn& q) {
     if (MODE == BG_FWD) {
       const int64_t at = (int64_t)m * a.ldc + n;
-      float y = gd_bn_apply(q, v);
-      if (a.act) {
-        y = y * gd_sigmoid(y);
-      } else if (a.res) {
-        y = fmaf(y, a.scale ? a.scale[m / a.ss] : 1.0f, a.res[at]);
-      }
       a.C[at] = v;
-      a.C2[at] = y;
+      if (!a.z_only) {
+        float y = gd_bn_apply(q, v);
+        if (a.act) {
+          y = y * gd_sigmoid(y);
+        } else if (a.res) {
+          y = fmaf(y, a.scale ? a.scale[m / a.ss] : 1.0f, a.res[at]);
+        }
+        a.C2[at] = y;
+      }
     } else if (MODE == BG_DATA) {
       a.C[(int64_t)m * a.ldc + n] = v;
     } else {
@@ -454,8 +462,10 @@ static inline void bg_chunks(int ss, int* chunk_rows, int* nchunk) {
   *nchunk = (ss + *chunk_rows - 1) / *chunk_rows;
 }
 
-int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why) {
+int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why, int bn_mode) {
   hep::Arch arch;
+  if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "backbone: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
+  p->bn_batch = bn_mode == HEP_BN_BATCH;
   if (!hep::make_arch(phi, &arch)) { *why = "backbone: phi must be in 0..7 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
   if ((int)arch.blocks.size() > BG_MAX_BLOCKS) { *why = "backbone: too many blocks"; return HEP_ERR_UNSUPPORTED; }
   p->phi = phi; p->nblocks = (int)arch.blocks.size(); p->stem = arch.stem; p->B = 0; p->size = 0;
@@ -525,6 +535,17 @@ int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why) {
   p->o_dxg = take(m_xg); p->o_da0 = take(m_a0); p->o_dx = take(m_x);
   p->o_pw = take(m_pw); p->o_pcol[0] = take(m_col); p->o_pcol[1] = take(m_col); p->o_pdw = take(m_pdw); p->o_pse = take(m_pse);
   p->o_dl = take(m_bc); p->o_dm = take(m_bc); p->o_dr = take(m_bs);
+  p->o_es = p->o_bnp = 0;
+  for (int i = 0; i < p->nblocks; i++) p->b[i].o_e0 = p->b[i].o_e1 = p->b[i].o_e2 = 0;
+  if (p->bn_batch) {                                       // an effective table per BatchNorm; [tile][C][2] doubles (the smallest map has 16 rows: never < 2)
+    p->o_es = take(4 * p->stem);
+    for (int i = 0; i < p->nblocks; i++) {
+      BGBlock& b = p->b[i];
+      if (b.expand) b.o_e0 = take(4 * b.cexp);
+      b.o_e1 = take(4 * b.cexp); b.o_e2 = take(4 * b.cout);
+    }
+    p->o_bnp = take(4 * m_col);
+  }
   p->ws_floats = w;
   return 0;
 }
@@ -583,10 +604,39 @@ void bg_bn_jobs(const BGPlan& p, float* ws, int R, int C, float* dbn, GDReduceAr
   rd->j[at + 1] = GDRedJob{ws + p.o_pcol[1], dbn + C, C, C, T};
   rd->j[at + 2] = GDRedJob{nullptr, dbn + 2 * C, 2 * C, 0, 0};
 }
+
+// Batch statistics: one BatchNorm over the rows [R][C] of z as a job of grad_dev.h's kernels, its effective table at ws + eff_at
+GDBnArgs<1> bg_bn_job(const BGPlan& p, float* ws, int R, int C, const float* z, const float* bn, int64_t eff_at) {
+  GDBnArgs<1> a{};
+  a.tile_rows = bg_tile_rows(R);
+  a.j[0].z = z; a.j[0].bn = bn; a.j[0].eff = ws + eff_at;
+  a.j[0].part = reinterpret_cast<double*>(ws + p.o_bnp);
+  a.j[0].R = R; a.j[0].C = C;
+  return a;
+}
+// what follows the kernel that left the "frozen" d z and the gamma / beta partials: their reduce first, then d z corrected in
+// place - before any product reads it; the stage's own reduce then has its weight job only
+void bg_bn_backward(const BGPlan& p, float* ws, int R, int C, const float* z, int64_t eff_at, float* dz, float* dbn, hipStream_t st) {
+  GDReduceArgs<BG_RED_JOBS> rd{};
+  bg_bn_jobs(p, ws, R, C, dbn, &rd, 1);
+  bg_reduce(rd, st);
+  GDBnArgs<1> a = bg_bn_job(p, ws, R, C, z, nullptr, eff_at);
+  a.j[0].io = dz; a.j[0].dbn = dbn;
+  gd_bn_dz(a, R, C, st);
+}
 }  // namespace
 
-void launch_backbone_forward(const BGPlan& p, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t st) {
-  const int B = p.B;
+void launch_backbone_forward(const BGPlan& p, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t st,
+                             float momentum, float* stats_out) {
+  const int B = p.B, zo = p.bn_batch;
+  // batch statistics: z -> statistics -> the effective table and the running-statistics update -> the activation
+  auto bn_forward = [&](int R, int C, const float* z, const float* bn, int64_t eff_at, int64_t table_at, float* out, int epi, const float* res,
+                        const float* scale, int ss) {
+    GDBnArgs<1> a = bg_bn_job(p, ws, R, C, z, bn, eff_at);
+    a.momentum = momentum;
+    a.j[0].io = out; a.j[0].stats = stats_out ? stats_out + table_at : nullptr; a.j[0].res = res; a.j[0].scale = scale; a.j[0].ss = ss;
+    gd_bn_forward(a, R, C, epi, st);
+  };
   {
     BGPackArgs pk{};
     int n = 0;
@@ -603,7 +653,8 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
   const int64_t nimg = (int64_t)B * 3 * p.size * p.size;
   hipLaunchKernelGGL(bg_copy_kernel, dim3(gd_blocks(nimg)), dim3(GD_THREADS), 0, st, nimg, image, ws + p.o_img);
   hipLaunchKernelGGL(bg_stem_fwd_kernel, dim3(gd_blocks((int64_t)p.R0 * p.stem)), dim3(GD_THREADS), 0, st, B, p.size, p.stem, image, ps,
-                     ps + (p.p_bn_stem - p.p_stem), ws + p.o_zs, ws + p.o_as);
+                     ps + (p.p_bn_stem - p.p_stem), ws + p.o_zs, ws + p.o_as, zo);
+  if (zo) bn_forward(p.R0, p.stem, ws + p.o_zs, ps + (p.p_bn_stem - p.p_stem), p.o_es, p.p_bn_stem, ws + p.o_as, GD_BN_SWISH, nullptr, nullptr, 1);
   const float* x = ws + p.o_as;
   for (int i = 0; i < p.nblocks; i++) {
     const BGBlock& b = p.b[i];
@@ -611,17 +662,19 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
     const float* dwin = x;
     if (b.expand) {
       BGGemmArgs m{}; m.A = x; m.Bm = bg_pa(p, ws, i, b.p_w0); m.bn = bg_pa(p, ws, i, b.p_bn0); m.C = ws + b.o_z0; m.C2 = ws + b.o_a0;
-      m.I = b.R_in; m.J = b.cexp; m.K = b.cin; m.lda = b.cin; m.ldb = b.cin; m.ldc = b.cexp; m.act = 1; m.ss = 1;
+      m.I = b.R_in; m.J = b.cexp; m.K = b.cin; m.lda = b.cin; m.ldb = b.cin; m.ldc = b.cexp; m.act = 1; m.ss = 1; m.z_only = zo;
       bg_gemm(BG_FWD, m, 1, st);
+      if (zo) bn_forward(b.R_in, b.cexp, m.C, m.bn, b.o_e0, b.p_bn0, m.C2, GD_BN_SWISH, nullptr, nullptr, 1);
       dwin = ws + b.o_a0;
     }
     const int64_t nmid = (int64_t)b.R_out * b.cexp;
     if (b.k == 3)
       hipLaunchKernelGGL(bg_dw_fwd_kernel<3>, dim3(gd_blocks(nmid)), dim3(GD_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, dwin,
-                         bg_pa(p, ws, i, b.p_dw), bg_pa(p, ws, i, b.p_bn1), ws + b.o_z1, ws + p.o_a1);
+                         bg_pa(p, ws, i, b.p_dw), bg_pa(p, ws, i, b.p_bn1), ws + b.o_z1, ws + p.o_a1, zo);
     else
       hipLaunchKernelGGL(bg_dw_fwd_kernel<5>, dim3(gd_blocks(nmid)), dim3(GD_THREADS), 0, st, B, b.s_in, b.s_out, b.stride, pad, b.cexp, dwin,
-                         bg_pa(p, ws, i, b.p_dw), bg_pa(p, ws, i, b.p_bn1), ws + b.o_z1, ws + p.o_a1);
+                         bg_pa(p, ws, i, b.p_dw), bg_pa(p, ws, i, b.p_bn1), ws + b.o_z1, ws + p.o_a1, zo);
+    if (zo) bn_forward(b.R_out, b.cexp, ws + b.o_z1, bg_pa(p, ws, i, b.p_bn1), b.o_e1, b.p_bn1, ws + p.o_a1, GD_BN_SWISH, nullptr, nullptr, 1);
     int cr, nc;
     bg_chunks(ss, &cr, &nc);
     hipLaunchKernelGGL(bg_se_sum_kernel<true>, dim3(gd_blocks((int64_t)B * nc * b.cexp)), dim3(GD_THREADS), 0, st, B, ss, b.cexp, nc, cr,
@@ -633,7 +686,9 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
     BGGemmArgs m{}; m.A = ws + b.o_xg; m.Bm = bg_pb(p, ws, i, b.p_w2); m.bn = bg_pb(p, ws, i, b.p_bn2); m.C = ws + b.o_z2; m.C2 = ws + b.o_y;
     m.I = b.R_out; m.J = b.cout; m.K = b.cexp; m.lda = b.cexp; m.ldb = b.cexp; m.ldc = b.cout; m.act = 0; m.ss = ss;
     if (b.skip) { m.res = x; m.scale = branch_scale ? branch_scale + (int64_t)i * B : nullptr; }
+    m.z_only = zo;
     bg_gemm(BG_FWD, m, 1, st);
+    if (zo) bn_forward(b.R_out, b.cout, m.C, m.bn, b.o_e2, b.p_bn2, m.C2, b.skip ? GD_BN_SCALE_SKIP : GD_BN_PLAIN, m.res, m.scale, ss);
     x = ws + b.o_y;
   }
   for (int t = 0; t < 3; t++) {
@@ -648,6 +703,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
   const int B = p.B;
   float* pg = ws + p.o_pcol[0];
   float* pb = ws + p.o_pcol[1];
+  const bool bb = p.bn_batch;       // batch statistics: the tables are the forward's effective ones; every d z is corrected before it is read
   for (int i = p.nblocks - 1; i >= 0; i--) {
     const BGBlock& b = p.b[i];
     const int ss = b.s_out * b.s_out, pad = b.stride == 1 ? (b.k - 1) / 2 : (b.k - 2) / 2;
@@ -657,8 +713,9 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     if (i + 1 < p.nblocks) { oa.gdata = ws + p.o_dx; if (p.b[i + 1].skip) oa.gskip = ws + p.o_dy[(i + 1) & 1]; }
     for (int t = 0; t < 3; t++) if (p.taps[t] == i) oa.cot = grad_taps[t];
     if (b.skip && branch_scale) oa.scale = branch_scale + (int64_t)i * B;
-    oa.Z = ws + b.o_z2; oa.bn = bg_pb(p, ws, i, b.p_bn2); oa.dY = ws + p.o_dy[i & 1]; oa.dZ = ws + p.o_dz2; oa.pgamma = pg; oa.pbeta = pb;
+    oa.Z = ws + b.o_z2; oa.bn = bb ? ws + b.o_e2 : bg_pb(p, ws, i, b.p_bn2); oa.dY = ws + p.o_dy[i & 1]; oa.dZ = ws + p.o_dz2; oa.pgamma = pg; oa.pbeta = pb;
     hipLaunchKernelGGL(bg_out_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cout)), dim3(GD_THREADS), 0, st, oa);
+    if (bb) bg_bn_backward(p, ws, b.R_out, b.cout, oa.Z, b.o_e2, ws + p.o_dz2, grad_params + b.p_bn2, st);
     // project conv
     BGGemmArgs md{}; md.A = ws + p.o_dz2; md.Bm = bg_pb(p, ws, i, b.p_w2); md.C = ws + p.o_dxg; md.I = b.R_out; md.J = b.cexp; md.K = b.cout;
     md.lda = b.cout; md.ldb = b.cexp; md.ldc = b.cexp;
@@ -671,22 +728,23 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     {
       GDReduceArgs<BG_RED_JOBS> rd{};
       rd.j[0] = GDRedJob{ws + p.o_pw, grad_params + b.p_w2, (int64_t)b.cout * b.cexp, (int64_t)b.cout * b.cexp, ns};
-      bg_bn_jobs(p, ws, b.R_out, b.cout, grad_params + b.p_bn2, &rd, 1);
+      if (!bb) bg_bn_jobs(p, ws, b.R_out, b.cout, grad_params + b.p_bn2, &rd, 1);
       bg_reduce(rd, st);
     }
     // squeeze-excite
     int cr, nc;
     bg_chunks(ss, &cr, &nc);
     hipLaunchKernelGGL(bg_se_sum_kernel<false>, dim3(gd_blocks((int64_t)B * nc * b.cexp)), dim3(GD_THREADS), 0, st, B, ss, b.cexp, nc, cr,
-                       (const float*)(ws + p.o_dxg), (const float*)(ws + b.o_z1), bg_pa(p, ws, i, b.p_bn1), ws + p.o_pse);
+                       (const float*)(ws + p.o_dxg), (const float*)(ws + b.o_z1), bb ? (const float*)(ws + b.o_e1) : bg_pa(p, ws, i, b.p_bn1), ws + p.o_pse);
     hipLaunchKernelGGL(bg_se_bwd_kernel, dim3(B), dim3(GD_THREADS), 0, st, ss, b.cexp, b.se, nc, (const float*)(ws + p.o_pse), bg_pa(p, ws, i, b.p_wr),
                        bg_pa(p, ws, i, b.p_we), (const float*)(ws + b.o_r), (const float*)(ws + b.o_g), ws + p.o_dl, ws + p.o_dr, ws + p.o_dm);
     hipLaunchKernelGGL(bg_se_wgrad_kernel, dim3(gd_blocks(b.p_w2 - b.p_wr)), dim3(GD_THREADS), 0, st, B, b.cexp, b.se, (const float*)(ws + b.o_m),
                        (const float*)(ws + b.o_r), (const float*)(ws + p.o_dl), (const float*)(ws + p.o_dr), grad_params + b.p_wr);
     // gate, swish, bn1: d z1 in place of d xg
     BGActArgs aa{}; aa.ss = ss; aa.C = b.cexp; aa.R = b.R_out; aa.tile_rows = bg_tile_rows(b.R_out);
-    aa.G = ws + p.o_dxg; aa.Z = ws + b.o_z1; aa.bn = bg_pa(p, ws, i, b.p_bn1); aa.gate = ws + b.o_g; aa.dmean = ws + p.o_dm; aa.pgamma = pg; aa.pbeta = pb;
+    aa.G = ws + p.o_dxg; aa.Z = ws + b.o_z1; aa.bn = bb ? ws + b.o_e1 : bg_pa(p, ws, i, b.p_bn1); aa.gate = ws + b.o_g; aa.dmean = ws + p.o_dm; aa.pgamma = pg; aa.pbeta = pb;
     hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cexp)), dim3(GD_THREADS), 0, st, aa);
+    if (bb) bg_bn_backward(p, ws, b.R_out, b.cexp, aa.Z, b.o_e1, aa.G, grad_params + b.p_bn1, st);
     // depthwise
     const float* dwin = b.expand ? ws + b.o_a0 : x;
     float* ddw = b.expand ? ws + p.o_da0 : ws + p.o_dx;
@@ -706,14 +764,15 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
       GDReduceArgs<BG_RED_JOBS> rd{};
       const int64_t n = (int64_t)b.cexp * b.k * b.k;
       rd.j[0] = GDRedJob{ws + p.o_pdw, grad_params + b.p_dw, n, n, bg_ntiles(b.R_out)};
-      bg_bn_jobs(p, ws, b.R_out, b.cexp, grad_params + b.p_bn1, &rd, 1);
+      if (!bb) bg_bn_jobs(p, ws, b.R_out, b.cexp, grad_params + b.p_bn1, &rd, 1);
       bg_reduce(rd, st);
     }
     // expand conv
     if (b.expand) {
       BGActArgs ea{}; ea.ss = b.s_in * b.s_in; ea.C = b.cexp; ea.R = b.R_in; ea.tile_rows = bg_tile_rows(b.R_in);
-      ea.G = ws + p.o_da0; ea.Z = ws + b.o_z0; ea.bn = bg_pa(p, ws, i, b.p_bn0); ea.pgamma = pg; ea.pbeta = pb;
+      ea.G = ws + p.o_da0; ea.Z = ws + b.o_z0; ea.bn = bb ? ws + b.o_e0 : bg_pa(p, ws, i, b.p_bn0); ea.pgamma = pg; ea.pbeta = pb;
       hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_in) * b.cexp)), dim3(GD_THREADS), 0, st, ea);
+      if (bb) bg_bn_backward(p, ws, b.R_in, b.cexp, ea.Z, b.o_e0, ea.G, grad_params + b.p_bn0, st);
       bg_slabs(b.R_in, &sr, &ns);
       BGGemmArgs ew{}; ew.A = ws + p.o_da0; ew.Bm = x; ew.C = ws + p.o_pw; ew.I = b.cexp; ew.J = b.cin; ew.K = b.R_in; ew.lda = b.cexp; ew.ldb = b.cin;
       ew.slab_rows = sr;
@@ -723,20 +782,21 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
       bg_gemm(BG_DATA, ed, 1, st);
       GDReduceArgs<BG_RED_JOBS> rd{};
       rd.j[0] = GDRedJob{ws + p.o_pw, grad_params + b.p_w0, (int64_t)b.cexp * b.cin, (int64_t)b.cexp * b.cin, ns};
-      bg_bn_jobs(p, ws, b.R_in, b.cexp, grad_params + b.p_bn0, &rd, 1);
+      if (!bb) bg_bn_jobs(p, ws, b.R_in, b.cexp, grad_params + b.p_bn0, &rd, 1);
       bg_reduce(rd, st);
     }
   }
   // the stem: d as = block 0's data path (block 0 never adds its input)
   const float* ps = ws + p.q_stem;
   BGActArgs sa{}; sa.ss = p.s0 * p.s0; sa.C = p.stem; sa.R = p.R0; sa.tile_rows = bg_tile_rows(p.R0);
-  sa.G = ws + p.o_dx; sa.Z = ws + p.o_zs; sa.bn = ps + (p.p_bn_stem - p.p_stem); sa.pgamma = pg; sa.pbeta = pb;
+  sa.G = ws + p.o_dx; sa.Z = ws + p.o_zs; sa.bn = bb ? ws + p.o_es : ps + (p.p_bn_stem - p.p_stem); sa.pgamma = pg; sa.pbeta = pb;
   hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(GD_THREADS), 0, st, sa);
+  if (bb) bg_bn_backward(p, ws, p.R0, p.stem, sa.Z, p.o_es, sa.G, grad_params + p.p_bn_stem, st);
   hipLaunchKernelGGL(bg_stem_wgrad_kernel, dim3(gd_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(GD_THREADS), 0, st, B, p.size, p.stem, p.R0,
                      bg_tile_rows(p.R0), (const float*)(ws + p.o_dx), (const float*)(ws + p.o_img), ws + p.o_pdw);
   GDReduceArgs<BG_RED_JOBS> rd{};
   rd.j[0] = GDRedJob{ws + p.o_pdw, grad_params + p.p_stem, (int64_t)p.stem * 27, (int64_t)p.stem * 27, bg_ntiles(p.R0)};
-  bg_bn_jobs(p, ws, p.R0, p.stem, grad_params + p.p_bn_stem, &rd, 1);
+  if (!bb) bg_bn_jobs(p, ws, p.R0, p.stem, grad_params + p.p_bn_stem, &rd, 1);
   bg_reduce(rd, st);
   if (grad_image)
     hipLaunchKernelGGL(bg_stem_dgrad_kernel, dim3(gd_blocks((int64_t)B * 3 * p.size * p.size)), dim3(GD_THREADS), 0, st, B, p.size, p.stem,

@@ -1,7 +1,10 @@
 // k_head_grad.hip - training forward and backward of the five head nets (regressor, classifier, rotation_net,
 // translation_net, hand_net; reference efficientdet/model.py:361-417, hmdegopose/model.py:55-228 with
-// num_iteration_steps == 0) on gfx950, fp32.  The function is the inference function: BatchNorm uses the RUNNING
-// statistics in forward and backward (frozen-statistics fine-tuning); gamma and beta get gradients.
+// num_iteration_steps == 0) on gfx950, fp32.  By default the function is the inference function: BatchNorm uses the RUNNING
+// statistics in forward and backward (frozen-statistics fine-tuning); gamma and beta get gradients.  HEP_BN_BATCH: every
+// bn_list.{level}.{i} normalises with the statistics of its level's rows (the shared passes of grad_dev.h): LAYER stores z only,
+// then statistics / finish / apply per layer; in the backward the gamma / beta reduce of a layer and the d z correction run
+// right behind the dw_bwd that produced them, ahead of the products that read d z.
 //
 // Plain layouts, none of the inference plan's (the GEMM tile, the 3 x 3 window and the reduce core are grad_dev.h's, shared
 // with the neck and the backbone): the parameters are one flat buffer in the reference's shapes and state_dict order,
@@ -84,7 +87,7 @@ __global__ __launch_bounds__(GD_THREADS) void hg_dw_fwd_kernel(HGDwArgs a) {
 enum { HG_LAYER = 0, HG_HEADER = 1, HG_DATA = 2, HG_WGRAD = 3 };
 struct HGGemmArgs {
   HGGeom g;
-  int ntmax, bn_lstride;
+  int ntmax, bn_lstride, z_only;       // z_only (batch statistics): LAYER stores z, the BatchNorm passes of grad_dev.h make x'
   const float* A[HG_SLOTS]; const float* Bm[HG_SLOTS]; float* C[HG_SLOTS]; float* C2[HG_SLOTS];
   const float* bias[HG_SLOTS]; const float* bn[HG_SLOTS];
   int I[HG_SLOTS], J[HG_SLOTS], K[HG_SLOTS], Kb[HG_SLOTS], lda[HG_SLOTS], ldb[HG_SLOTS], ldc[HG_SLOTS];
@@ -115,15 +118,17 @@ template <int MODE> __global__ __launch_bounds__(GD_THREADS) void hg_gemm_kernel
   float* const C2 = a.C2[slot];
   const float* const bias = a.bias[slot];
   const float* const bn = a.bn[slot];
-  const int ldc = a.ldc[slot], bn_lstride = a.bn_lstride, K = a.hK[slot], kh = a.hkh[slot], hoff = a.hoff[slot], sig = a.sigmoid[slot];
+  const int ldc = a.ldc[slot], bn_lstride = a.bn_lstride, z_only = a.z_only, K = a.hK[slot], kh = a.hkh[slot], hoff = a.hoff[slot], sig = a.sigmoid[slot];
   gd_acc_visit(acc, i0, I, j0, J, lane, wv, [=, &g](int m, int n, float v) {
     if (MODE == HG_LAYER) {
-      const int l = hg_level(g, m);
-      const GDBn q = gd_bn_load(bn + (int64_t)l * bn_lstride, g.W, n);
       const float z = v + bias[n];
-      const float act = gd_bn_apply(q, z);
       C[(int64_t)m * g.W + n] = z;
-      C2[(int64_t)m * g.W + n] = act * gd_sigmoid(act);
+      if (!z_only) {
+        const int l = hg_level(g, m);
+        const GDBn q = gd_bn_load(bn + (int64_t)l * bn_lstride, g.W, n);
+        const float act = gd_bn_apply(q, z);
+        C2[(int64_t)m * g.W + n] = act * gd_sigmoid(act);
+      }
     } else if (MODE == HG_HEADER) {
       const int l = hg_level(g, m), ss = g.s[l] * g.s[l], q = m - g.rowoff[l], b = q / ss, pix = q % ss;
       const int an = n / kh, jj = n % kh;
@@ -252,7 +257,7 @@ __global__ __launch_bounds__(GD_THREADS) void hg_dw_bwd_kernel(HGDwBwdArgs a) {
 // ------------------------------------------------------------------------------------------------------------------
 struct HGReduceArgs {
   HGGeom g;
-  int bn_lstride;
+  int bn_lstride, kind0;                                                                  // kind0: the first kind of this launch
   const float* pw[HG_SLOTS]; float* dW[HG_SLOTS]; int Cout[HG_SLOTS], I[HG_SLOTS];        // [slab][I][W] -> [Cout][W]
   const float* pdw[HG_SLOTS]; float* ddw[HG_SLOTS];                                       // [tile][W * 9] -> [W * 9]
   const float* pbias[HG_SLOTS]; float* dbias[HG_SLOTS]; int ldb[HG_SLOTS];                // [tile][ldb] -> [Cout]
@@ -260,10 +265,11 @@ struct HGReduceArgs {
 };
 
 // second pass (gd_reduce_core): a workgroup = 16 consecutive elements, 64-byte reads of a partial row.
-// blockIdx.y = slot, blockIdx.z = kind (0 pointwise weight, 1 depthwise weight, 2 bias, 3 BatchNorm of the five levels)
+// blockIdx.y = slot, kind0 + blockIdx.z = kind (0 pointwise weight, 1 depthwise weight, 2 bias - no partials: zero, the bias
+// in front of a batch-statistics BatchNorm - 3 BatchNorm of the five levels)
 __global__ __launch_bounds__(GD_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
   const HGGeom& g = a.g;
-  const int slot = blockIdx.y, kind = blockIdx.z, W = g.W, el = threadIdx.x % GD_RED_E, kl = threadIdx.x / GD_RED_E;
+  const int slot = blockIdx.y, kind = a.kind0 + blockIdx.z, W = g.W, el = threadIdx.x % GD_RED_E, kl = threadIdx.x / GD_RED_E;
   const int64_t e = (int64_t)blockIdx.x * GD_RED_E + el;
   const float* __restrict__ src = nullptr;      // partial k of this element: src[k * stride]
   float* dst = nullptr;
@@ -274,7 +280,7 @@ __global__ __launch_bounds__(GD_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
   } else if (kind == 1) {
     if (a.ddw[slot] && e < (int64_t)W * 9) { src = a.pdw[slot] + e; stride = (int64_t)W * 9; k1 = g.ntiles; dst = a.ddw[slot] + e; }
   } else if (kind == 2) {
-    if (a.dbias[slot] && e < a.Cout[slot]) { src = a.pbias[slot] + e; stride = a.ldb[slot]; k1 = g.ntiles; dst = a.dbias[slot] + e; }
+    if (a.dbias[slot] && e < a.Cout[slot]) { src = a.pbias[slot] ? a.pbias[slot] + e : nullptr; stride = a.ldb[slot]; k1 = g.ntiles; dst = a.dbias[slot] + e; }
   } else if (a.dbn[slot] && e < (int64_t)5 * 4 * W) {
     const int l = (int)(e / (4 * W)), which = (int)(e / W) % 4, c = (int)(e % W);
     dst = a.dbn[slot] + (int64_t)l * a.bn_lstride + which * W + c;
@@ -286,12 +292,14 @@ __global__ __launch_bounds__(GD_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
 
 // ------------------------------------------------------------------------------------------------------------------
 // host side
-int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why) {
+int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode) {
   if (phi < 0 || phi > 7) { *why = "heads: phi must be in 0..7 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
   if (num_classes < 1 || num_classes > 63) { *why = "heads: num_classes must be in 1..63"; return HEP_ERR_UNSUPPORTED; }
   HGGeom& g = p->g;
   g.W = kFpnWidth[phi]; g.D = kHeadDepth[phi];
   p->num_classes = num_classes;
+  p->bn_batch = bn_mode == HEP_BN_BATCH;
+  if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "heads: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
   const int W = g.W, D = g.D;
   const int vals[HG_SLOTS] = {4, num_classes, 3, 2, 1, 63};
   const int nets[HG_SLOTS] = {0, 1, 2, 3, 3, 4}, Ks[HG_SLOTS] = {4, num_classes, 3, 3, 3, 63}, offs[HG_SLOTS] = {0, 0, 0, 0, 2, 0};
@@ -320,6 +328,7 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
   g.pixoff[5] = S; g.S = S;
   if ((int64_t)batch * S > (1 << 22)) { *why = "heads: batch * pixels exceeds 4 Mi rows"; return HEP_ERR_UNSUPPORTED; }
   g.R = batch * S;
+  if (p->bn_batch && batch * g.s[4] * g.s[4] < 2) { *why = "heads: batch statistics need at least 2 rows per BatchNorm (batch * top-level pixels)"; return HEP_ERR_UNSUPPORTED; }
   for (int l = 0; l < 6; l++) g.rowoff[l] = batch * g.pixoff[l];
   for (int l = 0; l < 5; l++) { g.tileoff[l] = tiles; tiles += (batch * g.s[l] * g.s[l] + HG_TILE_ROWS - 1) / HG_TILE_ROWS; }
   g.tileoff[5] = tiles; g.ntiles = tiles;
@@ -335,13 +344,38 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
   for (int h = 0; h < HG_SLOTS; h++) p->o_pdw[h] = take((int64_t)tiles * W * 9);
   for (int h = 0; h < HG_SLOTS; h++) p->o_pbh[h] = take((int64_t)tiles * p->ld[h]);
   for (int k = 0; k < 2; k++) { p->o_pg[k] = take((int64_t)HG_NETS * tiles * W); p->o_pb[k] = take((int64_t)HG_NETS * tiles * W); p->o_pbi[k] = take((int64_t)HG_NETS * tiles * W); }
+  p->o_bne = p->o_bnp = 0;
+  if (p->bn_batch) {                                       // the effective tables in the layout of p_bn; [net][tile][W][2] doubles
+    p->o_bne = take((int64_t)HG_NETS * 5 * D * 4 * W);
+    p->o_bnp = take((int64_t)HG_NETS * tiles * W * 4);
+  }
   p->ws_floats = w;
   return 0;
 }
 
 static inline int64_t hg_conv_stride(const HGGeom& g) { return (int64_t)9 * g.W + (int64_t)g.W * g.W + g.W; }
 
-void launch_heads_forward(const HGPlan& p, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t st) {
+// the effective table of (net, layer) at level 0 (batch statistics), laid out as the parameters' bn_list of the net
+static inline float* hg_bn_eff(const HGPlan& p, float* ws, int n, int i) { return ws + p.o_bne + ((int64_t)n * 5 * p.g.D + i) * 4 * p.g.W; }
+// the 25 BatchNorms (net, level) of layer i as jobs of grad_dev.h's batch-statistics kernels; a job's rows are one level's
+static void hg_bn_jobs(const HGPlan& p, const float* params, float* ws, int i, GDBnArgs<HG_NETS * 5>* a) {
+  const HGGeom& g = p.g;
+  const int W = g.W, bn_lstride = g.D * 4 * W;
+  const int64_t RW = (int64_t)g.R * W;
+  a->tile_rows = HG_TILE_ROWS;
+  for (int n = 0; n < HG_NETS; n++)
+    for (int l = 0; l < 5; l++) {
+      GDBnJob& j = a->j[n * 5 + l];
+      j.z = ws + p.o_z + ((int64_t)i * HG_NETS + n) * RW + (int64_t)g.rowoff[l] * W;
+      j.bn = params + p.p_bn[n] + (int64_t)l * bn_lstride + (int64_t)i * 4 * W;
+      j.eff = hg_bn_eff(p, ws, n, i) + (int64_t)l * bn_lstride;
+      j.part = reinterpret_cast<double*>(ws + p.o_bnp) + ((int64_t)n * g.ntiles + g.tileoff[l]) * W * 2;
+      j.R = g.rowoff[l + 1] - g.rowoff[l]; j.C = W;
+    }
+}
+
+void launch_heads_forward(const HGPlan& p, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t st,
+                          float momentum, float* stats_out) {
   const HGGeom& g = p.g;
   const int W = g.W, D = g.D;
   const int64_t RW = (int64_t)g.R * W;
@@ -352,7 +386,7 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
   const int64_t dw_threads = (int64_t)((g.R + GD_DW_ROWS - 1) / GD_DW_ROWS) * W;
   for (int i = 0; i < D; i++) {
     HGDwArgs d{}; d.g = g;
-    HGGemmArgs m{}; m.g = g; m.ntmax = (W + GD_BN - 1) / GD_BN; m.bn_lstride = D * 4 * W;
+    HGGemmArgs m{}; m.g = g; m.ntmax = (W + GD_BN - 1) / GD_BN; m.bn_lstride = D * 4 * W; m.z_only = p.bn_batch;
     for (int n = 0; n < HG_NETS; n++) {
       const float* conv = params + p.p_conv[n] + i * hg_conv_stride(g);
       d.src[n] = i == 0 ? ws + p.o_x0 : ws + p.o_x + ((int64_t)(i - 1) * HG_NETS + n) * RW;
@@ -366,6 +400,18 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
     }
     hipLaunchKernelGGL(hg_dw_fwd_kernel, dim3(gd_blocks(dw_threads), HG_NETS), dim3(GD_THREADS), 0, st, d);
     hipLaunchKernelGGL(hg_gemm_kernel<HG_LAYER>, dim3(mt * m.ntmax, HG_NETS), dim3(GD_THREADS), 0, st, m);
+    if (p.bn_batch) {                                      // z -> batch statistics -> x' = swish(bn(z)), per (net, level)
+      GDBnArgs<HG_NETS * 5> bj{};
+      hg_bn_jobs(p, params, ws, i, &bj);
+      bj.momentum = momentum;
+      for (int n = 0; n < HG_NETS; n++)
+        for (int l = 0; l < 5; l++) {
+          GDBnJob& j = bj.j[n * 5 + l];
+          j.io = ws + p.o_x + ((int64_t)i * HG_NETS + n) * RW + (int64_t)g.rowoff[l] * W;
+          j.stats = stats_out ? stats_out + (j.bn - params) : nullptr;
+        }
+      gd_bn_forward(bj, g.rowoff[1], W, GD_BN_SWISH, st);
+    }
   }
   HGDwArgs d{}; d.g = g;
   HGGemmArgs m{}; m.g = g; m.ntmax = 1;
@@ -392,6 +438,25 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
   const int64_t RW = (int64_t)g.R * W, TW = (int64_t)T * W;
   const int mt = (g.R + GD_BM - 1) / GD_BM, bn_lstride = D * 4 * W;
   const unsigned col_blocks = gd_blocks(TW);
+  // batch statistics: the BatchNorm tables are the forward's effective ones, and a layer's d z is complete only after its
+  // gamma / beta reduce: reduce them right behind the dw_bwd that made their partials, correct d z in place, then the products
+  auto bn_table = [&](int n, int i) { return p.bn_batch ? (const float*)hg_bn_eff(p, ws, n, i) : params + p.p_bn[n] + (int64_t)i * 4 * W; };
+  auto bn_below = [&](int i) {
+    HGReduceArgs rb{}; rb.g = g; rb.bn_lstride = bn_lstride; rb.kind0 = 3;
+    GDBnArgs<HG_NETS * 5> bj{};
+    hg_bn_jobs(p, params, ws, i, &bj);
+    for (int n = 0; n < HG_NETS; n++) {
+      rb.pgamma[n] = ws + p.o_pg[i & 1] + n * TW; rb.pbeta[n] = ws + p.o_pb[i & 1] + n * TW;
+      rb.dbn[n] = grad_params + p.p_bn[n] + (int64_t)i * 4 * W;
+      for (int l = 0; l < 5; l++) {
+        GDBnJob& j = bj.j[n * 5 + l];
+        j.io = ws + p.o_g2 + (int64_t)n * RW + (int64_t)g.rowoff[l] * W;
+        j.dbn = rb.dbn[n] + (int64_t)l * bn_lstride;
+      }
+    }
+    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)5 * 4 * W + GD_RED_E - 1) / GD_RED_E), HG_NETS, 1), dim3(GD_THREADS), 0, st, rb);
+    gd_bn_dz(bj, g.rowoff[1], W, st);
+  };
   // ---- header stage ----
   {
     HGGatherArgs ga{}; ga.g = g;
@@ -425,7 +490,7 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
     for (int n = 0; n < HG_NETS; n++) {
       db.X[n] = ws + p.o_x + ((int64_t)(D - 1) * HG_NETS + n) * RW;
       db.Zprev[n] = ws + p.o_z + ((int64_t)(D - 1) * HG_NETS + n) * RW;
-      db.bnprev[n] = params + p.p_bn[n] + (int64_t)(D - 1) * 4 * W;
+      db.bnprev[n] = bn_table(n, D - 1);
       db.out[n] = ws + p.o_g2 + (int64_t)n * RW;
       const int par = (D - 1) & 1;
       db.pgamma[n] = ws + p.o_pg[par] + n * TW; db.pbeta[n] = ws + p.o_pb[par] + n * TW; db.pbias[n] = ws + p.o_pbi[par] + n * TW;
@@ -435,6 +500,7 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
     hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(itmax * mw.ntmax, HG_SLOTS, g.nslab), dim3(GD_THREADS), 0, st, mw);
     hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(GD_THREADS), 0, st, db);
     hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)((emax + GD_RED_E - 1) / GD_RED_E), HG_SLOTS, 3), dim3(GD_THREADS), 0, st, rd);
+    if (p.bn_batch) bn_below(D - 1);
   }
   // ---- the layers, top down ----
   for (int i = D - 1; i >= 0; i--) {
@@ -455,7 +521,7 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
       const int par = i & 1, below = (i - 1) & 1;
       if (i > 0) {
         db.Zprev[n] = ws + p.o_z + ((int64_t)(i - 1) * HG_NETS + n) * RW;
-        db.bnprev[n] = params + p.p_bn[n] + (int64_t)(i - 1) * 4 * W;
+        db.bnprev[n] = bn_table(n, i - 1);
         db.out[n] = ws + p.o_g2 + (int64_t)n * RW;
         db.pgamma[n] = ws + p.o_pg[below] + n * TW; db.pbeta[n] = ws + p.o_pb[below] + n * TW; db.pbias[n] = ws + p.o_pbi[below] + n * TW;
       } else {
@@ -463,14 +529,15 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
       }
       rd.pw[n] = mw.C[n]; rd.dW[n] = gconv + 9 * W; rd.Cout[n] = W; rd.I[n] = W;
       rd.pdw[n] = ws + p.o_pdw[n]; rd.ddw[n] = gconv;
-      rd.pbias[n] = ws + p.o_pbi[par] + n * TW; rd.dbias[n] = gconv + 9 * W + (int64_t)W * W; rd.ldb[n] = W;
+      rd.pbias[n] = p.bn_batch ? nullptr : ws + p.o_pbi[par] + n * TW; rd.dbias[n] = gconv + 9 * W + (int64_t)W * W; rd.ldb[n] = W;
       rd.pgamma[n] = ws + p.o_pg[par] + n * TW; rd.pbeta[n] = ws + p.o_pb[par] + n * TW;
       rd.dbn[n] = grad_params + p.p_bn[n] + (int64_t)i * 4 * W;
     }
     hipLaunchKernelGGL(hg_gemm_kernel<HG_DATA>, dim3(mt * md.ntmax, HG_NETS), dim3(GD_THREADS), 0, st, md);
     hipLaunchKernelGGL(hg_gemm_kernel<HG_WGRAD>, dim3(md.ntmax * mw.ntmax, HG_NETS, g.nslab), dim3(GD_THREADS), 0, st, mw);
     hipLaunchKernelGGL(hg_dw_bwd_kernel, dim3(col_blocks, HG_NETS), dim3(GD_THREADS), 0, st, db);
-    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)W * W + GD_RED_E - 1) / GD_RED_E), HG_NETS, 4), dim3(GD_THREADS), 0, st, rd);
+    hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)W * W + GD_RED_E - 1) / GD_RED_E), HG_NETS, p.bn_batch ? 3 : 4), dim3(GD_THREADS), 0, st, rd);
+    if (p.bn_batch && i > 0) bn_below(i - 1);
   }
   if (grad_feats) {
     HGPtr5 f{};

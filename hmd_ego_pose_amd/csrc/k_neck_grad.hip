@@ -1,7 +1,9 @@
 // k_neck_grad.hip - training forward and backward of the BiFPN neck (all fpn_cells cells of bifpn.{r}; reference
 // efficientdet/model.py:194-266, fast-attention fusion, phi 0..5) on gfx950, fp32, as a function of (its parameters, the
-// three backbone taps P3 / P4 / P5).  The function is the inference function: BatchNorm uses the RUNNING statistics in
-// forward and backward; gamma and beta get gradients, the statistics get zero.
+// three backbone taps P3 / P4 / P5).  By default the function is the inference function: BatchNorm uses the RUNNING statistics in
+// forward and backward; gamma and beta get gradients, the statistics get zero.  HEP_BN_BATCH: every BatchNorm (laterals and nodes)
+// normalises with the statistics of its map's rows (the shared passes of grad_dev.h): gemm<FWD> stores z only, then statistics /
+// finish / apply; in the backward the gamma / beta reduce and the d z correction follow the gather, ahead of the products.
 //
 // Plain layouts, as k_head_grad.hip has (the GEMM tile, the 3 x 3 window and the reduce are grad_dev.h's): every map is
 // rows [B * s * s][C], channels contiguous, one buffer per map.  The flat parameter buffer starts every cell with 19 fusion scalars, so no tensor behind them is 16-byte aligned:
@@ -182,6 +184,7 @@ struct NGGemmArgs {
   const float* A; const float* Bm; float* C; float* C2;
   const float* bias; const float* bn;          // FWD: [J]; gamma, beta, mean, var [4][J]
   int I, J, K, lda, ldb, ldc, ntn, slab_rows;
+  int z_only;                                  // FWD with batch statistics: store z, the BatchNorm passes of grad_dev.h make y
 };
 // C[i][j] = sum_k A(i,k) B(k,j), 64 x 64 per workgroup, wave w owns rows 16w..16w+15 and four 16-column accumulators.
 //   FWD     A = u rows (k contiguous), B = Wp [J][K] (k contiguous); z = C + bias -> C, bn(z) -> C2
@@ -203,7 +206,7 @@ template <int MODE> __global__ __launch_bounds__(GD_THREADS) void ng_gemm_kernel
     if (MODE == NG_FWD) {
       const float z = v + a.bias[n];
       a.C[(int64_t)m * a.ldc + n] = z;
-      a.C2[(int64_t)m * a.ldc + n] = gd_bn_apply(q, z);
+      if (!a.z_only) a.C2[(int64_t)m * a.ldc + n] = gd_bn_apply(q, z);
     } else if (MODE == NG_DATA) {
       a.C[(int64_t)m * a.ldc + n] = v;
     } else {
@@ -363,10 +366,12 @@ __global__ __launch_bounds__(GD_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
 static inline int64_t ng_node_stride(int W) { return (int64_t)9 * W + (int64_t)W * W + W + 4 * W; }
 static inline int64_t ng_lat_stride(int W, int K) { return (int64_t)W * K + W + 4 * W; }
 
-int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why) {
+int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why, int bn_mode) {
   if (phi == 6 || phi == 7) { *why = "neck: phi 6 and 7 fuse by plain sums at width 384 (no fast attention): not supported, phi must be in 0..5"; return HEP_ERR_UNSUPPORTED; }
   if (phi < 0 || phi > 5) { *why = "neck: phi must be in 0..5 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
+  if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "neck: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
   const int W = kNeckWidth[phi];
+  p->bn_batch = bn_mode == HEP_BN_BATCH;
   p->phi = phi; p->W = W; p->cells = kNeckCells[phi];
   for (int t = 0; t < 3; t++) p->tapc[t] = kNeckTaps[phi][t];
   int64_t o = 0;
@@ -382,6 +387,7 @@ int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why) {
   if (batch < 1) { *why = "neck: batch must be at least 1"; return HEP_ERR_UNSUPPORTED; }
   if ((int64_t)batch * (size / 8) * (size / 8) > (1 << 22)) { *why = "neck: batch * pixels exceeds 4 Mi rows"; return HEP_ERR_UNSUPPORTED; }
   p->B = batch;
+  if (p->bn_batch && batch * (size / 128) * (size / 128) < 2) { *why = "neck: batch statistics need at least 2 rows per BatchNorm (batch * P7 pixels)"; return HEP_ERR_UNSUPPORTED; }
   for (int l = 0; l < 5; l++) {
     p->s[l] = size / (8 << l); p->R[l] = batch * p->s[l] * p->s[l];
     p->ntiles[l] = (p->R[l] + NG_TILE_ROWS - 1) / NG_TILE_ROWS;
@@ -411,6 +417,11 @@ int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why) {
   p->o_pdw = take((int64_t)p->ntiles[0] * W * 9);
   for (int k = 0; k < 3; k++) { p->o_pb[k] = take((int64_t)p->ntiles[0] * W); p->o_pf[k] = take((int64_t)2 * p->ntiles[0] * W); }
   for (int i = 0; i < NG_LATERALS; i++) p->o_dtap[i] = take((int64_t)p->R[kLatTap[i]] * p->tapc[kLatTap[i]]);
+  p->o_bne = p->o_bnp = 0;
+  if (p->bn_batch) {                                       // an effective table per BatchNorm (laterals, then cell by cell); [tile][W][2] doubles
+    p->o_bne = take((int64_t)(NG_LATERALS + p->cells * NG_NODES) * 4 * W);
+    p->o_bnp = take((int64_t)p->ntiles[0] * W * 4);
+  }
   p->ws_floats = w;
   return 0;
 }
@@ -479,18 +490,49 @@ void ng_collect_pool(float* g, uint8_t* am, NGGatherArgs* ga) {
   c.g = g; c.fw = nullptr; c.am = am; c.n = 0; c.idx = 0; c.mode = NG_POOL;
 }
 
-// BatchNorm partials [tile][W] -> gamma, beta, zeros for the statistics, and the conv bias
+// BatchNorm partials [tile][W] -> gamma, beta, zeros for the statistics, and the conv bias (batch statistics: analytically
+// zero, written as zero)
 void ng_bn_jobs(const NGPlan& p, float* ws, int level, float* dbias, float* dbn, GDReduceArgs<NG_RED_JOBS>* rd, int at) {
   const int W = p.W, T = p.ntiles[level];
   rd->j[at + 0] = GDRedJob{ws + p.o_pb[0], dbn, W, W, T};
   rd->j[at + 1] = GDRedJob{ws + p.o_pb[1], dbn + W, W, W, T};
   rd->j[at + 2] = GDRedJob{nullptr, dbn + 2 * W, 2 * W, 0, 0};
-  rd->j[at + 3] = GDRedJob{ws + p.o_pb[2], dbias, W, W, T};
+  rd->j[at + 3] = p.bn_batch ? GDRedJob{nullptr, dbias, W, 0, 0} : GDRedJob{ws + p.o_pb[2], dbias, W, W, T};
+}
+
+// Batch statistics.  BatchNorm k (laterals 0..5, then 6 + 8 cell + node) as a job of grad_dev.h's kernels: its effective table,
+// and where its gamma, beta, mean, var lie in the flat parameter layout (table_at).
+inline float* ng_bn_eff(const NGPlan& p, float* ws, int k) { return ws + p.o_bne + (int64_t)k * 4 * p.W; }
+GDBnArgs<1> ng_bn_job(const NGPlan& p, float* ws, int k, int level, const float* z, const float* bn) {
+  GDBnArgs<1> a{};
+  a.tile_rows = NG_TILE_ROWS;
+  a.j[0].z = z; a.j[0].bn = bn; a.j[0].eff = ng_bn_eff(p, ws, k);
+  a.j[0].part = reinterpret_cast<double*>(ws + p.o_bnp);
+  a.j[0].R = p.R[level]; a.j[0].C = p.W;
+  return a;
+}
+// what follows a map's gather in the backward: its gamma / beta reduce first, then d z (ws + o_dz) corrected in place - before
+// any product reads it; the stage's own reduce then has the weight jobs only
+void ng_bn_backward(const NGPlan& p, float* ws, int k, int level, const float* z, float* dbias, float* dbn, hipStream_t st) {
+  GDReduceArgs<NG_RED_JOBS> rd{};
+  ng_bn_jobs(p, ws, level, dbias, dbn, &rd, 2);
+  hipLaunchKernelGGL(gd_reduce_kernel<NG_RED_JOBS>, dim3((unsigned)((2 * p.W + GD_RED_E - 1) / GD_RED_E), NG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
+  GDBnArgs<1> a = ng_bn_job(p, ws, k, level, z, nullptr);
+  a.j[0].io = ws + p.o_dz; a.j[0].dbn = dbn;
+  gd_bn_dz(a, p.R[level], p.W, st);
 }
 }  // namespace
 
-void launch_neck_forward(const NGPlan& p, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t st) {
+void launch_neck_forward(const NGPlan& p, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t st,
+                         float momentum, float* stats_out) {
   const int W = p.W, B = p.B;
+  // batch statistics: z (what the GEMM left) -> statistics -> the effective table and the running-statistics update -> y
+  auto bn_forward = [&](int k, int level, const NGGemmArgs& m, int64_t table_at) {
+    GDBnArgs<1> a = ng_bn_job(p, ws, k, level, m.C, m.bn);
+    a.momentum = momentum;
+    a.j[0].io = m.C2; a.j[0].stats = stats_out ? stats_out + table_at : nullptr;
+    gd_bn_forward(a, p.R[level], W, GD_BN_PLAIN, st);
+  };
   NGPackArgs pk{}; pk.cells = p.cells;
   for (int r = 0; r < p.cells; r++) { pk.src[r] = p.p_cell[r]; pk.dst[r] = p.o_pp[r]; }
   pk.src[p.cells] = p.nparams;
@@ -502,7 +544,9 @@ void launch_neck_forward(const NGPlan& p, const float* params, const float* cons
     const float* lp = ng_lat_params(p, ws, i);
     NGGemmArgs m{}; m.A = ws + p.o_tap[t]; m.Bm = lp; m.bias = lp + (int64_t)W * K; m.bn = lp + (int64_t)W * K + W;
     m.C = ws + p.o_lz[i]; m.C2 = ws + p.o_ly[i]; m.I = p.R[t]; m.J = W; m.K = K; m.lda = K; m.ldb = K; m.ldc = W; m.ntn = (W + GD_BN - 1) / GD_BN;
+    m.z_only = p.bn_batch;
     ng_gemm(NG_FWD, m, 1, st);
+    if (p.bn_batch) bn_forward(i, t, m, p.p_lat[i] + (int64_t)W * K + W);
   }
   hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(gd_blocks((int64_t)p.R[3] * W)), dim3(GD_THREADS), 0, st, B, p.s[2], W, (const float*)(ws + p.o_ly[3]), ws + p.o_p6, ng_bytes(ws, p.o_am6));
   hipLaunchKernelGGL(ng_pool_fwd_kernel, dim3(gd_blocks((int64_t)p.R[4] * W)), dim3(GD_THREADS), 0, st, B, p.s[3], W, (const float*)(ws + p.o_p6), ws + p.o_p7, ng_bytes(ws, p.o_am7));
@@ -519,7 +563,9 @@ void launch_neck_forward(const NGPlan& p, const float* params, const float* cons
                          (const float*)(ws + p.o_x), np, ws + p.o_u[r][j]);
       NGGemmArgs m{}; m.A = ws + p.o_u[r][j]; m.Bm = np + 9 * W; m.bias = np + 9 * W + (int64_t)W * W; m.bn = m.bias + W;
       m.C = ws + p.o_z[r][j]; m.C2 = ws + p.o_y[r][j]; m.I = R; m.J = W; m.K = W; m.lda = W; m.ldb = W; m.ldc = W; m.ntn = (W + GD_BN - 1) / GD_BN;
+      m.z_only = p.bn_batch;
       ng_gemm(NG_FWD, m, 1, st);
+      if (p.bn_batch) bn_forward(NG_LATERALS + r * NG_NODES + j, l, m, p.p_cell[r] + NG_FUSION_FLOATS + j * ng_node_stride(W) + 9 * W + (int64_t)W * W + W);
     }
   for (int l = 0; l < 5; l++) {
     NGRows3 rows{}; rows.p[0] = ws + p.o_y[p.cells - 1][kOutNode[l]]; rows.n = 1;
@@ -547,8 +593,10 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
       if (out_level >= 0 && r == p.cells - 1) ga.cot = grad_feats[out_level];
       ng_collect(p, ws, r, 8 + j, &ga);
       if (out_level >= 0 && r + 1 < p.cells) ng_collect(p, ws, r + 1, out_level, &ga);
-      ga.Z = ws + p.o_z[r][j]; ga.bn = np + 9 * W + (int64_t)W * W + W; ga.out = ws + p.o_dz;
+      const int bk = NG_LATERALS + r * NG_NODES + j;
+      ga.Z = ws + p.o_z[r][j]; ga.bn = p.bn_batch ? ng_bn_eff(p, ws, bk) : np + 9 * W + (int64_t)W * W + W; ga.out = ws + p.o_dz;
       gather(ga, l);
+      if (p.bn_batch) ng_bn_backward(p, ws, bk, l, ga.Z, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, st);
       NGGemmArgs md{}; md.A = ws + p.o_dz; md.Bm = np + 9 * W; md.C = ws + p.o_du; md.I = R; md.J = W; md.K = W; md.lda = W; md.ldb = W; md.ldc = W; md.ntn = ntn;
       ng_gemm(NG_DATA, md, 1, st);
       NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_u[r][j]; mw.C = ws + p.o_pw; mw.I = W; mw.J = W; mw.K = R; mw.lda = W; mw.ldb = W; mw.ntn = ntn;
@@ -562,7 +610,7 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
       GDReduceArgs<NG_RED_JOBS> rd{};
       rd.j[0] = GDRedJob{ws + p.o_pw, gn + 9 * W, (int64_t)W * W, (int64_t)W * W, p.nslab[l]};
       rd.j[1] = GDRedJob{ws + p.o_pdw, gn, (int64_t)W * 9, (int64_t)W * 9, T};
-      ng_bn_jobs(p, ws, l, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, &rd, 2);
+      if (!p.bn_batch) ng_bn_jobs(p, ws, l, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, &rd, 2);
       hipLaunchKernelGGL(gd_reduce_kernel<NG_RED_JOBS>, dim3((unsigned)(((int64_t)W * W + GD_RED_E - 1) / GD_RED_E), NG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
       NGFusionArgs fa{}; fa.n = kNodeNsrc[j]; fa.count = gd_blocks((int64_t)T * W); fa.p = ws + p.o_pp[r] + kNodeFw[j]; fa.dp = gcell + kNodeFw[j];
       for (int i = 0; i < 3; i++) fa.pf[i] = reinterpret_cast<const double*>(ws + p.o_pf[i]);
@@ -581,8 +629,9 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
     NGGatherArgs ga{};
     if (kLatCode[i] >= 0) ng_collect(p, ws, 0, kLatCode[i], &ga);
     else ng_collect_pool(ws + p.o_g6, ng_bytes(ws, p.o_am6), &ga);
-    ga.Z = ws + p.o_lz[i]; ga.bn = lp + (int64_t)W * K + W; ga.out = ws + p.o_dz;
+    ga.Z = ws + p.o_lz[i]; ga.bn = p.bn_batch ? ng_bn_eff(p, ws, i) : lp + (int64_t)W * K + W; ga.out = ws + p.o_dz;
     gather(ga, t);
+    if (p.bn_batch) ng_bn_backward(p, ws, i, t, ga.Z, gl + (int64_t)W * K, gl + (int64_t)W * K + W, st);
     NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_tap[t]; mw.C = ws + p.o_pw; mw.I = W; mw.J = K; mw.K = R; mw.lda = W; mw.ldb = K;
     mw.ntn = (K + GD_BN - 1) / GD_BN; mw.slab_rows = p.slab_rows[t];
     ng_gemm(NG_WGRAD, mw, p.nslab[t], st);
@@ -594,7 +643,7 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
     GDReduceArgs<NG_RED_JOBS> rd{};
     rd.j[0] = GDRedJob{ws + p.o_pw, gl, (int64_t)W * K, (int64_t)W * K, p.nslab[t]};
     rd.j[1] = GDRedJob{nullptr, nullptr, 0, 0, 0};
-    ng_bn_jobs(p, ws, t, gl + (int64_t)W * K, gl + (int64_t)W * K + W, &rd, 2);
+    if (!p.bn_batch) ng_bn_jobs(p, ws, t, gl + (int64_t)W * K, gl + (int64_t)W * K + W, &rd, 2);
     hipLaunchKernelGGL(gd_reduce_kernel<NG_RED_JOBS>, dim3((unsigned)(((int64_t)W * K + GD_RED_E - 1) / GD_RED_E), NG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
   }
   if (grad_taps)

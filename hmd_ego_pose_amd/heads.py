@@ -10,11 +10,17 @@ BiFPN maps (``feats``, the first value ``HMDEgoPose.forward`` returns), then per
 
 and finally ``export_to(model)`` copies the fitted heads back into the ``HMDEgoPose`` drop-in.
 
-BatchNorm: RUNNING statistics in every mode (``train()`` and ``eval()`` compute the same function), in forward and
-backward - frozen-statistics fine-tuning, the reference's ``freeze_bn`` (backbone.py:99).  That is the gradient of the
-function the inference path computes, so "train here, serve here" is consistent: ``gamma`` and ``beta`` get gradients,
-``running_mean`` / ``running_var`` never change.  Batch-statistics BatchNorm (``model.train()`` in the reference's
-train.py:162) is out of scope, and so is bf16 training (the BiFPN and the backbone in front of the heads are trainable too:
+BatchNorm, by default (``batch_norm="running"``): RUNNING statistics in every mode (``train()`` and ``eval()`` compute the
+same function), in forward and backward - frozen-statistics fine-tuning, the reference's ``freeze_bn`` (backbone.py:99).  That
+is the gradient of the function the inference path computes, so "train here, serve here" is consistent: ``gamma`` and
+``beta`` get gradients, ``running_mean`` / ``running_var`` never change.
+``batch_norm="batch"`` is ``nn.BatchNorm2d(momentum=0.01, eps=1e-3)`` as the reference's train.py:162 (``model.train()``)
+runs it: in ``train()`` mode every ``bn_list.{level}.{i}`` normalises with the mean and biased variance of its level's
+``B * s * s`` pixels, the backward is that function's, and each forward (under ``torch.no_grad()`` or not) moves
+``running_mean`` / ``running_var`` in place and adds one to every ``num_batches_tracked``; in ``eval()`` mode it is the
+running-statistics function, bit for bit.  A level with fewer than 2 rows (size 128 with batch 1) raises ``ValueError``, as
+torch does.  ``export_to`` copies the buffers, so the fitted statistics reach the inference session.  Out of scope: sync-BN
+across GPUs and bf16 training (the BiFPN and the backbone in front of the heads are trainable too:
 ``hmd_ego_pose_amd.neck.TrainableNeck``, ``hmd_ego_pose_amd.backbone.TrainableBackbone``).
 """
 from __future__ import annotations
@@ -40,33 +46,35 @@ def flat_keys(compound_coef: int, num_classes: int = 1) -> List[Tuple[str, tuple
     return _trainable.without_counters(head_spec(compound_coef, num_classes))
 
 
-def heads_forward(flat: torch.Tensor, feats: Sequence[torch.Tensor], compound_coef: int, num_classes: int, size: int):
-    """hep_heads_forward_device on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order),
+def heads_forward(flat: torch.Tensor, feats: Sequence[torch.Tensor], compound_coef: int, num_classes: int, size: int,
+                  bn_mode: int = _trainable.BN_RUNNING, momentum: float = _trainable.BN_MOMENTUM, stats: torch.Tensor = None):
+    """hep_heads_forward_device_bn on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order),
     ``feats``: five contiguous float32 NCHW maps.  Returns (outs, workspace): the five [B, N, K] outputs and the workspace
-    that hep_heads_backward_device needs.  No host synchronisation."""
+    that hep_heads_backward_device_bn needs (same ``bn_mode``).  ``stats`` (batch statistics): a buffer like ``flat`` whose
+    running_mean / running_var elements receive the updated statistics.  No host synchronisation."""
     dev, B = flat.device, int(feats[0].shape[0])
     N = NUM_ANCHORS * sum(s * s for s in level_sizes(size))
     l = _capi.lib()
-    nbytes = _capi.check(l.hep_heads_workspace_bytes(compound_coef, num_classes, size, B))
+    nbytes = _capi.check(l.hep_heads_workspace_bytes_bn(compound_coef, num_classes, size, B, bn_mode))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     outs = tuple(torch.empty((B, N, k), dtype=torch.float32, device=dev) for k in (4, num_classes, 3, 3, 63))
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(l.hep_heads_forward_device(flat.data_ptr(), _ptrs(feats), compound_coef, num_classes, size, B, _ptrs(outs),
-                                           ws.data_ptr(), nbytes, stream))
+    _capi.check(l.hep_heads_forward_device_bn(flat.data_ptr(), _ptrs(feats), compound_coef, num_classes, size, B, _ptrs(outs),
+                                              ws.data_ptr(), nbytes, bn_mode, momentum, None if stats is None else stats.data_ptr(), stream))
     return outs, ws
 
 
 def heads_backward(flat: torch.Tensor, grad_outs: Sequence[torch.Tensor], ws: torch.Tensor, compound_coef: int, num_classes: int,
-                   size: int, feat_shapes=None):
-    """hep_heads_backward_device on the current stream, after ``heads_forward`` with the same ``flat`` and ``ws``.
+                   size: int, feat_shapes=None, bn_mode: int = _trainable.BN_RUNNING):
+    """hep_heads_backward_device_bn on the current stream, after ``heads_forward`` with the same ``flat``, ``ws`` and ``bn_mode``.
     Returns (grad_flat, grad_feats): the parameter gradients in the layout of ``flat`` (running statistics zero) and the
     five map gradients (None when ``feat_shapes`` is None: the ABI then gets NULL and skips them)."""
     dev, B = flat.device, int(grad_outs[0].shape[0])
     g_flat = torch.empty_like(flat)
     g_feats = None if feat_shapes is None else tuple(torch.empty(tuple(s), dtype=torch.float32, device=dev) for s in feat_shapes)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _capi.check(_capi.lib().hep_heads_backward_device(flat.data_ptr(), _ptrs(grad_outs), compound_coef, num_classes, size, B,
-                                                      g_flat.data_ptr(), _ptrs(g_feats), ws.data_ptr(), ws.numel(), stream))
+    _capi.check(_capi.lib().hep_heads_backward_device_bn(flat.data_ptr(), _ptrs(grad_outs), compound_coef, num_classes, size, B,
+                                                         g_flat.data_ptr(), _ptrs(g_feats), ws.data_ptr(), ws.numel(), bn_mode, stream))
     return g_flat, g_feats
 
 
@@ -74,23 +82,23 @@ class _Heads(torch.autograd.Function):
     """The two ABI calls as one differentiable function of (flat parameters, five maps)."""
 
     @staticmethod
-    def forward(ctx, flat, phi, num_classes, size, *feats):
-        outs, ws = heads_forward(flat, feats, phi, num_classes, size)
+    def forward(ctx, flat, phi, num_classes, size, bn_mode, stats, *feats):
+        outs, ws = heads_forward(flat, feats, phi, num_classes, size, bn_mode, stats=stats)
         ctx.save_for_backward(flat, ws)
-        ctx.cfg = (phi, num_classes, size, [tuple(f.shape) for f in feats])
+        ctx.cfg = (phi, num_classes, size, [tuple(f.shape) for f in feats], bn_mode)
         return outs
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grad_outs):
         flat, ws = ctx.saved_tensors
-        phi, num_classes, size, shapes = ctx.cfg
+        phi, num_classes, size, shapes, bn_mode = ctx.cfg
         N = NUM_ANCHORS * sum(s * s for s in level_sizes(size))
         B = shapes[0][0]
         gs = _trainable.cotangents(grad_outs, [(B, N, k) for k in (4, num_classes, 3, 3, 63)], flat.device)
-        want_feats = any(ctx.needs_input_grad[4:])
-        g_flat, g_feats = heads_backward(flat, gs, ws, phi, num_classes, size, shapes if want_feats else None)
-        return (g_flat if ctx.needs_input_grad[0] else None, None, None, None, *(g_feats if want_feats else (None,) * 5))
+        want_feats = any(ctx.needs_input_grad[6:])
+        g_flat, g_feats = heads_backward(flat, gs, ws, phi, num_classes, size, shapes if want_feats else None, bn_mode)
+        return (g_flat if ctx.needs_input_grad[0] else None, None, None, None, None, None, *(g_feats if want_feats else (None,) * 5))
 
 
 class TrainableHeads(_trainable.TrainablePart):
@@ -99,13 +107,15 @@ class TrainableHeads(_trainable.TrainablePart):
     ``load_state_dict(model.state_dict(), strict=False)`` fills it.  ``forward(feats)`` takes the 5-tuple of BiFPN maps
     that ``HMDEgoPose.forward`` returns first and gives (regression, classification, rotation, translation_raw, hand) with
     a ``grad_fn``: HIP forward and HIP backward, gradients to the parameters and, where they require grad, to the maps.
-    Runs on a ROCm device only (no CPU fallback).  BatchNorm uses the running statistics in EVERY mode, ``train()``
-    included (see the module docstring); they receive no gradient and never change."""
+    Runs on a ROCm device only (no CPU fallback).  ``batch_norm="running"`` (the default): BatchNorm uses the running
+    statistics in EVERY mode, ``train()`` included; they receive no gradient and never change.  ``batch_norm="batch"``:
+    batch statistics in ``train()`` mode, the running statistics move (see the module docstring)."""
 
     NOUN, spec = "head", staticmethod(head_spec)
 
-    def __init__(self, compound_coef: int = 0, num_classes: int = 1):
+    def __init__(self, compound_coef: int = 0, num_classes: int = 1, batch_norm: str = "running"):
         super().__init__()
+        self._set_batch_norm(batch_norm)
         self.compound_coef = int(compound_coef)
         self.num_classes = int(num_classes)
         self.arch = get_arch(self.compound_coef)
@@ -138,7 +148,17 @@ class TrainableHeads(_trainable.TrainablePart):
         flat = self.flat_parameters()
         if flat.device != feats[0].device:
             raise ValueError("the heads and the maps live on different devices: move the module with .to(device)")
-        return _Heads.apply(flat, self.compound_coef, self.num_classes, size, *(f.contiguous() for f in feats))
+        bn_mode, stats = self._bn_mode(), None
+        if bn_mode == _trainable.BN_BATCH:
+            rows = int(feats[4].shape[0]) * int(feats[4].shape[2]) ** 2
+            if rows < 2:
+                raise ValueError(f"batch statistics need more than 1 value per channel: the top level has {rows} row (batch "
+                                 f"{int(feats[4].shape[0])} at size {size})")
+            stats = torch.empty_like(flat, requires_grad=False)
+        outs = _Heads.apply(flat, self.compound_coef, self.num_classes, size, bn_mode, stats, *(f.contiguous() for f in feats))
+        if stats is not None:
+            self._store_statistics(stats)
+        return outs
 
 
 def param_layout(compound_coef: int, num_classes: int = 1):

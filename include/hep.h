@@ -235,8 +235,8 @@ int hep_losses_backward_device(const float* gt_classification, const float* clas
  * hep_losses_device / hep_losses_backward_device.  Stateless: plain pointers and sizes, asynchronous on `stream`, no
  * allocation, no host synchronisation, argument checks before any HIP call, bit-reproducible (no float atomics).
  * BatchNorm uses its RUNNING statistics in forward and backward (the function the inference path computes; the
- * reference's freeze_bn): gamma and beta get gradients, the statistics never change.  Batch-statistics BatchNorm is out
- * of scope.
+ * reference's freeze_bn): gamma and beta get gradients, the statistics never change.  Batch-statistics BatchNorm (the
+ * reference's model.train()) is the hep_heads_*_bn group below with HEP_BN_BATCH.
  *
  * params: ONE flat fp32 device buffer (16-byte aligned) holding the head tensors in the reference's shapes and
  * state_dict order (regressor, classifier, rotation_net, translation_net, hand_net; per net conv_list.{i}.{depthwise
@@ -258,11 +258,32 @@ int hep_heads_forward_device(const float* params, const float* const feats[5], i
 int hep_heads_backward_device(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
                               float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same three calls with a BatchNorm mode.  HEP_BN_RUNNING: exactly the calls above (they are this one with that mode).
+ * HEP_BN_BATCH: F.batch_norm(training = True) - what the reference's train.py computes under model.train().  Every BatchNorm
+ * normalises with the mean and the biased variance of the rows it sees (one level's batch * s_l * s_l pixels: bn_list.{level}.{i}
+ * is per level, the convs are shared), eps 1e-3; the backward is that function's:
+ *   d beta = sum d a,  d gamma = sum d a x^,  d z = gamma rstd (d a - d beta / N - x^ d gamma / N);
+ * the conv bias in front of a BatchNorm gets exactly zero (its gradient is analytically zero), the running statistics too.
+ * stats_out (forward): a buffer in the layout of params, or NULL.  Its running_mean / running_var elements receive
+ *   (1 - momentum) running + momentum batch   (the variance unbiased, N / (N - 1));
+ * no other element is touched and params stays const; the caller owns num_batches_tracked.  The reference uses momentum 0.01.
+ * A BatchNorm with N < 2 rows (size 128, batch 1: a 1 x 1 top level) is HEP_ERR_UNSUPPORTED, as torch raises there.
+ * hep_heads_workspace_bytes_bn: the workspace of that mode (batch >= running); forward and backward take the same mode. */
+#define HEP_BN_RUNNING 0
+#define HEP_BN_BATCH 1
+int64_t hep_heads_workspace_bytes_bn(int phi, int num_classes, int size, int batch, int bn_mode);
+int hep_heads_forward_device_bn(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
+                                float* const outs[5], void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out,
+                                void* stream);
+int hep_heads_backward_device_bn(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
+                                 float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, int bn_mode,
+                                 void* stream);
+
 /* The BiFPN neck (every cell of bifpn.{r}; reference efficientdet/model.py:194-266) as a TRAINABLE function of its parameters
  * and the three backbone taps P3 / P4 / P5: forward and backward in HIP (csrc/k_neck_grad.hip).  Same conventions as the
  * hep_heads_* group: stateless, asynchronous on `stream`, no allocation, no host synchronisation, argument checks before any
  * HIP call, bit-reproducible (no float atomics), BatchNorm with its RUNNING statistics in forward and backward (gamma and beta
- * get gradients, the statistics get exactly zero).  Fast-attention fusion w = relu(p) / (sum relu(p) + 1e-4); relu'(p) = 0 for
+ * get gradients, the statistics get exactly zero; batch statistics: hep_neck_*_bn below).  Fast-attention fusion w = relu(p) / (sum relu(p) + 1e-4); relu'(p) = 0 for
  * p <= 0.  Max-pool gradients go to the FIRST maximal element in row-major order of the zero-padded 3 x 3 window (padding:
  * one column right, one row below).  The taps are inputs; grad_taps gives their gradient (what hep_backbone_backward_device
  * takes).
@@ -290,6 +311,15 @@ int hep_neck_forward_device(const float* params, const float* const taps[3], int
                             void* workspace, size_t workspace_bytes, void* stream);
 int hep_neck_backward_device(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
                              float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream);
+/* With a BatchNorm mode, as hep_heads_*_bn: HEP_BN_RUNNING is exactly the calls above; HEP_BN_BATCH normalises every BatchNorm
+ * (the six laterals and every node) with the statistics of its map's batch * s * s rows, the backward is that function's
+ * (every conv bias feeds a BatchNorm: its gradient is written as exactly zero), stats_out (layout of params, or NULL) receives the
+ * updated running_mean / running_var.  batch * (size / 128)^2 < 2 (P7 of one 128 image): HEP_ERR_UNSUPPORTED. */
+int64_t hep_neck_workspace_bytes_bn(int phi, int size, int batch, int bn_mode);
+int hep_neck_forward_device_bn(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                               void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out, void* stream);
+int hep_neck_backward_device_bn(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
+                                float* const grad_taps[3], void* workspace, size_t workspace_bytes, int bn_mode, void* stream);
 int hep_neck_stage_count(int phi);
 int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes);
 
@@ -298,7 +328,8 @@ int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, 
  * efficientdet/model.py:436-458) as a TRAINABLE function image [batch][3][size][size] -> (P3, P4, P5): forward and backward in
  * HIP (csrc/k_backbone_grad.hip).  Same conventions as the hep_neck_* group: stateless, asynchronous on `stream`, no
  * allocation, no host synchronisation, argument checks before any HIP call, bit-reproducible (no float atomics), BatchNorm
- * with its RUNNING statistics in forward and backward (gamma and beta get gradients, the statistics get exactly zero).
+ * with its RUNNING statistics in forward and backward (gamma and beta get gradients, the statistics get exactly zero; batch
+ * statistics: hep_backbone_*_bn below).
  *
  * Drop-connect (efficientnet/utils.py:85-94) enters as data.  branch_scale: fp32 [blocks][batch] on the device, or NULL for
  * all ones; a block that adds its input computes y = bn2(project) * branch_scale[block][image] + input, the other blocks
@@ -327,6 +358,16 @@ int hep_backbone_forward_device(const float* params, const float* image, const f
                                 float* const taps[3], void* workspace, size_t workspace_bytes, void* stream);
 int hep_backbone_backward_device(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
                                  float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, void* stream);
+/* With a BatchNorm mode, as hep_heads_*_bn: HEP_BN_RUNNING is exactly the calls above; HEP_BN_BATCH normalises the stem's
+ * BatchNorm and every block's bn0 / bn1 / bn2 with the statistics of its map's batch * s * s rows (the squeeze-excite, the
+ * branch scale and the skip add stay behind bn2 as they are), the backward is that function's, stats_out (layout of params, or
+ * NULL) receives the updated running_mean / running_var.  The smallest map has batch * 16 rows, so no size is refused. */
+int64_t hep_backbone_workspace_bytes_bn(int phi, int size, int batch, int bn_mode);
+int hep_backbone_forward_device_bn(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch,
+                                   float* const taps[3], void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out,
+                                   void* stream);
+int hep_backbone_backward_device_bn(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
+                                    float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, int bn_mode, void* stream);
 int hep_backbone_stage_count(int phi);
 int hep_backbone_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes);
 
