@@ -83,6 +83,7 @@ SYMBOLS = {
     "hep_kernel_count": (c_int, [_P, c_int]),
     "hep_kernel_info": (c_int, [_P, c_int, c_int, POINTER(c_char_p), POINTER(c_double), POINTER(c_double)]),
     "hep_kernel_symbol": (c_int, [_P, c_int, POINTER(c_char_p)]),
+    "hep_plan_launch_list": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_uint, c_void_p, c_size_t, POINTER(c_size_t)]),
     "hep_fp8_scale": (c_int, [_P, c_int, POINTER(c_float)]),
     "hep_calibrate_fp8": (c_int, [_P, _FP, c_int]),
     "hep_profile": (c_int, [_P, c_int, c_int, POINTER(c_float), _FP]),

@@ -12,7 +12,7 @@
 #include <memory>
 
 #include "hep.h"
-#include "hep_host.h"
+#include "hep_plan.h"
 
 using namespace hep;
 
@@ -40,6 +40,7 @@ static int hep_caught() noexcept {
 namespace hep {
 
 Session::~Session() {
+  if (!realised) return;            // planned on the host only (hep_plan_launch_list): no device object exists and no HIP call is made
   for (auto& g : graphs) for (hipGraphExec_t ge : g.second) hipGraphExecDestroy(ge);
   for (auto& lo : lane_ops) for (Op& o : lo) {
     if (o.kind == OP_SEP) { hipFree((void*)o.sep.segs); hipFree((void*)o.sep.tile_seg); }
@@ -222,6 +223,15 @@ int hep_device_count(void) try {
   return n;
 } HEP_CATCH_INT
 
+// knobs of the environment and the lanes they ask for: slices of the batch that run as parallel graph branches (HEP_LANES overrides)
+static void session_lanes(Session* s) {
+  s->knobs = read_knobs();
+  int lanes = s->knobs.lanes;   // 1: measured on MI355X at bs16, 2/4/8 lanes are 4 % / 75 % / 150 % SLOWER (kernels contend instead of overlapping)
+  lanes = std::max(1, std::min(lanes, std::min(s->max_batch, 16)));
+  s->lane_batch = (s->max_batch + lanes - 1) / lanes;
+  s->lanes = (s->max_batch + s->lane_batch - 1) / s->lane_batch;
+}
+
 int hep_create_from_memory(const void* pack, size_t pack_bytes, int phi, int size, int max_batch, int dtype, int device,
                            unsigned flags, hep_handle** out) try {
   if (!out) return fail(HEP_ERR_INVALID, "out is NULL");
@@ -248,13 +258,7 @@ int hep_create_from_memory(const void* pack, size_t pack_bytes, int phi, int siz
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(HEP_ERR_DEVICE, std::string("device is ") + prop.gcnArchName + ", libhep is built for gfx950 (MI355X) only");
   s.size = size; s.max_batch = max_batch; s.dtype = dtype; s.device = device; s.flags = flags;
-  {   // lanes: slices of the batch that run as parallel graph branches (HEP_LANES overrides)
-    s.knobs = read_knobs();
-    int lanes = s.knobs.lanes;   // 1: measured on MI355X at bs16, 2/4/8 lanes are 4 % / 75 % / 150 % SLOWER (kernels contend instead of overlapping)
-    lanes = std::max(1, std::min(lanes, std::min(max_batch, 16)));
-    s.lane_batch = (max_batch + lanes - 1) / lanes;
-    s.lanes = (max_batch + s.lane_batch - 1) / s.lane_batch;
-  }
+  session_lanes(&s);
   int rc = build_session(&s, pk, &err);
   if (rc != 0) return fail(rc, err);
   if (dtype == HEP_FP8) if (int rc2 = calibrate_fp8(s)) return rc2;
@@ -1060,12 +1064,10 @@ int hep_calibrate_fp8(hep_handle* h, const float* frames_nchw_device, int batch)
   return calibrate_fp8(s, frames_nchw_device, batch);
 } HEP_CATCH_INT
 
-int hep_kernel_symbol(const hep_handle* h, int i, const char** symbol) try {
-  if (!h || !symbol || i < 0 || i >= (int)h->s.ops.size()) return fail(HEP_ERR_INVALID, "bad kernel index");
-  static thread_local std::string buf;
-  const Op& o = h->s.ops[i];
-  const char* t = h->s.dtype ? "true" : "false";
-  const int prec = o.kind == OP_PW ? (o.pw.fp8 ? 2 : (h->s.dtype ? 1 : 0)) : 0;
+// the device function (as rocprofv3 --kernel-trace names it) that launch_op runs for `o` in session `s`: host arithmetic only
+static std::string kernel_symbol(const Session& s, const Op& o) {
+  const char* t = s.dtype ? "true" : "false";
+  const int prec = o.kind == OP_PW ? (o.pw.fp8 ? 2 : (s.dtype ? 1 : 0)) : 0;
   char tmp[128];
   switch (o.kind) {
     case OP_STEM: if (o.stem.mfma) snprintf(tmp, sizeof tmp, "stem_kernel<%s, %d>", t, (o.stem.Cout + 15) / 16);
@@ -1100,7 +1102,44 @@ int hep_kernel_symbol(const hep_handle* h, int i, const char** symbol) try {
              }
              break;
   }
-  buf = tmp; *symbol = buf.c_str();
+  return tmp;
+}
+
+int hep_kernel_symbol(const hep_handle* h, int i, const char** symbol) try {
+  if (!h || !symbol || i < 0 || i >= (int)h->s.ops.size()) return fail(HEP_ERR_INVALID, "bad kernel index");
+  static thread_local std::string buf;
+  buf = kernel_symbol(h->s, h->s.ops[i]); *symbol = buf.c_str();
+  return 0;
+} HEP_CATCH_INT
+
+int hep_plan_launch_list(const void* pack, size_t pack_bytes, int phi, int size, int max_batch, int dtype, unsigned flags,
+                         char* out, size_t capacity, size_t* needed) try {
+  if (!needed && !out) return fail(HEP_ERR_INVALID, "out and needed are both NULL");
+  if (needed) *needed = 0;
+  if (!pack || pack_bytes < 12) return fail(HEP_ERR_PACK, "weight pack: empty");
+  if (dtype != HEP_F32 && dtype != HEP_BF16 && dtype != HEP_FP8) return fail(HEP_ERR_INVALID, "dtype must be HEP_F32, HEP_BF16 or HEP_FP8");
+#ifndef HEP_WITH_FP8
+  if (dtype == HEP_FP8) return fail(HEP_ERR_UNSUPPORTED, "this libhep.so was built without the fp8 path (make -C hmd_ego_pose_amd/csrc FP8=1): it measured slower than bf16");
+#endif
+  if (max_batch < 1 || max_batch > 4096) return fail(HEP_ERR_INVALID, "max_batch out of range (1..4096)");
+  if (size < 128 || size > 2048 || size % 128 != 0)
+    return fail(HEP_ERR_UNSUPPORTED, "size must be a multiple of 128 in [128, 2048] (P7 has stride 128)");
+  Session s;                                        // never realised on a device: its destructor has nothing to release
+  if (!make_arch(phi, &s.arch)) return fail(HEP_ERR_UNSUPPORTED, "phi must be in 0..7 (phi 8 needs a P8 level)");
+  Pack pk; std::string err;
+  if (!pk.parse(pack, pack_bytes, &err, /*borrow=*/true)) return fail(HEP_ERR_PACK, err);
+  s.size = size; s.max_batch = max_batch; s.dtype = dtype; s.device = 0; s.flags = flags;
+  session_lanes(&s);
+  s.cu_count = 256;                                 // build_session's fallback when the device does not say
+  Plan plan; plan.layout_only = true;               // the launch list needs the ops, not the weight blob they would point into
+  if (int rc = plan_session(&s, pk, &plan, &err)) return fail(rc, err);
+  std::string text;
+  for (const Op& o : s.ops) { text += kernel_symbol(s, o); text += " | "; text += o.name; text += '\n'; }
+  if (needed) *needed = text.size() + 1;
+  if (out) {
+    if (capacity < text.size() + 1) return fail(HEP_ERR_INVALID, "hep_plan_launch_list: the output buffer is smaller than *needed");
+    memcpy(out, text.c_str(), text.size() + 1);
+  }
   return 0;
 } HEP_CATCH_INT
 

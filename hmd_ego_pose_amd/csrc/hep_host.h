@@ -33,7 +33,7 @@ struct PackTensor { std::vector<int64_t> dims; const float* data; size_t count; 
 struct Pack {
   std::vector<unsigned char> storage;
   std::unordered_map<std::string, PackTensor> tensors;
-  bool parse(const void* blob, size_t n, std::string* err);
+  bool parse(const void* blob, size_t n, std::string* err, bool borrow = false);   // borrow: the tensors point into `blob`, which outlives the Pack
   const PackTensor* get(const std::string& name, std::initializer_list<int64_t> dims, std::string* err) const;
 };
 
@@ -70,6 +70,7 @@ struct Session {
   // patched copy of the plan, and the captured hipGraph runs the lanes as parallel branches: the
   // forward is a chain of ~100 small latency-bound kernels, and independent chains overlap on the chip.
   int lanes = 1, lane_batch = 1;
+  bool realised = false;            // build_session has begun to create device objects: the destructor releases them
   std::vector<std::vector<Op>> lane_ops; std::vector<hipStream_t> lane_streams; std::vector<hipEvent_t> lane_events;
   hipEvent_t fork_event = nullptr;
   int levels[5]; int level_off[5]; int num_anchors;

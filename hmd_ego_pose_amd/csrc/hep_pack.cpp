@@ -11,9 +11,9 @@
 namespace hep {
 
 // ---- weight pack ----
-bool Pack::parse(const void* blob, size_t n, std::string* err) {
-  storage.assign((const unsigned char*)blob, (const unsigned char*)blob + n);
-  const unsigned char* p = storage.data();
+bool Pack::parse(const void* blob, size_t n, std::string* err, bool borrow) {
+  if (!borrow) storage.assign((const unsigned char*)blob, (const unsigned char*)blob + n);
+  const unsigned char* p = borrow ? (const unsigned char*)blob : storage.data();
   auto fail = [&](const char* m) { *err = std::string("weight pack: ") + m; return false; };
   if (n < 12 || memcmp(p, "HEPW", 4) != 0) return fail("bad magic (expected HEPW)");
   uint32_t ver, count; memcpy(&ver, p + 4, 4); memcpy(&count, p + 8, 4);
@@ -75,23 +75,25 @@ static uint8_t f32_to_e4m3(float f) {
 }
 
 size_t WBuilder::alloc(size_t bytes) {
-  size_t off = (host.size() + 255) & ~(size_t)255;
-  host.resize(off + bytes, 0);
+  size_t off = (size + 255) & ~(size_t)255;
+  size = off + bytes;
+  if (!layout_only) host.resize(size, 0);
   return off;
 }
 size_t WBuilder::put_bytes(const std::vector<unsigned char>& v) {
   size_t off = alloc(v.size());
-  memcpy(host.data() + off, v.data(), v.size());
+  if (!layout_only) memcpy(host.data() + off, v.data(), v.size());
   return off;
 }
 size_t WBuilder::put_f32(const std::vector<float>& v) {
   size_t off = alloc(v.size() * 4);
-  memcpy(host.data() + off, v.data(), v.size() * 4);
+  if (!layout_only) memcpy(host.data() + off, v.data(), v.size() * 4);
   return off;
 }
 size_t WBuilder::put_fp8(const std::vector<float>& v, int rows, int K, int stride, std::vector<float>* scales) {
   const size_t off = alloc((size_t)rows * stride);
   scales->assign(rows, 1.f);
+  if (layout_only) return off;
   for (int n = 0; n < rows; n++) {
     float amax = 0.f;
     for (int k = 0; k < K; k++) amax = std::max(amax, fabsf(v[(size_t)n * K + k]));
@@ -104,6 +106,7 @@ size_t WBuilder::put_fp8(const std::vector<float>& v, int rows, int K, int strid
 size_t WBuilder::put_typed(const std::vector<float>& v) {
   if (dtype == 0) return put_f32(v);
   size_t off = alloc(v.size() * 2);
+  if (layout_only) return off;
   uint16_t* d = (uint16_t*)(host.data() + off);
   for (size_t i = 0; i < v.size(); i++) d[i] = f32_to_bf16(v[i]);
   return off;

@@ -25,7 +25,7 @@ struct Planner {
   int& ntails;                        // fused fronts that finish their squeeze-excite in their tail (one counter block each)
   const Knobs kn;                     // plan knobs as the environment had them when the session was created (hep_knobs.h)
   std::map<int, int> front_of_out, front_of_part;   // tensor -> the fused front (OP_MBF) that writes it as its output / its partial squeeze-excite rows
-  Planner(Session* s_, const Pack& p, Plan* plan, std::string* e) : s(s_), pk(p), err(e), refs(plan->refs), ntails(plan->ntails), kn(s_->knobs) { wb.dtype = s_->dtype; }
+  Planner(Session* s_, const Pack& p, Plan* plan, std::string* e) : s(s_), pk(p), err(e), refs(plan->refs), ntails(plan->ntails), kn(s_->knobs) { wb.dtype = s_->dtype; wb.layout_only = plan->layout_only; }
 
   int tensor(const std::string& name, int H, int W, int C, bool f32 = false) {
     TensorDesc t; t.name = name; t.H = H; t.W = W; t.C = C; t.f32 = f32;

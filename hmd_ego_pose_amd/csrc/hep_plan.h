@@ -11,6 +11,8 @@ namespace hep {
 uint16_t f32_to_bf16(float f);
 struct WBuilder {
   std::vector<unsigned char> host;
+  size_t size = 0;                                  // bytes laid out so far (host.size() unless layout_only)
+  bool layout_only = false;                         // hand out offsets, write nothing: a plan that no device will run (Plan::layout_only)
   int dtype = 0;
   size_t alloc(size_t bytes);                       // 256-byte aligned, zero-filled
   size_t put_bytes(const std::vector<unsigned char>& v);
@@ -45,6 +47,7 @@ struct Plan {
   std::vector<unsigned char> weights;   // host copy of the weight blob
   std::vector<Ref> refs;
   int ntails = 0;                       // fused fronts that finish their squeeze-excite in their tail (one counter block each)
+  bool layout_only = false;             // set by the caller: same ops, references and offsets, but `weights` stays empty (hep_plan_launch_list)
 };
 // Fills s->ops, tensors (offset, first_op, last_op), arena_bytes, num_classes, levels, level_off, num_anchors, feat_ids from
 // arch / size / max_batch / dtype / flags / knobs / lanes / lane_batch (and cu_count).  0 or HEP_ERR_PACK.

@@ -34,6 +34,7 @@ void patch_lane(const Session& s, const Plan& plan, int lane, std::vector<Op>* o
 }
 
 int build_session(Session* s, const Pack& pack, std::string* err) {
+  s->realised = true;
   if (hipDeviceGetAttribute(&s->cu_count, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || s->cu_count <= 0) s->cu_count = 256;
   Plan plan;
   if (int rc = plan_session(s, pack, &plan, err)) return rc;

@@ -413,6 +413,14 @@ int hep_fp8_scale(const hep_handle* h, int i, float* a_scale);
 int hep_calibrate_fp8(hep_handle* h, const float* frames_nchw_device, int batch);
 /* Device function (as rocprofv3 --kernel-trace names it, e.g. "sep_kernel<true>") behind launch i. */
 int hep_kernel_symbol(const hep_handle* h, int i, const char** symbol);
+/* The launch list of the session that hep_create_from_memory(pack, ..., phi, size, max_batch, dtype, device, flags) would build,
+ * planned on the host alone: no HIP call is made, so it works on a machine without a GPU.  The plan knobs are read from the
+ * environment as at hep_create (HEP_LANES included); the compute-unit count, which a session asks its device for, is 256.
+ * Text, one line per launch in launch order, each "<device function> | <launch name>\n" with the strings of hep_kernel_symbol and
+ * hep_kernel_info, NUL-terminated.  *needed (optional) receives the byte count including the NUL; out may be NULL to ask for
+ * it, otherwise capacity must be at least that.  The weights decide nothing but the class count (read from the classifier header). */
+int hep_plan_launch_list(const void* pack, size_t pack_bytes, int phi, int size, int max_batch, int dtype, unsigned flags,
+                         char* out, size_t capacity, size_t* needed);
 /* Time `iters` replays of the forward at `batch` with HIP events on the handle's own stream; when
  * per_kernel_ms is non-NULL (length hep_kernel_count) also run the forward eagerly with a HIP event
  * in front of every launch and return each launch's average in-sequence duration. */

@@ -22,6 +22,74 @@ CASES = {  # tag -> (phi, size, batch, seed, input kind)
 CLASS_CASES = {  # tag -> (phi, size, batch, seed, input kind, num_classes): the classifier header with more than one class
     "phi0_s256_b2_seed0_k3": (0, 256, 2, 0, "normal", 3),
 }
+
+# ---- what the GPU parity suite compares with a reference -------------------------------------------------------------------
+# One entry per session that a test of tests/test_gpu_parity.py holds against the CPU oracle:
+#   (phi, size, batch, dtype, knob environment, kind)
+# kind "stages":     teacher-forced stage by stage with FLAG_KEEP_INTERMEDIATES (_teacher_forced_fp32 / _teacher_forced_bf16 and
+#                    test_planner_variants_match_oracle_stage_by_stage, which checks the stages that hold a variant nothing else reaches);
+# kind "end_to_end": the head outputs within the fp32 1e-3 gate of the oracle.
+# Sessions that are only compared bit for bit with another plan (the fragment-order and bf16 plan-variant tests), the bf16 loop
+# of test_other_input_sizes (finite and loosely close) and the several-class sessions are not listed: they pin no variant to a
+# reference.  The tests take their parameters from these groups; tests/test_plan_coverage_cpu.py plans every entry on the host
+# and requires that each variant the planner can select over its support matrix is reached by at least one of them.
+def _e2e(cfgs, env=None):
+    return [(phi, size, batch, "fp32", dict(env or {}), "end_to_end") for phi, size, batch in cfgs]
+
+
+def _stages(cfgs, dtype):
+    return [(phi, size, batch, dtype, {}, "stages") for phi, size, batch in cfgs]
+
+
+OTHER_WIDTHS = [(phi, 256, 2) for phi in (1, 2, 4, 5, 6)]            # test_other_widths_match_oracle
+RAGGED_TILES = [(0, 384, 3), (0, 640, 1)]                             # test_ragged_tiles_match_oracle
+OTHER_SIZES = [(0, 128, 5), (0, 384, 2)]                              # test_other_input_sizes
+BF16_BASELINE = [(0, 256, 16), (3, 512, 8)]                           # test_bf16_matches_bf16_emulating_oracle
+FP32_STAGEWISE = [(0, 256, 16)]                                       # test_fp32_stage_by_stage_at_rounding_level
+ALT_PLAN_CONFIG = (0, 256, 3)                                         # test_alternative_plans_keep_parity, under each environment of:
+ALT_PLAN_ENVS = [{"HEP_MBF_MP": "force"}, {"HEP_LANES": "2"}, {"HEP_SE_MAXMB": "0"}, {"HEP_SE_MAXMB": "1000"}, {"HEP_TOWER_COOP": "0"},
+                 {"HEP_XBF_GENERIC": "1"}, {"HEP_STEM_MFMA": "1"}]
+# test_planner_variants_match_oracle_stage_by_stage: (phi, size, batch, dtype, the variants the case is there for).  The smallest set of
+# configurations found (greedy by variants per cost, redundant picks dropped: tools/plan_variants.py --uncovered --without variant_cover)
+# that reaches every variant of the support matrix that no entry above selects; the test checks the stages that hold a listed variant
+VARIANT_COVER = [
+    (0, 128, 1, 'bf16', ("pw_gemm_kernel<1, 1, 1, 2, 0, 1, 4>", "pw_gemm_kernel<1, 1, 1, 2, 0, 2, 4>")),
+    (1, 128, 16, 'fp32', ("pw_gemm_kernel<0, 2, 1, 0, 0, 1, 4>",)),
+    (3, 128, 1, 'bf16', ("pw_gemm_kernel<1, 1, 1, 2, 0, 3, 4>", "sep_kernel<true, 2, true, false>")),
+    (3, 128, 1, 'fp32', ("pw_gemm_kernel<0, 1, 1, 2, 0, 2, 4>", "pw_gemm_kernel<0, 2, 1, 1, 0, 2, 4>", "pw_gemm_kernel<0, 2, 1, 2, 0, 1, 4>")),
+    (0, 384, 1, 'fp32', ("pw_gemm_kernel<0, 2, 1, 1, 1, 0, 4>",)),
+    (0, 256, 64, 'fp32', ("pw_gemm_kernel<0, 1, 5, 0, 0, 2, 4>", "pw_gemm_kernel<0, 1, 5, 0, 0, 3, 4>", "pw_gemm_kernel<0, 1, 7, 0, 0, 3, 4>", "pw_gemm_kernel<0, 2, 3, 0, 0, 1, 4>", "pw_gemm_kernel<0, 2, 3, 0, 0, 3, 4>")),
+    (2, 128, 64, 'bf16', ("pw_gemm_kernel<1, 1, 3, 0, 0, 2, 4>", "pw_gemm_kernel<1, 2, 1, 0, 0, 1, 4>")),
+    (0, 384, 32, 'fp32', ("pw_gemm_kernel<0, 1, 7, 0, 1, 0, 4>", "pw_gemm_kernel<0, 1, 8, 0, 1, 0, 4>")),
+    (4, 128, 64, 'bf16', ("pw_gemm_kernel<1, 1, 4, 0, 0, 1, 4>", "pw_gemm_kernel<1, 1, 4, 0, 0, 2, 4>")),
+    (4, 128, 64, 'fp32', ("pw_gemm_kernel<0, 1, 4, 0, 0, 1, 4>", "pw_gemm_kernel<0, 1, 4, 0, 0, 3, 4>")),
+    (0, 640, 16, 'bf16', ("mbf_kernel<true, 5, 1, 8, false, 1>", "pw_gemm_kernel<1, 1, 5, 0, 0, 1, 4>", "pw_gemm_kernel<1, 1, 5, 0, 0, 3, 4>", "pw_gemm_kernel<1, 1, 7, 0, 0, 3, 4>", "pw_gemm_kernel<1, 1, 7, 0, 1, 0, 4>", "pw_gemm_kernel<1, 1, 8, 0, 1, 0, 4>", "pw_gemm_kernel<1, 2, 3, 0, 0, 3, 4>")),
+    (2, 384, 1, 'fp32', ("dw_kernel<false, 3, 1, 1>",)),
+    (5, 128, 64, 'fp32', ("pw_gemm_kernel<0, 1, 4, 0, 0, 2, 4>",)),
+    (2, 256, 64, 'bf16', ("pw_gemm_kernel<1, 1, 6, 0, 0, 2, 4>", "pw_gemm_kernel<1, 1, 6, 0, 0, 3, 4>", "pw_gemm_kernel<1, 1, 8, 0, 0, 3, 4>", "pw_gemm_kernel<1, 2, 1, 0, 0, 3, 4>", "pw_gemm_kernel<1, 2, 3, 0, 0, 1, 4>")),
+    (2, 256, 64, 'fp32', ("pw_gemm_kernel<0, 1, 6, 0, 0, 3, 4>", "pw_gemm_kernel<0, 1, 8, 0, 0, 3, 4>", "pw_gemm_kernel<0, 2, 1, 0, 0, 3, 4>")),
+    (5, 256, 1, 'fp32', ("pw_gemm_kernel<0, 1, 2, 2, 1, 0, 4>",)),
+    (2, 512, 1, 'bf16', ("pw_gemm_kernel<1, 2, 1, 2, 0, 2, 4>", "pw_gemm_kernel<1, 2, 2, 2, 0, 2, 4>")),
+    (4, 256, 32, 'bf16', ("mbf_kernel<true, 5, 2, 8, false, 1>", "pw_gemm_kernel<1, 1, 4, 0, 0, 3, 4>")),
+    (3, 512, 3, 'fp32', ("pw_gemm_kernel<0, 1, 2, 0, 0, 3, 4>",)),
+    (4, 256, 64, 'bf16', ("pw_gemm_kernel<1, 1, 7, 0, 0, 2, 4>", "pw_gemm_kernel<1, 2, 4, 0, 0, 1, 4>", "pw_gemm_kernel<1, 2, 4, 0, 0, 3, 4>")),
+    (4, 256, 64, 'fp32', ("pw_gemm_kernel<0, 2, 4, 0, 0, 1, 4>", "pw_gemm_kernel<0, 2, 4, 0, 0, 3, 4>")),
+    (5, 256, 64, 'bf16', ("pw_gemm_kernel<1, 1, 8, 0, 0, 2, 4>",)),
+    (6, 640, 1, 'bf16', ("dw_kernel<true, 3, 1, 2>", "dw_kernel<true, 5, 1, 4>", "pw_gemm_kernel<1, 2, 2, 2, 1, 0, 4>")),
+]
+
+PARITY_GROUPS = {
+    "golden": _e2e([c[:3] for c in CASES.values()]),
+    "other_widths": _e2e(OTHER_WIDTHS) + _stages(OTHER_WIDTHS, "fp32") + _stages(OTHER_WIDTHS, "bf16"),
+    "ragged_tiles": _e2e(RAGGED_TILES) + _stages(RAGGED_TILES, "bf16"),
+    "other_sizes": _e2e(OTHER_SIZES),
+    "bf16_baseline": _stages(BF16_BASELINE, "bf16"),
+    "fp32_stagewise": _stages(FP32_STAGEWISE, "fp32"),
+    "alt_plans": [e for env in ALT_PLAN_ENVS for e in _e2e([ALT_PLAN_CONFIG], env)],
+    "variant_cover": [(phi, size, batch, dtype, {}, "stages") for phi, size, batch, dtype, _variants in VARIANT_COVER],
+}
+PARITY_CONFIGS = [e for group in PARITY_GROUPS.values() for e in group]
+
 CAMS = np.array([[480, 480, 128, 128, 1000, 1.0],
                  [572.4114, 573.57043, 325.2611, 242.04899, 1000, 0.8]], dtype=np.float32)
 

@@ -27,7 +27,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests._util import CAMS, CASES, CLASS_CASES, check_digest, golden_case, seeded_input, strides_for
+from tests._util import (ALT_PLAN_CONFIG, ALT_PLAN_ENVS, BF16_BASELINE, CAMS, CASES, CLASS_CASES, FP32_STAGEWISE, OTHER_SIZES, OTHER_WIDTHS,
+                         RAGGED_TILES, VARIANT_COVER, check_digest, golden_case, seeded_input, strides_for)
 
 pytestmark = pytest.mark.gpu
 
@@ -83,13 +84,13 @@ def test_fp32_forward_matches_oracle_and_reference_golden(api, tag):
     s.close()
 
 
-@pytest.mark.parametrize("phi", [1, 2, 4, 5, 6])
+@pytest.mark.parametrize("phi", [c[0] for c in OTHER_WIDTHS])
 def test_other_widths_match_oracle(api, phi):
     """BiFPN widths 88 / 112 / 224 / 288 / 384 (not multiples of the 32-channel MFMA k-step; 224 and up take the
     wide-layer paths of the head kernels, 288 and up the 4x4-tile fp32 path of the BiFPN kernel): fp32 within
     1e-3 of the oracle, bf16 finite and close.  The oracle is the
     same code that the phi 0 / phi 3 golden vectors pin; 256x256 keeps the CPU side to seconds."""
-    size, batch, seed = 256, 2, 2
+    (_, size, batch), seed = next(c for c in OTHER_WIDTHS if c[0] == phi), 2
     sd = api["sd"](phi, seed)
     x = torch.from_numpy(seeded_input((batch, 3, size, size), seed))
     ref = api["R"].forward(sd, x, phi)
@@ -115,12 +116,12 @@ def test_other_widths_match_oracle(api, phi):
     _teacher_forced_bf16(api, sd, phi, size, batch, x, ref, strict=False)
 
 
-@pytest.mark.parametrize("size,batch", [(384, 3), (640, 1)])
+@pytest.mark.parametrize("size,batch", [c[1:] for c in RAGGED_TILES])
 def test_ragged_tiles_match_oracle(api, size, batch):
     """Input sizes (multiples of 128, as the reference's up/down-sampling requires) whose pyramid levels are
     not multiples of the 8x8 kernel tiles - 384: 48,24,12,6,3; 640: 80,40,20,10,5 (odd maps: one-sided SAME
     padding of the stride-2 layers and max-pools): fp32 within 1e-3 of the oracle."""
-    phi, seed = 0, 4
+    phi, seed = RAGGED_TILES[0][0], 4
     sd = api["sd"](phi, seed)
     x = torch.from_numpy(seeded_input((batch, 3, size, size), seed))
     want = _named(*api["R"].forward(sd, x, phi))
@@ -258,14 +259,14 @@ def _teacher_forced_fp32(api, sd, phi, size, batch, x):
 def test_fp32_stage_by_stage_at_rounding_level(api):
     """BASELINE config 2's shape in fp32, every stage on the device's own input: stem / blocks / BiFPN cells within 2e-5 of the oracle
     (measured ~1e-6), heads within 5e-4 - the end-to-end 1e-3 gate above it, without the network's amplification."""
-    phi, size, batch, seed = 0, 256, 16, 0
+    (phi, size, batch), seed = FP32_STAGEWISE[0], 0
     sd = api["sd"](phi, seed)
     x = torch.from_numpy(seeded_input((batch, 3, size, size), seed))
     body, head = _teacher_forced_fp32(api, sd, phi, size, batch, x)
     assert body <= FP32_STAGE_TOL and head <= FP32_HEAD_TOL
 
 
-@pytest.mark.parametrize("phi,size,batch", [(0, 256, 16), (3, 512, 8)])
+@pytest.mark.parametrize("phi,size,batch", BF16_BASELINE)
 def test_bf16_matches_bf16_emulating_oracle(api, phi, size, batch):
     """BASELINE configs 1 and 3 (phi 0 @ 256 batch 16, phi 3 @ 512 batch 8) in the benchmarked dtype: the stem, every
     MBConv block, every BiFPN cell and the five heads against the oracle that rounds where the kernels round, each
@@ -274,6 +275,115 @@ def test_bf16_matches_bf16_emulating_oracle(api, phi, size, batch):
     sd = api["sd"](phi, seed)
     x = torch.from_numpy(seeded_input((batch, 3, size, size), seed))
     _teacher_forced_bf16(api, sd, phi, size, batch, x, api["R"].forward(sd, x, phi))
+
+
+def _launch_stages(name):
+    """The stages (as the teacher-forced gates cut the network: "stem", "block<i>", "cell<r>", "heads") that the launch called ``name``
+    computes for.  A boundary kernel "b3.project+b4.front" works for two blocks; a BiFPN chain that runs on from a cell's last
+    down-path node into up-path nodes ("c0.conv5_down+conv6_down+conv7_down+conv6_up+conv5_up") has crossed into the next cell."""
+    if name == "stem":
+        return ["stem"]
+    if name.startswith("heads."):
+        return ["heads"]
+    if name[0] == "b":
+        return [f"block{int(p[1:p.index('.')])}" for p in name.split("+")]
+    assert name[0] == "c", name
+    r, nodes = int(name[1:name.index(".")]), name[name.index(".") + 1:].split("+")
+    down = [i for i, n in enumerate(nodes) if n.endswith("_down")]
+    crossed = bool(down) and any(n.endswith("_up") for n in nodes[down[0]:])
+    return [f"cell{r}"] + ([f"cell{r + 1}"] if crossed else [])
+
+
+def _images_to_check(batch, syms, maps):
+    """The images of the batch a stage is evaluated on by the oracle (a stage is a per-image function: BatchNorm is folded, squeeze-
+    excite is per image): the first, the last and, for every pointwise GEMM among ``syms`` and every map size ``maps`` (pixels per
+    image) it can run over, the images from the one in which the GEMM's LAST row tile begins - rows are (image, pixel), a tile is
+    64 * MT rows in mode 0 and 16 * MT in the split modes (k_pw_impl.h), so on a small map it straddles several images."""
+    pick = {0, batch - 1}
+    for y in syms:
+        if not y.startswith("pw_gemm_kernel<"):
+            continue
+        _prec, mt, _nt, mode = (int(v) for v in y[y.index("<") + 1:].split(",")[:4])
+        rows = (64 if mode == 0 else 16) * mt
+        for hw in maps:
+            pick.update(range(((batch * hw - 1) // rows * rows) // hw, batch))
+    return sorted(pick)
+
+
+@pytest.mark.parametrize("phi,size,batch,dtype,wanted", VARIANT_COVER, ids=[f"phi{c[0]}-{c[1]}-b{c[2]}-{c[3]}" for c in VARIANT_COVER])
+def test_planner_variants_match_oracle_stage_by_stage(api, phi, size, batch, dtype, wanted):
+    """The kernel variants that the planner selects somewhere in its support matrix but at none of the configurations above
+    (tests/_util.py VARIANT_COVER; tests/test_plan_coverage_cpu.py holds the table to the planner): one session per case at its full
+    max_batch - the variant depends on it - with the keep flag, and every stage that holds a launch of a wanted variant compared
+    with the oracle's stage function applied to the DEVICE's own input of that stage, on the images of _images_to_check.  Bounds
+    are the suite's own: fp32 FP32_STAGE_TOL (heads FP32_HEAD_TOL); bf16 blocks BF16_TOL_MAX / BF16_TOL_MEAN, bf16 cells and heads the
+    mean-only rule of _teacher_forced_bf16 for configurations that are no BASELINE one.
+    Measured on MI355X: NOTEBOOK.md section 19."""
+    from tests._util import seeded_state_dict_once
+    R = api["R"]
+    sd = seeded_state_dict_once(phi, 0)
+    x = torch.from_numpy(seeded_input((batch, 3, size, size), 7))
+    s = api["Session"](sd, phi, size, batch, dtype, flags=api["capi"].FLAG_KEEP_INTERMEDIATES)
+    plan = _plan_syms(s, batch)
+    assert set(wanted) <= {y for _, y in plan}, f"not planned here: {sorted(set(wanted) - {y for _, y in plan})}"
+    by_stage = {}
+    for name, y in plan:
+        if y in wanted:
+            for stage in _launch_stages(name):
+                by_stage.setdefault(stage, set()).add(y)
+    out = s.forward(x.cuda())
+    torch.cuda.synchronize()
+    ident = lambda t: t
+    st = R.emulated_stages(sd, phi) if dtype == "bf16" else R.emulated_stages(sd, phi, q_act=ident, q_w=ident)
+    assert all(k in ("stem", "heads") or int(k[4 if k[0] == "c" else 5:]) < st["n_cells" if k[0] == "c" else "n_blocks"] for k in by_stage), by_stage
+    dev = lambda name, idx: s.stage(name, batch)[idx].permute(0, 3, 1, 2).contiguous()      # the device's tensor, images idx, as NCHW fp32
+    label = f"phi {phi} @ {size} b{batch} {dtype}"
+    worst = {}
+
+    def check(kind, got, want):
+        """kind: "block" (stem included), "cell" or "heads"; got / want: name -> tensor"""
+        if dtype == "bf16":
+            tol = {"block": dict(max_tol=BF16_TOL_MAX, mean_tol=BF16_TOL_MEAN), "cell": dict(max_tol=None, mean_tol=2.5 * BF16_TOL_MEAN),
+                   "heads": dict(max_tol=None, mean_tol=2 * BF16_TOL_MEAN)}[kind]
+            for k, w in want.items():
+                err = (got[k] - w).abs()
+                fig = (err.max().item() / max(w.abs().max().item(), 1e-6), err.mean().item() / max(w.abs().mean().item(), 1e-6))
+                worst[kind] = max(worst.get(kind, (0.0, 0.0, "")), fig + (k,))
+            _check_bf16(label, got, want, **tol)
+            return
+        bound = FP32_HEAD_TOL if kind == "heads" else FP32_STAGE_TOL
+        for k, w in want.items():
+            g = got[k]
+            assert g.shape == w.shape and torch.isfinite(g).all(), (label, k)
+            err = (g - w).abs().max().item() / max(1.0, w.abs().max().item())
+            print(f"{label} {k}: max|err|/max(1,|oracle|) = {err:.2e}")
+            worst[kind] = max(worst.get(kind, (0.0, "")), (err, k))
+            assert err <= bound, f"{label} stage {k}: {err:.3e} (bound {bound:g})"
+
+    for stage in sorted(by_stage, key=lambda k: ({"s": 0, "b": 1, "c": 2, "h": 3}[k[0]], int("".join(c for c in k if c.isdigit()) or 0))):
+        syms = by_stage[stage]
+        if stage == "stem":
+            idx = _images_to_check(batch, syms, [])
+            check("block", {"stem": dev("stem", idx)}, {"stem": st["stem"](x[idx])})
+        elif stage.startswith("block"):
+            i = int(stage[5:])
+            src = f"block{i - 1}" if i else "stem"
+            maps = [s.stage(n, 1).shape[1] * s.stage(n, 1).shape[2] for n in (src, stage)]          # the expand GEMM runs over the input map, the project GEMM over the output map
+            idx = _images_to_check(batch, syms, maps)
+            check("block", {stage: dev(stage, idx)}, {stage: st["block"](i, dev(src, idx))})
+        elif stage.startswith("cell"):
+            r = int(stage[4:])
+            idx = _images_to_check(batch, syms, [])
+            feats = [dev(f"block{t}", idx) for t in st["taps"]] if r == 0 else [dev(f"c{r - 1}.p{l + 3}_out", idx) for l in range(5)]
+            want = st["cell"](r, feats)
+            check("cell", {f"c{r}.p{l + 3}_out": dev(f"c{r}.p{l + 3}_out", idx) for l in range(5)}, {f"c{r}.p{l + 3}_out": w for l, w in enumerate(want)})
+        else:
+            idx = _images_to_check(batch, syms, [])
+            feats = [dev(f"c{st['n_cells'] - 1}.p{l + 3}_out", idx) for l in range(5)]
+            check("heads", dict(zip(HEADS, [t.float().cpu()[idx] for t in out[1:]])), dict(zip(HEADS, st["heads"](feats))))
+    s.close()
+    print(f"{label} variants {', '.join(wanted)}: stages {', '.join(by_stage)}; worst " +
+          "; ".join(f"{kind} {w[-1]} " + " / ".join(f"{v:.2e}" for v in w[:-1]) for kind, w in worst.items()))
 
 
 def _fp8_session(api, sd, phi, size, batch):
@@ -710,15 +820,18 @@ def _plan_syms(s, batch):
 # true ONLY when the variant really was planned - the knobs are read when a session is created, so a case that silently
 # re-tested the default plan would fail here.  The measured-and-rejected alternatives (and their kernels) live in libhep_alt.so:
 # tests/test_gpu_alt.py, run in a child process by test_alternative_plan_suite_runs_against_the_opt_in_library.
-ALT_PLANS = [
-    ({"HEP_MBF_MP": "force"}, lambda ks: sum(y.endswith(", false, 1>") for _, y in ks if "mbf_kernel" in y) >= 8),      # multi-pass fronts (K staged in slices) wherever they exist
-    ({"HEP_LANES": "2"}, None),
-    ({"HEP_SE_MAXMB": "0"}, lambda ks: sum("se_finish_kernel" in y for _, y in ks) >= 12),
-    ({"HEP_SE_MAXMB": "1000"}, lambda ks: not any("se_finish_kernel" in y for _, y in ks)),
-    ({"HEP_TOWER_COOP": "0"}, lambda ks: any(y.startswith("tower_kernel<") for _, y in ks) and not any("tower_coop_kernel" in y for _, y in ks)),   # wave-per-patch heads
-    ({"HEP_XBF_GENERIC": "1"}, lambda ks: any("xbf_kernel" in y for _, y in ks) and all(y.endswith(", 0, 0>") for _, y in ks if "xbf_kernel" in y)),
-    ({"HEP_STEM_MFMA": "1"}, lambda ks: any(y.startswith("stem_kernel<") for _, y in ks)),
+# (the environments are tests/_util.py ALT_PLAN_ENVS - the table of what this suite compares with a reference - in that order)
+_ALT_PLANNED = [
+    lambda ks: sum(y.endswith(", false, 1>") for _, y in ks if "mbf_kernel" in y) >= 8,      # HEP_MBF_MP=force: multi-pass fronts (K staged in slices) wherever they exist
+    None,                                                                                     # HEP_LANES=2
+    lambda ks: sum("se_finish_kernel" in y for _, y in ks) >= 12,                              # HEP_SE_MAXMB=0
+    lambda ks: not any("se_finish_kernel" in y for _, y in ks),                                # HEP_SE_MAXMB=1000
+    lambda ks: any(y.startswith("tower_kernel<") for _, y in ks) and not any("tower_coop_kernel" in y for _, y in ks),   # HEP_TOWER_COOP=0: wave-per-patch heads
+    lambda ks: any("xbf_kernel" in y for _, y in ks) and all(y.endswith(", 0, 0>") for _, y in ks if "xbf_kernel" in y),   # HEP_XBF_GENERIC=1
+    lambda ks: any(y.startswith("stem_kernel<") for _, y in ks),                               # HEP_STEM_MFMA=1
 ]
+assert [list(e) for e in ALT_PLAN_ENVS] == [["HEP_MBF_MP"], ["HEP_LANES"], ["HEP_SE_MAXMB"], ["HEP_SE_MAXMB"], ["HEP_TOWER_COOP"], ["HEP_XBF_GENERIC"], ["HEP_STEM_MFMA"]]
+ALT_PLANS = list(zip(ALT_PLAN_ENVS, _ALT_PLANNED))
 
 
 @pytest.mark.parametrize("env,planned", ALT_PLANS, ids=["-".join(f"{k}={v}" for k, v in e.items()) for e, _ in ALT_PLANS])
@@ -726,7 +839,7 @@ def test_alternative_plans_keep_parity(api, env, planned, monkeypatch):
     """The planner picks between implementations by measurement (fused MBConv front vs expand+depthwise,
     tower kernel vs tiled sepconv for the heads, node chains, LDS depthwise, batch lanes); every alternative
     must produce the same numbers - and must really be the plan that ran (``planned``)."""
-    phi, size, batch = 0, 256, 3
+    phi, size, batch = ALT_PLAN_CONFIG
     sd = api["sd"](phi, 4)
     s0 = api["Session"](sd, phi, size, batch, "fp32")
     default_plan = _plan_syms(s0, batch)
@@ -882,12 +995,12 @@ def test_fp32_chains_with_pointwise_weights_from_global_memory(api, phi, monkeyp
     s.close()
 
 
-@pytest.mark.parametrize("size,batch", [(128, 5), (384, 2)])
+@pytest.mark.parametrize("size,batch", [c[1:] for c in OTHER_SIZES])
 def test_other_input_sizes(api, size, batch):
     """Sizes other than the two benchmark ones move every layer onto other kernels (at 128 blocks 1-2 take the small-map
     front kernel with 16 / 24 input channels: a k-step whose tail lanes must never read the unwritten pad columns of an
     LDS row - 0 x NaN is NaN, and that is how this case once failed in bf16)."""
-    phi = 0
+    phi = OTHER_SIZES[0][0]
     sd = api["sd"](phi, 2)
     x = torch.from_numpy(seeded_input((batch, 3, size, size), 9))
     ref = api["R"].forward(sd, x, phi)
