@@ -88,6 +88,8 @@ SYMBOLS = {
     "hep_calibrate_fp8": (c_int, [_P, _FP, c_int]),
     "hep_profile": (c_int, [_P, c_int, c_int, POINTER(c_float), _FP]),
     "hep_profile_concurrent": (c_int, [_P, c_int, c_int, c_int, _FP]),
+    "hep_augment_workspace_bytes": (c_int64, [c_int] * 5),
+    "hep_augment_6dof_device": (c_int, [_FP] * 11 + [c_int] * 5 + [c_float] + [_FP] * 8 + [c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -1232,4 +1232,59 @@ int hep_profile_concurrent(hep_handle* h, int batch, int iters, int nstreams, fl
   return 0;
 } HEP_CATCH_INT
 
+// ---- training input: 6DoF augmentation + preprocess (k_augment.hip) ----
+static int augment_range(int batch, int height, int width, int size, int kmax) {
+  if (batch < 1) return fail(HEP_ERR_INVALID, "augment: batch must be >= 1");
+  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, "augment: height and width must be in [16, 4096]");
+  if (size < 16 || size > 4096 || size % 4 != 0) return fail(HEP_ERR_UNSUPPORTED, "augment: size must be a multiple of 4 in [16, 4096]");
+  if (kmax < 1 || kmax > AUG_MAX_K) return fail(HEP_ERR_UNSUPPORTED, "augment: kmax must be in 1..16 annotations per image");
+  return 0;
+}
+static int64_t augment_partial_bytes(int batch, int height, int kmax) {
+  const int64_t tiles = (height + AUG_TILE_ROWS - 1) / AUG_TILE_ROWS;
+  return ((int64_t)batch * tiles * (4 * kmax + 1) * 4 + 255) & ~(int64_t)255;
+}
+
+// the box partials and the uint8 frame of the resize launch (counted whether or not this size needs it: the figure never shrinks as an argument grows)
+int64_t hep_augment_workspace_bytes(int batch, int height, int width, int size, int kmax) try {
+  if (int rc = augment_range(batch, height, width, size, kmax)) return rc;
+  return augment_partial_bytes(batch, height, kmax) + (((int64_t)batch * height * width * 3 + 255) & ~(int64_t)255);
+} HEP_CATCH_INT
+
+int hep_augment_6dof_device(const uint8_t* rgb_hwc, const uint8_t* mask, const double* xform, const float* camera_k, const double* boxes,
+                            const int32_t* labels, const int32_t* mask_values, const float* rvec, const float* tvec, const float* extra,
+                            const int32_t* num_gt, int batch, int height, int width, int size, int kmax, float translation_scale_norm,
+                            float* image_nchw, uint8_t* mask_out, float* camera, double* gt_boxes, int32_t* gt_labels, float* gt_transform,
+                            int32_t* gt_num, int32_t* applied, void* workspace, int64_t workspace_bytes, void* stream) try {
+  if (!rgb_hwc || !mask || !xform || !camera_k || !boxes || !labels || !mask_values || !rvec || !tvec || !extra || !num_gt)
+    return fail(HEP_ERR_INVALID, "augment: a required input pointer is NULL");
+  if (!image_nchw || !camera || !gt_boxes || !gt_labels || !gt_transform || !gt_num || !applied)
+    return fail(HEP_ERR_INVALID, "augment: a required output pointer is NULL (only mask_out may be)");
+  if (!workspace) return fail(HEP_ERR_INVALID, "augment: workspace is NULL");
+  if (int rc = augment_range(batch, height, width, size, kmax)) return rc;
+  if (((uintptr_t)image_nchw & 15) != 0 || ((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "augment: image_nchw and workspace must be 16-byte aligned");
+  const int64_t need = hep_augment_workspace_bytes(batch, height, width, size, kmax);
+  if (workspace_bytes < need) return fail(HEP_ERR_INVALID, "augment: workspace too small (hep_augment_workspace_bytes)");
+  AugmentArgs a;
+  a.rgb = rgb_hwc; a.mask = mask; a.xform = xform; a.camera_k = camera_k; a.boxes = boxes; a.labels = labels; a.mask_values = mask_values;
+  a.rvec = rvec; a.tvec = tvec; a.extra = extra; a.num_gt = num_gt;
+  a.B = batch; a.H = height; a.W = width; a.S = size; a.kmax = kmax; a.tiles = (height + AUG_TILE_ROWS - 1) / AUG_TILE_ROWS;
+  a.tsn = translation_scale_norm;
+  // preprocess_image (common.py:576-607), as hep_preprocess_u8_device: the longer side becomes size, the other int(side * scale)
+  const int side = std::max(height, width);
+  a.resize = side != size;
+  a.image_scale = (double)size / side;
+  a.nh = height > width ? size : (int)(height * a.image_scale);
+  a.nw = height > width ? (int)(width * a.image_scale) : size;
+  if (!a.resize) { a.nh = height; a.nw = width; }
+  if (a.nh > size || a.nw > size || a.nh < 1 || a.nw < 1) return fail(HEP_ERR_UNSUPPORTED, "augment: resized frame does not fit the network size");
+  a.inv_scale_x = (double)width / a.nw; a.inv_scale_y = (double)height / a.nh;
+  a.image = image_nchw; a.mask_out = mask_out; a.camera = camera; a.gt_boxes = gt_boxes; a.gt_labels = gt_labels; a.gt_transform = gt_transform;
+  a.gt_num = gt_num; a.applied = applied;
+  a.partials = (int32_t*)workspace; a.frame_u8 = (uint8_t*)workspace + augment_partial_bytes(batch, height, kmax);
+  launch_augment(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 }  // extern "C"

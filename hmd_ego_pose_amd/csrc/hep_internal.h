@@ -338,6 +338,22 @@ struct AnchorTargetArgs {
 };
 void launch_anchor_targets(const AnchorTargetArgs&, hipStream_t);
 
+// ---- training side: 6DoF augmentation + preprocess of the generator (generators/common.py:348-479, :543-607), k_augment.hip ----
+#define AUG_MAX_K 16          // annotations per image
+#define AUG_TILE_ROWS 8       // rows of one aug_mask workgroup
+struct AugmentArgs {
+  const uint8_t* rgb; const uint8_t* mask;                         // [B][H][W][3] ; [B][H][W]
+  const double* xform; const float* camera_k;                      // [B][9] M (6), angle rad, scale, apply ; [B][4]
+  const double* boxes; const int32_t* labels; const int32_t* mask_values;      // [B][kmax][4] ; [B][kmax] ; [B][kmax]
+  const float* rvec; const float* tvec; const float* extra; const int32_t* num_gt;
+  int B, H, W, S, kmax, tiles;                                     // tiles = ceil(H / AUG_TILE_ROWS)
+  int resize, nh, nw; float tsn; double image_scale, inv_scale_x, inv_scale_y;
+  float* image; uint8_t* mask_out; float* camera;                  // [B][3][S][S] ; [B][H][W] (nullable) ; [B][6]
+  double* gt_boxes; int32_t* gt_labels; float* gt_transform; int32_t* gt_num; int32_t* applied;
+  int32_t* partials; uint8_t* frame_u8;                            // workspace: [B][tiles][4 kmax + 1] ; [B][H][W][3]
+};
+void launch_augment(const AugmentArgs&, hipStream_t);
+
 // ---- training side: the five losses of batch_iterate (hmdegopose/loss.py:54-99), forward values ----
 #define LOSS_MAX_POINTS 2048
 struct LossArgs {

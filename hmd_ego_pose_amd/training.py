@@ -65,6 +65,48 @@ def anchor_targets(anchors: torch.Tensor, boxes: Sequence[np.ndarray], labels: S
     return lab, reg, tra, crd
 
 
+def anchor_targets_device(anchors: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_transform: torch.Tensor,
+                          gt_coords: Optional[torch.Tensor], gt_num: torch.Tensor, image_hw, num_classes: int = 1,
+                          negative_overlap: float = 0.4, positive_overlap: float = 0.5):
+    """``anchor_targets`` on annotation tables that are ALREADY on the device, in the layout hep_anchor_targets_device reads (and
+    ``augment.augment_6dof`` writes): gt_boxes float64 [B,kmax,4], gt_labels int32 [B,kmax], gt_transform float32 [B,kmax,RT],
+    gt_coords float32 [B,kmax,63] or None, gt_num int32 [B] (the first gt_num[b] rows of image b count), ``image_hw`` an int32
+    device tensor [B,2] = (height, width) of the unpadded image or one (height, width) pair for the whole batch.  No numpy staging
+    and no stream synchronise: the launch is enqueued on the current stream and the outputs of ``anchor_targets`` are returned."""
+    if not anchors.is_cuda or anchors.dtype != torch.float32 or anchors.dim() != 2 or anchors.shape[1] != 4:
+        raise ValueError("anchors must be a float32 ROCm tensor [N,4]")
+    dev, N = anchors.device, anchors.shape[0]
+
+    def chk(t, name, dtype, dims):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or t.dim() != dims:
+            raise ValueError(f"{name} must be a {dtype} tensor with {dims} dimensions on {dev}")
+        return t.contiguous()
+
+    gb, gl, gt, ng = chk(gt_boxes, "gt_boxes", torch.float64, 3), chk(gt_labels, "gt_labels", torch.int32, 2), chk(gt_transform, "gt_transform", torch.float32, 3), chk(gt_num, "gt_num", torch.int32, 1)
+    B, kmax, rt = gl.shape[0], gl.shape[1], gt.shape[2]
+    if B < 1 or kmax < 1 or tuple(gb.shape) != (B, kmax, 4) or tuple(gt.shape) != (B, kmax, rt) or tuple(ng.shape) != (B,):
+        raise ValueError("gt_boxes [B,kmax,4], gt_labels [B,kmax], gt_transform [B,kmax,RT] and gt_num [B] must agree")
+    gc = None
+    if gt_coords is not None:
+        gc = chk(gt_coords, "gt_coords", torch.float32, 3)
+        if tuple(gc.shape) != (B, kmax, 63):
+            raise ValueError("gt_coords must be [B,kmax,63]")
+    if isinstance(image_hw, torch.Tensor):
+        hw = chk(image_hw, "image_hw", torch.int32, 2)
+        if tuple(hw.shape) != (B, 2):
+            raise ValueError("image_hw must be [B,2]")
+    else:
+        hw = torch.tensor([[int(image_hw[0]), int(image_hw[1])]] * B, dtype=torch.int32).to(dev, non_blocking=True)
+    f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    lab, reg, tra = f(B, N, num_classes + 1), f(B, N, 5), f(B, N, rt + 1)
+    crd = f(B, N, 64) if gc is not None else None
+    a = anchors.contiguous()
+    _capi.check(_capi.lib().hep_anchor_targets_device(a.data_ptr(), N, gb.data_ptr(), gl.data_ptr(), gt.data_ptr(), _capi.ptr(gc), ng.data_ptr(),
+                                                      hw.data_ptr(), B, kmax, num_classes, rt, float(negative_overlap), float(positive_overlap),
+                                                      lab.data_ptr(), reg.data_ptr(), tra.data_ptr(), _capi.ptr(crd), torch.cuda.current_stream(dev).cuda_stream))
+    return lab, reg, tra, crd
+
+
 _T_ANCHORS = {}
 
 

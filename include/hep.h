@@ -431,6 +431,46 @@ int hep_profile(hep_handle* h, int batch, int iters, float* total_ms_per_iter, f
  * batches in flight, so this - not the stand-alone duration - is what a launch costs the pipeline). */
 int hep_profile_concurrent(hep_handle* h, int batch, int iters, int nstreams, float* per_kernel_ms);
 
+/* Training input (the reference's host generator in front of the training step, pytorch-sandbox/generators/common.py:348-479
+ * augment_6DoF_image_and_annotations / augmentation_6DoF and :543-607 preprocess_group_entry), on device memory, in three launches
+ * (four when max(height, width) != size), with no host synchronisation and no allocation: the caller owns the workspace
+ * (hep_augment_workspace_bytes; >= 0, or a negative hep_status).
+ * Inputs: rgb_hwc uint8 [batch][height][width][3]; mask uint8 [batch][height][width]; xform float64 [batch][9] = the forward matrix
+ * of cv2.getRotationMatrix2D((cx, cy), -angle, scale) (6, row major, computed by the caller on the host), the angle in radians, the
+ * scale, apply (0: leave this image alone); camera_k [batch][4] = fx, fy, px, py; per annotation (the first num_gt[b] of kmax):
+ * boxes float64 x1,y1,x2,y2, labels, mask_values (the mask byte of the object), rvec / tvec float32 [3], extra [2] = is_symmetric,
+ * class index.
+ * Per image: the mask is warped (INTER_NEAREST); when the warped mask has no non-zero pixel, when apply is 0, or when the scale on
+ * the device is outside [0.25, 4], the image, boxes and poses pass through unchanged and applied[b] = 0.  Otherwise applied[b] = 1:
+ * the image is warped (INTER_LINEAR, constant border 0), each annotation's box is the extent of its mask value in the warped mask
+ * (an annotation with no pixel left is removed, the order of the rest is kept), its pose becomes R' = Rz(angle) R(rvec),
+ * t' = Rz t, t'_z /= scale (float32 in, double arithmetic, float32 out).  Then preprocess_group_entry: image_scale = size /
+ * max(height, width), boxes * image_scale, rotation / pi, the frame resized when max(height, width) != size (the 8-bit resize of
+ * hep_preprocess_u8_device), normalised with that entry point's arithmetic and zero-padded.
+ * Outputs: image_nchw float32 [batch][3][size][size] (16-byte aligned; what hep_backbone_forward_device takes); mask_out (may be
+ * NULL) uint8 [batch][height][width], the mask that goes with the image; camera [batch][6] = fx, fy, px, py,
+ * translation_scale_norm, image_scale; gt_boxes float64 [batch][kmax][4], gt_labels [batch][kmax], gt_transform [batch][kmax][8] =
+ * (rotation / pi [3], translation [3], is_symmetric, class index), gt_num [batch] - exactly the inputs of hep_anchor_targets_device,
+ * rows at and beyond gt_num[b] zero; applied [batch].
+ * PARITY-UNPINNED: OpenCV's conventions (the double inverse in warpAffine's order, the AB_BITS = 10 / INTER_BITS = 5 fixed-point map,
+ * the int32 bilinear weights that sum to 32768, Rodrigues) are restated from its source, cv2 is not available to this project; the
+ * definition is the numpy oracle tests/_augment.py, which the kernels reproduce bit for bit (image, mask, boxes, labels, camera).
+ * What OpenCV's int16 table does with a weight of 32768 is not restated.  Not reproduced: coords_3d is not touched (the reference
+ * does not rotate hand joints), translations_x_y_2D is not produced (anchor_targets_bbox never reads it), colour augmentation.
+ * Supported: height, width in [16, 4096], size a multiple of 4 in [16, 4096], kmax in 1..16 (HEP_ERR_UNSUPPORTED otherwise, with
+ * the reason, before any HIP call); a NULL required pointer, batch < 1, a misaligned image_nchw or a short workspace is
+ * HEP_ERR_INVALID.  The scale lives in device memory: the ABI cannot refuse it without a synchronisation, so an out-of-range scale
+ * shows as applied[b] = 0 (hmd_ego_pose_amd.augment refuses it on the host). */
+int64_t hep_augment_workspace_bytes(int batch, int height, int width, int size, int kmax);
+int hep_augment_6dof_device(
+    const uint8_t* rgb_hwc, const uint8_t* mask, const double* xform, const float* camera_k,
+    const double* boxes, const int32_t* labels, const int32_t* mask_values,
+    const float* rvec, const float* tvec, const float* extra,
+    const int32_t* num_gt, int batch, int height, int width, int size, int kmax, float translation_scale_norm,
+    float* image_nchw, uint8_t* mask_out, float* camera,
+    double* gt_boxes, int32_t* gt_labels, float* gt_transform, int32_t* gt_num, int32_t* applied,
+    void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
