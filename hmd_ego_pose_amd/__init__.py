@@ -21,6 +21,9 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name == "TrainableBackbone":
         from .backbone import TrainableBackbone
         return TrainableBackbone
+    if name == "Trainer":
+        from .trainer import Trainer
+        return Trainer
     if name == "InflightPool":
         from .pipeline import InflightPool
         return InflightPool

@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get("HEP_LIB") or os.path.join(os.path.dirname(os.path.abs
 HEP_F32, HEP_BF16, HEP_FP8 = 0, 1, 2
 FLAG_KEEP_INTERMEDIATES, FLAG_NO_GRAPH = 1, 2
 OUT_K = (4, 1, 3, 3, 63)
+PK_TRAIN, PK_STAT, PK_FROZEN = 0, 1, 2      # HEP_PK_* of include/hep.h
+OPT_ADAM, OPT_SGD_NESTEROV = 0, 1          # HEP_OPT_*
 
 # every symbol include/hep.h declares: (restype, argtypes)
 _P = c_void_p
@@ -90,6 +92,11 @@ SYMBOLS = {
     "hep_profile_concurrent": (c_int, [_P, c_int, c_int, c_int, _FP]),
     "hep_augment_workspace_bytes": (c_int64, [c_int] * 5),
     "hep_augment_6dof_device": (c_int, [_FP] * 11 + [c_int] * 5 + [c_float] + [_FP] * 8 + [c_void_p, c_int64, c_void_p]),
+    "hep_optim_workspace_bytes": (c_int64, [c_int64]),
+    "hep_optim_grad_norm_device": (c_int, [_FP, _FP, c_int64, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "hep_optim_update_device": (c_int, [_FP] * 6 + [c_int64, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),
+    "hep_transformation_pack_device": (c_int, [_FP] * 4 + [c_int] * 3 + [_FP, c_void_p]),
+    "hep_transformation_unpack_grad_device": (c_int, [_FP] * 4 + [c_int] * 3 + [_FP, _FP, c_void_p]),
 }
 
 

@@ -1287,4 +1287,80 @@ int hep_augment_6dof_device(const uint8_t* rgb_hwc, const uint8_t* mask, const d
   return 0;
 } HEP_CATCH_INT
 
+// ---- the training step between the parts: optimiser, gradient norm, translation glue (k_train.hip) ----
+static int optim_check(const char* what, int64_t n, int optimizer, const void* const* ptrs, int count, const void* kind, const void* state) {
+  if (n <= 0) return fail(HEP_ERR_INVALID, std::string(what) + ": n must be > 0");
+  if (!kind || !state) return fail(HEP_ERR_INVALID, std::string(what) + ": kind or state is NULL");
+  for (int i = 0; i < count; i++) {
+    if (!ptrs[i]) return fail(HEP_ERR_INVALID, std::string(what) + ": a required pointer is NULL");
+    if (((uintptr_t)ptrs[i] & 15) != 0) return fail(HEP_ERR_INVALID, std::string(what) + ": the float buffers must be 16-byte aligned");
+  }
+  if (((uintptr_t)kind & 3) != 0 || ((uintptr_t)state & 15) != 0) return fail(HEP_ERR_INVALID, std::string(what) + ": kind must be 4-byte, state 16-byte aligned");
+  if (optimizer != HEP_OPT_ADAM && optimizer != HEP_OPT_SGD_NESTEROV)
+    return fail(HEP_ERR_UNSUPPORTED, std::string(what) + ": optimizer " + std::to_string(optimizer) + " is not built (HEP_OPT_ADAM = 0, HEP_OPT_SGD_NESTEROV = 1)");
+  return 0;
+}
+
+int64_t hep_optim_workspace_bytes(int64_t n) try {
+  if (n <= 0) return fail(HEP_ERR_INVALID, "optim: n must be > 0");
+  return ((int64_t)optim_grid(n) * 8 + 15) & ~(int64_t)15;
+} HEP_CATCH_INT
+
+int hep_optim_grad_norm_device(const float* grad, const uint8_t* kind, int64_t n, int optimizer, float beta1, float beta2, float max_norm,
+                               void* state, void* workspace, size_t workspace_bytes, void* stream) try {
+  const void* ptrs[2] = {grad, workspace};
+  if (int rc = optim_check("optim_grad_norm", n, optimizer, ptrs, 2, kind, state)) return rc;
+  if ((int64_t)workspace_bytes < hep_optim_workspace_bytes(n)) return fail(HEP_ERR_INVALID, "optim_grad_norm: workspace too small (hep_optim_workspace_bytes)");
+  OptimArgs a{};
+  a.grad = grad; a.kind = kind; a.n = n; a.optimizer = optimizer; a.blocks = optim_grid(n); a.beta1 = beta1; a.beta2 = beta2; a.max_norm = max_norm;
+  a.state = (OptimState*)state; a.partials = (double*)workspace;
+  launch_optim_norm(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_optim_update_device(float* params, const float* grad, float* m, float* v, const float* stats, const uint8_t* kind, int64_t n,
+                            int optimizer, float lr, float beta1, float beta2, float eps, const void* state, void* stream) try {
+  const void* ptrs[4] = {params, grad, m, v};
+  if (int rc = optim_check("optim_update", n, optimizer, ptrs, optimizer == HEP_OPT_SGD_NESTEROV && !v ? 3 : 4, kind, state)) return rc;
+  if (stats && ((uintptr_t)stats & 15) != 0) return fail(HEP_ERR_INVALID, "optim_update: the float buffers must be 16-byte aligned");
+  OptimArgs a{};
+  a.params = params; a.grad = grad; a.m = m; a.v = v; a.stats = stats; a.kind = kind; a.n = n; a.optimizer = optimizer; a.blocks = optim_grid(n);
+  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.state = (OptimState*)state;
+  launch_optim_update(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+static int transform_check(const char* what, int batch, int num_anchors, int num_rotation) {
+  if (batch < 1 || num_anchors < 1 || num_rotation < 1 || num_rotation > 8) return fail(HEP_ERR_INVALID, std::string(what) + ": bad size");
+  return 0;
+}
+
+int hep_transformation_pack_device(const float* rotation, const float* translation_raw, const float* camera, const float* translation_anchors,
+                                   int batch, int num_anchors, int num_rotation, float* transformation, void* stream) try {
+  if (!rotation || !translation_raw || !camera || !translation_anchors || !transformation) return fail(HEP_ERR_INVALID, "transformation_pack: a pointer is NULL");
+  if (int rc = transform_check("transformation_pack", batch, num_anchors, num_rotation)) return rc;
+  TransformArgs a{};
+  a.rotation = rotation; a.raw = translation_raw; a.camera = camera; a.anchors = translation_anchors; a.transformation = transformation;
+  a.B = batch; a.N = num_anchors; a.R = num_rotation;
+  launch_transformation_pack(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+int hep_transformation_unpack_grad_device(const float* grad_transformation, const float* translation_raw, const float* camera,
+                                          const float* translation_anchors, int batch, int num_anchors, int num_rotation,
+                                          float* grad_rotation, float* grad_translation_raw, void* stream) try {
+  if (!grad_transformation || !translation_raw || !camera || !translation_anchors || !grad_rotation || !grad_translation_raw)
+    return fail(HEP_ERR_INVALID, "transformation_unpack_grad: a pointer is NULL");
+  if (int rc = transform_check("transformation_unpack_grad", batch, num_anchors, num_rotation)) return rc;
+  TransformArgs a{};
+  a.transformation = const_cast<float*>(grad_transformation); a.raw = translation_raw; a.camera = camera; a.anchors = translation_anchors;
+  a.g_rotation = grad_rotation; a.g_raw = grad_translation_raw; a.B = batch; a.N = num_anchors; a.R = num_rotation;
+  launch_transformation_unpack_grad(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 }  // extern "C"

@@ -354,6 +354,26 @@ struct AugmentArgs {
 };
 void launch_augment(const AugmentArgs&, hipStream_t);
 
+// ---- training side: optimiser update, gradient norm and the translation glue of the one-call step (k_train.hip) ----
+#define OPT_MAX_BLOCKS 1024   // the fixed grid of the streaming passes: at most this many workgroups, one double partial each
+struct OptimState { float norm, clip_coef, bias1, bias2_sqrt; int32_t step, skipped; int32_t pad[2]; };      // the 32-byte state block of include/hep.h
+struct OptimArgs {
+  float* params; const float* grad; float* m; float* v; const float* stats; const uint8_t* kind; int64_t n;
+  int optimizer, blocks; float lr, beta1, beta2, eps, max_norm;
+  OptimState* state; double* partials;                             // partials: [blocks] in the caller's workspace
+};
+int optim_grid(int64_t n);
+void launch_optim_norm(const OptimArgs&, hipStream_t);
+void launch_optim_update(const OptimArgs&, hipStream_t);
+struct TransformArgs {
+  const float* rotation; const float* raw; const float* camera; const float* anchors;      // [B][N][R] ; [B][N][3] ; [B][6] ; [N][3]
+  float* transformation;                                           // [B][N][R+3]: written by pack, the gradient read by unpack
+  float* g_rotation; float* g_raw;                                 // unpack: [B][N][R] ; [B][N][3]
+  int B, N, R;
+};
+void launch_transformation_pack(const TransformArgs&, hipStream_t);
+void launch_transformation_unpack_grad(const TransformArgs&, hipStream_t);
+
 // ---- training side: the five losses of batch_iterate (hmdegopose/loss.py:54-99), forward values ----
 #define LOSS_MAX_POINTS 2048
 struct LossArgs {

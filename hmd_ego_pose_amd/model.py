@@ -446,6 +446,17 @@ class TrainModelWithLoss(nn.Module):
         cls_l, reg_l, rot_l, tr_l, hand_l = out[0] * 1.0, out[1] * 1.0, out[2] * 100, out[3] * 0.1, out[4] * 1.0      # train.py:61-65
         return [cls_l, reg_l, rot_l, tr_l, hand_l, cls_l + reg_l + rot_l + tr_l + hand_l]
 
+    def fit_step(self, imgs, camera_params, classification_gt, regression_gt, transformation_gt, coords_3d_gt, model_3d_points, **trainer_kwargs):
+        """One TRAINING step of the wrapped model (train.py:186-214: forward, the five weighted losses, backward, optimiser) through
+        ``hmd_ego_pose_amd.trainer.Trainer``, built from the model on the first call (``trainer_kwargs``: ``optimizer``, ``lr``,
+        ``batch_norm``, ``max_grad_norm``, ... of ``Trainer.from_model``, read on that call only).  Returns the trainer's [6] device
+        tensor [classification, regression, rotation, translation, hands, total].  The fitted tensors live in ``self.trainer`` until
+        ``self.trainer.export_to(self.model)`` copies them back; ``forward`` and ``validation_losses`` serve the model as it is."""
+        if getattr(self, "trainer", None) is None:
+            from .trainer import Trainer
+            self.trainer = Trainer.from_model(self.model, **trainer_kwargs)
+        return self.trainer.step(imgs, camera_params, classification_gt, regression_gt, transformation_gt, coords_3d_gt, model_3d_points)
+
     def forward(self, imgs, camera_params, is_losses=False, model_3d_points=None, classification_gt=None, regression_gt=None,
                 transformation_gt=None, coords_3d_gt=None, params=None, **kwargs):
         if is_losses:

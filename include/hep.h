@@ -471,6 +471,61 @@ int hep_augment_6dof_device(
     double* gt_boxes, int32_t* gt_labels, float* gt_transform, int32_t* gt_num, int32_t* applied,
     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The training step between the parts (csrc/k_train.hip): the optimiser, the gradient norm and the translation glue over the flat
+ * buffers of the hep_{backbone,neck,heads}_*_device_bn calls, so that one object can own params | grad | stats for the whole model
+ * and run the reference's step (train.py:88-342) as plain calls on one stream.  Conventions of the hep_heads_* group: stateless,
+ * asynchronous on `stream`, no allocation, no host synchronisation, argument checks before any HIP call, bit-reproducible (fixed
+ * reduction order, no float atomics).
+ *
+ * kind: one uint8 per element of the flat buffer (4-byte aligned):
+ *   HEP_PK_TRAIN   updated by the optimiser
+ *   HEP_PK_STAT    running_mean / running_var: never touched by the optimiser; takes the value of `stats` when stats != NULL
+ *   HEP_PK_FROZEN  left bit-unchanged (padding between parts, a frozen part); any other value is treated like it
+ * state: 32 bytes on the device (16-byte aligned), owned by the caller and zeroed once:
+ *   float norm, clip_coef, bias1, bias2_sqrt; int32 step, skipped; int32 pad[2].
+ *
+ * hep_optim_grad_norm_device: the 2-norm of the HEP_PK_TRAIN elements of grad.  Pass 1: a fixed grid (a function of n only), each
+ * thread sums its squares in double, a fixed-order tree per workgroup, one double partial per workgroup in the workspace
+ * (hep_optim_workspace_bytes(n) bytes, 16-byte aligned).  Pass 2: one workgroup sums the partials in index order and writes the
+ * state block: norm = sqrt(sum); when it is finite (as a float) step += 1, clip_coef = max_norm > 0 ? min(1, max_norm / (norm +
+ * 1e-6)) : 1 (torch.nn.utils.clip_grad_norm_), bias1 = 1 - beta1^step, bias2_sqrt = sqrt(1 - beta2^step) (in double); otherwise
+ * skipped += 1, clip_coef = 0 and step stays.
+ *
+ * hep_optim_update_device: one pass over the buffer, after hep_optim_grad_norm_device of the same gradient (it reads the state
+ * block).  When that norm was not finite it writes nothing: params, m, v and the statistics stay bit-identical.  Otherwise, with
+ * g' = clip_coef g, for HEP_PK_TRAIN:
+ *   HEP_OPT_ADAM (torch.optim.Adam's defaults)   m += (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g'^2;
+ *                                                p -= (lr / bias1) m / (sqrt(v) / bias2_sqrt + eps)
+ *   HEP_OPT_SGD_NESTEROV (train.py:103)          m = beta1 m + g';  p = fma(-lr, fma(beta1, m, g'), p)      (v may be NULL; from m = 0
+ *                                                the first step is torch's buf = g)
+ * HEP_PK_STAT: p = stats[i] when stats != NULL.  m and v of the other kinds are not touched.  29 bytes per trainable element move.
+ * lr is a host argument (a scheduler on the host keeps working).  params, grad, m, v, stats: 16-byte aligned, n floats.
+ * NULL (but stats, and v under SGD), n <= 0, a misaligned pointer or a short workspace: HEP_ERR_INVALID; an unknown optimiser:
+ * HEP_ERR_UNSUPPORTED with the reason. */
+#define HEP_PK_TRAIN 0
+#define HEP_PK_STAT 1
+#define HEP_PK_FROZEN 2
+#define HEP_OPT_ADAM 0
+#define HEP_OPT_SGD_NESTEROV 1
+int64_t hep_optim_workspace_bytes(int64_t n);
+int hep_optim_grad_norm_device(const float* grad, const uint8_t* kind, int64_t n, int optimizer, float beta1, float beta2, float max_norm,
+                               void* state, void* workspace, size_t workspace_bytes, void* stream);
+int hep_optim_update_device(float* params, const float* grad, float* m, float* v, const float* stats, const uint8_t* kind, int64_t n,
+                            int optimizer, float lr, float beta1, float beta2, float eps, const void* state, void* stream);
+
+/* transformation = cat(rotation head, format_translation(translation head)) - hmdegopose/loss.py:30-51, train.py:39,49 - and the
+ * backward of that map.  rotation [batch][N][num_rotation], translation_raw [batch][N][3], camera [batch][6] = fx, fy, px, py,
+ * tz_scale, image_scale, translation_anchors [N][3] = cx, cy, stride (hep_anchors, on the device):
+ *   x = (cx + raw0 stride) / image_scale - px, y alike, tz = raw2 tz_scale, translation = (x tz / fx, y tz / fy, tz).
+ * pack writes transformation [batch][N][num_rotation + 3] (what hep_losses_device takes); unpack takes its gradient (what
+ * hep_losses_backward_device writes) and writes grad_rotation and grad_translation_raw (two of the cotangents of
+ * hep_heads_backward_device).  NULL, batch < 1, num_anchors < 1 or num_rotation outside 1..8: HEP_ERR_INVALID. */
+int hep_transformation_pack_device(const float* rotation, const float* translation_raw, const float* camera, const float* translation_anchors,
+                                   int batch, int num_anchors, int num_rotation, float* transformation, void* stream);
+int hep_transformation_unpack_grad_device(const float* grad_transformation, const float* translation_raw, const float* camera,
+                                          const float* translation_anchors, int batch, int num_anchors, int num_rotation,
+                                          float* grad_rotation, float* grad_translation_raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
