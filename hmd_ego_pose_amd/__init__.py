@@ -27,7 +27,7 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name == "InflightPool":
         from .pipeline import InflightPool
         return InflightPool
-    if name in ("augment_6dof", "draw_6dof", "rotation_matrices"):
+    if name in ("augment_6dof", "draw_6dof", "rotation_matrices", "colour_augment", "draw_colour", "COLOUR_OPS"):
         from . import augment
         return getattr(augment, name)
     raise AttributeError(name)

@@ -92,6 +92,8 @@ SYMBOLS = {
     "hep_profile_concurrent": (c_int, [_P, c_int, c_int, c_int, _FP]),
     "hep_augment_workspace_bytes": (c_int64, [c_int] * 5),
     "hep_augment_6dof_device": (c_int, [_FP] * 11 + [c_int] * 5 + [c_float] + [_FP] * 8 + [c_void_p, c_int64, c_void_p]),
+    "hep_colour_workspace_bytes": (c_int64, [c_int] * 3),
+    "hep_colour_augment_device": (c_int, [_FP] * 3 + [c_int] * 3 + [_FP, c_void_p, c_int64, c_void_p]),
     "hep_optim_workspace_bytes": (c_int64, [c_int64]),
     "hep_optim_grad_norm_device": (c_int, [_FP, _FP, c_int64, c_int, c_float, c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "hep_optim_update_device": (c_int, [_FP] * 6 + [c_int64, c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p]),

@@ -9,8 +9,14 @@ annotations on the device and leaves the normalised network input, the camera ve
 ``draw_6dof`` draws the random parameters in the reference's order (:329-371), ``rotation_matrices`` computes the forward
 matrices of ``cv2.getRotationMatrix2D`` in float64 on the host; they are uploaded as data, so the kernels and the numpy oracle
 (tests/_augment.py, the definition) see the same doubles.  OpenCV's conventions are restated, not pinned against cv2 (DESIGN.md
-section 7e).  Not reproduced: RandAugment colour operations, the rotation of hand joints (the reference does not rotate
-``coords_3d`` either: pass them to ``anchor_targets_device`` untouched), ``translations_x_y_2D`` (never read downstream).
+section 7e).  Not reproduced: the rotation of hand joints (the reference does not rotate ``coords_3d`` either: pass them to
+``anchor_targets_device`` untouched), ``translations_x_y_2D`` (never read downstream).
+
+The reference's colour augmentation (``RandAugment(n=(1, 3), m=(1, 14))``, generators/randaug.py, common.py:334-341) comes first, on
+the uint8 frames: ``draw_colour`` -> ``colour_augment`` (hep_colour_augment_device, csrc/k_colour.hip) -> ``augment_6dof``.  Its 14
+operations reproduce the numpy oracle tests/_colour.py bit for bit (the noise up to float32 rounding); that oracle is pinned against PIL
+for the ten operations that are PIL's.  Cutout, Invert, the noise and the random stream are restated, not pinned against imgaug
+(DESIGN.md section 7g).
 """
 from __future__ import annotations
 
@@ -183,3 +189,159 @@ def _run(l, frames, masks, d_xform, d_cam_k, ann, num_gt, B, H, W, size, kmax, t
         B, H, W, size, kmax, tsn, out["image"].data_ptr(), _capi.ptr(out.get("mask")), out["camera"].data_ptr(), out["gt_boxes"].data_ptr(),
         out["gt_labels"].data_ptr(), out["gt_transform"].data_ptr(), out["gt_num"].data_ptr(), out["applied"].data_ptr(),
         ws.data_ptr(), ws.numel(), stream))
+
+
+# ---- colour augmentation: the reference's RandAugment (generators/randaug.py:244-279) in front of the 6DoF warp ----
+COLOUR_OPS = ("Identity", "Autocontrast", "Equalize", "Invert", "Posterize", "Solarize", "EnhanceColor", "EnhanceContrast", "EnhanceBrightness",
+              "EnhanceSharpness", "Cutout", "FilterBlur", "FilterSmooth", "AdditiveGaussianNoise")
+COLOUR_SLOTS = 3                      # operations per image (include/hep.h)
+_M_MAX = 30                           # RandAugment._M_MAX
+
+
+def _clip(v, lo, hi):
+    return min(max(v, lo), hi)
+
+
+def colour_parameters(op: int, m: int, height: int, width: int, sign: int = 1, centre=(0.5, 0.5), seed: int = 0):
+    """One operation at magnitude ``m`` -> (i0, i1, i2, i3, seed, f): the formulas of randaug.py:244-279.  Posterize keeps
+    ``8 - min(int(m 6/30), 6)`` bits; Solarize's threshold is ``clip(256 - int(m 256/30), 0, 256)``; the enhance factor is
+    ``clip(1 + sign m 0.9/30, 0.1, 1.9)``; Cutout's square has the side ``clip(m (20/32)/30, 0, 0.625) height`` about
+    ``centre`` = (cx, cy) in [0, 1)^2, clipped to the frame and truncated; the noise has sigma ``(m / 100) 255``."""
+    i, f = [0, 0, 0, 0], 0.0
+    if op == 4:
+        i[0] = 8 - min(int(m * (6 / _M_MAX)), 6)
+    elif op == 5:
+        i[0] = _clip(256 - int(m * (256 / _M_MAX)), 0, 256)
+    elif op in (6, 7, 8, 9):
+        f = _clip(1.0 + sign * m * (0.9 / _M_MAX), 0.1, 1.9)
+    elif op == 10:
+        side = _clip(m * ((20 / 32) / _M_MAX), 0.0, 20 / 32) * height
+        x1 = centre[0] * width - side / 2
+        y1 = centre[1] * height - side / 2
+        i = [int(_clip(x1, 0, width)), int(_clip(y1, 0, height)), int(_clip(x1 + side, 0, width)), int(_clip(y1 + side, 0, height))]
+    elif op == 13:
+        f = (m / 100.0) * 255
+    return i[0], i[1], i[2], i[3], int(seed), f
+
+
+def draw_colour(rng, batch: int, n: Tuple[int, int] = (1, 3), m: Tuple[int, int] = (1, 14), apply=None, height: int = 0, width: int = 0):
+    """The table of ``colour_augment`` for one batch: (ops int32 [B,3,8], args float32 [B,3,2]) as numpy arrays (layout: include/hep.h).
+    ``rng`` needs a ``random()`` in [0, 1); an integer in 0..k-1 is ``int(rng.random() * k)``.  ``apply`` is ``draw_6dof``'s third
+    result (the reference's chance_no_augmentation gates both augmentations, common.py:330-331); None augments every image.
+    Draw order, per image with apply[b] != 0 and nothing for the others: the number of operations n_b in n[0]..n[1]; n_b distinct ids
+    in random order (partial Fisher-Yates over 0..13: for i < n_b, j = i + int(random() (14 - i)), swap); then per operation, in
+    that order, only for the ids that have a magnitude (4-10 and 13): the magnitude in m[0]..m[1], and after it the sign for 6-9
+    (+ when random() < 0.5), the centre cx then cy for 10, the seed's low then high 32 bits for 13.  Same seed, same table.
+    This is the project's stream: imgaug's is not reproduced."""
+    n0, n1, m0, m1 = int(n[0]), int(n[1]), int(m[0]), int(m[1])
+    if not 0 <= n0 <= n1 <= COLOUR_SLOTS:
+        raise ValueError(f"n must satisfy 0 <= n[0] <= n[1] <= {COLOUR_SLOTS}")
+    if not 0 <= m0 <= m1 <= _M_MAX:
+        raise ValueError(f"m must satisfy 0 <= m[0] <= m[1] <= {_M_MAX}")
+    if not (16 <= int(height) <= 4096 and 16 <= int(width) <= 4096):
+        raise ValueError("height and width (of the frames, for Cutout's rectangle) must be in [16, 4096]")
+    apply_h = np.ones(batch, np.int32) if apply is None else np.asarray(apply).reshape(-1)
+    if apply_h.shape[0] != batch:
+        raise ValueError("apply must have one entry per image")
+    ops = np.zeros((batch, COLOUR_SLOTS, 8), np.int32)
+    ops[:, :, 0] = -1
+    args = np.zeros((batch, COLOUR_SLOTS, 2), np.float32)
+    for b in range(batch):
+        if apply_h[b] == 0:
+            continue
+        n_b = n0 + int(rng.random() * (n1 - n0 + 1))
+        ids = list(range(len(COLOUR_OPS)))
+        for i in range(n_b):
+            j = i + int(rng.random() * (len(ids) - i))
+            ids[i], ids[j] = ids[j], ids[i]
+        for k in range(n_b):
+            op, mag, sign, centre, seed = ids[k], 0, 1, (0.5, 0.5), 0
+            if 4 <= op <= 10 or op == 13:
+                mag = m0 + int(rng.random() * (m1 - m0 + 1))
+                if 6 <= op <= 9:
+                    sign = 1 if rng.random() < 0.5 else -1
+                elif op == 10:
+                    cx = rng.random()
+                    centre = (cx, rng.random())
+                elif op == 13:
+                    lo = int(rng.random() * 4294967296.0)
+                    seed = lo | (int(rng.random() * 4294967296.0) << 32)
+            i0, i1, i2, i3, seed, f = colour_parameters(op, mag, int(height), int(width), sign, centre, seed)
+            ops[b, k, :5] = (op, i0, i1, i2, i3)
+            ops[b, k, 5:7] = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint32).view(np.int32)
+            args[b, k, 0] = f
+    return ops, args
+
+
+def check_colour_table(ops, args, batch: int, height: int, width: int):
+    """The host check of ``colour_augment``: (ops int32 [B,3,8], args float32 [B,3,2]) as contiguous numpy arrays, or ValueError."""
+    ops = np.asarray(ops)
+    args = np.asarray(args)
+    if ops.shape != (batch, COLOUR_SLOTS, 8) or not np.issubdtype(ops.dtype, np.integer):
+        raise ValueError(f"ops must be an integer array [{batch}, {COLOUR_SLOTS}, 8]")
+    if args.shape != (batch, COLOUR_SLOTS, 2) or not np.issubdtype(args.dtype, np.floating):
+        raise ValueError(f"args must be a float array [{batch}, {COLOUR_SLOTS}, 2]")
+    ops = np.ascontiguousarray(ops, np.int32)
+    args = np.ascontiguousarray(args, np.float32)
+    f01, f19, f255 = np.float32(0.1), np.float32(1.9), np.float32(255)
+    for b in range(batch):
+        empty = False
+        for k in range(COLOUR_SLOTS):
+            op, i, f = int(ops[b, k, 0]), [int(v) for v in ops[b, k, 1:5]], args[b, k, 0]
+            where = f"image {b} slot {k}"
+            if not -1 <= op < len(COLOUR_OPS):
+                raise ValueError(f"{where}: operation id {op} is not in -1..{len(COLOUR_OPS) - 1}")
+            if op == -1:
+                empty = True
+                continue
+            if empty:
+                raise ValueError(f"{where}: an operation behind an empty slot (slots are filled from the front)")
+            if op == 4 and not 2 <= i[0] <= 8:
+                raise ValueError(f"{where}: Posterize keeps 2..8 bits, not {i[0]}")
+            if op == 5 and not 0 <= i[0] <= 256:
+                raise ValueError(f"{where}: Solarize's threshold must be in 0..256, not {i[0]}")
+            if 6 <= op <= 9 and not f01 <= f <= f19:
+                raise ValueError(f"{where}: the enhance factor must be in [0.1, 1.9], not {f}")
+            if op == 10 and not (0 <= i[0] <= i[2] <= width and 0 <= i[1] <= i[3] <= height):
+                raise ValueError(f"{where}: Cutout's rectangle x1, y1, x2, y2 = {i} is not inside the {width} x {height} frame")
+            if op == 13 and not 0 <= f <= f255:
+                raise ValueError(f"{where}: the noise's sigma must be in [0, 255], not {f}")
+    return ops, args
+
+
+def colour_augment(frames_u8: torch.Tensor, ops, args, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames_u8 uint8 [B,H,W,3] on the device; (ops, args): ``draw_colour``'s table (numpy arrays or CPU tensors).  Returns the
+    augmented frames, uint8 [B,H,W,3] (``out`` when given: same shape, dtype and device, not ``frames_u8``) - what ``augment_6dof``
+    takes.  The table is checked on the host (ids in -1..13, slots filled from the front, 2..8 bits, threshold in 0..256, factor in
+    [0.1, 1.9], sigma in [0, 255], rectangles inside the frame): ValueError before the ABI sees a pointer.  Uploads the two small
+    tables, enqueues on the current stream (at most four launches and a memset) and does not synchronise."""
+    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise ValueError("frames_u8 must be a uint8 ROCm tensor [B,H,W,3]")
+    dev = frames_u8.device
+    B, H, W = (int(v) for v in frames_u8.shape[:3])
+    if B < 1 or not (16 <= H <= 4096 and 16 <= W <= 4096):
+        raise ValueError("frames must be [B >= 1, H, W, 3] with H and W in [16, 4096]")
+    if isinstance(ops, torch.Tensor) or isinstance(args, torch.Tensor):
+        if any(isinstance(t, torch.Tensor) and t.is_cuda for t in (ops, args)):
+            raise ValueError("ops and args must be on the host (they are checked there)")
+        ops = ops.numpy() if isinstance(ops, torch.Tensor) else ops
+        args = args.numpy() if isinstance(args, torch.Tensor) else args
+    ops_h, args_h = check_colour_table(ops, args, B, H, W)
+    frames = frames_u8.contiguous()
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (B, H, W, 3) or not out.is_contiguous()
+          or out.data_ptr() == frames.data_ptr()):
+        raise ValueError(f"out must be a contiguous uint8 tensor {[B, H, W, 3]} on {dev}, and not frames_u8")
+    d_ops = torch.from_numpy(ops_h).to(dev, non_blocking=True)
+    d_args = torch.from_numpy(args_h).to(dev, non_blocking=True)
+    l = _capi.lib()
+    ws = torch.empty((_capi.check(l.hep_colour_workspace_bytes(B, H, W)),), dtype=torch.uint8, device=dev)
+    _run_colour(l, frames, d_ops, d_args, B, H, W, out, ws, dev)
+    return out
+
+
+def _run_colour(l, frames, d_ops, d_args, B, H, W, out, ws, dev):
+    """The ABI call on tensors that passed the checks (tools/colour_time.py and the tests call it with buffers of their own)."""
+    _capi.check(l.hep_colour_augment_device(frames.data_ptr(), d_ops.data_ptr(), d_args.data_ptr(), B, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            torch.cuda.current_stream(dev).cuda_stream))

@@ -1287,6 +1287,43 @@ int hep_augment_6dof_device(const uint8_t* rgb_hwc, const uint8_t* mask, const d
   return 0;
 } HEP_CATCH_INT
 
+// ---- training input: colour augmentation (k_colour.hip) ----
+static int colour_range(int batch, int height, int width) {
+  if (batch < 1) return fail(HEP_ERR_INVALID, "colour: batch must be >= 1");
+  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, "colour: height and width must be in [16, 4096]");
+  if (batch > 65535) return fail(HEP_ERR_UNSUPPORTED, "colour: batch must be at most 65535");
+  return 0;
+}
+static int64_t colour_counter_bytes(int batch) { return ((int64_t)batch * 3 * COL_COUNTERS * 4 + 255) & ~(int64_t)255; }
+static int64_t colour_frame_bytes(int batch, int height, int width) { return ((int64_t)batch * height * width * 3 + 255) & ~(int64_t)255; }
+
+// the counters and the two frames the operations between an image's first and last go through
+int64_t hep_colour_workspace_bytes(int batch, int height, int width) try {
+  if (int rc = colour_range(batch, height, width)) return rc;
+  return colour_counter_bytes(batch) + 2 * colour_frame_bytes(batch, height, width);
+} HEP_CATCH_INT
+
+int hep_colour_augment_device(const uint8_t* rgb_hwc, const int32_t* ops, const float* args, int batch, int height, int width,
+                              uint8_t* out_hwc, void* workspace, int64_t workspace_bytes, void* stream) try {
+  if (!rgb_hwc || !ops || !args) return fail(HEP_ERR_INVALID, "colour: a required input pointer is NULL");
+  if (!out_hwc) return fail(HEP_ERR_INVALID, "colour: the output pointer is NULL");
+  if (!workspace) return fail(HEP_ERR_INVALID, "colour: workspace is NULL");
+  if (out_hwc == rgb_hwc) return fail(HEP_ERR_INVALID, "colour: out_hwc must not be rgb_hwc (the filters read neighbours)");
+  if (int rc = colour_range(batch, height, width)) return rc;
+  if (((uintptr_t)workspace & 15) != 0 || ((uintptr_t)ops & 3) != 0 || ((uintptr_t)args & 3) != 0)
+    return fail(HEP_ERR_INVALID, "colour: workspace must be 16-byte, ops and args 4-byte aligned");
+  if (workspace_bytes < hep_colour_workspace_bytes(batch, height, width)) return fail(HEP_ERR_INVALID, "colour: workspace too small (hep_colour_workspace_bytes)");
+  ColourArgs a;
+  a.rgb = rgb_hwc; a.ops = ops; a.args = args; a.B = batch; a.H = height; a.W = width; a.out = out_hwc;
+  a.counters = (uint32_t*)workspace;
+  a.frame0 = (uint8_t*)workspace + colour_counter_bytes(batch);
+  a.frame1 = a.frame0 + colour_frame_bytes(batch, height, width);
+  HIPRET(hipMemsetAsync(a.counters, 0, (size_t)batch * 3 * COL_COUNTERS * 4, (hipStream_t)stream));
+  launch_colour(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- the training step between the parts: optimiser, gradient norm, translation glue (k_train.hip) ----
 static int optim_check(const char* what, int64_t n, int optimizer, const void* const* ptrs, int count, const void* kind, const void* state) {
   if (n <= 0) return fail(HEP_ERR_INVALID, std::string(what) + ": n must be > 0");

@@ -354,6 +354,16 @@ struct AugmentArgs {
 };
 void launch_augment(const AugmentArgs&, hipStream_t);
 
+// ---- training side: colour augmentation of the generator (generators/randaug.py:244-279, common.py:334-341), k_colour.hip ----
+#define COL_COUNTERS 769      // per image and slot: three 256-bin histograms and the luma sum
+struct ColourArgs {
+  const uint8_t* rgb; const int32_t* ops; const float* args;      // [B][H][W][3] ; [B][3][8] ; [B][3][2]
+  int B, H, W;
+  uint8_t* out;                                                    // [B][H][W][3]
+  uint32_t* counters; uint8_t* frame0; uint8_t* frame1;            // workspace: [B][3][COL_COUNTERS] (zeroed per call) ; two frames
+};
+void launch_colour(const ColourArgs&, hipStream_t);
+
 // ---- training side: optimiser update, gradient norm and the translation glue of the one-call step (k_train.hip) ----
 #define OPT_MAX_BLOCKS 1024   // the fixed grid of the streaming passes: at most this many workgroups, one double partial each
 struct OptimState { float norm, clip_coef, bias1, bias2_sqrt; int32_t step, skipped; int32_t pad[2]; };      // the 32-byte state block of include/hep.h

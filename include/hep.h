@@ -456,7 +456,8 @@ int hep_profile_concurrent(hep_handle* h, int batch, int iters, int nstreams, fl
  * the int32 bilinear weights that sum to 32768, Rodrigues) are restated from its source, cv2 is not available to this project; the
  * definition is the numpy oracle tests/_augment.py, which the kernels reproduce bit for bit (image, mask, boxes, labels, camera).
  * What OpenCV's int16 table does with a weight of 32768 is not restated.  Not reproduced: coords_3d is not touched (the reference
- * does not rotate hand joints), translations_x_y_2D is not produced (anchor_targets_bbox never reads it), colour augmentation.
+ * does not rotate hand joints), translations_x_y_2D is not produced (anchor_targets_bbox never reads it).  The reference's colour augmentation runs BEFORE
+ * this call, on the uint8 frames: hep_colour_augment_device below.
  * Supported: height, width in [16, 4096], size a multiple of 4 in [16, 4096], kmax in 1..16 (HEP_ERR_UNSUPPORTED otherwise, with
  * the reason, before any HIP call); a NULL required pointer, batch < 1, a misaligned image_nchw or a short workspace is
  * HEP_ERR_INVALID.  The scale lives in device memory: the ABI cannot refuse it without a synchronisation, so an out-of-range scale
@@ -470,6 +471,35 @@ int hep_augment_6dof_device(
     float* image_nchw, uint8_t* mask_out, float* camera,
     double* gt_boxes, int32_t* gt_labels, float* gt_transform, int32_t* gt_num, int32_t* applied,
     void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Colour augmentation of the training input (the reference's RandAugment(n=(1, 3), m=(1, 14)), generators/randaug.py:244-279, applied
+ * to the RGB frame in front of the 6DoF augmentation, generators/common.py:334-341), on device memory: up to three operations per image
+ * from a table, at most four launches and one memset of the counters, stateless, no allocation, no host synchronisation; the caller owns
+ * the workspace (hep_colour_workspace_bytes; >= 0, or a negative hep_status; it is at least two frames).
+ * rgb_hwc, out_hwc: uint8 [batch][height][width][3] (out_hwc != rgb_hwc).  ops int32 [batch][3][8]: per slot (id, or -1 for an empty
+ * slot; i0, i1, i2, i3; seed_lo, seed_hi; 0).  args float32 [batch][3][2]: per slot (f or sigma, 0).  An image's operations are its
+ * leading slots up to the first id of -1, applied in order; none: the image is copied.  Ids, in the reference's order:
+ *    0 Identity            1 Autocontrast (cutoff 0)    2 Equalize             3 Invert
+ *    4 Posterize, i0 = bits kept, 2..8                  5 Solarize, i0 = threshold, 0..256 (v < threshold stays, else 255 - v)
+ *    6 EnhanceColor        7 EnhanceContrast            8 EnhanceBrightness    9 EnhanceSharpness: f in [0.1, 1.9], Image.blend of
+ *      the degenerate image (luma; the rounded mean luma; 0; the smoothed image) and the image
+ *   10 Cutout: the rectangle [i1, i3) x [i0, i2) = rows [y1, y2), columns [x1, x2) inside the frame becomes 128
+ *   11 FilterBlur (5 x 5 ring, scale 16, 2-pixel border copied)   12 FilterSmooth (3 x 3, centre 5, scale 13, 1-pixel border copied)
+ *   13 AdditiveGaussianNoise per channel: v + rint(sigma z) clipped, sigma in [0, 255], z from Philox4x32-10 with the slot's 64-bit seed
+ *      as the key and the counter (e / 4, 0, image, slot), e the element index in [height][width][3] order; Box-Muller in float32.
+ * The definition is the numpy oracle tests/_colour.py, which the kernels reproduce bit for bit for ids 0-12; for id 13 an element whose
+ * sigma z lies within 1e-3 of a half-integer may differ by 1 from the oracle's float64 evaluation.  Pinned: tests/test_colour_cpu.py
+ * holds the oracle to PIL with zero differing bytes for ids 1, 2, 4, 5, 6, 7, 8, 9, 11, 12 (imgaug's pillike augmenters call PIL).
+ * PARITY-UNPINNED: imgaug is not available to this project, so Cutout's rectangle convention, Invert and the noise's rounding are
+ * restated, and imgaug's random stream is not reproduced (hmd_ego_pose_amd.augment.draw_colour defines the project's draws).
+ * Supported: height, width in [16, 4096], batch <= 65535 (HEP_ERR_UNSUPPORTED otherwise, with the reason, before any HIP call); a NULL
+ * pointer, batch < 1, out_hwc == rgb_hwc, a workspace that is short or not 16-byte aligned: HEP_ERR_INVALID.  The table lives in device
+ * memory: the ABI cannot refuse it without a synchronisation, so a slot with an unknown id or an out-of-range argument runs as
+ * Identity (hmd_ego_pose_amd.augment.colour_augment refuses it on the host). */
+int64_t hep_colour_workspace_bytes(int batch, int height, int width);
+int hep_colour_augment_device(
+    const uint8_t* rgb_hwc, const int32_t* ops, const float* args, int batch, int height, int width,
+    uint8_t* out_hwc, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The training step between the parts (csrc/k_train.hip): the optimiser, the gradient norm and the translation glue over the flat
  * buffers of the hep_{backbone,neck,heads}_*_device_bn calls, so that one object can own params | grad | stats for the whole model
