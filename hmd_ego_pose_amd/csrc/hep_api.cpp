@@ -1,6 +1,7 @@
-// hep_api.cpp - the C ABI of libhep.so (include/hep.h) and the forward executor:
+// hep_api.cpp - the session side of the C ABI of libhep.so (include/hep.h) and the forward executor:
 // eager stem launch (it reads the caller's input pointer) + one captured hipGraph for
-// everything behind it, replayed on the caller's stream.
+// everything behind it, replayed on the caller's stream.  The entry points that take no handle - the stateless
+// training side - are in hep_api_train.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,30 +13,14 @@
 #include <memory>
 
 #include "hep.h"
+#include "hep_api_util.h"
 #include "hep_plan.h"
 
 using namespace hep;
 
+thread_local std::string hep::g_err;      // the message behind hep_last_error(): the one definition (hep_api_util.h)
+
 struct hep_handle { Session s; };
-
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPRET(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(HEP_ERR_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-
-// Nothing may leave an entry point as a C++ exception (include/hep.h: "never throws"; the C# host P/Invokes these symbols, and
-// ONNXRuntime - the library this one replaces - reports failures through its API, Program.cs:59-61).  Every extern "C" function
-// is a function-try-block ending in one of these handlers: std::bad_alloc / length_error from a hostile weight pack, a vector
-// that outgrew memory, anything else -> HEP_ERR_INTERNAL and a message in hep_last_error().
-static int hep_caught() noexcept {
-  try { throw; }
-  catch (const std::bad_alloc&) { try { g_err = "out of host memory (std::bad_alloc)"; } catch (...) {} }
-  catch (const std::exception& e) { try { g_err = std::string("internal error: ") + e.what(); } catch (...) {} }
-  catch (...) { try { g_err = "internal error: unknown C++ exception"; } catch (...) {} }
-  return HEP_ERR_INTERNAL;
-}
-#define HEP_CATCH_INT catch (...) { return hep_caught(); }
-#define HEP_CATCH_VOID catch (...) { hep_caught(); }
 
 namespace hep {
 
@@ -650,344 +635,6 @@ int hep_pose_errors(int device, const float* points, int num_points, const float
   return 0;
 } HEP_CATCH_INT
 
-// ---- training side ----
-int hep_anchor_targets_device(const float* anchors, int num_anchors, const double* gt_boxes, const int32_t* gt_labels,
-                              const float* gt_transform, const float* gt_coords, const int32_t* num_gt, const int32_t* image_hw,
-                              int batch, int kmax, int num_classes, int num_transform, double negative_overlap, double positive_overlap,
-                              float* labels, float* regression, float* transformation, float* coords, void* stream) try {
-  if (!anchors || !gt_boxes || !gt_labels || !gt_transform || !num_gt || !image_hw || !labels || !regression || !transformation)
-    return fail(HEP_ERR_INVALID, "bad argument");
-  if (num_anchors < 1 || batch < 1 || num_classes < 1 || num_transform < 0) return fail(HEP_ERR_INVALID, "bad size");
-  if (kmax < 1 || kmax > AT_MAX_GT) return fail(HEP_ERR_UNSUPPORTED, "kmax must be in 1..64 ground-truth boxes per image");
-  AnchorTargetArgs a; a.anchors = anchors; a.N = num_anchors; a.gt_boxes = gt_boxes; a.gt_labels = gt_labels; a.gt_transform = gt_transform;
-  a.gt_coords = gt_coords; a.num_gt = num_gt; a.image_hw = image_hw; a.B = batch; a.kmax = kmax; a.num_classes = num_classes; a.rt = num_transform;
-  a.negative_overlap = negative_overlap; a.positive_overlap = positive_overlap;
-  a.labels = labels; a.regression = regression; a.transformation = transformation; a.coords = coords;
-  launch_anchor_targets(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_losses_device(const float* gt_classification, const float* classification, const float* gt_regression, const float* regression,
-                      const float* gt_transformation, const float* transformation, const float* gt_hand, const float* hand,
-                      const float* model_points, int batch, int num_anchors, int num_classes, int num_rotation, int num_hand,
-                      int num_model_classes, int num_points, float* per_image, float* losses, void* stream) try {
-  if (!gt_classification || !classification || !gt_regression || !regression || !gt_transformation || !transformation || !model_points ||
-      !per_image || !losses) return fail(HEP_ERR_INVALID, "bad argument");
-  if ((gt_hand == nullptr) != (hand == nullptr)) return fail(HEP_ERR_INVALID, "gt_hand and hand go together");
-  if (batch < 1 || num_anchors < 1 || num_classes < 1 || num_rotation != 3 || num_hand < 0 || num_model_classes < 1) return fail(HEP_ERR_INVALID, "bad size");
-  if (num_points < 1 || num_points > LOSS_MAX_POINTS) return fail(HEP_ERR_UNSUPPORTED, "num_points must be in 1..2048 model points per class");
-  LossArgs a; a.gt_cls = gt_classification; a.cls = classification; a.gt_reg = gt_regression; a.reg = regression; a.gt_tr = gt_transformation;
-  a.tr = transformation; a.gt_hand = gt_hand; a.hand = hand; a.points = model_points; a.B = batch; a.N = num_anchors; a.K = num_classes;
-  a.R = num_rotation; a.H = num_hand; a.classes = num_model_classes; a.P = num_points; a.per_image = per_image; a.losses = losses;
-  launch_losses(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_losses_backward_device(const float* gt_classification, const float* classification, const float* gt_regression, const float* regression,
-                               const float* gt_transformation, const float* transformation, const float* gt_hand, const float* hand,
-                               const float* model_points, int batch, int num_anchors, int num_classes, int num_rotation, int num_hand,
-                               int num_model_classes, int num_points, const float* grad_per_image, float* grad_classification,
-                               float* grad_regression, float* grad_transformation, float* grad_hand, int32_t* workspace, void* stream) try {
-  if (!gt_classification || !classification || !gt_regression || !regression || !gt_transformation || !transformation || !model_points ||
-      !grad_per_image || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  if ((gt_hand == nullptr) != (hand == nullptr)) return fail(HEP_ERR_INVALID, "gt_hand and hand go together");
-  if (grad_hand && !hand) return fail(HEP_ERR_INVALID, "grad_hand needs hand");
-  if (batch < 1 || num_anchors < 1 || num_classes < 1 || num_rotation != 3 || num_hand < 0 || num_model_classes < 1) return fail(HEP_ERR_INVALID, "bad size");
-  if (grad_hand && num_hand < 1) return fail(HEP_ERR_INVALID, "grad_hand needs num_hand >= 1");
-  if (num_points < 1 || num_points > LOSS_MAX_POINTS) return fail(HEP_ERR_UNSUPPORTED, "num_points must be in 1..2048 model points per class");
-  LossGradArgs g;
-  LossArgs& a = g.f;
-  a.gt_cls = gt_classification; a.cls = classification; a.gt_reg = gt_regression; a.reg = regression; a.gt_tr = gt_transformation;
-  a.tr = transformation; a.gt_hand = gt_hand; a.hand = hand; a.points = model_points; a.B = batch; a.N = num_anchors; a.K = num_classes;
-  a.R = num_rotation; a.H = num_hand; a.classes = num_model_classes; a.P = num_points; a.per_image = nullptr; a.losses = nullptr;
-  g.u = grad_per_image; g.g_cls = grad_classification; g.g_reg = grad_regression; g.g_tr = grad_transformation; g.g_hand = grad_hand;
-  g.ws = workspace;
-  launch_losses_backward(g, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// ---- training side: the five head nets, forward and backward (k_head_grad.hip) ----
-int64_t hep_heads_param_count(int phi, int num_classes) try {
-  HGPlan p; const char* why = "";
-  if (int rc = heads_plan(phi, num_classes, 0, 0, &p, &why)) return fail(rc, why);
-  return p.nparams;
-} HEP_CATCH_INT
-
-int hep_heads_param_layout(int phi, int num_classes, int64_t* offsets, int capacity) try {
-  HGPlan p; const char* why = "";
-  if (int rc = heads_plan(phi, num_classes, 0, 0, &p, &why)) return fail(rc, why);
-  const int W = p.g.W, D = p.g.D, count = HG_NETS * (3 * D + 5 * D * 4) + HG_SLOTS * 3;
-  if (!offsets) return count;
-  if (capacity < count) return fail(HEP_ERR_INVALID, "hep_heads_param_layout: capacity is smaller than the number of head tensors");
-  int k = 0;
-  for (int n = 0; n < HG_NETS; n++) {
-    for (int i = 0; i < D; i++) {
-      const int64_t c = p.p_conv[n] + (int64_t)i * (9 * W + W * W + W);
-      offsets[k++] = c; offsets[k++] = c + 9 * W; offsets[k++] = c + 9 * W + (int64_t)W * W;
-    }
-    for (int j = 0; j < 5 * D * 4; j++) offsets[k++] = p.p_bn[n] + (int64_t)j * W;
-    for (int h = 0; h < HG_SLOTS; h++)
-      if (p.net[h] == n) { offsets[k++] = p.p_hdr[h]; offsets[k++] = p.p_hdr[h] + 9 * W; offsets[k++] = p.p_hdr[h] + 9 * W + (int64_t)p.C[h] * W; }
-  }
-  return count;
-} HEP_CATCH_INT
-
-int64_t hep_heads_workspace_bytes_bn(int phi, int num_classes, int size, int batch, int bn_mode) try {
-  HGPlan p; const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, "heads: size must be a multiple of 128 in [128, 2048]");
-  if (int rc = heads_plan(phi, num_classes, size, batch, &p, &why, bn_mode)) return fail(rc, why);
-  return p.ws_floats * (int64_t)sizeof(float);
-} HEP_CATCH_INT
-
-int64_t hep_heads_workspace_bytes(int phi, int num_classes, int size, int batch) try {
-  return hep_heads_workspace_bytes_bn(phi, num_classes, size, batch, HEP_BN_RUNNING);
-} HEP_CATCH_INT
-
-static int heads_check(int phi, int num_classes, int size, int batch, int bn_mode, const void* workspace, size_t workspace_bytes, HGPlan* p) {
-  const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, "heads: size must be a multiple of 128 in [128, 2048]");
-  if (int rc = heads_plan(phi, num_classes, size, batch, p, &why, bn_mode)) return fail(rc, why);
-  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "heads: the workspace must be 16-byte aligned");
-  if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "heads: the workspace is smaller than hep_heads_workspace_bytes");
-  return 0;
-}
-
-int hep_heads_forward_device_bn(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
-                                float* const outs[5], void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out,
-                                void* stream) try {
-  if (!params || !feats || !outs || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 5; i++) if (!feats[i] || !outs[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
-  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, "heads: the BatchNorm momentum must be in [0, 1]");
-  HGPlan p;
-  if (int rc = heads_check(phi, num_classes, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
-  launch_heads_forward(p, params, feats, outs, (float*)workspace, (hipStream_t)stream, momentum, stats_out);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_heads_forward_device(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
-                             float* const outs[5], void* workspace, size_t workspace_bytes, void* stream) try {
-  return hep_heads_forward_device_bn(params, feats, phi, num_classes, size, batch, outs, workspace, workspace_bytes, HEP_BN_RUNNING, 0.0f, nullptr, stream);
-} HEP_CATCH_INT
-
-int hep_heads_backward_device_bn(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
-                                 float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, int bn_mode,
-                                 void* stream) try {
-  if (!params || !grad_outs || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 5; i++) if (!grad_outs[i] || (grad_feats && !grad_feats[i])) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
-  HGPlan p;
-  if (int rc = heads_check(phi, num_classes, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
-  launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, (float*)workspace, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_heads_backward_device(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
-                              float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream) try {
-  return hep_heads_backward_device_bn(params, grad_outs, phi, num_classes, size, batch, grad_params, grad_feats, workspace, workspace_bytes,
-                                      HEP_BN_RUNNING, stream);
-} HEP_CATCH_INT
-
-// ---- training side: the BiFPN neck, forward and backward (k_neck_grad.hip) ----
-int64_t hep_neck_param_count(int phi) try {
-  NGPlan p; const char* why = "";
-  if (int rc = neck_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
-  return p.nparams;
-} HEP_CATCH_INT
-
-int hep_neck_param_layout(int phi, int64_t* offsets, int capacity) try {
-  NGPlan p; const char* why = "";
-  if (int rc = neck_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
-  const int W = p.W, count = p.cells * (8 + NG_NODES * 7) + NG_LATERALS * 6;
-  if (!offsets) return count;
-  if (capacity < count) return fail(HEP_ERR_INVALID, "hep_neck_param_layout: capacity is smaller than the number of neck tensors");
-  static const int fusion[8] = {2, 2, 2, 2, 3, 3, 3, 2};
-  int k = 0;
-  for (int r = 0; r < p.cells; r++) {
-    int64_t o = p.p_cell[r];
-    for (int f = 0; f < 8; f++) { offsets[k++] = o; o += fusion[f]; }
-    for (int j = 0; j < NG_NODES; j++) {
-      offsets[k++] = o; o += 9 * W;
-      offsets[k++] = o; o += (int64_t)W * W;
-      for (int t = 0; t < 5; t++) { offsets[k++] = o; o += W; }
-    }
-    if (r == 0)
-      for (int i = 0; i < NG_LATERALS; i++) {
-        o = p.p_lat[i];
-        offsets[k++] = o; o += (i + 1 < NG_LATERALS ? p.p_lat[i + 1] : p.p_cell[1]) - p.p_lat[i] - 5 * W;
-        for (int t = 0; t < 5; t++) { offsets[k++] = o; o += W; }
-      }
-  }
-  return count;
-} HEP_CATCH_INT
-
-static const char* kNeckSize = "neck: size must be a multiple of 128 in [128, 2048]";
-int64_t hep_neck_workspace_bytes_bn(int phi, int size, int batch, int bn_mode) try {
-  NGPlan p; const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
-  if (int rc = neck_plan(phi, size, batch, &p, &why, bn_mode)) return fail(rc, why);
-  return p.ws_floats * (int64_t)sizeof(float);
-} HEP_CATCH_INT
-
-int64_t hep_neck_workspace_bytes(int phi, int size, int batch) try { return hep_neck_workspace_bytes_bn(phi, size, batch, HEP_BN_RUNNING); } HEP_CATCH_INT
-
-static int neck_check(int phi, int size, int batch, int bn_mode, const void* workspace, size_t workspace_bytes, NGPlan* p) {
-  const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
-  if (int rc = neck_plan(phi, size, batch, p, &why, bn_mode)) return fail(rc, why);
-  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "neck: the workspace must be 16-byte aligned");
-  if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "neck: the workspace is smaller than hep_neck_workspace_bytes");
-  return 0;
-}
-
-int hep_neck_forward_device_bn(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
-                               void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out, void* stream) try {
-  if (!params || !taps || !feats || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 3; i++) if (!taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 5; i++) if (!feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, "neck: the BatchNorm momentum must be in [0, 1]");
-  NGPlan p;
-  if (int rc = neck_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
-  launch_neck_forward(p, params, taps, feats, (float*)workspace, (hipStream_t)stream, momentum, stats_out);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_neck_forward_device(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
-                            void* workspace, size_t workspace_bytes, void* stream) try {
-  return hep_neck_forward_device_bn(params, taps, phi, size, batch, feats, workspace, workspace_bytes, HEP_BN_RUNNING, 0.0f, nullptr, stream);
-} HEP_CATCH_INT
-
-int hep_neck_backward_device_bn(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
-                                float* const grad_taps[3], void* workspace, size_t workspace_bytes, int bn_mode, void* stream) try {
-  if (!params || !grad_feats || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 5; i++) if (!grad_feats[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 3; i++) if (grad_taps && !grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  NGPlan p;
-  if (int rc = neck_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
-  launch_neck_backward(p, grad_feats, grad_params, grad_taps, (float*)workspace, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_neck_backward_device(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
-                             float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream) try {
-  return hep_neck_backward_device_bn(params, grad_feats, phi, size, batch, grad_params, grad_taps, workspace, workspace_bytes, HEP_BN_RUNNING, stream);
-} HEP_CATCH_INT
-
-int hep_neck_stage_count(int phi) try {
-  NGPlan p; const char* why = "";
-  if (int rc = neck_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
-  return neck_stage_count(p);
-} HEP_CATCH_INT
-
-int hep_neck_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes) try {
-  NGPlan p; const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kNeckSize);
-  if (int rc = neck_plan(phi, size, batch, &p, &why)) return fail(rc, why);
-  static thread_local char buf[32];
-  int level = 0; int64_t off = 0;
-  if (neck_stage(p, i, buf, &level, &off)) return fail(HEP_ERR_INVALID, "bad stage index");
-  if (name) *name = buf;
-  if (dims) { dims[0] = p.B; dims[1] = p.s[level]; dims[2] = p.s[level]; dims[3] = p.W; }
-  if (offset_bytes) *offset_bytes = off * (int64_t)sizeof(float);
-  return 0;
-} HEP_CATCH_INT
-
-// ---- training side: the EfficientNet trunk, forward and backward (k_backbone_grad.hip) ----
-int64_t hep_backbone_param_count(int phi) try {
-  BGPlan p; const char* why = "";
-  if (int rc = backbone_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
-  return p.nparams;
-} HEP_CATCH_INT
-
-int hep_backbone_param_layout(int phi, int64_t* offsets, int capacity) try {
-  BGPlan p; const char* why = "";
-  if (int rc = backbone_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
-  const int count = backbone_tensor_count(p);
-  if (!offsets) return count;
-  if (capacity < count) return fail(HEP_ERR_INVALID, "hep_backbone_param_layout: capacity is smaller than the number of backbone tensors");
-  backbone_tensor_offsets(p, offsets);
-  return count;
-} HEP_CATCH_INT
-
-static const char* kBackboneSize = "backbone: size must be a multiple of 128 in [128, 2048]";
-int64_t hep_backbone_workspace_bytes_bn(int phi, int size, int batch, int bn_mode) try {
-  BGPlan p; const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
-  if (int rc = backbone_plan(phi, size, batch, &p, &why, bn_mode)) return fail(rc, why);
-  return p.ws_floats * (int64_t)sizeof(float);
-} HEP_CATCH_INT
-
-int64_t hep_backbone_workspace_bytes(int phi, int size, int batch) try { return hep_backbone_workspace_bytes_bn(phi, size, batch, HEP_BN_RUNNING); } HEP_CATCH_INT
-
-static int backbone_check(int phi, int size, int batch, int bn_mode, const void* workspace, size_t workspace_bytes, BGPlan* p) {
-  const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
-  if (int rc = backbone_plan(phi, size, batch, p, &why, bn_mode)) return fail(rc, why);
-  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "backbone: the workspace must be 16-byte aligned");
-  if (workspace_bytes < (size_t)p->ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, "backbone: the workspace is smaller than hep_backbone_workspace_bytes");
-  return 0;
-}
-
-int hep_backbone_forward_device_bn(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
-                                   void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out, void* stream) try {
-  if (!params || !image || !taps || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 3; i++) if (!taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, "backbone: the BatchNorm momentum must be in [0, 1]");
-  static thread_local BGPlan p;
-  if (int rc = backbone_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
-  launch_backbone_forward(p, params, image, branch_scale, taps, (float*)workspace, (hipStream_t)stream, momentum, stats_out);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_backbone_forward_device(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
-                                void* workspace, size_t workspace_bytes, void* stream) try {
-  return hep_backbone_forward_device_bn(params, image, branch_scale, phi, size, batch, taps, workspace, workspace_bytes, HEP_BN_RUNNING, 0.0f, nullptr, stream);
-} HEP_CATCH_INT
-
-int hep_backbone_backward_device_bn(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
-                                    float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, int bn_mode, void* stream) try {
-  if (!params || !grad_taps || !grad_params || !workspace) return fail(HEP_ERR_INVALID, "bad argument");
-  for (int i = 0; i < 3; i++) if (!grad_taps[i]) return fail(HEP_ERR_INVALID, "bad argument");
-  static thread_local BGPlan p;
-  if (int rc = backbone_check(phi, size, batch, bn_mode, workspace, workspace_bytes, &p)) return rc;
-  launch_backbone_backward(p, grad_taps, branch_scale, grad_params, grad_image, (float*)workspace, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_backbone_backward_device(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
-                                 float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, void* stream) try {
-  return hep_backbone_backward_device_bn(params, grad_taps, branch_scale, phi, size, batch, grad_params, grad_image, workspace, workspace_bytes,
-                                         HEP_BN_RUNNING, stream);
-} HEP_CATCH_INT
-
-int hep_backbone_stage_count(int phi) try {
-  static thread_local BGPlan p; const char* why = "";
-  if (int rc = backbone_plan(phi, 0, 0, &p, &why)) return fail(rc, why);
-  return backbone_stage_count(p);
-} HEP_CATCH_INT
-
-int hep_backbone_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes) try {
-  static thread_local BGPlan p; const char* why = "";
-  if (size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, kBackboneSize);
-  if (int rc = backbone_plan(phi, size, batch, &p, &why)) return fail(rc, why);
-  static thread_local char buf[32];
-  int side = 0, channels = 0; int64_t off = 0;
-  if (backbone_stage(p, i, buf, &side, &channels, &off)) return fail(HEP_ERR_INVALID, "bad stage index");
-  if (name) *name = buf;
-  if (dims) { dims[0] = p.B; dims[1] = side; dims[2] = side; dims[3] = channels; }
-  if (offset_bytes) *offset_bytes = off * (int64_t)sizeof(float);
-  return 0;
-} HEP_CATCH_INT
-
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {
@@ -1229,174 +876,6 @@ int hep_profile_concurrent(hep_handle* h, int batch, int iters, int nstreams, fl
       if (rep) per_kernel_ms[k] = (float)(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (double)std::max(1L, issued));      // per launch ISSUED
     }
   }
-  return 0;
-} HEP_CATCH_INT
-
-// ---- training input: 6DoF augmentation + preprocess (k_augment.hip) ----
-static int augment_range(int batch, int height, int width, int size, int kmax) {
-  if (batch < 1) return fail(HEP_ERR_INVALID, "augment: batch must be >= 1");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, "augment: height and width must be in [16, 4096]");
-  if (size < 16 || size > 4096 || size % 4 != 0) return fail(HEP_ERR_UNSUPPORTED, "augment: size must be a multiple of 4 in [16, 4096]");
-  if (kmax < 1 || kmax > AUG_MAX_K) return fail(HEP_ERR_UNSUPPORTED, "augment: kmax must be in 1..16 annotations per image");
-  return 0;
-}
-static int64_t augment_partial_bytes(int batch, int height, int kmax) {
-  const int64_t tiles = (height + AUG_TILE_ROWS - 1) / AUG_TILE_ROWS;
-  return ((int64_t)batch * tiles * (4 * kmax + 1) * 4 + 255) & ~(int64_t)255;
-}
-
-// the box partials and the uint8 frame of the resize launch (counted whether or not this size needs it: the figure never shrinks as an argument grows)
-int64_t hep_augment_workspace_bytes(int batch, int height, int width, int size, int kmax) try {
-  if (int rc = augment_range(batch, height, width, size, kmax)) return rc;
-  return augment_partial_bytes(batch, height, kmax) + (((int64_t)batch * height * width * 3 + 255) & ~(int64_t)255);
-} HEP_CATCH_INT
-
-int hep_augment_6dof_device(const uint8_t* rgb_hwc, const uint8_t* mask, const double* xform, const float* camera_k, const double* boxes,
-                            const int32_t* labels, const int32_t* mask_values, const float* rvec, const float* tvec, const float* extra,
-                            const int32_t* num_gt, int batch, int height, int width, int size, int kmax, float translation_scale_norm,
-                            float* image_nchw, uint8_t* mask_out, float* camera, double* gt_boxes, int32_t* gt_labels, float* gt_transform,
-                            int32_t* gt_num, int32_t* applied, void* workspace, int64_t workspace_bytes, void* stream) try {
-  if (!rgb_hwc || !mask || !xform || !camera_k || !boxes || !labels || !mask_values || !rvec || !tvec || !extra || !num_gt)
-    return fail(HEP_ERR_INVALID, "augment: a required input pointer is NULL");
-  if (!image_nchw || !camera || !gt_boxes || !gt_labels || !gt_transform || !gt_num || !applied)
-    return fail(HEP_ERR_INVALID, "augment: a required output pointer is NULL (only mask_out may be)");
-  if (!workspace) return fail(HEP_ERR_INVALID, "augment: workspace is NULL");
-  if (int rc = augment_range(batch, height, width, size, kmax)) return rc;
-  if (((uintptr_t)image_nchw & 15) != 0 || ((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "augment: image_nchw and workspace must be 16-byte aligned");
-  const int64_t need = hep_augment_workspace_bytes(batch, height, width, size, kmax);
-  if (workspace_bytes < need) return fail(HEP_ERR_INVALID, "augment: workspace too small (hep_augment_workspace_bytes)");
-  AugmentArgs a;
-  a.rgb = rgb_hwc; a.mask = mask; a.xform = xform; a.camera_k = camera_k; a.boxes = boxes; a.labels = labels; a.mask_values = mask_values;
-  a.rvec = rvec; a.tvec = tvec; a.extra = extra; a.num_gt = num_gt;
-  a.B = batch; a.H = height; a.W = width; a.S = size; a.kmax = kmax; a.tiles = (height + AUG_TILE_ROWS - 1) / AUG_TILE_ROWS;
-  a.tsn = translation_scale_norm;
-  // preprocess_image (common.py:576-607), as hep_preprocess_u8_device: the longer side becomes size, the other int(side * scale)
-  const int side = std::max(height, width);
-  a.resize = side != size;
-  a.image_scale = (double)size / side;
-  a.nh = height > width ? size : (int)(height * a.image_scale);
-  a.nw = height > width ? (int)(width * a.image_scale) : size;
-  if (!a.resize) { a.nh = height; a.nw = width; }
-  if (a.nh > size || a.nw > size || a.nh < 1 || a.nw < 1) return fail(HEP_ERR_UNSUPPORTED, "augment: resized frame does not fit the network size");
-  a.inv_scale_x = (double)width / a.nw; a.inv_scale_y = (double)height / a.nh;
-  a.image = image_nchw; a.mask_out = mask_out; a.camera = camera; a.gt_boxes = gt_boxes; a.gt_labels = gt_labels; a.gt_transform = gt_transform;
-  a.gt_num = gt_num; a.applied = applied;
-  a.partials = (int32_t*)workspace; a.frame_u8 = (uint8_t*)workspace + augment_partial_bytes(batch, height, kmax);
-  launch_augment(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// ---- training input: colour augmentation (k_colour.hip) ----
-static int colour_range(int batch, int height, int width) {
-  if (batch < 1) return fail(HEP_ERR_INVALID, "colour: batch must be >= 1");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, "colour: height and width must be in [16, 4096]");
-  if (batch > 65535) return fail(HEP_ERR_UNSUPPORTED, "colour: batch must be at most 65535");
-  return 0;
-}
-static int64_t colour_counter_bytes(int batch) { return ((int64_t)batch * 3 * COL_COUNTERS * 4 + 255) & ~(int64_t)255; }
-static int64_t colour_frame_bytes(int batch, int height, int width) { return ((int64_t)batch * height * width * 3 + 255) & ~(int64_t)255; }
-
-// the counters and the two frames the operations between an image's first and last go through
-int64_t hep_colour_workspace_bytes(int batch, int height, int width) try {
-  if (int rc = colour_range(batch, height, width)) return rc;
-  return colour_counter_bytes(batch) + 2 * colour_frame_bytes(batch, height, width);
-} HEP_CATCH_INT
-
-int hep_colour_augment_device(const uint8_t* rgb_hwc, const int32_t* ops, const float* args, int batch, int height, int width,
-                              uint8_t* out_hwc, void* workspace, int64_t workspace_bytes, void* stream) try {
-  if (!rgb_hwc || !ops || !args) return fail(HEP_ERR_INVALID, "colour: a required input pointer is NULL");
-  if (!out_hwc) return fail(HEP_ERR_INVALID, "colour: the output pointer is NULL");
-  if (!workspace) return fail(HEP_ERR_INVALID, "colour: workspace is NULL");
-  if (out_hwc == rgb_hwc) return fail(HEP_ERR_INVALID, "colour: out_hwc must not be rgb_hwc (the filters read neighbours)");
-  if (int rc = colour_range(batch, height, width)) return rc;
-  if (((uintptr_t)workspace & 15) != 0 || ((uintptr_t)ops & 3) != 0 || ((uintptr_t)args & 3) != 0)
-    return fail(HEP_ERR_INVALID, "colour: workspace must be 16-byte, ops and args 4-byte aligned");
-  if (workspace_bytes < hep_colour_workspace_bytes(batch, height, width)) return fail(HEP_ERR_INVALID, "colour: workspace too small (hep_colour_workspace_bytes)");
-  ColourArgs a;
-  a.rgb = rgb_hwc; a.ops = ops; a.args = args; a.B = batch; a.H = height; a.W = width; a.out = out_hwc;
-  a.counters = (uint32_t*)workspace;
-  a.frame0 = (uint8_t*)workspace + colour_counter_bytes(batch);
-  a.frame1 = a.frame0 + colour_frame_bytes(batch, height, width);
-  HIPRET(hipMemsetAsync(a.counters, 0, (size_t)batch * 3 * COL_COUNTERS * 4, (hipStream_t)stream));
-  launch_colour(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// ---- the training step between the parts: optimiser, gradient norm, translation glue (k_train.hip) ----
-static int optim_check(const char* what, int64_t n, int optimizer, const void* const* ptrs, int count, const void* kind, const void* state) {
-  if (n <= 0) return fail(HEP_ERR_INVALID, std::string(what) + ": n must be > 0");
-  if (!kind || !state) return fail(HEP_ERR_INVALID, std::string(what) + ": kind or state is NULL");
-  for (int i = 0; i < count; i++) {
-    if (!ptrs[i]) return fail(HEP_ERR_INVALID, std::string(what) + ": a required pointer is NULL");
-    if (((uintptr_t)ptrs[i] & 15) != 0) return fail(HEP_ERR_INVALID, std::string(what) + ": the float buffers must be 16-byte aligned");
-  }
-  if (((uintptr_t)kind & 3) != 0 || ((uintptr_t)state & 15) != 0) return fail(HEP_ERR_INVALID, std::string(what) + ": kind must be 4-byte, state 16-byte aligned");
-  if (optimizer != HEP_OPT_ADAM && optimizer != HEP_OPT_SGD_NESTEROV)
-    return fail(HEP_ERR_UNSUPPORTED, std::string(what) + ": optimizer " + std::to_string(optimizer) + " is not built (HEP_OPT_ADAM = 0, HEP_OPT_SGD_NESTEROV = 1)");
-  return 0;
-}
-
-int64_t hep_optim_workspace_bytes(int64_t n) try {
-  if (n <= 0) return fail(HEP_ERR_INVALID, "optim: n must be > 0");
-  return ((int64_t)optim_grid(n) * 8 + 15) & ~(int64_t)15;
-} HEP_CATCH_INT
-
-int hep_optim_grad_norm_device(const float* grad, const uint8_t* kind, int64_t n, int optimizer, float beta1, float beta2, float max_norm,
-                               void* state, void* workspace, size_t workspace_bytes, void* stream) try {
-  const void* ptrs[2] = {grad, workspace};
-  if (int rc = optim_check("optim_grad_norm", n, optimizer, ptrs, 2, kind, state)) return rc;
-  if ((int64_t)workspace_bytes < hep_optim_workspace_bytes(n)) return fail(HEP_ERR_INVALID, "optim_grad_norm: workspace too small (hep_optim_workspace_bytes)");
-  OptimArgs a{};
-  a.grad = grad; a.kind = kind; a.n = n; a.optimizer = optimizer; a.blocks = optim_grid(n); a.beta1 = beta1; a.beta2 = beta2; a.max_norm = max_norm;
-  a.state = (OptimState*)state; a.partials = (double*)workspace;
-  launch_optim_norm(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_optim_update_device(float* params, const float* grad, float* m, float* v, const float* stats, const uint8_t* kind, int64_t n,
-                            int optimizer, float lr, float beta1, float beta2, float eps, const void* state, void* stream) try {
-  const void* ptrs[4] = {params, grad, m, v};
-  if (int rc = optim_check("optim_update", n, optimizer, ptrs, optimizer == HEP_OPT_SGD_NESTEROV && !v ? 3 : 4, kind, state)) return rc;
-  if (stats && ((uintptr_t)stats & 15) != 0) return fail(HEP_ERR_INVALID, "optim_update: the float buffers must be 16-byte aligned");
-  OptimArgs a{};
-  a.params = params; a.grad = grad; a.m = m; a.v = v; a.stats = stats; a.kind = kind; a.n = n; a.optimizer = optimizer; a.blocks = optim_grid(n);
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.state = (OptimState*)state;
-  launch_optim_update(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-static int transform_check(const char* what, int batch, int num_anchors, int num_rotation) {
-  if (batch < 1 || num_anchors < 1 || num_rotation < 1 || num_rotation > 8) return fail(HEP_ERR_INVALID, std::string(what) + ": bad size");
-  return 0;
-}
-
-int hep_transformation_pack_device(const float* rotation, const float* translation_raw, const float* camera, const float* translation_anchors,
-                                   int batch, int num_anchors, int num_rotation, float* transformation, void* stream) try {
-  if (!rotation || !translation_raw || !camera || !translation_anchors || !transformation) return fail(HEP_ERR_INVALID, "transformation_pack: a pointer is NULL");
-  if (int rc = transform_check("transformation_pack", batch, num_anchors, num_rotation)) return rc;
-  TransformArgs a{};
-  a.rotation = rotation; a.raw = translation_raw; a.camera = camera; a.anchors = translation_anchors; a.transformation = transformation;
-  a.B = batch; a.N = num_anchors; a.R = num_rotation;
-  launch_transformation_pack(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_transformation_unpack_grad_device(const float* grad_transformation, const float* translation_raw, const float* camera,
-                                          const float* translation_anchors, int batch, int num_anchors, int num_rotation,
-                                          float* grad_rotation, float* grad_translation_raw, void* stream) try {
-  if (!grad_transformation || !translation_raw || !camera || !translation_anchors || !grad_rotation || !grad_translation_raw)
-    return fail(HEP_ERR_INVALID, "transformation_unpack_grad: a pointer is NULL");
-  if (int rc = transform_check("transformation_unpack_grad", batch, num_anchors, num_rotation)) return rc;
-  TransformArgs a{};
-  a.transformation = const_cast<float*>(grad_transformation); a.raw = translation_raw; a.camera = camera; a.anchors = translation_anchors;
-  a.g_rotation = grad_rotation; a.g_raw = grad_translation_raw; a.B = batch; a.N = num_anchors; a.R = num_rotation;
-  launch_transformation_unpack_grad(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
   return 0;
 } HEP_CATCH_INT
 

@@ -433,6 +433,8 @@ struct HGPlan {
 };
 // fills the plan; returns 0, or a negative HEP_ERR_* with a reason in *why (a static string)
 int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode = 0);
+int heads_tensor_count(const HGPlan&);      // the tensors of the flat buffer in state_dict order: how many, and (below) the float offset of each; all three parts alike
+void heads_tensor_offsets(const HGPlan&, int64_t* offsets);
 // momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
 void launch_heads_forward(const HGPlan&, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t,
                           float momentum = 0.0f, float* stats_out = nullptr);
@@ -461,10 +463,14 @@ struct NGPlan {
   int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
   int64_t o_bne, o_bnp;                                 // ... an effective table per BatchNorm (laterals, then cell by cell); the statistics partials
 };
-// fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
-int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why, int bn_mode = 0);
+// fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why.  The three plan
+// functions have one signature: num_classes is the heads' alone and ignored here
+int neck_plan(int phi, int num_classes, int size, int batch, NGPlan* p, const char** why, int bn_mode = 0);
+int neck_tensor_count(const NGPlan&);
+void neck_tensor_offsets(const NGPlan&, int64_t* offsets);
+// stage i of the workspace a forward leaves: its name, NHWC dims and float offset; -1 for an index past the end (neck and backbone alike)
 int neck_stage_count(const NGPlan&);
-int neck_stage(const NGPlan&, int i, char name[32], int* level, int64_t* offset_floats);
+int neck_stage(const NGPlan&, int i, char name[32], int64_t dims[4], int64_t* offset_floats);
 // momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
 void launch_neck_forward(const NGPlan&, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t,
                          float momentum = 0.0f, float* stats_out = nullptr);
@@ -498,11 +504,11 @@ struct BGPlan {
   int64_t o_es, o_bnp;                                  // ... the stem's effective table; the statistics partials
 };
 // fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
-int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why, int bn_mode = 0);
+int backbone_plan(int phi, int num_classes, int size, int batch, BGPlan* p, const char** why, int bn_mode = 0);      // (num_classes ignored, as neck_plan)
 int backbone_tensor_count(const BGPlan&);
 void backbone_tensor_offsets(const BGPlan&, int64_t* offsets);
 int backbone_stage_count(const BGPlan&);
-int backbone_stage(const BGPlan&, int i, char name[32], int* side, int* channels, int64_t* offset_floats);
+int backbone_stage(const BGPlan&, int i, char name[32], int64_t dims[4], int64_t* offset_floats);
 // momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
 void launch_backbone_forward(const BGPlan&, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t,
                              float momentum = 0.0f, float* stats_out = nullptr);

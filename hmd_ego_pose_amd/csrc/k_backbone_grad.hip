@@ -462,7 +462,7 @@ static inline void bg_chunks(int ss, int* chunk_rows, int* nchunk) {
   *nchunk = (ss + *chunk_rows - 1) / *chunk_rows;
 }
 
-int backbone_plan(int phi, int size, int batch, BGPlan* p, const char** why, int bn_mode) {
+int backbone_plan(int phi, int, int size, int batch, BGPlan* p, const char** why, int bn_mode) {
   hep::Arch arch;
   if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "backbone: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
   p->bn_batch = bn_mode == HEP_BN_BATCH;
@@ -570,13 +570,14 @@ void backbone_tensor_offsets(const BGPlan& p, int64_t* out) {
 }
 
 int backbone_stage_count(const BGPlan& p) { return 1 + p.nblocks; }
-// stage 0: "stem" (after BN + swish), stage 1 + i: "block{i}" (the block's output)
-int backbone_stage(const BGPlan& p, int i, char name[32], int* side, int* channels, int64_t* offset_floats) {
+// stage 0: "stem" (after BN + swish), stage 1 + i: "block{i}" (the block's output); dims: [B, s, s, C]
+int backbone_stage(const BGPlan& p, int i, char name[32], int64_t dims[4], int64_t* offset_floats) {
   if (i < 0 || i >= backbone_stage_count(p)) return -1;
-  if (i == 0) { snprintf(name, 32, "stem"); *side = p.s0; *channels = p.stem; *offset_floats = p.o_as; return 0; }
+  dims[0] = p.B;
+  if (i == 0) { snprintf(name, 32, "stem"); dims[1] = dims[2] = p.s0; dims[3] = p.stem; *offset_floats = p.o_as; return 0; }
   const BGBlock& b = p.b[i - 1];
   snprintf(name, 32, "block%d", i - 1);
-  *side = b.s_out; *channels = b.cout; *offset_floats = b.o_y;
+  dims[1] = dims[2] = b.s_out; dims[3] = b.cout; *offset_floats = b.o_y;
   return 0;
 }
 

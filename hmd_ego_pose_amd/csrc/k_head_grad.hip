@@ -355,6 +355,22 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
 
 static inline int64_t hg_conv_stride(const HGGeom& g) { return (int64_t)9 * g.W + (int64_t)g.W * g.W + g.W; }
 
+// the tensors of the flat buffer in state_dict order: per net depth x (depthwise, pointwise, bias), 5 levels x depth BatchNorms of 4 vectors, a header's three
+int heads_tensor_count(const HGPlan& p) { return HG_NETS * (3 * p.g.D + 5 * p.g.D * 4) + HG_SLOTS * 3; }
+void heads_tensor_offsets(const HGPlan& p, int64_t* out) {
+  const int W = p.g.W, D = p.g.D;
+  int k = 0;
+  for (int n = 0; n < HG_NETS; n++) {
+    for (int i = 0; i < D; i++) {
+      const int64_t c = p.p_conv[n] + i * hg_conv_stride(p.g);
+      out[k++] = c; out[k++] = c + 9 * W; out[k++] = c + 9 * W + (int64_t)W * W;
+    }
+    for (int j = 0; j < 5 * D * 4; j++) out[k++] = p.p_bn[n] + (int64_t)j * W;
+    for (int h = 0; h < HG_SLOTS; h++)
+      if (p.net[h] == n) { out[k++] = p.p_hdr[h]; out[k++] = p.p_hdr[h] + 9 * W; out[k++] = p.p_hdr[h] + 9 * W + (int64_t)p.C[h] * W; }
+  }
+}
+
 // the effective table of (net, layer) at level 0 (batch statistics), laid out as the parameters' bn_list of the net
 static inline float* hg_bn_eff(const HGPlan& p, float* ws, int n, int i) { return ws + p.o_bne + ((int64_t)n * 5 * p.g.D + i) * 4 * p.g.W; }
 // the 25 BatchNorms (net, level) of layer i as jobs of grad_dev.h's batch-statistics kernels; a job's rows are one level's

@@ -366,7 +366,7 @@ __global__ __launch_bounds__(GD_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
 static inline int64_t ng_node_stride(int W) { return (int64_t)9 * W + (int64_t)W * W + W + 4 * W; }
 static inline int64_t ng_lat_stride(int W, int K) { return (int64_t)W * K + W + 4 * W; }
 
-int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why, int bn_mode) {
+int neck_plan(int phi, int, int size, int batch, NGPlan* p, const char** why, int bn_mode) {
   if (phi == 6 || phi == 7) { *why = "neck: phi 6 and 7 fuse by plain sums at width 384 (no fast attention): not supported, phi must be in 0..5"; return HEP_ERR_UNSUPPORTED; }
   if (phi < 0 || phi > 5) { *why = "neck: phi must be in 0..5 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
   if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "neck: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
@@ -426,15 +426,36 @@ int neck_plan(int phi, int size, int batch, NGPlan* p, const char** why, int bn_
   return 0;
 }
 
+// the tensors of the flat buffer in state_dict order: per cell 8 fusion vectors, per node (depthwise, pointwise, bias, BatchNorm's 4); behind cell 0 the laterals' 6
+int neck_tensor_count(const NGPlan& p) { return p.cells * (NG_NODES + NG_NODES * 7) + NG_LATERALS * 6; }
+void neck_tensor_offsets(const NGPlan& p, int64_t* out) {
+  const int W = p.W;
+  int k = 0;
+  auto vectors = [&](int64_t at) { for (int t = 0; t < 5; t++) out[k++] = at + (int64_t)t * W; };      // bias, then the BatchNorm
+  for (int r = 0; r < p.cells; r++) {
+    for (int j = 0; j < NG_NODES; j++) out[k++] = p.p_cell[r] + kNodeFw[j];
+    for (int j = 0; j < NG_NODES; j++) {
+      const int64_t o = p.p_cell[r] + NG_FUSION_FLOATS + j * ng_node_stride(W);
+      out[k++] = o; out[k++] = o + 9 * W; vectors(o + 9 * W + (int64_t)W * W);
+    }
+    if (r == 0)
+      for (int i = 0; i < NG_LATERALS; i++) { out[k++] = p.p_lat[i]; vectors(p.p_lat[i] + (int64_t)W * p.tapc[kLatTap[i]]); }
+  }
+}
+
 int neck_stage_count(const NGPlan& p) { return 2 + 5 * p.cells; }
-// stage i: 0 p6_pre (the p5_to_p6 lateral's output), 1 bifpn0_p6_in, then bifpn{r}_p{3..7}
-int neck_stage(const NGPlan& p, int i, char name[32], int* level, int64_t* offset_floats) {
+// stage i: 0 p6_pre (the p5_to_p6 lateral's output), 1 bifpn0_p6_in, then bifpn{r}_p{3..7}; dims: [B, s, s, W] of the stage's level
+int neck_stage(const NGPlan& p, int i, char name[32], int64_t dims[4], int64_t* offset_floats) {
   if (i < 0 || i >= neck_stage_count(p)) return -1;
-  if (i == 0) { snprintf(name, 32, "p6_pre"); *level = 2; *offset_floats = p.o_ly[3]; return 0; }
-  if (i == 1) { snprintf(name, 32, "bifpn0_p6_in"); *level = 3; *offset_floats = p.o_p6; return 0; }
-  const int r = (i - 2) / 5, l = (i - 2) % 5;
-  snprintf(name, 32, "bifpn%d_p%d", r, l + 3);
-  *level = l; *offset_floats = p.o_y[r][kOutNode[l]];
+  int level;
+  if (i == 0) { snprintf(name, 32, "p6_pre"); level = 2; *offset_floats = p.o_ly[3]; }
+  else if (i == 1) { snprintf(name, 32, "bifpn0_p6_in"); level = 3; *offset_floats = p.o_p6; }
+  else {
+    const int r = (i - 2) / 5, l = (i - 2) % 5;
+    snprintf(name, 32, "bifpn%d_p%d", r, l + 3);
+    level = l; *offset_floats = p.o_y[r][kOutNode[l]];
+  }
+  dims[0] = p.B; dims[1] = dims[2] = p.s[level]; dims[3] = p.W;
   return 0;
 }
 

@@ -88,6 +88,51 @@ def test_phi7_is_phi6_for_the_backbone_and_the_heads():
         assert l.hep_heads_workspace_bytes(7, 1, size, batch) == l.hep_heads_workspace_bytes(6, 1, size, batch) > 0
 
 
+@pytest.mark.parametrize("part", ["heads", "neck", "backbone"])
+def test_plain_part_entry_points_are_their_bn_twins_in_running_mode(part):
+    """hep_{part}_workspace_bytes / _forward_device / _backward_device are one-line forwards to the _bn calls with HEP_BN_RUNNING,
+    momentum 0 and stats_out NULL: the same return value and the same hep_last_error text, at sizes 128 and 256 with batches 1
+    and 2 and for the refused size 0, size 200, phi 8 and batch 0.  No device here, and none is touched where there is one: at
+    the shapes the plan accepts, forward and backward get a workspace four bytes short, which is the last host check in front of
+    the launch; the pointers are one host address that is never dereferenced."""
+    l = _capi.lib()
+    heads = (1,) if part == "heads" else ()
+    buf = np.zeros(64, np.float32)
+    a = (buf.ctypes.data + 15) // 16 * 16
+    five, three = (ctypes.c_void_p * 5)(*([a] * 5)), (ctypes.c_void_p * 3)(*([a] * 3))
+    f = lambda name: getattr(l, f"hep_{part}_{name}")
+
+    def twins(phi, size, batch, nbytes):
+        shape = (phi, *heads, size, batch)
+        if part == "heads":
+            fwd, bwd = (a, five, *shape, five, a, nbytes), (a, five, *shape, a, None, a, nbytes)
+        elif part == "neck":
+            fwd, bwd = (a, three, *shape, five, a, nbytes), (a, five, *shape, a, None, a, nbytes)
+        else:
+            fwd, bwd = (a, a, None, *shape, three, a, nbytes), (a, three, None, *shape, a, None, a, nbytes)
+        return [("workspace_bytes", lambda: f("workspace_bytes")(*shape), lambda: f("workspace_bytes_bn")(*shape, 0)),
+                ("forward_device", lambda: f("forward_device")(*fwd, None), lambda: f("forward_device_bn")(*fwd, 0, 0.0, None, None)),
+                ("backward_device", lambda: f("backward_device")(*bwd, None), lambda: f("backward_device_bn")(*bwd, 0, None))]
+
+    def outcome(call):
+        assert l.hep_anchors(100, None, None) < 0               # another message in between: an equal text below is never a stale one
+        rc = call()
+        return rc, l.hep_last_error()
+
+    accepted = [(0, size, batch) for size in (128, 256) for batch in (1, 2)]
+    refused = [(0, 0, 2), (0, 0, 0), (0, 200, 2), (8, 256, 2), (0, 256, 0)]
+    for phi, size, batch in accepted + refused:
+        need = f("workspace_bytes")(phi, *heads, size, batch)
+        assert (need > 0) == ((phi, size, batch) in accepted), (phi, size, batch, need)
+        for name, plain, bn in twins(phi, size, batch, need - 4 if need > 0 else 1 << 40):
+            got, want = outcome(plain), outcome(bn)
+            assert got == want, (part, name, phi, size, batch, got, want)
+            if name != "workspace_bytes":
+                assert got[0] == (-1 if need > 0 else -4) and part.encode() in got[1], (part, name, phi, size, batch, got)
+                if need > 0:
+                    assert b"workspace is smaller" in got[1]
+
+
 def test_module_constructs_with_the_seeded_weights_at_the_deepest_phi():
     """HMDEgoPose.__init__ fills its 2314 tensors at phi 7 from seeded_state_dict(phi, 0) through reset_parameters, each
     key copied once (the constructor used to rebuild its state_dict per key: 20 s at phi 4, which is what the
