@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("HEP_LIB") or os.path.join(os.path.dirname(os.path.abs
 HEP_F32, HEP_BF16, HEP_FP8 = 0, 1, 2
 FLAG_KEEP_INTERMEDIATES, FLAG_NO_GRAPH = 1, 2
 OUT_K = (4, 1, 3, 3, 63)
+POSE_RECORD_WORDS = 80                     # HEP_POSE_RECORD_WORDS
 PK_TRAIN, PK_STAT, PK_FROZEN = 0, 1, 2      # HEP_PK_* of include/hep.h
 OPT_ADAM, OPT_SGD_NESTEROV = 0, 1          # HEP_OPT_*
 
@@ -46,6 +47,9 @@ SYMBOLS = {
     "hep_set_class_specific_filter": (c_int, [_P, c_int]),
     "hep_filter": (c_int, [_P, _FP, _FP, _FP, _FP, _FP, c_int, c_float, c_float, c_int] + [_FP] * 8),
     "hep_filter_device": (c_int, [_P, _FP, _FP, _FP, _FP, _FP, c_int, c_float, c_float, c_int] + [_FP] * 8 + [c_void_p]),
+    "hep_top1_device": (c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_float, c_void_p, c_void_p]),
+    "hep_pose_from_i420": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8),
+    "hep_pose_from_input": (c_int, [_P, _FP, c_int, _FP, c_float] + [_FP] * 8),
     "hep_pose_errors": (c_int, [c_int, _FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP]),
     "hep_pose_errors_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP, c_void_p]),
     "hep_anchor_targets_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_double, c_double, _FP, _FP, _FP, _FP, c_void_p]),

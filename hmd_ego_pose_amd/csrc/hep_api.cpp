@@ -40,6 +40,7 @@ Session::~Session() {
   hipFree(d_in); hipFree(d_anchors); hipFree(d_tanchors); hipFree(d_boxes); hipFree(d_trans); hipFree(d_cam);
   hipFree(d_keys); hipFree(d_det); hipFree(d_part);
   for (int i = 0; i < 5; i++) hipFree(d_stage[i]);
+  hipFree(d_pose_in); hipFree(d_rec); hipHostFree(h_pose_in); hipHostFree(h_rec);
   if (stream) hipStreamDestroy(stream);
 }
 
@@ -397,15 +398,16 @@ int hep_preprocess_u8_device(hep_handle* h, const uint8_t* rgb_hwc, int batch, i
   return 0;
 } HEP_CATCH_INT
 
-int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                               float* out_hwc, void* stream) try {
-  if (!h || !yuv || !out_hwc || batch < 1) return fail(HEP_ERR_INVALID, "bad argument");
+// the frame geometry both I420 entry points refuse (host arithmetic only)
+static int check_i420(int height, int width, int crop, int resized) {
   if (height < 2 || width < 2 || (height & 1) || (width & 1)) return fail(HEP_ERR_INVALID, "4:2:0 frames have even sides");
   if (crop < 1 || crop > height || crop > width || resized < 1) return fail(HEP_ERR_INVALID, "crop must fit the frame, resized must be positive");
-  Session& s = h->s;
-  HIPRET(hipSetDevice(s.device));
-  std::lock_guard<std::mutex> lk(s.mu);          // the two scratch buffers belong to the handle
-  hipStream_t st = (hipStream_t)stream;
+  return 0;
+}
+
+// the launches of the frame path on `st`; s.mu is held (the two scratch buffers belong to the handle)
+static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                                  float* out_hwc, hipStream_t st) {
   // The scratch frames are used ASYNCHRONOUSLY on the caller's stream and the mutex only covers the enqueue: a second call on
   // another stream (an in-flight pool) must not overwrite them while the first call's kernels still read them.  An event is
   // recorded behind the last launch of every call and the next call's stream waits for it first (device-side, no host stall).
@@ -446,6 +448,16 @@ int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int
   launch_resize_u8(r2, st);
   HIPRET(hipGetLastError());
   return 0;
+}
+
+int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                               float* out_hwc, void* stream) try {
+  if (!h || !yuv || !out_hwc || batch < 1) return fail(HEP_ERR_INVALID, "bad argument");
+  if (int rc = check_i420(height, width, crop, resized)) return rc;
+  Session& s = h->s;
+  HIPRET(hipSetDevice(s.device));
+  std::lock_guard<std::mutex> lk(s.mu);
+  return preprocess_i420_locked(s, yuv, batch, height, width, crop, resized, out_hwc, (hipStream_t)stream);
 } HEP_CATCH_INT
 
 // ---- decode / filter ----
@@ -595,6 +607,154 @@ int hep_filter(hep_handle* h, const float* boxes, const float* classification, c
   HIPRET(hipMemcpyAsync(det_count, ct_, (size_t)batch * 4, hipMemcpyDeviceToHost, s.stream));
   HIPRET(hipStreamSynchronize(s.stream));
   return 0;
+} HEP_CATCH_INT
+
+// ---- top detection / frame to pose ----
+static int top1_locked(Session& s, const float* regression, const float* classification, const float* rotation,
+                       const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
+                       uint32_t* records, hipStream_t st) {
+  Top1Args a;
+  a.regression = regression ? regression : s.d_out[0];         // NULL = the handle's own last outputs
+  a.scores = classification ? classification : s.d_out[1];
+  a.rotation = rotation ? rotation : s.d_out[2];
+  a.translation_raw = translation_raw ? translation_raw : s.d_out[3];
+  a.hand = hand ? hand : s.d_out[4];
+  a.camera = camera; a.anchors = s.d_anchors; a.t_anchors = s.d_tanchors;
+  a.B = batch; a.N = s.num_anchors; a.K = s.num_classes; a.any_class = s.class_specific_filter ? 0 : 1;
+  a.score_thr = score_threshold; a.clip_max = (float)(s.size - 1);
+  a.records = records;
+  launch_top1(a, st);
+  HIPRET(hipGetLastError());
+  return 0;
+}
+
+int hep_top1_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
+                    const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
+                    uint32_t* records, void* stream) try {
+  if (!h) return fail(HEP_ERR_INVALID, "hep_top1_device: handle is NULL");
+  if (!camera) return fail(HEP_ERR_INVALID, "hep_top1_device: camera is NULL");
+  if (!records) return fail(HEP_ERR_INVALID, "hep_top1_device: records is NULL");
+  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_top1_device: batch outside 1..max_batch");      // (the handle is not read before the pointers are checked)
+  Session& s = h->s;
+  if (batch > s.max_batch) return fail(HEP_ERR_INVALID, "hep_top1_device: batch outside 1..max_batch");
+  std::lock_guard<std::mutex> lk(s.mu);
+  HIPRET(hipSetDevice(s.device));
+  return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream);
+} HEP_CATCH_INT
+
+namespace {
+struct PoseOut { int32_t* found; float* scores; int32_t* labels; int32_t* index; float* boxes; float* rotation; float* translation; float* hand; };
+constexpr size_t kRecBytes = (size_t)HEP_POSE_RECORD_WORDS * 4;
+static_assert(HEP_POSE_RECORD_WORDS == POSE_RECORD_WORDS, "the record of include/hep.h is the kernel's");
+}  // namespace
+
+// what the two host entry points share, before any HIP call: NULL pointers and a batch below 1 without reading the handle (check_pose),
+// then - behind the frame geometry - the batch against the handle's max_batch (check_pose_batch)
+static int check_pose(const char* who, const hep_handle* h, const void* input, const char* input_name, int batch, const float* camera, const int32_t* found) {
+  if (!h) return fail(HEP_ERR_INVALID, std::string(who) + ": handle is NULL");
+  if (!input) return fail(HEP_ERR_INVALID, std::string(who) + ": " + input_name + " is NULL");
+  if (!camera) return fail(HEP_ERR_INVALID, std::string(who) + ": camera is NULL");
+  if (!found) return fail(HEP_ERR_INVALID, std::string(who) + ": found is NULL");
+  if (batch < 1) return fail(HEP_ERR_INVALID, std::string(who) + ": batch outside 1..max_batch given to hep_create");
+  return 0;
+}
+static int check_pose_batch(const char* who, const hep_handle* h, int batch) {
+  if (batch > h->s.max_batch) return fail(HEP_ERR_INVALID, std::string(who) + ": batch outside 1..max_batch given to hep_create");
+  return 0;
+}
+
+// Staging of one call: [camera rows, padded to cam_pad bytes | payload] on the device.  Direct (the default): two hipMemcpyAsync from
+// the caller's pageable memory.  Pinned (HEP_POSE_UPLOAD=pinned, kept for the A/B of tools/pose_call_time.py): camera and payload are
+// copied into a pinned buffer of the handle and go up as ONE hipMemcpyAsync.  Measured twice (NOTEBOOK.md section 24): the 3 MB float
+// blob is 0.05 ms faster direct (the host copy into the pinned buffer costs more than the runtime's own staging), the 1.4 MB frame
+// 0.02 ms faster back to back and level at 60 Hz.  Buffers are sized for max_batch payloads of this call's per-image size and only
+// ever grown: a repeated shape allocates nothing.
+static size_t pose_cam_pad(const Session& s) { return ((size_t)s.max_batch * 24 + 255) & ~(size_t)255; }
+static int pose_stage(Session& s, const void* payload, size_t per_image, int batch, const float* camera) {
+  const size_t pad = pose_cam_pad(s), need = pad + per_image * (size_t)s.max_batch;
+  if (!s.d_rec) {
+    const char* e = getenv("HEP_POSE_UPLOAD");
+    s.pose_upload_pinned = e && !strcmp(e, "pinned");
+    HIPRET(hipMalloc((void**)&s.d_rec, kRecBytes * s.max_batch));
+  }
+  const bool direct = !s.pose_upload_pinned;
+  if (!s.h_rec) HIPRET(hipHostMalloc((void**)&s.h_rec, kRecBytes * s.max_batch, hipHostMallocDefault));
+  if (s.pose_in_bytes < need) {
+    HIPRET(hipStreamSynchronize(s.stream));
+    hipFree(s.d_pose_in); s.d_pose_in = nullptr; s.pose_in_bytes = 0;
+    HIPRET(hipMalloc((void**)&s.d_pose_in, need)); s.pose_in_bytes = need;
+  }
+  if (!direct && s.pose_pin_bytes < need) {
+    HIPRET(hipStreamSynchronize(s.stream));
+    hipHostFree(s.h_pose_in); s.h_pose_in = nullptr; s.pose_pin_bytes = 0;
+    HIPRET(hipHostMalloc((void**)&s.h_pose_in, need, hipHostMallocDefault)); s.pose_pin_bytes = need;
+  }
+  const size_t bytes = per_image * (size_t)batch;
+  if (direct) {
+    HIPRET(hipMemcpyAsync(s.d_pose_in, camera, (size_t)batch * 24, hipMemcpyHostToDevice, s.stream));
+    HIPRET(hipMemcpyAsync(s.d_pose_in + pad, payload, bytes, hipMemcpyHostToDevice, s.stream));
+  } else {
+    memcpy(s.h_pose_in, camera, (size_t)batch * 24);
+    memcpy(s.h_pose_in + pad, payload, bytes);
+    HIPRET(hipMemcpyAsync(s.d_pose_in, s.h_pose_in, pad + bytes, hipMemcpyHostToDevice, s.stream));
+  }
+  return 0;
+}
+
+// top-detection launch on the handle's own head outputs, the records back through the pinned buffer, synchronise, scatter
+static int pose_finish(Session& s, int batch, float score_threshold, const PoseOut& o) {
+  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, batch, score_threshold, s.d_rec, s.stream)) return rc;
+  HIPRET(hipMemcpyAsync(s.h_rec, s.d_rec, kRecBytes * batch, hipMemcpyDeviceToHost, s.stream));
+  HIPRET(hipStreamSynchronize(s.stream));
+  for (int b = 0; b < batch; b++) {
+    const uint32_t* r = s.h_rec + (size_t)b * HEP_POSE_RECORD_WORDS;
+    memcpy(&o.found[b], r + 0, 4);
+    if (o.labels) memcpy(&o.labels[b], r + 1, 4);
+    if (o.index) memcpy(&o.index[b], r + 2, 4);
+    if (o.scores) memcpy(&o.scores[b], r + 4, 4);
+    if (o.boxes) memcpy(o.boxes + (size_t)b * 4, r + 5, 16);
+    if (o.rotation) memcpy(o.rotation + (size_t)b * 3, r + 9, 12);
+    if (o.translation) memcpy(o.translation + (size_t)b * 3, r + 12, 12);
+    if (o.hand) memcpy(o.hand + (size_t)b * 63, r + 15, 63 * 4);
+  }
+  return 0;
+}
+
+int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
+                        int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
+                        float* translation, float* hand) try {
+  if (int rc = check_pose("hep_pose_from_input", h, input_nchw, "input_nchw", batch, camera, found)) return rc;
+  if (int rc = check_pose_batch("hep_pose_from_input", h, batch)) return rc;
+  Session& s = h->s;
+  std::lock_guard<std::mutex> lk(s.mu);
+  HIPRET(hipSetDevice(s.device));
+  if (int rc = pose_stage(s, input_nchw, (size_t)3 * s.size * s.size * 4, batch, camera)) return rc;
+  std::string err;
+  if (int rc = run_forward(&s, (const float*)(s.d_pose_in + pose_cam_pad(s)), nullptr, batch, s.stream, &err)) return fail(rc, err);
+  return pose_finish(s, batch, score_threshold, PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                       int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
+  if (int rc = check_pose("hep_pose_from_i420", h, yuv, "yuv", batch, camera, found)) return rc;
+  if (int rc = check_i420(height, width, crop, resized)) return rc;
+  if (int rc = check_pose_batch("hep_pose_from_i420", h, batch)) return rc;
+  Session& s = h->s;
+  {   // ResizeAndNormalizeMat's row count (preprocess_i420_locked computes the same): refused here, before any HIP call
+    const int nh = (int)((float)resized * ((float)s.size / (float)resized));
+    if (nh < 1 || nh > s.size) return fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size");
+  }
+  std::lock_guard<std::mutex> lk(s.mu);
+  HIPRET(hipSetDevice(s.device));
+  const size_t in_floats = (size_t)3 * s.size * s.size;
+  if (!s.d_in) HIPRET(hipMalloc((void**)&s.d_in, in_floats * s.max_batch * 4));
+  if (int rc = pose_stage(s, yuv, (size_t)height * width * 3 / 2, batch, camera)) return rc;
+  if (int rc = preprocess_i420_locked(s, s.d_pose_in + pose_cam_pad(s), batch, height, width, crop, resized, s.d_in, s.stream)) return rc;
+  const int64_t S = s.size; const int64_t nhwc[4] = {3 * S * S, 1, 3 * S, 3};      // the NCHW view of the [batch,S,S,3] frames
+  std::string err;
+  if (int rc = run_forward(&s, s.d_in, nhwc, batch, s.stream, &err)) return fail(rc, err);
+  return pose_finish(s, batch, score_threshold, PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
 } HEP_CATCH_INT
 
 // ---- pose errors (evaluator) ----

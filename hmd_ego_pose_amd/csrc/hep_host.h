@@ -95,6 +95,11 @@ struct Session {
   int32_t* d_part = nullptr;        // per-class survivors of the detection filter (num_classes > 1)
   float* d_det = nullptr; size_t det_floats = 0;   // staging for host-buffer filter
   float* d_stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // host-side inputs of hep_decode / hep_filter (never the forward's outputs)
+  // hep_pose_from_i420 / hep_pose_from_input: [camera rows, padded | frame bytes or input floats] on the device and its pinned
+  // twin on the host (when the upload goes through it), the records on both sides; allocated at first use, only ever grown
+  unsigned char* d_pose_in = nullptr; unsigned char* h_pose_in = nullptr; size_t pose_in_bytes = 0, pose_pin_bytes = 0;
+  uint32_t* d_rec = nullptr; uint32_t* h_rec = nullptr;
+  bool pose_upload_pinned = false;  // HEP_POSE_UPLOAD=pinned: the upload goes through h_pose_in (the measured alternative, hep_api.cpp pose_stage)
   unsigned* d_sync = nullptr;       // meeting counters of grouped launches (k_late.hip): an allocation of its own, zeroed once - never arena memory
   hipStream_t stream = nullptr;     // handle's own stream (host API, capture, profiling)
   std::map<int, std::vector<hipGraphExec_t>> graphs;   // per batch size: one graph per lane

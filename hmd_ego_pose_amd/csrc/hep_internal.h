@@ -316,6 +316,18 @@ struct FilterArgs {
   float* det_hand; int32_t* det_index; int32_t* det_count;
 };
 
+// ---- top detection per image: row 0 of decode + filter without the sort, the NMS and the other rows (k_post.hip top1_kernel) ----
+#define POSE_RECORD_WORDS 80      // HEP_POSE_RECORD_WORDS of include/hep.h: the record's layout is stated there
+struct Top1Args {
+  const float* regression; const float* scores; const float* rotation; const float* translation_raw; const float* hand;   // raw head outputs [B][N][4 | K | 3 | 3 | 63]
+  const float* camera; const float* anchors; const float* t_anchors;
+  int B, N, K;
+  int any_class;       // as FilterArgs::any_class
+  float score_thr, clip_max;
+  uint32_t* records;   // [B][POSE_RECORD_WORDS]
+};
+void launch_top1(const Top1Args&, hipStream_t);
+
 // ---- pose errors: ADD / ADD-S of D pose pairs over P model points (eval/common.py:682-746) ----
 struct PoseErrArgs {
   const float* points;                       // [P,3]

@@ -11,37 +11,46 @@
 // Tx=(x/scale-px)*Tz/fx with Tz = raw_z*tz_scale.  Same fp32 operation order as the torch code
 // (no fma contraction across the reference's separate ops) so results agree to the last few ulps.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void decode_kernel(DecodeArgs a) {
+// The per-anchor arithmetic, shared by decode_kernel (every anchor) and top1_kernel (the winning anchor only), which must agree
+// bit for bit.  The back end contracts a * b + c wherever it likes (-ffp-contract=fast; the pragma below does not reach it) and it
+// chose differently in the two kernels, so every rounding is stated here - as decode_kernel has always computed it: fmaf where its
+// code had a fused multiply-add (the half extents, the translation anchors' offset), rounded(a * b) - a value the optimiser
+// cannot look through - where it had a product and a sum (the box centre).
+__device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ f32x4 decode_box(const f32x4 an, const f32x4 d, float clip_max) {
 #pragma clang fp contract(off)
+  const float cxa = rounded((an[0] + an[2]) / 2.f), cya = rounded((an[1] + an[3]) / 2.f);
+  const float wa = an[2] - an[0], ha = an[3] - an[1];
+  const float ty = d[0], tx = d[1], th = d[2], tw = d[3];
+  const float w = rounded(expf(tw) * wa), h = rounded(expf(th) * ha);
+  const float cy = rounded(ty * ha) + cya, cx = rounded(tx * wa) + cxa;
+  f32x4 o;
+  o[0] = fminf(fmaxf(fmaf(-0.5f, w, cx), 0.f), clip_max);      // cx - w / 2
+  o[1] = fminf(fmaxf(fmaf(-0.5f, h, cy), 0.f), clip_max);
+  o[2] = fminf(fmaxf(fmaf(0.5f, w, cx), 0.f), clip_max);       // cx + w / 2
+  o[3] = fminf(fmaxf(fmaf(0.5f, h, cy), 0.f), clip_max);
+  return o;
+}
+__device__ __forceinline__ void decode_translation(const float* ta, const float* r, const float* cam, float* t) {
+#pragma clang fp contract(off)
+  const float stride = ta[2];
+  float x = fmaf(r[0], stride, ta[0]), y = fmaf(r[1], stride, ta[1]);
+  x = x / cam[5] - cam[2];
+  y = y / cam[5] - cam[3];
+  const float tz = rounded(r[2] * cam[4]);
+  t[0] = rounded(x * tz) / cam[0];
+  t[1] = rounded(y * tz) / cam[1];
+  t[2] = tz;
+}
+
+__global__ __launch_bounds__(256) void decode_kernel(DecodeArgs a) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (int64_t)a.B * a.N) return;
   const int n = (int)(idx % a.N), b = (int)(idx / a.N);
   const f32x4 an = *reinterpret_cast<const f32x4*>(a.anchors + (int64_t)n * 4);
   const f32x4 d = *reinterpret_cast<const f32x4*>(a.regression + idx * 4);
-  const float cxa = (an[0] + an[2]) / 2.f, cya = (an[1] + an[3]) / 2.f;
-  const float wa = an[2] - an[0], ha = an[3] - an[1];
-  const float ty = d[0], tx = d[1], th = d[2], tw = d[3];
-  const float w = expf(tw) * wa, h = expf(th) * ha;
-  const float cy = ty * ha + cya, cx = tx * wa + cxa;
-  f32x4 o;
-  o[0] = fminf(fmaxf(cx - w / 2.f, 0.f), a.clip_max);
-  o[1] = fminf(fmaxf(cy - h / 2.f, 0.f), a.clip_max);
-  o[2] = fminf(fmaxf(cx + w / 2.f, 0.f), a.clip_max);
-  o[3] = fminf(fmaxf(cy + h / 2.f, 0.f), a.clip_max);
-  *reinterpret_cast<f32x4*>(a.boxes + idx * 4) = o;
-
-  const float* ta = a.t_anchors + (int64_t)n * 3;
-  const float* r = a.translation_raw + idx * 3;
-  const float* cam = a.camera + (int64_t)b * 6;
-  const float stride = ta[2];
-  float x = ta[0] + r[0] * stride, y = ta[1] + r[1] * stride;
-  x = x / cam[5] - cam[2];
-  y = y / cam[5] - cam[3];
-  const float tz = r[2] * cam[4];
-  float* t = a.translation + idx * 3;
-  t[0] = x * tz / cam[0];
-  t[1] = y * tz / cam[1];
-  t[2] = tz;
+  *reinterpret_cast<f32x4*>(a.boxes + idx * 4) = decode_box(an, d, a.clip_max);
+  decode_translation(a.t_anchors + (int64_t)n * 3, a.translation_raw + idx * 3, a.camera + (int64_t)b * 6, a.translation + idx * 3);
 }
 void launch_decode(const DecodeArgs& a, hipStream_t s) {
   const int64_t total = (int64_t)a.B * a.N;
@@ -271,6 +280,93 @@ void launch_filter(const FilterArgs& a, hipStream_t s) {
     while (np2 < a.K * a.max_det) np2 <<= 1;
     hipLaunchKernelGGL(filter_merge_kernel, dim3(a.B), dim3(FILTER_THREADS), (size_t)np2 * 8, s, a);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Top detection per image = row 0 of decode_kernel -> filter_kernel (-> filter_merge_kernel), for any nms_thr and max_det >= 1:
+// the best-scoring candidate is first in every sorted order and nothing can suppress it.  One workgroup per image:
+//   1. every lane keeps the largest key of its share of the scores, with the filter's key (score_bits << 32 | ~position; 0 = no
+//      candidate).  position: the anchor index; class-specific mode with K classes: class * N + anchor - the order of
+//      filter_merge_kernel's concatenation "class by class, NMS order inside a class", whose first entry per class is that
+//      class's lowest-index best anchor
+//   2. maximum over the wave (shuffles), then over the 16 waves (LDS)
+//   3. box / translation of the winning anchor with decode_kernel's own arithmetic, rotation and hand gathered, record written
+//      (include/hep.h: HEP_POSE_RECORD_WORDS); no candidate: the padding filter_emit writes.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FILTER_THREADS) void top1_kernel(Top1Args a) {
+  __shared__ uint64_t wave_best[FILTER_THREADS / 64];
+  __shared__ float s_geo[8];                                  // box, translation of the winner
+  const int b = blockIdx.x, tid = threadIdx.x, K = a.K, N = a.N;
+  const bool anyc = a.any_class != 0 && K > 1;
+  const float* scores = a.scores + (int64_t)b * N * K;        // [N][K]
+  uint64_t best = 0;
+  if (anyc || K == 1) {
+    for (int n = tid; n < N; n += FILTER_THREADS) {           // (n < N guards the tail: N is no multiple of the workgroup)
+      int l;
+      const float sc = anyc ? best_class(scores + (int64_t)n * K, K, &l) : scores[n];
+      if (sc > a.score_thr) {
+        const uint64_t key = ((uint64_t)__float_as_uint(sc) << 32) | (uint32_t)(~(uint32_t)n);
+        best = key > best ? key : best;
+      }
+    }
+  } else {
+    const int total = N * K;                                  // <= 63 * 786 096 anchors at size 2048: fits 32 bits
+    for (int m = tid; m < total; m += FILTER_THREADS) {       // memory order [n][c]: coalesced
+      const int n = m / K, c = m - n * K;
+      const float sc = scores[m];
+      if (sc > a.score_thr) {
+        const uint64_t key = ((uint64_t)__float_as_uint(sc) << 32) | (uint32_t)(~(uint32_t)(c * N + n));
+        best = key > best ? key : best;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint64_t other = (uint64_t)__shfl_xor((unsigned long long)best, o, 64);
+    best = other > best ? other : best;
+  }
+  if ((tid & 63) == 0) wave_best[tid >> 6] = best;
+  __syncthreads();
+  best = wave_best[0];
+#pragma unroll
+  for (int w = 1; w < FILTER_THREADS / 64; w++) best = wave_best[w] > best ? wave_best[w] : best;   // (LDS broadcast reads: every lane ends with the winner)
+  const bool found = best != 0;
+  const uint32_t pos = ~(uint32_t)best;
+  int n = 0, label = 0;
+  if (found) {
+    if (anyc) { n = (int)pos; best_class(scores + (int64_t)n * K, K, &label); }
+    else if (K == 1) n = (int)pos;
+    else { label = (int)(pos / (uint32_t)N); n = (int)(pos - (uint32_t)label * (uint32_t)N); }
+  }
+  const int64_t src = (int64_t)b * N + n;
+  if (tid == 0 && found) {
+    const f32x4 an = *reinterpret_cast<const f32x4*>(a.anchors + (int64_t)n * 4);
+    const f32x4 d = *reinterpret_cast<const f32x4*>(a.regression + src * 4);
+    const f32x4 o = decode_box(an, d, a.clip_max);
+    s_geo[0] = o[0]; s_geo[1] = o[1]; s_geo[2] = o[2]; s_geo[3] = o[3];
+    decode_translation(a.t_anchors + (int64_t)n * 3, a.translation_raw + src * 3, a.camera + (int64_t)b * 6, s_geo + 4);
+  }
+  __syncthreads();
+  if (tid >= POSE_RECORD_WORDS) return;
+  uint32_t v = 0;                                             // words 3, 78, 79
+  if (tid == 0) v = found ? 1u : 0u;
+  else if (tid == 1) v = (uint32_t)(found ? label : -1);
+  else if (tid == 2) v = (uint32_t)(found ? n : -1);
+  else if (tid >= 4 && tid < 78) {
+    float f = -1.f;
+    if (found) {
+      if (tid == 4) f = __uint_as_float((uint32_t)(best >> 32));          // = scores[src * K + label]
+      else if (tid < 9) f = s_geo[tid - 5];
+      else if (tid < 12) f = a.rotation[src * 3 + (tid - 9)];
+      else if (tid < 15) f = s_geo[4 + (tid - 12)];
+      else f = a.hand[src * 63 + (tid - 15)];
+    }
+    v = __float_as_uint(f);
+  }
+  a.records[(int64_t)b * POSE_RECORD_WORDS + tid] = v;
+}
+void launch_top1(const Top1Args& a, hipStream_t s) {
+  hipLaunchKernelGGL(top1_kernel, dim3(a.B), dim3(FILTER_THREADS), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -174,6 +174,94 @@ class Session:
                                                       stream))
         return out
 
+    # -- top detection / frame to pose ----------------------------------------------------
+    _POSE_KEYS = ("found", "score", "label", "index", "box", "rotation", "translation", "hand")
+
+    def top1(self, camera, score_threshold=0.5, heads=None, class_specific_filter=None):
+        """The top detection of every image in one launch (hep_top1_device): row 0 of ``decode`` + ``filter`` bit for bit, for any NMS
+        threshold and ``max_detections``.  ``camera`` [B,6] on the device.  ``heads``: the five RAW head tensors (regression,
+        classification, rotation, translation_raw, hand) of a forward, or None for the handle's own output buffers (the last
+        ``hep_run_device`` without output pointers).  ``class_specific_filter``: None keeps the handle's current mode.  Returns device
+        tensors: found [B] int32, score [B], label [B] int32, index [B] int32, box [B,4], rotation [B,3], translation [B,3],
+        hand [B,63] - views of ``record`` [B,80] int32, the record of include/hep.h."""
+        dev = self.device
+        if not isinstance(camera, torch.Tensor) or camera.dim() != 2 or camera.shape[1] != 6 or camera.dtype != torch.float32 or camera.device != dev:
+            raise ValueError(f"top1: camera must be a float32 tensor of shape (B, 6) on {dev}")
+        B, N = camera.shape[0], self.num_anchors
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"top1: batch {B} is outside 1..{self.max_batch}")
+        ptrs = [None] * 5
+        if heads is not None:
+            if len(heads) != 5:
+                raise ValueError("top1: heads must be (regression, classification, rotation, translation_raw, hand)")
+            names = ("regression", "classification", "rotation", "translation_raw", "hand")
+            for name, t, k in zip(names, heads, self.out_width):
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, N, k) or t.dtype != torch.float32 or t.device != dev:
+                    raise ValueError(f"top1: {name} must be a float32 tensor of shape ({B}, {N}, {k}) on {dev}")
+            heads = [t.contiguous() for t in heads]
+            ptrs = [t.data_ptr() for t in heads]
+        rec = torch.empty((B, _capi.POSE_RECORD_WORDS), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with self._filter_lock:
+            if class_specific_filter is not None and bool(class_specific_filter) != self._class_specific:
+                _capi.check(_capi.lib().hep_set_class_specific_filter(self.handle, int(bool(class_specific_filter))))
+                self._class_specific = bool(class_specific_filter)
+            _capi.check(_capi.lib().hep_top1_device(self.handle, *ptrs, camera.contiguous().data_ptr(), B, float(score_threshold), rec.data_ptr(), stream))
+        f = rec.view(torch.float32)
+        return dict(found=rec[:, 0], label=rec[:, 1], index=rec[:, 2], score=f[:, 4], box=f[:, 5:9], rotation=f[:, 9:12],
+                    translation=f[:, 12:15], hand=f[:, 15:78], record=rec)
+
+    def _pose_call(self, who, fn, lead, B, camera, score_threshold):
+        import numpy as np
+        cam = np.ascontiguousarray(camera, dtype=np.float32) if not isinstance(camera, torch.Tensor) else None
+        if cam is None:
+            if camera.is_cuda:
+                raise ValueError(f"{who}: camera must live in host memory")
+            cam = np.ascontiguousarray(camera.numpy(), dtype=np.float32)
+        if cam.shape != (B, 6):
+            raise ValueError(f"{who}: camera must have shape ({B}, 6), got {cam.shape}")
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"{who}: batch {B} is outside 1..{self.max_batch}")
+        out = dict(found=np.empty(B, np.int32), score=np.empty(B, np.float32), label=np.empty(B, np.int32), index=np.empty(B, np.int32),
+                   box=np.empty((B, 4), np.float32), rotation=np.empty((B, 3), np.float32), translation=np.empty((B, 3), np.float32),
+                   hand=np.empty((B, 63), np.float32))
+        _capi.check(fn(self.handle, *lead, cam.ctypes.data, float(score_threshold), *[out[k].ctypes.data for k in self._POSE_KEYS]))
+        return out
+
+    @staticmethod
+    def _host_array(who, x, dtype):
+        import numpy as np
+        if isinstance(x, torch.Tensor):
+            if x.is_cuda:
+                raise ValueError(f"{who}: the input must live in host memory (device tensors: preprocess_i420 / forward / top1)")
+            x = x.numpy()
+        if not isinstance(x, np.ndarray) or x.dtype != dtype:
+            raise ValueError(f"{who}: expected a host array of dtype {np.dtype(dtype).name}")
+        return np.ascontiguousarray(x)
+
+    def pose_from_i420(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, score_threshold=0.5):
+        """Frame to pose in one synchronous call (hep_pose_from_i420): I420 frames [B, height * width * 3 // 2] (uint8, HOST memory)
+        -> the frame path of ``preprocess_i420`` -> forward -> top detection -> numpy arrays found / score / label / index / box /
+        rotation / translation / hand, one row per frame.  ``camera`` [B,6] on the host."""
+        import numpy as np
+        x = self._host_array("pose_from_i420", frames_u8_host, np.uint8)
+        if height < 2 or width < 2 or height % 2 or width % 2:
+            raise ValueError("pose_from_i420: 4:2:0 frames have even sides")
+        if not 1 <= crop <= min(height, width) or resized < 1:
+            raise ValueError("pose_from_i420: crop must fit the frame, resized must be positive")
+        if x.ndim != 2 or x.shape[1] != height * width * 3 // 2:
+            raise ValueError(f"pose_from_i420: expected uint8 frames of shape (B, {height * width * 3 // 2}), got {x.shape}")
+        return self._pose_call("pose_from_i420", _capi.lib().hep_pose_from_i420, (x.ctypes.data, x.shape[0], height, width, crop, resized),
+                               x.shape[0], camera, score_threshold)
+
+    def pose_from_input(self, x_host, camera, score_threshold=0.5):
+        """The same from the normalised float32 blob [B,3,S,S] in HOST memory that ``hep_run`` takes (hep_pose_from_input)."""
+        import numpy as np
+        x = self._host_array("pose_from_input", x_host, np.float32)
+        if x.ndim != 4 or x.shape[1:] != (3, self.size, self.size):
+            raise ValueError(f"pose_from_input: expected float32 of shape (B, 3, {self.size}, {self.size}), got {x.shape}")
+        return self._pose_call("pose_from_input", _capi.lib().hep_pose_from_input, (x.ctypes.data, x.shape[0]), x.shape[0], camera, score_threshold)
+
     # -- introspection ------------------------------------------------------------------
     def stage(self, name: str, batch: int) -> torch.Tensor:
         """fp32 NHWC copy of a stage tensor of the last forward (needs FLAG_KEEP_INTERMEDIATES)."""

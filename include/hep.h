@@ -21,6 +21,10 @@
  *                                 (C# twins Program.cs:225-470)
  *   hep_filter / _device       <- FilterDetections / filter_detections, pytorch-sandbox/hmdegopose/layers.py:264-482
  *                                 (C# twin Program.cs:472-627)
+ *   hep_top1_device            <- the ONE detection the streaming app keeps of filter_detections (WebRTCNetCoreSandbox/Program.cs:261-282):
+ *                                 row 0 of hep_decode_device + hep_filter_device in one launch
+ *   hep_pose_from_i420         <- the whole I420AVideoFrameReady callback, Program.cs:128-298 (frame bytes in host memory -> pose)
+ *   hep_pose_from_input        <- the same from the float blob of OpenCVDNNSandboxNetCore/Program.cs:95-122
  *   hep_anchor_targets_device  <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
@@ -168,6 +172,53 @@ int hep_filter_device(hep_handle* h, const float* boxes, const float* classifica
                       float nms_threshold, int max_detections, float* det_boxes, float* det_scores,
                       int32_t* det_labels, float* det_rotation, float* det_translation, float* det_hand,
                       int32_t* det_index, int32_t* det_count, void* stream);
+
+/* The top detection of every image - what the streaming app sends (unity-sandbox/WebRTCNetCoreSandbox/Program.cs:272-298 reads one
+ * detection) - as ONE launch on the raw head outputs, with no decode of the other anchors, no sort and no NMS.
+ * DEFINITION: the record of image b is row 0 of hep_decode_device -> hep_filter_device on the same inputs, bit for bit, for any
+ * nms_threshold and any max_detections >= 1, in the handle's current hep_set_class_specific_filter mode (the best-scoring
+ * candidate always survives greedy NMS).  As a rule: class-specific mode - the maximal score over all (anchor, class) pairs with
+ * score > score_threshold, ties to the lower class, then to the lower anchor index; other mode - per anchor the maximum over the
+ * class columns (label = first argmax), then the maximal such score above the threshold, ties to the lower anchor index.  A score
+ * exactly at the threshold is no candidate.
+ * regression, classification, rotation, translation_raw, hand: the RAW head outputs on the device (each may be NULL = the handle's
+ * own output buffer, as for hep_decode_device / hep_filter_device); camera [batch,6] on the device.
+ * records: device memory, batch x HEP_POSE_RECORD_WORDS 4-byte words:
+ *   word 0      found, int32 0 / 1                    word 4       score
+ *   word 1      label, int32                          words 5-8    box xmin, ymin, xmax, ymax
+ *   word 2      anchor index, int32                   words 9-11   rotation (the network's output, as the filter returns it)
+ *   word 3      0                                     words 12-14  translation Tx, Ty, Tz
+ *   words 15-77 hand (63)                             words 78-79  0
+ * With no candidate found is 0 and every other word holds the filter's padding (-1 / -1.0f); words 3, 78 and 79 stay 0.
+ * Asynchronous on `stream`, no allocation, no host synchronisation.  NULL handle / camera / records or a batch outside
+ * 1..max_batch: HEP_ERR_INVALID. */
+#define HEP_POSE_RECORD_WORDS 80
+int hep_top1_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
+                    const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
+                    uint32_t* records, void* stream);
+
+/* Frame to pose in one synchronous call on HOST memory - the whole frame callback of the streaming app (Program.cs:128-298):
+ * yuv [batch][height * width * 3 / 2] I420 bytes as WebRTC delivers them -> the kernels of hep_preprocess_i420_device (same
+ * arguments, same arithmetic) -> the forward -> the top-detection launch above -> one device-to-host copy of batch x 320 bytes.
+ * No decode or filter launch, no head array on the host.  camera [batch,6] on the host.  Outputs on the host, per image:
+ * found [batch] int32, scores [batch], labels [batch] int32, index [batch] int32 (anchor), boxes [batch,4], rotation [batch,3],
+ * translation [batch,3], hand [batch,63]; any of them except found may be NULL.  An image with found == 0 gets the padding
+ * (-1 / -1.0f) everywhere else.  rotation is the network's output as the filter returns it (the evaluator multiplies by pi,
+ * eval/common.py:419-447; the app converts to a quaternion itself).
+ * The handle's mutex is held from staging to the final synchronise (the callback may re-enter from worker threads).  The record
+ * comes back through a pinned host buffer of the handle; the frame is handed to hipMemcpyAsync where it lies (measured faster than
+ * a copy into a pinned buffer of the handle first, which HEP_POSE_UPLOAD=pinned in the environment still selects).  The handle's
+ * buffers are allocated at first use and only ever grown: after the first call of a shape nothing is allocated or freed, on host
+ * or device.  Every argument is checked before any HIP call: a NULL handle /
+ * yuv / camera / found, a batch outside 1..max_batch, an odd height or width, a crop larger than the frame or resized < 1 is
+ * HEP_ERR_INVALID with the reason in hep_last_error. */
+int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                       int32_t* index, float* boxes, float* rotation, float* translation, float* hand);
+/* The same from the normalised fp32 NCHW blob [batch,3,S,S] that hep_run takes (OpenCVDNNSandboxNetCore/Program.cs:95-122). */
+int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
+                        int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
+                        float* translation, float* hand);
 
 /* ADD and ADD-S of num_pairs (ground truth, prediction) poses over one object model: points [num_points,3]; rotations
  * as axis-angle vectors in radians (what _get_detections hands on: network output * pi), translations in the model's

@@ -1,0 +1,197 @@
+#!/usr/bin/env python3
+"""Time the frame-to-pose calls against the compositions they replace, through the C ABI as a C# host would call it, in the regime of
+bench.py's latency_b1: phi 0 @ 512, fp32, batch 1, a 1280x720 I420 frame, the classifier bias shifted as latency_b1 does (about 30
+candidates).  Host clock around calls that end in a synchronise; 300 calls after 20 warm-ups; p50 / p99, back to back and paced at
+60 Hz (one call per 16.7 ms: the device idles between frames).
+
+  (a) host array in:  old = hep_run -> hep_decode -> hep_filter on host arrays     new = hep_pose_from_input
+  (b) frame bytes in: old = the frame composition exactly as latency_b1 builds it   new = hep_pose_from_i420
+      (torch H2D of the frame, hep_preprocess_i420_device, hep_run_device, hep_decode_device, hep_filter_device, D2H of the rows)
+
+Every measurement runs in a child process; old and new alternate, twice each (old, new, old, new).  Then the new calls once each with
+HEP_POSE_UPLOAD=pinned and =direct: camera and payload copied into the handle's pinned buffer and sent as one copy, against two
+copies straight from the caller's pageable memory (the library's default is the second: it measured faster).
+A child that fails ends the run: nothing further is started on the device.
+
+Acceptance (the rule of NOTEBOOK.md section 15), stated per regime: spread = |old run 1 - old run 2| of the p50;
+  (b) the new call's slower run is not above the old composition's slower run by more than that spread;
+  (a) the new call's slower run is below the old composition's faster run by more than that spread.
+
+    python tools/pose_call_time.py [--calls 300] [--warmup 20] [--json FILE]
+"""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+CLS_BIAS_KEY = "classifier.header.pointwise_conv.conv.bias"
+
+
+def child(args):
+    import numpy as np
+    import torch
+
+    from hmd_ego_pose_amd import _capi
+    from hmd_ego_pose_amd.model import Session
+    from hmd_ego_pose_amd.weights import seeded_state_dict
+    assert torch.cuda.is_available(), "needs the MI355X"
+    lib = _capi.lib()
+    dev = torch.device("cuda", 0)
+    phi, S, M, thr = 0, 512, 100, 0.5
+    sd = seeded_state_dict(phi, 0)
+    rng = np.random.Generator(np.random.PCG64(5))
+    x = rng.standard_normal((1, 3, S, S)).astype(np.float32)
+    shift = 0.0                                       # latency_b1's load knob: the quantile of the logits that leaves ~30 candidates
+    for _ in range(6):
+        sd_l = dict(sd); sd_l[CLS_BIAS_KEY] = sd[CLS_BIAS_KEY] - shift
+        s = Session(sd_l, phi, S, 1, "fp32", dev)
+        p = s.forward(torch.from_numpy(x).to(dev), want_features=False)[2].double().flatten()
+        n_pass = int((p > thr).sum())
+        if 10 <= n_pass <= 60:
+            break
+        pc = p.clamp(1e-6, 1 - 1e-6)
+        shift += float(torch.quantile(torch.log(pc / (1 - pc)), 1.0 - 30.0 / p.numel()))
+        s.close()
+    N = s.num_anchors
+    cam = np.array([[480, 480, 128, 128, 1000, 1.0]], np.float32)
+    FH, FW = 720, 1280
+    frame = rng.integers(0, 256, (1, FH * FW * 3 // 2), dtype=np.uint8)
+    top = {"found": np.empty(1, np.int32), "score": np.empty(1, np.float32), "label": np.empty(1, np.int32), "index": np.empty(1, np.int32),
+           "box": np.empty((1, 4), np.float32), "rotation": np.empty((1, 3), np.float32), "translation": np.empty((1, 3), np.float32),
+           "hand": np.empty((1, 63), np.float32)}
+    top_ptrs = [top[k].ctypes.data for k in Session._POSE_KEYS]
+    row0 = {}
+
+    if args.child == "old":
+        ho = [np.empty((1, N, k), np.float32) for k in s.out_width]
+        hb, ht = np.empty((1, N, 4), np.float32), np.empty((1, N, 3), np.float32)
+        hd_ = [np.empty((1, M, 4), np.float32), np.empty((1, M), np.float32), np.empty((1, M), np.int32), np.empty((1, M, 3), np.float32),
+               np.empty((1, M, 3), np.float32), np.empty((1, M, 63), np.float32), np.empty((1, M), np.int32), np.empty((1,), np.int32)]
+
+        def call_a():
+            _capi.check(lib.hep_run(s.handle, x.ctypes.data, 1, None, *[o.ctypes.data for o in ho]))
+            _capi.check(lib.hep_decode(s.handle, ho[0].ctypes.data, ho[3].ctypes.data, cam.ctypes.data, 1, hb.ctypes.data, ht.ctypes.data))
+            _capi.check(lib.hep_filter(s.handle, hb.ctypes.data, ho[1].ctypes.data, ho[2].ctypes.data, ht.ctypes.data, ho[4].ctypes.data, 1, thr, 0.5, M,
+                                       *[a.ctypes.data for a in hd_]))
+            row0["a"] = (int(hd_[6][0, 0]), float(hd_[1][0, 0]))
+
+        tframe = torch.from_numpy(frame)
+        st = torch.cuda.Stream(dev)
+        cam_d = torch.from_numpy(cam).to(dev)
+        pre = torch.empty((1, S, S, 3), dtype=torch.float32, device=dev)
+        xv = pre.permute(0, 3, 1, 2)
+        xstr = (ctypes.c_int64 * 4)(*xv.stride())
+        bx, tr = torch.empty((1, N, 4), device=dev), torch.empty((1, N, 3), device=dev)
+        f = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+        i = lambda *sh: torch.empty(sh, dtype=torch.int32, device=dev)
+        det = [f(1, M, 4), f(1, M), i(1, M), f(1, M, 3), f(1, M, 3), f(1, M, 63), i(1, M), i(1)]
+
+        def call_b():
+            with torch.cuda.stream(st):
+                fd = tframe.to(dev, non_blocking=True)
+                _capi.check(lib.hep_preprocess_i420_device(s.handle, fd.data_ptr(), 1, FH, FW, 256, 512, pre.data_ptr(), st.cuda_stream))
+                _capi.check(lib.hep_run_device(s.handle, xv.data_ptr(), xstr, 1, None, None, st.cuda_stream))
+                _capi.check(lib.hep_decode_device(s.handle, None, None, cam_d.data_ptr(), 1, bx.data_ptr(), tr.data_ptr(), st.cuda_stream))
+                _capi.check(lib.hep_filter_device(s.handle, bx.data_ptr(), None, None, tr.data_ptr(), None, 1, thr, 0.5, M, *[d.data_ptr() for d in det], st.cuda_stream))
+                rows = [d.cpu() for d in det]                # D2H of the detection rows (synchronises the stream)
+            row0["b"] = (int(rows[6][0, 0]), float(rows[1][0, 0]))
+    else:
+        def call_a():
+            _capi.check(lib.hep_pose_from_input(s.handle, x.ctypes.data, 1, cam.ctypes.data, thr, *top_ptrs))
+            row0["a"] = (int(top["index"][0]), float(top["score"][0]))
+
+        def call_b():
+            _capi.check(lib.hep_pose_from_i420(s.handle, frame.ctypes.data, 1, FH, FW, 256, 512, cam.ctypes.data, thr, *top_ptrs))
+            row0["b"] = (int(top["index"][0]), float(top["score"][0]))
+
+    def stats(ts):
+        ts = sorted(ts)
+        return {"p50_ms": round(ts[len(ts) // 2], 4), "p99_ms": round(ts[min(len(ts) - 1, int(len(ts) * 0.99))], 4), "min_ms": round(ts[0], 4)}
+
+    def back_to_back(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize(dev)
+        ts = []
+        for _ in range(args.calls):
+            t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+        return stats(ts)
+
+    def paced(fn, hz):
+        ts, period = [], 1.0 / hz
+        nxt = time.perf_counter() + period
+        for _ in range(args.calls):
+            while time.perf_counter() < nxt:
+                time.sleep(max(0.0, min(0.002, nxt - time.perf_counter())))
+            nxt += period
+            t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+        return stats(ts)
+
+    out = {"path": args.child, "upload": os.environ.get("HEP_POSE_UPLOAD", "default"), "candidates": n_pass,
+           "a": back_to_back(call_a), "a_60hz": paced(call_a, 60.0), "b": back_to_back(call_b), "b_60hz": paced(call_b, 60.0),
+           "row0": row0, "forward_launches": lib.hep_kernel_count(s.handle, 1)}
+    s.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+# per call, beside the forward's own launches (hep_kernel_count; one eager stem launch + one graph replay)
+LAUNCHES = {
+    "old a": "kernels: decode 1, filter 1; copies: H2D 1 + 3 + 5 (input; regression, translation, camera; boxes and four heads), D2H 5 + 2 + 8; three synchronises",
+    "new a": "kernels: top-1 1; copies: H2D 2 (camera, input), D2H 1 (320 bytes); one synchronise",
+    "old b": "kernels: preprocess 3, decode 1, filter 1; copies: H2D 1 (frame), D2H 8 (rows, each synchronising)",
+    "new b": "kernels: preprocess 3, top-1 1; copies: H2D 2 (camera, frame), D2H 1 (320 bytes); one synchronise",
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--json", default=None, help="also write every child's result to this file")
+    ap.add_argument("--timeout", type=int, default=180, help="time limit of one measuring child process, seconds")
+    ap.add_argument("--child", default=None, choices=["old", "new"], help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    runs = []
+    for path, upload in (("old", None), ("new", None), ("old", None), ("new", None), ("new", "pinned"), ("new", "direct")):
+        env = dict(os.environ)
+        env.pop("HEP_POSE_UPLOAD", None)
+        if upload:
+            env["HEP_POSE_UPLOAD"] = upload
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--calls", str(args.calls), "--warmup", str(args.warmup)]
+        r = subprocess.run(cmd, timeout=args.timeout, env=env, capture_output=True, text=True)
+        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+        if r.returncode != 0 or not line:
+            print(r.stdout[-2000:], r.stderr[-4000:], sep="\n")
+            sys.exit(f"the {path} child failed (exit status {r.returncode}): nothing further is started")
+        runs.append(json.loads(line[0][7:]))
+        d = runs[-1]
+        print(f"{path:<3} upload={d['upload']:<7} candidates={d['candidates']}  " + "  ".join(
+            f"{k}: p50 {d[k]['p50_ms']:.4f} p99 {d[k]['p99_ms']:.4f}" for k in ("a", "a_60hz", "b", "b_60hz")), flush=True)
+    old = [r for r in runs if r["path"] == "old"]
+    new = [r for r in runs if r["path"] == "new" and r["upload"] == "default"]
+    assert all(r["row0"] == runs[0]["row0"] for r in runs), [r["row0"] for r in runs]      # every path returns the same top detection
+    verdict = {}
+    for k in ("a", "a_60hz", "b", "b_60hz"):
+        o, n = [r[k]["p50_ms"] for r in old], [r[k]["p50_ms"] for r in new]
+        spread = abs(o[0] - o[1])
+        ok = (max(n) < min(o) - spread) if k.startswith("a") else (max(n) <= max(o) + spread)
+        verdict[k] = {"old_p50": o, "new_p50": n, "old_spread": round(spread, 4), "met": bool(ok)}
+        print(f"{k:<7} old p50 {o}  new p50 {n}  old spread {spread:.4f} ms  -> {'met' if ok else 'NOT met'}")
+    print(f"forward: {runs[0]['forward_launches']} launches (one eager, the rest one graph replay)")
+    for k, v in LAUNCHES.items():
+        print(f"{k}: {v}")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"runs": runs, "verdict": verdict, "launches": LAUNCHES}, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
