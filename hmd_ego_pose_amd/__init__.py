@@ -24,6 +24,12 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name == "Trainer":
         from .trainer import Trainer
         return Trainer
+    if name == "PlateauSchedule":
+        from .trainer import PlateauSchedule
+        return PlateauSchedule
+    if name in ("DeviceEvaluator", "evaluate_device", "gt_table"):
+        from . import evaluate
+        return getattr(evaluate, name)
     if name == "InflightPool":
         from .pipeline import InflightPool
         return InflightPool

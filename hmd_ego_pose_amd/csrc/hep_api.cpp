@@ -795,6 +795,34 @@ int hep_pose_errors(int device, const float* points, int num_points, const float
   return 0;
 } HEP_CATCH_INT
 
+// ---- evaluator: matching and pose metrics of a batch in one launch ----
+static_assert(HEP_SCORE_GT_DOUBLES == SCORE_GT_DOUBLES && HEP_SCORE_RECORD_DOUBLES == SCORE_RECORD_DOUBLES, "the tables of include/hep.h are the kernel's");
+int hep_score_detections_device(const float* det_boxes, const float* det_scores, const int32_t* det_labels, const float* det_rotation,
+                                const float* det_translation, const float* det_hand, int batch, int rows, const double* gt,
+                                const float* points, int num_points, int max_points, int label, float score_threshold,
+                                int max_detections, double iou_threshold, double* records, float* out_scores, int32_t* out_tp,
+                                void* stream) try {
+  // every check before any HIP call
+  const std::pair<const void*, const char*> ptrs[] = {{det_boxes, "det_boxes"}, {det_scores, "det_scores"}, {det_labels, "det_labels"},
+      {det_rotation, "det_rotation"}, {det_translation, "det_translation"}, {gt, "gt"}, {points, "points"}, {records, "records"},
+      {out_scores, "out_scores"}, {out_tp, "out_tp"}};
+  for (const auto& p : ptrs)
+    if (!p.first) return fail(HEP_ERR_INVALID, std::string("hep_score_detections_device: ") + p.second + " is NULL");
+  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_score_detections_device: batch must be >= 1");
+  if (rows < 1 || rows > SCORE_MAX_ROWS) return fail(HEP_ERR_INVALID, "hep_score_detections_device: rows outside 1..256");
+  if (max_detections < 1 || max_detections > rows) return fail(HEP_ERR_INVALID, "hep_score_detections_device: max_detections outside 1..rows");
+  if (num_points < 1) return fail(HEP_ERR_INVALID, "hep_score_detections_device: num_points must be >= 1");
+  if (max_points < 1 || max_points > 1024) return fail(HEP_ERR_INVALID, "hep_score_detections_device: max_points must be in 1..1024 (the reference uses 1000)");
+  ScoreArgs a;
+  a.boxes = det_boxes; a.scores = det_scores; a.labels = det_labels; a.rotation = det_rotation; a.translation = det_translation; a.hand = det_hand;
+  a.gt = gt; a.points = points; a.records = records; a.out_scores = out_scores; a.out_tp = out_tp;
+  a.B = batch; a.rows = rows; a.P = num_points; a.max_points = max_points; a.label = label; a.max_det = max_detections;
+  a.score_thr = score_threshold; a.iou_thr = iou_threshold;
+  launch_score(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

@@ -338,6 +338,21 @@ struct PoseErrArgs {
 };
 void launch_pose_errors(const PoseErrArgs&, hipStream_t);
 
+// ---- evaluator: per-image matching + all pose metrics of the matched pair (k_score.hip; eval/common.py:866-1121) ----
+#define SCORE_GT_DOUBLES 88          // HEP_SCORE_GT_DOUBLES
+#define SCORE_RECORD_DOUBLES 16      // HEP_SCORE_RECORD_DOUBLES
+#define SCORE_MAX_ROWS 256
+struct ScoreArgs {
+  const float* boxes; const float* scores; const int32_t* labels;      // [B][rows][4|1|1], the rows of the detection filter
+  const float* rotation; const float* translation; const float* hand;  // [B][rows][3|3|63]; hand nullable
+  const double* gt;                                                    // [B][SCORE_GT_DOUBLES]
+  const float* points;                                                 // [P,3]
+  double* records; float* out_scores; int32_t* out_tp;                 // [B][SCORE_RECORD_DOUBLES], [B][max_det], [B][max_det]
+  int B, rows, P, max_points, label, max_det;
+  float score_thr; double iou_thr;
+};
+void launch_score(const ScoreArgs&, hipStream_t);
+
 // ---- training side: anchor-target assignment (generators/utils/anchors.py:69-221) ----
 #define AT_MAX_GT 64
 struct AnchorTargetArgs {

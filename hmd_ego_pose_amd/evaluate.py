@@ -19,6 +19,10 @@ it runs here:
                               dataset's ``hands/<frame>_coords_3d.npy`` (generators/colibri.py:430-436)
   AP                          ``compute_ap`` (eval/common.py:328-354)
 
+``evaluate_device`` / ``DeviceEvaluator`` run the same loop with matching and EVERY metric above on the GPU - one launch of
+hep_score_detections_device per batch (csrc/k_score.hip), one device-to-host copy per evaluation - and add the keys train.py
+reports and steers by (``ADD(-S)``, ``mixed_distance_mean`` / ``_std``, ``translation_tip_std``; train.py:255-334).
+
 ``python -m hmd_ego_pose_amd.evaluate --dataset-path <object folder> --weights ckpt.pth --phi 0`` runs it on a
 supplied dataset; nothing ships with the reference (dataset, checkpoint and mesh are absent), so the numbers of the
 paper cannot be reproduced here - tests drive this module with a synthetic folder.
@@ -278,7 +282,7 @@ def evaluate(dataset: LinemodFolder, model, image_size: int, score_threshold: fl
     if detections_out is not None:
         detections_out.extend(all_det)
 
-    fp, tp, scores = [], [], []
+    tp, scores = [], []
     pairs = []                      # (rvec_gt, t_gt, rvec_pr, t_pr, drill_tip) of every correct 2D detection
     pair_cam, hand_err = [], []     # its camera matrix; mean joint distance in mm where the dataset carries hand joints
     for i, (boxes, sc, labels, rots, trans, hands) in enumerate(all_det):
@@ -293,42 +297,208 @@ def evaluate(dataset: LinemodFolder, model, image_size: int, score_threshold: fl
             ov = compute_overlap(boxes[d:d + 1], ann["bbox"][None])[0, 0]
             if ov >= iou_threshold and not detected:
                 detected = True
-                fp.append(0); tp.append(1)
+                tp.append(1)
                 pairs.append((ann["rotation"], ann["translation"], rots[d].astype(np.float64), trans[d].astype(np.float64), ann["drill_tip"]))
                 pair_cam.append(dataset.camera[i])
                 if "coords_3d" in ann:       # eval/common.py:970-982: mean over the 21 joints of |gt - pred|, metres -> mm
                     hand_err.append(float(np.linalg.norm(ann["coords_3d"] - hands[d].astype(np.float64).reshape(21, 3), axis=-1).mean() * 1000.0))
             else:
-                fp.append(1); tp.append(0)
-    num_ann = float(n)
-    out: Dict[str, float] = {"num_annotations": num_ann, "num_matched": float(len(pairs))}
-    order = np.argsort(-np.asarray(scores), kind="stable") if scores else np.zeros(0, np.int64)
-    tpc, fpc = np.cumsum(np.asarray(tp, np.float64)[order]), np.cumsum(np.asarray(fp, np.float64)[order])
-    out["AP"] = compute_ap(tpc / num_ann, tpc / np.maximum(tpc + fpc, np.finfo(np.float64).eps)) if num_ann else 0.0
+                tp.append(0)
+    m = None
     if pairs:
         rg, tg, rp, tpv, tips = (np.stack([p[k] for p in pairs]) for k in range(5))
         add, add_s = pose_errors(dataset.points, rg, tg, rp, tpv, device.index or 0)
-        thr = dataset.diameter * diameter_threshold
         t_diff = np.linalg.norm(tg - tpv, axis=1)
         r_diff = np.array([calc_rotation_diff(axis_angle_to_matrix(a), axis_angle_to_matrix(b)) for a, b in zip(rg, rp)])
         tip_gt = np.stack([axis_angle_to_matrix(a) @ t[:3] + b for a, b, t in zip(rg, tg, tips)])
         tip_pr = np.stack([axis_angle_to_matrix(a) @ t[:3] + b for a, b, t in zip(rp, tpv, tips)])
         reproj = np.array([reprojection_distance(dataset.points, axis_angle_to_matrix(a), b, axis_angle_to_matrix(c), d_, K)
                            for a, b, c, d_, K in zip(rg, tg, rp, tpv, pair_cam)])
+        m = dict(add=add, add_s=add_s, t_diff=t_diff, r_diff=r_diff, tip=np.linalg.norm(tip_gt - tip_pr, axis=1), reproj=reproj, hand=hand_err)
+    return metric_summary(float(n), scores, tp, m, dataset.diameter * diameter_threshold)
+
+
+def metric_summary(num_ann: float, scores, tp, m: Optional[dict], thr: float, symmetric: Optional[bool] = None) -> Dict[str, float]:
+    """The tail of eval/common.py:1040-1121 shared by ``evaluate`` and ``DeviceEvaluator.result``: AP from the considered detections'
+    scores and flags (stable sort by score), the accuracy fractions over ``num_ann`` and ``np.mean`` / ``np.std`` over the matched
+    images in image order.  ``m``: the per-matched-image arrays add, add_s, t_diff, r_diff, tip, reproj and the list hand, or None
+    without a match.  ``symmetric`` not None adds the keys train.py reports and steers by: ``translation_tip_std``, ``ADD(-S)`` and
+    ``mixed_distance_mean`` / ``mixed_distance_std`` (the ADD-S values of a symmetric object, else ADD: eval/common.py:1105-1119)."""
+    out: Dict[str, float] = {"num_annotations": num_ann, "num_matched": float(len(m["add"])) if m else 0.0}
+    tp = np.asarray(tp, np.float64)
+    order = np.argsort(-np.asarray(scores), kind="stable") if len(scores) else np.zeros(0, np.int64)
+    tpc, fpc = np.cumsum(tp[order]), np.cumsum((1.0 - tp)[order])
+    out["AP"] = compute_ap(tpc / num_ann, tpc / np.maximum(tpc + fpc, np.finfo(np.float64).eps)) if num_ann else 0.0
+    if m:
+        add, add_s, t_diff, r_diff, tip, reproj, hand_err = (m[k] for k in ("add", "add_s", "t_diff", "r_diff", "tip", "reproj", "hand"))
         out["2D_projection"] = float(np.sum(reproj <= 5.0) / num_ann)
         out["2D_projection_distance_mean"] = float(reproj.mean())
-        if hand_err:
+        if len(hand_err):
             out["hand_mean"] = float(np.mean(hand_err)); out["hand_std"] = float(np.std(hand_err))
         out.update({"ADD": float(np.sum(add <= thr) / num_ann), "ADD-S": float(np.sum(add_s <= thr) / num_ann),
                     "5cm_5deg": float(np.sum((t_diff <= 50) & (r_diff <= 5)) / num_ann),
                     "translation_mean": float(t_diff.mean()), "translation_std": float(t_diff.std()),
                     "rotation_mean": float(r_diff.mean()), "rotation_std": float(r_diff.std()),
-                    "translation_tip_mean": float(np.linalg.norm(tip_gt - tip_pr, axis=1).mean()),
+                    "translation_tip_mean": float(tip.mean()),
                     "ADD_distance_mean": float(add.mean()), "ADD_distance_std": float(add.std()),
                     "ADD-S_distance_mean": float(add_s.mean()), "ADD-S_distance_std": float(add_s.std())})
     else:
         out.update({"ADD": 0.0, "ADD-S": 0.0, "5cm_5deg": 0.0, "2D_projection": 0.0})
+    if symmetric is not None:
+        mixed = "ADD-S" if symmetric else "ADD"
+        out["ADD(-S)"] = out[mixed]
+        nan = float("nan")                          # the reference's np.mean of nothing
+        out["translation_tip_std"] = float(tip.std()) if m else nan
+        out["mixed_distance_mean"] = out[mixed + "_distance_mean"] if m else nan
+        out["mixed_distance_std"] = out[mixed + "_distance_std"] if m else nan
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the same loop with matching and every pose metric on the GPU (hep_score_detections_device, csrc/k_score.hip)
+# ----------------------------------------------------------------------------------------------------------------
+GT_DOUBLES, RECORD_DOUBLES = _capi.SCORE_GT_DOUBLES, _capi.SCORE_RECORD_DOUBLES
+
+
+def gt_table(annotations: Sequence[dict], cameras: Sequence[np.ndarray], scale) -> np.ndarray:
+    """The ground-truth table of hep_score_detections_device, float64 [n, 88], from ``LinemodFolder``'s annotation dicts
+    (``bbox``, ``rotation`` axis-angle, ``translation``, ``drill_tip``, optional ``coords_3d`` [21,3] in metres) and camera
+    matrices.  ``scale``: the image scale of every frame (network size / longer image side), one number or one per image.
+    Layout: include/hep.h.  One annotation per image."""
+    n = len(annotations)
+    if len(cameras) != n:
+        raise ValueError("gt_table: one camera matrix per annotation")
+    scales = np.broadcast_to(np.asarray(scale, np.float64), (n,))
+    t = np.zeros((n, GT_DOUBLES), np.float64)
+    for i, (ann, K) in enumerate(zip(annotations, cameras)):
+        K = np.asarray(K, np.float64)
+        t[i, 0] = 1.0
+        t[i, 1:5] = np.asarray(ann["bbox"], np.float64).reshape(4)
+        t[i, 5:8] = np.asarray(ann["rotation"], np.float64).reshape(3)
+        t[i, 8:11] = np.asarray(ann["translation"], np.float64).reshape(3)
+        t[i, 11:14] = np.asarray(ann["drill_tip"], np.float64).reshape(-1)[:3]
+        t[i, 14:18] = (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        t[i, 18] = scales[i]
+        if "coords_3d" in ann:
+            t[i, 19] = 1.0
+            t[i, 20:83] = np.asarray(ann["coords_3d"], np.float64).reshape(63)
+    return t
+
+
+class DeviceEvaluator:
+    """``evaluate`` with nothing on the host until the end: ``add`` runs preprocess (uint8 frames), ``model.detect`` and ONE launch of
+    hep_score_detections_device per batch - per-image matching plus ADD, ADD-S, translation, rotation, tip, reprojection and hand
+    errors of the matched pair - into device buffers of ``capacity`` images at a running offset, with no device-to-host copy and no
+    synchronisation; ``result`` makes the one copy of an evaluation and finishes on the host like ``evaluate`` (``metric_summary``).
+
+    ``model``: a ``TrainModelWithLoss`` in eval mode on the GPU.  ``points`` [P,3] and ``diameter``: the object model.  The
+    dictionary has every key of ``evaluate`` plus ``translation_tip_std``, ``ADD(-S)`` and ``mixed_distance_mean`` / ``_std`` (ADD-S
+    values when ``symmetric``, else ADD - what train.py steps ``ReduceLROnPlateau`` with and keeps the best checkpoint by).
+
+    Scope: one annotation per image and one evaluated ``label``, as ``evaluate`` has; several annotations per image are not
+    supported."""
+
+    def __init__(self, model, points, diameter: float, image_size: int, capacity: int, score_threshold: float = 0.05, max_detections: int = 10,
+                 iou_threshold: float = 0.5, diameter_threshold: float = 0.1, label: int = 0, symmetric: bool = False,
+                 device: Optional[torch.device] = None, max_points: int = 1000):
+        if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
+            raise ValueError("DeviceEvaluator: capacity and max_detections must be >= 1, max_points in 1..1024")
+        self.model, self.image_size, self.capacity = model, int(image_size), int(capacity)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+            raise ValueError("DeviceEvaluator: points must be [P,3] with P >= 1")
+        self.points = torch.from_numpy(pts).to(self.device)
+        self.diameter, self.diameter_threshold = float(diameter), float(diameter_threshold)
+        self.score_threshold, self.max_detections, self.iou_threshold = float(score_threshold), int(max_detections), float(iou_threshold)
+        self.label, self.symmetric, self.max_points = int(label), bool(symmetric), int(max_points)
+        # ONE allocation, so that ``result`` is one copy: records [capacity,16] float64 | scores [capacity,M] float32 | flags [capacity,M] int32
+        M, C = self.max_detections, self.capacity
+        self._buf = torch.zeros((C * (RECORD_DOUBLES * 8 + M * 8),), dtype=torch.uint8, device=self.device)
+        self._records = self._buf[:C * RECORD_DOUBLES * 8].view(torch.float64).view(C, RECORD_DOUBLES)
+        self._scores = self._buf[C * RECORD_DOUBLES * 8:C * (RECORD_DOUBLES * 8 + M * 4)].view(torch.float32).view(C, M)
+        self._tp = self._buf[C * (RECORD_DOUBLES * 8 + M * 4):].view(torch.int32).view(C, M)
+        self.count = 0
+
+    def reset(self) -> None:
+        self.count = 0
+
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor) -> None:
+        """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6]
+        (``LinemodFolder.camera_input``); ``gt`` float64 [B,88] (``gt_table``); all on the evaluator's device.  Everything is checked on
+        the host before the library sees a pointer; a batch that does not fit the remaining capacity raises ValueError."""
+        dev = self.device
+        for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
+            if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
+                raise ValueError(f"DeviceEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
+        if frames.dim() != 4 or frames.shape[0] < 1:
+            raise ValueError("DeviceEvaluator.add: frames must be uint8 [B,H,W,3] or float32 [B,3,S,S]")
+        B = int(frames.shape[0])
+        if frames.dtype == torch.uint8:
+            if frames.shape[3] != 3:
+                raise ValueError("DeviceEvaluator.add: uint8 frames must be [B,H,W,3]")
+        elif frames.dtype != torch.float32 or tuple(frames.shape[1:]) != (3, self.image_size, self.image_size):
+            raise ValueError(f"DeviceEvaluator.add: an image must be float32 [B,3,{self.image_size},{self.image_size}]")
+        if tuple(camera.shape) != (B, 6) or tuple(gt.shape) != (B, GT_DOUBLES):
+            raise ValueError(f"DeviceEvaluator.add: camera must be [{B},6] and gt [{B},{GT_DOUBLES}]")
+        if self.count + B > self.capacity:
+            raise ValueError(f"DeviceEvaluator.add: {self.count} + {B} images exceed the capacity of {self.capacity}")
+        x = self.model.model.session(self.image_size, B, dev).preprocess(frames) if frames.dtype == torch.uint8 else frames
+        det = self.model.detect(x, camera)
+        rows = int(det["scores"].shape[1]) if det["scores"].dim() == 2 else 0
+        for k, w, dt in (("boxes", 4, torch.float32), ("scores", None, torch.float32), ("labels", None, torch.int32), ("rotation", 3, torch.float32),
+                         ("translation", 3, torch.float32), ("hand", 63, torch.float32)):
+            t = det[k]
+            if tuple(t.shape) != ((B, rows) if w is None else (B, rows, w)) or t.dtype != dt or t.device != dev:
+                raise ValueError(f"DeviceEvaluator.add: detection rows '{k}' have shape {tuple(t.shape)} / {t.dtype} on {t.device}")
+        if not 1 <= rows <= 256 or self.max_detections > rows:
+            raise ValueError(f"DeviceEvaluator.add: {rows} detection rows: must be 1..256 and >= max_detections {self.max_detections}")
+        d = [det[k].contiguous() for k in ("boxes", "scores", "labels", "rotation", "translation", "hand")]
+        g = gt.contiguous()
+        o = self.count
+        _capi.check(_capi.lib().hep_score_detections_device(
+            *[t.data_ptr() for t in d], B, rows, g.data_ptr(), self.points.data_ptr(), int(self.points.shape[0]), self.max_points,
+            self.label, self.score_threshold, self.max_detections, self.iou_threshold,
+            self._records[o:].data_ptr(), self._scores[o:].data_ptr(), self._tp[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        self.count += B
+
+    def result(self) -> Dict[str, float]:
+        """The metric dictionary of the images added since the last ``reset``: one device-to-host copy (which waits for the launches),
+        then the host arithmetic of ``evaluate``'s tail."""
+        host = self._buf.cpu().numpy()
+        C, M, n = self.capacity, self.max_detections, self.count
+        rec = host[:C * RECORD_DOUBLES * 8].view(np.float64).reshape(C, RECORD_DOUBLES)[:n]
+        sc = host[C * RECORD_DOUBLES * 8:C * (RECORD_DOUBLES * 8 + M * 4)].view(np.float32).reshape(C, M)[:n]
+        tp = host[C * (RECORD_DOUBLES * 8 + M * 4):].view(np.int32).reshape(C, M)[:n]
+        keep = np.arange(M)[None, :] < rec[:, 0:1]                       # the considered detections, image by image, in row order
+        r = rec[rec[:, 1] == 1.0]
+        m = None
+        if r.shape[0]:
+            m = dict(add=r[:, 5], add_s=r[:, 6], t_diff=r[:, 7], r_diff=r[:, 8], tip=r[:, 9], reproj=r[:, 10], hand=r[:, 11][~np.isnan(r[:, 11])])
+        return metric_summary(float(n), [float(v) for v in sc[keep]], tp[keep], m, self.diameter * self.diameter_threshold, symmetric=self.symmetric)
+
+
+def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
+                    iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16, device: Optional[torch.device] = None,
+                    symmetric: bool = False) -> Dict[str, float]:
+    """``evaluate`` through a ``DeviceEvaluator``: same arguments (the per-detection ``detections_out`` aside - no detection ever reaches
+    the host), same dictionary plus the keys train.py steers by.  One host synchronisation for the whole folder."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    n = len(dataset)
+    ev = DeviceEvaluator(model, dataset.points, dataset.diameter, image_size, max(n, 1), score_threshold, max_detections, iou_threshold,
+                         diameter_threshold, symmetric=symmetric, device=device)
+    for i0 in range(0, n, batch_size):
+        idx = list(range(i0, min(n, i0 + batch_size)))
+        frames = [dataset.load_image(i) for i in idx]
+        h, w = frames[0].shape[:2]
+        if any(f.shape[:2] != (h, w) for f in frames):
+            raise ValueError("frames of one batch must share a size")
+        scale = image_size / max(h, w)
+        u8 = torch.from_numpy(np.stack(frames)).to(device)
+        cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
+        gt = torch.from_numpy(gt_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale)).to(device)
+        ev.add(u8, cam, gt)
+    return ev.result()
 
 
 def main(argv=None):

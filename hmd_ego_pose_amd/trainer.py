@@ -59,6 +59,44 @@ def combined_layout(compound_coef: int, num_classes: int = 1, freeze_backbone: b
     return dict(total=base, parts=parts, entries=entries, kind=kind)
 
 
+class PlateauSchedule:
+    """The learning-rate rule of the reference's epoch tail, train.py:107-109 and :276 - ``ReduceLROnPlateau(mode='min', factor=0.5,
+    patience=15, threshold=1e-4, threshold_mode='rel', cooldown=0, min_lr=1e-7, eps=1e-8)`` - restated on the host with no optimiser
+    behind it (``Trainer`` keeps its rate in ``Trainer.lr``): ``tr.lr = sched.step(res["mixed_distance_mean"])``.
+
+    ``step(metric)``: a metric below ``best * (1 - threshold)`` becomes the best and clears the count of bad epochs; any other (a NaN
+    included) adds one.  More than ``patience`` bad epochs in a row: ``lr = max(lr * factor, min_lr)`` - unless that lowers the rate
+    by ``eps`` or less, then it stays - and the count starts again.  Exactly torch's arithmetic (tests/test_score_cpu.py)."""
+
+    def __init__(self, lr: float, factor: float = 0.5, patience: int = 15, threshold: float = 1e-4, min_lr: float = 1e-7, eps: float = 1e-8):
+        if not factor < 1.0:
+            raise ValueError("PlateauSchedule: factor must be < 1.0")
+        self.lr, self.factor, self.patience, self.threshold = float(lr), float(factor), int(patience), float(threshold)
+        self.min_lr, self.eps = float(min_lr), float(eps)
+        self.best, self.num_bad_epochs, self.last_epoch = float("inf"), 0, 0
+
+    def step(self, metric) -> float:
+        current = float(metric)
+        self.last_epoch += 1
+        if current < self.best * (1.0 - self.threshold):
+            self.best, self.num_bad_epochs = current, 0
+        else:
+            self.num_bad_epochs += 1
+        if self.num_bad_epochs > self.patience:
+            new_lr = max(self.lr * self.factor, self.min_lr)
+            if self.lr - new_lr > self.eps:
+                self.lr = new_lr
+            self.num_bad_epochs = 0
+        return self.lr
+
+    def state_dict(self) -> Dict[str, float]:
+        return dict(lr=self.lr, best=self.best, num_bad_epochs=self.num_bad_epochs, last_epoch=self.last_epoch)
+
+    def load_state_dict(self, sd) -> None:
+        self.lr, self.best = float(sd["lr"]), float(sd["best"])
+        self.num_bad_epochs, self.last_epoch = int(sd["num_bad_epochs"]), int(sd["last_epoch"])
+
+
 class _Shape:
     """Everything one (size, batch, hand) needs, allocated once."""
 
