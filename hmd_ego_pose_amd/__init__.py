@@ -27,7 +27,7 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name == "PlateauSchedule":
         from .trainer import PlateauSchedule
         return PlateauSchedule
-    if name in ("DeviceEvaluator", "evaluate_device", "gt_table"):
+    if name in ("DeviceEvaluator", "evaluate_device", "gt_table", "SceneEvaluator", "SceneFolder", "evaluate_scene_device", "gt_scene_table"):
         from . import evaluate
         return getattr(evaluate, name)
     if name == "InflightPool":

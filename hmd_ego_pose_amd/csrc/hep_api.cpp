@@ -823,6 +823,39 @@ int hep_score_detections_device(const float* det_boxes, const float* det_scores,
   return 0;
 } HEP_CATCH_INT
 
+static_assert(HEP_SCORE_MAX_ANNOTATIONS == SCORE_MAX_ANN, "the annotation limit of include/hep.h is the kernel's");
+int hep_score_scene_device(const float* det_boxes, const float* det_scores, const int32_t* det_labels, const float* det_rotation,
+                           const float* det_translation, const float* det_hand, int batch, int rows, const double* gt, int amax,
+                           const float* points, const int32_t* point_offsets, int num_labels, int max_points, float score_threshold,
+                           int max_detections, double iou_threshold, double* records, float* out_scores, int32_t* out_tp,
+                           int32_t* out_labels, int32_t* out_count, void* stream) try {
+  // every check before any HIP call
+  const std::pair<const void*, const char*> ptrs[] = {{det_boxes, "det_boxes"}, {det_scores, "det_scores"}, {det_labels, "det_labels"},
+      {det_rotation, "det_rotation"}, {det_translation, "det_translation"}, {gt, "gt"}, {points, "points"}, {point_offsets, "point_offsets"},
+      {records, "records"}, {out_scores, "out_scores"}, {out_tp, "out_tp"}, {out_labels, "out_labels"}, {out_count, "out_count"}};
+  for (const auto& p : ptrs)
+    if (!p.first) return fail(HEP_ERR_INVALID, std::string("hep_score_scene_device: ") + p.second + " is NULL");
+  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_score_scene_device: batch must be >= 1");
+  if (rows < 1 || rows > SCORE_MAX_ROWS) return fail(HEP_ERR_INVALID, "hep_score_scene_device: rows outside 1..256");
+  if (max_detections < 1 || max_detections > rows) return fail(HEP_ERR_INVALID, "hep_score_scene_device: max_detections outside 1..rows");
+  if (amax < 1 || amax > SCORE_MAX_ANN) return fail(HEP_ERR_INVALID, "hep_score_scene_device: amax outside 1..16");
+  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, "hep_score_scene_device: num_labels outside 1..63");
+  if (point_offsets[0] != 0) return fail(HEP_ERR_INVALID, "hep_score_scene_device: point_offsets[0] must be 0");
+  for (int l = 0; l < num_labels; l++)
+    if (point_offsets[l + 1] <= point_offsets[l])
+      return fail(HEP_ERR_INVALID, "hep_score_scene_device: point_offsets must increase (label " + std::to_string(l) + " has no point)");
+  if (max_points < 1 || max_points > 1024) return fail(HEP_ERR_INVALID, "hep_score_scene_device: max_points must be in 1..1024 (the reference uses 1000)");
+  SceneScoreArgs a;
+  a.boxes = det_boxes; a.scores = det_scores; a.labels = det_labels; a.rotation = det_rotation; a.translation = det_translation; a.hand = det_hand;
+  a.gt = gt; a.points = points; a.records = records; a.out_scores = out_scores; a.out_tp = out_tp; a.out_labels = out_labels; a.out_count = out_count;
+  a.B = batch; a.rows = rows; a.amax = amax; a.num_labels = num_labels; a.max_points = max_points; a.max_det = max_detections;
+  a.score_thr = score_threshold; a.iou_thr = iou_threshold;
+  for (int l = 0; l <= SCORE_MAX_LABELS; l++) a.offsets[l] = l <= num_labels ? point_offsets[l] : point_offsets[num_labels];
+  launch_score_scene(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

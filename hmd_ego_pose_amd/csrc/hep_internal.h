@@ -352,6 +352,21 @@ struct ScoreArgs {
   float score_thr; double iou_thr;
 };
 void launch_score(const ScoreArgs&, hipStream_t);
+// several annotations per image, several labels (score_scene_kernel): gt and records gain the annotation-slot axis
+#define SCORE_MAX_ANN 16             // HEP_SCORE_MAX_ANNOTATIONS
+#define SCORE_MAX_LABELS 63
+struct SceneScoreArgs {
+  const float* boxes; const float* scores; const int32_t* labels;      // [B][rows][4|1|1]
+  const float* rotation; const float* translation; const float* hand;  // [B][rows][3|3|63]; hand nullable
+  const double* gt;                                                    // [B][amax][SCORE_GT_DOUBLES], slot 83 = label
+  const float* points;                                                 // the clouds of all labels, concatenated
+  double* records;                                                     // [B][amax][SCORE_RECORD_DOUBLES]
+  float* out_scores; int32_t* out_tp; int32_t* out_labels; int32_t* out_count;      // [B][max_det] x 3, [B]
+  int B, rows, amax, num_labels, max_points, max_det;
+  float score_thr; double iou_thr;
+  int32_t offsets[SCORE_MAX_LABELS + 1];                               // label l owns points [offsets[l], offsets[l+1]); checked on the host
+};
+void launch_score_scene(const SceneScoreArgs&, hipStream_t);
 
 // ---- training side: anchor-target assignment (generators/utils/anchors.py:69-221) ----
 #define AT_MAX_GT 64

@@ -22,6 +22,10 @@ it runs here:
 ``evaluate_device`` / ``DeviceEvaluator`` run the same loop with matching and EVERY metric above on the GPU - one launch of
 hep_score_detections_device per batch (csrc/k_score.hip), one device-to-host copy per evaluation - and add the keys train.py
 reports and steers by (``ADD(-S)``, ``mixed_distance_mean`` / ``_std``, ``translation_tip_std``; train.py:255-334).
+``evaluate_scene_device`` / ``SceneEvaluator`` / ``SceneFolder`` do it for scenes - several annotations per image over several labels,
+every label scored in ONE launch of hep_score_scene_device per batch, each detection assigned to the annotation of its label it
+overlaps most (eval/common.py:953-960), per-label dictionaries and evaluate_model's average of them (eval/common.py:92-265);
+``--object-ids 1,5,6`` on the command line.
 
 ``python -m hmd_ego_pose_amd.evaluate --dataset-path <object folder> --weights ckpt.pth --phi 0`` runs it on a
 supplied dataset; nothing ships with the reference (dataset, checkpoint and mesh are absent), so the numbers of the
@@ -395,8 +399,8 @@ class DeviceEvaluator:
     dictionary has every key of ``evaluate`` plus ``translation_tip_std``, ``ADD(-S)`` and ``mixed_distance_mean`` / ``_std`` (ADD-S
     values when ``symmetric``, else ADD - what train.py steps ``ReduceLROnPlateau`` with and keeps the best checkpoint by).
 
-    Scope: one annotation per image and one evaluated ``label``, as ``evaluate`` has; several annotations per image are not
-    supported."""
+    Scope: one annotation per image and one evaluated ``label``, as ``evaluate`` has; several annotations per image and several
+    labels in one pass: ``SceneEvaluator``."""
 
     def __init__(self, model, points, diameter: float, image_size: int, capacity: int, score_threshold: float = 0.05, max_detections: int = 10,
                  iou_threshold: float = 0.5, diameter_threshold: float = 0.1, label: int = 0, symmetric: bool = False,
@@ -501,11 +505,276 @@ def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_thresh
     return ev.result()
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# scenes: several annotations per image and several labels in one launch (hep_score_scene_device, csrc/k_score.hip)
+# ----------------------------------------------------------------------------------------------------------------
+MAX_ANNOTATIONS, MAX_LABELS = _capi.SCORE_MAX_ANNOTATIONS, _capi.SCORE_MAX_LABELS
+FRACTION_KEYS = ("AP", "ADD", "ADD-S", "ADD(-S)", "5cm_5deg", "2D_projection")
+
+
+def gt_scene_table(annotations_per_image: Sequence[Sequence[dict]], cameras: Sequence[np.ndarray], scale, amax: Optional[int] = None) -> np.ndarray:
+    """The ground-truth table of hep_score_scene_device, float64 [n, amax, 88]: one list of annotation dicts per image (``gt_table``'s
+    keys plus ``label``, an integer >= 0), one camera matrix per image.  Row layout: ``gt_table``'s with slot 83 = label; padding
+    rows have slot 0 == 0; camera and scale are repeated in every row of an image.  ``amax``: the slot count, by default the largest
+    annotation count (at least 1).  ValueError for more than 16 annotations in an image (or more than ``amax``), a negative or
+    non-integral label, or a missing key."""
+    n = len(annotations_per_image)
+    if len(cameras) != n:
+        raise ValueError("gt_scene_table: one camera matrix per image")
+    most = max([len(a) for a in annotations_per_image], default=0)
+    if most > MAX_ANNOTATIONS:
+        raise ValueError(f"gt_scene_table: {most} annotations in one image, at most {MAX_ANNOTATIONS} are supported")
+    amax = max(1, most) if amax is None else int(amax)
+    if not 1 <= amax <= MAX_ANNOTATIONS or most > amax:
+        raise ValueError(f"gt_scene_table: amax {amax} must be in 1..{MAX_ANNOTATIONS} and hold the {most} annotations of the fullest image")
+    scales = np.broadcast_to(np.asarray(scale, np.float64), (n,))
+    t = np.zeros((n, amax, GT_DOUBLES), np.float64)
+    for i, (anns, K) in enumerate(zip(annotations_per_image, cameras)):
+        K = np.asarray(K, np.float64)
+        t[i, :, 14:18] = (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+        t[i, :, 18] = scales[i]
+        for k, ann in enumerate(anns):
+            missing = [q for q in ("bbox", "rotation", "translation", "drill_tip", "label") if q not in ann]
+            if missing:
+                raise ValueError(f"gt_scene_table: annotation {k} of image {i} lacks {missing}")
+            label = ann["label"]
+            if label != int(label) or int(label) < 0:
+                raise ValueError(f"gt_scene_table: annotation {k} of image {i} has label {label!r}: must be an integer >= 0")
+            t[i, k, :14] = gt_table([ann], [K], scales[i])[0, :14]
+            if "coords_3d" in ann:
+                t[i, k, 19] = 1.0
+                t[i, k, 20:83] = np.asarray(ann["coords_3d"], np.float64).reshape(63)
+            t[i, k, 83] = float(int(label))
+    return t
+
+
+def scene_mean(per_label: Dict[int, Dict[str, float]]) -> Dict[str, float]:
+    """evaluate_model's averaging of the per-label dictionaries (eval/common.py:92-265): the fraction keys are summed over ALL labels
+    and divided by the number of labels that have annotations; every other key is the plain average over the labels that have
+    annotations (the ones the reference's metric dictionaries hold) - a label with annotations and no match contributes NaN, the
+    reference's np.mean of nothing.  ``num_annotations`` / ``num_matched`` are totals."""
+    with_ann = [l for l, d in per_label.items() if d["num_annotations"] > 0]
+    out = {"num_annotations": float(sum(d["num_annotations"] for d in per_label.values())),
+           "num_matched": float(sum(d["num_matched"] for d in per_label.values())), "num_labels": float(len(with_ann))}
+    if not with_ann:
+        return out
+    nan = float("nan")
+    for k in FRACTION_KEYS:
+        out[k] = sum(d[k] for d in per_label.values()) / len(with_ann)
+    keys = sorted({k for l in with_ann for k in per_label[l]} - set(FRACTION_KEYS) - {"num_annotations", "num_matched"})
+    for k in keys:
+        out[k] = sum(per_label[l].get(k, nan) for l in with_ann) / len(with_ann)
+    return out
+
+
+class SceneEvaluator:
+    """``DeviceEvaluator`` for scenes: up to ``amax`` annotations per image over ``len(models)`` labels.  ``add`` runs preprocess,
+    ``model.detect`` (ONE forward per batch, whatever the number of labels) and ONE launch of hep_score_scene_device per batch into
+    ONE allocation at a running offset, with no device-to-host copy; ``result`` makes the one copy of an evaluation.
+
+    ``models``: a sequence indexed by label of ``(points [P,3], diameter, symmetric)``.  ``result()`` returns ``{"labels": {l: dict},
+    "mean": dict}``: each per-label dictionary is ``metric_summary`` of that label's annotation count, considered scores and flags
+    (image, then row order) and matched records (image, then slot order); ``"mean"`` is ``scene_mean`` of them -
+    ``result()["mean"]["mixed_distance_mean"]`` is the reference's ``mean_mixed_transformed_mean``, what train.py:273 steps the
+    scheduler with."""
+
+    def __init__(self, model, models, image_size: int, capacity: int, amax: int, score_threshold: float = 0.05, max_detections: int = 10,
+                 iou_threshold: float = 0.5, diameter_threshold: float = 0.1, device: Optional[torch.device] = None, max_points: int = 1000):
+        if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
+            raise ValueError("SceneEvaluator: capacity and max_detections must be >= 1, max_points in 1..1024")
+        if not 1 <= amax <= MAX_ANNOTATIONS:
+            raise ValueError(f"SceneEvaluator: amax must be in 1..{MAX_ANNOTATIONS}")
+        if not 1 <= len(models) <= MAX_LABELS:
+            raise ValueError(f"SceneEvaluator: 1..{MAX_LABELS} object models, one per label")
+        self.model, self.image_size, self.capacity, self.amax = model, int(image_size), int(capacity), int(amax)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        clouds, self.diameters, self.symmetric = [], [], []
+        for l, (points, diameter, symmetric) in enumerate(models):
+            pts = np.ascontiguousarray(points, dtype=np.float32)
+            if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+                raise ValueError(f"SceneEvaluator: the points of label {l} must be [P,3] with P >= 1")
+            clouds.append(pts); self.diameters.append(float(diameter)); self.symmetric.append(bool(symmetric))
+        self.num_labels = len(clouds)
+        self._offsets = (ctypes.c_int32 * (self.num_labels + 1))(*np.concatenate(([0], np.cumsum([len(c) for c in clouds]))).tolist())
+        self.points = torch.from_numpy(np.concatenate(clouds)).to(self.device)
+        self.diameter_threshold = float(diameter_threshold)
+        self.score_threshold, self.max_detections, self.iou_threshold = float(score_threshold), int(max_detections), float(iou_threshold)
+        self.max_points = int(max_points)
+        # ONE allocation, so that ``result`` is one copy: records [C,amax,16] float64 | scores [C,M] float32 | flags, labels [C,M] int32 | counts [C] int32
+        M, C, A = self.max_detections, self.capacity, self.amax
+        self._cut = np.cumsum([0, C * A * RECORD_DOUBLES * 8, C * M * 4, C * M * 4, C * M * 4, C * 4]).tolist()
+        self._buf = torch.zeros((self._cut[-1],), dtype=torch.uint8, device=self.device)
+        part = lambda k, dt, *shape: self._buf[self._cut[k]:self._cut[k + 1]].view(dt).view(*shape)
+        self._records, self._scores = part(0, torch.float64, C, A, RECORD_DOUBLES), part(1, torch.float32, C, M)
+        self._tp, self._labels, self._counts = part(2, torch.int32, C, M), part(3, torch.int32, C, M), part(4, torch.int32, C)
+        self.count = 0
+
+    def reset(self) -> None:
+        self.count = 0
+
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor) -> None:
+        """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6];
+        ``gt`` float64 [B,amax,88] (``gt_scene_table``); all on the evaluator's device.  Everything is checked on the host before the
+        library sees a pointer; a batch that does not fit the remaining capacity raises ValueError."""
+        dev = self.device
+        for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
+            if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
+                raise ValueError(f"SceneEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
+        if frames.dim() != 4 or frames.shape[0] < 1:
+            raise ValueError("SceneEvaluator.add: frames must be uint8 [B,H,W,3] or float32 [B,3,S,S]")
+        B = int(frames.shape[0])
+        if frames.dtype == torch.uint8:
+            if frames.shape[3] != 3:
+                raise ValueError("SceneEvaluator.add: uint8 frames must be [B,H,W,3]")
+        elif frames.dtype != torch.float32 or tuple(frames.shape[1:]) != (3, self.image_size, self.image_size):
+            raise ValueError(f"SceneEvaluator.add: an image must be float32 [B,3,{self.image_size},{self.image_size}]")
+        if tuple(camera.shape) != (B, 6) or tuple(gt.shape) != (B, self.amax, GT_DOUBLES):
+            raise ValueError(f"SceneEvaluator.add: camera must be [{B},6] and gt [{B},{self.amax},{GT_DOUBLES}]")
+        if self.count + B > self.capacity:
+            raise ValueError(f"SceneEvaluator.add: {self.count} + {B} images exceed the capacity of {self.capacity}")
+        x = self.model.model.session(self.image_size, B, dev).preprocess(frames) if frames.dtype == torch.uint8 else frames
+        det = self.model.detect(x, camera)
+        rows = int(det["scores"].shape[1]) if det["scores"].dim() == 2 else 0
+        for k, w, dt in (("boxes", 4, torch.float32), ("scores", None, torch.float32), ("labels", None, torch.int32), ("rotation", 3, torch.float32),
+                         ("translation", 3, torch.float32), ("hand", 63, torch.float32)):
+            t = det[k]
+            if tuple(t.shape) != ((B, rows) if w is None else (B, rows, w)) or t.dtype != dt or t.device != dev:
+                raise ValueError(f"SceneEvaluator.add: detection rows '{k}' have shape {tuple(t.shape)} / {t.dtype} on {t.device}")
+        if not 1 <= rows <= 256 or self.max_detections > rows:
+            raise ValueError(f"SceneEvaluator.add: {rows} detection rows: must be 1..256 and >= max_detections {self.max_detections}")
+        d = [det[k].contiguous() for k in ("boxes", "scores", "labels", "rotation", "translation", "hand")]
+        g = gt.contiguous()
+        o = self.count
+        _capi.check(_capi.lib().hep_score_scene_device(
+            *[t.data_ptr() for t in d], B, rows, g.data_ptr(), self.amax, self.points.data_ptr(), self._offsets, self.num_labels, self.max_points,
+            self.score_threshold, self.max_detections, self.iou_threshold, self._records[o:].data_ptr(), self._scores[o:].data_ptr(),
+            self._tp[o:].data_ptr(), self._labels[o:].data_ptr(), self._counts[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        self.count += B
+
+    def result(self) -> Dict[str, dict]:
+        """``{"labels": {l: dict}, "mean": dict}`` of the images added since the last ``reset``: one device-to-host copy (which waits
+        for the launches), then the host arithmetic."""
+        host = self._buf.cpu().numpy()
+        C, M, A, n = self.capacity, self.max_detections, self.amax, self.count
+        part = lambda k, dt, *shape: host[self._cut[k]:self._cut[k + 1]].view(dt).reshape(*shape)[:n]
+        return summarise_scene(part(0, np.float64, C, A, RECORD_DOUBLES), part(1, np.float32, C, M), part(2, np.int32, C, M), part(3, np.int32, C, M),
+                               part(4, np.int32, C), self.diameters, self.symmetric, self.diameter_threshold)
+
+
+def summarise_scene(rec: np.ndarray, sc: np.ndarray, tp: np.ndarray, labels: np.ndarray, counts: np.ndarray, diameters: Sequence[float],
+                    symmetric: Sequence[bool], diameter_threshold: float = 0.1) -> Dict[str, dict]:
+    """The host tail of ``SceneEvaluator.result`` on the five outputs of hep_score_scene_device (records [n,amax,16], scores / flags /
+    labels [n,M], counts [n]): per label ``metric_summary``, and ``scene_mean`` of the labels."""
+    keep = np.arange(sc.shape[1])[None, :] < counts[:, None] if sc.shape[0] else np.zeros(sc.shape, bool)
+    flat = rec.reshape(-1, RECORD_DOUBLES)                                # image, then slot
+    per_label = {}
+    for l, (diameter, sym) in enumerate(zip(diameters, symmetric)):
+        own = keep & (labels == l)
+        r = flat[(flat[:, 0] == 1.0) & (flat[:, 12] == l)]
+        num_ann = float(r.shape[0])
+        r = r[r[:, 1] == 1.0]
+        m = None
+        if r.shape[0]:
+            m = dict(add=r[:, 5], add_s=r[:, 6], t_diff=r[:, 7], r_diff=r[:, 8], tip=r[:, 9], reproj=r[:, 10], hand=r[:, 11][~np.isnan(r[:, 11])])
+        per_label[l] = metric_summary(num_ann, [float(v) for v in sc[own]], tp[own], m, diameter * diameter_threshold, symmetric=sym)
+    return {"labels": per_label, "mean": scene_mean(per_label)}
+
+
+class SceneFolder:
+    """One scene folder of a Linemod-format dataset (``<root>/data/<NN>/`` as ``LinemodFolder`` reads it) with EVERY ground-truth entry of
+    a frame whose ``obj_id`` is in ``object_ids``; the label of an entry is the index of its object in that list.  ``scene_id``: the
+    folder number (default: the first object id).  Boxes come from ``obj_bb`` (x, y, w, h) or, for the objects ``mask_values`` maps to
+    their byte in the frame's merged mask ``mask/<frame>.png``, from the pixels equal to that byte.  ``models``: per label
+    ``(points, diameter, symmetric)`` from ``models/`` (symmetric: models_info.yml lists symmetries for the object)."""
+
+    def __init__(self, dataset_path: str, object_ids: Sequence[int], scene_id: Optional[int] = None, fold: int = 0, split: str = "test",
+                 mask_values: Optional[Dict[int, int]] = None, image_extension: str = ".png"):
+        import yaml
+        loader = getattr(yaml, "CSafeLoader", yaml.SafeLoader)
+        self.object_ids = [int(o) for o in object_ids]
+        if not self.object_ids or len(set(self.object_ids)) != len(self.object_ids):
+            raise ValueError("SceneFolder: object_ids must be a non-empty list without repeats")
+        scene_id = self.object_ids[0] if scene_id is None else int(scene_id)
+        self.object_path = os.path.join(dataset_path, "data", f"{scene_id:02}")
+        self.model_path = os.path.join(dataset_path, "models")
+        with open(os.path.join(self.object_path, f"{split}_{fold}.txt")) as f:
+            examples = [e.strip() for e in f if e.strip()]
+        with open(os.path.join(self.object_path, f"gt_{fold}.yml")) as f:
+            gt = yaml.load(f, Loader=loader)
+        with open(os.path.join(self.object_path, f"info_{fold}.yml")) as f:
+            info = yaml.load(f, Loader=loader)
+        with open(os.path.join(self.model_path, "models_info.yml")) as f:
+            models = yaml.load(f, Loader=loader)
+        self.models = [(load_ply_vertices(os.path.join(self.model_path, f"obj_{o:02}.ply")), float(models[o]["diameter"]),
+                        any(k.startswith("symmetries") for k in models[o])) for o in self.object_ids]
+        names = sorted(n for n in os.listdir(os.path.join(self.object_path, "rgb"))
+                       if n.endswith(image_extension) and n[:-len(image_extension)] in examples)
+        self.image_paths = [os.path.join(self.object_path, "rgb", n) for n in names]
+        self.annotations, self.camera = [], []
+        mask_values = mask_values or {}
+        for n in names:
+            key = int(n.split(".")[0])
+            mask = None
+            entries = []
+            for a in gt[key]:
+                if a["obj_id"] not in self.object_ids:
+                    continue
+                R = np.array(a["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
+                entry = {"label": self.object_ids.index(a["obj_id"]), "rotation": matrix_to_axis_angle(R),
+                         "translation": np.array(a["cam_t_m2c"], dtype=np.float64),
+                         "drill_tip": np.array(a.get("drill_tip_transform", [0, 0, 0, 1]), dtype=np.float64)}
+                if a["obj_id"] in mask_values:
+                    if mask is None:
+                        from PIL import Image
+                        mask = np.asarray(Image.open(os.path.join(self.object_path, "mask", n)))
+                        mask = mask.reshape(mask.shape[0], mask.shape[1], -1)[:, :, 0]
+                    ys, xs = np.nonzero(mask == mask_values[a["obj_id"]])
+                    entry["bbox"] = np.array([xs.min(), ys.min(), xs.max(), ys.max()], dtype=np.float32) if ys.size else np.zeros(4, np.float32)
+                else:                                     # Linemod's own field: x, y, w, h
+                    x, y, w, h = a["obj_bb"]
+                    entry["bbox"] = np.array([x, y, x + w, y + h], dtype=np.float32)
+                entries.append(entry)
+            if len(entries) > MAX_ANNOTATIONS:
+                raise ValueError(f"SceneFolder: frame {n} holds {len(entries)} annotations, at most {MAX_ANNOTATIONS} are supported")
+            self.annotations.append(entries)
+            self.camera.append(np.array(info[key]["cam_K"], dtype=np.float64).reshape(3, 3))
+        self.amax = max([len(e) for e in self.annotations] + [1])
+
+    __len__ = LinemodFolder.__len__
+    load_image = LinemodFolder.load_image
+    camera_input = LinemodFolder.camera_input
+
+
+def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
+                          iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16,
+                          device: Optional[torch.device] = None) -> Dict[str, dict]:
+    """A ``SceneFolder`` through a ``SceneEvaluator``, driven like ``evaluate_device``: one forward and one scoring launch per batch,
+    one host synchronisation for the whole folder.  Returns ``SceneEvaluator.result()``."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    n = len(dataset)
+    ev = SceneEvaluator(model, dataset.models, image_size, max(n, 1), dataset.amax, score_threshold, max_detections, iou_threshold,
+                        diameter_threshold, device=device)
+    for i0 in range(0, n, batch_size):
+        idx = list(range(i0, min(n, i0 + batch_size)))
+        frames = [dataset.load_image(i) for i in idx]
+        h, w = frames[0].shape[:2]
+        if any(f.shape[:2] != (h, w) for f in frames):
+            raise ValueError("frames of one batch must share a size")
+        scale = image_size / max(h, w)
+        u8 = torch.from_numpy(np.stack(frames)).to(device)
+        cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
+        gt = torch.from_numpy(gt_scene_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale, dataset.amax)).to(device)
+        ev.add(u8, cam, gt)
+    return ev.result()
+
+
 def main(argv=None):
     """The reference's ``evaluate.py`` entry point for this path (evaluate.py:18-128; its argument names)."""
     ap = argparse.ArgumentParser(description="Evaluate an HMD-EgoPose checkpoint on a Linemod-format object folder (MI355X)")
     ap.add_argument("--dataset-path", required=True, help="folder holding data/<NN>/ and models/ (reference: --dataset-path)")
     ap.add_argument("--object-id", type=int, default=1)
+    ap.add_argument("--object-ids", default=None, help="comma-separated object ids of one scene folder, e.g. 1,5,6: every listed object is a label "
+                    "and every annotation of a frame is scored (evaluate_scene_device); the folder is data/<first id>/")
     ap.add_argument("--fold", type=int, default=0)
     ap.add_argument("--phi", type=int, default=0)
     ap.add_argument("--img-size", default="256,256")
@@ -520,9 +789,17 @@ def main(argv=None):
         state = {k: torch.from_numpy(np.array(v)) for k, v in load_pack(open(a.weights, "rb").read()).items()}
     else:
         state = strip_checkpoint_prefix(torch.load(a.weights, map_location="cpu", weights_only=True))
-    m = HMDEgoPose({"iter": 0}, num_classes=1, compound_coef=a.phi, onnx_export=True, input_sizes=[size] * 9, precision=a.precision)
+    ids = [int(v) for v in a.object_ids.split(",")] if a.object_ids else None
+    m = HMDEgoPose({"iter": 0}, num_classes=len(ids) if ids else 1, compound_coef=a.phi, onnx_export=True, input_sizes=[size] * 9, precision=a.precision)
     m.load_state_dict(state, strict=False)
     model = TrainModelWithLoss(m.to("cuda").eval()).eval()
+    if ids:
+        res = evaluate_scene_device(SceneFolder(a.dataset_path, ids, fold=a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size)
+        for name, d in [(f"object {o}", res["labels"][l]) for l, o in enumerate(ids)] + [("mean", res["mean"])]:
+            print(name)
+            for k, v in d.items():
+                print(f"{k:>28s}: {v:.6g}")
+        return res
     res = evaluate(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size)
     for k, v in res.items():
         print(f"{k:>24s}: {v:.6g}")

@@ -36,6 +36,8 @@
  *                                 metric arithmetic of evaluate.py's loop, eval/common.py:866-1121)
  *   hep_score_detections_device <- the per-image body of evaluate_model, eval/common.py:866-1121: matching (942-957) and the
  *                                 metrics of the matched pair (682-778, 646-679, 970-982) for a whole batch in one launch
+ *   hep_score_scene_device     <- the same loop as the reference writes it (912-1030): every label, several annotations per
+ *                                 image, each detection assigned to the annotation of its label it overlaps most
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a
  * negative hep_status, never throws (every entry point catches what its C++ body could raise -> HEP_ERR_INTERNAL) and never aborts; hep_last_error() gives a thread-local
@@ -265,7 +267,7 @@ int hep_pose_errors_device(const float* points, int num_points, const float* rve
  *   2  matched row, or -1      6  ADD-S                        10  reprojection distance, pixels
  *   3  matched score           7  translation difference       11  hand error, mm
  *   12-15 zero.  Slots 3-11 of an image without a match, and slot 11 without hand ground truth (or det_hand), hold NaN.
- * One annotation per image and one evaluated label.  Checked before any HIP call, HEP_ERR_INVALID with the reason in
+ * One annotation per image and one evaluated label (several of either: hep_score_scene_device below).  Checked before any HIP call, HEP_ERR_INVALID with the reason in
  * hep_last_error: a NULL pointer (except det_hand and stream), batch < 1, rows outside 1..256, max_detections outside
  * 1..rows, num_points < 1, max_points outside 1..1024 (what hep_pose_errors_device accepts). */
 #define HEP_SCORE_GT_DOUBLES 88
@@ -275,6 +277,48 @@ int hep_score_detections_device(const float* det_boxes, const float* det_scores,
                                 int batch, int rows, const double* gt, const float* points, int num_points, int max_points,
                                 int label, float score_threshold, int max_detections, double iou_threshold,
                                 double* records, float* out_scores, int32_t* out_tp, void* stream);
+
+/* hep_score_detections_device for scenes: up to HEP_SCORE_MAX_ANNOTATIONS = 16 annotations per image over num_labels labels, every
+ * label and every annotation scored in ONE launch (the generic loop of eval/common.py:912-1030 behind post_filter).  Stateless
+ * like its sibling: no handle, no allocation, no host synchronisation, asynchronous on `stream`.  One workgroup of 256 threads
+ * per (image, annotation slot).
+ * det_*: as above; det_hand may be NULL.
+ * gt: [batch][amax][HEP_SCORE_GT_DOUBLES], each row in the layout above with slot 83 = the annotation's label as an integral
+ *   double; slot 0 marks a valid row, padding rows have slot 0 == 0.  Camera and scale (14-18) are repeated in every row of an
+ *   image; the metrics of a pair read them from the pair's row, the image scale of the detection boxes comes from row 0.
+ * points: the model clouds of all labels concatenated; point_offsets (HOST memory, [num_labels + 1], copied into the kernel
+ *   argument): label l owns points [point_offsets[l], point_offsets[l+1]).
+ * DEFINITION, image b (roundings as for hep_score_detections_device: float32 score compare, float32(box) / float32(scale),
+ * float32(r) * float32(pi), float64 IoU with the "+1" convention compared with >=, ground truth rounded to float32 for ADD and
+ * ADD-S only):
+ *   1. a candidate is a row with score > score_threshold; the first max_detections candidates are kept (the cap counts every
+ *      label), THEN the kept rows whose label is outside 0..num_labels-1 are dropped; the rest are the considered rows.  Their
+ *      score, flag and label go to out_scores / out_tp / out_labels [batch][max_detections], compacted in row order and padded
+ *      with -1.0f / -1 / -1; their number goes to out_count[b]
+ *   2. each considered row of label l, in row order, looks at the valid annotations of label l: none - flag 0; otherwise the
+ *      assigned annotation is the FIRST one with the maximal IoU (np.argmax), and the flag is 1 only when that IoU >=
+ *      iou_threshold and the annotation has not been assigned before - then the annotation is taken.  A row whose best
+ *      annotation is already taken is a false positive even if it overlaps another free annotation above the threshold
+ *   3. every taken annotation's pair is scored exactly as hep_score_detections_device scores its pair, with the points of the
+ *      annotation's label and that row's ground truth, tip offset, camera and hand joints; ADD and ADD-S are bit-identical to
+ *      hep_pose_errors_device on the same pair with that label's cloud
+ * records: [batch][amax][HEP_SCORE_RECORD_DOUBLES], one row per annotation slot:
+ *   0  valid (0 / 1)           3  matched score                5-11  the seven metrics, as above
+ *   1  matched (0 / 1)         4  matched IoU                  12    label
+ *   2  matched row, or -1                                      13-15 zero
+ *   Slots 3-11 of an unmatched row hold NaN, slot 11 also without hand ground truth or det_hand.  An invalid row has slots 0-1
+ *   zero, slot 2 = -1, slots 3-11 NaN, slot 12 = -1; a valid row whose label is outside 0..num_labels-1 is treated as invalid
+ *   (the device cannot refuse it without a synchronisation; hmd_ego_pose_amd.evaluate.gt_scene_table refuses it on the host).
+ * Checked before any HIP call, HEP_ERR_INVALID with the reason in hep_last_error: a NULL pointer (except det_hand and stream),
+ * batch < 1, rows outside 1..256, max_detections outside 1..rows, amax outside 1..16, num_labels outside 1..63,
+ * point_offsets[0] != 0, an offset that does not increase (every label needs at least one point), max_points outside 1..1024. */
+#define HEP_SCORE_MAX_ANNOTATIONS 16
+int hep_score_scene_device(const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                           const float* det_rotation, const float* det_translation, const float* det_hand,
+                           int batch, int rows, const double* gt, int amax,
+                           const float* points, const int32_t* point_offsets /* HOST, [num_labels + 1] */, int num_labels, int max_points,
+                           float score_threshold, int max_detections, double iou_threshold,
+                           double* records, float* out_scores, int32_t* out_tp, int32_t* out_labels, int32_t* out_count, void* stream);
 
 /* Training side: anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 with the IoU
  * matrix of generators/utils/compute_overlap.pyx:33-73 and bbox_transform anchors.py:422-458, on device memory: per
