@@ -94,14 +94,41 @@ __device__ __forceinline__ long cvt_fp8x8(u32x4 raw, const float* s8, float inv_
   return (long)(((unsigned long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
+// 8 consecutive channels as they lie in memory: one 16-byte vector (bf16, 4 VGPRs) or two (fp32)
+template <bool BF16> struct Raw8;
+template <> struct Raw8<true> {
+  u32x4 v;
+  static __device__ __forceinline__ Raw8 load(const void* p) { Raw8 r; r.v = *reinterpret_cast<const u32x4*>(p); return r; }
+  __device__ __forceinline__ void load(const void* base, int64_t idx) { v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(base) + idx); }
+  __device__ __forceinline__ void store(void* p) const { *reinterpret_cast<u32x4*>(p) = v; }
+  __device__ __forceinline__ void zero() { v = (u32x4){0, 0, 0, 0}; }
+  __device__ __forceinline__ void unpack(float o[8]) const {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { o[2 * i] = __uint_as_float(v[i] << 16); o[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u); }
+  }
+  __device__ __forceinline__ float get(int c) const { return (c & 1) ? __uint_as_float(v[c >> 1] & 0xffff0000u) : __uint_as_float(v[c >> 1] << 16); }
+};
+template <> struct Raw8<false> {
+  f32x4 a, b;
+  static __device__ __forceinline__ Raw8 load(const void* p) { Raw8 r; r.a = reinterpret_cast<const f32x4*>(p)[0]; r.b = reinterpret_cast<const f32x4*>(p)[1]; return r; }
+  __device__ __forceinline__ void load(const void* base, int64_t idx) {
+    const f32x4* p = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx); a = p[0]; b = p[1];
+  }
+  __device__ __forceinline__ void store(void* p) const { reinterpret_cast<f32x4*>(p)[0] = a; reinterpret_cast<f32x4*>(p)[1] = b; }
+  __device__ __forceinline__ void zero() { a = (f32x4){0.f, 0.f, 0.f, 0.f}; b = a; }
+  __device__ __forceinline__ void unpack(float o[8]) const {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { o[i] = a[i]; o[4 + i] = b[i]; }
+  }
+  __device__ __forceinline__ float get(int c) const { return c < 4 ? a[c] : b[c - 4]; }
+};
+
 // 8 consecutive channels <-> 8 floats
 template <bool BF16> struct Vec8;
 template <> struct Vec8<true> {
   typedef bf16_t elem;
   static __device__ __forceinline__ void load(const void* base, int64_t idx, float v[8]) {
-    u32x4 r = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(base) + idx);
-#pragma unroll
-    for (int i = 0; i < 4; i++) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
+    Raw8<true> r; r.load(base, idx); r.unpack(v);
   }
   static __device__ __forceinline__ void store(void* base, int64_t idx, const float v[8]) {
     u32x4 r;
@@ -122,10 +149,7 @@ template <> struct Vec8<true> {
 template <> struct Vec8<false> {
   typedef float elem;
   static __device__ __forceinline__ void load(const void* base, int64_t idx, float v[8]) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
-    f32x4 a = p[0], b = p[1];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { v[i] = a[i]; v[4 + i] = b[i]; }
+    Raw8<false> r; r.load(base, idx); r.unpack(v);
   }
   static __device__ __forceinline__ void store(void* base, int64_t idx, const float v[8]) {
     f32x4* p = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(base) + idx);
@@ -141,6 +165,28 @@ template <> struct Vec8<false> {
   static __device__ __forceinline__ void load4(const void* base, int64_t idx, float v[4]) {
     f32x4 a = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx);
     v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
+  }
+};
+
+// The MFMA operand fragment of the 16x16 tile kernels - the one place that says how channels meet the matrix pipe.  A k-step is KSTEP
+// channels (32 bf16 / 16 fp32); lane group g = lane >> 4 owns the KLANE consecutive channels KLANE * g .. of it as one `raw` (16 bytes
+// either way), lane & 15 is the row (weights) or the pixel (activations).  mma is one k-step of a 16x16 tile, weights first: one
+// v_mfma_f32_16x16x32_bf16, or four chained v_mfma_f32_16x16x4_f32 (exact fp32; lane group g supplies k = 4 g + q).
+template <bool BF16> struct Frag;
+template <> struct Frag<true> {
+  typedef u32x4 raw;
+  static constexpr int KSTEP = 32, KLANE = 8;
+  static __device__ __forceinline__ f32x4 mma(const raw& w, const raw& x, f32x4 acc) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
+  }
+};
+template <> struct Frag<false> {
+  typedef f32x4 raw;
+  static constexpr int KSTEP = 16, KLANE = 4;
+  static __device__ __forceinline__ f32x4 mma(const raw& w, const raw& x, f32x4 acc) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[q], x[q], acc, 0, 0, 0);
+    return acc;
   }
 };
 

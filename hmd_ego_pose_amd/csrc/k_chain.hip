@@ -43,29 +43,6 @@ __device__ unsigned long long* g_chain_trace = nullptr;
 
 namespace {
 
-// 8 consecutive channels as they lie in memory: 16 bytes (bf16) or two 16-byte vectors (fp32)
-template <bool BF16> struct Raw8;
-template <> struct Raw8<true> {
-  u32x4 v;
-  static __device__ __forceinline__ Raw8 load(const void* p) { Raw8 r; r.v = *reinterpret_cast<const u32x4*>(p); return r; }
-  __device__ __forceinline__ void store(void* p) const { *reinterpret_cast<u32x4*>(p) = v; }
-  __device__ __forceinline__ void zero() { v = (u32x4){0, 0, 0, 0}; }
-  __device__ __forceinline__ void unpack(float o[8]) const {
-#pragma unroll
-    for (int i = 0; i < 4; i++) { o[2 * i] = __uint_as_float(v[i] << 16); o[2 * i + 1] = __uint_as_float(v[i] & 0xffff0000u); }
-  }
-};
-template <> struct Raw8<false> {
-  f32x4 a, b;
-  static __device__ __forceinline__ Raw8 load(const void* p) { Raw8 r; r.a = reinterpret_cast<const f32x4*>(p)[0]; r.b = reinterpret_cast<const f32x4*>(p)[1]; return r; }
-  __device__ __forceinline__ void store(void* p) const { reinterpret_cast<f32x4*>(p)[0] = a; reinterpret_cast<f32x4*>(p)[1] = b; }
-  __device__ __forceinline__ void zero() { a = (f32x4){0.f, 0.f, 0.f, 0.f}; b = a; }
-  __device__ __forceinline__ void unpack(float o[8]) const {
-#pragma unroll
-    for (int i = 0; i < 4; i++) { o[i] = a[i]; o[4 + i] = b[i]; }
-  }
-};
-
 // 8 channels of a map slot at pixel (y, x) as floats; zero outside the map (SAME padding of the pool / the depthwise halo).
 // The load is unconditional (clamped address) and the zero is a select: conditional loads would each sit in a basic
 // block of their own and serialise into one memory round trip per tap.
@@ -123,8 +100,9 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_kernel(ChainArgs a) {
   typedef Vec8<BF16> V;
   typedef typename V::elem T;
   typedef Raw8<BF16> R8;
-  typedef typename std::conditional<BF16, u32x4, f32x4>::type frag_t;
-  constexpr int PAD = BF16 ? 8 : 4, KSTEP = BF16 ? 32 : 16, KLANE = BF16 ? 8 : 4;
+  typedef Frag<BF16> F;
+  typedef typename F::raw frag_t;
+  constexpr int PAD = BF16 ? 8 : 4, KSTEP = F::KSTEP, KLANE = F::KLANE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   HEP_POISON(smem, a.lds_bytes);
   T* slots = reinterpret_cast<T*>(smem);
@@ -332,22 +310,14 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_kernel(ChainArgs a) {
           if (ks < ksteps) {
             frag_t xa = {};
             if (ks * KSTEP + KLANE * g < C) xa = *reinterpret_cast<const frag_t*>(arow + ks * KSTEP);
-            if constexpr (BF16) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr[ks]), __builtin_bit_cast(bf16x8, xa), acc, 0, 0, 0);
-            else {
-#pragma unroll
-              for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wfr[ks][q], xa[q], acc, 0, 0, 0);
-            }
+            acc = F::mma(wfr[ks], xa, acc);
           }
         }
       } else
       for (int ks = 0; ks < ksteps; ks++) {
         frag_t wf = {}, xa = {};
         if (ks * KSTEP + KLANE * g < C) { wf = *reinterpret_cast<const frag_t*>(wrow + ks * KSTEP); xa = *reinterpret_cast<const frag_t*>(arow + ks * KSTEP); }
-        if constexpr (BF16) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, xa), acc, 0, 0, 0);
-        else {
-#pragma unroll
-          for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q], xa[q], acc, 0, 0, 0);      // exact fp32; lane group g supplies k = 16 ks + 4 g + q
-        }
+        acc = F::mma(wf, xa, acc);
       }
       const int nn = nt * 16 + 4 * g;
       if (m < hw && nn < C) {

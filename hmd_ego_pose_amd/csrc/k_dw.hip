@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void dw_kernel(DwArgs a) {
     // bounds check and the compiler waited for each one before the next (18 dependent round trips per lane for 3x3 and
     // four pixels: the kernel lived on occupancy alone); with no condition at all and the rows unrolled it hoisted all
     // 18 loads (196 VGPRs, two waves per SIMD, slower).  The row loop is a real loop: WIN raw vectors live at a time.
-    typedef typename std::conditional<BF16, u32x4, f32x4>::type raw_t;
+    typedef typename Frag<BF16>::raw raw_t;
     typedef typename V::elem T;
     const unsigned char* in_b = reinterpret_cast<const unsigned char*>(a.in) + (int64_t)b * a.H * a.W * a.C * (int)sizeof(T);
     auto load_row = [&](int ky, raw_t* x0, raw_t* x1) {

@@ -20,6 +20,7 @@
 
 #include "hep_dev.h"
 #include "hep_internal.h"
+#include "tower_frag.h"
 
 // per-wave phase stamps (make trace: -DHEP_HEADS_TRACE), read back with hep_dbg_heads_trace() (tools/trace_heads.py): 0 start, 1 region loaded,
 // 2 + i layer i done (its results written back), 6 header operands parked, 7 end; 8: item id
@@ -31,27 +32,11 @@ __device__ unsigned long long* g_heads_trace = nullptr;
 #endif
 
 namespace {
-typedef __attribute__((ext_vector_type(2))) float hf2;
 constexpr int HF_C = 64, HF_P = HF_C + 8;          // channels, LDS pixel pitch (bf16 elements: 144 bytes)
 constexpr int HF_T = 16;                           // output tile side
 constexpr int HF_MTW = 3;                          // m-tiles per wave and layer (26 x 26 region at D = 4: 36 m-tiles on 16 waves)
 
-struct HAcc { hf2 a[4]; };                          // channels (0,2) (1,3) (4,6) (5,7) of a lane's eight: k_tower.hip's Frag<true>
-__device__ __forceinline__ void hf_fma_tap(HAcc& c, const u32x4& x, const float* w /* 8 swizzled weights in LDS */) {
-  const f32x4 wa = reinterpret_cast<const f32x4*>(w)[0], wb = reinterpret_cast<const f32x4*>(w)[1];
-  const hf2 e0 = {__uint_as_float(x[0] << 16), __uint_as_float(x[1] << 16)}, o0 = {__uint_as_float(x[0] & 0xffff0000u), __uint_as_float(x[1] & 0xffff0000u)};
-  const hf2 e1 = {__uint_as_float(x[2] << 16), __uint_as_float(x[3] << 16)}, o1 = {__uint_as_float(x[2] & 0xffff0000u), __uint_as_float(x[3] & 0xffff0000u)};
-  c.a[0] = __builtin_elementwise_fma(e0, (hf2){wa[0], wa[1]}, c.a[0]);
-  c.a[1] = __builtin_elementwise_fma(o0, (hf2){wa[2], wa[3]}, c.a[1]);
-  c.a[2] = __builtin_elementwise_fma(e1, (hf2){wb[0], wb[1]}, c.a[2]);
-  c.a[3] = __builtin_elementwise_fma(o1, (hf2){wb[2], wb[3]}, c.a[3]);
-}
-__device__ __forceinline__ u32x4 hf_pack(const HAcc& c) {
-  return (u32x4){pack_bf16x2(c.a[0][0], c.a[1][0]), pack_bf16x2(c.a[0][1], c.a[1][1]), pack_bf16x2(c.a[2][0], c.a[3][0]), pack_bf16x2(c.a[2][1], c.a[3][1])};
-}
-__device__ __forceinline__ f32x4 hf_mma(const u32x4& a, const u32x4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+typedef TowerFrag<true> F;                          // depthwise accumulator, fragment and k-step product: the tower's own (tower_frag.h)
 }  // namespace
 
 __global__ __launch_bounds__(1024) void heads_kernel(HeadsArgs a_by_value) {
@@ -124,17 +109,17 @@ __global__ __launch_bounds__(1024) void heads_kernel(HeadsArgs a_by_value) {
         u32x4 xa[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) {
-          HAcc acc; for (int e = 0; e < 4; e++) acc.a[e] = (hf2){0.f, 0.f};
+          F::Acc acc; F::zero(acc);
 #pragma unroll
           for (int q = 0; q < 9; q++)
-            hf_fma_tap(acc, *reinterpret_cast<const u32x4*>(ctr + ((q / 3 - 1) * RP + q % 3 - 1) * HF_P + ks * 32), wdw_s + q * 64 + ks * 32 + 8 * g);
-          xa[ks] = hf_pack(acc);
+            F::fma_tap(acc, *reinterpret_cast<const u32x4*>(ctr + ((q / 3 - 1) * RP + q % 3 - 1) * HF_P + ks * 32), wdw_s + q * 64 + ks * 32 + 8 * g);
+          xa[ks] = F::pack(acc);
         }
 #pragma unroll
         for (int nt = 0; nt < 4; nt++) {
           f32x4 acc = bias[nt];
-          acc = hf_mma(wf[nt][0], xa[0], acc);
-          acc = hf_mma(wf[nt][1], xa[1], acc);
+          acc = F::mma(wf[nt][0], xa[0], acc);
+          acc = F::mma(wf[nt][1], xa[1], acc);
           float v[4] = {acc[0], acc[1], acc[2], acc[3]};
           swish_n<true, 4>(v);
           res[s][nt] = (u32x2){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
@@ -171,11 +156,11 @@ __global__ __launch_bounds__(1024) void heads_kernel(HeadsArgs a_by_value) {
         const float* wd = wdw_s + (1 + h) * 576;
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) {
-          HAcc acc; for (int e = 0; e < 4; e++) acc.a[e] = (hf2){0.f, 0.f};
+          F::Acc acc; F::zero(acc);
 #pragma unroll
           for (int q = 0; q < 9; q++)
-            hf_fma_tap(acc, *reinterpret_cast<const u32x4*>(ctr + ((q / 3 - 1) * RP + q % 3 - 1) * HF_P + ks * 32), wd + q * 64 + ks * 32 + 8 * g);
-          xa_s[(wave * 2 + ks) * 64 + lane] = hf_pack(acc);
+            F::fma_tap(acc, *reinterpret_cast<const u32x4*>(ctr + ((q / 3 - 1) * RP + q % 3 - 1) * HF_P + ks * 32), wd + q * 64 + ks * 32 + 8 * g);
+          xa_s[(wave * 2 + ks) * 64 + lane] = F::pack(acc);
         }
       }
       __syncthreads();
@@ -194,8 +179,8 @@ __global__ __launch_bounds__(1024) void heads_kernel(HeadsArgs a_by_value) {
         const int n = nt * 16 + 4 * g;
         for (int mt = mt0; mt < mt1; mt++) {
           f32x4 acc = bs;
-          acc = hf_mma(w0, xa_s[(mt * 2) * 64 + lane], acc);
-          acc = hf_mma(w1, xa_s[(mt * 2 + 1) * 64 + lane], acc);
+          acc = F::mma(w0, xa_s[(mt * 2) * 64 + lane], acc);
+          acc = F::mma(w1, xa_s[(mt * 2 + 1) * 64 + lane], acc);
           const int pp = mt * 16 + r;
           if (pp < npx && n < N) {
             const int pr = udiv_f(pp, wdt, wdt_inv), y = by0 + r0 + pr, x = bx0 + q0 + pp - pr * wdt;

@@ -137,7 +137,7 @@ __device__ __forceinline__ void late_project(const LateArgs& a, const LateBlock&
           for (int j = 0; j < NTW; j++)
 #pragma unroll
             for (int mt = 0; mt < 4; mt++)
-              acc[j][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[s][j]), __builtin_bit_cast(bf16x8, x[mt]), acc[j][mt], 0, 0, 0);
+              acc[j][mt] = Frag<true>::mma(wf[s][j], x[mt], acc[j][mt]);
           const int kn = min(ks + s + R, KSH - 1);           // (past the slice: the last step again, never used)
 #pragma unroll
           for (int j = 0; j < NTW; j++) wf[s][j] = late_ldg(wp + (size_t)(kn * NTW + j) * 1024);
@@ -247,7 +247,7 @@ __device__ __forceinline__ void late_block(const LateArgs& a, const LateBlock& L
 #pragma unroll
       for (int mt = 0; mt < 4; mt++) {
         const u32x4 x = *reinterpret_cast<const u32x4*>(Xs + (mt * 16 + r) * XP + ks * 32 + 8 * g);
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr[ks]), __builtin_bit_cast(bf16x8, x), acc[mt], 0, 0, 0);
+        acc[mt] = Frag<true>::mma(wfr[ks], x, acc[mt]);
       }
     }
 #pragma unroll

@@ -70,8 +70,9 @@ __global__ __launch_bounds__(TS == 16 ? 1024 : 512) void mbf_kernel(MbfArgs a) {
   constexpr int MBF_THREADS = TS == 16 ? 1024 : 512, MBF_WAVES = MBF_THREADS / 64;
   typedef Vec8<BF16> V;
   typedef typename V::elem T;
-  typedef typename std::conditional<BF16, u32x4, f32x4>::type raw_t;
-  constexpr int KSTEP = BF16 ? 32 : 16, KLANE = BF16 ? 8 : 4, PAD = BF16 ? 8 : 4;
+  typedef Frag<BF16> F;
+  typedef typename F::raw raw_t;
+  constexpr int KSTEP = F::KSTEP, KLANE = F::KLANE, PAD = BF16 ? 8 : 4;
   constexpr int PW = (TS - 1) * S + KS;              // input tile side
   constexpr int PIN = PW * PW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -270,11 +271,7 @@ __global__ __launch_bounds__(TS == 16 ? 1024 : 512) void mbf_kernel(MbfArgs a) {
               for (int ks = 0; ks < KSPMAX; ks++) {
                 if (ks < kspp) {                                     // (uniform)
                   const raw_t xa = *reinterpret_cast<const raw_t*>(arow + ks * KSTEP);
-                  if constexpr (BF16) acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr[ks]), __builtin_bit_cast(bf16x8, xa), acc[i], 0, 0, 0);
-                  else {
-#pragma unroll
-                    for (int q = 0; q < 4; q++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wfr[ks][q], xa[q], acc[i], 0, 0, 0);
-                  }
+                  acc[i] = F::mma(wfr[ks], xa, acc[i]);
                 }
               }
             }
@@ -432,13 +429,8 @@ __global__ __launch_bounds__(TS == 16 ? 1024 : 512) void mbf_kernel(MbfArgs a) {
             if (ks < ksteps) {                                      // (uniform)
               const int ko = ks * KSTEP + KLANE * g < K ? ks * KSTEP + KLANE * g : 0;
               const raw_t xa0 = *reinterpret_cast<const raw_t*>(arow0 + ko), xa1 = *reinterpret_cast<const raw_t*>(arow1 + ko);
-              if constexpr (BF16) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr[ks]), __builtin_bit_cast(bf16x8, xa0), acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr[ks]), __builtin_bit_cast(bf16x8, xa1), acc1, 0, 0, 0);
-              } else {
-#pragma unroll
-                for (int q = 0; q < 4; q++) { acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfr[ks][q], xa0[q], acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wfr[ks][q], xa1[q], acc1, 0, 0, 0); }
-              }
+              acc0 = F::mma(wfr[ks], xa0, acc0);
+              acc1 = F::mma(wfr[ks], xa1, acc1);
             }
           }
           if (n < cc) {
@@ -488,13 +480,8 @@ __global__ __launch_bounds__(TS == 16 ? 1024 : 512) void mbf_kernel(MbfArgs a) {
           acc1 = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wl, cvt_fp8x8(xa1, nullptr, inv_as), acc1, 0, 0, 0);
         } else {
           const raw_t wf = *reinterpret_cast<const raw_t*>(wrow + ko);
-          if constexpr (BF16) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, xa0), acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, xa1), acc1, 0, 0, 0);
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; q++) { acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q], xa0[q], acc0, 0, 0, 0); acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q], xa1[q], acc1, 0, 0, 0); }
-          }
+          acc0 = F::mma(wf, xa0, acc0);
+          acc1 = F::mma(wf, xa1, acc1);
         }
       }
       const int n = nt * 16 + 4 * g;          // lane: 4 consecutive expanded channels of tile pixels m0, m1

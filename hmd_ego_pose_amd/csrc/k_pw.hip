@@ -3,10 +3,6 @@
 #include "hep_dev.h"
 #include "hep_internal.h"
 
-template <bool BF16> struct Frag;
-template <> struct Frag<true> { typedef u32x4 raw; static constexpr int KSTEP = 32, KLANE = 8; };
-template <> struct Frag<false> { typedef f32x4 raw; static constexpr int KSTEP = 16, KLANE = 4; };
-
 template <int PREC> void launch_pw_prec(const PwArgs&, hipStream_t);
 extern template void launch_pw_prec<0>(const PwArgs&, hipStream_t);
 extern template void launch_pw_prec<1>(const PwArgs&, hipStream_t);
@@ -76,12 +72,7 @@ __global__ __launch_bounds__(256) void pw_group_kernel(PwgArgs a) {
     for (int ks = 0; ks < ksteps; ks++) {
       raw_t xa = {}, wf = {};
       if (ks * F::KSTEP + F::KLANE * g < K) { wf = *reinterpret_cast<const raw_t*>(Wr + ks * F::KSTEP); if (rok) xa = *reinterpret_cast<const raw_t*>(A + ks * F::KSTEP); }
-      if constexpr (BF16) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, xa), acc, 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q], xa[q], acc, 0, 0, 0);
-      }
+      acc = F::mma(wf, xa, acc);
     }
     const int n = nt * 16 + 4 * g;
     if (rok && n < N) {

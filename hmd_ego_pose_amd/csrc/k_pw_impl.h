@@ -38,10 +38,6 @@
 #define HEP_PW_UF32 2
 #endif
 
-template <bool BF16> struct Frag;
-template <> struct Frag<true> { typedef u32x4 raw; static constexpr int KSTEP = 32, KLANE = 8; };
-template <> struct Frag<false> { typedef f32x4 raw; static constexpr int KSTEP = 16, KLANE = 4; };
-
 // PREC: 0 fp32 (exact-fp32 MFMA), 1 bf16, 2 fp8 - bf16 activations in memory, e4m3 operands in the MFMA: the weights
 // are stored as e4m3 with one scale per output channel (folded behind the BN scale), the activation fragments are
 // converted on the fly with one power-of-two scale per tensor (calibrated at hep_create), v_mfma_f32_16x16x32_fp8_fp8

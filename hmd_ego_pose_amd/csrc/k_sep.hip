@@ -56,23 +56,6 @@ __device__ int g_sep_trace_hw = 0;
 #define SEP_M1_WAVES 4
 #endif
 
-// 8 channels as loaded (bf16: one 16-byte vector = 4 VGPRs; fp32: two)
-template <bool BF16> struct Raw8;
-template <> struct Raw8<true> {
-  u32x4 v;
-  __device__ __forceinline__ void zero() { v = (u32x4){0, 0, 0, 0}; }
-  __device__ __forceinline__ void load(const void* base, int64_t idx) { v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(base) + idx); }
-  __device__ __forceinline__ float get(int c) const { return (c & 1) ? __uint_as_float(v[c >> 1] & 0xffff0000u) : __uint_as_float(v[c >> 1] << 16); }
-};
-template <> struct Raw8<false> {
-  f32x4 a, b;
-  __device__ __forceinline__ void zero() { a = (f32x4){0.f, 0.f, 0.f, 0.f}; b = a; }
-  __device__ __forceinline__ void load(const void* base, int64_t idx) {
-    const f32x4* p = reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(base) + idx); a = p[0]; b = p[1];
-  }
-  __device__ __forceinline__ float get(int c) const { return c < 4 ? a[c] : b[c - 4]; }
-};
-
 // fused value of 8 channels at (y, x): sum_i fw_i * gather_i, optional swish.  Every load of the
 // item is issued before the first one is consumed (one memory round trip per item in bf16; the
 // fp32 parity mode walks the max-pool window row by row to stay inside the register budget).
@@ -144,8 +127,9 @@ __global__ __launch_bounds__(W8 ? 512 : SEP_THREADS_OF(MODE, BF16), MODE == 1 ? 
   constexpr bool SINGLE = MODE == 0;
   typedef Vec8<BF16> V;
   typedef typename V::elem T;
-  typedef typename std::conditional<BF16, u32x4, f32x4>::type raw_t;
-  constexpr int KSTEP = BF16 ? 32 : 16, KLANE = BF16 ? 8 : 4, PAD = BF16 ? 8 : 4;
+  typedef Frag<BF16> F;
+  typedef typename F::raw raw_t;
+  constexpr int KSTEP = F::KSTEP, KLANE = F::KLANE, PAD = BF16 ? 8 : 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   HEP_POISON(smem, a.lds_bytes);
 #ifdef HEP_TOWER_TRACE
@@ -313,12 +297,7 @@ __global__ __launch_bounds__(W8 ? 512 : SEP_THREADS_OF(MODE, BF16), MODE == 1 ? 
           if (ks < ksteps) {                                  // (uniform)
             raw_t xa = {};
             if (ks * KSTEP + KLANE * g < C) xa = *reinterpret_cast<const raw_t*>(arow + ks * KSTEP);
-            if constexpr (BF16) {
-              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wfr[q]), __builtin_bit_cast(bf16x8, xa), acc, 0, 0, 0);
-            } else {
-#pragma unroll
-              for (int qq = 0; qq < 4; qq++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wfr[q][qq], xa[qq], acc, 0, 0, 0);
-            }
+            acc = F::mma(wfr[q], xa, acc);
           }
         }
       }
@@ -338,8 +317,7 @@ __global__ __launch_bounds__(W8 ? 512 : SEP_THREADS_OF(MODE, BF16), MODE == 1 ? 
             if (pair == wave && ks0 == 0) wf = wpre[q];       // (uniform) requested at kernel start
             else wf = *reinterpret_cast<const raw_t*>(wrow + ks * KSTEP);
           }
-#pragma unroll
-          for (int qq = 0; qq < 4; qq++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[qq], xa[qq], acc, 0, 0, 0);
+          acc = F::mma(wf, xa, acc);
         }
       }
     }

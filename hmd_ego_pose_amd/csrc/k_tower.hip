@@ -28,10 +28,10 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "hep_dev.h"
 #include "hep_internal.h"
+#include "tower_frag.h"
 
 // Optional per-wave timeline (make EXTRA=-DHEP_TOWER_TRACE): every wave stamps s_memrealtime (100 MHz)
 // at its phase boundaries into a device buffer read back with hep_dbg_tower_trace() - a profiling build
@@ -48,70 +48,13 @@ __device__ int g_tower_trace_maps = 0;      // 0: the header launch writes the s
 
 #define GLOBAL __attribute__((address_space(1)))   // pointers read from the descriptor are global, not flat
 
-namespace {
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-// One MFMA operand fragment (8 bf16 / 4 fp32 channels of one pixel) and the depthwise accumulation over
-// it.  bf16: the even channels of two packed words are unpacked with one shift each, the odd ones with
-// one mask each, and every pair feeds one v_pk_fma_f32 - so the accumulators (and the depthwise
-// weights in LDS, see `swz`) are kept in the order 0,2,1,3 | 4,6,5,7.
-template <bool BF16> struct Frag;
-template <> struct Frag<true> {
-  typedef u32x4 raw;
-  struct Acc { f32x2 a[4]; };      // channels (0,2) (1,3) (4,6) (5,7)
-  static __device__ __forceinline__ f32x4 swz(f32x4 w) { return (f32x4){w[0], w[2], w[1], w[3]}; }
-  static __device__ __forceinline__ void zero(Acc& c) { for (int i = 0; i < 4; i++) c.a[i] = (f32x2){0.f, 0.f}; }
-  static __device__ __forceinline__ void fma_tap(Acc& c, const raw& x, const float* w /* 8 swizzled weights in LDS */) {
-    const f32x4 wa = reinterpret_cast<const f32x4*>(w)[0], wb = reinterpret_cast<const f32x4*>(w)[1];
-    const f32x2 e0 = {__uint_as_float(x[0] << 16), __uint_as_float(x[1] << 16)}, o0 = {__uint_as_float(x[0] & 0xffff0000u), __uint_as_float(x[1] & 0xffff0000u)};
-    const f32x2 e1 = {__uint_as_float(x[2] << 16), __uint_as_float(x[3] << 16)}, o1 = {__uint_as_float(x[2] & 0xffff0000u), __uint_as_float(x[3] & 0xffff0000u)};
-    c.a[0] = __builtin_elementwise_fma(e0, (f32x2){wa[0], wa[1]}, c.a[0]);
-    c.a[1] = __builtin_elementwise_fma(o0, (f32x2){wa[2], wa[3]}, c.a[1]);
-    c.a[2] = __builtin_elementwise_fma(e1, (f32x2){wb[0], wb[1]}, c.a[2]);
-    c.a[3] = __builtin_elementwise_fma(o1, (f32x2){wb[2], wb[3]}, c.a[3]);
-  }
-  static __device__ __forceinline__ void fma_tap_r(Acc& c, const raw& x, const f32x4& wa, const f32x4& wb) {   // weights in registers (swizzled)
-    const f32x2 e0 = {__uint_as_float(x[0] << 16), __uint_as_float(x[1] << 16)}, o0 = {__uint_as_float(x[0] & 0xffff0000u), __uint_as_float(x[1] & 0xffff0000u)};
-    const f32x2 e1 = {__uint_as_float(x[2] << 16), __uint_as_float(x[3] << 16)}, o1 = {__uint_as_float(x[2] & 0xffff0000u), __uint_as_float(x[3] & 0xffff0000u)};
-    c.a[0] = __builtin_elementwise_fma(e0, (f32x2){wa[0], wa[1]}, c.a[0]);
-    c.a[1] = __builtin_elementwise_fma(o0, (f32x2){wa[2], wa[3]}, c.a[1]);
-    c.a[2] = __builtin_elementwise_fma(e1, (f32x2){wb[0], wb[1]}, c.a[2]);
-    c.a[3] = __builtin_elementwise_fma(o1, (f32x2){wb[2], wb[3]}, c.a[3]);
-  }
-  static __device__ __forceinline__ raw pack(const Acc& c) {
-    return (raw){pack_bf16x2(c.a[0][0], c.a[1][0]), pack_bf16x2(c.a[0][1], c.a[1][1]), pack_bf16x2(c.a[2][0], c.a[3][0]), pack_bf16x2(c.a[2][1], c.a[3][1])};
-  }
-  static __device__ __forceinline__ f32x4 mma(const raw& a, const raw& b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Frag<false> {
-  typedef f32x4 raw;
-  struct Acc { f32x4 a; };
-  static __device__ __forceinline__ f32x4 swz(f32x4 w) { return w; }
-  static __device__ __forceinline__ void zero(Acc& c) { c.a = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-  static __device__ __forceinline__ void fma_tap(Acc& c, const raw& x, const float* w) {
-    c.a = __builtin_elementwise_fma(x, *reinterpret_cast<const f32x4*>(w), c.a);
-  }
-  static __device__ __forceinline__ void fma_tap_r(Acc& c, const raw& x, const f32x4& wa, const f32x4&) { c.a = __builtin_elementwise_fma(x, wa, c.a); }
-  static __device__ __forceinline__ raw pack(const Acc& c) { return c.a; }
-  static __device__ __forceinline__ f32x4 mma(const raw& a, const raw& b, f32x4 c) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], b[q], c, 0, 0, 0);
-    return c;
-  }
-};
-
-}  // namespace
-
 // LDS layout of one workgroup (4 waves), shared with tower_lds_bytes():
 //   [9*CW] f32 depthwise weights | [BIAS] f32 bias (16 per n-tile of the widest segment) | 4 waves x KS x 64 lanes operand fragments
 //   | (when it fits in 48 KB) the segment's pointwise weights, rows padded against bank conflicts
 //   | (when they fit in 40 KB) the 6x6-pixel input halos of the 4 waves
 template <bool BF16, int CW, bool HDR> struct TowerCfg {
   static constexpr int ES = BF16 ? 2 : 4;
-  static constexpr int KL = BF16 ? 8 : 4, KSTEP = 4 * KL, KS = (CW + KSTEP - 1) / KSTEP;
+  static constexpr int KL = Frag<BF16>::KLANE, KSTEP = Frag<BF16>::KSTEP, KS = (CW + KSTEP - 1) / KSTEP;
   // Waves per workgroup: the four 4x4 patches of one 8x8 tile, images one after the other.  (Measured at width 160, phi 3 @
   // 512 b8: 16 waves = the same patches of four images side by side around ONE copy of the weights, 16 waves per CU
   // instead of 8 - 76.5 us per tower layer against 72.5: the layer is not short of waves.)
@@ -136,7 +79,7 @@ template <bool BF16, int CW, bool HDR> struct TowerCfg {
 
 template <bool BF16, int CW, bool HDR>
 __global__ __launch_bounds__(256, BF16 ? 4 : 2) void tower_kernel(const SepSeg* __restrict__ segs, const int* __restrict__ tile_seg, int B, int ipb) {
-  typedef Frag<BF16> F;
+  typedef TowerFrag<BF16> F;
   typedef typename F::raw raw_t;
   typedef typename Vec8<BF16>::elem T;
   typedef TowerCfg<BF16, CW, HDR> Cfg;
@@ -307,31 +250,31 @@ __global__ __launch_bounds__(256, BF16 ? 4 : 2) void tower_kernel(const SepSeg* 
     // depthwise, quad form: lane = (channel quad cq, patch row py) computes the four pixels of its row for four channels.  The six halo
     // columns of a tap row are read (8 bytes) and unpacked ONCE for the four pixels and a row's three weight vectors once: 18 + 9 LDS reads
     // and 72 unpack instructions per image and lane instead of 18 + 36 reads (16 bytes each) and 144.  Taps in the order q = ky * 3 + kx
-    // into the same (c0, c2) / (c1, c3) accumulator pairs as Frag::fma_tap: bit-identical.
-    f32x2 ae[4], ao[4];
+    // into the same (c0, c2) / (c1, c3) accumulator pairs as TowerFrag::fma_tap: bit-identical.
+    f32x2_t ae[4], ao[4];
 #pragma unroll
-    for (int px = 0; px < 4; px++) { ae[px] = (f32x2){0.f, 0.f}; ao[px] = (f32x2){0.f, 0.f}; }
+    for (int px = 0; px < 4; px++) { ae[px] = (f32x2_t){0.f, 0.f}; ao[px] = (f32x2_t){0.f, 0.f}; }
     const T* hrow = halo + dq_py * HP + dq_cq * 4;
 #pragma unroll
     for (int ky = 0; ky < 3; ky++) {
       // the row's three weight vectors (one 16-byte LDS read each, shared by the four pixels), then the six halo columns one at a time:
       // column hx feeds pixel px = hx - kx with tap kx, so every output still sees its taps in the order kx = 0, 1, 2
-      f32x2 we[3], wo[3];
+      f32x2_t we[3], wo[3];
 #pragma unroll
       for (int kx = 0; kx < 3; kx++) {
         const f32x4 wv4 = *reinterpret_cast<const f32x4*>(wdw_s + (ky * 3 + kx) * CW + dq_cq * 4);
-        we[kx] = (f32x2){wv4[0], wv4[1]}; wo[kx] = (f32x2){wv4[2], wv4[3]};
+        we[kx] = (f32x2_t){wv4[0], wv4[1]}; wo[kx] = (f32x2_t){wv4[2], wv4[3]};
       }
 #pragma unroll
       for (int hx = 0; hx < 6; hx++) {
-        f32x2 e, o;                                                  // bf16: channels (c0, c2) / (c1, c3) as Frag<true>; fp32: (c0, c1) / (c2, c3)
+        f32x2_t e, o;                                                  // bf16: channels (c0, c2) / (c1, c3) as TowerFrag<true>; fp32: (c0, c1) / (c2, c3)
         if constexpr (BF16) {
           const u32x2 v = *reinterpret_cast<const u32x2*>(hrow + (hx * 6 + ky) * HP);
-          e = (f32x2){__uint_as_float(v[0] << 16), __uint_as_float(v[1] << 16)};
-          o = (f32x2){__uint_as_float(v[0] & 0xffff0000u), __uint_as_float(v[1] & 0xffff0000u)};
+          e = (f32x2_t){__uint_as_float(v[0] << 16), __uint_as_float(v[1] << 16)};
+          o = (f32x2_t){__uint_as_float(v[0] & 0xffff0000u), __uint_as_float(v[1] & 0xffff0000u)};
         } else {
           const f32x4 v = *reinterpret_cast<const f32x4*>(hrow + (hx * 6 + ky) * HP);
-          e = (f32x2){v[0], v[1]}; o = (f32x2){v[2], v[3]};
+          e = (f32x2_t){v[0], v[1]}; o = (f32x2_t){v[2], v[3]};
         }
 #pragma unroll
         for (int kx = 2; kx >= 0; kx--) {
@@ -473,7 +416,7 @@ __global__ __launch_bounds__(256, BF16 ? 4 : 2) void tower_kernel(const SepSeg* 
 // The widths pair up: k-steps == units for every BiFPN width in bf16 (in fp32 units >= k-steps), so NWV = units.
 // Two barriers per image; LDS at width 160: 33.6 KB halo + 20 KB fragments + bias = 55 KB, two workgroups (10 waves) per CU.
 template <bool BF16, int CW, bool HDR> struct CoopCfg {
-  static constexpr int ES = BF16 ? 2 : 4, KL = BF16 ? 8 : 4, KSTEP = 4 * KL, KS = (CW + KSTEP - 1) / KSTEP;
+  static constexpr int ES = BF16 ? 2 : 4, KL = Frag<BF16>::KLANE, KSTEP = Frag<BF16>::KSTEP, KS = (CW + KSTEP - 1) / KSTEP;
   static constexpr int NTMAP = (((CW + 15) / 16) + 1) & ~1;
   static constexpr int UN = (BF16 && !HDR) ? 2 : 1;                   // n-tiles per output unit
   static constexpr int NU = BF16 ? NTMAP / 2 : NTMAP;                 // output units of a map layer (>= KS)
@@ -503,7 +446,7 @@ template <bool BF16, int CW, bool HDR> struct CoopCfg {
 
 template <bool BF16, int CW, bool HDR>
 __global__ __launch_bounds__((CoopCfg<BF16, CW, HDR>::IPAR * CoopCfg<BF16, CW, HDR>::NWV * 64), (CoopCfg<BF16, CW, HDR>::MINW)) void tower_coop_kernel(const SepSeg* __restrict__ segs, const int* __restrict__ tile_seg, int B, int ipb) {
-  typedef Frag<BF16> F;
+  typedef TowerFrag<BF16> F;
   typedef typename F::raw raw_t;
   typedef typename Vec8<BF16>::elem T;
   typedef CoopCfg<BF16, CW, HDR> Cfg;

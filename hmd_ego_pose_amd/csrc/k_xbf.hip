@@ -52,10 +52,11 @@ template <bool BF16, int KS, int S, int TOH, int TOW, int NT1, int K1C, int NT2C
 __global__ __launch_bounds__(XT, KS == 3 ? 4 : 2) void xbf_kernel(XbfArgs a) {   // (3x3 layers: two workgroups per CU, at most 128 VGPRs)
   typedef Vec8<BF16> V;
   typedef typename V::elem T;
-  typedef typename std::conditional<BF16, u32x4, f32x4>::type raw_t;      // 16 bytes of activations / weights
+  typedef Frag<BF16> F;
+  typedef typename F::raw raw_t;                                          // 16 bytes of activations / weights
   typedef typename std::conditional<BF16, u32x2, f32x4>::type xfrag_t;    // 4 consecutive channels of one pixel
   constexpr int ES = (int)sizeof(T);
-  constexpr int KSTEP = BF16 ? 32 : 16, KLANE = BF16 ? 8 : 4, PAD = BF16 ? 8 : 4;
+  constexpr int KSTEP = F::KSTEP, KLANE = F::KLANE, PAD = BF16 ? 8 : 4;
   constexpr int PH = (TOH - 1) * S + KS, PW = (TOW - 1) * S + KS, PIN = PH * PW;
   constexpr int MT_TOTAL = (PIN + 15) / 16;
   constexpr int K2P = NT1 * 16, W2P = K2P + PAD;
@@ -260,11 +261,7 @@ __global__ __launch_bounds__(XT, KS == 3 ? 4 : 2) void xbf_kernel(XbfArgs a) {  
 #pragma unroll
       for (int t = 0; t < NT1; t++) {
         const raw_t wf = *reinterpret_cast<const raw_t*>(w1_s + (t * 16 + r) * W1P + kc);
-        if constexpr (BF16) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf), __builtin_bit_cast(bf16x8, av), acc[t], 0, 0, 0);
-        else {
-#pragma unroll
-          for (int q = 0; q < 4; q++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q], av[q], acc[t], 0, 0, 0);
-        }
+        acc[t] = F::mma(wf, av, acc[t]);
       }
     }
     // epilogue: lane holds channels n = 16 t + 4 g + {0..3} of tile pixel p
@@ -324,8 +321,7 @@ __global__ __launch_bounds__(XT, KS == 3 ? 4 : 2) void xbf_kernel(XbfArgs a) {  
               acc[u] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, wf), __builtin_bit_cast(s16x4, xf[i][t]), acc[u], 0, 0, 0);
             } else {
               const f32x4 wf = *reinterpret_cast<const f32x4*>(wrow + t * 16);
-#pragma unroll
-              for (int q = 0; q < 4; q++) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[q], xf[i][t][q], acc[u], 0, 0, 0);
+              acc[u] = F::mma(wf, xf[i][t], acc[u]);      // (fp32: 16 channels are the plain k-step)
             }
           }
         }

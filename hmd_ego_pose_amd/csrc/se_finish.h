@@ -2,8 +2,6 @@
 // sigmoid) from the partial reduce-FC rows a fused front left: one body for se_finish_kernel (k_dw.hip: a launch of its own)
 // and for the tail of the fused front (k_mbf.hip: the last workgroup of an image to arrive runs it - no launch).
 #pragma once
-#include <type_traits>
-
 #include "hep_dev.h"
 #include "hep_internal.h"
 
@@ -13,7 +11,7 @@
 template <bool BF16, int NTHR, bool SC1>
 __device__ __forceinline__ void se_finish_body(const SeFinishArgs& a, const int b, const int c0, const int c1, const int tid, float* se_sm) {
   typedef typename Vec8<BF16>::elem T;
-  typedef typename std::conditional<BF16, u32x4, f32x4>::type raw_t;
+  typedef typename Frag<BF16>::raw raw_t;
   constexpr int JV = BF16 ? 8 : 4, NV = BF16 ? 6 : 12;     // hidden units per 16-byte vector; vectors held per lane (sqp <= 48)
   float* hid_s = se_sm;                    // hidden [sqp] | helper-group row sums [G][sqp]
   float* red_s = se_sm + a.sqp;

@@ -1,4 +1,4 @@
-# bit-compare two builds of the library on the benchmark shapes (bf16): python /tmp/bitcmp.py libA libB
+# bit-compare two builds of the library on the benchmark shapes (bf16): python tools/exp/bitcmp.py libA libB (exit status 0: every line IDENTICAL; the last line is the hash table)
 import sys, os, subprocess, json
 code = r'''
 import sys, torch, numpy as np, hashlib
@@ -20,6 +20,10 @@ import json; print(json.dumps(out))
 res = []
 for lib in sys.argv[1:3]:
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HEP_LIB=os.path.abspath(lib)), capture_output=True, text=True)
-    res.append(json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 else r.stderr[-500:])
+    if r.returncode != 0:      # nothing more is started on the GPU after a child that failed
+        sys.exit(f"{lib}: child ended with status {r.returncode}\n{r.stderr[-500:]}")
+    res.append(json.loads(r.stdout.strip().splitlines()[-1]))
 for k in res[0]:
     print(k, "IDENTICAL" if res[0][k] == res[1][k] else f"DIFFER {res[0][k]} {res[1][k]}")
+print(json.dumps(res[1]))
+sys.exit(0 if res[0] == res[1] else 1)
