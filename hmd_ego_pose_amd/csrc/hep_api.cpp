@@ -951,9 +951,10 @@ static std::string kernel_symbol(const Session& s, const Op& o) {
     case OP_PWG: snprintf(tmp, sizeof tmp, "pw_group_kernel<%s>", t); break;
     case OP_CHAIN: snprintf(tmp, sizeof tmp, "chain_kernel<%s, %d>", o.chain.bf16 ? "true" : "false", o.chain.stream_w); break;
     case OP_SE: snprintf(tmp, sizeof tmp, "se_finish_kernel<%s>", t); break;
-    case OP_MBF: snprintf(tmp, sizeof tmp, "mbf_kernel<%s, %d, %d, %d, %s, %d>", t, o.mbf.k, o.mbf.s, o.mbf.ts, o.mbf.fp8 ? "true" : "false",
-                          o.mbf.has_expand && o.mbf.npass > 1 ? (o.mbf.mp_resident ? 2 : 1) : 0);      // (last argument: 1 / 2 = multi-pass expand)
-                 break;
+    case OP_MBF: { const int mp = o.mbf.has_expand && o.mbf.npass > 1 ? (o.mbf.mp_resident ? 2 : 1) : 0;      // (1 / 2 = multi-pass expand)
+                   if (const int id = mbf_shape_id(o.mbf)) snprintf(tmp, sizeof tmp, "mbf_shape_kernel<%s, %d, %d, %d, %d, %d>", t, o.mbf.k, o.mbf.s, o.mbf.ts, mp, id);   // (last argument: the row of MBF_SHAPES)
+                   else snprintf(tmp, sizeof tmp, "mbf_kernel<%s, %d, %d, %d, %s, %d>", t, o.mbf.k, o.mbf.s, o.mbf.ts, o.mbf.fp8 ? "true" : "false", mp);
+                   break; }
 #ifdef HEP_ALT
     case OP_SBF: snprintf(tmp, sizeof tmp, "sbf_kernel<%s>", t); break;
     case OP_LATE: snprintf(tmp, sizeof tmp, "late_kernel"); break;

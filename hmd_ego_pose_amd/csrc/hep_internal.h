@@ -8,7 +8,7 @@
 // exact unsigned division by a launch-time constant: rcp_u32(d) on the host, udiv_rcp(x, rcp) in the kernel.
 // floor(x / d) == mulhi(x, floor(2^32 / d) + 1) whenever x * d < 2^32 (grid indices and tile counts here); d == 1 is
 // flagged with rcp == 0.  A run-time integer division costs ~30 VALU instructions per wave.
-static inline uint32_t rcp_u32(uint32_t d) { return d <= 1 ? 0u : (uint32_t)(0x100000000ull / d) + 1u; }
+static constexpr inline uint32_t rcp_u32(uint32_t d) { return d <= 1 ? 0u : (uint32_t)(0x100000000ull / d) + 1u; }
 
 #define HEP_MAX_SRC 3
 #define SEP_MAX_TILES_N 6    // n-tiles (16 columns) per head-output sepconv segment; wider headers are split into segments
@@ -122,6 +122,7 @@ struct MbfArgs {
   int se_tail; unsigned* tail_counter /* [B] counters, 32 words (one 128-byte line) apart, zero between launches */; SeFinishArgs tail;
   int out_frag;        // store the output in the project GEMM's fragment order [m-tile = 16 rows of (image, pixel)][k-step][lane][8] (k_pw_impl.h FRAG)
   int trace;           // profiling builds (-DHEP_MBF_TRACE): this launch writes its phase time stamps
+  int generic;         // plan: 1 = the generic kernel although a shape-specialised one exists (HEP_MBF_GENERIC, A/B and parity runs)
   int chunks, tiles_x;                          // filled by launch_mbf: channel chunks per tile, tiles per row
   uint32_t chunks_rcp, tiles_x_rcp, gx_rcp;     // rcp_u32() of chunks, tiles_x, gridDim.x (device: udiv_rcp)
 };
@@ -570,6 +571,7 @@ int mbf_mp_fits(int CC, int kp, int bf16, int max_inside, int ts);     // the mu
 int mbf_mp_resident(int Cin, int CC, int max_inside, int ts);          // ... with the whole tile held in registers
 int mbf_max_inside(int H, int W, int k, int s, int pad_t, int pad_l, int ts);
 int mbf_prepare(void);
+int mbf_shape_id(const MbfArgs&);                // > 0: the row of MBF_SHAPES (k_mbf_impl.h) whose mbf_shape_kernel runs this launch; 0: the generic mbf_kernel
 void launch_sep(const SepArgs&, hipStream_t);
 void launch_tower(const SepArgs&, hipStream_t);
 #define TOWER_BIAS_MAX 384       // bias floats staged per segment: >= 16 * n-tiles of any segment (24 map tiles, 12 per header chunk)

@@ -14,6 +14,7 @@ struct Knobs {
   int chain_stream = -1;      // HEP_CHAIN_STREAM=0|1|2: chain_kernel weight mode (resident / LDS-DMA streamed / pointwise fragments from global memory); -1 = by fit
   int tower_coop = -1;        // HEP_TOWER_COOP=0|1|2|3: cooperative tower kernel off / everywhere / map layers / headers; -1 = by dtype and width
   int mbf_mp = 1;             // HEP_MBF_MP=0|1|2|force(3): multi-pass expand of the fused fronts off / by rounds / bf16 from two rounds / wherever it exists
+  int mbf_generic = 0;        // HEP_MBF_GENERIC=1: the generic fused-front kernel where a shape-specialised one exists
   int xbf_generic = 0;        // HEP_XBF_GENERIC=1: the generic boundary-kernel instantiation where a shape-specialised one exists
   int stem_mfma = -1;         // HEP_STEM_MFMA=0|1: VALU / MFMA stem; -1 = by width
   double se_maxmb = 4.0;      // HEP_SE_MAXMB: squeeze-excite finished in the project GEMM's prologue below this many MB of re-read expand-FC weights per launch

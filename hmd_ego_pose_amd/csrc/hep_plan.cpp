@@ -467,7 +467,7 @@ struct Planner {
       MbfArgs& m = s->ops[op].mbf;
       m.H = Hin; m.W = Win; m.Cin = cin; m.Cexp = b.cexp; m.Ho = Ho; m.Wo = Wo; m.k = b.k; m.s = b.stride;
       m.pad_t = pt; m.pad_l = pl; m.has_expand = has_expand; m.bf16 = s->dtype; m.CC = cc; m.sq = b.se; m.sqp = sqp; m.ts = ts_;
-      m.npass = npass_; m.kp = kp_;
+      m.npass = npass_; m.kp = kp_; m.generic = kn.mbf_generic != 0;
       mbf_lds_layout(cin, cc, b.k, b.stride, s->dtype, has_expand, max_in_, ts_, &m, kp_);
       front_of_out[dw_t] = op; front_of_part[part_t] = op;
       return op;

@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 from hmd_ego_pose_amd import _capi, seeded_state_dict  # noqa: E402
 from hmd_ego_pose_amd.model import Session  # noqa: E402
 
-KNOBS = [{"HEP_MBF_MP": "force"}, {"HEP_SE_MAXMB": "0"}, {"HEP_SE_MAXMB": "1000"}, {"HEP_XBF_GENERIC": "1"}, {"HEP_STEM_MFMA": "1"},
+KNOBS = [{"HEP_MBF_MP": "force"}, {"HEP_SE_MAXMB": "0"}, {"HEP_SE_MAXMB": "1000"}, {"HEP_XBF_GENERIC": "1"}, {"HEP_MBF_GENERIC": "1"}, {"HEP_STEM_MFMA": "1"},
          {"HEP_PW_FRAG": "0"}, {"HEP_SEP_WLDS": "0"}, {"HEP_CHAIN_STREAM": "1"}, {"HEP_CHAIN_STREAM": "2"}, {"HEP_TOWER_COOP": "0"},
          {"HEP_TOWER_COOP": "1"}]
 KEEP = _capi.FLAG_KEEP_INTERMEDIATES
