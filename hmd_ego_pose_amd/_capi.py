@@ -52,6 +52,9 @@ SYMBOLS = {
     "hep_top1_device": (c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_float, c_void_p, c_void_p]),
     "hep_pose_from_i420": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8),
     "hep_pose_from_input": (c_int, [_P, _FP, c_int, _FP, c_float] + [_FP] * 8),
+    "hep_top_labels_device": (c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_float, c_void_p, c_void_p]),
+    "hep_poses_from_i420": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7),
+    "hep_poses_from_input": (c_int, [_P, _FP, c_int, _FP, c_float] + [_FP] * 7),
     "hep_pose_errors": (c_int, [c_int, _FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP]),
     "hep_pose_errors_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP, c_void_p]),
     "hep_score_detections_device": (c_int, [_FP] * 6 + [c_int, c_int, _FP, _FP, c_int, c_int, c_int, c_float, c_int, c_double, _FP, _FP, _FP, c_void_p]),

@@ -40,7 +40,7 @@ Session::~Session() {
   hipFree(d_in); hipFree(d_anchors); hipFree(d_tanchors); hipFree(d_boxes); hipFree(d_trans); hipFree(d_cam);
   hipFree(d_keys); hipFree(d_det); hipFree(d_part);
   for (int i = 0; i < 5; i++) hipFree(d_stage[i]);
-  hipFree(d_pose_in); hipFree(d_rec); hipHostFree(h_pose_in); hipHostFree(h_rec);
+  hipFree(d_pose_in); hipFree(d_rec); hipHostFree(h_pose_in); hipHostFree(h_rec); hipFree(d_recs); hipHostFree(h_recs);
   if (stream) hipStreamDestroy(stream);
 }
 
@@ -612,7 +612,7 @@ int hep_filter(hep_handle* h, const float* boxes, const float* classification, c
 // ---- top detection / frame to pose ----
 static int top1_locked(Session& s, const float* regression, const float* classification, const float* rotation,
                        const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
-                       uint32_t* records, hipStream_t st) {
+                       uint32_t* records, hipStream_t st, bool per_label = false) {
   Top1Args a;
   a.regression = regression ? regression : s.d_out[0];         // NULL = the handle's own last outputs
   a.scores = classification ? classification : s.d_out[1];
@@ -622,8 +622,8 @@ static int top1_locked(Session& s, const float* regression, const float* classif
   a.camera = camera; a.anchors = s.d_anchors; a.t_anchors = s.d_tanchors;
   a.B = batch; a.N = s.num_anchors; a.K = s.num_classes; a.any_class = s.class_specific_filter ? 0 : 1;
   a.score_thr = score_threshold; a.clip_max = (float)(s.size - 1);
-  a.records = records;
-  launch_top1(a, st);
+  a.records = records;                                         // per_label: [batch][num_classes] records, class-specific whatever the handle's mode
+  if (per_label) launch_toplabel(a, st); else launch_top1(a, st);
   HIPRET(hipGetLastError());
   return 0;
 }
@@ -640,6 +640,20 @@ int hep_top1_device(hep_handle* h, const float* regression, const float* classif
   std::lock_guard<std::mutex> lk(s.mu);
   HIPRET(hipSetDevice(s.device));
   return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream);
+} HEP_CATCH_INT
+
+int hep_top_labels_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
+                          const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
+                          uint32_t* records, void* stream) try {
+  if (!h) return fail(HEP_ERR_INVALID, "hep_top_labels_device: handle is NULL");
+  if (!camera) return fail(HEP_ERR_INVALID, "hep_top_labels_device: camera is NULL");
+  if (!records) return fail(HEP_ERR_INVALID, "hep_top_labels_device: records is NULL");
+  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_top_labels_device: batch outside 1..max_batch");
+  Session& s = h->s;
+  if (batch > s.max_batch) return fail(HEP_ERR_INVALID, "hep_top_labels_device: batch outside 1..max_batch");
+  std::lock_guard<std::mutex> lk(s.mu);
+  HIPRET(hipSetDevice(s.device));
+  return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream, true);
 } HEP_CATCH_INT
 
 namespace {
@@ -701,13 +715,26 @@ static int pose_stage(Session& s, const void* payload, size_t per_image, int bat
   return 0;
 }
 
-// top-detection launch on the handle's own head outputs, the records back through the pinned buffer, synchronise, scatter
-static int pose_finish(Session& s, int batch, float score_threshold, const PoseOut& o) {
-  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, batch, score_threshold, s.d_rec, s.stream)) return rc;
-  HIPRET(hipMemcpyAsync(s.h_rec, s.d_rec, kRecBytes * batch, hipMemcpyDeviceToHost, s.stream));
+// the handle's buffers for num_classes records per image (hep_poses_from_*): allocated at the first such call for max_batch images - the
+// size never changes for a handle, so nothing is allocated or freed afterwards
+static int poses_buffers(Session& s) {
+  const size_t need = kRecBytes * s.max_batch * s.num_classes;
+  if (!s.d_recs) HIPRET(hipMalloc((void**)&s.d_recs, need));
+  if (!s.h_recs) HIPRET(hipHostMalloc((void**)&s.h_recs, need, hipHostMallocDefault));
+  return 0;
+}
+
+// top-detection launch on the handle's own head outputs, the records back through the pinned buffer, synchronise, scatter.
+// per_label (hep_poses_from_*): the launch of hep_top_labels_device, num_classes records per image, output row b * num_classes + c
+static int pose_finish(Session& s, int batch, float score_threshold, const PoseOut& o, bool per_label) {
+  uint32_t* d = per_label ? s.d_recs : s.d_rec;
+  uint32_t* hr = per_label ? s.h_recs : s.h_rec;
+  const int rows = per_label ? batch * s.num_classes : batch;
+  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, batch, score_threshold, d, s.stream, per_label)) return rc;
+  HIPRET(hipMemcpyAsync(hr, d, kRecBytes * rows, hipMemcpyDeviceToHost, s.stream));
   HIPRET(hipStreamSynchronize(s.stream));
-  for (int b = 0; b < batch; b++) {
-    const uint32_t* r = s.h_rec + (size_t)b * HEP_POSE_RECORD_WORDS;
+  for (int b = 0; b < rows; b++) {
+    const uint32_t* r = hr + (size_t)b * HEP_POSE_RECORD_WORDS;
     memcpy(&o.found[b], r + 0, 4);
     if (o.labels) memcpy(&o.labels[b], r + 1, 4);
     if (o.index) memcpy(&o.index[b], r + 2, 4);
@@ -720,26 +747,25 @@ static int pose_finish(Session& s, int batch, float score_threshold, const PoseO
   return 0;
 }
 
-int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
-                        int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
-                        float* translation, float* hand) try {
-  if (int rc = check_pose("hep_pose_from_input", h, input_nchw, "input_nchw", batch, camera, found)) return rc;
-  if (int rc = check_pose_batch("hep_pose_from_input", h, batch)) return rc;
+// the bodies of hep_pose_from_input / hep_poses_from_input and of hep_pose_from_i420 / hep_poses_from_i420: `who` names the entry point
+static int pose_from_input(const char* who, bool per_label, hep_handle* h, const float* input_nchw, int batch, const float* camera,
+                           float score_threshold, const PoseOut& o) {
+  if (int rc = check_pose(who, h, input_nchw, "input_nchw", batch, camera, o.found)) return rc;
+  if (int rc = check_pose_batch(who, h, batch)) return rc;
   Session& s = h->s;
   std::lock_guard<std::mutex> lk(s.mu);
   HIPRET(hipSetDevice(s.device));
+  if (per_label) if (int rc = poses_buffers(s)) return rc;
   if (int rc = pose_stage(s, input_nchw, (size_t)3 * s.size * s.size * 4, batch, camera)) return rc;
   std::string err;
   if (int rc = run_forward(&s, (const float*)(s.d_pose_in + pose_cam_pad(s)), nullptr, batch, s.stream, &err)) return fail(rc, err);
-  return pose_finish(s, batch, score_threshold, PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
-                       int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
-  if (int rc = check_pose("hep_pose_from_i420", h, yuv, "yuv", batch, camera, found)) return rc;
+  return pose_finish(s, batch, score_threshold, o, per_label);
+}
+static int pose_from_i420(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop,
+                          int resized, const float* camera, float score_threshold, const PoseOut& o) {
+  if (int rc = check_pose(who, h, yuv, "yuv", batch, camera, o.found)) return rc;
   if (int rc = check_i420(height, width, crop, resized)) return rc;
-  if (int rc = check_pose_batch("hep_pose_from_i420", h, batch)) return rc;
+  if (int rc = check_pose_batch(who, h, batch)) return rc;
   Session& s = h->s;
   {   // ResizeAndNormalizeMat's row count (preprocess_i420_locked computes the same): refused here, before any HIP call
     const int nh = (int)((float)resized * ((float)s.size / (float)resized));
@@ -749,12 +775,42 @@ int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height,
   HIPRET(hipSetDevice(s.device));
   const size_t in_floats = (size_t)3 * s.size * s.size;
   if (!s.d_in) HIPRET(hipMalloc((void**)&s.d_in, in_floats * s.max_batch * 4));
+  if (per_label) if (int rc = poses_buffers(s)) return rc;
   if (int rc = pose_stage(s, yuv, (size_t)height * width * 3 / 2, batch, camera)) return rc;
   if (int rc = preprocess_i420_locked(s, s.d_pose_in + pose_cam_pad(s), batch, height, width, crop, resized, s.d_in, s.stream)) return rc;
   const int64_t S = s.size; const int64_t nhwc[4] = {3 * S * S, 1, 3 * S, 3};      // the NCHW view of the [batch,S,S,3] frames
   std::string err;
   if (int rc = run_forward(&s, s.d_in, nhwc, batch, s.stream, &err)) return fail(rc, err);
-  return pose_finish(s, batch, score_threshold, PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
+  return pose_finish(s, batch, score_threshold, o, per_label);
+}
+
+int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
+                        int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
+                        float* translation, float* hand) try {
+  return pose_from_input("hep_pose_from_input", false, h, input_nchw, batch, camera, score_threshold,
+                         PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                       int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
+  return pose_from_i420("hep_pose_from_i420", false, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
+                        PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+// several objects: [batch][num_classes] rows per output, slot c = label c (no labels array)
+int hep_poses_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
+                         int32_t* found, float* scores, int32_t* index, float* boxes, float* rotation, float* translation,
+                         float* hand) try {
+  return pose_from_input("hep_poses_from_input", true, h, input_nchw, batch, camera, score_threshold,
+                         PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+int hep_poses_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
+                        float* rotation, float* translation, float* hand) try {
+  return pose_from_i420("hep_poses_from_i420", true, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
+                        PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
 } HEP_CATCH_INT
 
 // ---- pose errors (evaluator) ----

@@ -99,6 +99,8 @@ struct Session {
   // twin on the host (when the upload goes through it), the records on both sides; allocated at first use, only ever grown
   unsigned char* d_pose_in = nullptr; unsigned char* h_pose_in = nullptr; size_t pose_in_bytes = 0, pose_pin_bytes = 0;
   uint32_t* d_rec = nullptr; uint32_t* h_rec = nullptr;
+  // hep_poses_from_i420 / hep_poses_from_input: max_batch x num_classes records on both sides, allocated at the first of these calls
+  uint32_t* d_recs = nullptr; uint32_t* h_recs = nullptr;
   bool pose_upload_pinned = false;  // HEP_POSE_UPLOAD=pinned: the upload goes through h_pose_in (the measured alternative, hep_api.cpp pose_stage)
   unsigned* d_sync = nullptr;       // meeting counters of grouped launches (k_late.hip): an allocation of its own, zeroed once - never arena memory
   hipStream_t stream = nullptr;     // handle's own stream (host API, capture, profiling)

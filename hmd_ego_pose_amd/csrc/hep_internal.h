@@ -328,6 +328,9 @@ struct Top1Args {
   uint32_t* records;   // [B][POSE_RECORD_WORDS]
 };
 void launch_top1(const Top1Args&, hipStream_t);
+// the top detection of every label (k_post.hip toplabel_kernel): records [B][K][POSE_RECORD_WORDS], record (b, c) = the best candidate of
+// class c alone; class-specific by definition - any_class is not read
+void launch_toplabel(const Top1Args&, hipStream_t);
 
 // ---- pose errors: ADD / ADD-S of D pose pairs over P model points (eval/common.py:682-746) ----
 struct PoseErrArgs {

@@ -370,6 +370,86 @@ void launch_top1(const Top1Args& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Top detection of EVERY label per image: record (b, c) = row 0 of decode_kernel -> filter_kernel on the scores with every column but c
+// masked out - in class-specific mode a class is thresholded and suppressed on its own, so its best candidate is first in its order and
+// nothing can suppress it.  Always class-specific (any_class is not read: in the other mode a box of another label can suppress the
+// anchor, and "top per label" needs the NMS).  One workgroup per image:
+//   1. the [N][K] scores are scanned in memory order (coalesced dwords: an image's base is not 16-byte aligned in general, N * K is no
+//      multiple of anything), four loads in flight per lane; a score above the threshold meets the table of K <= 63 keys in LDS - the
+//      filter's key, score_bits << 32 | ~anchor, 0 = no candidate - with a 64-bit atomic max that is issued only when the key is larger
+//      than the entry read first (entries only grow: a stale read costs one atomic, never a winner).  Candidates are rare in real use;
+//      at threshold 0 the read keeps up to 63 contended addresses from serialising the scan
+//   2. lanes c < K decode their winner's box and translation (decode_kernel's arithmetic) into LDS
+//   3. the workgroup writes the K * POSE_RECORD_WORDS words, rotation and hand gathered; no candidate: the padding filter_emit writes.
+// ------------------------------------------------------------------------------------------------
+#define TOPLABEL_MAX_K 63
+__global__ __launch_bounds__(FILTER_THREADS) void toplabel_kernel(Top1Args a) {
+  __shared__ unsigned long long s_key[TOPLABEL_MAX_K + 1];    // best key per class
+  __shared__ float s_geo[TOPLABEL_MAX_K][8];                  // box, translation of every class's winner
+  const int b = blockIdx.x, tid = threadIdx.x, K = a.K, N = a.N;
+  const float* scores = a.scores + (int64_t)b * N * K;        // [N][K]
+  if (tid <= TOPLABEL_MAX_K) s_key[tid] = 0;
+  __syncthreads();
+  const int total = N * K;                                    // <= 63 * 786 096 at size 2048: fits 32 bits
+  for (int m0 = tid; m0 < total; m0 += 4 * FILTER_THREADS) {
+    float sc[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {                             // (m < total guards the tail; score_thr itself is no candidate)
+      const int m = m0 + u * FILTER_THREADS;
+      sc[u] = m < total ? scores[m] : a.score_thr;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (sc[u] > a.score_thr) {
+        const int m = m0 + u * FILTER_THREADS, n = m / K, c = m - n * K;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(sc[u]) << 32) | (uint32_t)(~(uint32_t)n);
+        if (key > __hip_atomic_load(&s_key[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMax(&s_key[c], key);
+      }
+  }
+  __syncthreads();
+  if (tid < K) {
+    const unsigned long long key = s_key[tid];
+    if (key != 0) {
+      const int n = (int)(~(uint32_t)key);
+      const int64_t src = (int64_t)b * N + n;
+      const f32x4 an = *reinterpret_cast<const f32x4*>(a.anchors + (int64_t)n * 4);
+      const f32x4 d = *reinterpret_cast<const f32x4*>(a.regression + src * 4);
+      const f32x4 o = decode_box(an, d, a.clip_max);
+      float* g = s_geo[tid];
+      g[0] = o[0]; g[1] = o[1]; g[2] = o[2]; g[3] = o[3];
+      decode_translation(a.t_anchors + (int64_t)n * 3, a.translation_raw + src * 3, a.camera + (int64_t)b * 6, g + 4);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < K * POSE_RECORD_WORDS; i += FILTER_THREADS) {
+    const int c = i / POSE_RECORD_WORDS, w = i - c * POSE_RECORD_WORDS;
+    const unsigned long long key = s_key[c];
+    const bool found = key != 0;
+    const int n = found ? (int)(~(uint32_t)key) : 0;
+    const int64_t src = (int64_t)b * N + n;
+    uint32_t v = 0;                                           // words 3, 78, 79
+    if (w == 0) v = found ? 1u : 0u;
+    else if (w == 1) v = (uint32_t)(found ? c : -1);
+    else if (w == 2) v = (uint32_t)(found ? n : -1);
+    else if (w >= 4 && w < 78) {
+      float f = -1.f;
+      if (found) {
+        if (w == 4) f = __uint_as_float((uint32_t)(key >> 32));             // = scores[n * K + c]
+        else if (w < 9) f = s_geo[c][w - 5];
+        else if (w < 12) f = a.rotation[src * 3 + (w - 9)];
+        else if (w < 15) f = s_geo[c][4 + (w - 12)];
+        else f = a.hand[src * 63 + (w - 15)];
+      }
+      v = __float_as_uint(f);
+    }
+    a.records[((int64_t)b * K + c) * POSE_RECORD_WORDS + w] = v;
+  }
+}
+void launch_toplabel(const Top1Args& a, hipStream_t s) {
+  hipLaunchKernelGGL(toplabel_kernel, dim3(a.B), dim3(FILTER_THREADS), 0, s, a);
+}
+
+// ------------------------------------------------------------------------------------------------
 // preprocess_image (reference generators/colibri_common.py:622-656): uint8 RGB [B,H,W,3] ->
 //   cv2.resize(image, (resized_width, resized_height)) with scale = S / max(H, W), the longer side = S and the
 //   shorter one int(side * scale)                                                (skipped when scale == 1)

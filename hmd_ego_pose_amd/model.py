@@ -177,6 +177,26 @@ class Session:
     # -- top detection / frame to pose ----------------------------------------------------
     _POSE_KEYS = ("found", "score", "label", "index", "box", "rotation", "translation", "hand")
 
+    def _top_args(self, who, camera, heads):
+        """camera and the optional raw head tensors of ``top1`` / ``top_labels``, checked before a pointer reaches the ABI -> (B, head pointers, tensors to keep alive)"""
+        dev = self.device
+        if not isinstance(camera, torch.Tensor) or camera.dim() != 2 or camera.shape[1] != 6 or camera.dtype != torch.float32 or camera.device != dev:
+            raise ValueError(f"{who}: camera must be a float32 tensor of shape (B, 6) on {dev}")
+        B, N = camera.shape[0], self.num_anchors
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"{who}: batch {B} is outside 1..{self.max_batch}")
+        ptrs = [None] * 5
+        if heads is not None:
+            if len(heads) != 5:
+                raise ValueError(f"{who}: heads must be (regression, classification, rotation, translation_raw, hand)")
+            names = ("regression", "classification", "rotation", "translation_raw", "hand")
+            for name, t, k in zip(names, heads, self.out_width):
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, N, k) or t.dtype != torch.float32 or t.device != dev:
+                    raise ValueError(f"{who}: {name} must be a float32 tensor of shape ({B}, {N}, {k}) on {dev}")
+            heads = [t.contiguous() for t in heads]
+            ptrs = [t.data_ptr() for t in heads]
+        return B, ptrs, heads
+
     def top1(self, camera, score_threshold=0.5, heads=None, class_specific_filter=None):
         """The top detection of every image in one launch (hep_top1_device): row 0 of ``decode`` + ``filter`` bit for bit, for any NMS
         threshold and ``max_detections``.  ``camera`` [B,6] on the device.  ``heads``: the five RAW head tensors (regression,
@@ -185,21 +205,7 @@ class Session:
         tensors: found [B] int32, score [B], label [B] int32, index [B] int32, box [B,4], rotation [B,3], translation [B,3],
         hand [B,63] - views of ``record`` [B,80] int32, the record of include/hep.h."""
         dev = self.device
-        if not isinstance(camera, torch.Tensor) or camera.dim() != 2 or camera.shape[1] != 6 or camera.dtype != torch.float32 or camera.device != dev:
-            raise ValueError(f"top1: camera must be a float32 tensor of shape (B, 6) on {dev}")
-        B, N = camera.shape[0], self.num_anchors
-        if not 1 <= B <= self.max_batch:
-            raise ValueError(f"top1: batch {B} is outside 1..{self.max_batch}")
-        ptrs = [None] * 5
-        if heads is not None:
-            if len(heads) != 5:
-                raise ValueError("top1: heads must be (regression, classification, rotation, translation_raw, hand)")
-            names = ("regression", "classification", "rotation", "translation_raw", "hand")
-            for name, t, k in zip(names, heads, self.out_width):
-                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, N, k) or t.dtype != torch.float32 or t.device != dev:
-                    raise ValueError(f"top1: {name} must be a float32 tensor of shape ({B}, {N}, {k}) on {dev}")
-            heads = [t.contiguous() for t in heads]
-            ptrs = [t.data_ptr() for t in heads]
+        B, ptrs, heads = self._top_args("top1", camera, heads)
         rec = torch.empty((B, _capi.POSE_RECORD_WORDS), dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         with self._filter_lock:
@@ -211,7 +217,22 @@ class Session:
         return dict(found=rec[:, 0], label=rec[:, 1], index=rec[:, 2], score=f[:, 4], box=f[:, 5:9], rotation=f[:, 9:12],
                     translation=f[:, 12:15], hand=f[:, 15:78], record=rec)
 
-    def _pose_call(self, who, fn, lead, B, camera, score_threshold):
+    def top_labels(self, camera, score_threshold=0.5, heads=None):
+        """The top detection of EVERY label of every image in one launch (hep_top_labels_device): slot ``c`` is row 0 of ``decode`` +
+        ``filter(class_specific_filter=True)`` on the classification with every column but ``c`` masked out, bit for bit, for any NMS
+        threshold and ``max_detections``.  Class-specific by definition: the handle's filter mode is not read.  ``camera`` and
+        ``heads`` as for ``top1``.  Returns device tensors: found [B,K] int32, score [B,K], index [B,K] int32, box [B,K,4],
+        rotation [B,K,3], translation [B,K,3], hand [B,K,63] - views of ``record`` [B,K,80] int32 (include/hep.h); K = num_classes."""
+        dev = self.device
+        B, ptrs, heads = self._top_args("top_labels", camera, heads)
+        rec = torch.empty((B, self.num_classes, _capi.POSE_RECORD_WORDS), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _capi.check(_capi.lib().hep_top_labels_device(self.handle, *ptrs, camera.contiguous().data_ptr(), B, float(score_threshold), rec.data_ptr(), stream))
+        f = rec.view(torch.float32)
+        return dict(found=rec[..., 0], index=rec[..., 2], score=f[..., 4], box=f[..., 5:9], rotation=f[..., 9:12],
+                    translation=f[..., 12:15], hand=f[..., 15:78], record=rec)
+
+    def _pose_call(self, who, fn, lead, B, camera, score_threshold, per_label=False):
         import numpy as np
         cam = np.ascontiguousarray(camera, dtype=np.float32) if not isinstance(camera, torch.Tensor) else None
         if cam is None:
@@ -222,10 +243,13 @@ class Session:
             raise ValueError(f"{who}: camera must have shape ({B}, 6), got {cam.shape}")
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"{who}: batch {B} is outside 1..{self.max_batch}")
-        out = dict(found=np.empty(B, np.int32), score=np.empty(B, np.float32), label=np.empty(B, np.int32), index=np.empty(B, np.int32),
-                   box=np.empty((B, 4), np.float32), rotation=np.empty((B, 3), np.float32), translation=np.empty((B, 3), np.float32),
-                   hand=np.empty((B, 63), np.float32))
-        _capi.check(fn(self.handle, *lead, cam.ctypes.data, float(score_threshold), *[out[k].ctypes.data for k in self._POSE_KEYS]))
+        lead_shape = (B, self.num_classes) if per_label else (B,)       # per_label (poses_from_*): slot c is label c, no label array
+        e = lambda dtype, *tail: np.empty(lead_shape + tail, dtype)
+        out = dict(found=e(np.int32), score=e(np.float32), label=e(np.int32), index=e(np.int32), box=e(np.float32, 4),
+                   rotation=e(np.float32, 3), translation=e(np.float32, 3), hand=e(np.float32, 63))
+        if per_label:
+            del out["label"]
+        _capi.check(fn(self.handle, *lead, cam.ctypes.data, float(score_threshold), *[out[k].ctypes.data for k in self._POSE_KEYS if k in out]))
         return out
 
     @staticmethod
@@ -239,28 +263,50 @@ class Session:
             raise ValueError(f"{who}: expected a host array of dtype {np.dtype(dtype).name}")
         return np.ascontiguousarray(x)
 
+    def _i420_host(self, who, frames_u8_host, height, width, crop, resized):
+        import numpy as np
+        x = self._host_array(who, frames_u8_host, np.uint8)
+        if height < 2 or width < 2 or height % 2 or width % 2:
+            raise ValueError(f"{who}: 4:2:0 frames have even sides")
+        if not 1 <= crop <= min(height, width) or resized < 1:
+            raise ValueError(f"{who}: crop must fit the frame, resized must be positive")
+        if x.ndim != 2 or x.shape[1] != height * width * 3 // 2:
+            raise ValueError(f"{who}: expected uint8 frames of shape (B, {height * width * 3 // 2}), got {x.shape}")
+        return x
+
+    def _input_host(self, who, x_host):
+        import numpy as np
+        x = self._host_array(who, x_host, np.float32)
+        if x.ndim != 4 or x.shape[1:] != (3, self.size, self.size):
+            raise ValueError(f"{who}: expected float32 of shape (B, 3, {self.size}, {self.size}), got {x.shape}")
+        return x
+
     def pose_from_i420(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, score_threshold=0.5):
         """Frame to pose in one synchronous call (hep_pose_from_i420): I420 frames [B, height * width * 3 // 2] (uint8, HOST memory)
         -> the frame path of ``preprocess_i420`` -> forward -> top detection -> numpy arrays found / score / label / index / box /
         rotation / translation / hand, one row per frame.  ``camera`` [B,6] on the host."""
-        import numpy as np
-        x = self._host_array("pose_from_i420", frames_u8_host, np.uint8)
-        if height < 2 or width < 2 or height % 2 or width % 2:
-            raise ValueError("pose_from_i420: 4:2:0 frames have even sides")
-        if not 1 <= crop <= min(height, width) or resized < 1:
-            raise ValueError("pose_from_i420: crop must fit the frame, resized must be positive")
-        if x.ndim != 2 or x.shape[1] != height * width * 3 // 2:
-            raise ValueError(f"pose_from_i420: expected uint8 frames of shape (B, {height * width * 3 // 2}), got {x.shape}")
+        x = self._i420_host("pose_from_i420", frames_u8_host, height, width, crop, resized)
         return self._pose_call("pose_from_i420", _capi.lib().hep_pose_from_i420, (x.ctypes.data, x.shape[0], height, width, crop, resized),
                                x.shape[0], camera, score_threshold)
 
     def pose_from_input(self, x_host, camera, score_threshold=0.5):
         """The same from the normalised float32 blob [B,3,S,S] in HOST memory that ``hep_run`` takes (hep_pose_from_input)."""
-        import numpy as np
-        x = self._host_array("pose_from_input", x_host, np.float32)
-        if x.ndim != 4 or x.shape[1:] != (3, self.size, self.size):
-            raise ValueError(f"pose_from_input: expected float32 of shape (B, 3, {self.size}, {self.size}), got {x.shape}")
+        x = self._input_host("pose_from_input", x_host)
         return self._pose_call("pose_from_input", _capi.lib().hep_pose_from_input, (x.ctypes.data, x.shape[0]), x.shape[0], camera, score_threshold)
+
+    def poses_from_i420(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, score_threshold=0.5):
+        """``pose_from_i420`` for several objects (hep_poses_from_i420): the top detection of every label of every frame, class-specific
+        by definition (``top_labels``).  numpy arrays found / score / index [B,K], box [B,K,4], rotation / translation [B,K,3],
+        hand [B,K,63]; slot ``c`` is label ``c``, K = num_classes."""
+        x = self._i420_host("poses_from_i420", frames_u8_host, height, width, crop, resized)
+        return self._pose_call("poses_from_i420", _capi.lib().hep_poses_from_i420, (x.ctypes.data, x.shape[0], height, width, crop, resized),
+                               x.shape[0], camera, score_threshold, per_label=True)
+
+    def poses_from_input(self, x_host, camera, score_threshold=0.5):
+        """The same from the normalised float32 blob [B,3,S,S] in HOST memory (hep_poses_from_input)."""
+        x = self._input_host("poses_from_input", x_host)
+        return self._pose_call("poses_from_input", _capi.lib().hep_poses_from_input, (x.ctypes.data, x.shape[0]), x.shape[0], camera,
+                               score_threshold, per_label=True)
 
     # -- introspection ------------------------------------------------------------------
     def stage(self, name: str, batch: int) -> torch.Tensor:

@@ -25,6 +25,9 @@
  *                                 row 0 of hep_decode_device + hep_filter_device in one launch
  *   hep_pose_from_i420         <- the whole I420AVideoFrameReady callback, Program.cs:128-298 (frame bytes in host memory -> pose)
  *   hep_pose_from_input        <- the same from the float blob of OpenCVDNNSandboxNetCore/Program.cs:95-122
+ *   hep_top_labels_device, hep_poses_from_i420, hep_poses_from_input <- the same three for a model of several objects
+ *                                 (num_classes > 1, backbone.py:14): the top detection of EVERY label, class-specific as the
+ *                                 reference constructs its filter (train.py:78-81)
  *   hep_anchor_targets_device  <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
@@ -223,6 +226,37 @@ int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height,
 int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
                         int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
                         float* translation, float* hand);
+
+/* The top detection of EVERY label of every image, in one launch on the raw head outputs: the serving call of a model trained on several
+ * objects (num_classes = K > 1; hep_top1_device reports only whichever object scores highest in the frame).
+ * DEFINITION: record (b, c) is row 0 of hep_decode_device -> hep_filter_device in class-specific mode on image b with every
+ * classification column but c set to -1, bit for bit, for any nms_threshold and any max_detections >= 1.  As a rule: the maximal
+ * classification[b, n, c] over the anchors n with a score > score_threshold, ties to the lower anchor index; a score exactly at the
+ * threshold is no candidate.  Where an image has no more than max_detections candidate pairs in all, record (b, c) is also the first
+ * row with det_labels == c of the unmasked filter.
+ * CLASS-SPECIFIC BY DEFINITION: hep_set_class_specific_filter is ignored.  In the other mode an anchor whose best class is c can be
+ * suppressed by a box of another label, so "the top detection per label" has no NMS-free meaning there.
+ * Arguments as for hep_top1_device (NULL head pointer = the handle's own output buffer; camera [batch,6] on the device).
+ * records: device memory, batch x num_classes x HEP_POSE_RECORD_WORDS words, [batch][num_classes] records of the layout above; the label
+ * word of record (b, c) is c when found.  A label without a candidate gets found = 0 and the filter's padding (-1 / -1.0f) everywhere
+ * else; words 3, 78 and 79 stay 0.  Asynchronous on `stream`, no allocation, no host synchronisation.  NULL handle / camera / records or
+ * a batch outside 1..max_batch: HEP_ERR_INVALID. */
+int hep_top_labels_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
+                          const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
+                          uint32_t* records, void* stream);
+
+/* hep_pose_from_i420 / hep_pose_from_input for several objects: the same staging, mutex, one pinned download (batch x num_classes x 320
+ * bytes) and one synchronise, with the launch of hep_top_labels_device in place of the top-detection launch.  Every output has
+ * [batch][num_classes] rows and slot c is label c, so there is no labels array: found [batch,K] int32, scores [batch,K], index [batch,K]
+ * int32, boxes [batch,K,4], rotation [batch,K,3], translation [batch,K,3], hand [batch,K,63]; any of them except found may be NULL.  A
+ * slot with found == 0 holds the padding (-1 / -1.0f).  The buffers for num_classes records per image belong to the handle, are allocated
+ * at the first of these calls and only ever grown; hep_pose_from_* keep their own.  Argument checks as for hep_pose_from_*. */
+int hep_poses_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
+                        float* rotation, float* translation, float* hand);
+int hep_poses_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
+                         int32_t* found, float* scores, int32_t* index, float* boxes, float* rotation, float* translation,
+                         float* hand);
 
 /* ADD and ADD-S of num_pairs (ground truth, prediction) poses over one object model: points [num_points,3]; rotations
  * as axis-angle vectors in radians (what _get_detections hands on: network output * pi), translations in the model's

@@ -18,6 +18,15 @@ Acceptance (the rule of NOTEBOOK.md section 15), stated per regime: spread = |ol
   (a) the new call's slower run is below the old composition's faster run by more than that spread.
 
     python tools/pose_call_time.py [--calls 300] [--warmup 20] [--json FILE]
+
+--labels K: the same regime with seeded K-class weights, for the calls that return the top detection of EVERY label:
+  (a) old = hep_run -> hep_decode -> hep_filter on host arrays, the rows then searched by label   new = hep_poses_from_input
+  (b) old = the frame composition above, the rows searched by label                               new = hep_poses_from_i420
+old and new alternate twice; both (a) and (b) must have the new call's slower run below the old path's faster run by more than the old
+path's spread.  With K = 1 a third child, "top1" (hep_pose_from_input / hep_pose_from_i420), runs between them: the two kernels on the
+same scores should be level.  No upload A/B in this mode.
+
+    python tools/pose_call_time.py --labels 3 [--calls 300] [--warmup 20] [--json FILE]
 """
 import argparse
 import ctypes
@@ -44,7 +53,8 @@ def child(args):
     lib = _capi.lib()
     dev = torch.device("cuda", 0)
     phi, S, M, thr = 0, 512, 100, 0.5
-    sd = seeded_state_dict(phi, 0)
+    K = args.labels or 1
+    sd = seeded_state_dict(phi, 0, num_classes=K)
     rng = np.random.Generator(np.random.PCG64(5))
     x = rng.standard_normal((1, 3, S, S)).astype(np.float32)
     shift = 0.0                                       # latency_b1's load knob: the quantile of the logits that leaves ~30 candidates
@@ -66,7 +76,17 @@ def child(args):
            "box": np.empty((1, 4), np.float32), "rotation": np.empty((1, 3), np.float32), "translation": np.empty((1, 3), np.float32),
            "hand": np.empty((1, 63), np.float32)}
     top_ptrs = [top[k].ctypes.data for k in Session._POSE_KEYS]
+    per = {k: np.empty((1, K) + v.shape[1:], v.dtype) for k, v in top.items() if k != "label"}      # hep_poses_from_*: slot c = label c
+    per_ptrs = [per[k].ctypes.data for k in Session._POSE_KEYS if k != "label"]
     row0 = {}
+
+    def by_label(labels, index, scores):
+        """what the caller of the old path does with the filter's rows: the first row of every label"""
+        out = []
+        for c in range(K):
+            r = np.nonzero(np.asarray(labels) == c)[0]
+            out.append((int(index[r[0]]), float(scores[r[0]])) if len(r) else (-1, -1.0))
+        return out
 
     if args.child == "old":
         ho = [np.empty((1, N, k), np.float32) for k in s.out_width]
@@ -79,7 +99,7 @@ def child(args):
             _capi.check(lib.hep_decode(s.handle, ho[0].ctypes.data, ho[3].ctypes.data, cam.ctypes.data, 1, hb.ctypes.data, ht.ctypes.data))
             _capi.check(lib.hep_filter(s.handle, hb.ctypes.data, ho[1].ctypes.data, ho[2].ctypes.data, ht.ctypes.data, ho[4].ctypes.data, 1, thr, 0.5, M,
                                        *[a.ctypes.data for a in hd_]))
-            row0["a"] = (int(hd_[6][0, 0]), float(hd_[1][0, 0]))
+            row0["a"] = by_label(hd_[2][0], hd_[6][0], hd_[1][0]) if args.labels else (int(hd_[6][0, 0]), float(hd_[1][0, 0]))
 
         tframe = torch.from_numpy(frame)
         st = torch.cuda.Stream(dev)
@@ -100,15 +120,23 @@ def child(args):
                 _capi.check(lib.hep_decode_device(s.handle, None, None, cam_d.data_ptr(), 1, bx.data_ptr(), tr.data_ptr(), st.cuda_stream))
                 _capi.check(lib.hep_filter_device(s.handle, bx.data_ptr(), None, None, tr.data_ptr(), None, 1, thr, 0.5, M, *[d.data_ptr() for d in det], st.cuda_stream))
                 rows = [d.cpu() for d in det]                # D2H of the detection rows (synchronises the stream)
-            row0["b"] = (int(rows[6][0, 0]), float(rows[1][0, 0]))
-    else:
+            row0["b"] = by_label(rows[2][0].numpy(), rows[6][0].numpy(), rows[1][0].numpy()) if args.labels else (int(rows[6][0, 0]), float(rows[1][0, 0]))
+    elif args.labels and args.child == "new":
+        def call_a():
+            _capi.check(lib.hep_poses_from_input(s.handle, x.ctypes.data, 1, cam.ctypes.data, thr, *per_ptrs))
+            row0["a"] = [(int(per["index"][0, c]), float(per["score"][0, c])) for c in range(K)]
+
+        def call_b():
+            _capi.check(lib.hep_poses_from_i420(s.handle, frame.ctypes.data, 1, FH, FW, 256, 512, cam.ctypes.data, thr, *per_ptrs))
+            row0["b"] = [(int(per["index"][0, c]), float(per["score"][0, c])) for c in range(K)]
+    else:                                             # "new" without --labels, "top1" with it: the single-detection calls
         def call_a():
             _capi.check(lib.hep_pose_from_input(s.handle, x.ctypes.data, 1, cam.ctypes.data, thr, *top_ptrs))
-            row0["a"] = (int(top["index"][0]), float(top["score"][0]))
+            row0["a"] = [(int(top["index"][0]), float(top["score"][0]))] if args.labels else (int(top["index"][0]), float(top["score"][0]))
 
         def call_b():
             _capi.check(lib.hep_pose_from_i420(s.handle, frame.ctypes.data, 1, FH, FW, 256, 512, cam.ctypes.data, thr, *top_ptrs))
-            row0["b"] = (int(top["index"][0]), float(top["score"][0]))
+            row0["b"] = [(int(top["index"][0]), float(top["score"][0]))] if args.labels else (int(top["index"][0]), float(top["score"][0]))
 
     def stats(ts):
         ts = sorted(ts)
@@ -155,17 +183,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--json", default=None, help="also write every child's result to this file")
     ap.add_argument("--timeout", type=int, default=180, help="time limit of one measuring child process, seconds")
-    ap.add_argument("--child", default=None, choices=["old", "new"], help=argparse.SUPPRESS)
+    ap.add_argument("--labels", type=int, default=0, help="K: time hep_poses_from_* with seeded K-class weights (see above)")
+    ap.add_argument("--child", default=None, choices=["old", "new", "top1"], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not 0 <= args.labels <= 63:
+        sys.exit("--labels must be in 1..63")
     if args.child:
         return child(args)
     runs = []
-    for path, upload in (("old", None), ("new", None), ("old", None), ("new", None), ("new", "pinned"), ("new", "direct")):
+    plan = (("old", None), ("new", None), ("old", None), ("new", None), ("new", "pinned"), ("new", "direct"))
+    if args.labels:
+        plan = (("old", None), ("top1", None), ("new", None)) * 2 if args.labels == 1 else (("old", None), ("new", None)) * 2
+    for path, upload in plan:
         env = dict(os.environ)
         env.pop("HEP_POSE_UPLOAD", None)
         if upload:
             env["HEP_POSE_UPLOAD"] = upload
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--calls", str(args.calls), "--warmup", str(args.warmup)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--calls", str(args.calls), "--warmup", str(args.warmup), "--labels", str(args.labels)]
         r = subprocess.run(cmd, timeout=args.timeout, env=env, capture_output=True, text=True)
         line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
         if r.returncode != 0 or not line:
@@ -173,7 +207,7 @@ def main():
             sys.exit(f"the {path} child failed (exit status {r.returncode}): nothing further is started")
         runs.append(json.loads(line[0][7:]))
         d = runs[-1]
-        print(f"{path:<3} upload={d['upload']:<7} candidates={d['candidates']}  " + "  ".join(
+        print(f"{path:<4} upload={d['upload']:<7} candidates={d['candidates']}  " + "  ".join(
             f"{k}: p50 {d[k]['p50_ms']:.4f} p99 {d[k]['p99_ms']:.4f}" for k in ("a", "a_60hz", "b", "b_60hz")), flush=True)
     old = [r for r in runs if r["path"] == "old"]
     new = [r for r in runs if r["path"] == "new" and r["upload"] == "default"]
@@ -182,12 +216,18 @@ def main():
     for k in ("a", "a_60hz", "b", "b_60hz"):
         o, n = [r[k]["p50_ms"] for r in old], [r[k]["p50_ms"] for r in new]
         spread = abs(o[0] - o[1])
-        ok = (max(n) < min(o) - spread) if k.startswith("a") else (max(n) <= max(o) + spread)
+        ok = (max(n) < min(o) - spread) if k.startswith("a") or args.labels else (max(n) <= max(o) + spread)
         verdict[k] = {"old_p50": o, "new_p50": n, "old_spread": round(spread, 4), "met": bool(ok)}
         print(f"{k:<7} old p50 {o}  new p50 {n}  old spread {spread:.4f} ms  -> {'met' if ok else 'NOT met'}")
+    top1 = [r for r in runs if r["path"] == "top1"]
+    if top1:                                          # K = 1: hep_poses_from_* against hep_pose_from_* on the same scores
+        for k in ("a", "a_60hz", "b", "b_60hz"):
+            t, n = [r[k]["p50_ms"] for r in top1], [r[k]["p50_ms"] for r in new]
+            verdict[k]["top1_p50"] = t
+            print(f"{k:<7} hep_pose_from_* p50 {t}  hep_poses_from_* p50 {n}  difference of the means {sum(n) / len(n) - sum(t) / len(t):+.4f} ms")
     print(f"forward: {runs[0]['forward_launches']} launches (one eager, the rest one graph replay)")
     for k, v in LAUNCHES.items():
-        print(f"{k}: {v}")
+        print(f"{k}: {v.replace('top-1', 'top-per-label').replace('320 bytes', f'{args.labels} x 320 bytes') if args.labels else v}")
     if args.json:
         with open(args.json, "w") as f:
             json.dump({"runs": runs, "verdict": verdict, "launches": LAUNCHES}, f, indent=1)
