@@ -70,6 +70,9 @@ SYMBOLS = {
     "hep_heads_workspace_bytes_bn": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "hep_heads_forward_device_bn": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_int, c_float, _FP, c_void_p]),
     "hep_heads_backward_device_bn": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, c_int, _FP, POINTER(_FP), c_void_p, c_size_t, c_int, c_void_p]),
+    "hep_heads_workspace_bytes_sync": (c_int64, [c_int, c_int, c_int, c_int]),
+    "hep_heads_forward_device_sync": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_float, _FP, c_void_p, c_void_p]),
+    "hep_heads_backward_device_sync": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, c_int, _FP, POINTER(_FP), c_void_p, c_size_t, c_void_p, c_void_p]),
     "hep_neck_param_count": (c_int64, [c_int]),
     "hep_neck_param_layout": (c_int, [c_int, POINTER(c_int64), c_int]),
     "hep_neck_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
@@ -78,6 +81,9 @@ SYMBOLS = {
     "hep_neck_workspace_bytes_bn": (c_int64, [c_int, c_int, c_int, c_int]),
     "hep_neck_forward_device_bn": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_int, c_float, _FP, c_void_p]),
     "hep_neck_backward_device_bn": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, _FP, POINTER(_FP), c_void_p, c_size_t, c_int, c_void_p]),
+    "hep_neck_workspace_bytes_sync": (c_int64, [c_int, c_int, c_int]),
+    "hep_neck_forward_device_sync": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_float, _FP, c_void_p, c_void_p]),
+    "hep_neck_backward_device_sync": (c_int, [_FP, POINTER(_FP), c_int, c_int, c_int, _FP, POINTER(_FP), c_void_p, c_size_t, c_void_p, c_void_p]),
     "hep_neck_stage_count": (c_int, [c_int]),
     "hep_neck_stage_info": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
     "hep_backbone_param_count": (c_int64, [c_int]),
@@ -88,6 +94,9 @@ SYMBOLS = {
     "hep_backbone_workspace_bytes_bn": (c_int64, [c_int, c_int, c_int, c_int]),
     "hep_backbone_forward_device_bn": (c_int, [_FP, _FP, _FP, c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_int, c_float, _FP, c_void_p]),
     "hep_backbone_backward_device_bn": (c_int, [_FP, POINTER(_FP), _FP, c_int, c_int, c_int, _FP, _FP, c_void_p, c_size_t, c_int, c_void_p]),
+    "hep_backbone_workspace_bytes_sync": (c_int64, [c_int, c_int, c_int]),
+    "hep_backbone_forward_device_sync": (c_int, [_FP, _FP, _FP, c_int, c_int, c_int, POINTER(_FP), c_void_p, c_size_t, c_float, _FP, c_void_p, c_void_p]),
+    "hep_backbone_backward_device_sync": (c_int, [_FP, POINTER(_FP), _FP, c_int, c_int, c_int, _FP, _FP, c_void_p, c_size_t, c_void_p, c_void_p]),
     "hep_backbone_stage_count": (c_int, [c_int]),
     "hep_backbone_stage_info": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_char_p), POINTER(c_int64), POINTER(c_int64)]),
     "hep_debug_tensor_count": (c_int, [_P]),

@@ -55,6 +55,8 @@ def stage_views(part: str, ws: torch.Tensor, compound_coef: int, size: int, batc
 
 BN_RUNNING, BN_BATCH = 0, 1        # HEP_BN_RUNNING, HEP_BN_BATCH of include/hep.h
 BN_MODES = {"running": BN_RUNNING, "batch": BN_BATCH}
+BN_SYNC = "sync"                   # batch statistics over the rows of all replicas: its own entry points (hep_*_device_sync), no bn_mode value
+BN_NAMES = (*BN_MODES, BN_SYNC)
 BN_MOMENTUM = 0.01                 # every nn.BatchNorm2d of the reference (efficientnet/model.py, efficientdet/model.py, hmdegopose/model.py)
 
 
@@ -62,18 +64,31 @@ class TrainablePart(nn.Module):
     """Base of the three trainable parts.  A subclass sets ``spec`` and ``NOUN``, calls ``_attach_spec`` in its ``__init__``
     and adds its own ``forward``.  ``batch_norm``: "running" (every mode evaluates BatchNorm with the running statistics) or
     "batch" (``train()`` mode normalises with the statistics of the batch and moves the running statistics, as
-    ``nn.BatchNorm2d`` does; ``eval()`` is the running-statistics function)."""
+    ``nn.BatchNorm2d`` does; ``eval()`` is the running-statistics function) or "sync" ("batch" with every BatchNorm seeing the
+    rows of ALL replicas of ``process_group``, a ``torch.distributed`` group - the reference's ``utils/sync_batchnorm``; with no
+    group it is "batch" bit for bit).  Under "sync" this replica's parameter gradients are its own contribution: their plain SUM
+    over the replicas is the gradient of the global-batch function."""
     NOUN = ""     # "head" | "BiFPN" | "backbone": what from_model's error calls the part's tensors
     spec = None   # staticmethod(*cfg) -> [(key, shape)]: the part's subset of ``param_spec``, in state_dict order
 
-    def _set_batch_norm(self, batch_norm):
-        if batch_norm not in BN_MODES:
-            raise ValueError(f"batch_norm must be 'running' or 'batch', not {batch_norm!r}")
+    def _set_batch_norm(self, batch_norm, process_group=None):
+        if batch_norm not in BN_NAMES:
+            raise ValueError(f"batch_norm must be 'running', 'batch' or 'sync', not {batch_norm!r}")
+        if process_group is not None and batch_norm != BN_SYNC:
+            raise ValueError("process_group goes with batch_norm='sync'")
         self.batch_norm = batch_norm
+        self._hook = None                  # (a plain attribute: no tensor, nothing in state_dict)
+        if batch_norm == BN_SYNC:
+            from .sync import SumHook
+            self._hook = SumHook(process_group)
+
+    def _sync_hook(self):
+        """The sum hook of this call: only in ``train()`` mode of a ``batch_norm="sync"`` part (None otherwise)."""
+        return self._hook if self.batch_norm == BN_SYNC and self.training else None
 
     def _bn_mode(self) -> int:
         """The BatchNorm mode of this call: batch statistics only in ``train()`` mode of a ``batch_norm="batch"`` part."""
-        return BN_BATCH if self.batch_norm == "batch" and self.training else BN_RUNNING
+        return BN_BATCH if self.batch_norm in ("batch", BN_SYNC) and self.training else BN_RUNNING
 
     def _store_statistics(self, stats: torch.Tensor):
         """After a batch-statistics forward: ``stats`` (layout of ``flat_parameters``, its running_mean / running_var elements

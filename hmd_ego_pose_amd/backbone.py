@@ -17,8 +17,9 @@ BatchNorm and every block's ``_bn0`` / ``_bn1`` / ``_bn2`` normalise with the st
 move their running statistics (momentum 0.01), ``eval()`` stays the running-statistics function bit for bit.  Drop-connect (efficientnet/utils.py:85-94 with the rate of efficientdet/model.py:447-449), the
 only stochastic op on the path, enters the kernels as DATA: a per-block, per-image scale of the residual branch,
 ``y = bn2(project) * scale[i][b] + input``, used only where the block adds its input.  The module draws the scales itself only
-when ``drop_connect_rate`` is non-zero AND it is in ``train()``; the default rate 0.0 makes it deterministic.  Out of scope:
-sync-BN across GPUs and bf16 training.
+when ``drop_connect_rate`` is non-zero AND it is in ``train()``; the default rate 0.0 makes it deterministic.
+``batch_norm="sync"`` (with ``process_group=``): batch statistics over the rows of all replicas (``_trainable.TrainablePart``).
+Out of scope: bf16 training.
 """
 from __future__ import annotations
 
@@ -51,27 +52,34 @@ def _check_size(size: int):
 
 
 def backbone_forward(flat: torch.Tensor, image: torch.Tensor, compound_coef: int, branch_scale: Optional[torch.Tensor] = None,
-                     bn_mode: int = _trainable.BN_RUNNING, momentum: float = _trainable.BN_MOMENTUM, stats: Optional[torch.Tensor] = None):
+                     bn_mode: int = _trainable.BN_RUNNING, momentum: float = _trainable.BN_MOMENTUM, stats: Optional[torch.Tensor] = None, sync=None):
     """hep_backbone_forward_device_bn on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order), ``image``:
     contiguous float32 NCHW [B, 3, S, S], ``branch_scale``: float32 [blocks, B] on the same device or None (all ones).
     Returns (taps, workspace): P3, P4, P5 as float32 NCHW and the workspace hep_backbone_backward_device_bn needs (same
     ``bn_mode``).  ``stats`` (batch statistics): a buffer like ``flat`` whose running_mean / running_var elements receive the
-    updated statistics.  No host synchronisation."""
+    updated statistics.  No host synchronisation.  ``sync``: a ``sync.SumHook`` - hep_backbone_forward_device_sync instead (batch
+    statistics over all replicas; ``bn_mode`` is not read)."""
     a = get_arch(compound_coef)
     dev, B, size = flat.device, int(image.shape[0]), int(image.shape[-1])
     _check_size(size)
     l = _capi.lib()
-    nbytes = _capi.check(l.hep_backbone_workspace_bytes_bn(compound_coef, size, B, bn_mode))
+    nbytes = _capi.check(l.hep_backbone_workspace_bytes_bn(compound_coef, size, B, bn_mode) if sync is None else
+                         l.hep_backbone_workspace_bytes_sync(compound_coef, size, B))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     taps = tuple(torch.empty((B, c, size // (8 << t), size // (8 << t)), dtype=torch.float32, device=dev) for t, c in enumerate(a.tap_channels))
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if sync is not None:
+        sync.register(ws)
+        sync.check(l.hep_backbone_forward_device_sync(flat.data_ptr(), image.data_ptr(), _capi.ptr(branch_scale), compound_coef, size, B,
+                                                      _capi.ptr_array(list(taps)), ws.data_ptr(), nbytes, momentum, _capi.ptr(stats), sync.ref(), stream))
+        return taps, ws
     _capi.check(l.hep_backbone_forward_device_bn(flat.data_ptr(), image.data_ptr(), _capi.ptr(branch_scale), compound_coef, size, B,
                                                  _capi.ptr_array(list(taps)), ws.data_ptr(), nbytes, bn_mode, momentum, _capi.ptr(stats), stream))
     return taps, ws
 
 
 def backbone_backward(flat: torch.Tensor, grad_taps, ws: torch.Tensor, compound_coef: int, size: int,
-                      branch_scale: Optional[torch.Tensor] = None, want_image: bool = False, bn_mode: int = _trainable.BN_RUNNING):
+                      branch_scale: Optional[torch.Tensor] = None, want_image: bool = False, bn_mode: int = _trainable.BN_RUNNING, sync=None):
     """hep_backbone_backward_device_bn on the current stream, after ``backbone_forward`` with the same ``flat``, ``branch_scale``,
     ``ws`` and ``bn_mode``.  Returns (grad_flat, grad_image): the parameter gradients in the layout of ``flat`` (running statistics zero)
     and the image gradient (None unless ``want_image``: the ABI then gets NULL and skips it)."""
@@ -79,6 +87,11 @@ def backbone_backward(flat: torch.Tensor, grad_taps, ws: torch.Tensor, compound_
     g_flat = torch.empty_like(flat)
     g_img = torch.empty((B, 3, size, size), dtype=torch.float32, device=dev) if want_image else None
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if sync is not None:               # (the forward's hook: grad_flat is this replica's contribution, to be SUMMED over the replicas)
+        sync.register(ws)
+        sync.check(_capi.lib().hep_backbone_backward_device_sync(flat.data_ptr(), _capi.ptr_array(list(grad_taps)), _capi.ptr(branch_scale), compound_coef,
+                                                                 size, B, g_flat.data_ptr(), _capi.ptr(g_img), ws.data_ptr(), ws.numel(), sync.ref(), stream))
+        return g_flat, g_img
     _capi.check(_capi.lib().hep_backbone_backward_device_bn(flat.data_ptr(), _capi.ptr_array(list(grad_taps)), _capi.ptr(branch_scale), compound_coef,
                                                             size, B, g_flat.data_ptr(), _capi.ptr(g_img), ws.data_ptr(), ws.numel(), bn_mode, stream))
     return g_flat, g_img
@@ -119,20 +132,21 @@ class _Backbone(torch.autograd.Function):
     """The two ABI calls as one differentiable function of (flat parameters, image); the branch scales are data."""
 
     @staticmethod
-    def forward(ctx, flat, image, phi, scale, bn_mode, stats):
-        taps, ws = backbone_forward(flat, image, phi, scale, bn_mode, stats=stats)
+    def forward(ctx, flat, image, phi, scale, bn_mode, stats, sync):
+        taps, ws = backbone_forward(flat, image, phi, scale, bn_mode, stats=stats, sync=sync)
         ctx.save_for_backward(flat, ws, *(() if scale is None else (scale,)))
-        ctx.cfg = (phi, int(image.shape[-1]), [tuple(t.shape) for t in taps], bn_mode)
+        ctx.cfg = (phi, int(image.shape[-1]), [tuple(t.shape) for t in taps], bn_mode, sync)
         return taps
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grad_taps):
         flat, ws, *rest = ctx.saved_tensors
-        phi, size, shapes, bn_mode = ctx.cfg
+        phi, size, shapes, bn_mode, sync = ctx.cfg
         gs = _trainable.cotangents(grad_taps, shapes, flat.device)
-        g_flat, g_img = backbone_backward(flat, gs, ws, phi, size, rest[0] if rest else None, want_image=ctx.needs_input_grad[1], bn_mode=bn_mode)
-        return (g_flat if ctx.needs_input_grad[0] else None, g_img, None, None, None, None)
+        g_flat, g_img = backbone_backward(flat, gs, ws, phi, size, rest[0] if rest else None, want_image=ctx.needs_input_grad[1], bn_mode=bn_mode,
+                                         sync=sync)
+        return (g_flat if ctx.needs_input_grad[0] else None, g_img, None, None, None, None, None)
 
 
 class TrainableBackbone(_trainable.TrainablePart):
@@ -148,9 +162,9 @@ class TrainableBackbone(_trainable.TrainablePart):
 
     NOUN, spec = "backbone", staticmethod(backbone_spec)
 
-    def __init__(self, compound_coef: int = 0, drop_connect_rate: float = 0.0, batch_norm: str = "running"):
+    def __init__(self, compound_coef: int = 0, drop_connect_rate: float = 0.0, batch_norm: str = "running", process_group=None):
         super().__init__()
-        self._set_batch_norm(batch_norm)
+        self._set_batch_norm(batch_norm, process_group)
         self.compound_coef = int(compound_coef)
         self.arch = get_arch(self.compound_coef)
         self.drop_connect_rate = float(drop_connect_rate)
@@ -187,7 +201,7 @@ class TrainableBackbone(_trainable.TrainablePart):
             branch_scale = branch_scale.detach().to(device=x.device, dtype=torch.float32).contiguous()
         bn_mode = self._bn_mode()
         stats = torch.empty_like(flat) if bn_mode == _trainable.BN_BATCH else None
-        taps = _Backbone.apply(flat, x.contiguous(), self.compound_coef, branch_scale, bn_mode, stats)
+        taps = _Backbone.apply(flat, x.contiguous(), self.compound_coef, branch_scale, bn_mode, stats, self._sync_hook())
         if stats is not None:
             self._store_statistics(stats)
         return taps

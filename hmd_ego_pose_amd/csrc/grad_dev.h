@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "hep_dev.h"
+#include "hep_internal.h"
 
 #define GD_THREADS 256
 #define GD_BM 64
@@ -202,6 +203,10 @@ struct GDBnJob {
   const float* dbn;      // dz: the reduced d gamma, d beta [2][C]
   const float* res; const float* scale;   // apply GD_BN_SCALE_SKIP: the rows to add, the per-image scale of bn(z) (NULL: 1); images of ss rows
   int R, C, ss;
+  // synchronised statistics only (GDSync below): this BatchNorm's slice [2 C + 2] of the exchange block; the float partials
+  // [pn][pstride] of d gamma and d beta that the part's own reduce reads (the same partials, the same order)
+  double* xch;
+  const float* pg; const float* pb; int pn, pstride;
 };
 template <int NJOBS> struct GDBnArgs { GDBnJob j[NJOBS]; int tile_rows; float momentum; };
 
@@ -222,8 +227,22 @@ template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_stats_k
   j.part[((int64_t)tile * j.C + c) * 2 + 1] = q;
 }
 
-// workgroup = 16 channels x 16 partial lanes (gd_reduce_core_d, twice)
-template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_finish_kernel(GDBnArgs<NJOBS> a) {
+// mean, biased variance, the effective table and the running-statistics update of channel c from the sums s = sum z, q = sum z^2
+// over n rows, all in double (one body for the local and the synchronised finish: the same sums give the same bits)
+__device__ __forceinline__ void gd_bn_finish_write(const GDBnJob& j, int c, double s, double q, double n, float momentum) {
+  const int C = j.C;
+  const double mean = s / n, var = fmax((q - mean * s) / n, 0.0);
+  j.eff[c] = j.bn[c]; j.eff[C + c] = j.bn[C + c]; j.eff[2 * C + c] = (float)mean; j.eff[3 * C + c] = (float)var;
+  if (j.stats) {
+    const double m = (double)momentum;
+    j.stats[2 * C + c] = (float)((1.0 - m) * (double)j.bn[2 * C + c] + m * mean);
+    j.stats[3 * C + c] = (float)((1.0 - m) * (double)j.bn[3 * C + c] + m * (var * n / (n - 1.0)));
+  }
+}
+
+// workgroup = 16 channels x 16 partial lanes (gd_reduce_core_d, twice).  SYNC: the sums and the row count go to the job's
+// slice of the exchange block instead (sum z [C], sum z^2 [C], R, 0), the finish waits for the other replicas' (below)
+template <int NJOBS, bool SYNC = false> __global__ __launch_bounds__(GD_THREADS) void gd_bn_finish_kernel(GDBnArgs<NJOBS> a) {
   const GDBnJob& j = a.j[blockIdx.y];
   const int el = threadIdx.x % GD_RED_E, kl = threadIdx.x / GD_RED_E, C = j.C;
   if ((int)blockIdx.x * GD_RED_E >= C) return;              // uniform over the workgroup
@@ -234,13 +253,19 @@ template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_finish_
   __syncthreads();                                          // the first sum is read before the second reuses the staging array
   const double q = gd_reduce_core_d(live ? j.part + 2 * c + 1 : nullptr, (int64_t)2 * C, 0, tiles, el, kl);
   if (kl != 0 || !live) return;
-  const double n = (double)j.R, mean = s / n, var = fmax((q - mean * s) / n, 0.0);
-  j.eff[c] = j.bn[c]; j.eff[C + c] = j.bn[C + c]; j.eff[2 * C + c] = (float)mean; j.eff[3 * C + c] = (float)var;
-  if (j.stats) {
-    const double m = (double)a.momentum;
-    j.stats[2 * C + c] = (float)((1.0 - m) * (double)j.bn[2 * C + c] + m * mean);
-    j.stats[3 * C + c] = (float)((1.0 - m) * (double)j.bn[3 * C + c] + m * (var * n / (n - 1.0)));
+  if (SYNC) {
+    j.xch[c] = s; j.xch[C + c] = q;
+    if (c == 0) { j.xch[2 * C] = (double)j.R; j.xch[2 * C + 1] = 0.0; }
+  } else {
+    gd_bn_finish_write(j, c, s, q, (double)j.R, a.momentum);
   }
+}
+// the finish over the GLOBAL sums and row count of the exchange block; thread = channel
+template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_sync_finish_kernel(GDBnArgs<NJOBS> a) {
+  const GDBnJob& j = a.j[blockIdx.y];
+  const int c = blockIdx.x * GD_THREADS + threadIdx.x, C = j.C;
+  if (c >= C) return;
+  gd_bn_finish_write(j, c, j.xch[c], j.xch[C + c], j.xch[2 * C], a.momentum);
 }
 
 // a = bn(z) with the effective table, then nothing | swish(a) | a * scale[image] + res; thread = (GD_DW_ROWS consecutive rows, channel)
@@ -261,8 +286,9 @@ template <int NJOBS, int EPI> __global__ __launch_bounds__(GD_THREADS) void gd_b
   }
 }
 
-// d z -= gamma rstd (d beta + x^ d gamma) / R; thread = (GD_DW_ROWS consecutive rows, channel)
-template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_dz_kernel(GDBnArgs<NJOBS> a) {
+// d z -= gamma rstd (d beta + x^ d gamma) / R; thread = (GD_DW_ROWS consecutive rows, channel).  SYNC: the global sums (rounded
+// once, here) and the global row count of the exchange block
+template <int NJOBS, bool SYNC = false> __global__ __launch_bounds__(GD_THREADS) void gd_bn_dz_kernel(GDBnArgs<NJOBS> a) {
   const GDBnJob& j = a.j[blockIdx.y];
   const int64_t gid = (int64_t)blockIdx.x * GD_THREADS + threadIdx.x;
   const int64_t ra = gid / j.C * GD_DW_ROWS;
@@ -270,11 +296,27 @@ template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_dz_kern
   if (ra >= j.R) return;
   const int rb = (int)min((int64_t)j.R, ra + GD_DW_ROWS);
   const GDBn q = gd_bn_load(j.eff, j.C, c);
-  const float dg = j.dbn[c], db = j.dbn[j.C + c], k = q.gamma * q.rstd / (float)j.R;
+  const float dg = SYNC ? (float)j.xch[c] : j.dbn[c], db = SYNC ? (float)j.xch[j.C + c] : j.dbn[j.C + c];
+  const float k = q.gamma * q.rstd / (SYNC ? (float)j.xch[2 * j.C] : (float)j.R);
   for (int r = (int)ra; r < rb; r++) {
     const float zh = (j.z[(int64_t)r * j.C + c] - q.mean) * q.rstd;
     j.io[(int64_t)r * j.C + c] = fmaf(-k, fmaf(zh, dg, db), j.io[(int64_t)r * j.C + c]);
   }
+}
+// this replica's d gamma, d beta [C] before their rounding to float, and its row count, into the job's slice of the exchange
+// block: the walk of the part's own reduce over the same partials (gd_reduce_core_d); workgroup = 16 channels x 16 partial lanes
+template <int NJOBS> __global__ __launch_bounds__(GD_THREADS) void gd_bn_sync_dsums_kernel(GDBnArgs<NJOBS> a) {
+  const GDBnJob& j = a.j[blockIdx.y];
+  const int el = threadIdx.x % GD_RED_E, kl = threadIdx.x / GD_RED_E, C = j.C;
+  if ((int)blockIdx.x * GD_RED_E >= C) return;              // uniform over the workgroup
+  const int c = blockIdx.x * GD_RED_E + el;
+  const bool live = c < C;
+  const double dg = gd_reduce_core_d(live ? j.pg + c : nullptr, (int64_t)j.pstride, 0, j.pn, el, kl);
+  __syncthreads();
+  const double db = gd_reduce_core_d(live ? j.pb + c : nullptr, (int64_t)j.pstride, 0, j.pn, el, kl);
+  if (kl != 0 || !live) return;
+  j.xch[c] = dg; j.xch[C + c] = db;
+  if (c == 0) { j.xch[2 * C] = (double)j.R; j.xch[2 * C + 1] = 0.0; }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -286,17 +328,45 @@ static inline void gd_slabs(int R, int max_slabs, int* slab_rows, int* nslab) {
   *slab_rows = ((R + ns - 1) / ns + GD_BK - 1) / GD_BK * GD_BK;
   *nslab = (R + *slab_rows - 1) / *slab_rows;
 }
+// Synchronised statistics: the sums of every BatchNorm of a launch cross the replicas in ONE contiguous block of doubles in
+// the caller's workspace, job after job [sum z | sum z^2 | R, 0] (forward) or [d gamma | d beta | R, 0] (backward), through
+// the caller's hook (hep_sync of include/hep.h): when the work it enqueued on the stream has run, every element is the sum over
+// all replicas.  A hook that fails ends the call: GDSyncFailed leaves the launch function, nothing further is launched.
+struct GDSync { int (*sum)(void* ctx, void* data, int64_t count, int is_double, void* stream); void* ctx; double* block; };
+template <int NJOBS> static inline void gd_sync_exchange(GDBnArgs<NJOBS>* a, const GDSync& sy, hipStream_t st, bool backward, int max_c) {
+  int64_t n = 0;
+  for (int k = 0; k < NJOBS; k++) { a->j[k].xch = sy.block + n; n += 2 * (int64_t)a->j[k].C + 2; }
+  const dim3 grid((unsigned)((max_c + GD_RED_E - 1) / GD_RED_E), NJOBS);
+  if (backward) hipLaunchKernelGGL(gd_bn_sync_dsums_kernel<NJOBS>, grid, dim3(GD_THREADS), 0, st, *a);
+  else hipLaunchKernelGGL((gd_bn_finish_kernel<NJOBS, true>), grid, dim3(GD_THREADS), 0, st, *a);
+  if (const int rc = sy.sum(sy.ctx, sy.block, n, 1, (void*)st)) throw GDSyncFailed{rc};
+}
+// doubles of the exchange block of a launch over njobs BatchNorms of at most max_c channels
+static inline int64_t gd_sync_doubles(int njobs, int max_c) { return (int64_t)njobs * (2 * (int64_t)max_c + 2); }
+
 // the batch-statistics launches over NJOBS BatchNorms whose largest map has max_rows rows and max_c channels
-template <int NJOBS> static inline void gd_bn_forward(const GDBnArgs<NJOBS>& a, int max_rows, int max_c, int epi, hipStream_t st) {
+template <int NJOBS> static inline void gd_bn_forward(GDBnArgs<NJOBS>& a, int max_rows, int max_c, int epi, hipStream_t st, const GDSync* sy = nullptr) {
   const int64_t tiles = (max_rows + a.tile_rows - 1) / a.tile_rows, quads = (max_rows + GD_DW_ROWS - 1) / GD_DW_ROWS;
   hipLaunchKernelGGL(gd_bn_stats_kernel<NJOBS>, dim3(gd_blocks(tiles * max_c), NJOBS), dim3(GD_THREADS), 0, st, a);
-  hipLaunchKernelGGL(gd_bn_finish_kernel<NJOBS>, dim3((unsigned)((max_c + GD_RED_E - 1) / GD_RED_E), NJOBS), dim3(GD_THREADS), 0, st, a);
+  if (sy) {
+    gd_sync_exchange(&a, *sy, st, false, max_c);
+    hipLaunchKernelGGL(gd_bn_sync_finish_kernel<NJOBS>, dim3(gd_blocks(max_c), NJOBS), dim3(GD_THREADS), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((gd_bn_finish_kernel<NJOBS, false>), dim3((unsigned)((max_c + GD_RED_E - 1) / GD_RED_E), NJOBS), dim3(GD_THREADS), 0, st, a);
+  }
   const dim3 grid(gd_blocks(quads * max_c), NJOBS);
   if (epi == GD_BN_SWISH) hipLaunchKernelGGL((gd_bn_apply_kernel<NJOBS, GD_BN_SWISH>), grid, dim3(GD_THREADS), 0, st, a);
   else if (epi == GD_BN_SCALE_SKIP) hipLaunchKernelGGL((gd_bn_apply_kernel<NJOBS, GD_BN_SCALE_SKIP>), grid, dim3(GD_THREADS), 0, st, a);
   else hipLaunchKernelGGL((gd_bn_apply_kernel<NJOBS, GD_BN_PLAIN>), grid, dim3(GD_THREADS), 0, st, a);
 }
-template <int NJOBS> static inline void gd_bn_dz(const GDBnArgs<NJOBS>& a, int max_rows, int max_c, hipStream_t st) {
+// sy: the jobs carry pg / pb / pn / pstride, the partials the part's reduce of d gamma / d beta has just read
+template <int NJOBS> static inline void gd_bn_dz(GDBnArgs<NJOBS>& a, int max_rows, int max_c, hipStream_t st, const GDSync* sy = nullptr) {
   const int64_t quads = (max_rows + GD_DW_ROWS - 1) / GD_DW_ROWS;
-  hipLaunchKernelGGL(gd_bn_dz_kernel<NJOBS>, dim3(gd_blocks(quads * max_c), NJOBS), dim3(GD_THREADS), 0, st, a);
+  const dim3 grid(gd_blocks(quads * max_c), NJOBS);
+  if (sy) {
+    gd_sync_exchange(&a, *sy, st, true, max_c);
+    hipLaunchKernelGGL((gd_bn_dz_kernel<NJOBS, true>), grid, dim3(GD_THREADS), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((gd_bn_dz_kernel<NJOBS, false>), grid, dim3(GD_THREADS), 0, st, a);
+  }
 }

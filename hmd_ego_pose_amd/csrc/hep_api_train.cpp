@@ -82,7 +82,7 @@ int hep_losses_backward_device(const float* gt_classification, const float* clas
 namespace {
 template <class Plan> struct Part {
   const char *name, *noun;
-  int (*plan)(int phi, int num_classes, int size, int batch, Plan* p, const char** why, int bn_mode);
+  int (*plan)(int phi, int num_classes, int size, int batch, Plan* p, const char** why, int bn_mode, int sync);
   int (*tensor_count)(const Plan&); void (*tensor_offsets)(const Plan&, int64_t* offsets);
   int (*stage_count)(const Plan&); int (*stage)(const Plan&, int i, char name[32], int64_t dims[4], int64_t* offset_floats);      // (NULL for the heads: no stage_* call is theirs)
 };
@@ -90,10 +90,11 @@ const Part<HGPlan> kHeads = {"heads", "head", heads_plan, heads_tensor_count, he
 const Part<NGPlan> kNeck = {"neck", "neck", neck_plan, neck_tensor_count, neck_tensor_offsets, neck_stage_count, neck_stage};
 const Part<BGPlan> kBackbone = {"backbone", "backbone", backbone_plan, backbone_tensor_count, backbone_tensor_offsets, backbone_stage_count, backbone_stage};
 // fills the part's plan.  size == batch == 0 is how the plan functions are asked for the parameter layout alone (layout_only): a run may not say it
-template <class Plan> int plan_part(const Part<Plan>& part, int phi, int num_classes, int size, int batch, int bn_mode, Plan* p, bool layout_only = false) {
+template <class Plan> int plan_part(const Part<Plan>& part, int phi, int num_classes, int size, int batch, int bn_mode, Plan* p, bool layout_only = false,
+                                    bool sync = false) {
   const char* why = "";
   if (!layout_only && size == 0 && batch == 0) return fail(HEP_ERR_UNSUPPORTED, std::string(part.name) + ": size must be a multiple of 128 in [128, 2048]");
-  if (int rc = part.plan(phi, num_classes, size, batch, p, &why, bn_mode)) return fail(rc, why);
+  if (int rc = part.plan(phi, num_classes, size, batch, p, &why, bn_mode, sync)) return fail(rc, why);
   return 0;
 }
 template <class Plan> int64_t param_count(const Part<Plan>& part, int phi, int num_classes) {
@@ -107,19 +108,25 @@ template <class Plan> int param_layout(const Part<Plan>& part, int phi, int num_
   if (offsets) part.tensor_offsets(p, offsets);
   return count;
 }
-template <class Plan> int64_t workspace_bytes(const Part<Plan>& part, int phi, int num_classes, int size, int batch, int bn_mode) {
-  Plan p; const int rc = plan_part(part, phi, num_classes, size, batch, bn_mode, &p);
+template <class Plan> int64_t workspace_bytes(const Part<Plan>& part, int phi, int num_classes, int size, int batch, int bn_mode, bool sync = false) {
+  Plan p; const int rc = plan_part(part, phi, num_classes, size, batch, bn_mode, &p, false, sync);
   return rc ? rc : p.ws_floats * (int64_t)sizeof(float);
 }
-// a forward or backward behind the checks of its own pointers: the momentum (a backward passes 0), the plan, the workspace, `launch(plan, workspace)`, its status
+// a forward or backward behind the checks of its own pointers: the momentum (a backward passes 0), the plan, the workspace, `launch(plan, workspace)`, its status.
+// sync (the *_sync group): batch statistics over all replicas through the caller's hook, checked first; a hook that fails ends the launch (GDSyncFailed)
 template <class Plan, class Launch> int run(const Part<Plan>& part, int phi, int num_classes, int size, int batch, int bn_mode, float momentum, void* workspace,
-                                            size_t workspace_bytes, Launch launch) {
+                                            size_t workspace_bytes, Launch launch, const hep_sync* const* sync = nullptr) {
   const std::string name = part.name;
+  if (sync && (!*sync || !(*sync)->sum)) return fail(HEP_ERR_INVALID, name + ": sync and sync->sum must not be NULL");
   if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, name + ": the BatchNorm momentum must be in [0, 1]");
-  Plan p; if (int rc = plan_part(part, phi, num_classes, size, batch, bn_mode, &p)) return rc;
+  Plan p; if (int rc = plan_part(part, phi, num_classes, size, batch, bn_mode, &p, false, sync != nullptr)) return rc;
   if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, name + ": the workspace must be 16-byte aligned");
   if (workspace_bytes < (size_t)p.ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, name + ": the workspace is smaller than hep_" + name + "_workspace_bytes");
-  launch(p, (float*)workspace);
+  try {
+    launch(p, (float*)workspace);
+  } catch (const GDSyncFailed& e) {
+    return fail(HEP_ERR_DEVICE, name + ": the sum hook (hep_sync.sum) returned " + std::to_string(e.rc) + ": nothing further was launched");
+  }
   HIPRET(hipGetLastError());
   return 0;
 }
@@ -166,6 +173,22 @@ int hep_heads_backward_device(const float* params, const float* const grad_outs[
                               float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes, void* stream) try {
   return hep_heads_backward_device_bn(params, grad_outs, phi, num_classes, size, batch, grad_params, grad_feats, workspace, workspace_bytes, HEP_BN_RUNNING, stream);
 } HEP_CATCH_INT
+// synchronised statistics: HEP_BN_BATCH over the rows of all replicas (all three parts alike)
+int64_t hep_heads_workspace_bytes_sync(int phi, int num_classes, int size, int batch) try { return workspace_bytes(kHeads, phi, num_classes, size, batch, HEP_BN_BATCH, true); } HEP_CATCH_INT
+int hep_heads_forward_device_sync(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch, float* const outs[5],
+                                  void* workspace, size_t workspace_bytes, float momentum, float* stats_out, const hep_sync* sync, void* stream) try {
+  if (!params || !feats || !outs || !workspace || any_null(feats, 5) || any_null(outs, 5)) return fail(HEP_ERR_INVALID, "bad argument");
+  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  return run(kHeads, phi, num_classes, size, batch, HEP_BN_BATCH, momentum, workspace, workspace_bytes,
+             [&](const HGPlan& p, float* ws) { launch_heads_forward(p, params, feats, outs, ws, (hipStream_t)stream, momentum, stats_out, sync); }, &sync);
+} HEP_CATCH_INT
+int hep_heads_backward_device_sync(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch, float* grad_params,
+                                   float* const grad_feats[5], void* workspace, size_t workspace_bytes, const hep_sync* sync, void* stream) try {
+  if (!params || !grad_outs || !grad_params || !workspace || any_null(grad_outs, 5) || (grad_feats && any_null(grad_feats, 5))) return fail(HEP_ERR_INVALID, "bad argument");
+  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  return run(kHeads, phi, num_classes, size, batch, HEP_BN_BATCH, 0.0f, workspace, workspace_bytes,
+             [&](const HGPlan& p, float* ws) { launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, ws, (hipStream_t)stream, sync); }, &sync);
+} HEP_CATCH_INT
 
 // ---- the BiFPN neck ----
 int64_t hep_neck_param_count(int phi) try { return param_count(kNeck, phi, 0); } HEP_CATCH_INT
@@ -196,6 +219,19 @@ int hep_neck_backward_device(const float* params, const float* const grad_feats[
                              float* const grad_taps[3], void* workspace, size_t workspace_bytes, void* stream) try {
   return hep_neck_backward_device_bn(params, grad_feats, phi, size, batch, grad_params, grad_taps, workspace, workspace_bytes, HEP_BN_RUNNING, stream);
 } HEP_CATCH_INT
+int64_t hep_neck_workspace_bytes_sync(int phi, int size, int batch) try { return workspace_bytes(kNeck, phi, 0, size, batch, HEP_BN_BATCH, true); } HEP_CATCH_INT
+int hep_neck_forward_device_sync(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                                 void* workspace, size_t workspace_bytes, float momentum, float* stats_out, const hep_sync* sync, void* stream) try {
+  if (!params || !taps || !feats || !workspace || any_null(taps, 3) || any_null(feats, 5)) return fail(HEP_ERR_INVALID, "bad argument");
+  return run(kNeck, phi, 0, size, batch, HEP_BN_BATCH, momentum, workspace, workspace_bytes,
+             [&](const NGPlan& p, float* ws) { launch_neck_forward(p, params, taps, feats, ws, (hipStream_t)stream, momentum, stats_out, sync); }, &sync);
+} HEP_CATCH_INT
+int hep_neck_backward_device_sync(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
+                                  float* const grad_taps[3], void* workspace, size_t workspace_bytes, const hep_sync* sync, void* stream) try {
+  if (!params || !grad_feats || !grad_params || !workspace || any_null(grad_feats, 5) || (grad_taps && any_null(grad_taps, 3))) return fail(HEP_ERR_INVALID, "bad argument");
+  return run(kNeck, phi, 0, size, batch, HEP_BN_BATCH, 0.0f, workspace, workspace_bytes,
+             [&](const NGPlan& p, float* ws) { launch_neck_backward(p, grad_feats, grad_params, grad_taps, ws, (hipStream_t)stream, sync); }, &sync);
+} HEP_CATCH_INT
 
 // ---- the EfficientNet trunk ----
 int64_t hep_backbone_param_count(int phi) try { return param_count(kBackbone, phi, 0); } HEP_CATCH_INT
@@ -225,6 +261,19 @@ int hep_backbone_backward_device_bn(const float* params, const float* const grad
 int hep_backbone_backward_device(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
                                  float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, void* stream) try {
   return hep_backbone_backward_device_bn(params, grad_taps, branch_scale, phi, size, batch, grad_params, grad_image, workspace, workspace_bytes, HEP_BN_RUNNING, stream);
+} HEP_CATCH_INT
+int64_t hep_backbone_workspace_bytes_sync(int phi, int size, int batch) try { return workspace_bytes(kBackbone, phi, 0, size, batch, HEP_BN_BATCH, true); } HEP_CATCH_INT
+int hep_backbone_forward_device_sync(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch, float* const taps[3],
+                                     void* workspace, size_t workspace_bytes, float momentum, float* stats_out, const hep_sync* sync, void* stream) try {
+  if (!params || !image || !taps || !workspace || any_null(taps, 3)) return fail(HEP_ERR_INVALID, "bad argument");
+  return run(kBackbone, phi, 0, size, batch, HEP_BN_BATCH, momentum, workspace, workspace_bytes,
+             [&](const BGPlan& p, float* ws) { launch_backbone_forward(p, params, image, branch_scale, taps, ws, (hipStream_t)stream, momentum, stats_out, sync); }, &sync);
+} HEP_CATCH_INT
+int hep_backbone_backward_device_sync(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size, int batch,
+                                      float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes, const hep_sync* sync, void* stream) try {
+  if (!params || !grad_taps || !grad_params || !workspace || any_null(grad_taps, 3)) return fail(HEP_ERR_INVALID, "bad argument");
+  return run(kBackbone, phi, 0, size, batch, HEP_BN_BATCH, 0.0f, workspace, workspace_bytes,
+             [&](const BGPlan& p, float* ws) { launch_backbone_backward(p, grad_taps, branch_scale, grad_params, grad_image, ws, (hipStream_t)stream, sync); }, &sync);
 } HEP_CATCH_INT
 
 // ---- training input: 6DoF augmentation + preprocess (k_augment.hip) ----

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct hep_sync;      // include/hep.h: the sum hook of synchronised BatchNorm
+struct GDSyncFailed { int rc; };      // thrown by a launch function whose hook returned rc != 0 (grad_dev.h); caught at the ABI
+
 // exact unsigned division by a launch-time constant: rcp_u32(d) on the host, udiv_rcp(x, rcp) in the kernel.
 // floor(x / d) == mulhi(x, floor(2^32 / d) + 1) whenever x * d < 2^32 (grid indices and tile counts here); d == 1 is
 // flagged with rcp == 0.  A run-time integer division costs ~30 VALU instructions per wave.
@@ -476,16 +479,18 @@ struct HGPlan {
       o_pg[2], o_pb[2], o_pbi[2], ws_floats;            // float offsets into the workspace
   int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
   int64_t o_bne, o_bnp;                                 // ... its effective tables (layout of p_bn per net) and the statistics partials
+  int bn_sync; int64_t o_xch;                           // synchronised statistics (with bn_batch): the exchange block of grad_dev.h's GDSync
 };
 // fills the plan; returns 0, or a negative HEP_ERR_* with a reason in *why (a static string)
-int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode = 0);
+int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode = 0, int sync = 0);
 int heads_tensor_count(const HGPlan&);      // the tensors of the flat buffer in state_dict order: how many, and (below) the float offset of each; all three parts alike
 void heads_tensor_offsets(const HGPlan&, int64_t* offsets);
 // momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
+// sync: the plan's bn_sync only (the hook the sums of every BatchNorm cross the replicas through; forward and backward alike, all three parts)
 void launch_heads_forward(const HGPlan&, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t,
-                          float momentum = 0.0f, float* stats_out = nullptr);
+                          float momentum = 0.0f, float* stats_out = nullptr, const hep_sync* sync = nullptr);
 void launch_heads_backward(const HGPlan&, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
-                           float* ws, hipStream_t);
+                           float* ws, hipStream_t, const hep_sync* sync = nullptr);
 
 // ---- training side: forward and backward of the BiFPN neck (k_neck_grad.hip) ----
 // Every map is fp32 rows [B * s_l * s_l][C] in a buffer of its own; the parameters are read from an aligned copy in the workspace.
@@ -508,10 +513,11 @@ struct NGPlan {
   int64_t o_x, o_dz, o_du, o_ds[2][NG_NODES], o_g6, o_g7, o_pw, o_pdw, o_pb[3], o_pf[3], o_dtap[NG_LATERALS], ws_floats;
   int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
   int64_t o_bne, o_bnp;                                 // ... an effective table per BatchNorm (laterals, then cell by cell); the statistics partials
+  int bn_sync; int64_t o_xch;                           // synchronised statistics (with bn_batch): the exchange block of grad_dev.h's GDSync
 };
 // fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why.  The three plan
 // functions have one signature: num_classes is the heads' alone and ignored here
-int neck_plan(int phi, int num_classes, int size, int batch, NGPlan* p, const char** why, int bn_mode = 0);
+int neck_plan(int phi, int num_classes, int size, int batch, NGPlan* p, const char** why, int bn_mode = 0, int sync = 0);
 int neck_tensor_count(const NGPlan&);
 void neck_tensor_offsets(const NGPlan&, int64_t* offsets);
 // stage i of the workspace a forward leaves: its name, NHWC dims and float offset; -1 for an index past the end (neck and backbone alike)
@@ -519,8 +525,9 @@ int neck_stage_count(const NGPlan&);
 int neck_stage(const NGPlan&, int i, char name[32], int64_t dims[4], int64_t* offset_floats);
 // momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
 void launch_neck_forward(const NGPlan&, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t,
-                         float momentum = 0.0f, float* stats_out = nullptr);
-void launch_neck_backward(const NGPlan&, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t);
+                         float momentum = 0.0f, float* stats_out = nullptr, const hep_sync* sync = nullptr);
+void launch_neck_backward(const NGPlan&, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t,
+                          const hep_sync* sync = nullptr);
 
 // ---- training side: forward and backward of the EfficientNet trunk (k_backbone_grad.hip) ----
 // Every map is fp32 rows [B * s * s][C] in a buffer of its own; the parameters are read from an aligned copy in the workspace.
@@ -548,18 +555,19 @@ struct BGPlan {
   int64_t q_stem, o_img, o_zs, o_as, o_a1, o_dy[2], o_dz2, o_dxg, o_da0, o_dx, o_pw, o_pcol[2], o_pdw, o_pse, o_dl, o_dr, o_dm, ws_floats;
   int bn_batch;                                         // HEP_BN_BATCH: batch-statistics BatchNorm (the passes of grad_dev.h)
   int64_t o_es, o_bnp;                                  // ... the stem's effective table; the statistics partials
+  int bn_sync; int64_t o_xch;                           // synchronised statistics (with bn_batch): the exchange block of grad_dev.h's GDSync
 };
 // fills the plan (size == batch == 0: the parameter layout only); returns 0, or a negative HEP_ERR_* with a reason in *why
-int backbone_plan(int phi, int num_classes, int size, int batch, BGPlan* p, const char** why, int bn_mode = 0);      // (num_classes ignored, as neck_plan)
+int backbone_plan(int phi, int num_classes, int size, int batch, BGPlan* p, const char** why, int bn_mode = 0, int sync = 0);      // (num_classes ignored, as neck_plan)
 int backbone_tensor_count(const BGPlan&);
 void backbone_tensor_offsets(const BGPlan&, int64_t* offsets);
 int backbone_stage_count(const BGPlan&);
 int backbone_stage(const BGPlan&, int i, char name[32], int64_t dims[4], int64_t* offset_floats);
 // momentum, stats_out: batch statistics only (stats_out: layout of params, the running_mean / running_var slots written; NULL: no update)
 void launch_backbone_forward(const BGPlan&, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t,
-                             float momentum = 0.0f, float* stats_out = nullptr);
+                             float momentum = 0.0f, float* stats_out = nullptr, const hep_sync* sync = nullptr);
 void launch_backbone_backward(const BGPlan&, const float* const grad_taps[3], const float* branch_scale, float* grad_params, float* grad_image, float* ws,
-                              hipStream_t);
+                              hipStream_t, const hep_sync* sync = nullptr);
 
 void launch_stem(const StemArgs&, hipStream_t);
 int stem_uses_mfma(int cout, int force = -1);      // which of the two stem kernels the plan takes (force: Knobs::stem_mfma, -1 = by width)

@@ -462,10 +462,10 @@ static inline void bg_chunks(int ss, int* chunk_rows, int* nchunk) {
   *nchunk = (ss + *chunk_rows - 1) / *chunk_rows;
 }
 
-int backbone_plan(int phi, int, int size, int batch, BGPlan* p, const char** why, int bn_mode) {
+int backbone_plan(int phi, int, int size, int batch, BGPlan* p, const char** why, int bn_mode, int sync) {
   hep::Arch arch;
   if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "backbone: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
-  p->bn_batch = bn_mode == HEP_BN_BATCH;
+  p->bn_batch = bn_mode == HEP_BN_BATCH; p->bn_sync = p->bn_batch && sync;
   if (!hep::make_arch(phi, &arch)) { *why = "backbone: phi must be in 0..7 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
   if ((int)arch.blocks.size() > BG_MAX_BLOCKS) { *why = "backbone: too many blocks"; return HEP_ERR_UNSUPPORTED; }
   p->phi = phi; p->nblocks = (int)arch.blocks.size(); p->stem = arch.stem; p->B = 0; p->size = 0;
@@ -546,6 +546,12 @@ int backbone_plan(int phi, int, int size, int batch, BGPlan* p, const char** why
     }
     p->o_bnp = take(4 * m_col);
   }
+  p->o_xch = 0;
+  if (p->bn_sync) {                                        // the widest BatchNorm's sums
+    int cmax = p->stem;
+    for (int i = 0; i < p->nblocks; i++) cmax = std::max(cmax, std::max(p->b[i].cexp, p->b[i].cout));
+    p->o_xch = take(2 * gd_sync_doubles(1, cmax));
+  }
   p->ws_floats = w;
   return 0;
 }
@@ -617,26 +623,30 @@ GDBnArgs<1> bg_bn_job(const BGPlan& p, float* ws, int R, int C, const float* z, 
 }
 // what follows the kernel that left the "frozen" d z and the gamma / beta partials: their reduce first, then d z corrected in
 // place - before any product reads it; the stage's own reduce then has its weight job only
-void bg_bn_backward(const BGPlan& p, float* ws, int R, int C, const float* z, int64_t eff_at, float* dz, float* dbn, hipStream_t st) {
+inline GDSync bg_sync(const BGPlan& p, float* ws, const hep_sync* sync) { return GDSync{sync->sum, sync->ctx, reinterpret_cast<double*>(ws + p.o_xch)}; }
+void bg_bn_backward(const BGPlan& p, float* ws, int R, int C, const float* z, int64_t eff_at, float* dz, float* dbn, hipStream_t st, const GDSync* sy) {
   GDReduceArgs<BG_RED_JOBS> rd{};
   bg_bn_jobs(p, ws, R, C, dbn, &rd, 1);
   bg_reduce(rd, st);
   GDBnArgs<1> a = bg_bn_job(p, ws, R, C, z, nullptr, eff_at);
   a.j[0].io = dz; a.j[0].dbn = dbn;
-  gd_bn_dz(a, R, C, st);
+  a.j[0].pg = ws + p.o_pcol[0]; a.j[0].pb = ws + p.o_pcol[1]; a.j[0].pn = bg_ntiles(R); a.j[0].pstride = C;
+  gd_bn_dz(a, R, C, st, sy);
 }
 }  // namespace
 
 void launch_backbone_forward(const BGPlan& p, const float* params, const float* image, const float* branch_scale, float* const taps[3], float* ws, hipStream_t st,
-                             float momentum, float* stats_out) {
+                             float momentum, float* stats_out, const hep_sync* sync) {
   const int B = p.B, zo = p.bn_batch;
+  GDSync sy{};
+  if (p.bn_sync) sy = bg_sync(p, ws, sync);
   // batch statistics: z -> statistics -> the effective table and the running-statistics update -> the activation
   auto bn_forward = [&](int R, int C, const float* z, const float* bn, int64_t eff_at, int64_t table_at, float* out, int epi, const float* res,
                         const float* scale, int ss) {
     GDBnArgs<1> a = bg_bn_job(p, ws, R, C, z, bn, eff_at);
     a.momentum = momentum;
     a.j[0].io = out; a.j[0].stats = stats_out ? stats_out + table_at : nullptr; a.j[0].res = res; a.j[0].scale = scale; a.j[0].ss = ss;
-    gd_bn_forward(a, R, C, epi, st);
+    gd_bn_forward(a, R, C, epi, st, p.bn_sync ? &sy : nullptr);
   };
   {
     BGPackArgs pk{};
@@ -700,8 +710,11 @@ void launch_backbone_forward(const BGPlan& p, const float* params, const float* 
 }
 
 void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], const float* branch_scale, float* grad_params,
-                              float* grad_image, float* ws, hipStream_t st) {
+                              float* grad_image, float* ws, hipStream_t st, const hep_sync* sync) {
   const int B = p.B;
+  GDSync sy{};
+  if (p.bn_sync) sy = bg_sync(p, ws, sync);
+  const GDSync* const syp = p.bn_sync ? &sy : nullptr;
   float* pg = ws + p.o_pcol[0];
   float* pb = ws + p.o_pcol[1];
   const bool bb = p.bn_batch;       // batch statistics: the tables are the forward's effective ones; every d z is corrected before it is read
@@ -716,7 +729,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     if (b.skip && branch_scale) oa.scale = branch_scale + (int64_t)i * B;
     oa.Z = ws + b.o_z2; oa.bn = bb ? ws + b.o_e2 : bg_pb(p, ws, i, b.p_bn2); oa.dY = ws + p.o_dy[i & 1]; oa.dZ = ws + p.o_dz2; oa.pgamma = pg; oa.pbeta = pb;
     hipLaunchKernelGGL(bg_out_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cout)), dim3(GD_THREADS), 0, st, oa);
-    if (bb) bg_bn_backward(p, ws, b.R_out, b.cout, oa.Z, b.o_e2, ws + p.o_dz2, grad_params + b.p_bn2, st);
+    if (bb) bg_bn_backward(p, ws, b.R_out, b.cout, oa.Z, b.o_e2, ws + p.o_dz2, grad_params + b.p_bn2, st, syp);
     // project conv
     BGGemmArgs md{}; md.A = ws + p.o_dz2; md.Bm = bg_pb(p, ws, i, b.p_w2); md.C = ws + p.o_dxg; md.I = b.R_out; md.J = b.cexp; md.K = b.cout;
     md.lda = b.cout; md.ldb = b.cexp; md.ldc = b.cexp;
@@ -745,7 +758,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
     BGActArgs aa{}; aa.ss = ss; aa.C = b.cexp; aa.R = b.R_out; aa.tile_rows = bg_tile_rows(b.R_out);
     aa.G = ws + p.o_dxg; aa.Z = ws + b.o_z1; aa.bn = bb ? ws + b.o_e1 : bg_pa(p, ws, i, b.p_bn1); aa.gate = ws + b.o_g; aa.dmean = ws + p.o_dm; aa.pgamma = pg; aa.pbeta = pb;
     hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_out) * b.cexp)), dim3(GD_THREADS), 0, st, aa);
-    if (bb) bg_bn_backward(p, ws, b.R_out, b.cexp, aa.Z, b.o_e1, aa.G, grad_params + b.p_bn1, st);
+    if (bb) bg_bn_backward(p, ws, b.R_out, b.cexp, aa.Z, b.o_e1, aa.G, grad_params + b.p_bn1, st, syp);
     // depthwise
     const float* dwin = b.expand ? ws + b.o_a0 : x;
     float* ddw = b.expand ? ws + p.o_da0 : ws + p.o_dx;
@@ -773,7 +786,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
       BGActArgs ea{}; ea.ss = b.s_in * b.s_in; ea.C = b.cexp; ea.R = b.R_in; ea.tile_rows = bg_tile_rows(b.R_in);
       ea.G = ws + p.o_da0; ea.Z = ws + b.o_z0; ea.bn = bb ? ws + b.o_e0 : bg_pa(p, ws, i, b.p_bn0); ea.pgamma = pg; ea.pbeta = pb;
       hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(b.R_in) * b.cexp)), dim3(GD_THREADS), 0, st, ea);
-      if (bb) bg_bn_backward(p, ws, b.R_in, b.cexp, ea.Z, b.o_e0, ea.G, grad_params + b.p_bn0, st);
+      if (bb) bg_bn_backward(p, ws, b.R_in, b.cexp, ea.Z, b.o_e0, ea.G, grad_params + b.p_bn0, st, syp);
       bg_slabs(b.R_in, &sr, &ns);
       BGGemmArgs ew{}; ew.A = ws + p.o_da0; ew.Bm = x; ew.C = ws + p.o_pw; ew.I = b.cexp; ew.J = b.cin; ew.K = b.R_in; ew.lda = b.cexp; ew.ldb = b.cin;
       ew.slab_rows = sr;
@@ -792,7 +805,7 @@ void launch_backbone_backward(const BGPlan& p, const float* const grad_taps[3], 
   BGActArgs sa{}; sa.ss = p.s0 * p.s0; sa.C = p.stem; sa.R = p.R0; sa.tile_rows = bg_tile_rows(p.R0);
   sa.G = ws + p.o_dx; sa.Z = ws + p.o_zs; sa.bn = bb ? ws + p.o_es : ps + (p.p_bn_stem - p.p_stem); sa.pgamma = pg; sa.pbeta = pb;
   hipLaunchKernelGGL(bg_act_bwd_kernel, dim3(gd_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(GD_THREADS), 0, st, sa);
-  if (bb) bg_bn_backward(p, ws, p.R0, p.stem, sa.Z, p.o_es, sa.G, grad_params + p.p_bn_stem, st);
+  if (bb) bg_bn_backward(p, ws, p.R0, p.stem, sa.Z, p.o_es, sa.G, grad_params + p.p_bn_stem, st, syp);
   hipLaunchKernelGGL(bg_stem_wgrad_kernel, dim3(gd_blocks((int64_t)bg_ntiles(p.R0) * p.stem)), dim3(GD_THREADS), 0, st, B, p.size, p.stem, p.R0,
                      bg_tile_rows(p.R0), (const float*)(ws + p.o_dx), (const float*)(ws + p.o_img), ws + p.o_pdw);
   GDReduceArgs<BG_RED_JOBS> rd{};

@@ -292,13 +292,13 @@ __global__ __launch_bounds__(GD_THREADS) void hg_reduce_kernel(HGReduceArgs a) {
 
 // ------------------------------------------------------------------------------------------------------------------
 // host side
-int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode) {
+int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const char** why, int bn_mode, int sync) {
   if (phi < 0 || phi > 7) { *why = "heads: phi must be in 0..7 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
   if (num_classes < 1 || num_classes > 63) { *why = "heads: num_classes must be in 1..63"; return HEP_ERR_UNSUPPORTED; }
   HGGeom& g = p->g;
   g.W = kFpnWidth[phi]; g.D = kHeadDepth[phi];
   p->num_classes = num_classes;
-  p->bn_batch = bn_mode == HEP_BN_BATCH;
+  p->bn_batch = bn_mode == HEP_BN_BATCH; p->bn_sync = p->bn_batch && sync;
   if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "heads: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
   const int W = g.W, D = g.D;
   const int vals[HG_SLOTS] = {4, num_classes, 3, 2, 1, 63};
@@ -328,7 +328,7 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
   g.pixoff[5] = S; g.S = S;
   if ((int64_t)batch * S > (1 << 22)) { *why = "heads: batch * pixels exceeds 4 Mi rows"; return HEP_ERR_UNSUPPORTED; }
   g.R = batch * S;
-  if (p->bn_batch && batch * g.s[4] * g.s[4] < 2) { *why = "heads: batch statistics need at least 2 rows per BatchNorm (batch * top-level pixels)"; return HEP_ERR_UNSUPPORTED; }
+  if (p->bn_batch && !p->bn_sync && batch * g.s[4] * g.s[4] < 2) { *why = "heads: batch statistics need at least 2 rows per BatchNorm (batch * top-level pixels)"; return HEP_ERR_UNSUPPORTED; }
   for (int l = 0; l < 6; l++) g.rowoff[l] = batch * g.pixoff[l];
   for (int l = 0; l < 5; l++) { g.tileoff[l] = tiles; tiles += (batch * g.s[l] * g.s[l] + HG_TILE_ROWS - 1) / HG_TILE_ROWS; }
   g.tileoff[5] = tiles; g.ntiles = tiles;
@@ -349,6 +349,7 @@ int heads_plan(int phi, int num_classes, int size, int batch, HGPlan* p, const c
     p->o_bne = take((int64_t)HG_NETS * 5 * D * 4 * W);
     p->o_bnp = take((int64_t)HG_NETS * tiles * W * 4);
   }
+  p->o_xch = p->bn_sync ? take(2 * gd_sync_doubles(HG_NETS * 5, W)) : 0;
   p->ws_floats = w;
   return 0;
 }
@@ -374,6 +375,7 @@ void heads_tensor_offsets(const HGPlan& p, int64_t* out) {
 // the effective table of (net, layer) at level 0 (batch statistics), laid out as the parameters' bn_list of the net
 static inline float* hg_bn_eff(const HGPlan& p, float* ws, int n, int i) { return ws + p.o_bne + ((int64_t)n * 5 * p.g.D + i) * 4 * p.g.W; }
 // the 25 BatchNorms (net, level) of layer i as jobs of grad_dev.h's batch-statistics kernels; a job's rows are one level's
+static inline GDSync hg_sync(const HGPlan& p, float* ws, const hep_sync* sync) { return GDSync{sync->sum, sync->ctx, reinterpret_cast<double*>(ws + p.o_xch)}; }
 static void hg_bn_jobs(const HGPlan& p, const float* params, float* ws, int i, GDBnArgs<HG_NETS * 5>* a) {
   const HGGeom& g = p.g;
   const int W = g.W, bn_lstride = g.D * 4 * W;
@@ -391,9 +393,11 @@ static void hg_bn_jobs(const HGPlan& p, const float* params, float* ws, int i, G
 }
 
 void launch_heads_forward(const HGPlan& p, const float* params, const float* const feats[5], float* const outs[5], float* ws, hipStream_t st,
-                          float momentum, float* stats_out) {
+                          float momentum, float* stats_out, const hep_sync* sync) {
   const HGGeom& g = p.g;
   const int W = g.W, D = g.D;
+  GDSync sy{};
+  if (p.bn_sync) sy = hg_sync(p, ws, sync);
   const int64_t RW = (int64_t)g.R * W;
   HGPtr5 f{};
   for (int l = 0; l < 5; l++) f.in[l] = feats[l];
@@ -426,7 +430,7 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
           j.io = ws + p.o_x + ((int64_t)i * HG_NETS + n) * RW + (int64_t)g.rowoff[l] * W;
           j.stats = stats_out ? stats_out + (j.bn - params) : nullptr;
         }
-      gd_bn_forward(bj, g.rowoff[1], W, GD_BN_SWISH, st);
+      gd_bn_forward(bj, g.rowoff[1], W, GD_BN_SWISH, st, p.bn_sync ? &sy : nullptr);
     }
   }
   HGDwArgs d{}; d.g = g;
@@ -448,9 +452,11 @@ void launch_heads_forward(const HGPlan& p, const float* params, const float* con
 }
 
 void launch_heads_backward(const HGPlan& p, const float* params, const float* const grad_outs[5], float* grad_params, float* const grad_feats[5],
-                           float* ws, hipStream_t st) {
+                           float* ws, hipStream_t st, const hep_sync* sync) {
   const HGGeom& g = p.g;
   const int W = g.W, D = g.D, T = g.ntiles;
+  GDSync sy{};
+  if (p.bn_sync) sy = hg_sync(p, ws, sync);
   const int64_t RW = (int64_t)g.R * W, TW = (int64_t)T * W;
   const int mt = (g.R + GD_BM - 1) / GD_BM, bn_lstride = D * 4 * W;
   const unsigned col_blocks = gd_blocks(TW);
@@ -468,10 +474,12 @@ void launch_heads_backward(const HGPlan& p, const float* params, const float* co
         GDBnJob& j = bj.j[n * 5 + l];
         j.io = ws + p.o_g2 + (int64_t)n * RW + (int64_t)g.rowoff[l] * W;
         j.dbn = rb.dbn[n] + (int64_t)l * bn_lstride;
+        j.pg = rb.pgamma[n] + (int64_t)g.tileoff[l] * W; j.pb = rb.pbeta[n] + (int64_t)g.tileoff[l] * W;
+        j.pn = g.tileoff[l + 1] - g.tileoff[l]; j.pstride = W;
       }
     }
     hipLaunchKernelGGL(hg_reduce_kernel, dim3((unsigned)(((int64_t)5 * 4 * W + GD_RED_E - 1) / GD_RED_E), HG_NETS, 1), dim3(GD_THREADS), 0, st, rb);
-    gd_bn_dz(bj, g.rowoff[1], W, st);
+    gd_bn_dz(bj, g.rowoff[1], W, st, p.bn_sync ? &sy : nullptr);
   };
   // ---- header stage ----
   {

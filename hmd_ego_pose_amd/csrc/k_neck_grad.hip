@@ -366,12 +366,12 @@ __global__ __launch_bounds__(GD_THREADS) void ng_fusion_kernel(NGFusionArgs a) {
 static inline int64_t ng_node_stride(int W) { return (int64_t)9 * W + (int64_t)W * W + W + 4 * W; }
 static inline int64_t ng_lat_stride(int W, int K) { return (int64_t)W * K + W + 4 * W; }
 
-int neck_plan(int phi, int, int size, int batch, NGPlan* p, const char** why, int bn_mode) {
+int neck_plan(int phi, int, int size, int batch, NGPlan* p, const char** why, int bn_mode, int sync) {
   if (phi == 6 || phi == 7) { *why = "neck: phi 6 and 7 fuse by plain sums at width 384 (no fast attention): not supported, phi must be in 0..5"; return HEP_ERR_UNSUPPORTED; }
   if (phi < 0 || phi > 5) { *why = "neck: phi must be in 0..5 (phi 8 needs a P8 level)"; return HEP_ERR_UNSUPPORTED; }
   if (bn_mode != HEP_BN_RUNNING && bn_mode != HEP_BN_BATCH) { *why = "neck: the BatchNorm mode must be HEP_BN_RUNNING or HEP_BN_BATCH"; return HEP_ERR_INVALID; }
   const int W = kNeckWidth[phi];
-  p->bn_batch = bn_mode == HEP_BN_BATCH;
+  p->bn_batch = bn_mode == HEP_BN_BATCH; p->bn_sync = p->bn_batch && sync;
   p->phi = phi; p->W = W; p->cells = kNeckCells[phi];
   for (int t = 0; t < 3; t++) p->tapc[t] = kNeckTaps[phi][t];
   int64_t o = 0;
@@ -387,7 +387,7 @@ int neck_plan(int phi, int, int size, int batch, NGPlan* p, const char** why, in
   if (batch < 1) { *why = "neck: batch must be at least 1"; return HEP_ERR_UNSUPPORTED; }
   if ((int64_t)batch * (size / 8) * (size / 8) > (1 << 22)) { *why = "neck: batch * pixels exceeds 4 Mi rows"; return HEP_ERR_UNSUPPORTED; }
   p->B = batch;
-  if (p->bn_batch && batch * (size / 128) * (size / 128) < 2) { *why = "neck: batch statistics need at least 2 rows per BatchNorm (batch * P7 pixels)"; return HEP_ERR_UNSUPPORTED; }
+  if (p->bn_batch && !p->bn_sync && batch * (size / 128) * (size / 128) < 2) { *why = "neck: batch statistics need at least 2 rows per BatchNorm (batch * P7 pixels)"; return HEP_ERR_UNSUPPORTED; }
   for (int l = 0; l < 5; l++) {
     p->s[l] = size / (8 << l); p->R[l] = batch * p->s[l] * p->s[l];
     p->ntiles[l] = (p->R[l] + NG_TILE_ROWS - 1) / NG_TILE_ROWS;
@@ -422,6 +422,7 @@ int neck_plan(int phi, int, int size, int batch, NGPlan* p, const char** why, in
     p->o_bne = take((int64_t)(NG_LATERALS + p->cells * NG_NODES) * 4 * W);
     p->o_bnp = take((int64_t)p->ntiles[0] * W * 4);
   }
+  p->o_xch = p->bn_sync ? take(2 * gd_sync_doubles(1, W)) : 0;
   p->ws_floats = w;
   return 0;
 }
@@ -534,25 +535,29 @@ GDBnArgs<1> ng_bn_job(const NGPlan& p, float* ws, int k, int level, const float*
 }
 // what follows a map's gather in the backward: its gamma / beta reduce first, then d z (ws + o_dz) corrected in place - before
 // any product reads it; the stage's own reduce then has the weight jobs only
-void ng_bn_backward(const NGPlan& p, float* ws, int k, int level, const float* z, float* dbias, float* dbn, hipStream_t st) {
+inline GDSync ng_sync(const NGPlan& p, float* ws, const hep_sync* sync) { return GDSync{sync->sum, sync->ctx, reinterpret_cast<double*>(ws + p.o_xch)}; }
+void ng_bn_backward(const NGPlan& p, float* ws, int k, int level, const float* z, float* dbias, float* dbn, hipStream_t st, const GDSync* sy) {
   GDReduceArgs<NG_RED_JOBS> rd{};
   ng_bn_jobs(p, ws, level, dbias, dbn, &rd, 2);
   hipLaunchKernelGGL(gd_reduce_kernel<NG_RED_JOBS>, dim3((unsigned)((2 * p.W + GD_RED_E - 1) / GD_RED_E), NG_RED_JOBS), dim3(GD_THREADS), 0, st, rd);
   GDBnArgs<1> a = ng_bn_job(p, ws, k, level, z, nullptr);
   a.j[0].io = ws + p.o_dz; a.j[0].dbn = dbn;
-  gd_bn_dz(a, p.R[level], p.W, st);
+  a.j[0].pg = ws + p.o_pb[0]; a.j[0].pb = ws + p.o_pb[1]; a.j[0].pn = p.ntiles[level]; a.j[0].pstride = p.W;
+  gd_bn_dz(a, p.R[level], p.W, st, sy);
 }
 }  // namespace
 
 void launch_neck_forward(const NGPlan& p, const float* params, const float* const taps[3], float* const feats[5], float* ws, hipStream_t st,
-                         float momentum, float* stats_out) {
+                         float momentum, float* stats_out, const hep_sync* sync) {
   const int W = p.W, B = p.B;
+  GDSync sy{};
+  if (p.bn_sync) sy = ng_sync(p, ws, sync);
   // batch statistics: z (what the GEMM left) -> statistics -> the effective table and the running-statistics update -> y
   auto bn_forward = [&](int k, int level, const NGGemmArgs& m, int64_t table_at) {
     GDBnArgs<1> a = ng_bn_job(p, ws, k, level, m.C, m.bn);
     a.momentum = momentum;
     a.j[0].io = m.C2; a.j[0].stats = stats_out ? stats_out + table_at : nullptr;
-    gd_bn_forward(a, p.R[level], W, GD_BN_PLAIN, st);
+    gd_bn_forward(a, p.R[level], W, GD_BN_PLAIN, st, p.bn_sync ? &sy : nullptr);
   };
   NGPackArgs pk{}; pk.cells = p.cells;
   for (int r = 0; r < p.cells; r++) { pk.src[r] = p.p_cell[r]; pk.dst[r] = p.o_pp[r]; }
@@ -594,8 +599,12 @@ void launch_neck_forward(const NGPlan& p, const float* params, const float* cons
   }
 }
 
-void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t st) {
+void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], float* grad_params, float* const grad_taps[3], float* ws, hipStream_t st,
+                          const hep_sync* sync) {
   const int W = p.W, B = p.B, ntn = (W + GD_BN - 1) / GD_BN;
+  GDSync sy{};
+  if (p.bn_sync) sy = ng_sync(p, ws, sync);
+  const GDSync* const syp = p.bn_sync ? &sy : nullptr;
   auto gather = [&](NGGatherArgs& ga, int l) {
     ga.B = B; ga.s = p.s[l]; ga.W = W; ga.R = p.R[l];
     ga.pgamma = ws + p.o_pb[0]; ga.pbeta = ws + p.o_pb[1]; ga.pbias = ws + p.o_pb[2];
@@ -617,7 +626,7 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
       const int bk = NG_LATERALS + r * NG_NODES + j;
       ga.Z = ws + p.o_z[r][j]; ga.bn = p.bn_batch ? ng_bn_eff(p, ws, bk) : np + 9 * W + (int64_t)W * W + W; ga.out = ws + p.o_dz;
       gather(ga, l);
-      if (p.bn_batch) ng_bn_backward(p, ws, bk, l, ga.Z, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, st);
+      if (p.bn_batch) ng_bn_backward(p, ws, bk, l, ga.Z, gn + 9 * W + (int64_t)W * W, gn + 9 * W + (int64_t)W * W + W, st, syp);
       NGGemmArgs md{}; md.A = ws + p.o_dz; md.Bm = np + 9 * W; md.C = ws + p.o_du; md.I = R; md.J = W; md.K = W; md.lda = W; md.ldb = W; md.ldc = W; md.ntn = ntn;
       ng_gemm(NG_DATA, md, 1, st);
       NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_u[r][j]; mw.C = ws + p.o_pw; mw.I = W; mw.J = W; mw.K = R; mw.lda = W; mw.ldb = W; mw.ntn = ntn;
@@ -652,7 +661,7 @@ void launch_neck_backward(const NGPlan& p, const float* const grad_feats[5], flo
     else ng_collect_pool(ws + p.o_g6, ng_bytes(ws, p.o_am6), &ga);
     ga.Z = ws + p.o_lz[i]; ga.bn = p.bn_batch ? ng_bn_eff(p, ws, i) : lp + (int64_t)W * K + W; ga.out = ws + p.o_dz;
     gather(ga, t);
-    if (p.bn_batch) ng_bn_backward(p, ws, i, t, ga.Z, gl + (int64_t)W * K, gl + (int64_t)W * K + W, st);
+    if (p.bn_batch) ng_bn_backward(p, ws, i, t, ga.Z, gl + (int64_t)W * K, gl + (int64_t)W * K + W, st, syp);
     NGGemmArgs mw{}; mw.A = ws + p.o_dz; mw.Bm = ws + p.o_tap[t]; mw.C = ws + p.o_pw; mw.I = W; mw.J = K; mw.K = R; mw.lda = W; mw.ldb = K;
     mw.ntn = (K + GD_BN - 1) / GD_BN; mw.slab_rows = p.slab_rows[t];
     ng_gemm(NG_WGRAD, mw, p.nslab[t], st);

@@ -18,7 +18,8 @@ running-statistics function bit for bit, and P7 of one 128-pixel image (a single
 ``w = relu(p) / (sum relu(p) + 1e-4)`` with ``relu'(p) = 0`` for ``p <= 0``; a max-pool window sends its gradient to its first
 maximal element in row-major order of the zero-padded window.  phi 6 and 7 (plain-sum fusion) are refused.  The taps are
 inputs; their gradient is available when they require grad, which is how ``hmd_ego_pose_amd.backbone.TrainableBackbone`` chains
-in front of the neck.  Out of scope: sync-BN across GPUs and bf16 training.
+in front of the neck.  ``batch_norm="sync"`` (with ``process_group=``): batch statistics over the rows of all replicas
+(``_trainable.TrainablePart``).  Out of scope: bf16 training.
 """
 from __future__ import annotations
 
@@ -52,25 +53,32 @@ def flat_keys(compound_coef: int) -> List[Tuple[str, tuple]]:
 
 
 def neck_forward(flat: torch.Tensor, taps: Sequence[torch.Tensor], compound_coef: int, size: int, bn_mode: int = _trainable.BN_RUNNING,
-                 momentum: float = _trainable.BN_MOMENTUM, stats: torch.Tensor = None):
+                 momentum: float = _trainable.BN_MOMENTUM, stats: torch.Tensor = None, sync=None):
     """hep_neck_forward_device_bn on the current stream.  ``flat``: the flat parameter buffer (``flat_keys`` order), ``taps``:
     three contiguous float32 NCHW tensors.  Returns (feats, workspace): the five maps [B, W, s_l, s_l] and the workspace that
     hep_neck_backward_device_bn needs (same ``bn_mode``).  ``stats`` (batch statistics): a buffer like ``flat`` whose
-    running_mean / running_var elements receive the updated statistics.  No host synchronisation."""
+    running_mean / running_var elements receive the updated statistics.  No host synchronisation.  ``sync``: a ``sync.SumHook`` -
+    hep_neck_forward_device_sync instead (batch statistics over all replicas; ``bn_mode`` is not read)."""
     _check_phi(compound_coef)
     dev, B, W = flat.device, int(taps[0].shape[0]), get_arch(compound_coef).fpn_w
     l = _capi.lib()
-    nbytes = _capi.check(l.hep_neck_workspace_bytes_bn(compound_coef, size, B, bn_mode))
+    nbytes = _capi.check(l.hep_neck_workspace_bytes_bn(compound_coef, size, B, bn_mode) if sync is None else
+                         l.hep_neck_workspace_bytes_sync(compound_coef, size, B))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     feats = tuple(torch.empty((B, W, s, s), dtype=torch.float32, device=dev) for s in level_sizes(size))
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if sync is not None:
+        sync.register(ws)
+        sync.check(l.hep_neck_forward_device_sync(flat.data_ptr(), _ptrs(taps), compound_coef, size, B, _ptrs(feats), ws.data_ptr(), nbytes,
+                                                  momentum, None if stats is None else stats.data_ptr(), sync.ref(), stream))
+        return feats, ws
     _capi.check(l.hep_neck_forward_device_bn(flat.data_ptr(), _ptrs(taps), compound_coef, size, B, _ptrs(feats), ws.data_ptr(), nbytes,
                                              bn_mode, momentum, None if stats is None else stats.data_ptr(), stream))
     return feats, ws
 
 
 def neck_backward(flat: torch.Tensor, grad_feats: Sequence[torch.Tensor], ws: torch.Tensor, compound_coef: int, size: int, tap_shapes=None,
-                  bn_mode: int = _trainable.BN_RUNNING):
+                  bn_mode: int = _trainable.BN_RUNNING, sync=None):
     """hep_neck_backward_device_bn on the current stream, after ``neck_forward`` with the same ``flat``, ``ws`` and ``bn_mode``.  Returns
     (grad_flat, grad_taps): the parameter gradients in the layout of ``flat`` (running statistics zero) and the three tap
     gradients (None when ``tap_shapes`` is None: the ABI then gets NULL and skips them)."""
@@ -78,6 +86,11 @@ def neck_backward(flat: torch.Tensor, grad_feats: Sequence[torch.Tensor], ws: to
     g_flat = torch.empty_like(flat)
     g_taps = None if tap_shapes is None else tuple(torch.empty(tuple(s), dtype=torch.float32, device=dev) for s in tap_shapes)
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if sync is not None:               # (the forward's hook: grad_flat is this replica's contribution, to be SUMMED over the replicas)
+        sync.register(ws)
+        sync.check(_capi.lib().hep_neck_backward_device_sync(flat.data_ptr(), _ptrs(grad_feats), compound_coef, size, B, g_flat.data_ptr(),
+                                                             _ptrs(g_taps), ws.data_ptr(), ws.numel(), sync.ref(), stream))
+        return g_flat, g_taps
     _capi.check(_capi.lib().hep_neck_backward_device_bn(flat.data_ptr(), _ptrs(grad_feats), compound_coef, size, B, g_flat.data_ptr(),
                                                         _ptrs(g_taps), ws.data_ptr(), ws.numel(), bn_mode, stream))
     return g_flat, g_taps
@@ -92,21 +105,21 @@ class _Neck(torch.autograd.Function):
     """The two ABI calls as one differentiable function of (flat parameters, three taps)."""
 
     @staticmethod
-    def forward(ctx, flat, phi, size, bn_mode, stats, *taps):
-        feats, ws = neck_forward(flat, taps, phi, size, bn_mode, stats=stats)
+    def forward(ctx, flat, phi, size, bn_mode, stats, sync, *taps):
+        feats, ws = neck_forward(flat, taps, phi, size, bn_mode, stats=stats, sync=sync)
         ctx.save_for_backward(flat, ws)
-        ctx.cfg = (phi, size, [tuple(t.shape) for t in taps], [tuple(f.shape) for f in feats], bn_mode)
+        ctx.cfg = (phi, size, [tuple(t.shape) for t in taps], [tuple(f.shape) for f in feats], bn_mode, sync)
         return feats
 
     @staticmethod
     @once_differentiable
     def backward(ctx, *grad_feats):
         flat, ws = ctx.saved_tensors
-        phi, size, tap_shapes, feat_shapes, bn_mode = ctx.cfg
+        phi, size, tap_shapes, feat_shapes, bn_mode, sync = ctx.cfg
         gs = _trainable.cotangents(grad_feats, feat_shapes, flat.device)
-        want_taps = any(ctx.needs_input_grad[5:])
-        g_flat, g_taps = neck_backward(flat, gs, ws, phi, size, tap_shapes if want_taps else None, bn_mode)
-        return (g_flat if ctx.needs_input_grad[0] else None, None, None, None, None, *(g_taps if want_taps else (None,) * 3))
+        want_taps = any(ctx.needs_input_grad[6:])
+        g_flat, g_taps = neck_backward(flat, gs, ws, phi, size, tap_shapes if want_taps else None, bn_mode, sync)
+        return (g_flat if ctx.needs_input_grad[0] else None, None, None, None, None, None, *(g_taps if want_taps else (None,) * 3))
 
 
 class TrainableNeck(_trainable.TrainablePart):
@@ -120,9 +133,9 @@ class TrainableNeck(_trainable.TrainablePart):
 
     NOUN, spec = "BiFPN", staticmethod(neck_spec)
 
-    def __init__(self, compound_coef: int = 0, batch_norm: str = "running"):
+    def __init__(self, compound_coef: int = 0, batch_norm: str = "running", process_group=None):
         super().__init__()
-        self._set_batch_norm(batch_norm)
+        self._set_batch_norm(batch_norm, process_group)
         self.compound_coef = int(compound_coef)
         _check_phi(self.compound_coef)
         self.arch = get_arch(self.compound_coef)
@@ -152,13 +165,13 @@ class TrainableNeck(_trainable.TrainablePart):
         flat = self.flat_parameters()
         if flat.device != taps[0].device:
             raise ValueError("the neck and the taps live on different devices: move the module with .to(device)")
-        bn_mode, stats = self._bn_mode(), None
+        bn_mode, stats, sync = self._bn_mode(), None, self._sync_hook()
         if bn_mode == _trainable.BN_BATCH:
             rows = int(taps[0].shape[0]) * (size // 128) ** 2
-            if rows < 2:
+            if rows < 2 and (sync is None or sync.world == 1):      # (a replica cannot know the global rows: the caller's to check)
                 raise ValueError(f"batch statistics need more than 1 value per channel: P7 has {rows} row (batch {int(taps[0].shape[0])} at size {size})")
             stats = torch.empty_like(flat)
-        feats = _Neck.apply(flat, self.compound_coef, size, bn_mode, stats, *(t.contiguous() for t in taps))
+        feats = _Neck.apply(flat, self.compound_coef, size, bn_mode, stats, sync, *(t.contiguous() for t in taps))
         if stats is not None:
             self._store_statistics(stats)
         return feats

@@ -16,6 +16,13 @@ heads / neck / backbone backward -> hep_optim_grad_norm_device -> hep_optim_upda
 ``drop_connect_rate`` > 0 the table of the step is drawn with torch, ``backbone.draw_branch_scale``: one small tensor per block from the
 caching allocator - the default rate 0.0 draws nothing).  The three
 ``Trainable*`` modules are not touched by any of this: they stay the yardstick of the new path (tests/test_gpu_trainer.py).
+
+Data-parallel: ``Trainer(..., batch_norm="sync", process_group=pg)`` on every rank of a ``torch.distributed`` group, each rank
+stepping on its shard (``dist.shard_range``) of the global batch.  The forwards and backwards are the hep_*_device_sync calls:
+every BatchNorm sees the rows of all ranks (``sync.SumHook``), the upstream gradient is ``weight_k * scale_k / global_batch``,
+and each rank's ``grad`` is its own contribution, so ONE ``all_reduce`` of the flat buffer gives every rank the gradient of the
+global-batch function - the same bits on all ranks, hence the same norm, clipping, skip decision and update.  The step equals
+the single-process step on the concatenated batch up to summation order.
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _capi, _trainable, backbone as _bb, heads as _hd, neck as _nk, training
+from . import _capi, _trainable, backbone as _bb, heads as _hd, neck as _nk, sync as _sync, training
 from .arch import NUM_ANCHORS, get_arch, level_sizes
 
 PARTS = ("backbone", "neck", "heads")
@@ -109,15 +116,33 @@ class Trainer:
     (train.py:100); "sgd": ``SGD(momentum=0.9, nesterov=True)`` (train.py:103).  ``max_grad_norm``: ``clip_grad_norm_`` over every
     trainable element (train.py:210).  A step whose gradient norm is not finite changes nothing and counts in ``steps_skipped``.
     ``batch_norm`` as the three modules define it; ``freeze_backbone`` runs the trunk with its running statistics, skips its
-    backward and leaves every one of its elements bit-unchanged.  phi 0..5 (the neck's range).  ROCm device only."""
+    backward and leaves every one of its elements bit-unchanged.  phi 0..5 (the neck's range).  ROCm device only.
+
+    ``process_group`` (a ``torch.distributed`` group; every rank builds the same trainer): data-parallel steps.  With
+    ``batch_norm="sync"`` the step is the single-process step on the concatenated batch; with "running" it is plain gradient
+    averaging; "batch" is refused (the running statistics of the ranks would drift apart).  The constructor and
+    ``load_state_dict`` broadcast ``params``, ``m``, ``v`` and ``state`` from rank 0.  The drop-connect table stays per-rank local.
+    ``batch_norm="sync"`` always names its replicas: ``process_group=sync.LOCAL`` is this process alone - no group, "batch" bit for
+    bit, ``torch.distributed`` never imported; ``batch_norm="sync"`` without ``process_group`` raises ``ValueError``."""
 
     def __init__(self, state_dict, compound_coef: int = 0, num_classes: int = 1, device=None, optimizer: str = "adam", lr: float = 1e-4,
                  batch_norm: str = "batch", max_grad_norm: Optional[float] = None, drop_connect_rate: float = 0.0,
-                 freeze_backbone: bool = False, loss_weights=LOSS_WEIGHTS, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9):
+                 freeze_backbone: bool = False, loss_weights=LOSS_WEIGHTS, betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9,
+                 process_group=None):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be 'adam' or 'sgd', not {optimizer!r}")
-        if batch_norm not in _trainable.BN_MODES:
-            raise ValueError(f"batch_norm must be 'running' or 'batch', not {batch_norm!r}")
+        if batch_norm not in _trainable.BN_NAMES:
+            raise ValueError(f"batch_norm must be 'running', 'batch' or 'sync', not {batch_norm!r}")
+        if batch_norm == _trainable.BN_SYNC and process_group is None:
+            raise ValueError("batch_norm='sync' takes process_group=: a torch.distributed group, or sync.LOCAL for this process alone "
+                             "(then it is batch_norm='batch' bit for bit)")
+        if isinstance(process_group, str):
+            if process_group != _sync.LOCAL:
+                raise ValueError(f"process_group must be a torch.distributed group, sync.LOCAL or None, not {process_group!r}")
+            process_group = None
+        if process_group is not None and batch_norm == "batch":
+            raise ValueError("process_group with batch_norm='batch': every rank would move its running statistics with its own shard "
+                             "and they would drift apart - use batch_norm='sync' (or 'running' for plain gradient averaging)")
         if len(loss_weights) != 5:
             raise ValueError("loss_weights: five values (classification, regression, rotation, translation, hand)")
         self.compound_coef, self.num_classes = int(compound_coef), int(num_classes)
@@ -154,6 +179,16 @@ class Trainer:
         self._weights = torch.tensor(self.loss_weights, dtype=torch.float32).to(dev)
         self._shapes: Dict[tuple, _Shape] = {}
         self._exported = 0                                             # steps already added to a model's num_batches_tracked
+        self.process_group = process_group
+        self.world, self.rank = _sync.group_world(process_group), _sync.group_rank(process_group)
+        self._hook = _sync.SumHook(process_group) if batch_norm == _trainable.BN_SYNC else None
+        self._broadcast()
+
+    def _broadcast(self):
+        """Rank 0's ``params``, ``m``, ``v`` and ``state`` into every rank's (nothing without a group)."""
+        for t in (self.params, self.m, self.v, self.state):
+            if t is not None:
+                _sync.broadcast(t, self.process_group, 0)
 
     @classmethod
     def from_model(cls, model, **kwargs):
@@ -196,26 +231,35 @@ class Trainer:
 
     # ---- per-shape buffers ---------------------------------------------------------------------------------------------------
     def _bn_modes(self):
-        mode = _trainable.BN_MODES[self.batch_norm]
+        """The BatchNorm mode of backbone, neck, heads ("sync" is HEP_BN_BATCH through the hep_*_device_sync calls)."""
+        mode = _trainable.BN_BATCH if self.batch_norm == _trainable.BN_SYNC else _trainable.BN_MODES[self.batch_norm]
         return (_trainable.BN_RUNNING if self.freeze_backbone else mode), mode, mode
 
-    def _shape(self, size: int, B: int, hand: bool) -> _Shape:
-        key = (size, B, hand)
+    def _shape(self, size: int, B: int, hand: bool, global_batch: Optional[int] = None) -> _Shape:
+        G = B * self.world if global_batch is None else int(global_batch)
+        if G < B or (self.world == 1 and G != B):
+            raise ValueError(f"global_batch {G} with a local batch of {B} on {self.world} rank(s)")
+        key = (size, B, hand, G)
         c = self._shapes.get(key)
         if c is not None:
             return c
         _bb._check_size(size)
         phi, K, dev, l = self.compound_coef, self.num_classes, self.device, _capi.lib()
         modes = self._bn_modes()
-        if _trainable.BN_BATCH in modes and B * (size // 128) ** 2 < 2:
-            raise ValueError(f"batch statistics need more than 1 value per channel: P7 has {B * (size // 128) ** 2} row (batch {B} at size {size})")
+        if _trainable.BN_BATCH in modes and G * (size // 128) ** 2 < 2:
+            raise ValueError(f"batch statistics need more than 1 value per channel: P7 has {G * (size // 128) ** 2} row (batch {G} at size {size})")
         c = _Shape()
+        c.G = G
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         ws = lambda n: torch.empty((_capi.check(n),), dtype=torch.uint8, device=dev)
         W, N = self.arch.fpn_w, NUM_ANCHORS * sum(s * s for s in level_sizes(size))
         c.N = N
-        c.ws = (ws(l.hep_backbone_workspace_bytes_bn(phi, size, B, modes[0])), ws(l.hep_neck_workspace_bytes_bn(phi, size, B, modes[1])),
-                ws(l.hep_heads_workspace_bytes_bn(phi, K, size, B, modes[2])))
+        if self._hook is None:
+            c.ws = (ws(l.hep_backbone_workspace_bytes_bn(phi, size, B, modes[0])), ws(l.hep_neck_workspace_bytes_bn(phi, size, B, modes[1])),
+                    ws(l.hep_heads_workspace_bytes_bn(phi, K, size, B, modes[2])))
+        else:                                                          # (a frozen backbone runs its running statistics: the _bn call)
+            c.ws = (ws(l.hep_backbone_workspace_bytes_bn(phi, size, B, modes[0]) if self.freeze_backbone else l.hep_backbone_workspace_bytes_sync(phi, size, B)),
+                    ws(l.hep_neck_workspace_bytes_sync(phi, size, B)), ws(l.hep_heads_workspace_bytes_sync(phi, K, size, B)))
         tap_shapes = [(B, ch, size // (8 << t), size // (8 << t)) for t, ch in enumerate(self.arch.tap_channels)]
         feat_shapes = [(B, W, s, s) for s in level_sizes(size)]
         out_k = [K if k is None else k for k in HEAD_K]
@@ -227,7 +271,7 @@ class Trainer:
             c.g_outs[4].zero_()                                        # no hand targets: the hand cotangent is this persistent zero
         c.transformation, c.g_transformation = f(B, N, NUM_ROTATION + 3), f(B, N, NUM_ROTATION + 3)
         c.per, c.out5, c.result = f(B, 5), f(5), f(6)
-        scale = torch.tensor([w * s / B for w, s in zip(self.loss_weights, training._MEAN_SCALE)], dtype=torch.float32)
+        scale = torch.tensor([w * s / G for w, s in zip(self.loss_weights, training._MEAN_SCALE)], dtype=torch.float32)
         c.upstream = scale[None].repeat(B, 1).contiguous().to(dev)
         c.loss_ws = torch.empty((B * (N + 4),), dtype=torch.int32, device=dev)
         c.anchors = training.translation_anchors(size).to(dev).contiguous()
@@ -237,7 +281,7 @@ class Trainer:
         return c
 
     # ---- the step --------------------------------------------------------------------------------------------------------------
-    def _check(self, image, camera, gt_classification, gt_regression, gt_transformation, gt_hand, model_3d_points):
+    def _check(self, image, camera, gt_classification, gt_regression, gt_transformation, gt_hand, model_3d_points, global_batch=None):
         def chk(t, name, shape):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != self.params.device:
                 raise ValueError(f"{name} must be a float32 tensor on {self.params.device}")
@@ -248,7 +292,7 @@ class Trainer:
             raise ValueError("image must be a tensor [B, 3, S, S]")
         B, size = int(image.shape[0]), int(image.shape[-1])
         image = chk(image, "image", None)
-        c = self._shape(size, B, gt_hand is not None)
+        c = self._shape(size, B, gt_hand is not None, global_batch)
         N, K = c.N, self.num_classes
         t = (image, chk(camera, "camera", (B, 6)), chk(gt_classification, "gt_classification", (B, N, K + 1)),
              chk(gt_regression, "gt_regression", (B, N, 5)), chk(gt_transformation, "gt_transformation", (B, N, NUM_ROTATION + 6)),
@@ -258,31 +302,48 @@ class Trainer:
             raise ValueError("model_3d_points must be [classes, P, 3] with P in 1..2048")
         return c, B, size, t
 
-    def step(self, image, camera, gt_classification, gt_regression, gt_transformation, gt_hand, model_3d_points):
+    def step(self, image, camera, gt_classification, gt_regression, gt_transformation, gt_hand, model_3d_points, global_batch: Optional[int] = None):
         """One training step on the current stream.  ``image`` [B, 3, S, S], ``camera`` [B, 6], the targets as
         ``training.anchor_targets`` returns them (``gt_hand`` [B, N, 64] or None), ``model_3d_points`` [classes, P, 3]: float32
         tensors on the trainer's device.  Raises ``ValueError`` before any pointer reaches the ABI.  Returns a float32 [6] device
         tensor: the five weighted losses and their sum, in the order of train.py:70.  It is the trainer's own buffer of this
-        shape: the next step overwrites it (``.clone()`` what has to last)."""
+        shape: the next step overwrites it (``.clone()`` what has to last).  With a process group: ``image`` and the targets are
+        this rank's shard, ``global_batch`` the images of all ranks in this step (default ``B * world``: even shards); the losses
+        returned are those of the global batch, the same on every rank."""
         c, B, size, (image, camera, gt_cls, gt_reg, gt_tr, gt_hand, pts) = self._check(image, camera, gt_classification, gt_regression,
-                                                                                         gt_transformation, gt_hand, model_3d_points)
+                                                                                         gt_transformation, gt_hand, model_3d_points, global_batch)
         l, check, ptr = _capi.lib(), _capi.check, _capi.ptr
         phi, K, N, R = self.compound_coef, self.num_classes, c.N, NUM_ROTATION
         stream = torch.cuda.current_stream(self.device).cuda_stream
         m_bb, m_nk, m_hd = self._bn_modes()
-        batch_stats = self.batch_norm == "batch"
+        batch_stats = self.batch_norm in ("batch", _trainable.BN_SYNC)
         mom = _trainable.BN_MOMENTUM
         par = {n: self.part(self.params, n).data_ptr() for n in PARTS}
         grd = {n: self.part(self.grad, n).data_ptr() for n in PARTS}
         sts = {n: (self.part(self.stats, n).data_ptr() if batch_stats and not (n == "backbone" and self.freeze_backbone) else None) for n in PARTS}
         scale = None if self.freeze_backbone else _bb.draw_branch_scale(phi, self.drop_connect_rate, B, self.device)
+        hook = self._hook
         # 1. forward
-        check(l.hep_backbone_forward_device_bn(par["backbone"], image.data_ptr(), ptr(scale), phi, size, B, c.p_taps, c.ws[0].data_ptr(),
-                                               c.ws[0].numel(), m_bb, mom, sts["backbone"], stream))
-        check(l.hep_neck_forward_device_bn(par["neck"], c.p_taps, phi, size, B, c.p_feats, c.ws[1].data_ptr(), c.ws[1].numel(), m_nk, mom,
-                                           sts["neck"], stream))
-        check(l.hep_heads_forward_device_bn(par["heads"], c.p_feats, phi, K, size, B, c.p_outs, c.ws[2].data_ptr(), c.ws[2].numel(), m_hd, mom,
-                                            sts["heads"], stream))
+        if hook is None:
+            check(l.hep_backbone_forward_device_bn(par["backbone"], image.data_ptr(), ptr(scale), phi, size, B, c.p_taps, c.ws[0].data_ptr(),
+                                                   c.ws[0].numel(), m_bb, mom, sts["backbone"], stream))
+            check(l.hep_neck_forward_device_bn(par["neck"], c.p_taps, phi, size, B, c.p_feats, c.ws[1].data_ptr(), c.ws[1].numel(), m_nk, mom,
+                                               sts["neck"], stream))
+            check(l.hep_heads_forward_device_bn(par["heads"], c.p_feats, phi, K, size, B, c.p_outs, c.ws[2].data_ptr(), c.ws[2].numel(), m_hd, mom,
+                                                sts["heads"], stream))
+        else:
+            hook.register(*c.ws)
+            check, ref = hook.check, hook.ref()
+            if self.freeze_backbone:
+                check(l.hep_backbone_forward_device_bn(par["backbone"], image.data_ptr(), ptr(scale), phi, size, B, c.p_taps, c.ws[0].data_ptr(),
+                                                       c.ws[0].numel(), m_bb, mom, sts["backbone"], stream))
+            else:
+                check(l.hep_backbone_forward_device_sync(par["backbone"], image.data_ptr(), ptr(scale), phi, size, B, c.p_taps, c.ws[0].data_ptr(),
+                                                         c.ws[0].numel(), mom, sts["backbone"], ref, stream))
+            check(l.hep_neck_forward_device_sync(par["neck"], c.p_taps, phi, size, B, c.p_feats, c.ws[1].data_ptr(), c.ws[1].numel(), mom,
+                                                 sts["neck"], ref, stream))
+            check(l.hep_heads_forward_device_sync(par["heads"], c.p_feats, phi, K, size, B, c.p_outs, c.ws[2].data_ptr(), c.ws[2].numel(), mom,
+                                                  sts["heads"], ref, stream))
         reg, cls, rot, raw, hand = c.outs
         # 2. - 5. pack, losses, their backward, unpack
         check(l.hep_transformation_pack_device(rot.data_ptr(), raw.data_ptr(), camera.data_ptr(), c.anchors.data_ptr(), B, N, R,
@@ -297,13 +358,25 @@ class Trainer:
         check(l.hep_transformation_unpack_grad_device(c.g_transformation.data_ptr(), raw.data_ptr(), camera.data_ptr(), c.anchors.data_ptr(),
                                                       B, N, R, c.g_outs[2].data_ptr(), c.g_outs[3].data_ptr(), stream))
         # 6. backward of the parts
-        check(l.hep_heads_backward_device_bn(par["heads"], c.p_g_outs, phi, K, size, B, grd["heads"], c.p_g_feats, c.ws[2].data_ptr(),
-                                             c.ws[2].numel(), m_hd, stream))
-        check(l.hep_neck_backward_device_bn(par["neck"], c.p_g_feats, phi, size, B, grd["neck"], None if self.freeze_backbone else c.p_g_taps,
-                                            c.ws[1].data_ptr(), c.ws[1].numel(), m_nk, stream))
-        if not self.freeze_backbone:
-            check(l.hep_backbone_backward_device_bn(par["backbone"], c.p_g_taps, ptr(scale), phi, size, B, grd["backbone"], None,
-                                                    c.ws[0].data_ptr(), c.ws[0].numel(), m_bb, stream))
+        if hook is None:
+            check(l.hep_heads_backward_device_bn(par["heads"], c.p_g_outs, phi, K, size, B, grd["heads"], c.p_g_feats, c.ws[2].data_ptr(),
+                                                 c.ws[2].numel(), m_hd, stream))
+            check(l.hep_neck_backward_device_bn(par["neck"], c.p_g_feats, phi, size, B, grd["neck"], None if self.freeze_backbone else c.p_g_taps,
+                                                c.ws[1].data_ptr(), c.ws[1].numel(), m_nk, stream))
+            if not self.freeze_backbone:
+                check(l.hep_backbone_backward_device_bn(par["backbone"], c.p_g_taps, ptr(scale), phi, size, B, grd["backbone"], None,
+                                                        c.ws[0].data_ptr(), c.ws[0].numel(), m_bb, stream))
+        else:
+            check(l.hep_heads_backward_device_sync(par["heads"], c.p_g_outs, phi, K, size, B, grd["heads"], c.p_g_feats, c.ws[2].data_ptr(),
+                                                   c.ws[2].numel(), ref, stream))
+            check(l.hep_neck_backward_device_sync(par["neck"], c.p_g_feats, phi, size, B, grd["neck"], None if self.freeze_backbone else c.p_g_taps,
+                                                  c.ws[1].data_ptr(), c.ws[1].numel(), ref, stream))
+            if not self.freeze_backbone:
+                check(l.hep_backbone_backward_device_sync(par["backbone"], c.p_g_taps, ptr(scale), phi, size, B, grd["backbone"], None,
+                                                          c.ws[0].data_ptr(), c.ws[0].numel(), ref, stream))
+            check = _capi.check
+        # every rank's grad is its own contribution to the gradient of the global-batch function: one collective over the flat buffer
+        _sync.all_reduce_sum(self.grad, self.process_group)
         # 7. - 8. norm and update
         opt = OPTIMIZERS[self.optimizer]
         check(l.hep_optim_grad_norm_device(self.grad.data_ptr(), self.kind.data_ptr(), self.total, opt, self.beta1, self.beta2, self.max_grad_norm,
@@ -312,6 +385,9 @@ class Trainer:
                                         self.stats.data_ptr() if batch_stats else None, self.kind.data_ptr(), self.total, opt, self.lr,
                                         self.beta1, self.beta2, self.eps, self.state.data_ptr(), stream))
         torch.mul(c.out5, self._weights, out=c.result[:5])
+        if self.world > 1:                                             # this rank's five batch means -> the global batch's, one small collective
+            c.result[:5].mul_(B / c.G)
+            _sync.all_reduce_sum(c.result[:5], self.process_group)
         torch.sum(c.result[:5], dim=0, keepdim=True, out=c.result[5:])
         return c.result
 
@@ -364,4 +440,5 @@ class Trainer:
             self.params.copy_(sd["params"]); self.m.copy_(sd["m"]); self.state.copy_(sd["state"])
             if self.v is not None:
                 self.v.copy_(sd["v"])
+        self._broadcast()
         self._exported = self.steps_taken                              # the saved steps are taken to be in the model's counters already

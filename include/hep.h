@@ -544,6 +544,49 @@ int hep_backbone_backward_device_bn(const float* params, const float* const grad
 int hep_backbone_stage_count(int phi);
 int hep_backbone_stage_info(int phi, int size, int batch, int i, const char** name, int64_t dims[4], int64_t* offset_bytes);
 
+/* Synchronised BatchNorm: HEP_BN_BATCH of the three parts with the row set of every BatchNorm being the UNION over all
+ * replicas of a data-parallel step (the reference's utils/sync_batchnorm).  The function, its backward, stats_out and every
+ * argument rule are those of the *_bn group with HEP_BN_BATCH; there is no bn_mode argument.  What crosses the replicas are
+ * double sums, through a hook of the caller's:
+ *   forward   per BatchNorm sum z [C], sum z^2 [C] and this replica's row count R; mean = S / N, var = max((Q - mean S) / N, 0)
+ *             in double from the global sums, the running-statistics update with the unbiased N / (N - 1) of the GLOBAL N:
+ *             every replica writes the same values to stats_out.
+ *   backward  per BatchNorm this replica's d gamma [C], d beta [C] (before their rounding to float) and R; the d z correction
+ *             uses the global sums, rounded once, and the global N.  grad_params holds this replica's LOCAL contribution in
+ *             EVERY element (d gamma and d beta included): the plain sum of grad_params over the replicas is the gradient of
+ *             the global-batch function.
+ * All sums of one launch (25 BatchNorms in the heads, 1 in the neck and the backbone) lie in ONE contiguous, 16-byte aligned
+ * block of doubles inside the workspace; sum is called once per block:
+ *   data      device memory inside the workspace handed to the call; count elements, double (is_double != 0; float otherwise)
+ *   contract  when the work that sum enqueued on stream has run, every element holds the sum over all replicas; it may
+ *             enqueue and return.  All replicas make the same sequence of calls with the same counts; the sequence depends on
+ *             phi, num_classes and size, never on batch: shards may be uneven (the row counts travel in the block).
+ *   failure   a non-zero return: the entry point launches nothing further and returns HEP_ERR_DEVICE, the error text names the hook.
+ * sync == NULL or sync->sum == NULL: HEP_ERR_INVALID before any HIP call.  A replica cannot know the global row count, so any
+ * local batch >= 1 is accepted here; "at least 2 rows per BatchNorm" is the caller's to check on the global batch.
+ * An identity hook (one replica) gives HEP_BN_BATCH bit for bit.  The *_workspace_bytes_sync size is >= the batch-mode size. */
+typedef int (*hep_sum_fn)(void* ctx, void* data, int64_t count, int is_double, void* stream);
+typedef struct hep_sync { hep_sum_fn sum; void* ctx; } hep_sync;
+int64_t hep_heads_workspace_bytes_sync(int phi, int num_classes, int size, int batch);
+int hep_heads_forward_device_sync(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch,
+                                  float* const outs[5], void* workspace, size_t workspace_bytes, float momentum, float* stats_out,
+                                  const hep_sync* sync, void* stream);
+int hep_heads_backward_device_sync(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch,
+                                   float* grad_params, float* const grad_feats[5], void* workspace, size_t workspace_bytes,
+                                   const hep_sync* sync, void* stream);
+int64_t hep_neck_workspace_bytes_sync(int phi, int size, int batch);
+int hep_neck_forward_device_sync(const float* params, const float* const taps[3], int phi, int size, int batch, float* const feats[5],
+                                 void* workspace, size_t workspace_bytes, float momentum, float* stats_out, const hep_sync* sync, void* stream);
+int hep_neck_backward_device_sync(const float* params, const float* const grad_feats[5], int phi, int size, int batch, float* grad_params,
+                                  float* const grad_taps[3], void* workspace, size_t workspace_bytes, const hep_sync* sync, void* stream);
+int64_t hep_backbone_workspace_bytes_sync(int phi, int size, int batch);
+int hep_backbone_forward_device_sync(const float* params, const float* image, const float* branch_scale, int phi, int size, int batch,
+                                     float* const taps[3], void* workspace, size_t workspace_bytes, float momentum, float* stats_out,
+                                     const hep_sync* sync, void* stream);
+int hep_backbone_backward_device_sync(const float* params, const float* const grad_taps[3], const float* branch_scale, int phi, int size,
+                                      int batch, float* grad_params, float* grad_image, void* workspace, size_t workspace_bytes,
+                                      const hep_sync* sync, void* stream);
+
 /* preprocess_image (reference generators/colibri_common.py:622-656): device uint8 RGB [batch, height, width, 3] ->
  * device float32 [batch, size, size, 3]: resize by scale = size / max(height, width) (8-bit bilinear, OpenCV
  * INTER_LINEAR fixed-point convention - restated, parity unpinned: cv2 is absent here; skipped when scale == 1, every
