@@ -1005,7 +1005,9 @@ static std::string kernel_symbol(const Session& s, const Op& o) {
     case OP_DW: snprintf(tmp, sizeof tmp, "dw_kernel<%s, %d, %d, %d>", t, o.dw.k, o.dw.s, o.dw.TW); break;
     case OP_POOL: snprintf(tmp, sizeof tmp, "pool_kernel<%s>", t); break;
     case OP_PWG: snprintf(tmp, sizeof tmp, "pw_group_kernel<%s>", t); break;
-    case OP_CHAIN: snprintf(tmp, sizeof tmp, "chain_kernel<%s, %d>", o.chain.bf16 ? "true" : "false", o.chain.stream_w); break;
+    case OP_CHAIN: if (const int id = chain_shape_id(o.chain)) snprintf(tmp, sizeof tmp, "chain_shape_kernel<true, %d>", id);      // (the row of chain_shape(), k_chain_impl.h)
+                   else snprintf(tmp, sizeof tmp, "chain_kernel<%s, %d>", o.chain.bf16 ? "true" : "false", o.chain.stream_w);
+                   break;
     case OP_SE: snprintf(tmp, sizeof tmp, "se_finish_kernel<%s>", t); break;
     case OP_MBF: { const int mp = o.mbf.has_expand && o.mbf.npass > 1 ? (o.mbf.mp_resident ? 2 : 1) : 0;      // (1 / 2 = multi-pass expand)
                    if (const int id = mbf_shape_id(o.mbf)) snprintf(tmp, sizeof tmp, "mbf_shape_kernel<%s, %d, %d, %d, %d, %d>", t, o.mbf.k, o.mbf.s, o.mbf.ts, mp, id);   // (last argument: the row of MBF_SHAPES)
@@ -1022,7 +1024,8 @@ static std::string kernel_symbol(const Session& s, const Op& o) {
              else {
                const int mode = o.sep.chain ? 2 : (o.sep.nseg == 1 ? 0 : 1);
                const bool wl = o.sep.bf16 && o.sep.off_wpw && mode != 1;         // (launch_sep: staged pointwise weights)
-               if (mode == 0 && sep_w8(o.sep)) snprintf(tmp, sizeof tmp, "sep_kernel<%s, 0, false, true>", t);
+               if (const int id = mode == 0 ? sep_shape_id(o.sep) : 0) snprintf(tmp, sizeof tmp, "sep_shape_kernel<true, %d>", id);      // (the row of SEP_SHAPES, k_sep_impl.h)
+               else if (mode == 0 && sep_w8(o.sep)) snprintf(tmp, sizeof tmp, "sep_kernel<%s, 0, false, true>", t);
                else snprintf(tmp, sizeof tmp, wl ? "sep_kernel<%s, %d, true, false>" : "sep_kernel<%s, %d, false, false>", t, mode);
              }
              break;

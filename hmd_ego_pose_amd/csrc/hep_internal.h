@@ -258,6 +258,7 @@ struct SepArgs {
   int chain;                                 // segments are a dependency chain run by one workgroup per image
   int direct;                                // k_tower.hip (wave-per-patch, no LDS staging): 1 = map layer, 2 = headers
   int coop;                                  // ... in its cooperative form (tower_coop_kernel: one 10x10 halo per workgroup, weights in registers)
+  int generic;                               // plan: 1 = the generic kernel although a shape-specialised one exists (HEP_NECK_GENERIC, A/B and parity runs)
   size_t off_atile, off_wdw, off_bias, lds_bytes;   // LDS layout (k_sep.hip: sep_lds_layout)
   size_t off_wpw;                            // 0, or where the node's pointwise weights [C][C + pad] are staged (bf16 nodes wider than 64 that fit)
 };
@@ -274,16 +275,19 @@ struct ChainNode {
 struct ChainExt {                                        // an input map produced by an earlier launch
   const void* src; void* store;                          // store: the pooled map is also written here (p6_in of cell 0), else NULL
   int sh, sw, kind, h, w, pool_pad, off;                 // kind SRC_DOWN: pooled to h x w while it is loaded; else copied (h x w == sh x sw)
+  int has_store;                                         // plan: 1 = `store` will be bound (known before the session has addresses: chain_shape_id)
 };
 struct ChainArgs {
   const ChainNode* nodes; const void* wblob;             // device: node table, the nodes' weights in LDS layout
   ChainExt ext[CH_MAX_EXT];
   int nnodes, nconv, next, B, C, wnode_bytes;           // nconv: nodes with a convolution (the others are plain max-pools)
+  int generic;                                           // plan: 1 = the generic kernel although a shape-specialised one exists (HEP_NECK_GENERIC, A/B and parity runs)
   int bf16, stream_w;                                    // session dtype; stream_w: 0 all node weights resident in LDS, 1 two nodes' weights in LDS (the next node's streamed by LDS-DMA), 2 pointwise weights straight from global memory
   uint32_t nt_rcp;                                       // rcp_u32(ceil(C / 16)): (m-tile, n-tile) pair -> m-tile (filled by launch_chain)
   size_t off_w, off_halo, off_atile, lds_bytes;
 };
 void launch_chain(const ChainArgs&, hipStream_t);
+int chain_shape_id(const ChainArgs&);            // > 0: the row of chain_shape() (k_chain_impl.h) whose chain_shape_kernel runs this launch; 0: the generic chain_kernel
 int chain_prepare(void);
 
 // ---- decode: boxes + translation from raw heads (loss.py:12-51) ----
@@ -621,5 +625,6 @@ int filter_prepare(void);     // raises the dynamic-LDS limit of filter_kernel (
 void launch_amax_bf16(const void* x, int64_t n, unsigned* out /* float bits, zeroed */, hipStream_t);
 int dw_blocks_per_image(int Ho, int Wo, int C, int TW);
 void sep_lds_layout(int C, int bf16, int ts, int max_cols_f32, int max_cols_map, SepArgs* a, int stage_w = 0);   // stage_w: single nodes / chains of map-to-map nodes may keep their pointwise weights in LDS
+int sep_shape_id(const SepArgs&);   // > 0: the row of SEP_SHAPES (k_sep_impl.h) whose sep_shape_kernel runs this launch; 0: a generic sep_kernel
 int sep_w8(const SepArgs&);   // launch_sep picks the eight-wave single-node instantiation (k_sep.hip)
 int sep_prepare(void);   // raises the dynamic-LDS limit of the sepconv kernels (call once per device)

@@ -16,6 +16,7 @@ Knobs read_knobs() {
   if (const char* e = getenv("HEP_MBF_MP")) k.mbf_mp = !strcmp(e, "force") ? 3 : (atoi(e) == 2 ? 2 : (atoi(e) != 0 ? 1 : 0));
   env_int("HEP_MBF_GENERIC", &k.mbf_generic);
   env_int("HEP_XBF_GENERIC", &k.xbf_generic);
+  env_int("HEP_NECK_GENERIC", &k.neck_generic);
   env_int("HEP_STEM_MFMA", &k.stem_mfma);
   if (const char* e = getenv("HEP_SE_MAXMB")) k.se_maxmb = atof(e);
   env_int("HEP_PW_FRAG", &k.pw_frag);

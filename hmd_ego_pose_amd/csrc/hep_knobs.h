@@ -1,6 +1,6 @@
 // hep_knobs.h - every environment variable the plan builder looks at, read in ONE place (hep_knobs.cpp) when a session is created.
 //
-// Default library (libhep.so): the ten knobs below "default build" - each forces a form that the planner selects by itself for
+// Default library (libhep.so): the knobs below "default build" - each forces a form that the planner selects by itself for
 // some other shape or precision (so that the parity tests reach that form at a small size), or is a reporting switch.
 // Alternative library (libhep_alt.so, `make -C hmd_ego_pose_amd/csrc alt`, -DHEP_ALT): additionally the A/B knobs whose measurement is a
 // recorded loss or tie (NOTEBOOK.md), and the three rejected kernels they select (k_late.hip, k_heads.hip, k_sbf.hip).
@@ -16,6 +16,7 @@ struct Knobs {
   int mbf_mp = 1;             // HEP_MBF_MP=0|1|2|force(3): multi-pass expand of the fused fronts off / by rounds / bf16 from two rounds / wherever it exists
   int mbf_generic = 0;        // HEP_MBF_GENERIC=1: the generic fused-front kernel where a shape-specialised one exists
   int xbf_generic = 0;        // HEP_XBF_GENERIC=1: the generic boundary-kernel instantiation where a shape-specialised one exists
+  int neck_generic = 0;       // HEP_NECK_GENERIC=1: the generic BiFPN node and chain kernels where a shape-specialised one exists (2: the nodes only, 3: the chains only - per-family A/B)
   int stem_mfma = -1;         // HEP_STEM_MFMA=0|1: VALU / MFMA stem; -1 = by width
   double se_maxmb = 4.0;      // HEP_SE_MAXMB: squeeze-excite finished in the project GEMM's prologue below this many MB of re-read expand-FC weights per launch
   int pw_frag = 1;            // HEP_PW_FRAG=0: row-major operands for the split-K project GEMMs (bit-identity test of the fragment order)

@@ -792,6 +792,8 @@ struct Planner {
     o.sep.chain = chain && o.segs.size() > 1;
     o.sep.direct = direct;
     o.sep.coop = coop;
+    o.sep.generic = kn.neck_generic == 1 || kn.neck_generic == 2;
+    o.sep.seg0 = o.segs[0];      // (its shape fields decide the kernel - sep_shape_id, also for a plan that is never realised; build_session copies it again with the addresses)
     bool all_maps = true;
     for (const SegSpec& sp : specs) all_maps = all_maps && sp.out_t >= 0 && sp.N == C;
     sep_lds_layout(C, s->dtype, ts_max, cols_f32, cols_map, &o.sep, (chain || specs.size() == 1) && all_maps && !direct && kn.sep_wlds != 0);
@@ -948,6 +950,7 @@ struct Planner {
       ChainExt x; memset(&x, 0, sizeof x);
       x.sh = td.H; x.sw = td.W; x.kind = pooled ? SRC_DOWN : SRC_SAME;
       x.h = pooled ? (td.H + 1) / 2 : td.H; x.w = pooled ? (td.W + 1) / 2 : td.W; x.pool_pad = pool_pad_of(td.H);
+      x.has_store = store_t >= 0;
       x.off = new_slot(store_t >= 0 ? store_t : t, store_t >= 0 ? 0 : (pooled ? 1 : 0), x.h, x.w, -1).off;
       exts.push_back(x); ext_t.push_back(t); ext_store_t.push_back(store_t);
     };
@@ -1048,7 +1051,7 @@ struct Planner {
       top = ntop;
     }
     ChainArgs ca; memset(&ca, 0, sizeof ca);
-    ca.nnodes = (int)nodes.size(); ca.nconv = nconv; ca.next = (int)exts.size(); ca.C = C; ca.wnode_bytes = wnode_bytes; ca.bf16 = s->dtype ? 1 : 0;
+    ca.nnodes = (int)nodes.size(); ca.nconv = nconv; ca.next = (int)exts.size(); ca.C = C; ca.wnode_bytes = wnode_bytes; ca.bf16 = s->dtype ? 1 : 0; ca.generic = kn.neck_generic == 1 || kn.neck_generic == 3;
     const size_t halo_b = (((size_t)(hw_max + 2) * (hw_max + 2) * (C + pad) * es2 + 15) & ~(size_t)15);
     const size_t atile_b = (size_t)((hw_max * hw_max + 15) & ~15) * (C + pad) * es2;
     ca.off_w = ((size_t)top * es2 + 15) & ~(size_t)15;

@@ -1,0 +1,38 @@
+// k_sep_shape.hip - the shape-specialised single BiFPN nodes (k_sep_impl.h SEP_SHAPES: sep_shape_kernel<true, D>): a translation unit
+// of its own so that the build stays parallel; k_sep.hip selects a row (sep_shape_id) and launches it through launch_sep_shape.
+#include <algorithm>
+
+#include "k_sep_impl.h"
+
+// A/B hook (NOTEBOOK.md section 31): the dynamic LDS a row asks for at least.  The rows need 76-78 VGPRs and 25.6 KB of LDS, so three
+// 512-thread workgroups fit on a CU where the generic kernel (112 VGPRs) has two; -DSEP_SHAPE_MIN_LDS=55296 keeps two.
+#ifndef SEP_SHAPE_MIN_LDS
+#define SEP_SHAPE_MIN_LDS 0
+#endif
+
+#define SEP_SHAPE_PREP_ROW(id, ...) \
+  rc |= hipFuncSetAttribute(reinterpret_cast<const void*>(sep_shape_kernel<true, id>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
+#define SEP_SHAPE_LAUNCH_ROW(id, ...) \
+  case id: hipLaunchKernelGGL((sep_shape_kernel<true, id>), grid, dim3(512), std::max<size_t>(a.lds_bytes, SEP_SHAPE_MIN_LDS), s, a); return true;
+
+int sep_shape_prepare(void) {
+  int rc = 0;
+  SEP_SHAPES(SEP_SHAPE_PREP_ROW)
+  return rc;
+}
+
+// false when `id` is no row of the table
+bool launch_sep_shape(int id, const SepArgs& a, dim3 grid, hipStream_t s) {
+  switch (id) {
+    SEP_SHAPES(SEP_SHAPE_LAUNCH_ROW)
+    default: return false;
+  }
+}
+
+void sep_shape_trace_bind(unsigned long long* p, int hw) {
+#ifdef HEP_TOWER_TRACE
+  sep_trace_bind_tu(p, hw);
+#else
+  (void)p; (void)hw;
+#endif
+}
