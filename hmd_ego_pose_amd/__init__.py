@@ -36,4 +36,7 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name in ("augment_6dof", "draw_6dof", "rotation_matrices", "colour_augment", "draw_colour", "COLOUR_OPS"):
         from . import augment
         return getattr(augment, name)
+    if name in ("draw_poses", "cuboid_corners", "label_colours", "detections_from_records"):
+        from . import draw
+        return getattr(draw, name)
     raise AttributeError(name)

@@ -912,6 +912,50 @@ int hep_score_scene_device(const float* det_boxes, const float* det_scores, cons
   return 0;
 } HEP_CATCH_INT
 
+// ---- pose overlays: annotations and kept detections drawn into the frames in one launch ----
+static_assert(HEP_DRAW_MAX_DETECTIONS == DRAW_MAX_DET && HEP_DRAW_BOX2D == DRAW_BOX2D && HEP_DRAW_CUBOID == DRAW_CUBOID && HEP_DRAW_HAND == DRAW_HAND,
+              "the limits and layer bits of include/hep.h are the kernel's");
+int hep_draw_poses_device(uint8_t* frames, int batch, int height, int width, const double* gt, int amax, const double* camera,
+                          const float* det_boxes, const float* det_scores, const int32_t* det_labels, const float* det_rotation,
+                          const float* det_translation, const float* det_hand, int rows, float score_threshold, int max_detections,
+                          const float* cuboids, const uint8_t* colours, int num_labels, int ann_layers, int det_layers, int thickness,
+                          void* stream) try {
+  // every check before any HIP call
+  const char* who = "hep_draw_poses_device: ";
+  const std::pair<const void*, const char*> ptrs[] = {{frames, "frames"}, {cuboids, "cuboids"}, {colours, "colours"}};
+  for (const auto& p : ptrs)
+    if (!p.first) return fail(HEP_ERR_INVALID, std::string(who) + p.second + " is NULL");
+  if (!gt && !camera) return fail(HEP_ERR_INVALID, std::string(who) + "gt and camera are both NULL (the camera comes from one of them)");
+  if (batch < 1) return fail(HEP_ERR_INVALID, std::string(who) + "batch must be >= 1");
+  if (gt && (amax < 1 || amax > SCORE_MAX_ANN)) return fail(HEP_ERR_INVALID, std::string(who) + "amax outside 1..16");
+  const int given = (det_boxes != nullptr) + (det_scores != nullptr) + (det_labels != nullptr) + (det_rotation != nullptr) + (det_translation != nullptr);
+  if (given != 0 && given != 5)
+    return fail(HEP_ERR_INVALID, std::string(who) + "det_boxes, det_scores, det_labels, det_rotation and det_translation must all be given or all be NULL");
+  if (given == 0 && det_hand) return fail(HEP_ERR_INVALID, std::string(who) + "det_hand without the other det_* arrays");
+  if (given == 5) {
+    if (rows < 1 || rows > SCORE_MAX_ROWS) return fail(HEP_ERR_INVALID, std::string(who) + "rows outside 1..256");
+    if (max_detections < 1 || max_detections > (rows < DRAW_MAX_DET ? rows : DRAW_MAX_DET))
+      return fail(HEP_ERR_INVALID, std::string(who) + "max_detections outside 1..min(rows, 64)");
+  }
+  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, std::string(who) + "num_labels outside 1..63");
+  if (thickness < 1 || thickness > 8) return fail(HEP_ERR_INVALID, std::string(who) + "thickness outside 1..8");
+  const int all_layers = DRAW_BOX2D | DRAW_CUBOID | DRAW_HAND;
+  if ((ann_layers & ~all_layers) || (det_layers & ~all_layers))
+    return fail(HEP_ERR_INVALID, std::string(who) + "layer bits outside HEP_DRAW_BOX2D | HEP_DRAW_CUBOID | HEP_DRAW_HAND");
+  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, std::string(who) + "height and width must be in 16..4096");
+  DrawArgs a;
+  a.frames = frames; a.gt = gt; a.camera = camera;
+  a.boxes = det_boxes; a.scores = det_scores; a.labels = det_labels; a.rotation = det_rotation; a.translation = det_translation; a.hand = det_hand;
+  a.cuboids = cuboids;
+  a.B = batch; a.H = height; a.W = width; a.amax = gt ? amax : 0; a.rows = given ? rows : 0; a.max_det = given ? max_detections : 0;
+  a.num_labels = num_labels; a.ann_layers = ann_layers; a.det_layers = det_layers; a.thickness = thickness; a.score_thr = score_threshold;
+  memset(a.colours, 0, sizeof(a.colours));
+  memcpy(a.colours, colours, (size_t)num_labels * 3);
+  launch_draw(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

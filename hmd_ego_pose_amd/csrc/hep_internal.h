@@ -379,6 +379,24 @@ struct SceneScoreArgs {
 };
 void launch_score_scene(const SceneScoreArgs&, hipStream_t);
 
+// ---- pose overlays: annotations and kept detections drawn into uint8 frames in place (k_draw.hip; eval/common.py:452-479) ----
+#define DRAW_MAX_DET 64              // HEP_DRAW_MAX_DETECTIONS
+#define DRAW_BOX2D 1                 // HEP_DRAW_BOX2D / _CUBOID / _HAND
+#define DRAW_CUBOID 2
+#define DRAW_HAND 4
+struct DrawArgs {
+  uint8_t* frames;                                                     // [B][H][W][3]
+  const double* gt;                                                    // [B][amax][SCORE_GT_DOUBLES], nullable
+  const double* camera;                                                // [B][5] fx, fy, cx, cy, scale; nullable when gt is given
+  const float* boxes; const float* scores; const int32_t* labels;      // [B][rows][4|1|1]; all five required ones, or none
+  const float* rotation; const float* translation; const float* hand;  // [B][rows][3|3|63]; hand nullable
+  const float* cuboids;                                                // [num_labels][8][3]
+  int B, H, W, amax, rows, max_det, num_labels, ann_layers, det_layers, thickness;
+  float score_thr;
+  uint8_t colours[SCORE_MAX_LABELS * 3 + 3];                           // [num_labels][3], copied from the host
+};
+void launch_draw(const DrawArgs&, hipStream_t);
+
 // ---- training side: anchor-target assignment (generators/utils/anchors.py:69-221) ----
 #define AT_MAX_GT 64
 struct AnchorTargetArgs {

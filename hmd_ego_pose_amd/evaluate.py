@@ -31,8 +31,13 @@ overlaps most (eval/common.py:953-960), per-label dictionaries and evaluate_mode
 supplied dataset; nothing ships with the reference (dataset, checkpoint and mesh are absent), so the numbers of the
 paper cannot be reproduced here - tests drive this module with a synthetic folder.
 
-Not reproduced: the visualisations (draw_samplevis / MANO hand meshes, eval/common.py:449-590); ``cv2.Rodrigues`` and
-``cv2.projectPoints`` are restated (parity unpinned: cv2 is absent from the build image).
+  drawing (eval/common.py:452-479)  ``save_path`` of ``evaluate_device`` / ``evaluate_scene_device`` (``--save-images DIR``): ground truth and kept
+                              detections drawn into the frames on the GPU by ONE launch of hep_draw_poses_device per batch
+                              (``draw_into`` of the evaluators' ``add``; hmd_ego_pose_amd/draw.py), written as ``<i>.png``
+
+Not reproduced: ``draw_samplevis`` / MANO hand meshes (eval/common.py:481-590), captions and anti-aliased lines; ``cv2.Rodrigues`` and
+``cv2.projectPoints`` are restated, and the overlays' line and disc rasterisation is this project's own integer definition, not
+``cv2.line`` / ``cv2.circle`` (parity unpinned: cv2 is absent from the build image).
 """
 from __future__ import annotations
 
@@ -188,6 +193,16 @@ def load_ply_vertices(path: str) -> np.ndarray:
         return np.stack([v["x"], v["y"], v["z"]], axis=-1).astype(np.float32)
 
 
+def _model_cuboid(info: dict) -> Optional[np.ndarray]:
+    """The model cuboid of one models_info.yml entry (``min_x`` .. ``size_z``) as ``draw.cuboid_corners``, or None when the entry lacks it."""
+    keys = [p + a for p in ("min_", "size_") for a in "xyz"]
+    if not all(k in info for k in keys):
+        return None
+    from .draw import cuboid_corners
+    v = [float(info[k]) for k in keys]
+    return cuboid_corners(v[:3], v[3:])
+
+
 class LinemodFolder:
     """One object of a Linemod-format dataset as the reference's ColibriGenerator reads it: ``<root>/data/<NN>/`` with
     ``rgb/*.png``, ``mask/*.png``, ``gt_<fold>.yml``, ``info_<fold>.yml``, ``test_<fold>.txt`` and
@@ -208,6 +223,7 @@ class LinemodFolder:
         with open(os.path.join(self.model_path, "models_info.yml")) as f:
             models = yaml.load(f, Loader=loader)
         self.diameter = float(models[object_id]["diameter"])
+        self.cuboid = _model_cuboid(models[object_id])                 # float32 [8,3], or None without min_* / size_*
         self.points = load_ply_vertices(os.path.join(self.model_path, f"obj_{object_id:02}.ply"))
         names = sorted(n for n in os.listdir(os.path.join(self.object_path, "rgb"))
                        if n.endswith(image_extension) and n[:-len(image_extension)] in examples)
@@ -389,6 +405,21 @@ def gt_table(annotations: Sequence[dict], cameras: Sequence[np.ndarray], scale) 
     return t
 
 
+def _check_draw_into(who: str, draw_into, frames, cuboids, dev, max_detections: int) -> None:
+    """The ``draw_into`` argument of the evaluators' ``add``, checked before anything is launched."""
+    if draw_into is None:
+        return
+    if cuboids is None:
+        raise ValueError(f"{who}: draw_into needs the evaluator's model cuboids")
+    if (not isinstance(draw_into, torch.Tensor) or draw_into.dtype != torch.uint8 or draw_into.device != dev or draw_into.dim() != 4
+            or draw_into.shape[3] != 3 or not draw_into.is_contiguous() or (isinstance(frames, torch.Tensor) and draw_into.shape[0] != frames.shape[0])):
+        raise ValueError(f"{who}: draw_into must be a contiguous uint8 tensor [B,H,W,3] on {dev}, one image per frame")
+    if not (16 <= draw_into.shape[1] <= 4096 and 16 <= draw_into.shape[2] <= 4096):
+        raise ValueError(f"{who}: draw_into: height and width must be in 16..4096")
+    if max_detections > _capi.DRAW_MAX_DETECTIONS:
+        raise ValueError(f"{who}: draw_into draws at most {_capi.DRAW_MAX_DETECTIONS} detections per image, max_detections is {max_detections}")
+
+
 class DeviceEvaluator:
     """``evaluate`` with nothing on the host until the end: ``add`` runs preprocess (uint8 frames), ``model.detect`` and ONE launch of
     hep_score_detections_device per batch - per-image matching plus ADD, ADD-S, translation, rotation, tip, reprojection and hand
@@ -404,11 +435,21 @@ class DeviceEvaluator:
 
     def __init__(self, model, points, diameter: float, image_size: int, capacity: int, score_threshold: float = 0.05, max_detections: int = 10,
                  iou_threshold: float = 0.5, diameter_threshold: float = 0.1, label: int = 0, symmetric: bool = False,
-                 device: Optional[torch.device] = None, max_points: int = 1000):
+                 device: Optional[torch.device] = None, max_points: int = 1000, cuboid=None, draw_layers: int = _capi.DRAW_CUBOID,
+                 draw_thickness: int = 2):
         if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
             raise ValueError("DeviceEvaluator: capacity and max_detections must be >= 1, max_points in 1..1024")
         self.model, self.image_size, self.capacity = model, int(image_size), int(capacity)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
+        # ``add(..., draw_into=)``: the model cuboid float32 [8,3] (``LinemodFolder.cuboid``) at every label up to ``label`` - the table's rows carry
+        # label 0, the detections theirs - and the layers (HEP_DRAW_*) and line thickness of both annotation and detections
+        self._cuboids = None
+        if cuboid is not None:
+            c = np.ascontiguousarray(cuboid, dtype=np.float32)
+            if c.shape != (8, 3):
+                raise ValueError("DeviceEvaluator: cuboid must be [8,3]")
+            self._cuboids = torch.from_numpy(np.repeat(c[None], int(label) + 1, axis=0)).to(self.device)
+        self.draw_layers, self.draw_thickness = int(draw_layers), int(draw_thickness)
         pts = np.ascontiguousarray(points, dtype=np.float32)
         if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
             raise ValueError("DeviceEvaluator: points must be [P,3] with P >= 1")
@@ -427,11 +468,15 @@ class DeviceEvaluator:
     def reset(self) -> None:
         self.count = 0
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor) -> None:
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None) -> None:
         """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6]
         (``LinemodFolder.camera_input``); ``gt`` float64 [B,88] (``gt_table``); all on the evaluator's device.  Everything is checked on
-        the host before the library sees a pointer; a batch that does not fit the remaining capacity raises ValueError."""
+        the host before the library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.
+        ``draw_into``: uint8 [B,H,W,3] on the device that already holds the original frames (it may be ``frames``): after scoring, the
+        ground truth and the kept detections are drawn into it from the same table and rows, on the same stream
+        (hep_draw_poses_device; needs the evaluator's ``cuboid``).  The scores do not depend on it."""
         dev = self.device
+        _check_draw_into("DeviceEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
         for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
             if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
                 raise ValueError(f"DeviceEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
@@ -465,6 +510,11 @@ class DeviceEvaluator:
             self.label, self.score_threshold, self.max_detections, self.iou_threshold,
             self._records[o:].data_ptr(), self._scores[o:].data_ptr(), self._tp[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.count += B
+        if draw_into is not None:
+            from .draw import draw_poses
+            draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(("boxes", "scores", "labels", "rotation", "translation", "hand"), d)),
+                       score_threshold=self.score_threshold, max_detections=self.max_detections, ann_layers=self.draw_layers,
+                       det_layers=self.draw_layers, thickness=self.draw_thickness)
 
     def result(self) -> Dict[str, float]:
         """The metric dictionary of the images added since the last ``reset``: one device-to-host copy (which waits for the launches),
@@ -484,13 +534,21 @@ class DeviceEvaluator:
 
 def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
                     iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16, device: Optional[torch.device] = None,
-                    symmetric: bool = False) -> Dict[str, float]:
+                    symmetric: bool = False, save_path: Optional[str] = None, draw_hand: bool = False, draw_bbox_2d: bool = False) -> Dict[str, float]:
     """``evaluate`` through a ``DeviceEvaluator``: same arguments (the per-detection ``detections_out`` aside - no detection ever reaches
-    the host), same dictionary plus the keys train.py steers by.  One host synchronisation for the whole folder."""
+    the host), same dictionary plus the keys train.py steers by.  One host synchronisation for the whole folder.
+    ``save_path``: a folder (created if missing) that receives every frame with its ground truth and kept detections drawn in as
+    ``<i>.png``, ``i`` the index in dataset order (eval/common.py:452-479): projected cuboid and centre, plus the hand skeleton with
+    ``draw_hand`` and the 2D box with ``draw_bbox_2d``.  The frames are drawn on the GPU and each batch is copied down once (one
+    synchronisation per batch); the dictionary is the same with and without it."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     n = len(dataset)
+    layers = _capi.DRAW_CUBOID | (_capi.DRAW_HAND if draw_hand else 0) | (_capi.DRAW_BOX2D if draw_bbox_2d else 0)
+    if save_path is not None and dataset.cuboid is None:
+        raise ValueError("evaluate_device: save_path needs the model cuboid (min_* / size_* in models_info.yml)")
     ev = DeviceEvaluator(model, dataset.points, dataset.diameter, image_size, max(n, 1), score_threshold, max_detections, iou_threshold,
-                         diameter_threshold, symmetric=symmetric, device=device)
+                         diameter_threshold, symmetric=symmetric, device=device, cuboid=dataset.cuboid if save_path is not None else None,
+                         draw_layers=layers)
     for i0 in range(0, n, batch_size):
         idx = list(range(i0, min(n, i0 + batch_size)))
         frames = [dataset.load_image(i) for i in idx]
@@ -501,8 +559,19 @@ def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_thresh
         u8 = torch.from_numpy(np.stack(frames)).to(device)
         cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
         gt = torch.from_numpy(gt_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale)).to(device)
-        ev.add(u8, cam, gt)
+        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None)
+        if save_path is not None:
+            save_frames(save_path, idx, u8)
     return ev.result()
+
+
+def save_frames(save_path: str, indices: Sequence[int], frames: torch.Tensor) -> None:
+    """One copy of a drawn batch (uint8 [B,H,W,3], RGB) to the host, then ``<save_path>/<i>.png`` per frame (eval/common.py:479)."""
+    from PIL import Image
+    os.makedirs(save_path, exist_ok=True)
+    host = frames.cpu().numpy()
+    for i, img in zip(indices, host):
+        Image.fromarray(img).save(os.path.join(save_path, f"{i}.png"))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -579,7 +648,8 @@ class SceneEvaluator:
     scheduler with."""
 
     def __init__(self, model, models, image_size: int, capacity: int, amax: int, score_threshold: float = 0.05, max_detections: int = 10,
-                 iou_threshold: float = 0.5, diameter_threshold: float = 0.1, device: Optional[torch.device] = None, max_points: int = 1000):
+                 iou_threshold: float = 0.5, diameter_threshold: float = 0.1, device: Optional[torch.device] = None, max_points: int = 1000,
+                 cuboids=None, draw_layers: int = _capi.DRAW_CUBOID, draw_thickness: int = 2):
         if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
             raise ValueError("SceneEvaluator: capacity and max_detections must be >= 1, max_points in 1..1024")
         if not 1 <= amax <= MAX_ANNOTATIONS:
@@ -588,6 +658,14 @@ class SceneEvaluator:
             raise ValueError(f"SceneEvaluator: 1..{MAX_LABELS} object models, one per label")
         self.model, self.image_size, self.capacity, self.amax = model, int(image_size), int(capacity), int(amax)
         self.device = device or torch.device("cuda", torch.cuda.current_device())
+        # ``add(..., draw_into=)``: the model cuboids float32 [labels,8,3] (``SceneFolder.cuboids``), the layers (HEP_DRAW_*) and line thickness
+        self._cuboids = None
+        if cuboids is not None:
+            c = np.ascontiguousarray(cuboids, dtype=np.float32)
+            if c.shape != (len(models), 8, 3):
+                raise ValueError(f"SceneEvaluator: cuboids must be [{len(models)},8,3], one per label")
+            self._cuboids = torch.from_numpy(c).to(self.device)
+        self.draw_layers, self.draw_thickness = int(draw_layers), int(draw_thickness)
         clouds, self.diameters, self.symmetric = [], [], []
         for l, (points, diameter, symmetric) in enumerate(models):
             pts = np.ascontiguousarray(points, dtype=np.float32)
@@ -612,11 +690,13 @@ class SceneEvaluator:
     def reset(self) -> None:
         self.count = 0
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor) -> None:
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None) -> None:
         """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6];
         ``gt`` float64 [B,amax,88] (``gt_scene_table``); all on the evaluator's device.  Everything is checked on the host before the
-        library sees a pointer; a batch that does not fit the remaining capacity raises ValueError."""
+        library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.  ``draw_into``: as for
+        ``DeviceEvaluator.add`` - every valid annotation and every kept detection, each with its label's cuboid."""
         dev = self.device
+        _check_draw_into("SceneEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
         for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
             if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
                 raise ValueError(f"SceneEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
@@ -650,6 +730,11 @@ class SceneEvaluator:
             self.score_threshold, self.max_detections, self.iou_threshold, self._records[o:].data_ptr(), self._scores[o:].data_ptr(),
             self._tp[o:].data_ptr(), self._labels[o:].data_ptr(), self._counts[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.count += B
+        if draw_into is not None:
+            from .draw import draw_poses
+            draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(("boxes", "scores", "labels", "rotation", "translation", "hand"), d)),
+                       score_threshold=self.score_threshold, max_detections=self.max_detections, ann_layers=self.draw_layers,
+                       det_layers=self.draw_layers, thickness=self.draw_thickness)
 
     def result(self) -> Dict[str, dict]:
         """``{"labels": {l: dict}, "mean": dict}`` of the images added since the last ``reset``: one device-to-host copy (which waits
@@ -707,6 +792,8 @@ class SceneFolder:
             models = yaml.load(f, Loader=loader)
         self.models = [(load_ply_vertices(os.path.join(self.model_path, f"obj_{o:02}.ply")), float(models[o]["diameter"]),
                         any(k.startswith("symmetries") for k in models[o])) for o in self.object_ids]
+        boxes = [_model_cuboid(models[o]) for o in self.object_ids]
+        self.cuboids = np.stack(boxes) if all(c is not None for c in boxes) else None      # float32 [labels,8,3], or None without min_* / size_*
         names = sorted(n for n in os.listdir(os.path.join(self.object_path, "rgb"))
                        if n.endswith(image_extension) and n[:-len(image_extension)] in examples)
         self.image_paths = [os.path.join(self.object_path, "rgb", n) for n in names]
@@ -747,13 +834,18 @@ class SceneFolder:
 
 def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
                           iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16,
-                          device: Optional[torch.device] = None) -> Dict[str, dict]:
+                          device: Optional[torch.device] = None, save_path: Optional[str] = None, draw_hand: bool = False,
+                          draw_bbox_2d: bool = False) -> Dict[str, dict]:
     """A ``SceneFolder`` through a ``SceneEvaluator``, driven like ``evaluate_device``: one forward and one scoring launch per batch,
-    one host synchronisation for the whole folder.  Returns ``SceneEvaluator.result()``."""
+    one host synchronisation for the whole folder.  Returns ``SceneEvaluator.result()``.  ``save_path``, ``draw_hand``,
+    ``draw_bbox_2d``: as for ``evaluate_device`` - every annotation and every kept detection of a frame, each with its label's cuboid."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     n = len(dataset)
+    layers = _capi.DRAW_CUBOID | (_capi.DRAW_HAND if draw_hand else 0) | (_capi.DRAW_BOX2D if draw_bbox_2d else 0)
+    if save_path is not None and dataset.cuboids is None:
+        raise ValueError("evaluate_scene_device: save_path needs the model cuboids (min_* / size_* in models_info.yml)")
     ev = SceneEvaluator(model, dataset.models, image_size, max(n, 1), dataset.amax, score_threshold, max_detections, iou_threshold,
-                        diameter_threshold, device=device)
+                        diameter_threshold, device=device, cuboids=dataset.cuboids if save_path is not None else None, draw_layers=layers)
     for i0 in range(0, n, batch_size):
         idx = list(range(i0, min(n, i0 + batch_size)))
         frames = [dataset.load_image(i) for i in idx]
@@ -764,7 +856,9 @@ def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_th
         u8 = torch.from_numpy(np.stack(frames)).to(device)
         cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
         gt = torch.from_numpy(gt_scene_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale, dataset.amax)).to(device)
-        ev.add(u8, cam, gt)
+        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None)
+        if save_path is not None:
+            save_frames(save_path, idx, u8)
     return ev.result()
 
 
@@ -782,6 +876,10 @@ def main(argv=None):
     ap.add_argument("--score-threshold", type=float, default=0.5)
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "fp8"])
+    ap.add_argument("--save-images", default=None, metavar="DIR", help="write every frame with its ground truth and kept detections drawn in (on the GPU) "
+                    "as DIR/<i>.png (reference: --validation-image-save-path); a single object then runs through evaluate_device")
+    ap.add_argument("--draw-hand", action="store_true", help="with --save-images: the hand skeletons as well")
+    ap.add_argument("--draw-bbox-2d", action="store_true", help="with --save-images: the 2D boxes as well")
     a = ap.parse_args(argv)
     from . import HMDEgoPose, TrainModelWithLoss, load_pack, strip_checkpoint_prefix
     size = int(str(a.img_size).split(",")[0])
@@ -794,13 +892,18 @@ def main(argv=None):
     m.load_state_dict(state, strict=False)
     model = TrainModelWithLoss(m.to("cuda").eval()).eval()
     if ids:
-        res = evaluate_scene_device(SceneFolder(a.dataset_path, ids, fold=a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size)
+        res = evaluate_scene_device(SceneFolder(a.dataset_path, ids, fold=a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size,
+                                    save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d)
         for name, d in [(f"object {o}", res["labels"][l]) for l, o in enumerate(ids)] + [("mean", res["mean"])]:
             print(name)
             for k, v in d.items():
                 print(f"{k:>28s}: {v:.6g}")
         return res
-    res = evaluate(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size)
+    if a.save_images:             # the drawing runs on the GPU path (the host ``evaluate`` does not draw)
+        res = evaluate_device(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size,
+                              save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d)
+    else:
+        res = evaluate(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size)
     for k, v in res.items():
         print(f"{k:>24s}: {v:.6g}")
     return res

@@ -354,6 +354,59 @@ int hep_score_scene_device(const float* det_boxes, const float* det_scores, cons
                            float score_threshold, int max_detections, double iou_threshold,
                            double* records, float* out_scores, int32_t* out_tp, int32_t* out_labels, int32_t* out_count, void* stream);
 
+/* Pose overlays: the valid annotations and the kept detections of every image of a batch drawn into the frames, in place, in ONE
+ * launch - the step of eval/common.py:452-479 (projected cuboid with its centre point, optionally the 2D box and the hand skeleton:
+ * generators/utils/visualization.py:85-117, 143-232, 234-290) from what the evaluators already hold on the device.  Stateless like
+ * hep_score_scene_device: no handle, no allocation, no host synchronisation, asynchronous on `stream`.  The drawing is THIS
+ * library's own definition in integer arithmetic (tests/_draw.py states it in numpy; the kernel matches it byte for byte): cv2's
+ * line / circle rasterisers, LINE_AA and fonts are not restated (parity unpinned, as for the other cv2 conventions), no text.
+ * frames: uint8 [batch][height][width][3], device memory, drawn in place; bytes are written in the channel order given.
+ * gt: [batch][amax][HEP_SCORE_GT_DOUBLES] in the layout of hep_score_scene_device (0 valid, 1-4 box, 5-7 axis-angle in radians, 8-10
+ *   translation, 19 has-hand, 20-82 joints, 83 label), or NULL: no annotation is drawn.  Rows with slot 0 == 0 or a label outside
+ *   0..num_labels-1 (NaN included; the label is truncated to an integer) are skipped.
+ * camera: [batch][5] float64 fx, fy, cx, cy, scale, or NULL: then slots 14-18 of row 0 of the image's gt rows.  Used when given.
+ * det_*: the six arrays of hep_filter_device, [batch][rows][4|1|1|3|3|63]; all five of boxes, scores, labels, rotation, translation,
+ *   or none (no detection is drawn; rows and max_detections are then not read); det_hand may be NULL: no detection hand is drawn.
+ *   A candidate is a row with score > score_threshold (float32 compare; padding and NaN are none); the first max_detections
+ *   candidates are kept, then the kept rows with a label outside 0..num_labels-1 are skipped.  Box = float32(box) / float32(scale),
+ *   rotation = float32(r) * float32(pi) in float32: the roundings of hep_score_detections_device.
+ * cuboids: device, float32 [num_labels][8][3], corner order of generators/colibri.py:121-151.  colours: HOST, uint8 [num_labels][3],
+ *   copied into the kernel argument.
+ * PROJECTION (float64, no contraction): R = Rodrigues of the axis-angle (float64 for an annotation, the float32 product for a
+ *   detection; identity below an angle of 1e-12); cuboid corner p = ((R0 c0 + R1 c1) + R2 c2) + t per row of R, the centre is t, hand
+ *   joints (annotation: slots 20-82, detection: det_hand) are camera-frame points as they are; u = (fx X) / Z + cx, v = (fy Y) / Z + cy.
+ *   A point with Z <= 0 (or a NaN anywhere) is invalid.  Each coordinate - the box corners as well, unprojected - is saturated to
+ *   [-8192, 8191], then truncated toward zero.
+ * PRIMITIVES of a shape, in this order: (1) with HEP_DRAW_BOX2D the four segments (x1,y1)-(x2,y1)-(x2,y2)-(x1,y2)-(x1,y1); (2) with
+ *   HEP_DRAW_CUBOID the twelve edges 0-1 1-2 2-3 0-3 4-5 5-6 6-7 4-7 0-4 1-5 2-6 3-7 (visualization.py:99-112), then the disc of radius 3
+ *   at the centre; (3) with HEP_DRAW_HAND, for a shape that has joints, the 20 segments of the chains 0-1-2-3-4, 0-5-..-8, 0-9-..-12,
+ *   0-13-..-16, 0-17-..-20.  A segment with an invalid end point and a disc with an invalid centre are skipped.
+ * COVERAGE, exact in int64: pixel p = (x, y) belongs to the segment (a, b) of thickness t when its distance to the segment is at
+ *   most t / 2: with d = b - a, L = d.d, s = (p - a).d:  s <= 0: 4 |p-a|^2 <= t^2;  s >= L: 4 |p-b|^2 <= t^2;  otherwise
+ *   4 ((p-a) x d)^2 <= t^2 L  (a == b: the disc of radius t / 2).  Disc of radius 3: |p-c|^2 <= 9.  No gaps at t = 1; axis-aligned lines
+ *   are 1, 3, 3, 5 pixels wide for t = 1..4.
+ * ORDER AND COLOURS: per image the valid annotation slots in slot order, then the kept detections in row order; a later primitive
+ *   overwrites an earlier one, a pixel nothing covers keeps its bytes.  Annotation: cuboid and disc (0,255,0), 2D box (0,127,0), hand
+ *   (0,178,0).  Detection: cuboid, disc and hand the label's colour, 2D box (255,0,255).
+ * One workgroup per 64 x 16 pixel tile; a thread writes only its own pixels (no atomics, deterministic), never outside
+ * frames[0 .. batch*height*width*3).
+ * Checked before any HIP call, HEP_ERR_INVALID with the reason in hep_last_error: NULL frames, cuboids or colours; gt and camera both
+ * NULL; gt given with amax outside 1..16; a partial set of the five required det_* pointers (or det_hand alone); with detections, rows
+ * outside 1..256 and max_detections outside 1..min(rows, HEP_DRAW_MAX_DETECTIONS); num_labels outside 1..63; thickness outside 1..8;
+ * layer bits outside the three flags; batch < 1.  height or width outside 16..4096: HEP_ERR_UNSUPPORTED. */
+#define HEP_DRAW_BOX2D 1
+#define HEP_DRAW_CUBOID 2
+#define HEP_DRAW_HAND 4
+#define HEP_DRAW_MAX_DETECTIONS 64
+int hep_draw_poses_device(uint8_t* frames, int batch, int height, int width,
+                          const double* gt, int amax, const double* camera,
+                          const float* det_boxes, const float* det_scores, const int32_t* det_labels,
+                          const float* det_rotation, const float* det_translation, const float* det_hand, int rows,
+                          float score_threshold, int max_detections,
+                          const float* cuboids /* device [num_labels][8][3] */,
+                          const uint8_t* colours /* HOST [num_labels][3], copied into the kernel argument */,
+                          int num_labels, int ann_layers, int det_layers, int thickness, void* stream);
+
 /* Training side: anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 with the IoU
  * matrix of generators/utils/compute_overlap.pyx:33-73 and bbox_transform anchors.py:422-458, on device memory: per
  * image the ground-truth boxes [batch][kmax][4] (float64 x1,y1,x2,y2; the first num_gt[b] are valid), their labels,
