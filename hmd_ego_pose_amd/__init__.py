@@ -39,4 +39,7 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name in ("draw_poses", "cuboid_corners", "label_colours", "detections_from_records"):
         from . import draw
         return getattr(draw, name)
+    if name in ("render_models", "MeshSet", "load_ply_mesh", "poses_from_annotations", "poses_from_detections"):
+        from . import render
+        return getattr(render, name)
     raise AttributeError(name)

@@ -956,6 +956,58 @@ int hep_draw_poses_device(uint8_t* frames, int batch, int height, int width, con
   return 0;
 } HEP_CATCH_INT
 
+// ---- object models under poses: mask, depth and filled overlays from one z-buffered rasteriser ----
+static_assert(HEP_RENDER_MAX_POSES == RENDER_MAX_POSES && HEP_RENDER_MAX_ELEMENTS == RENDER_MAX_ELEMS, "the limits of include/hep.h are the kernel's");
+static int render_range(int batch, int height, int width, int pmax, int num_vertices) {
+  const char* who = "hep_render_models_device: ";
+  if (batch < 1) return fail(HEP_ERR_INVALID, std::string(who) + "batch must be >= 1");
+  if (pmax < 1 || pmax > RENDER_MAX_POSES) return fail(HEP_ERR_INVALID, std::string(who) + "pmax outside 1..16");
+  if (num_vertices < 1 || num_vertices > RENDER_MAX_ELEMS) return fail(HEP_ERR_INVALID, std::string(who) + "num_vertices outside 1..16777216");
+  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, std::string(who) + "height and width must be in 16..4096");
+  return 0;
+}
+
+int64_t hep_render_workspace_bytes(int batch, int height, int width, int pmax, int num_vertices) try {
+  if (int rc = render_range(batch, height, width, pmax, num_vertices)) return rc;
+  return (int64_t)batch * pmax * ((int64_t)num_vertices + 1) * (int64_t)sizeof(RenderVertex);      // the vertex records, then one bounding box per (image, slot)
+} HEP_CATCH_INT
+
+int hep_render_models_device(const double* poses, int batch, int pmax, const double* camera, const float* vertices, int num_vertices,
+                             const int32_t* faces, int num_faces, const int32_t* face_start, int num_labels, int height, int width,
+                             uint8_t* mask, float* depth, uint8_t* frames, const uint8_t* colours, int alpha,
+                             void* workspace, int64_t workspace_bytes, void* stream) try {
+  // every check before any HIP call
+  const char* who = "hep_render_models_device: ";
+  const std::pair<const void*, const char*> ptrs[] = {{poses, "poses"}, {camera, "camera"}, {vertices, "vertices"}, {faces, "faces"},
+                                                      {face_start, "face_start"}, {workspace, "workspace"}};
+  for (const auto& p : ptrs)
+    if (!p.first) return fail(HEP_ERR_INVALID, std::string(who) + p.second + " is NULL");
+  if (!mask && !depth && !frames) return fail(HEP_ERR_INVALID, std::string(who) + "mask, depth and frames are all NULL");
+  if (int rc = render_range(batch, height, width, pmax, num_vertices)) return rc;
+  if (num_faces < 1 || num_faces > RENDER_MAX_ELEMS) return fail(HEP_ERR_INVALID, std::string(who) + "num_faces outside 1..16777216");
+  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, std::string(who) + "num_labels outside 1..63");
+  if (face_start[0] < 0 || face_start[num_labels] > num_faces) return fail(HEP_ERR_INVALID, std::string(who) + "face_start leaves 0..num_faces");
+  for (int l = 0; l < num_labels; l++)
+    if (face_start[l] > face_start[l + 1]) return fail(HEP_ERR_INVALID, std::string(who) + "face_start decreases");
+  if (frames && !colours) return fail(HEP_ERR_INVALID, std::string(who) + "frames without colours");
+  if (frames && (alpha < 0 || alpha > 256)) return fail(HEP_ERR_INVALID, std::string(who) + "alpha outside 0..256");
+  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, std::string(who) + "workspace must be 16-byte aligned");
+  if (workspace_bytes < hep_render_workspace_bytes(batch, height, width, pmax, num_vertices))
+    return fail(HEP_ERR_INVALID, std::string(who) + "workspace too small (hep_render_workspace_bytes)");
+  RenderArgs a;
+  a.poses = poses; a.camera = camera; a.vertices = vertices; a.faces = faces; a.mask = mask; a.depth = depth; a.frames = frames;
+  a.ws = (RenderVertex*)workspace;
+  a.boxes = (int4*)(a.ws + (int64_t)batch * pmax * num_vertices);
+  a.B = batch; a.H = height; a.W = width; a.pmax = pmax; a.V = num_vertices; a.F = num_faces; a.num_labels = num_labels; a.alpha = frames ? alpha : 0;
+  memset(a.face_start, 0, sizeof(a.face_start));
+  memcpy(a.face_start, face_start, (size_t)(num_labels + 1) * sizeof(int32_t));
+  memset(a.colours, 0, sizeof(a.colours));
+  if (frames) memcpy(a.colours, colours, (size_t)num_labels * 3);
+  launch_render(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

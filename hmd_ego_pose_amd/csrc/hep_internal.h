@@ -397,6 +397,24 @@ struct DrawArgs {
 };
 void launch_draw(const DrawArgs&, hipStream_t);
 
+// ---- object models rendered under poses: mask, depth and filled overlays from one z-buffered rasteriser (k_render.hip) ----
+#define RENDER_MAX_POSES 16          // HEP_RENDER_MAX_POSES
+#define RENDER_MAX_ELEMS (1 << 24)   // HEP_RENDER_MAX_ELEMENTS: vertices and faces; a face index fits the 24 low bits of a winner's key
+struct RenderVertex { int32_t sx, sy; double w; };                     // sub-pixel coordinates, 1 / Z; w < 0: invalid
+static_assert(sizeof(RenderVertex) == 16 && sizeof(int4) == 16, "the workspace holds 16 bytes per (image, slot, vertex) and per (image, slot)");
+struct RenderArgs {
+  const double* poses;                                                 // [B][pmax][16]
+  const double* camera;                                                // [B][5] fx, fy, cx, cy, (scale)
+  const float* vertices; const int32_t* faces;                         // [V][3], [F][3]
+  uint8_t* mask; float* depth; uint8_t* frames;                        // [B][H][W], [B][H][W], [B][H][W][3]; each nullable, not all
+  RenderVertex* ws;                                                    // [B][pmax][V]
+  int4* boxes;                                                         // [B][pmax] sub-pixel x0, y0, x1, y1 of a slot's valid vertices, behind ws
+  int B, H, W, pmax, V, F, num_labels, alpha;
+  int32_t face_start[SCORE_MAX_LABELS + 1];                            // label l owns faces [face_start[l], face_start[l+1]); checked on the host
+  uint8_t colours[SCORE_MAX_LABELS * 3 + 3];                           // [num_labels][3], copied from the host (zeros without frames)
+};
+void launch_render(const RenderArgs&, hipStream_t);
+
 // ---- training side: anchor-target assignment (generators/utils/anchors.py:69-221) ----
 #define AT_MAX_GT 64
 struct AnchorTargetArgs {

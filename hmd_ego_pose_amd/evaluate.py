@@ -34,6 +34,8 @@ paper cannot be reproduced here - tests drive this module with a synthetic folde
   drawing (eval/common.py:452-479)  ``save_path`` of ``evaluate_device`` / ``evaluate_scene_device`` (``--save-images DIR``): ground truth and kept
                               detections drawn into the frames on the GPU by ONE launch of hep_draw_poses_device per batch
                               (``draw_into`` of the evaluators' ``add``; hmd_ego_pose_amd/draw.py), written as ``<i>.png``
+  filled models (no counterpart)    ``draw_model`` (``--draw-model``; ``meshes`` of the evaluators' ``add``): the model mesh of every kept detection
+                              under its pose blended in beneath the lines by hep_render_models_device (hmd_ego_pose_amd/render.py)
 
 Not reproduced: ``draw_samplevis`` / MANO hand meshes (eval/common.py:481-590), captions and anti-aliased lines; ``cv2.Rodrigues`` and
 ``cv2.projectPoints`` are restated, and the overlays' line and disc rasterisation is this project's own integer definition, not
@@ -420,6 +422,39 @@ def _check_draw_into(who: str, draw_into, frames, cuboids, dev, max_detections: 
         raise ValueError(f"{who}: draw_into draws at most {_capi.DRAW_MAX_DETECTIONS} detections per image, max_detections is {max_detections}")
 
 
+def _check_meshes(who: str, meshes, draw_into, dev, max_detections: int) -> None:
+    """The ``meshes`` argument of the evaluators' ``add``, checked before anything is launched."""
+    if meshes is None:
+        return
+    from .render import MeshSet
+    if draw_into is None:
+        raise ValueError(f"{who}: meshes are blended into draw_into, which is missing")
+    if not isinstance(meshes, MeshSet) or meshes.device != dev:
+        raise ValueError(f"{who}: meshes must be a render.MeshSet on {dev}")
+    if max_detections > _capi.RENDER_MAX_POSES:
+        raise ValueError(f"{who}: meshes are rendered for at most {_capi.RENDER_MAX_POSES} detections per image, max_detections is {max_detections}")
+
+
+def _blend_models(draw_into, meshes, gt0, d, score_threshold: float, max_detections: int) -> None:
+    """The filled models of the kept detections blended into ``draw_into`` (hep_render_models_device) - before the lines are drawn.
+    ``gt0``: row 0 of each image's ground-truth rows [B,88], whose slots 14-18 are the camera the draw call uses too."""
+    from .render import poses_from_detections, render_models
+    poses = poses_from_detections(dict(scores=d[1], labels=d[2], rotation=d[3], translation=d[4]), score_threshold, max_detections)
+    render_models(poses, gt0[:, 14:19].contiguous(), meshes, int(draw_into.shape[1]), int(draw_into.shape[2]), mask=False, blend_into=draw_into)
+
+
+def _folder_meshes(who: str, model_path: str, object_ids, device):
+    """The ``draw_model`` argument of the folder evaluations: the triangle meshes of the folder's PLY files, one label per object."""
+    from .render import MeshSet, load_ply_mesh
+    meshes = []
+    for o in object_ids:
+        try:
+            meshes.append(load_ply_mesh(os.path.join(model_path, f"obj_{o:02}.ply")))
+        except ValueError as e:
+            raise ValueError(f"{who}: draw_model needs triangle faces in the folder's PLY files ({e})") from None
+    return MeshSet(meshes, device=device)
+
+
 class DeviceEvaluator:
     """``evaluate`` with nothing on the host until the end: ``add`` runs preprocess (uint8 frames), ``model.detect`` and ONE launch of
     hep_score_detections_device per batch - per-image matching plus ADD, ADD-S, translation, rotation, tip, reprojection and hand
@@ -468,15 +503,18 @@ class DeviceEvaluator:
     def reset(self) -> None:
         self.count = 0
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None) -> None:
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None) -> None:
         """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6]
         (``LinemodFolder.camera_input``); ``gt`` float64 [B,88] (``gt_table``); all on the evaluator's device.  Everything is checked on
         the host before the library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.
         ``draw_into``: uint8 [B,H,W,3] on the device that already holds the original frames (it may be ``frames``): after scoring, the
         ground truth and the kept detections are drawn into it from the same table and rows, on the same stream
-        (hep_draw_poses_device; needs the evaluator's ``cuboid``).  The scores do not depend on it."""
+        (hep_draw_poses_device; needs the evaluator's ``cuboid``).  The scores do not depend on it.
+        ``meshes``: a ``render.MeshSet`` next to ``draw_into``: the filled models of the kept detections are blended in first
+        (hep_render_models_device, the labels' colours at half weight), then the lines are drawn on top."""
         dev = self.device
         _check_draw_into("DeviceEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
+        _check_meshes("DeviceEvaluator.add", meshes, draw_into, dev, self.max_detections)
         for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
             if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
                 raise ValueError(f"DeviceEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
@@ -510,6 +548,8 @@ class DeviceEvaluator:
             self.label, self.score_threshold, self.max_detections, self.iou_threshold,
             self._records[o:].data_ptr(), self._scores[o:].data_ptr(), self._tp[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.count += B
+        if meshes is not None:
+            _blend_models(draw_into, meshes, g, d, self.score_threshold, self.max_detections)
         if draw_into is not None:
             from .draw import draw_poses
             draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(("boxes", "scores", "labels", "rotation", "translation", "hand"), d)),
@@ -534,18 +574,23 @@ class DeviceEvaluator:
 
 def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
                     iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16, device: Optional[torch.device] = None,
-                    symmetric: bool = False, save_path: Optional[str] = None, draw_hand: bool = False, draw_bbox_2d: bool = False) -> Dict[str, float]:
+                    symmetric: bool = False, save_path: Optional[str] = None, draw_hand: bool = False, draw_bbox_2d: bool = False,
+                    draw_model: bool = False) -> Dict[str, float]:
     """``evaluate`` through a ``DeviceEvaluator``: same arguments (the per-detection ``detections_out`` aside - no detection ever reaches
     the host), same dictionary plus the keys train.py steers by.  One host synchronisation for the whole folder.
     ``save_path``: a folder (created if missing) that receives every frame with its ground truth and kept detections drawn in as
     ``<i>.png``, ``i`` the index in dataset order (eval/common.py:452-479): projected cuboid and centre, plus the hand skeleton with
     ``draw_hand`` and the 2D box with ``draw_bbox_2d``.  The frames are drawn on the GPU and each batch is copied down once (one
-    synchronisation per batch); the dictionary is the same with and without it."""
+    synchronisation per batch); the dictionary is the same with and without it.  ``draw_model`` (with ``save_path``): the filled model
+    of every kept detection under its pose, blended in beneath the lines; the folder's PLY file must have triangle faces (ValueError)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     n = len(dataset)
     layers = _capi.DRAW_CUBOID | (_capi.DRAW_HAND if draw_hand else 0) | (_capi.DRAW_BOX2D if draw_bbox_2d else 0)
     if save_path is not None and dataset.cuboid is None:
         raise ValueError("evaluate_device: save_path needs the model cuboid (min_* / size_* in models_info.yml)")
+    if draw_model and save_path is None:
+        raise ValueError("evaluate_device: draw_model draws into the saved frames: it needs save_path")
+    meshes = _folder_meshes("evaluate_device", dataset.model_path, [dataset.object_id], device) if draw_model else None
     ev = DeviceEvaluator(model, dataset.points, dataset.diameter, image_size, max(n, 1), score_threshold, max_detections, iou_threshold,
                          diameter_threshold, symmetric=symmetric, device=device, cuboid=dataset.cuboid if save_path is not None else None,
                          draw_layers=layers)
@@ -559,7 +604,7 @@ def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_thresh
         u8 = torch.from_numpy(np.stack(frames)).to(device)
         cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
         gt = torch.from_numpy(gt_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale)).to(device)
-        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None)
+        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes)
         if save_path is not None:
             save_frames(save_path, idx, u8)
     return ev.result()
@@ -690,13 +735,15 @@ class SceneEvaluator:
     def reset(self) -> None:
         self.count = 0
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None) -> None:
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None) -> None:
         """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6];
         ``gt`` float64 [B,amax,88] (``gt_scene_table``); all on the evaluator's device.  Everything is checked on the host before the
         library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.  ``draw_into``: as for
-        ``DeviceEvaluator.add`` - every valid annotation and every kept detection, each with its label's cuboid."""
+        ``DeviceEvaluator.add`` - every valid annotation and every kept detection, each with its label's cuboid.  ``meshes``: as for
+        ``DeviceEvaluator.add``, one mesh per label."""
         dev = self.device
         _check_draw_into("SceneEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
+        _check_meshes("SceneEvaluator.add", meshes, draw_into, dev, self.max_detections)
         for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
             if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
                 raise ValueError(f"SceneEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
@@ -730,6 +777,8 @@ class SceneEvaluator:
             self.score_threshold, self.max_detections, self.iou_threshold, self._records[o:].data_ptr(), self._scores[o:].data_ptr(),
             self._tp[o:].data_ptr(), self._labels[o:].data_ptr(), self._counts[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.count += B
+        if meshes is not None:
+            _blend_models(draw_into, meshes, g[:, 0], d, self.score_threshold, self.max_detections)
         if draw_into is not None:
             from .draw import draw_poses
             draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(("boxes", "scores", "labels", "rotation", "translation", "hand"), d)),
@@ -835,15 +884,19 @@ class SceneFolder:
 def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
                           iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16,
                           device: Optional[torch.device] = None, save_path: Optional[str] = None, draw_hand: bool = False,
-                          draw_bbox_2d: bool = False) -> Dict[str, dict]:
+                          draw_bbox_2d: bool = False, draw_model: bool = False) -> Dict[str, dict]:
     """A ``SceneFolder`` through a ``SceneEvaluator``, driven like ``evaluate_device``: one forward and one scoring launch per batch,
     one host synchronisation for the whole folder.  Returns ``SceneEvaluator.result()``.  ``save_path``, ``draw_hand``,
-    ``draw_bbox_2d``: as for ``evaluate_device`` - every annotation and every kept detection of a frame, each with its label's cuboid."""
+    ``draw_bbox_2d``, ``draw_model``: as for ``evaluate_device`` - every annotation and every kept detection of a frame, each with its
+    label's cuboid (and, with ``draw_model``, every kept detection's filled model)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     n = len(dataset)
     layers = _capi.DRAW_CUBOID | (_capi.DRAW_HAND if draw_hand else 0) | (_capi.DRAW_BOX2D if draw_bbox_2d else 0)
     if save_path is not None and dataset.cuboids is None:
         raise ValueError("evaluate_scene_device: save_path needs the model cuboids (min_* / size_* in models_info.yml)")
+    if draw_model and save_path is None:
+        raise ValueError("evaluate_scene_device: draw_model draws into the saved frames: it needs save_path")
+    meshes = _folder_meshes("evaluate_scene_device", dataset.model_path, dataset.object_ids, device) if draw_model else None
     ev = SceneEvaluator(model, dataset.models, image_size, max(n, 1), dataset.amax, score_threshold, max_detections, iou_threshold,
                         diameter_threshold, device=device, cuboids=dataset.cuboids if save_path is not None else None, draw_layers=layers)
     for i0 in range(0, n, batch_size):
@@ -856,7 +909,7 @@ def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_th
         u8 = torch.from_numpy(np.stack(frames)).to(device)
         cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
         gt = torch.from_numpy(gt_scene_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale, dataset.amax)).to(device)
-        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None)
+        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes)
         if save_path is not None:
             save_frames(save_path, idx, u8)
     return ev.result()
@@ -880,6 +933,8 @@ def main(argv=None):
                     "as DIR/<i>.png (reference: --validation-image-save-path); a single object then runs through evaluate_device")
     ap.add_argument("--draw-hand", action="store_true", help="with --save-images: the hand skeletons as well")
     ap.add_argument("--draw-bbox-2d", action="store_true", help="with --save-images: the 2D boxes as well")
+    ap.add_argument("--draw-model", action="store_true", help="with --save-images: the filled model of every kept detection under its pose, beneath the "
+                    "lines (the folder's PLY files need triangle faces)")
     a = ap.parse_args(argv)
     from . import HMDEgoPose, TrainModelWithLoss, load_pack, strip_checkpoint_prefix
     size = int(str(a.img_size).split(",")[0])
@@ -893,15 +948,15 @@ def main(argv=None):
     model = TrainModelWithLoss(m.to("cuda").eval()).eval()
     if ids:
         res = evaluate_scene_device(SceneFolder(a.dataset_path, ids, fold=a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size,
-                                    save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d)
+                                    save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d, draw_model=a.draw_model)
         for name, d in [(f"object {o}", res["labels"][l]) for l, o in enumerate(ids)] + [("mean", res["mean"])]:
             print(name)
             for k, v in d.items():
                 print(f"{k:>28s}: {v:.6g}")
         return res
-    if a.save_images:             # the drawing runs on the GPU path (the host ``evaluate`` does not draw)
+    if a.save_images or a.draw_model:             # the drawing runs on the GPU path (the host ``evaluate`` does not draw)
         res = evaluate_device(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size,
-                              save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d)
+                              save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d, draw_model=a.draw_model)
     else:
         res = evaluate(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size)
     for k, v in res.items():
