@@ -1115,7 +1115,8 @@ static std::string kernel_symbol(const Session& s, const Op& o) {
     case OP_HEADS: snprintf(tmp, sizeof tmp, "heads_kernel"); break;
 #endif
     case OP_XBF: { const int sp = xbf_specialised(o.xbf);
-                   snprintf(tmp, sizeof tmp, "xbf_kernel<%s, %d, %d, %d, %d, %d, %d, %d>", t, o.xbf.k, o.xbf.s, o.xbf.toh, o.xbf.tow, o.xbf.NT1, sp ? o.xbf.K1 : 0, sp ? o.xbf.NT2 : 0); break; }
+                   if (const int id = xbf_shape_id(o.xbf)) snprintf(tmp, sizeof tmp, "xbf_kernel_shape<true, %d>", id);      // (the row of XBF_SHAPES, k_xbf_impl.h)
+                   else snprintf(tmp, sizeof tmp, "xbf_kernel<%s, %d, %d, %d, %d, %d, %d, %d>", t, o.xbf.k, o.xbf.s, o.xbf.toh, o.xbf.tow, o.xbf.NT1, sp ? o.xbf.K1 : 0, sp ? o.xbf.NT2 : 0); break; }
     default: if (o.sep.direct) snprintf(tmp, sizeof tmp, "%s<%s, %d, %s>", o.sep.coop ? "tower_coop_kernel" : "tower_kernel", t, o.sep.C, o.sep.direct == 2 ? "true" : "false");
              else {
                const int mode = o.sep.chain ? 2 : (o.sep.nseg == 1 ? 0 : 1);

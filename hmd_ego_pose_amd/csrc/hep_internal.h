@@ -149,15 +149,18 @@ struct XbfArgs {
   int chunk_tiles, nchunks;                                         // expanded n-tiles per LDS chunk (<= 2 chunks)
   uint32_t tiles_rcp, tiles_x_rcp, sw_rcp;                          // rcp_u32 of workgroups per image, tiles_x, lane sweeps per input tile row
   int trace;                                                         // profiling builds: this launch writes its phase stamps
-  int generic;                                                       // plan: 1 = the generic instantiation although a shape-specialised one exists (HEP_XBF_GENERIC, A/B and parity runs)
-  int off_w1, off_w2, off_f, off_misc; size_t lds_bytes;            // LDS: [a_s | e_s union][blob: w1 | w2 | floats][scale, hidden, red, csum]
+  int generic;                                                       // plan: 1 = the generic instantiation although a shape-specialised one exists, 2 = the width-specialised instantiation although a shape row exists (HEP_XBF_GENERIC, A/B and parity runs)
+  int off_w1, off_w2, off_f, off_misc;                              // LDS: [a_s | e_s union][blob: w1 | w2 | floats][scale, hidden, red, csum]
+  int has_res;                                                       // plan: block i-1 has a residual input (`res` is set when the session is realised; xbf_shape_id asks before that).  (In the padding in front of lds_bytes: the argument block keeps its size and offsets)
+  size_t lds_bytes;
 };
 size_t xbf_layout(XbfArgs* a);                   // fills the LDS offsets / chunking from the shapes; returns lds_bytes (0: does not fit)
 int xbf_supports(int k, int s);                  // tile instantiations
 void xbf_tile(int k, int s, int* toh, int* tow);
 void launch_xbf(const XbfArgs&, hipStream_t);
 int xbf_prepare(void);
-int xbf_specialised(const XbfArgs&);          // 1: a shape-specialised instantiation exists (names the device function)
+int xbf_specialised(const XbfArgs&);          // 1: a width-specialised instantiation exists (names the device function)
+int xbf_shape_id(const XbfArgs&);             // > 0: the row of XBF_SHAPES (k_xbf_impl.h) whose xbf_kernel_shape runs this launch; 0: an xbf_kernel
 
 #ifdef HEP_ALT
 // ---- image-resident run of late MBConv blocks (k_late.hip): ONE workgroup per image runs several consecutive stride-1 blocks

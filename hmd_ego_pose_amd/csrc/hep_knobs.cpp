@@ -22,6 +22,7 @@ Knobs read_knobs() {
   env_int("HEP_PW_FRAG", &k.pw_frag);
   env_int("HEP_SEP_WLDS", &k.sep_wlds);
   env_int("HEP_PLAN_DEBUG", &k.plan_debug);
+  env_int("HEP_XBF_TPW", &k.xbf_tpw);
 #ifdef HEP_ALT
   env_int("HEP_PW_NT2", &k.pw_nt2);
   env_int("HEP_PW_MT2", &k.pw_mt2);
@@ -32,7 +33,6 @@ Knobs read_knobs() {
   env_int("HEP_SE_TAIL", &k.se_tail);
   env_int("HEP_XBF", &k.xbf);
   env_int("HEP_XBF_MINH", &k.xbf_minh);
-  env_int("HEP_XBF_TPW", &k.xbf_tpw);
   if (const char* e = getenv("HEP_MBF")) k.mbf = !strcmp(e, "all") ? 1 : (!strcmp(e, "none") ? 0 : -1);
   env_int("HEP_MBF_MAXH", &k.mbf_maxh);
   if (const char* e = getenv("HEP_MBF_TS")) k.mbf_ts8 = atoi(e) == 8;

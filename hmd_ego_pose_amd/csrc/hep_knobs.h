@@ -15,7 +15,8 @@ struct Knobs {
   int tower_coop = -1;        // HEP_TOWER_COOP=0|1|2|3: cooperative tower kernel off / everywhere / map layers / headers; -1 = by dtype and width
   int mbf_mp = 1;             // HEP_MBF_MP=0|1|2|force(3): multi-pass expand of the fused fronts off / by rounds / bf16 from two rounds / wherever it exists
   int mbf_generic = 0;        // HEP_MBF_GENERIC=1: the generic fused-front kernel where a shape-specialised one exists
-  int xbf_generic = 0;        // HEP_XBF_GENERIC=1: the generic boundary-kernel instantiation where a shape-specialised one exists
+  int xbf_generic = 0;        // HEP_XBF_GENERIC=1: the generic boundary-kernel instantiation where a specialised one exists (2: no shape row, the width-specialised instantiation - A/B and bit-identity runs)
+  int xbf_tpw = 0;            // HEP_XBF_TPW: tiles per workgroup of the boundary launches (0: by workgroup count; the tests reach the second-tile path at a small batch with it)
   int neck_generic = 0;       // HEP_NECK_GENERIC=1: the generic BiFPN node and chain kernels where a shape-specialised one exists (2: the nodes only, 3: the chains only - per-family A/B)
   int stem_mfma = -1;         // HEP_STEM_MFMA=0|1: VALU / MFMA stem; -1 = by width
   double se_maxmb = 4.0;      // HEP_SE_MAXMB: squeeze-excite finished in the project GEMM's prologue below this many MB of re-read expand-FC weights per launch
@@ -32,7 +33,6 @@ struct Knobs {
   int se_tail = 0;            // HEP_SE_TAIL=1: squeeze-excite finish in the tail of the fused front
   int xbf = 1;                // HEP_XBF=0: no boundary launches
   int xbf_minh = 64;          // HEP_XBF_MINH: smallest input map that takes the boundary kernel
-  int xbf_tpw = 0;            // HEP_XBF_TPW: tiles per workgroup (0: by workgroup count)
   int mbf = -1;               // HEP_MBF=all(1)|none(0): fused front everywhere / nowhere; -1 = by map size
   int mbf_maxh = 32;          // HEP_MBF_MAXH: largest input map that takes the fused front
   int mbf_ts8 = 0;            // HEP_MBF_TS=8: 8x8 tiles only

@@ -264,7 +264,8 @@ struct Planner {
     xa.H = Hin; xa.W = Win; xa.K1 = pb.cexp; xa.N1 = pb.cout; xa.NT1 = (pb.cout + 15) / 16; xa.Cexp = b.cexp; xa.NT2 = b.cexp / 16;
     xa.Ho = Ho; xa.Wo = Wo; xa.k = b.k; xa.s = b.stride; xa.pad_t = pt; xa.pad_l = pl; xa.bf16 = s->dtype;
     xa.se_rows = defer.se.rows; xa.sq = defer.se.sq; xa.sqp = defer.se.sqp; xa.inv_hw = defer.se.inv_hw; xa.sq2 = b.se; xa.sqp2 = sqp2;
-    xa.generic = kn.xbf_generic != 0;
+    xa.generic = kn.xbf_generic == 2 ? 2 : (kn.xbf_generic != 0);
+    xa.has_res = pb.skip ? 1 : 0;
     if (xbf_layout(&xa) == 0) return false;
     xa.tiles_x = (Wo + xa.tow - 1) / xa.tow; xa.tiles = xa.tiles_x * ((Ho + xa.toh - 1) / xa.toh);
     // weights: project of the deferred block (BN2 folded), expand of this block (BN0 folded), depthwise (BN1 folded, by the caller)
@@ -317,7 +318,7 @@ struct Planner {
     o.xbf = xa;
     wref(op, SLOT(xbf.blob), boff); wref(op, SLOT(xbf.se_br), defer.se.br); wref(op, SLOT(xbf.se_we), defer.se.we); wref(op, SLOT(xbf.se_be), defer.se.be); wref(op, SLOT(xbf.se_wr), wr_off);
     tref(op, SLOT(xbf.in), defer.dw_t, false); tref(op, SLOT(xbf.hpart), defer.se.hpart_t, false);
-    if (pb.skip) tref(op, SLOT(xbf.res), defer.inp, false);
+    if (xa.has_res) tref(op, SLOT(xbf.res), defer.inp, false);
     if (mid_needed) tref(op, SLOT(xbf.mid), defer.out_t, true);
     tref(op, SLOT(xbf.out), dw_t, true); tref(op, SLOT(xbf.hpart_out), *part_t, true);
     const double HWin = (double)Hin * Win;
