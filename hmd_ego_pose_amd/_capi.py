@@ -23,6 +23,7 @@ SCORE_GT_DOUBLES, SCORE_RECORD_DOUBLES = 88, 16      # HEP_SCORE_GT_DOUBLES, HEP
 SCORE_MAX_ANNOTATIONS, SCORE_MAX_LABELS = 16, 63     # HEP_SCORE_MAX_ANNOTATIONS; hep_score_scene_device's num_labels
 DRAW_BOX2D, DRAW_CUBOID, DRAW_HAND, DRAW_MAX_DETECTIONS = 1, 2, 4, 64      # HEP_DRAW_* of include/hep.h
 RENDER_MAX_POSES, RENDER_MAX_ELEMENTS = 16, 1 << 24      # HEP_RENDER_* of include/hep.h
+BOP_PAIR_DOUBLES, BOP_MAX_SYMMETRIES, BOP_MAX_TAUS = 32, 64, 16      # HEP_BOP_* of include/hep.h
 PK_TRAIN, PK_STAT, PK_FROZEN = 0, 1, 2      # HEP_PK_* of include/hep.h
 OPT_ADAM, OPT_SGD_NESTEROV = 0, 1          # HEP_OPT_*
 
@@ -65,6 +66,9 @@ SYMBOLS = {
     "hep_render_workspace_bytes": (c_int64, [c_int] * 5),
     "hep_render_models_device": (c_int, [_FP, c_int, c_int, _FP, _FP, c_int, _FP, c_int, POINTER(c_int32), c_int, c_int, c_int, c_void_p, _FP, c_void_p, c_void_p, c_int,
                                          c_void_p, c_int64, c_void_p]),
+    "hep_bop_point_errors_device": (c_int, [_FP, c_int, _FP, c_int, POINTER(c_int32), _FP, c_int, POINTER(c_int32), c_int, _FP, c_void_p]),
+    "hep_bop_workspace_bytes": (c_int64, [c_int, c_int]),
+    "hep_bop_vsd_device": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, c_int, c_int, c_int, c_double, POINTER(c_double), c_int, _FP, _FP, c_void_p, c_int64, c_void_p]),
     "hep_anchor_targets_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_int, c_int, c_int, c_double, c_double, _FP, _FP, _FP, _FP, c_void_p]),
     "hep_losses_device": (c_int, [_FP] * 9 + [c_int] * 7 + [_FP, _FP, c_void_p]),
     "hep_losses_backward_device": (c_int, [_FP] * 9 + [c_int] * 7 + [_FP] * 6 + [c_void_p]),

@@ -1008,6 +1008,84 @@ int hep_render_models_device(const double* poses, int batch, int pmax, const dou
   return 0;
 } HEP_CATCH_INT
 
+// ---- BOP pose errors of matched pairs: MSSD / MSPD and VSD ----
+static_assert(HEP_BOP_PAIR_DOUBLES == BOP_PAIR_DOUBLES && HEP_BOP_MAX_SYMMETRIES == BOP_MAX_SYM && HEP_BOP_MAX_TAUS == BOP_MAX_TAUS,
+              "the table and limits of include/hep.h are the kernel's");
+// a host start table [num_labels + 1]: starts at 0 or above, increases strictly, ends inside `count`, at most `most` entries per label (0: no limit)
+static int bop_start_table(const std::string& who, const char* name, const int32_t* start, int num_labels, int count, int most) {
+  if (start[0] < 0) return fail(HEP_ERR_INVALID, who + name + " starts below 0");
+  for (int l = 0; l < num_labels; l++) {
+    if (start[l + 1] <= start[l]) return fail(HEP_ERR_INVALID, who + name + " must increase (label " + std::to_string(l) + " has no entry)");
+    if (most && start[l + 1] - start[l] > most) return fail(HEP_ERR_INVALID, who + name + ": label " + std::to_string(l) + " has more than " + std::to_string(most) + " entries");
+  }
+  if (start[num_labels] > count) return fail(HEP_ERR_INVALID, who + name + " ends past the array");
+  return 0;
+}
+
+int hep_bop_point_errors_device(const double* pairs, int n, const float* vertices, int num_vertices, const int32_t* vertex_start,
+                                const double* symmetries, int num_symmetries, const int32_t* symmetry_start, int num_labels,
+                                double* errors, void* stream) try {
+  // every check before any HIP call
+  const std::string who = "hep_bop_point_errors_device: ";
+  const std::pair<const void*, const char*> ptrs[] = {{pairs, "pairs"}, {vertices, "vertices"}, {vertex_start, "vertex_start"}, {symmetries, "symmetries"},
+                                                      {symmetry_start, "symmetry_start"}, {errors, "errors"}};
+  for (const auto& p : ptrs)
+    if (!p.first) return fail(HEP_ERR_INVALID, who + p.second + " is NULL");
+  if (n < 1) return fail(HEP_ERR_INVALID, who + "n must be >= 1");
+  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, who + "num_labels outside 1..63");
+  if (num_vertices < 1 || num_symmetries < 1) return fail(HEP_ERR_INVALID, who + "num_vertices and num_symmetries must be >= 1");
+  if (int rc = bop_start_table(who, "vertex_start", vertex_start, num_labels, num_vertices, 0)) return rc;
+  if (int rc = bop_start_table(who, "symmetry_start", symmetry_start, num_labels, num_symmetries, BOP_MAX_SYM)) return rc;
+  BopPointArgs a;
+  a.pairs = pairs; a.vertices = vertices; a.sym = symmetries; a.out = errors; a.n = n; a.num_labels = num_labels;
+  for (int l = 0; l <= SCORE_MAX_LABELS; l++) {
+    a.vertex_start[l] = vertex_start[l <= num_labels ? l : num_labels];
+    a.sym_start[l] = symmetry_start[l <= num_labels ? l : num_labels];
+  }
+  launch_bop_points(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+static int bop_vsd_range(int n, int num_taus) {
+  const char* who = "hep_bop_vsd_device: ";
+  if (n < 1) return fail(HEP_ERR_INVALID, std::string(who) + "n must be >= 1");
+  if (num_taus < 1 || num_taus > BOP_MAX_TAUS) return fail(HEP_ERR_INVALID, std::string(who) + "num_taus outside 1..16");
+  return 0;
+}
+
+int64_t hep_bop_workspace_bytes(int n, int num_taus) try {
+  if (int rc = bop_vsd_range(n, num_taus)) return rc;
+  return ((int64_t)n * (2 + num_taus) * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15;      // the counters, rounded up to the alignment
+} HEP_CATCH_INT
+
+int hep_bop_vsd_device(const double* pairs, int n, int num_labels, const float* depth_gt, const float* depth_est, const float* depth_test,
+                       int num_images, int height, int width, double delta, const double* taus, int num_taus, double* vsd, int32_t* counts,
+                       void* workspace, int64_t workspace_bytes, void* stream) try {
+  // every check before any HIP call
+  const std::string who = "hep_bop_vsd_device: ";
+  const std::pair<const void*, const char*> ptrs[] = {{pairs, "pairs"}, {depth_gt, "depth_gt"}, {depth_est, "depth_est"}, {taus, "taus"}, {vsd, "vsd"},
+                                                      {counts, "counts"}, {workspace, "workspace"}};
+  for (const auto& p : ptrs)
+    if (!p.first) return fail(HEP_ERR_INVALID, who + p.second + " is NULL");
+  if (int rc = bop_vsd_range(n, num_taus)) return rc;
+  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, who + "num_labels outside 1..63");
+  if (depth_test && num_images < 1) return fail(HEP_ERR_INVALID, who + "num_images must be >= 1 with a depth_test");
+  if (!(std::isfinite(delta) && delta > 0.0)) return fail(HEP_ERR_INVALID, who + "delta must be finite and positive");
+  for (int j = 0; j < num_taus; j++)
+    if (!(std::isfinite(taus[j]) && taus[j] > 0.0)) return fail(HEP_ERR_INVALID, who + "tau " + std::to_string(j) + " must be finite and positive");
+  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, who + "workspace must be 16-byte aligned");
+  if (workspace_bytes < hep_bop_workspace_bytes(n, num_taus)) return fail(HEP_ERR_INVALID, who + "workspace too small (hep_bop_workspace_bytes)");
+  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, who + "height and width must be in 16..4096");
+  BopVsdArgs a;
+  a.pairs = pairs; a.depth_gt = depth_gt; a.depth_est = depth_est; a.depth_test = depth_test; a.ws = (int32_t*)workspace; a.vsd = vsd; a.counts = counts;
+  a.n = n; a.H = height; a.W = width; a.T = num_taus; a.images = depth_test ? num_images : 0; a.num_labels = num_labels; a.delta = delta;
+  for (int j = 0; j < BOP_MAX_TAUS; j++) a.taus[j] = j < num_taus ? taus[j] : 0.0;
+  launch_bop_vsd(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // ---- introspection ----
 int hep_debug_tensor_count(const hep_handle* h) try { return h ? (int)h->s.tensors.size() : 0; } HEP_CATCH_INT
 int hep_debug_tensor_info(const hep_handle* h, int i, const char** name, int64_t dims[4]) try {

@@ -418,6 +418,32 @@ struct RenderArgs {
 };
 void launch_render(const RenderArgs&, hipStream_t);
 
+// ---- BOP pose errors of matched pairs: MSSD / MSPD over vertices and symmetries, VSD over rendered depth maps (k_bop.hip) ----
+#define BOP_PAIR_DOUBLES 32          // HEP_BOP_PAIR_DOUBLES
+#define BOP_MAX_SYM 64               // HEP_BOP_MAX_SYMMETRIES
+#define BOP_MAX_TAUS 16              // HEP_BOP_MAX_TAUS
+struct BopPointArgs {
+  const double* pairs;                                                 // [n][BOP_PAIR_DOUBLES]
+  const float* vertices;                                               // [V][3]
+  const double* sym;                                                   // [S_total][12] R row-major, t
+  double* out;                                                         // [n][2] MSSD, MSPD
+  int n, num_labels;
+  int32_t vertex_start[SCORE_MAX_LABELS + 1];                          // label l owns vertices [vertex_start[l], vertex_start[l+1]); checked on the host
+  int32_t sym_start[SCORE_MAX_LABELS + 1];                             // ... and symmetries [sym_start[l], sym_start[l+1]), 1..BOP_MAX_SYM of them
+};
+void launch_bop_points(const BopPointArgs&, hipStream_t);
+struct BopVsdArgs {
+  const double* pairs;                                                 // [n][BOP_PAIR_DOUBLES]
+  const float* depth_gt; const float* depth_est;                       // [n][H][W]
+  const float* depth_test;                                             // [images][H][W], nullable
+  int32_t* ws;                                                         // [n][2 + T] union, intersection, cost per tau
+  double* vsd; int32_t* counts;                                        // [n][T], [n][2 + T]
+  int n, H, W, T, images, num_labels;
+  double delta;
+  double taus[BOP_MAX_TAUS];                                           // copied from the host, zeros behind T
+};
+void launch_bop_vsd(const BopVsdArgs&, hipStream_t);
+
 // ---- training side: anchor-target assignment (generators/utils/anchors.py:69-221) ----
 #define AT_MAX_GT 64
 struct AnchorTargetArgs {

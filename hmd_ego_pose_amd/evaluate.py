@@ -455,6 +455,33 @@ def _folder_meshes(who: str, model_path: str, object_ids, device):
     return MeshSet(meshes, device=device)
 
 
+def _check_bop(who: str, bop, depth_test, frames, dev, num_labels: int):
+    """The ``bop`` and ``depth_test`` arguments of the evaluators' ``add``, checked before anything is launched: the image size, or None."""
+    if bop is None and depth_test is None:
+        return None
+    from .bop import check_settings
+    return check_settings(who, bop, depth_test, frames, dev, num_labels)
+
+
+def _score_bop(ev, bop, size, gt, d, records, diameters, depth_test, o: int, B: int, A: int) -> None:
+    """MSSD, MSPD and VSD of a batch's matched pairs into the evaluator's second buffer [capacity,A,2+T] at image offset ``o``."""
+    from .bop import score_batch
+    T = int(bop.tau_fractions.size)
+    if ev._bop_buf is None or ev._bop_buf.shape[2] != 2 + T:
+        ev._bop_buf = torch.full((ev.capacity, A, 2 + T), float("nan"), dtype=torch.float64, device=ev.device)
+    score_batch(bop, size, gt, dict(rotation=d[3], translation=d[4]), records, diameters, depth_test, ev._bop_buf[o:o + B])
+    ev._bop_count += B
+    ev._bop_width = int(size[1])
+
+
+def _bop_result(ev, who: str, rec: np.ndarray, diameters) -> Dict[str, dict]:
+    """The ``"bop"`` entry of ``result``: one extra copy, then ``bop.summarise_bop``."""
+    from .bop import summarise_bop
+    if ev._bop_count != ev.count:
+        raise ValueError(f"{who}: bop= was given for {ev._bop_count} of the {ev.count} images: give it to every add of an evaluation, or to none")
+    return summarise_bop(rec, ev._bop_buf.cpu().numpy()[:ev.count], diameters, ev._bop_width)
+
+
 class DeviceEvaluator:
     """``evaluate`` with nothing on the host until the end: ``add`` runs preprocess (uint8 frames), ``model.detect`` and ONE launch of
     hep_score_detections_device per batch - per-image matching plus ADD, ADD-S, translation, rotation, tip, reprojection and hand
@@ -499,11 +526,13 @@ class DeviceEvaluator:
         self._scores = self._buf[C * RECORD_DOUBLES * 8:C * (RECORD_DOUBLES * 8 + M * 4)].view(torch.float32).view(C, M)
         self._tp = self._buf[C * (RECORD_DOUBLES * 8 + M * 4):].view(torch.int32).view(C, M)
         self.count = 0
+        self._bop_buf, self._bop_count, self._bop_width = None, 0, 0      # ``add(..., bop=)``: errors [C,1,2+T] float64, allocated on first use
 
     def reset(self) -> None:
-        self.count = 0
+        self.count = self._bop_count = 0
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None) -> None:
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None, bop=None,
+            depth_test: Optional[torch.Tensor] = None) -> None:
         """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6]
         (``LinemodFolder.camera_input``); ``gt`` float64 [B,88] (``gt_table``); all on the evaluator's device.  Everything is checked on
         the host before the library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.
@@ -511,10 +540,14 @@ class DeviceEvaluator:
         ground truth and the kept detections are drawn into it from the same table and rows, on the same stream
         (hep_draw_poses_device; needs the evaluator's ``cuboid``).  The scores do not depend on it.
         ``meshes``: a ``render.MeshSet`` next to ``draw_into``: the filled models of the kept detections are blended in first
-        (hep_render_models_device, the labels' colours at half weight), then the lines are drawn on top."""
+        (hep_render_models_device, the labels' colours at half weight), then the lines are drawn on top.
+        ``bop``: a ``bop.BopSettings`` (its sets hold labels 0..``label``): MSSD, MSPD and VSD of every matched pair go into a second
+        buffer at the running offset and ``result`` gains a ``"bop"`` entry; ``depth_test``: float32 [B,H,W] measured depth in the
+        model's unit for VSD's visibility.  Without ``bop`` nothing changes."""
         dev = self.device
         _check_draw_into("DeviceEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
         _check_meshes("DeviceEvaluator.add", meshes, draw_into, dev, self.max_detections)
+        bop_size = _check_bop("DeviceEvaluator.add", bop, depth_test, frames, dev, self.label + 1)
         for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
             if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
                 raise ValueError(f"DeviceEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
@@ -548,6 +581,11 @@ class DeviceEvaluator:
             self.label, self.score_threshold, self.max_detections, self.iou_threshold,
             self._records[o:].data_ptr(), self._scores[o:].data_ptr(), self._tp[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.count += B
+        if bop is not None:
+            # the scene layout of this evaluator's records: every image is an annotation of ``label``; slot 1 matched and 2 the row as they are
+            rec = self._records[o:o + B].clone()[:, None, :]
+            rec[..., 0], rec[..., 12] = 1.0, float(self.label)
+            _score_bop(self, bop, bop_size, g[:, None, :], d, rec, [self.diameter] * (self.label + 1), depth_test, o, B, 1)
         if meshes is not None:
             _blend_models(draw_into, meshes, g, d, self.score_threshold, self.max_detections)
         if draw_into is not None:
@@ -569,7 +607,12 @@ class DeviceEvaluator:
         m = None
         if r.shape[0]:
             m = dict(add=r[:, 5], add_s=r[:, 6], t_diff=r[:, 7], r_diff=r[:, 8], tip=r[:, 9], reproj=r[:, 10], hand=r[:, 11][~np.isnan(r[:, 11])])
-        return metric_summary(float(n), [float(v) for v in sc[keep]], tp[keep], m, self.diameter * self.diameter_threshold, symmetric=self.symmetric)
+        out = metric_summary(float(n), [float(v) for v in sc[keep]], tp[keep], m, self.diameter * self.diameter_threshold, symmetric=self.symmetric)
+        if self._bop_count:
+            scene = rec.copy()[:, None, :]
+            scene[..., 0], scene[..., 12] = 1.0, float(self.label)
+            out["bop"] = _bop_result(self, "DeviceEvaluator.result", scene, [self.diameter] * (self.label + 1))
+        return out
 
 
 def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
@@ -731,19 +774,25 @@ class SceneEvaluator:
         self._records, self._scores = part(0, torch.float64, C, A, RECORD_DOUBLES), part(1, torch.float32, C, M)
         self._tp, self._labels, self._counts = part(2, torch.int32, C, M), part(3, torch.int32, C, M), part(4, torch.int32, C)
         self.count = 0
+        self._bop_buf, self._bop_count, self._bop_width = None, 0, 0      # ``add(..., bop=)``: errors [C,amax,2+T] float64, allocated on first use
 
     def reset(self) -> None:
-        self.count = 0
+        self.count = self._bop_count = 0
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None) -> None:
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None, bop=None,
+            depth_test: Optional[torch.Tensor] = None) -> None:
         """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6];
         ``gt`` float64 [B,amax,88] (``gt_scene_table``); all on the evaluator's device.  Everything is checked on the host before the
         library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.  ``draw_into``: as for
         ``DeviceEvaluator.add`` - every valid annotation and every kept detection, each with its label's cuboid.  ``meshes``: as for
-        ``DeviceEvaluator.add``, one mesh per label."""
+        ``DeviceEvaluator.add``, one mesh per label.  ``bop``: a ``bop.BopSettings`` over the evaluator's labels: MSSD, MSPD and VSD
+        (tau = the label's diameter times each tau fraction) of every matched (annotation, detection) pair go into a second buffer at
+        the running offset, and ``result`` gains a ``"bop"`` entry with one extra copy; ``depth_test``: float32 [B,H,W] measured depth
+        in the model's unit, one image per frame, for VSD's visibility.  Without ``bop`` nothing changes: same launches, same bytes."""
         dev = self.device
         _check_draw_into("SceneEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
         _check_meshes("SceneEvaluator.add", meshes, draw_into, dev, self.max_detections)
+        bop_size = _check_bop("SceneEvaluator.add", bop, depth_test, frames, dev, self.num_labels)
         for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
             if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
                 raise ValueError(f"SceneEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
@@ -777,6 +826,8 @@ class SceneEvaluator:
             self.score_threshold, self.max_detections, self.iou_threshold, self._records[o:].data_ptr(), self._scores[o:].data_ptr(),
             self._tp[o:].data_ptr(), self._labels[o:].data_ptr(), self._counts[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         self.count += B
+        if bop is not None:
+            _score_bop(self, bop, bop_size, g, d, self._records[o:o + B], self.diameters, depth_test, o, B, self.amax)
         if meshes is not None:
             _blend_models(draw_into, meshes, g[:, 0], d, self.score_threshold, self.max_detections)
         if draw_into is not None:
@@ -791,8 +842,11 @@ class SceneEvaluator:
         host = self._buf.cpu().numpy()
         C, M, A, n = self.capacity, self.max_detections, self.amax, self.count
         part = lambda k, dt, *shape: host[self._cut[k]:self._cut[k + 1]].view(dt).reshape(*shape)[:n]
-        return summarise_scene(part(0, np.float64, C, A, RECORD_DOUBLES), part(1, np.float32, C, M), part(2, np.int32, C, M), part(3, np.int32, C, M),
-                               part(4, np.int32, C), self.diameters, self.symmetric, self.diameter_threshold)
+        out = summarise_scene(part(0, np.float64, C, A, RECORD_DOUBLES), part(1, np.float32, C, M), part(2, np.int32, C, M), part(3, np.int32, C, M),
+                              part(4, np.int32, C), self.diameters, self.symmetric, self.diameter_threshold)
+        if self._bop_count:
+            out["bop"] = _bop_result(self, "SceneEvaluator.result", part(0, np.float64, C, A, RECORD_DOUBLES), self.diameters)
+        return out
 
 
 def summarise_scene(rec: np.ndarray, sc: np.ndarray, tp: np.ndarray, labels: np.ndarray, counts: np.ndarray, diameters: Sequence[float],
@@ -841,6 +895,7 @@ class SceneFolder:
             models = yaml.load(f, Loader=loader)
         self.models = [(load_ply_vertices(os.path.join(self.model_path, f"obj_{o:02}.ply")), float(models[o]["diameter"]),
                         any(k.startswith("symmetries") for k in models[o])) for o in self.object_ids]
+        self.models_info = [models[o] for o in self.object_ids]                              # ``bop.symmetry_transforms`` reads the symmetries
         boxes = [_model_cuboid(models[o]) for o in self.object_ids]
         self.cuboids = np.stack(boxes) if all(c is not None for c in boxes) else None      # float32 [labels,8,3], or None without min_* / size_*
         names = sorted(n for n in os.listdir(os.path.join(self.object_path, "rgb"))
@@ -884,13 +939,19 @@ class SceneFolder:
 def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
                           iou_threshold: float = 0.5, diameter_threshold: float = 0.1, batch_size: int = 16,
                           device: Optional[torch.device] = None, save_path: Optional[str] = None, draw_hand: bool = False,
-                          draw_bbox_2d: bool = False, draw_model: bool = False) -> Dict[str, dict]:
+                          draw_bbox_2d: bool = False, draw_model: bool = False, bop: bool = False, max_sym_disc_step: float = 0.01) -> Dict[str, dict]:
     """A ``SceneFolder`` through a ``SceneEvaluator``, driven like ``evaluate_device``: one forward and one scoring launch per batch,
     one host synchronisation for the whole folder.  Returns ``SceneEvaluator.result()``.  ``save_path``, ``draw_hand``,
     ``draw_bbox_2d``, ``draw_model``: as for ``evaluate_device`` - every annotation and every kept detection of a frame, each with its
-    label's cuboid (and, with ``draw_model``, every kept detection's filled model)."""
+    label's cuboid (and, with ``draw_model``, every kept detection's filled model).  ``bop``: MSSD, MSPD and VSD of every matched pair
+    and their average recalls as ``result()["bop"]`` (``bop.BopSettings`` built from the folder's ``models/``: the PLY meshes, which
+    need triangle faces, and the symmetries of models_info.yml in steps of ``max_sym_disc_step``; no measured depth is read)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     n = len(dataset)
+    settings = None
+    if bop:
+        from .bop import folder_settings
+        settings = folder_settings("evaluate_scene_device", dataset.model_path, dataset.object_ids, dataset.models_info, device, max_sym_disc_step)
     layers = _capi.DRAW_CUBOID | (_capi.DRAW_HAND if draw_hand else 0) | (_capi.DRAW_BOX2D if draw_bbox_2d else 0)
     if save_path is not None and dataset.cuboids is None:
         raise ValueError("evaluate_scene_device: save_path needs the model cuboids (min_* / size_* in models_info.yml)")
@@ -909,7 +970,7 @@ def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_th
         u8 = torch.from_numpy(np.stack(frames)).to(device)
         cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
         gt = torch.from_numpy(gt_scene_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale, dataset.amax)).to(device)
-        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes)
+        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes, bop=settings)
         if save_path is not None:
             save_frames(save_path, idx, u8)
     return ev.result()
@@ -935,6 +996,9 @@ def main(argv=None):
     ap.add_argument("--draw-bbox-2d", action="store_true", help="with --save-images: the 2D boxes as well")
     ap.add_argument("--draw-model", action="store_true", help="with --save-images: the filled model of every kept detection under its pose, beneath the "
                     "lines (the folder's PLY files need triangle faces)")
+    ap.add_argument("--bop", action="store_true", help="with --object-ids: MSSD, MSPD and VSD of every matched pair and their average recalls "
+                    "(the folder's PLY files need triangle faces; symmetries from models_info.yml)")
+    ap.add_argument("--max-sym-disc-step", type=float, default=0.01, help="with --bop: the step of continuous symmetries (at most 64 transforms per object)")
     a = ap.parse_args(argv)
     from . import HMDEgoPose, TrainModelWithLoss, load_pack, strip_checkpoint_prefix
     size = int(str(a.img_size).split(",")[0])
@@ -948,11 +1012,17 @@ def main(argv=None):
     model = TrainModelWithLoss(m.to("cuda").eval()).eval()
     if ids:
         res = evaluate_scene_device(SceneFolder(a.dataset_path, ids, fold=a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size,
-                                    save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d, draw_model=a.draw_model)
+                                    save_path=a.save_images, draw_hand=a.draw_hand, draw_bbox_2d=a.draw_bbox_2d, draw_model=a.draw_model,
+                                    bop=a.bop, max_sym_disc_step=a.max_sym_disc_step)
         for name, d in [(f"object {o}", res["labels"][l]) for l, o in enumerate(ids)] + [("mean", res["mean"])]:
             print(name)
             for k, v in d.items():
                 print(f"{k:>28s}: {v:.6g}")
+        if a.bop:
+            for name, d in [(f"object {o} (BOP)", res["bop"]["labels"][l]) for l, o in enumerate(ids)] + [("mean (BOP)", res["bop"]["mean"])]:
+                print(name)
+                for k, v in d.items():
+                    print(f"{k:>28s}: {v:.6g}")
         return res
     if a.save_images or a.draw_model:             # the drawing runs on the GPU path (the host ``evaluate`` does not draw)
         res = evaluate_device(LinemodFolder(a.dataset_path, a.object_id, a.fold), model, size, score_threshold=a.score_threshold, batch_size=a.batch_size,

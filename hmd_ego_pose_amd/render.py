@@ -97,13 +97,13 @@ def load_ply_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
 
 class MeshSet:
     """The triangle meshes of labels 0..L-1 concatenated and uploaded once: ``vertices`` float32 [V,3] and ``faces`` int32 [F,3] on the
-    device (face indices offset into the common vertex array), ``face_start`` host int32 [L+1].  ``meshes_per_label``: a sequence of
+    device (face indices offset into the common vertex array), ``face_start`` and ``vertex_start`` host int32 [L+1].  ``meshes_per_label``: a sequence of
     (vertices [v,3], faces [f,3]) pairs, e.g. ``load_ply_mesh`` results.  Every index is checked here, on the host."""
 
     def __init__(self, meshes_per_label: Sequence[Tuple[np.ndarray, np.ndarray]], device: Optional[torch.device] = None):
         if not 1 <= len(meshes_per_label) <= _capi.SCORE_MAX_LABELS:
             raise ValueError(f"MeshSet: {len(meshes_per_label)} labels: must be 1..{_capi.SCORE_MAX_LABELS}")
-        vs, fs, start, off = [], [], [0], 0
+        vs, fs, start, vstart, off = [], [], [0], [0], 0
         for l, (v, f) in enumerate(meshes_per_label):
             v, f = np.asarray(v), np.asarray(f)
             if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1 or not np.issubdtype(v.dtype, np.floating):
@@ -116,12 +116,14 @@ class MeshSet:
             fs.append(f.astype(np.int64) + off)
             off += v.shape[0]
             start.append(start[-1] + f.shape[0])
+            vstart.append(off)
         if off > MAX_ELEMENTS or start[-1] > MAX_ELEMENTS:
             raise ValueError(f"MeshSet: {off} vertices and {start[-1]} faces: at most {MAX_ELEMENTS} of each")
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.host_vertices = np.ascontiguousarray(np.concatenate(vs))
         self.host_faces = np.ascontiguousarray(np.concatenate(fs).astype(np.int32))
         self.face_start = np.ascontiguousarray(np.asarray(start, np.int32))
+        self.vertex_start = np.ascontiguousarray(np.asarray(vstart, np.int32))      # label l owns vertices [vertex_start[l], vertex_start[l+1])
         self.num_labels, self.num_vertices, self.num_faces = len(meshes_per_label), off, int(start[-1])
         self.vertices = torch.from_numpy(self.host_vertices).to(self.device)
         self.faces = torch.from_numpy(self.host_faces).to(self.device)

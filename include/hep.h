@@ -455,6 +455,61 @@ int hep_render_models_device(const double* poses, int batch, int pmax, const dou
                              const uint8_t* colours /* HOST [num_labels][3], or NULL without frames */, int alpha,
                              void* workspace, int64_t workspace_bytes, void* stream);
 
+/* BOP pose errors of matched (ground truth, estimate) pairs: MSSD and MSPD over a model's vertices and its set of symmetry transforms
+ * from one entry point, VSD over rendered depth maps from a second.  Stateless like hep_render_models_device: no handle, no allocation, no
+ * host synchronisation, asynchronous on `stream`.  This is BOP's mssd, mspd and vsd (bop19 visibility rule, step cost) RESTATED with this
+ * library's own roundings: tests/_bop.py states them in numpy and IS the definition.  bop_toolkit is not part of this project's
+ * environment: parity with it is UNPINNED, as it is for cv2.  Out of scope: BOP's error-based matching, the tlinear cost, depth PNGs.
+ * pairs: device, float64 [n][HEP_BOP_PAIR_DOUBLES = 32], one row per pair:
+ *   0      valid (0 / 1)                 4-12   R_gt, the rotation MATRIX row-major         16-24  R_est
+ *   1      label                         13-15  t_gt                                        25-27  t_est
+ *   2      image index (VSD's depth_test)                                                   28-31  fx, fy, cx, cy
+ *   3      reserved
+ *   A row is skipped and all of its outputs are NaN (its counts -1) when slot 0 is 0, when the label is outside 0..num_labels-1 (NaN
+ *   included; the label is then truncated to an integer) or when a NaN sits anywhere in slots 4-27.
+ * symmetries: device, float64 [num_symmetries][12], R row-major then t; symmetry_start: HOST, int32 [num_labels + 1], copied into the
+ *   kernel argument: label c owns the transforms symmetry_start[c] .. symmetry_start[c+1], 1..HEP_BOP_MAX_SYMMETRIES = 64 of them.  Entry
+ *   0 of every label must be the identity: hmd_ego_pose_amd.bop.SymmetrySet guarantees it, the ABI cannot see device memory.
+ * vertices: device, float32 [num_vertices][3]; vertex_start: HOST, int32 [num_labels + 1]: label c owns vertex_start[c] .. vertex_start[c+1].
+ * POINT ERRORS, float64, no contraction.  For pair i and symmetry s: R' = R_gt R_s, t' = R_gt t_s + t_gt, each element
+ *   ((a0 b0 + a1 b1) + a2 b2) [+ t].  For vertex v widened: p = ((R0 v0 + R1 v1) + R2 v2) + t under the estimate, q alike under (R', t').
+ *   mssd2(s) = max over v of ((dx dx + dy dy) + dz dz) with d = p - q; MSSD = sqrt(min over s of mssd2(s)): max and min are taken on the
+ *   squared values - the selection is exact and independent of the order - and one sqrt comes at the end.  MSPD is the same with
+ *   u = (fx X) / Z + cx, v = (fy Y) / Z + cy and du du + dv dv.  If any vertex has Z <= 0 (tested as not Z > 0) under the estimate or under any
+ *   (R', t'), the pair's MSPD is NaN; MSSD is unaffected.  A NaN squared distance (non-finite input) makes the error it belongs to NaN.
+ *   errors: float64 [n][2] MSSD, MSPD.  One workgroup per pair.
+ * VSD.  depth_gt, depth_est: device, float32 [n][height][width]: what hep_render_models_device writes with batch = n and pmax = 1 for
+ *   the pair's two poses, 0 where nothing is rendered.  depth_test: device, float32 [num_images][height][width] in the model's unit, 0 where
+ *   there is no measurement, or NULL; pair i reads image slot 2; with a depth_test a row whose slot 2 is outside 0..num_images-1 is skipped
+ *   too.  delta and taus (HOST, float64 [num_taus], 1..HEP_BOP_MAX_TAUS = 16) are in the model's unit.
+ *   With zg, ze, zt the three depths of pixel (x, y) widened to float64 (zt = 0 without depth_test):
+ *     a = (x - cx) / fx, b = (y - cy) / fy, k2 = (a a + b b) + 1: the squared ratio of distance-from-camera to depth - no sqrt anywhere;
+ *     far(zm, zr, d): false when zm - zr <= 0, else k2 ((zm - zr)(zm - zr)) > d d;
+ *     visible(zm): zm > 0 and (zt == 0 or not far(zm, zt, delta));  vis_gt = visible(zg);  vis_est = visible(ze) or (vis_gt and ze > 0);
+ *     inter = vis_gt and vis_est, union = vis_gt or vis_est;  a pixel of inter costs 1 at tau when k2 ((zg - ze)(zg - ze)) >= tau tau;
+ *     VSD(tau) = (cost_count(tau) + (union_count - inter_count)) / union_count, one float64 division of exactly converted integers;
+ *     1.0 when union_count is 0.
+ *   vsd: float64 [n][num_taus].  counts: int32 [n][2 + num_taus] union_count, inter_count, cost_count per tau.  The counters are summed in
+ *   the caller's workspace (hep_bop_workspace_bytes: n * (2 + num_taus) * 4 bytes rounded up to 16, or a negative hep_status; 16-byte
+ *   aligned) with integer atomics after a zeroing launch: the sums do not depend on the order.
+ * Never writes outside errors [0 .. 2 n), vsd [0 .. n num_taus), counts [0 .. n (2 + num_taus)) and the workspace's stated bytes.
+ * Checked before any HIP call, HEP_ERR_INVALID with the reason in hep_last_error: a NULL pointer (except depth_test and stream); n < 1;
+ * num_labels outside 1..63; num_vertices or num_symmetries < 1; a start table that starts below 0, does not increase or ends past its
+ * array; more than 64 symmetries for a label; num_taus outside 1..16; a tau or delta that is not finite and positive; num_images < 1 with a
+ * depth_test; a workspace that is misaligned or too small.  height or width outside 16..4096: HEP_ERR_UNSUPPORTED. */
+#define HEP_BOP_PAIR_DOUBLES 32
+#define HEP_BOP_MAX_SYMMETRIES 64
+#define HEP_BOP_MAX_TAUS 16
+int hep_bop_point_errors_device(const double* pairs, int n, const float* vertices, int num_vertices,
+                                const int32_t* vertex_start /* HOST [num_labels + 1] */,
+                                const double* symmetries, int num_symmetries, const int32_t* symmetry_start /* HOST [num_labels + 1] */,
+                                int num_labels, double* errors, void* stream);
+int64_t hep_bop_workspace_bytes(int n, int num_taus);
+int hep_bop_vsd_device(const double* pairs, int n, int num_labels, const float* depth_gt, const float* depth_est,
+                       const float* depth_test /* or NULL */, int num_images, int height, int width, double delta,
+                       const double* taus /* HOST [num_taus] */, int num_taus, double* vsd, int32_t* counts,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Training side: anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 with the IoU
  * matrix of generators/utils/compute_overlap.pyx:33-73 and bbox_transform anchors.py:422-458, on device memory: per
  * image the ground-truth boxes [batch][kmax][4] (float64 x1,y1,x2,y2; the first num_gt[b] are valid), their labels,
