@@ -404,7 +404,8 @@ def emulated_stages(sd: Mapping[str, torch.Tensor], phi: int, q_act=q_bf16, q_w=
     @torch.no_grad()
     def stem(x):
         s, sh = _fold(sd, bb + "._bn0")
-        return E.qa(swish(conv_same(x.float(), sd[bb + "._conv_stem.conv.weight"] * s[:, None, None, None], sh, stride=2)))
+        x = x if x.dtype == torch.float64 else x.float()        # (a float64 state dict with float64 inputs runs every stage in float64)
+        return E.qa(swish(conv_same(x, sd[bb + "._conv_stem.conv.weight"] * s[:, None, None, None], sh, stride=2)))
 
     @torch.no_grad()
     def block(i, y):

@@ -53,12 +53,15 @@ ZERO_PATTERN = {
 
 
 @contextlib.contextmanager
-def batch_statistics(record=None):
+def batch_statistics(record=None, observe=None):
     """``oracle.efficientpose_ref.bn`` as training-mode BatchNorm.  The running statistics of the state dict are cloned, never
-    written; ``record`` (a dict) receives the updated clones under their state_dict keys."""
+    written; ``record`` (a dict) receives the updated clones under their state_dict keys; ``observe(prefix, x)`` sees every
+    BatchNorm's input."""
     from oracle import efficientpose_ref as R
 
     def bn(sd, p, x):
+        if observe is not None:
+            observe(p, x.detach())
         rm, rv = sd[p + ".running_mean"].detach().clone(), sd[p + ".running_var"].detach().clone()
         y = F.batch_norm(x, rm, rv, sd[p + ".weight"], sd[p + ".bias"], True, MOMENTUM, EPS)
         if record is not None:
@@ -114,14 +117,15 @@ def inputs(part, case):
     return [image], cots
 
 
-def oracle(part, sd, case, dtype, argmax=None):
+def oracle(part, sd, case, dtype, argmax=None, statistics="batch", observe=None):
     """The patched oracle in ``dtype`` on the CPU: dict(outs, grads {key: grad of every trainable tensor}, gin [input gradients],
     stats {running key: the buffer after the forward}, pool).  Neck: ``argmax`` routes the max-pools and ``pool`` is the
-    tests/_neck_grad.RoutedPool that did it (its slack and scale lists)."""
+    tests/_neck_grad.RoutedPool that did it (its slack and scale lists).  ``statistics`` "running": the oracle as it is (eval-mode
+    BatchNorm, no stats); ``observe``: see ``batch_statistics``."""
     phi, classes = case[0], case[4]
     x, cots = inputs(part, case)
     stats, pool = {}, None
-    with batch_statistics(stats):
+    with batch_statistics(stats, observe) if statistics == "batch" else contextlib.nullcontext():
         if part == "heads":
             outs, grads, gin = H.oracle_grads(sd, x, cots, phi, classes, dtype)
         elif part == "neck":
@@ -159,6 +163,21 @@ def group_errors(got, ref, zeros):
         out["fusion"] = max(float(np.abs(_np(got["grads"][k]) - _np(ref["grads"][k])).max()) for k in fusion) / fscale
     out["zeros"] = max(float(np.abs(_np(got["grads"][k])).max()) for k in zeros) if zeros else 0.0
     return out
+
+
+def tensor_errors(got, ref, zeros):
+    """Error against the float64 ``ref`` PER TENSOR, name -> e: every output ("out.<i>"), every input gradient ("input.<i>") and
+    every trainable tensor outside ``zeros``, each max |a - b| / max |b|; the neck's fusion scalars on their one common scale
+    (``group_errors``).  A tensor whose gradient nearly cancels then widens only its own bound."""
+    errs = {f"out.{i}": H.rel_err(_np(a), _np(b)) for i, (a, b) in enumerate(zip(got["outs"], ref["outs"]))}
+    errs.update({f"input.{i}": H.rel_err(_np(a), _np(b)) for i, (a, b) in enumerate(zip(got["gin"], ref["gin"]))})
+    fusion = [k for k in ref["grads"] if N.is_fusion(k) and k not in zeros]
+    fscale = max([float(np.abs(_np(ref["grads"][k])).max()) for k in fusion] or [1.0])
+    for k, v in ref["grads"].items():
+        if k in zeros:
+            continue
+        errs[k] = float(np.abs(_np(got["grads"][k]) - _np(v)).max()) / fscale if N.is_fusion(k) else H.rel_err(_np(got["grads"][k]), _np(v))
+    return errs
 
 
 def stat_errors(got, ref):

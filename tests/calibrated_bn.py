@@ -20,28 +20,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def calibrate(phi, seed, size, frames):
-    import torch
     from hmd_ego_pose_amd.weights import seeded_state_dict
-    from oracle import efficientpose_ref as R
-    sd = dict(seeded_state_dict(phi, seed))
-    rng = np.random.Generator(np.random.PCG64([seed, 0xCA1B]))             # calibration frames: not the frames any test evaluates
-    x = torch.from_numpy(rng.standard_normal((frames, 3, size, size)).astype(np.float32))
-    stats = {}
-    plain_bn = R.bn
-
-    def measuring_bn(sd_, p, t):
-        m = t.mean(dim=(0, 2, 3)); v = t.var(dim=(0, 2, 3), unbiased=False)
-        sd_[p + ".running_mean"] = m.clone(); sd_[p + ".running_var"] = v.clone()
-        stats[p + ".running_mean"] = m.numpy().copy(); stats[p + ".running_var"] = v.numpy().copy()
-        return plain_bn(sd_, p, t)
-
-    R.bn = measuring_bn
-    try:
-        with torch.no_grad():
-            R.forward(sd, x, phi)
-    finally:
-        R.bn = plain_bn
-    return stats
+    from tests import _hard_values
+    # (the measuring pass itself lives in tests/_hard_values.py, which calibrates any state dict)
+    return {k: v.numpy().copy() for k, v in _hard_values.calibrate(seeded_state_dict(phi, seed), phi, size, frames, seed).items()}
 
 
 def calibrated_state_dict(phi, seed=0, size=256, frames=8):

@@ -153,16 +153,53 @@ def _check_bf16(label, got, want, max_tol=BF16_TOL_MAX, mean_tol=BF16_TOL_MEAN):
         assert (max_tol is None or emax <= max_tol) and emean <= mean_tol, (label, k, emax, emean)
 
 
-def _teacher_forced_bf16(api, sd, phi, size, batch, x, ref, strict=True, precision="bf16", block_max_tol=BF16_TOL_MAX):
+def _stage_images(s, batch, images):
+    """stage ("stem", "block<i>", "cell<r>", "heads") -> the images of the batch the oracle evaluates it on.  ``images``: None (the
+    whole batch), a list, or "plan": per stage what _images_to_check picks for the launches the session's own plan runs for it."""
+    if images is None:
+        return lambda stage: slice(None)
+    if images != "plan":
+        return lambda stage: list(images)
+    by_stage = {}
+    for name, y in _plan_syms(s, batch):
+        for stage in _launch_stages(name):
+            by_stage.setdefault(stage, set()).add(y)
+    pixels = lambda n: s.stage(n, 1).shape[1] * s.stage(n, 1).shape[2]
+
+    def pick(stage):
+        maps = []
+        if stage.startswith("block"):        # the expand GEMM runs over the input map, the project GEMM over the output map
+            i = int(stage[5:])
+            maps = [pixels(f"block{i - 1}" if i else "stem"), pixels(stage)]
+        return _images_to_check(batch, by_stage.get(stage, ()), maps)
+    return pick
+
+
+def _stage_reader(s, batch, whole_batch_finite):
+    """name -> the device's stage tensor as NCHW fp32, the whole batch (``whole_batch_finite``: asserted finite before a caller
+    picks images from it)."""
+    def dev(name):
+        t = s.stage(name, batch).permute(0, 3, 1, 2).contiguous()
+        finite = not whole_batch_finite or bool(torch.isfinite(t).all())
+        assert finite, f"stage {name}: non-finite values on the device"
+        return t
+    return dev
+
+
+def _teacher_forced_bf16(api, sd, phi, size, batch, x, ref, strict=True, precision="bf16", block_max_tol=BF16_TOL_MAX, images=None):
     """bf16 (or fp8) session vs the emulating oracle, stage by stage on the device's own stage inputs; ``block_max_tol``
-    is the max bound of the backbone stages (fp8 sessions: one flipped e4m3 rounding is 2^-4 of an element)."""
+    is the max bound of the backbone stages (fp8 sessions: one flipped e4m3 rounding is 2^-4 of an element).  ``images``: the
+    images the oracle evaluates (_stage_images; the device always runs the batch, and every value of the batch is then asserted
+    finite); ``ref`` None leaves out the end-to-end report (it needs the oracle on the whole batch)."""
     R = api["R"]
     s = api["Session"](sd, phi, size, batch, precision, flags=api["capi"].FLAG_KEEP_INTERMEDIATES)
     out = s.forward(x.cuda())
     torch.cuda.synchronize()
     got = dict(zip(HEADS, [t.float().cpu() for t in out[1:]]))
+    assert images is None or all(torch.isfinite(t).all() for t in got.values()), "non-finite head values on the device"
     st = R.emulated_stages(sd, phi, q_pw=R.make_q_pw_fp8(s.fp8_scales()) if precision == "fp8" else None)
-    dev = lambda name: s.stage(name, batch).permute(0, 3, 1, 2).contiguous()       # the device's tensor as NCHW fp32 (bf16 values)
+    dev = _stage_reader(s, batch, images is not None)       # the device's tensor as NCHW fp32 (bf16 values)
+    pick = _stage_images(s, batch, images)
     label = f"phi {phi} @ {size} b{batch} {precision}"
     y = dev("stem")
     # strict (BASELINE configurations): BF16_TOL_MAX / BF16_TOL_MEAN per stage; the heads are D + 1 separable convs deep
@@ -177,21 +214,28 @@ def _teacher_forced_bf16(api, sd, phi, size, batch, x, ref, strict=True, precisi
     #  magnitude depending on the plan of the BACKBONE in front of it (the cell's input differs in its last bits), i.e. one
     #  bf16 ulp per element and a noisy statistic over 3072 values.  2.5x the bound there; BASELINE configurations keep 1x.)
     cell_tol = dict(max_tol=BF16_TOL_MAX, mean_tol=BF16_TOL_MEAN) if strict else dict(max_tol=None, mean_tol=2.5 * BF16_TOL_MEAN)
-    _check_bf16(label, {"stem": y}, {"stem": st["stem"](x)}, **tol)
+    idx = pick("stem")
+    _check_bf16(label, {"stem": y[idx]}, {"stem": st["stem"](x[idx])}, **tol)
     blocks = []
     for i in range(st["n_blocks"]):
-        want = st["block"](i, y)
+        idx = pick(f"block{i}")
+        want = st["block"](i, y[idx])
         y = dev(f"block{i}")
-        _check_bf16(label, {f"block{i}": y}, {f"block{i}": want}, **tol)
+        _check_bf16(label, {f"block{i}": y[idx]}, {f"block{i}": want}, **tol)
         blocks.append(y)
     feats = [blocks[t] for t in st["taps"]]
     for r in range(st["n_cells"]):
-        want = st["cell"](r, feats)
+        idx = pick(f"cell{r}")
+        want = st["cell"](r, [f[idx] for f in feats])
         feats = [dev(f"c{r}.p{l + 3}_out") for l in range(5)]
-        _check_bf16(label, {f"c{r}.p{l + 3}_out": f for l, f in enumerate(feats)}, {f"c{r}.p{l + 3}_out": w for l, w in enumerate(want)}, **cell_tol)
+        _check_bf16(label, {f"c{r}.p{l + 3}_out": f[idx] for l, f in enumerate(feats)}, {f"c{r}.p{l + 3}_out": w for l, w in enumerate(want)}, **cell_tol)
     for l, f in enumerate(out[0]):      # exported feature maps = the last BiFPN cell
         assert torch.equal(f.float().cpu(), feats[l])
-    _check_bf16(label, got, dict(zip(HEADS, st["heads"](feats))), **head_tol)
+    idx = pick("heads")
+    _check_bf16(label, {k: v[idx] for k, v in got.items()}, dict(zip(HEADS, st["heads"]([f[idx] for f in feats]))), **head_tol)
+    if ref is None:
+        s.close()
+        return
     # end to end: the distance between two bf16 realisations is of the size of the bf16 drift itself (chaotic
     # amplification of rounding flips, see the module docstring): reported, and bounded by 2x the drift
     emu = R.forward_emulated(sd, x, phi, q_pw=R.make_q_pw_fp8(s.fp8_scales()) if precision == "fp8" else None)
@@ -211,18 +255,24 @@ FP32_STAGE_TOL = 2e-5
 FP32_HEAD_TOL = 5e-4
 
 
-def _teacher_forced_fp32(api, sd, phi, size, batch, x):
+def _teacher_forced_fp32(api, sd, phi, size, batch, x, images=None, on_stage=None, oracle_sd=None):
     """fp32 session against the fp32 oracle STAGE BY STAGE on the device's own stage inputs (the oracle's stage functions with identity
     rounding).  End to end the seeded deep networks amplify summation-order differences (phi 4: ~1e-3 at the sigmoid); cut into stages
     nothing amplifies, so every kernel of every width is held to fp32 rounding level - a gate that does not depend on how the seeded
-    gains were tuned.  Returns the worst stage error."""
+    gains were tuned.  Returns the worst stage error.  ``images``: the images the oracle evaluates (_stage_images; the device always
+    runs the batch, and every stage of the whole batch is then asserted finite); ``oracle_sd``: the weights the oracle runs on, when
+    they are a float64 copy of ``sd`` the oracle runs in float64; ``on_stage(kind, index, inputs, got, want)`` is called per stage
+    after its gate, with the stage's device input and name -> tensor dicts."""
     R = api["R"]
     ident = lambda t: t
     s = api["Session"](sd, phi, size, batch, "fp32", flags=api["capi"].FLAG_KEEP_INTERMEDIATES)
     out = s.forward(x.cuda())
     torch.cuda.synchronize()
-    st = R.emulated_stages(sd, phi, q_act=ident, q_w=ident)
-    dev = lambda name: s.stage(name, batch).permute(0, 3, 1, 2).contiguous()
+    ref_sd = sd if oracle_sd is None else oracle_sd
+    rdt = ref_sd["backbone_net.model._bn0.weight"].dtype
+    st = R.emulated_stages(ref_sd, phi, q_act=ident, q_w=ident)
+    dev = _stage_reader(s, batch, images is not None)
+    pick = _stage_images(s, batch, images)
     worst = [0.0, ""]
 
     worst_head = [0.0, ""]
@@ -235,22 +285,34 @@ def _teacher_forced_fp32(api, sd, phi, size, batch, x):
             w[0], w[1] = err, name
         assert err <= tol, f"phi {phi} @ {size} fp32 stage {name}: {err:.3e} (bound {tol:g})"
 
+    def stage(kind, index, inputs, got, want, tol=FP32_STAGE_TOL):
+        for k in want:
+            check(k, got[k], want[k], tol)
+        if on_stage:
+            on_stage(kind, index, inputs, got, want)
+
     y = dev("stem")
-    check("stem", y, st["stem"](x))
+    idx = pick("stem")
+    stage("stem", 0, x[idx], {"stem": y[idx]}, {"stem": st["stem"](x[idx].to(rdt))})
     blocks = []
     for i in range(st["n_blocks"]):
-        want = st["block"](i, y)
-        y = dev(f"block{i}")
-        check(f"block{i}", y, want)
+        idx = pick(f"block{i}")
+        want = st["block"](i, y[idx].to(rdt))
+        src, y = y, dev(f"block{i}")
+        stage("block", i, src[idx], {f"block{i}": y[idx]}, {f"block{i}": want})
         blocks.append(y)
     feats = [blocks[t] for t in st["taps"]]
     for r in range(st["n_cells"]):
-        want = st["cell"](r, feats)
+        idx = pick(f"cell{r}")
+        src = [f[idx] for f in feats]
+        want = st["cell"](r, [f.to(rdt) for f in src])
         feats = [dev(f"c{r}.p{l + 3}_out") for l in range(5)]
-        for l in range(5):
-            check(f"c{r}.p{l + 3}_out", feats[l], want[l])
-    for name, g, w in zip(HEADS, out[1:], st["heads"](feats)):
-        check(name, g.float().cpu(), w, FP32_HEAD_TOL)
+        stage("cell", r, src, {f"c{r}.p{l + 3}_out": feats[l][idx] for l in range(5)}, {f"c{r}.p{l + 3}_out": want[l] for l in range(5)})
+    idx = pick("heads")
+    src = [f[idx] for f in feats]
+    heads = [g.float().cpu() for g in out[1:]]
+    assert images is None or all(torch.isfinite(g).all() for g in heads), "non-finite head values on the device"
+    stage("heads", 0, src, {k: g[idx] for k, g in zip(HEADS, heads)}, dict(zip(HEADS, st["heads"]([f.to(rdt) for f in src]))), FP32_HEAD_TOL)
     s.close()
     print(f"phi {phi} @ {size} b{batch} fp32 teacher-forced: worst backbone / BiFPN stage {worst[1]} {worst[0]:.2e}, worst head {worst_head[1]} {worst_head[0]:.2e}")
     return worst[0], worst_head[0]
