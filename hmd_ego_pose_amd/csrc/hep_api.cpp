@@ -77,6 +77,28 @@ void launch_op(const Session& s, const Op& op, int batch, hipStream_t st, const 
   }
 }
 
+// the device function launch_op runs for `op` and how (hep_pick.h): the family's own pick, which reads what the planner set
+Pick op_pick(const Op& op) {
+  switch (op.kind) {
+    case OP_STEM: return stem_pick(op.stem);
+    case OP_PW: return pw_pick(op.pw);
+    case OP_DW: return dw_pick(op.dw);
+    case OP_POOL: return pool_pick(op.pool);
+    case OP_PWG: return pwg_pick(op.pwg);
+    case OP_MBF: return mbf_pick(op.mbf);
+    case OP_CHAIN: return chain_pick(op.chain);
+    case OP_SE: return se_finish_pick(op.se);
+    case OP_XBF: return xbf_pick(op.xbf);
+#ifdef HEP_ALT
+    case OP_LATE: return late_pick(op.late);
+    case OP_HEADS: return heads_pick(op.heads);
+    case OP_SBF: return sbf_pick(op.sbf);
+#endif
+    case OP_SEP: return op.sep.direct ? tower_pick(op.sep) : sep_pick(op.sep);
+    default: return Pick();
+  }
+}
+
 // forward = per lane: ops[0] (stem, eager: its input pointer belongs to the caller) + the rest inside
 // ONE hipGraph whose lanes are parallel branches (fork/join captured through events)
 int run_forward(Session* s, const float* in_dev, const int64_t* strides, int batch, hipStream_t st, std::string* err) {
@@ -1162,56 +1184,12 @@ int hep_calibrate_fp8(hep_handle* h, const float* frames_nchw_device, int batch)
   return calibrate_fp8(s, frames_nchw_device, batch);
 } HEP_CATCH_INT
 
-// the device function (as rocprofv3 --kernel-trace names it) that launch_op runs for `o` in session `s`: host arithmetic only
-static std::string kernel_symbol(const Session& s, const Op& o) {
-  const char* t = s.dtype ? "true" : "false";
-  const int prec = o.kind == OP_PW ? (o.pw.fp8 ? 2 : (s.dtype ? 1 : 0)) : 0;
-  char tmp[128];
-  switch (o.kind) {
-    case OP_STEM: if (o.stem.mfma) snprintf(tmp, sizeof tmp, "stem_kernel<%s, %d>", t, (o.stem.Cout + 15) / 16);
-                  else snprintf(tmp, sizeof tmp, "stem_valu_kernel<%s>", t);
-                  break;
-    case OP_PW: { const int sev = pw_se_variant(o.pw);
-                  const bool w8 = o.pw.nwv == 8 && prec == 0 && o.pw.mode == 2 && o.pw.act != ACT_SWISH && (sev == 0 || sev == 3) && o.pw.NT <= 2;
-                  // (the names rocprofv3 prints: bench.py looks the PMC traffic of a device function up by this string)
-                  const bool fr = o.pw.frag && prec != 2 && o.pw.MT == 2 && o.pw.NT <= PW_FRAG_MAX_NT && o.pw.mode == 2 && sev >= 1 && o.pw.act != ACT_SWISH;      // (launch_nt: fragment-ordered operands)
-                  snprintf(tmp, sizeof tmp, fr ? "pw_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, true>" : "pw_gemm_kernel<%d, %d, %d, %d, %d, %d, %d>", prec, o.pw.MT, o.pw.NT, o.pw.mode, o.pw.act == ACT_SWISH ? 1 : 0, sev, (w8 || (fr && o.pw.nwv == 8 && prec == 0 && sev == 3 && o.pw.NT <= 2)) ? 8 : 4); break; }
-    case OP_DW: snprintf(tmp, sizeof tmp, "dw_kernel<%s, %d, %d, %d>", t, o.dw.k, o.dw.s, o.dw.TW); break;
-    case OP_POOL: snprintf(tmp, sizeof tmp, "pool_kernel<%s>", t); break;
-    case OP_PWG: snprintf(tmp, sizeof tmp, "pw_group_kernel<%s>", t); break;
-    case OP_CHAIN: if (const int id = chain_shape_id(o.chain)) snprintf(tmp, sizeof tmp, "chain_shape_kernel<true, %d>", id);      // (the row of chain_shape(), k_chain_impl.h)
-                   else snprintf(tmp, sizeof tmp, "chain_kernel<%s, %d>", o.chain.bf16 ? "true" : "false", o.chain.stream_w);
-                   break;
-    case OP_SE: snprintf(tmp, sizeof tmp, "se_finish_kernel<%s>", t); break;
-    case OP_MBF: { const int mp = o.mbf.has_expand && o.mbf.npass > 1 ? (o.mbf.mp_resident ? 2 : 1) : 0;      // (1 / 2 = multi-pass expand)
-                   if (const int id = mbf_shape_id(o.mbf)) snprintf(tmp, sizeof tmp, "mbf_shape_kernel<%s, %d, %d, %d, %d, %d>", t, o.mbf.k, o.mbf.s, o.mbf.ts, mp, id);   // (last argument: the row of MBF_SHAPES)
-                   else snprintf(tmp, sizeof tmp, "mbf_kernel<%s, %d, %d, %d, %s, %d>", t, o.mbf.k, o.mbf.s, o.mbf.ts, o.mbf.fp8 ? "true" : "false", mp);
-                   break; }
-#ifdef HEP_ALT
-    case OP_SBF: snprintf(tmp, sizeof tmp, "sbf_kernel<%s>", t); break;
-    case OP_LATE: snprintf(tmp, sizeof tmp, "late_kernel"); break;
-    case OP_HEADS: snprintf(tmp, sizeof tmp, "heads_kernel"); break;
-#endif
-    case OP_XBF: { const int sp = xbf_specialised(o.xbf);
-                   if (const int id = xbf_shape_id(o.xbf)) snprintf(tmp, sizeof tmp, "xbf_kernel_shape<true, %d>", id);      // (the row of XBF_SHAPES, k_xbf_impl.h)
-                   else snprintf(tmp, sizeof tmp, "xbf_kernel<%s, %d, %d, %d, %d, %d, %d, %d>", t, o.xbf.k, o.xbf.s, o.xbf.toh, o.xbf.tow, o.xbf.NT1, sp ? o.xbf.K1 : 0, sp ? o.xbf.NT2 : 0); break; }
-    default: if (o.sep.direct) snprintf(tmp, sizeof tmp, "%s<%s, %d, %s>", o.sep.coop ? "tower_coop_kernel" : "tower_kernel", t, o.sep.C, o.sep.direct == 2 ? "true" : "false");
-             else {
-               const int mode = o.sep.chain ? 2 : (o.sep.nseg == 1 ? 0 : 1);
-               const bool wl = o.sep.bf16 && o.sep.off_wpw && mode != 1;         // (launch_sep: staged pointwise weights)
-               if (const int id = mode == 0 ? sep_shape_id(o.sep) : 0) snprintf(tmp, sizeof tmp, "sep_shape_kernel<true, %d>", id);      // (the row of SEP_SHAPES, k_sep_impl.h)
-               else if (mode == 0 && sep_w8(o.sep)) snprintf(tmp, sizeof tmp, "sep_kernel<%s, 0, false, true>", t);
-               else snprintf(tmp, sizeof tmp, wl ? "sep_kernel<%s, %d, true, false>" : "sep_kernel<%s, %d, false, false>", t, mode);
-             }
-             break;
-  }
-  return tmp;
-}
-
+// the device function (as rocprofv3 --kernel-trace names it) that launch_op runs for launch i: the name of its pick, host arithmetic only
+// (bench.py looks the PMC traffic of a device function up by this string)
 int hep_kernel_symbol(const hep_handle* h, int i, const char** symbol) try {
   if (!h || !symbol || i < 0 || i >= (int)h->s.ops.size()) return fail(HEP_ERR_INVALID, "bad kernel index");
   static thread_local std::string buf;
-  buf = kernel_symbol(h->s, h->s.ops[i]); *symbol = buf.c_str();
+  buf = op_pick(h->s.ops[i]).name(); *symbol = buf.c_str();
   return 0;
 } HEP_CATCH_INT
 
@@ -1237,7 +1215,7 @@ int hep_plan_launch_list(const void* pack, size_t pack_bytes, int phi, int size,
   Plan plan; plan.layout_only = true;               // the launch list needs the ops, not the weight blob they would point into
   if (int rc = plan_session(&s, pk, &plan, &err)) return fail(rc, err);
   std::string text;
-  for (const Op& o : s.ops) { text += kernel_symbol(s, o); text += " | "; text += o.name; text += '\n'; }
+  for (const Op& o : s.ops) { text += op_pick(o).name(); text += " | "; text += o.name; text += '\n'; }
   if (needed) *needed = text.size() + 1;
   if (out) {
     if (capacity < text.size() + 1) return fail(HEP_ERR_INVALID, "hep_plan_launch_list: the output buffer is smaller than *needed");

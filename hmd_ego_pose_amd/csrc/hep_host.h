@@ -117,6 +117,7 @@ struct Session {
 
 int build_session(Session* s, const Pack& pack, std::string* err);
 void launch_op(const Session& s, const Op& op, int batch, hipStream_t st, const float* in, const int64_t* strides);   // batch frames starting at `in`
+Pick op_pick(const Op& op);          // the device function launch_op runs for `op` (hep_pick.h); empty: none is built - plan_session refuses such a plan
 int run_forward(Session* s, const float* in_dev, const int64_t* strides, int batch, hipStream_t st, std::string* err);
 int host_anchors(int size, std::vector<float>* anchors, std::vector<float>* tanchors);
 

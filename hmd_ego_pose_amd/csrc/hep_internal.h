@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hep_pick.h"      // Pick: which device function a launch runs; one *_pick(const Args&) per kernel family below
+
 struct hep_sync;      // include/hep.h: the sum hook of synchronised BatchNorm
 struct GDSyncFailed { int rc; };      // thrown by a launch function whose hook returned rc != 0 (grad_dev.h); caught at the ABI
 
@@ -46,10 +48,11 @@ struct SbfArgs {
 };
 void sbf_layout(SbfArgs* a);                     // fills tiles and the LDS layout from the shapes
 void launch_sbf(const SbfArgs&, hipStream_t);
+Pick sbf_pick(const SbfArgs&);
 #endif
 
-// widest split-K tile (n-tiles per workgroup) the fragment-ordered GEMM is instantiated for: the planner (add_pw), the launcher (launch_nt)
-// and hep_kernel_symbol all test against THIS constant - a fragment-ordered tensor handed to a row-major instantiation would be misread
+// widest split-K tile (n-tiles per workgroup) the fragment-ordered GEMM is instantiated for: the planner (add_pw) and the pick
+// (pw_pick_nt, k_pw_impl.h) test against THIS constant - a fragment-ordered tensor handed to a row-major instantiation would be misread
 #ifdef HEP_ALT
 constexpr int PW_FRAG_MAX_NT = 8;      // (HEP_PW_WIDE)
 #else
@@ -75,7 +78,7 @@ struct PwArgs {
   int mode;            // wave arrangement inside a workgroup: 0 along M, 1 along N, 2 split-K (k_pw.hip)
   int nwv;             // waves per workgroup: 4; 8 for the split-K project convs of fp32 sessions (k_pw_impl.h)
   int frag;            // A and W are stored in MFMA fragment order ([tile][k-step][lane][8]: k_pw_impl.h FRAG; the front kernel wrote A that way)
-  int chunksN; uint32_t chunksN_rcp;   // filled by launch_pw_prec: workgroups along N and rcp_u32() of that
+  int chunksN; uint32_t chunksN_rcp;   // filled by launch_pw: workgroups along N and rcp_u32() of that
   unsigned long long* trace_buf;   // profiling builds (-DHEP_PW_TRACE): stamps of this launch go here
 };
 
@@ -100,6 +103,7 @@ struct SeFinishArgs {
   int B, C, sq, sqp, rows, bf16; float inv_hw;
 };
 void launch_se_finish(const SeFinishArgs&, hipStream_t);
+Pick se_finish_pick(const SeFinishArgs&);
 
 // ---- fused MBConv front: expand 1x1 (+BN,swish) -> depthwise kxk (+BN,swish) -> SE partial sums ----
 struct MbfArgs {
@@ -158,8 +162,7 @@ size_t xbf_layout(XbfArgs* a);                   // fills the LDS offsets / chun
 int xbf_supports(int k, int s);                  // tile instantiations
 void xbf_tile(int k, int s, int* toh, int* tow);
 void launch_xbf(const XbfArgs&, hipStream_t);
-int xbf_prepare(void);
-int xbf_specialised(const XbfArgs&);          // 1: a width-specialised instantiation exists (names the device function)
+Pick xbf_pick(const XbfArgs&);                // the instantiation launch_xbf runs: shape row, width-specialised or generic
 int xbf_shape_id(const XbfArgs&);             // > 0: the row of XBF_SHAPES (k_xbf_impl.h) whose xbf_kernel_shape runs this launch; 0: an xbf_kernel
 
 #ifdef HEP_ALT
@@ -207,8 +210,8 @@ struct LateArgs {
 };
 int late_layout(LateArgs* a);      // fills the LDS offsets from the blocks' shapes; returns lds_bytes, 0 when the run does not fit
 int late_block_supported(int Cin, int Cexp, int N, int k, int stride, int H, int W, int sq);
-int late_prepare(void);
 void launch_late(const LateArgs&, hipStream_t);
+Pick late_pick(const LateArgs&);
 
 // ---- the five head towers depth-first (k_heads.hip): tower layers + headers of every (net, level) as ONE launch ----
 struct HeadItem {               // one workgroup per image: a 16x16 output tile of one (net, level); a table of these opens the blob
@@ -228,8 +231,8 @@ struct HeadsArgs {
 };
 int heads_fused_supported(int C, int depth, int bf16);
 int heads_lds_bytes(int depth, int* off_wdw);
-int heads_prepare(void);
 void launch_heads(const HeadsArgs&, hipStream_t);
+Pick heads_pick(const HeadsArgs&);
 #endif   // HEP_ALT
 
 // ---- 3x3 s2 max-pool, TF-SAME with ZERO padding (utils_extra.py:72-86) ----
@@ -290,8 +293,8 @@ struct ChainArgs {
   size_t off_w, off_halo, off_atile, lds_bytes;
 };
 void launch_chain(const ChainArgs&, hipStream_t);
+Pick chain_pick(const ChainArgs&);                // the instantiation launch_chain runs: shape row or generic
 int chain_shape_id(const ChainArgs&);            // > 0: the row of chain_shape() (k_chain_impl.h) whose chain_shape_kernel runs this launch; 0: the generic chain_kernel
-int chain_prepare(void);
 
 // ---- decode: boxes + translation from raw heads (loss.py:12-51) ----
 struct DecodeArgs {
@@ -638,22 +641,30 @@ void launch_backbone_forward(const BGPlan&, const float* params, const float* im
 void launch_backbone_backward(const BGPlan&, const float* const grad_taps[3], const float* branch_scale, float* grad_params, float* grad_image, float* ws,
                               hipStream_t, const hep_sync* sync = nullptr);
 
+// launch_X(args) finishes the arguments (reciprocals, grid) and launches X_pick(args): the pick reads only fields the planner sets, so it
+// can be asked for a launch's device function before any session exists (hep_kernel_symbol, plan_session's check of the plan)
 void launch_stem(const StemArgs&, hipStream_t);
+Pick stem_pick(const StemArgs&);
 int stem_uses_mfma(int cout, int force = -1);      // which of the two stem kernels the plan takes (force: Knobs::stem_mfma, -1 = by width)
 void launch_pw(const PwArgs&, hipStream_t);
-int pw_se_variant(const PwArgs&);   // 0 none, 1 shallow, 2 deep (template parameter of pw_gemm_kernel)
+Pick pw_pick(const PwArgs&);
 void launch_pwg(const PwgArgs&, hipStream_t);
+Pick pwg_pick(const PwgArgs&);
 void launch_dw(const DwArgs&, hipStream_t);
+Pick dw_pick(const DwArgs&);
 void launch_pool(const PoolArgs&, hipStream_t);
+Pick pool_pick(const PoolArgs&);
 void launch_mbf(const MbfArgs&, hipStream_t);
+Pick mbf_pick(const MbfArgs&);
 size_t mbf_lds_layout(int Cin, int CC, int k, int s, int bf16, int has_expand, int max_inside, int ts, MbfArgs* a, int kp = 0);
 int mbf_mp_fits(int CC, int kp, int bf16, int max_inside, int ts);     // the multi-pass plan fits the kernel's compile-time budgets
 int mbf_mp_resident(int Cin, int CC, int max_inside, int ts);          // ... with the whole tile held in registers
 int mbf_max_inside(int H, int W, int k, int s, int pad_t, int pad_l, int ts);
-int mbf_prepare(void);
 int mbf_shape_id(const MbfArgs&);                // > 0: the row of MBF_SHAPES (k_mbf_impl.h) whose mbf_shape_kernel runs this launch; 0: the generic mbf_kernel
 void launch_sep(const SepArgs&, hipStream_t);
+Pick sep_pick(const SepArgs&);
 void launch_tower(const SepArgs&, hipStream_t);
+Pick tower_pick(const SepArgs&);      // empty for a width outside tower_supports() or a cooperative form that is not built
 #define TOWER_BIAS_MAX 384       // bias floats staged per segment: >= 16 * n-tiles of any segment (24 map tiles, 12 per header chunk)
 // n-tiles (16 columns) per header segment of k_tower.hip; wider headers are split into segments.  As many as keep the
 // segment's pointwise weights in LDS (TOWER_WLDS_MAX bytes, rows padded by 16 bytes) next to the depthwise weights and the
@@ -678,8 +689,8 @@ constexpr int tower_hdr_tiles(int C, bool bf16, int cap = 6) {
 // head's last map and its input are then computed / read once, not once per 12-tile chunk
 // (the wide bf16 layers keep segments of up to 12 tiles: with 6 phi 3 @ 512 loses 1.8 %, 5618 -> 5519 frames/s)
 constexpr int tower_coop_hdr_tiles(int C, bool bf16) { return bf16 && C == 64 ? 36 : tower_hdr_tiles(C, bf16, 12); }
-int tower_prepare(void);         // raises the dynamic-LDS limit of the tower kernels (call once per device)
-int tower_coop_supported(int C, int bf16);   // widths / dtypes tower_coop_kernel is instantiated for
+// the tower widths / dtypes tower_coop_kernel is instantiated for: k_tower.hip builds exactly these, the planner asks before it selects the form
+constexpr bool tower_coop_built(bool bf16, int C) { return bf16 ? (C >= 160 || C == 64) : C == 64; }
 int tower_supports(int C);       // BiFPN widths k_tower.hip is instantiated for
 int tower_map_tiles(int C);      // n-tiles (even) of a map layer: its weight rows are permuted, see k_tower.hip
 void launch_decode(const DecodeArgs&, hipStream_t);
@@ -691,5 +702,3 @@ void launch_amax_bf16(const void* x, int64_t n, unsigned* out /* float bits, zer
 int dw_blocks_per_image(int Ho, int Wo, int C, int TW);
 void sep_lds_layout(int C, int bf16, int ts, int max_cols_f32, int max_cols_map, SepArgs* a, int stage_w = 0);   // stage_w: single nodes / chains of map-to-map nodes may keep their pointwise weights in LDS
 int sep_shape_id(const SepArgs&);   // > 0: the row of SEP_SHAPES (k_sep_impl.h) whose sep_shape_kernel runs this launch; 0: a generic sep_kernel
-int sep_w8(const SepArgs&);   // launch_sep picks the eight-wave single-node instantiation (k_sep.hip)
-int sep_prepare(void);   // raises the dynamic-LDS limit of the sepconv kernels (call once per device)

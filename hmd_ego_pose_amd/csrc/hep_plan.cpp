@@ -726,7 +726,7 @@ struct Planner {
     // on tower_kernel: 113 against 118 us - its segments have 1-10 n-tiles for five waves), fp32 at width 64 (24.7k -> 25.7k).
     // HEP_TOWER_COOP: 0 off, 1 on wherever instantiated, 2 map layers only, 3 headers only
     int coop = 0;
-    if (direct && tower_coop_supported(C, s->dtype != 0)) {
+    if (direct && tower_coop_built(s->dtype != 0, C)) {      // (direct: C is a tower width)
       const int v = kn.tower_coop;
       // bf16 below width 160 stays on tower_kernel.  At width 64 (instantiated for the A/B, bit-identical): map layers 16 against 13.3 us, the
       // header launch - the hand head as one 36-tile segment on eight waves - 47.6 against 27.3 us; 49.0k against 49.7k frames/s with both:
@@ -1366,6 +1366,9 @@ int plan_session(Session* s, const Pack& pack, Plan* plan, std::string* err) {
   for (int l = 0; l < 5; l++) s->feat_ids[l] = feat[l];
   P.add_heads(feat);
   if (!P.ok) return HEP_ERR_PACK;
+  // every launch has a device function: a tower width that is not built, a cooperative form that is not, a shape id without a row
+  for (const Op& o : s->ops)
+    if (!op_pick(o).fn) { *err = "plan: no kernel instantiation is built for launch '" + o.name + "'"; return HEP_ERR_INTERNAL; }
 
   // ---- liveness, then the arena ----
   const int nops = (int)s->ops.size();

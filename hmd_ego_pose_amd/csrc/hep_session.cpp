@@ -41,14 +41,14 @@ int build_session(Session* s, const Pack& pack, std::string* err) {
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { *err = std::string(#x) + ": " + hipGetErrorString(e_); return HEP_ERR_DEVICE; } } while (0)
   HIPCHK(hipSetDevice(s->device));
-  const struct { int (*prepare)(); const char* kernel; } dynamic_lds[] = {
-    {mbf_prepare, "mbf_kernel"}, {xbf_prepare, "xbf_kernel"}, {chain_prepare, "chain_kernel"}, {tower_prepare, "tower_kernel"}, {filter_prepare, "filter_kernel"}, {sep_prepare, "sep_kernel"},
-#ifdef HEP_ALT
-    {heads_prepare, "heads_kernel"}, {late_prepare, "late_kernel"},
-#endif
-  };
-  for (const auto& k : dynamic_lds)
-    if (k.prepare() != 0) { *err = std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for ") + k.kernel; return HEP_ERR_DEVICE; }
+  // dynamic LDS beyond the default limit: raised for the device functions this plan launches (their picks say how far), and for the detection filter
+  for (const Op& o : s->ops) {
+    const Pick p = op_pick(o);
+    if (p.max_lds && hipFuncSetAttribute(p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, p.max_lds) != hipSuccess) {
+      *err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for " + p.name() + " (" + o.name + ")"; return HEP_ERR_DEVICE;
+    }
+  }
+  if (filter_prepare() != 0) { *err = "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for filter_kernel"; return HEP_ERR_DEVICE; }
   HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
   s->weights_bytes = plan.weights.size();
   HIPCHK(hipMalloc((void**)&s->d_weights, s->weights_bytes));

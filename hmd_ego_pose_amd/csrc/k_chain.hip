@@ -30,8 +30,7 @@
 #include "k_chain_impl.h"
 
 // k_chain_shape.hip
-int chain_shape_prepare(void);
-bool launch_chain_shape(int id, const ChainArgs&, dim3 grid, hipStream_t);
+Pick chain_shape_pick(int id, const ChainArgs&);
 void chain_shape_trace_bind(unsigned long long* p);
 
 #ifdef HEP_MBF_TRACE
@@ -44,14 +43,6 @@ extern "C" int hep_dbg_chain_trace(unsigned long long* host, int nblocks, int en
   return 0;
 }
 #endif
-
-template <bool BF16, int WMODE> static int chain_prep_one() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel<BF16, WMODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-}
-int chain_prepare(void) {
-  return chain_prep_one<true, 0>() | chain_prep_one<true, 1>() | chain_prep_one<true, 2>() | chain_prep_one<false, 0>() | chain_prep_one<false, 1>() | chain_prep_one<false, 2>() |
-         chain_shape_prepare();
-}
 
 // the row of chain_shape() (k_chain_impl.h) whose kernel runs this launch: every field the kernel folds must equal the row, the
 // external-map table included; 0 = the generic kernel (no such row, or the plan asked for it: HEP_NECK_GENERIC)
@@ -70,19 +61,17 @@ int chain_shape_id(const ChainArgs& a) {
   return 0;
 }
 
+// the instantiation a launch runs (hep_pick.h): its shape row when it has one, else the generic kernel of its dtype and weight mode
+Pick chain_pick(const ChainArgs& a) {
+  if (const int id = chain_shape_id(a)) return chain_shape_pick(id, a);
+#define CHAIN_PICK(...) HEP_PICK(CHAIN_THREADS, a.lds_bytes, 159 * 1024, chain_kernel, __VA_ARGS__)
+  if (a.bf16) return a.stream_w == 2 ? CHAIN_PICK(true, 2) : (a.stream_w == 1 ? CHAIN_PICK(true, 1) : CHAIN_PICK(true, 0));
+  return a.stream_w == 2 ? CHAIN_PICK(false, 2) : (a.stream_w == 1 ? CHAIN_PICK(false, 1) : CHAIN_PICK(false, 0));
+#undef CHAIN_PICK
+}
+
 void launch_chain(const ChainArgs& a_, hipStream_t s) {
   ChainArgs a = a_;
   a.nt_rcp = rcp_u32((uint32_t)((a.C + 15) >> 4));
-  const dim3 g(a.B), b(CHAIN_THREADS);
-  if (const int id = chain_shape_id(a))
-    if (launch_chain_shape(id, a, g, s)) return;
-  if (a.bf16) {
-    if (a.stream_w == 2) hipLaunchKernelGGL((chain_kernel<true, 2>), g, b, a.lds_bytes, s, a);
-    else if (a.stream_w == 1) hipLaunchKernelGGL((chain_kernel<true, 1>), g, b, a.lds_bytes, s, a);
-    else hipLaunchKernelGGL((chain_kernel<true, 0>), g, b, a.lds_bytes, s, a);
-  } else {
-    if (a.stream_w == 2) hipLaunchKernelGGL((chain_kernel<false, 2>), g, b, a.lds_bytes, s, a);
-    else if (a.stream_w == 1) hipLaunchKernelGGL((chain_kernel<false, 1>), g, b, a.lds_bytes, s, a);
-    else hipLaunchKernelGGL((chain_kernel<false, 0>), g, b, a.lds_bytes, s, a);
-  }
+  chain_pick(a).launch(dim3(a.B), s, a);
 }

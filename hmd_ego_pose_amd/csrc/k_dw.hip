@@ -214,6 +214,16 @@ __global__ __launch_bounds__(256) void stem_valu_kernel(StemArgs a) {
 //  stems wider than 64 channels have no MFMA instantiation and keep the VALU form)
 int stem_uses_mfma(int cout, int force) { return cout <= 64 && (force >= 0 ? force != 0 : cout > 32); }      // force: Knobs::stem_mfma (-1 = by width)
 
+Pick stem_pick(const StemArgs& a) {
+  if (!a.mfma) return a.bf16 ? HEP_PICK(256, 0, 0, stem_valu_kernel, true) : HEP_PICK(256, 0, 0, stem_valu_kernel, false);
+  switch ((a.Cout + 15) >> 4) {     // (stem widths are 32 .. 64)
+#define STEM_CASE(N) case N: return a.bf16 ? HEP_PICK(256, 0, 0, stem_kernel, true, N) : HEP_PICK(256, 0, 0, stem_kernel, false, N);
+    STEM_CASE(1) STEM_CASE(2) STEM_CASE(3) STEM_CASE(4)
+#undef STEM_CASE
+  }
+  return Pick();
+}
+
 void launch_stem(const StemArgs& a_, hipStream_t s) {
   StemArgs a = a_;
   // Measured (b16 / b8, stand-alone): phi 0 (32 channels) bf16 MFMA 18.5-19.7 us, VALU 14.5 us; fp32 22.2 / 20.2 us;
@@ -221,18 +231,14 @@ void launch_stem(const StemArgs& a_, hipStream_t s) {
   // pipe saves on the narrow stem; it wins once the VALU form needs a fifth channel group.  HEP_STEM_MFMA=0|1 overrides.
   if (!a.mfma) {
     dim3 grid((unsigned)((a.Wo + 63) / 64), (unsigned)((a.Ho + 3) / 4), (unsigned)a.B);
-    if (a.bf16) hipLaunchKernelGGL(stem_valu_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(stem_valu_kernel<false>, grid, dim3(256), 0, s, a);
+    stem_pick(a).launch(grid, s, a);
     return;
   }
   const int TX = (a.Wo + 15) >> 4, total = a.B * a.Ho * TX;
   a.mpw = 2;                     // m-tiles per wave (measured 1 / 2 / 3 / 4 / 8: 21.2 / 18.5 / 21.4 / 19.7 / 26.1 us at phi 0)
   a.tx_rcp = rcp_u32((uint32_t)TX); a.ho_rcp = rcp_u32((uint32_t)a.Ho);
   dim3 grid((unsigned)((total + 4 * a.mpw - 1) / (4 * a.mpw)));
-  const int nt = (a.Cout + 15) >> 4;
-#define STEM_CASE(N) case N: if (a.bf16) hipLaunchKernelGGL((stem_kernel<true, N>), grid, dim3(256), 0, s, a); else hipLaunchKernelGGL((stem_kernel<false, N>), grid, dim3(256), 0, s, a); break;
-  switch (nt) { STEM_CASE(1) STEM_CASE(2) STEM_CASE(3) STEM_CASE(4) default: break; }     // (stem widths are 32 .. 64)
-#undef STEM_CASE
+  stem_pick(a).launch(grid, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -445,28 +451,30 @@ int dw_blocks_per_image(int Ho, int Wo, int C, int TW) {
 }
 
 template <bool BF16, int KS, int S>
-static void launch_dw_tw(const DwArgs& a, dim3 grid, hipStream_t s) {
+static Pick dw_pick_tw(const DwArgs& a) {
   const size_t lds = ((size_t)(KS * KS + 1) * a.C + 256 * 9 + a.C) * sizeof(float);
   switch (a.TW) {
-    case 1: hipLaunchKernelGGL((dw_kernel<BF16, KS, S, 1>), grid, dim3(256), lds, s, a); break;
-    case 2: hipLaunchKernelGGL((dw_kernel<BF16, KS, S, 2>), grid, dim3(256), lds, s, a); break;
-    default: hipLaunchKernelGGL((dw_kernel<BF16, KS, S, 4>), grid, dim3(256), lds, s, a); break;
+    case 1: return HEP_PICK(256, lds, 0, dw_kernel, BF16, KS, S, 1);
+    case 2: return HEP_PICK(256, lds, 0, dw_kernel, BF16, KS, S, 2);
+    default: return HEP_PICK(256, lds, 0, dw_kernel, BF16, KS, S, 4);
   }
 }
 template <bool BF16>
-static void launch_dw_t(const DwArgs& a, dim3 grid, hipStream_t s) {
-  if (a.k == 3 && a.s == 1) launch_dw_tw<BF16, 3, 1>(a, grid, s);
-  else if (a.k == 3 && a.s == 2) launch_dw_tw<BF16, 3, 2>(a, grid, s);
-  else if (a.k == 5 && a.s == 1) launch_dw_tw<BF16, 5, 1>(a, grid, s);
-  else launch_dw_tw<BF16, 5, 2>(a, grid, s);
+static Pick dw_pick_t(const DwArgs& a) {
+  if (a.k == 3 && a.s == 1) return dw_pick_tw<BF16, 3, 1>(a);
+  if (a.k == 3 && a.s == 2) return dw_pick_tw<BF16, 3, 2>(a);
+  if (a.k == 5 && a.s == 1) return dw_pick_tw<BF16, 5, 1>(a);
+  return dw_pick_tw<BF16, 5, 2>(a);
 }
+Pick dw_pick(const DwArgs& a) { return a.bf16 ? dw_pick_t<true>(a) : dw_pick_t<false>(a); }
+
 void launch_dw(const DwArgs& a_, hipStream_t s) {
   DwArgs a = a_;
   const uint32_t CG = (uint32_t)a.C >> 3, SW = (uint32_t)(a.Wo + a.TW - 1) / a.TW;
   a.cg_magic = (uint32_t)(0x100000000ull / CG) + 1; a.sw_magic = (uint32_t)(0x100000000ull / SW) + 1;
   a.c_magic = (uint32_t)(0x100000000ull / (uint32_t)a.C) + 1;
   dim3 grid(a.blocks_per_image, a.B);
-  if (a.bf16) launch_dw_t<true>(a, grid, s); else launch_dw_t<false>(a, grid, s);
+  dw_pick(a).launch(grid, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -484,11 +492,11 @@ __global__ __launch_bounds__(256) void se_finish_kernel(SeFinishArgs a) {
   const int c0 = blockIdx.y * per, c1 = min(a.C, c0 + per);
   se_finish_body<BF16, 256, false>(a, blockIdx.x, c0, c1, threadIdx.x, se_sm);      // (se_finish.h)
 }
-void launch_se_finish(const SeFinishArgs& a, hipStream_t s) {
+Pick se_finish_pick(const SeFinishArgs& a) {
   const size_t lds = ((size_t)a.sqp + 256 + a.sqp) * sizeof(float);
-  if (a.bf16) hipLaunchKernelGGL(se_finish_kernel<true>, dim3(a.B, SE_SPLIT), dim3(256), lds, s, a);
-  else hipLaunchKernelGGL(se_finish_kernel<false>, dim3(a.B, SE_SPLIT), dim3(256), lds, s, a);
+  return a.bf16 ? HEP_PICK(256, lds, 0, se_finish_kernel, true) : HEP_PICK(256, lds, 0, se_finish_kernel, false);
 }
+void launch_se_finish(const SeFinishArgs& a, hipStream_t s) { se_finish_pick(a).launch(dim3(a.B, SE_SPLIT), s, a); }
 
 // ------------------------------------------------------------------------------------------------
 // MaxPool2dStaticSamePadding(3,2): the pad value is ZERO, not -inf (reference
@@ -521,11 +529,11 @@ __global__ __launch_bounds__(256) void pool_kernel(PoolArgs a) {
     }
   Vec8<BF16>::store(a.out, idx * 8, m);
 }
+Pick pool_pick(const PoolArgs& a) { return a.bf16 ? HEP_PICK(256, 0, 0, pool_kernel, true) : HEP_PICK(256, 0, 0, pool_kernel, false); }
 void launch_pool(const PoolArgs& a, hipStream_t s) {
   const int64_t total = (int64_t)a.B * a.Ho * a.Wo * (a.C >> 3);
   dim3 grid((unsigned)((total + 255) / 256));
-  if (a.bf16) hipLaunchKernelGGL(pool_kernel<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(pool_kernel<false>, grid, dim3(256), 0, s, a);
+  pool_pick(a).launch(grid, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -231,10 +231,7 @@ int heads_lds_bytes(int depth, int* off_wdw) {
   return o + 3 * 576 * 4 + 16 * 2 * 1024;      // + the header operand fragments of 16 m-tiles
 }
 
-int heads_prepare(void) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(heads_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 0 : -1;
-}
+// (no template: the pick is spelled out, its name is the kernel's)
+Pick heads_pick(const HeadsArgs& a) { return Pick(reinterpret_cast<const void*>(&heads_kernel), "heads_kernel", 1024, (size_t)a.lds_bytes, 160 * 1024, {}); }
 
-void launch_heads(const HeadsArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(heads_kernel, dim3(a.B, a.nitems), dim3(1024), (size_t)a.lds_bytes, s, a);
-}
+void launch_heads(const HeadsArgs& a, hipStream_t s) { heads_pick(a).launch(dim3(a.B, a.nitems), s, a); }

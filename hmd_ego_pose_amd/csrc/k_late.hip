@@ -606,11 +606,10 @@ int late_layout(LateArgs* a) {
   return a->lds_bytes <= 160 * 1024 ? a->lds_bytes : 0;
 }
 
-int late_prepare(void) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(late_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 0 : -1;
-}
+// (no template: the pick is spelled out, its name is the kernel's)
+Pick late_pick(const LateArgs& a) { return Pick(reinterpret_cast<const void*>(&late_kernel), "late_kernel", LATE_THREADS, (size_t)a.lds_bytes, 160 * 1024, {}); }
 
 void launch_late(const LateArgs& a, hipStream_t s) {
   const int nwg = a.G > 1 && !a.cross_xcd ? ((a.B + 7) / 8) * 8 * a.G : a.B * a.G;
-  hipLaunchKernelGGL(late_kernel, dim3(nwg), dim3(LATE_THREADS), (size_t)a.lds_bytes, s, a);
+  late_pick(a).launch(dim3(nwg), s, a);
 }

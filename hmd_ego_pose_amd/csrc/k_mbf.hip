@@ -35,9 +35,7 @@
 #include "k_mbf_impl.h"
 
 // k_mbf_s16.hip, k_mbf_s8.hip
-int mbf_shape_prepare_16(void); int mbf_shape_prepare_8(void);
-bool launch_mbf_shape_16(int id, const MbfArgs&, dim3 grid, hipStream_t);
-bool launch_mbf_shape_8(int id, const MbfArgs&, dim3 grid, hipStream_t);
+Pick mbf_shape_pick_16(int id, const MbfArgs&); Pick mbf_shape_pick_8(int id, const MbfArgs&);
 void mbf_trace_bind_16(unsigned long long*); void mbf_trace_bind_8(unsigned long long*);
 
 #ifdef HEP_MBF_TRACE
@@ -104,28 +102,13 @@ int mbf_mp_resident(int Cin, int CC, int max_inside, int ts) {
   return Cin % 8 == 0 && items <= 6L * mbf_threads(ts);
 }
 
-template <bool BF16, int KS, int S, int TS>
-static int prep_one() {
-  int rc = hipFuncSetAttribute(reinterpret_cast<const void*>(mbf_kernel<BF16, KS, S, TS, false, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-  rc |= hipFuncSetAttribute(reinterpret_cast<const void*>(mbf_kernel<BF16, KS, S, TS, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-  rc |= hipFuncSetAttribute(reinterpret_cast<const void*>(mbf_kernel<BF16, KS, S, TS, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-#ifdef HEP_WITH_FP8
-  if constexpr (BF16) rc |= hipFuncSetAttribute(reinterpret_cast<const void*>(mbf_kernel<true, KS, S, TS, true, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-#endif
-  return rc;
-}
-int mbf_prepare(void) {
-  return prep_one<true, 3, 1, 8>() | prep_one<true, 3, 2, 8>() | prep_one<true, 5, 1, 8>() | prep_one<true, 5, 2, 8>() |
-         prep_one<false, 3, 1, 8>() | prep_one<false, 3, 2, 8>() | prep_one<false, 5, 1, 8>() | prep_one<false, 5, 2, 8>() |
-         prep_one<true, 3, 1, 16>() | prep_one<true, 5, 1, 16>() | prep_one<false, 3, 1, 16>() | prep_one<false, 5, 1, 16>() |
-         mbf_shape_prepare_16() | mbf_shape_prepare_8();
-}
+static int mbf_mp(const MbfArgs& a) { return a.has_expand && a.npass > 1 ? (a.mp_resident ? 2 : 1) : 0; }      // template parameter MP: 1 / 2 = multi-pass expand
 
 // the row of MBF_SHAPES (k_mbf_impl.h) whose kernel runs this launch: every field the kernel folds must equal the row; 0 = the
 // generic kernel (no such row, or the plan asked for it: HEP_MBF_GENERIC)
 int mbf_shape_id(const MbfArgs& a) {
   if (a.generic || a.fp8 || a.se_tail) return 0;
-  const int mp = a.has_expand && a.npass > 1 ? (a.mp_resident ? 2 : 1) : 0;
+  const int mp = mbf_mp(a);
 #define X(id, bf, ks, s_, ts_, mp_, cin, cexp, cc, h, w, ho, wo, pt, pl, sq_, sqp_, he, of) \
   if ((a.bf16 != 0) == bf && a.k == ks && a.s == s_ && a.ts == ts_ && mp == mp_ && a.Cin == cin && a.Cexp == cexp && a.CC == cc && a.H == h && a.W == w && \
       a.Ho == ho && a.Wo == wo && a.pad_t == pt && a.pad_l == pl && a.sq == sq_ && a.sqp == sqp_ && (a.has_expand != 0) == (he != 0) && (a.out_frag != 0) == (of != 0)) return id;
@@ -134,16 +117,26 @@ int mbf_shape_id(const MbfArgs& a) {
   return 0;
 }
 
+#define MBF_PICK(ks, s_, ts_) HEP_PICK(ts_ == 16 ? 1024 : 512, a.lds_bytes, 159 * 1024, mbf_kernel, BF16, ks, s_, ts_, F8, MP)
 template <bool BF16, bool F8, int MP>
-static void launch_mbf_t(const MbfArgs& a, dim3 grid, hipStream_t s) {
-  if (a.ts == 16) {       // stride 1 only (the planner never asks for 16x16 tiles on a stride-2 layer)
-    if (a.k == 3) hipLaunchKernelGGL((mbf_kernel<BF16, 3, 1, 16, F8, MP>), grid, dim3(1024), a.lds_bytes, s, a);
-    else hipLaunchKernelGGL((mbf_kernel<BF16, 5, 1, 16, F8, MP>), grid, dim3(1024), a.lds_bytes, s, a);
-  }
-  else if (a.k == 3 && a.s == 1) hipLaunchKernelGGL((mbf_kernel<BF16, 3, 1, 8, F8, MP>), grid, dim3(512), a.lds_bytes, s, a);
-  else if (a.k == 3 && a.s == 2) hipLaunchKernelGGL((mbf_kernel<BF16, 3, 2, 8, F8, MP>), grid, dim3(512), a.lds_bytes, s, a);
-  else if (a.k == 5 && a.s == 1) hipLaunchKernelGGL((mbf_kernel<BF16, 5, 1, 8, F8, MP>), grid, dim3(512), a.lds_bytes, s, a);
-  else hipLaunchKernelGGL((mbf_kernel<BF16, 5, 2, 8, F8, MP>), grid, dim3(512), a.lds_bytes, s, a);
+static Pick mbf_pick_t(const MbfArgs& a) {
+  if (a.ts == 16) return a.k == 3 ? MBF_PICK(3, 1, 16) : MBF_PICK(5, 1, 16);       // stride 1 only (the planner never asks for 16x16 tiles on a stride-2 layer)
+  if (a.k == 3 && a.s == 1) return MBF_PICK(3, 1, 8);
+  if (a.k == 3 && a.s == 2) return MBF_PICK(3, 2, 8);
+  if (a.k == 5 && a.s == 1) return MBF_PICK(5, 1, 8);
+  return MBF_PICK(5, 2, 8);
+}
+#undef MBF_PICK
+// the instantiation a launch runs (hep_pick.h): the fp8 fronts are single-pass, a launch whose every folded field equals a row of
+// MBF_SHAPES runs that row, everything else the generic kernel of its tap size, stride, tile and expand form
+Pick mbf_pick(const MbfArgs& a) {
+#ifdef HEP_WITH_FP8
+  if (a.bf16 && a.fp8) return mbf_pick_t<true, true, 0>(a);
+#endif
+  if (const int id = mbf_shape_id(a)) { const Pick p = mbf_shape_pick_16(id, a); return p.fn ? p : mbf_shape_pick_8(id, a); }
+  const int mp = mbf_mp(a);
+  if (a.bf16) return mp == 2 ? mbf_pick_t<true, false, 2>(a) : (mp == 1 ? mbf_pick_t<true, false, 1>(a) : mbf_pick_t<true, false, 0>(a));
+  return mp == 2 ? mbf_pick_t<false, false, 2>(a) : (mp == 1 ? mbf_pick_t<false, false, 1>(a) : mbf_pick_t<false, false, 0>(a));
 }
 void launch_mbf(const MbfArgs& a_, hipStream_t s) {
   MbfArgs a = a_;
@@ -159,14 +152,6 @@ void launch_mbf(const MbfArgs& a_, hipStream_t s) {
   dim3 grid(tiles * chunks, a.B);
   a.chunks = chunks; a.tiles_x = (a.Wo + a.ts - 1) / a.ts;
   a.chunks_rcp = rcp_u32(chunks); a.tiles_x_rcp = rcp_u32(a.tiles_x); a.gx_rcp = rcp_u32(grid.x);
-#ifdef HEP_WITH_FP8
-  if (a.bf16 && a.fp8) { launch_mbf_t<true, true, 0>(a, grid, s); return; }
-#endif
-  const int mp = a.has_expand && a.npass > 1 ? (a.mp_resident ? 2 : 1) : 0;
-  a.vk_rcp = rcp_u32((uint32_t)std::max(1, a.Cin >> 3)); a.kpv_rcp = rcp_u32((uint32_t)std::max(1, a.kp >> 3));
-  if (const int id = mbf_shape_id(a)) {
-    if (launch_mbf_shape_16(id, a, grid, s) || launch_mbf_shape_8(id, a, grid, s)) return;
-  }
-  if (a.bf16) { if (mp == 2) launch_mbf_t<true, false, 2>(a, grid, s); else if (mp == 1) launch_mbf_t<true, false, 1>(a, grid, s); else launch_mbf_t<true, false, 0>(a, grid, s); }
-  else { if (mp == 2) launch_mbf_t<false, false, 2>(a, grid, s); else if (mp == 1) launch_mbf_t<false, false, 1>(a, grid, s); else launch_mbf_t<false, false, 0>(a, grid, s); }
+  a.vk_rcp = rcp_u32((uint32_t)std::max(1, a.Cin >> 3)); a.kpv_rcp = rcp_u32((uint32_t)std::max(1, a.kp >> 3));      // (read by the resident multi-pass form only)
+  mbf_pick(a).launch(grid, s, a);
 }

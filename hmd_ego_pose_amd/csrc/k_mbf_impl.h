@@ -725,24 +725,17 @@ __global__ __launch_bounds__(TS == 16 ? 1024 : 512) void mbf_kernel(MbfArgs a) {
 template <bool BF16, int KS, int S, int TS, int MP, int D>
 __global__ __launch_bounds__(TS == 16 ? 1024 : 512) void mbf_shape_kernel(MbfArgs a) { mbf_body<BF16, KS, S, TS, false, MP, D>(a); }
 
-// prepare / launch of the rows a translation unit instantiates (k_mbf_s16.hip, k_mbf_s8.hip): -1 / false when the row is not theirs
-#define MBF_SHAPE_TU(ROWS, PREPARE, LAUNCH, BIND) \
-  int PREPARE(void) { \
-    int rc = 0; \
-    ROWS(MBF_SHAPE_PREP_ROW) \
-    return rc; \
-  } \
-  bool LAUNCH(int id, const MbfArgs& a, dim3 grid, hipStream_t s) { \
+// the pick (hep_pick.h) of the rows a translation unit instantiates (k_mbf_s16.hip, k_mbf_s8.hip): empty when the row is not theirs
+#define MBF_SHAPE_TU(ROWS, PICK, BIND) \
+  Pick PICK(int id, const MbfArgs& a) { \
     switch (id) { \
-      ROWS(MBF_SHAPE_LAUNCH_ROW) \
-      default: return false; \
+      ROWS(MBF_SHAPE_PICK_ROW) \
+      default: return Pick(); \
     } \
   } \
   void BIND(unsigned long long* p) { MBF_TRACE_BIND_TU(p); }
-#define MBF_SHAPE_PREP_ROW(id, bf, ks, s_, ts, mp, ...) \
-  rc |= hipFuncSetAttribute(reinterpret_cast<const void*>(mbf_shape_kernel<bf, ks, s_, ts, mp, id>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-#define MBF_SHAPE_LAUNCH_ROW(id, bf, ks, s_, ts, mp, ...) \
-  case id: hipLaunchKernelGGL((mbf_shape_kernel<bf, ks, s_, ts, mp, id>), grid, dim3(ts == 16 ? 1024 : 512), a.lds_bytes, s, a); return true;
+#define MBF_SHAPE_PICK_ROW(id, bf, ks, s_, ts, mp, ...) \
+  case id: return HEP_PICK(ts == 16 ? 1024 : 512, a.lds_bytes, 159 * 1024, mbf_shape_kernel, bf, ks, s_, ts, mp, id);
 #ifdef HEP_MBF_TRACE
 #define MBF_TRACE_BIND_TU(p) mbf_trace_bind_tu(p)
 #else

@@ -2,4 +2,4 @@
 // own so that the library builds in the wall time it had (as k_pw_{bf16,f32}.hip).
 #include "k_mbf_impl.h"
 
-MBF_SHAPE_TU(MBF_SHAPES_16, mbf_shape_prepare_16, launch_mbf_shape_16, mbf_trace_bind_16)
+MBF_SHAPE_TU(MBF_SHAPES_16, mbf_shape_pick_16, mbf_trace_bind_16)

@@ -3,17 +3,14 @@
 #include "hep_dev.h"
 #include "hep_internal.h"
 
-template <int PREC> void launch_pw_prec(const PwArgs&, hipStream_t);
-extern template void launch_pw_prec<0>(const PwArgs&, hipStream_t);
-extern template void launch_pw_prec<1>(const PwArgs&, hipStream_t);
-extern template void launch_pw_prec<2>(const PwArgs&, hipStream_t);
+#include <stdio.h>
+#include <stdlib.h>
 
-// squeeze-excite prologue variant of a launch (also names the device function, hep_kernel_symbol)
-int pw_se_variant(const PwArgs& a) {
-  if (a.sq <= 0 || a.act == ACT_SWISH) return 0;          // (sq is set by the planner for project convs only)
-  if (a.se_from_tensor) return 3;
-  return (a.K > 256 || a.sqp / (a.bf16 ? 8 : 4) > 2) ? 2 : 1;
-}
+// k_pw_impl.h pw_pick_nt decides the instantiation; one explicit instantiation per precision's translation unit
+template <int PREC> Pick pw_pick_prec(const PwArgs&);
+extern template Pick pw_pick_prec<0>(const PwArgs&);
+extern template Pick pw_pick_prec<1>(const PwArgs&);
+extern template Pick pw_pick_prec<2>(const PwArgs&);
 
 #ifdef HEP_PW_TRACE
 unsigned long long* g_pw_trace_host = nullptr;
@@ -27,12 +24,23 @@ extern "C" int hep_dbg_pw_trace(unsigned long long* host, int max_waves, int ena
 }
 #endif
 
-void launch_pw(const PwArgs& a, hipStream_t s) {
+Pick pw_pick(const PwArgs& a) {
 #ifdef HEP_WITH_FP8
-  if (a.fp8) { launch_pw_prec<2>(a, s); return; }
+  if (a.fp8) return pw_pick_prec<2>(a);
 #endif
-  if (a.bf16) launch_pw_prec<1>(a, s);
-  else launch_pw_prec<0>(a, s);
+  return a.bf16 ? pw_pick_prec<1>(a) : pw_pick_prec<0>(a);
+}
+
+void launch_pw(const PwArgs& a_, hipStream_t s) {
+  const int per_block_n = a_.mode == 1 ? 4 * a_.NT : a_.NT;
+  const int chunksN = (a_.tilesN + per_block_n - 1) / per_block_n;
+  const int rows = a_.mode == 0 ? 64 * a_.MT : 16 * a_.MT;
+  dim3 grid(((a_.M + rows - 1) / rows) * chunksN);
+  PwArgs a = a_; a.chunksN = chunksN; a.chunksN_rcp = rcp_u32(chunksN);
+#ifdef HEP_PW_TRACE
+  { static const char* sel = getenv("HEP_PW_TRACE_SEL"); int k = 0, n = 0; if (sel) sscanf(sel, "%d,%d", &k, &n); a.trace_buf = sel && a.K == k && a.N == n ? g_pw_trace_host : nullptr; }
+#endif
+  pw_pick(a).launch(grid, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -85,8 +93,9 @@ __global__ __launch_bounds__(256) void pw_group_kernel(PwgArgs a) {
   }
 }
 
+Pick pwg_pick(const PwgArgs& a) { return a.bf16 ? HEP_PICK(256, 0, 0, pw_group_kernel, true) : HEP_PICK(256, 0, 0, pw_group_kernel, false); }
+
 void launch_pwg(const PwgArgs& a, hipStream_t s) {
   const dim3 grid(a.strips_per_image, a.B);
-  if (a.bf16) hipLaunchKernelGGL(pw_group_kernel<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(pw_group_kernel<false>, grid, dim3(256), 0, s, a);
+  pwg_pick(a).launch(grid, s, a);
 }

@@ -1,3 +1,3 @@
 // k_pw_fp8.hip - the pointwise GEMM kernels of k_pw_impl.h for precision 2 (0 fp32, 1 bf16, 2 fp8 operands).
 #include "k_pw_impl.h"
-template void launch_pw_prec<2>(const PwArgs&, hipStream_t);
+template Pick pw_pick_prec<2>(const PwArgs&);

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(NWV * 64) void pw_gemm_kernel(PwArgs a) {
   // ---- block / wave -> tile assignment ----
   const int chunksN = a.chunksN;
   const int logical = xcd_remap(blockIdx.x, gridDim.x);     // blocks sharing an A strip stay on one XCD
-  const int mblk = udiv_rcp(logical, a.chunksN_rcp), nchunk = logical - mblk * chunksN;   // (launch_pw_prec made the reciprocal)
+  const int mblk = udiv_rcp(logical, a.chunksN_rcp), nchunk = logical - mblk * chunksN;   // (launch_pw made the reciprocal)
   int m0, ntile0, kbeg = 0, kend = K;
   if (MODE == 0) { m0 = (mblk * 4 + wave) * (16 * MT); ntile0 = nchunk * NT; }
   else if (MODE == 1) { m0 = mblk * (16 * MT); ntile0 = nchunk * 4 * NT + wave * NT; }
@@ -452,29 +452,33 @@ __global__ __launch_bounds__(NWV * 64) void pw_gemm_kernel(PwArgs a) {
 #endif
 }
 
+// squeeze-excite prologue variant of a launch: 0 none, 1 shallow, 2 deep, 3 the scale copied from se_finish_kernel (template parameter SEV)
+static inline int pw_se_variant(const PwArgs& a) {
+  if (a.sq <= 0 || a.act == ACT_SWISH) return 0;          // (sq is set by the planner for project convs only)
+  if (a.se_from_tensor) return 3;
+  return (a.K > 256 || a.sqp / (a.bf16 ? 8 : 4) > 2) ? 2 : 1;
+}
+
+// the instantiation a launch runs (hep_pick.h): the one place that decides it.  Non-fragment picks leave the defaulted FRAG out.
 template <int PREC, int MT, int MODE>
-static void launch_nt(const PwArgs& a, dim3 grid, hipStream_t s) {
+static Pick pw_pick_nt(const PwArgs& a) {
   // dynamic LDS of the squeeze-excite prologue: scale [se_nimg][K] | hidden [sqp] | helper-group row sums [<= 256]
   const size_t lds = a.sq > 0 ? ((size_t)a.se_nimg * a.K + a.sqp + 256 + a.sqp) * sizeof(float) : 0;
   const int sev = pw_se_variant(a);
   if constexpr (PREC == 0 && MODE == 2) {
     if (a.nwv == 8 && a.act != ACT_SWISH && (sev == 0 || sev == 3) && a.NT <= 2 && !a.frag) {
-      if (sev == 3) { if (a.NT == 2) hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, 2, MODE, ACT_NONE, 3, 8>), grid, dim3(512), lds, s, a); else hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, 1, MODE, ACT_NONE, 3, 8>), grid, dim3(512), lds, s, a); }
-      else { if (a.NT == 2) hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, 2, MODE, ACT_NONE, 0, 8>), grid, dim3(512), 0, s, a); else hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, 1, MODE, ACT_NONE, 0, 8>), grid, dim3(512), 0, s, a); }
-      return;
+      if (sev == 3) return a.NT == 2 ? HEP_PICK(512, lds, 0, pw_gemm_kernel, PREC, MT, 2, MODE, ACT_NONE, 3, 8) : HEP_PICK(512, lds, 0, pw_gemm_kernel, PREC, MT, 1, MODE, ACT_NONE, 3, 8);
+      return a.NT == 2 ? HEP_PICK(512, 0, 0, pw_gemm_kernel, PREC, MT, 2, MODE, ACT_NONE, 0, 8) : HEP_PICK(512, 0, 0, pw_gemm_kernel, PREC, MT, 1, MODE, ACT_NONE, 0, 8);
     }
   }
   if constexpr (PREC != 2 && MT == 2 && MODE == 2) {
-    if (a.frag && a.act != ACT_SWISH && sev >= 1 && a.NT <= PW_FRAG_MAX_NT) {        // fragment-ordered operands (add_pw decides; hep_kernel_symbol names it)
-      if (PREC == 0 && a.nwv == 8 && sev == 3 && a.NT <= 2) {
-        if (a.NT == 2) hipLaunchKernelGGL((pw_gemm_kernel<PREC, 2, 2, 2, ACT_NONE, 3, 8, true>), grid, dim3(512), lds, s, a);
-        else hipLaunchKernelGGL((pw_gemm_kernel<PREC, 2, 1, 2, ACT_NONE, 3, 8, true>), grid, dim3(512), lds, s, a);
-        return;
-      }
+    if (a.frag && a.act != ACT_SWISH && sev >= 1 && a.NT <= PW_FRAG_MAX_NT) {        // fragment-ordered operands (add_pw decides)
+      if (PREC == 0 && a.nwv == 8 && sev == 3 && a.NT <= 2)
+        return a.NT == 2 ? HEP_PICK(512, lds, 0, pw_gemm_kernel, PREC, 2, 2, 2, ACT_NONE, 3, 8, true) : HEP_PICK(512, lds, 0, pw_gemm_kernel, PREC, 2, 1, 2, ACT_NONE, 3, 8, true);
       switch (a.NT) {
-#define FCASE(n) case n: if (sev == 1) hipLaunchKernelGGL((pw_gemm_kernel<PREC, 2, n, 2, ACT_NONE, 1, 4, true>), grid, dim3(256), lds, s, a); \
-                 else if (sev == 2) hipLaunchKernelGGL((pw_gemm_kernel<PREC, 2, n, 2, ACT_NONE, 2, 4, true>), grid, dim3(256), lds, s, a); \
-                 else hipLaunchKernelGGL((pw_gemm_kernel<PREC, 2, n, 2, ACT_NONE, 3, 4, true>), grid, dim3(256), lds, s, a); return;
+#define FCASE(n) case n: if (sev == 1) return HEP_PICK(256, lds, 0, pw_gemm_kernel, PREC, 2, n, 2, ACT_NONE, 1, 4, true); \
+                 if (sev == 2) return HEP_PICK(256, lds, 0, pw_gemm_kernel, PREC, 2, n, 2, ACT_NONE, 2, 4, true); \
+                 return HEP_PICK(256, lds, 0, pw_gemm_kernel, PREC, 2, n, 2, ACT_NONE, 3, 4, true);
         FCASE(1) FCASE(2) FCASE(3) FCASE(4)
 #ifdef HEP_ALT
         FCASE(5) FCASE(6) FCASE(7) FCASE(8)      // (HEP_PW_WIDE: measured loss, NOTEBOOK.md section 11)
@@ -484,29 +488,22 @@ static void launch_nt(const PwArgs& a, dim3 grid, hipStream_t s) {
     }
   }
   switch (a.NT) {
-#define CASE(n) case n: if (a.act == ACT_SWISH) hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, n, MODE, ACT_SWISH, 0>), grid, dim3(256), 0, s, a); \
-                else if (sev == 0) hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, n, MODE, ACT_NONE, 0>), grid, dim3(256), 0, s, a); \
-                else if (sev == 1) hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, n, MODE, ACT_NONE, 1>), grid, dim3(256), lds, s, a); \
-                else if (sev == 3) hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, n, MODE, ACT_NONE, 3>), grid, dim3(256), lds, s, a); \
-                else hipLaunchKernelGGL((pw_gemm_kernel<PREC, MT, n, MODE, ACT_NONE, 2>), grid, dim3(256), lds, s, a); break;
+#define CASE(n) case n: if (a.act == ACT_SWISH) return HEP_PICK(256, 0, 0, pw_gemm_kernel, PREC, MT, n, MODE, ACT_SWISH, 0, 4); \
+                if (sev == 0) return HEP_PICK(256, 0, 0, pw_gemm_kernel, PREC, MT, n, MODE, ACT_NONE, 0, 4); \
+                if (sev == 1) return HEP_PICK(256, lds, 0, pw_gemm_kernel, PREC, MT, n, MODE, ACT_NONE, 1, 4); \
+                if (sev == 3) return HEP_PICK(256, lds, 0, pw_gemm_kernel, PREC, MT, n, MODE, ACT_NONE, 3, 4); \
+                return HEP_PICK(256, lds, 0, pw_gemm_kernel, PREC, MT, n, MODE, ACT_NONE, 2, 4);
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
 #undef CASE
   }
+  return Pick();      // no instantiation for this tile width
 }
 
 // one translation unit per precision (k_pw_f32.hip, k_pw_bf16.hip, k_pw_fp8.hip) instantiates this: the three sets of
 // ~190 kernels compile in parallel
 template <int PREC>
-void launch_pw_prec(const PwArgs& a_, hipStream_t s) {
-  const int per_block_n = a_.mode == 1 ? 4 * a_.NT : a_.NT;
-  const int chunksN = (a_.tilesN + per_block_n - 1) / per_block_n;
-  const int rows = a_.mode == 0 ? 64 * a_.MT : 16 * a_.MT;
-  dim3 grid(((a_.M + rows - 1) / rows) * chunksN);
-  PwArgs a = a_; a.chunksN = chunksN; a.chunksN_rcp = rcp_u32(chunksN);
-#ifdef HEP_PW_TRACE
-  { static const char* sel = getenv("HEP_PW_TRACE_SEL"); int k = 0, n = 0; if (sel) sscanf(sel, "%d,%d", &k, &n); a.trace_buf = sel && a.K == k && a.N == n ? g_pw_trace_host : nullptr; }
-#endif
-  if (a.mode == 0) { if (a.MT == 2) launch_nt<PREC, 2, 0>(a, grid, s); else launch_nt<PREC, 1, 0>(a, grid, s); }
-  else if (a.mode == 1) { if (a.MT == 2) launch_nt<PREC, 2, 1>(a, grid, s); else launch_nt<PREC, 1, 1>(a, grid, s); }
-  else { if (a.MT == 2) launch_nt<PREC, 2, 2>(a, grid, s); else launch_nt<PREC, 1, 2>(a, grid, s); }
+Pick pw_pick_prec(const PwArgs& a) {
+  if (a.mode == 0) return a.MT == 2 ? pw_pick_nt<PREC, 2, 0>(a) : pw_pick_nt<PREC, 1, 0>(a);
+  if (a.mode == 1) return a.MT == 2 ? pw_pick_nt<PREC, 2, 1>(a) : pw_pick_nt<PREC, 1, 1>(a);
+  return a.MT == 2 ? pw_pick_nt<PREC, 2, 2>(a) : pw_pick_nt<PREC, 1, 2>(a);
 }

@@ -334,10 +334,11 @@ void sbf_layout(SbfArgs* a) {
   a->tiles_x = (a->Ws + TO - 1) / TO; a->tiles = a->tiles_x * ((a->Hs + TO - 1) / TO);
 }
 
+Pick sbf_pick(const SbfArgs& a) { return a.bf16 ? HEP_PICK(ST, a.lds_bytes, 0, sbf_kernel, true) : HEP_PICK(ST, a.lds_bytes, 0, sbf_kernel, false); }
+
 void launch_sbf(const SbfArgs& a_, hipStream_t s) {
   SbfArgs a = a_;
   a.tiles_rcp = rcp_u32((uint32_t)a.tiles); a.tiles_x_rcp = rcp_u32((uint32_t)a.tiles_x);
   dim3 grid(a.tiles, a.B);
-  if (a.bf16) hipLaunchKernelGGL(sbf_kernel<true>, grid, dim3(ST), a.lds_bytes, s, a);
-  else hipLaunchKernelGGL(sbf_kernel<false>, grid, dim3(ST), a.lds_bytes, s, a);
+  sbf_pick(a).launch(grid, s, a);
 }

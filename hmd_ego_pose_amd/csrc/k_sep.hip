@@ -31,8 +31,7 @@
 #include "k_sep_impl.h"
 
 // k_sep_shape.hip
-int sep_shape_prepare(void);
-bool launch_sep_shape(int id, const SepArgs&, dim3 grid, hipStream_t);
+Pick sep_shape_pick(int id, const SepArgs&);
 void sep_shape_trace_bind(unsigned long long* p, int hw);
 
 #ifdef HEP_TOWER_TRACE
@@ -62,19 +61,8 @@ void sep_lds_layout(int C, int bf16, int ts, int max_cols_f32, int max_cols_map,
   if (stage_w && bf16 && C > 64 && (ts == 8 || ts == 4) && wrows * (C / 8) <= 4 * 1024 && a->lds_bytes + wbytes <= 159 * 1024) { a->off_wpw = (a->lds_bytes + 15) & ~(size_t)15; a->lds_bytes = a->off_wpw + wbytes; }
 }
 
-int sep_prepare(void) {
-  const void* fns[9] = {reinterpret_cast<const void*>(sep_kernel<true, 0, false, true>),
-                        reinterpret_cast<const void*>(sep_kernel<true, 0>), reinterpret_cast<const void*>(sep_kernel<true, 1>),
-                        reinterpret_cast<const void*>(sep_kernel<true, 2>), reinterpret_cast<const void*>(sep_kernel<false, 0>),
-                        reinterpret_cast<const void*>(sep_kernel<false, 1>), reinterpret_cast<const void*>(sep_kernel<false, 2>),
-                        reinterpret_cast<const void*>(sep_kernel<true, 0, true>), reinterpret_cast<const void*>(sep_kernel<true, 2, true>)};
-  for (const void* f : fns)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) return -1;
-  return sep_shape_prepare();
-}
-
-// single bf16 node of width <= 64 without staged weights: the eight-wave instantiation (launch_sep and hep_kernel_symbol agree through this)
-int sep_w8(const SepArgs& a) { return a.bf16 && !a.chain && a.nseg == 1 && !a.off_wpw && a.C <= 64; }
+// single bf16 node of width <= 64 without staged weights: the eight-wave instantiation (sep_pick; the shape rows are all of this kind)
+static int sep_w8(const SepArgs& a) { return a.bf16 && !a.chain && a.nseg == 1 && !a.off_wpw && a.C <= 64; }
 
 // the row of SEP_SHAPES (k_sep_impl.h) whose kernel runs this launch: every field the kernel folds must equal the row; 0 = the
 // generic kernel (no such row, or the plan asked for it: HEP_NECK_GENERIC)
@@ -96,25 +84,31 @@ int sep_shape_id(const SepArgs& a) {
   return 0;
 }
 
-void launch_sep(const SepArgs& a_, hipStream_t s) {
-  const SepArgs& a = a_;
-  const int mode = a.chain ? 2 : (a.nseg == 1 ? 0 : 1);
-  dim3 grid(mode == 2 ? 1 : a.total_tiles, a.B);
-  const dim3 block(SEP_THREADS_OF(mode, a.bf16));
+static int sep_mode(const SepArgs& a) { return a.chain ? 2 : (a.nseg == 1 ? 0 : 1); }      // 0 one node, 1 independent segments, 2 a chain
+
+// the instantiation a launch runs (hep_pick.h): a single node on its shape row when it has one, else a generic sep_kernel
+Pick sep_pick(const SepArgs& a) {
+  const int mode = sep_mode(a);
+  const unsigned block = SEP_THREADS_OF(mode, a.bf16);
   if (mode == 0)
-    if (const int id = sep_shape_id(a))
-      if (launch_sep_shape(id, a, grid, s)) return;
+    if (const int id = sep_shape_id(a)) return sep_shape_pick(id, a);
+#define SEP_PICK(blk, ...) HEP_PICK(blk, a.lds_bytes, 159 * 1024, sep_kernel, __VA_ARGS__)
   if (a.bf16) {
     // (staged weights: every segment of the launch is a map-to-map node of the full width - the planner only sets off_wpw then)
-    if (mode == 0 && a.off_wpw) hipLaunchKernelGGL((sep_kernel<true, 0, true>), grid, block, a.lds_bytes, s, a);
-    else if (mode == 2 && a.off_wpw) hipLaunchKernelGGL((sep_kernel<true, 2, true>), grid, block, a.lds_bytes, s, a);
-    else if (mode == 0 && sep_w8(a)) hipLaunchKernelGGL((sep_kernel<true, 0, false, true>), grid, dim3(512), a.lds_bytes, s, a);
-    else if (mode == 0) hipLaunchKernelGGL((sep_kernel<true, 0>), grid, block, a.lds_bytes, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((sep_kernel<true, 1>), grid, block, a.lds_bytes, s, a);
-    else hipLaunchKernelGGL((sep_kernel<true, 2>), grid, block, a.lds_bytes, s, a);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((sep_kernel<false, 0>), grid, block, a.lds_bytes, s, a);
-    else if (mode == 1) hipLaunchKernelGGL((sep_kernel<false, 1>), grid, block, a.lds_bytes, s, a);
-    else hipLaunchKernelGGL((sep_kernel<false, 2>), grid, block, a.lds_bytes, s, a);
+    if (mode == 0 && a.off_wpw) return SEP_PICK(block, true, 0, true, false);
+    if (mode == 2 && a.off_wpw) return SEP_PICK(block, true, 2, true, false);
+    if (mode == 0 && sep_w8(a)) return SEP_PICK(512, true, 0, false, true);
+    if (mode == 0) return SEP_PICK(block, true, 0, false, false);
+    if (mode == 1) return SEP_PICK(block, true, 1, false, false);
+    return SEP_PICK(block, true, 2, false, false);
   }
+  if (mode == 0) return SEP_PICK(block, false, 0, false, false);
+  if (mode == 1) return SEP_PICK(block, false, 1, false, false);
+  return SEP_PICK(block, false, 2, false, false);
+#undef SEP_PICK
+}
+
+void launch_sep(const SepArgs& a, hipStream_t s) {
+  dim3 grid(sep_mode(a) == 2 ? 1 : a.total_tiles, a.B);
+  sep_pick(a).launch(grid, s, a);
 }

@@ -1,5 +1,5 @@
 // k_sep_shape.hip - the shape-specialised single BiFPN nodes (k_sep_impl.h SEP_SHAPES: sep_shape_kernel<true, D>): a translation unit
-// of its own so that the build stays parallel; k_sep.hip selects a row (sep_shape_id) and launches it through launch_sep_shape.
+// of its own so that the build stays parallel; k_sep.hip selects a row (sep_shape_id) and takes its pick from sep_shape_pick.
 #include <algorithm>
 
 #include "k_sep_impl.h"
@@ -10,22 +10,14 @@
 #define SEP_SHAPE_MIN_LDS 0
 #endif
 
-#define SEP_SHAPE_PREP_ROW(id, ...) \
-  rc |= hipFuncSetAttribute(reinterpret_cast<const void*>(sep_shape_kernel<true, id>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) == hipSuccess ? 0 : -1;
-#define SEP_SHAPE_LAUNCH_ROW(id, ...) \
-  case id: hipLaunchKernelGGL((sep_shape_kernel<true, id>), grid, dim3(512), std::max<size_t>(a.lds_bytes, SEP_SHAPE_MIN_LDS), s, a); return true;
+#define SEP_SHAPE_PICK_ROW(id, ...) \
+  case id: return HEP_PICK(512, std::max<size_t>(a.lds_bytes, SEP_SHAPE_MIN_LDS), 159 * 1024, sep_shape_kernel, true, id);
 
-int sep_shape_prepare(void) {
-  int rc = 0;
-  SEP_SHAPES(SEP_SHAPE_PREP_ROW)
-  return rc;
-}
-
-// false when `id` is no row of the table
-bool launch_sep_shape(int id, const SepArgs& a, dim3 grid, hipStream_t s) {
+// empty when `id` is no row of the table
+Pick sep_shape_pick(int id, const SepArgs& a) {
   switch (id) {
-    SEP_SHAPES(SEP_SHAPE_LAUNCH_ROW)
-    default: return false;
+    SEP_SHAPES(SEP_SHAPE_PICK_ROW)
+    default: return Pick();
   }
 }
 

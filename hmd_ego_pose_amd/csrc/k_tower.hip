@@ -691,60 +691,45 @@ int tower_supports(int C) {
 
 int tower_map_tiles(int C) { return (((C + 15) / 16) + 1) & ~1; }      // n-tiles of a map layer (even)
 
-// widths / dtypes the cooperative form is instantiated for
-template <bool BF16, int CW> struct CoopBuilt { static constexpr bool value = BF16 ? (CW >= 160 || CW == 64) : CW == 64; };
-int tower_coop_supported(int C, int bf16) {
-  if (bf16) return C == 64 || C == 160 || C == 224 || C == 288 || C == 384;
-  return C == 64;
-}
-
+// the cooperative form exists for tower_coop_built(bf16, width) only (hep_internal.h: the planner asks the same predicate)
 template <bool BF16, int CW, bool HDR>
-static void launch_coop(const SepArgs& a, dim3 grid, hipStream_t s, int ipb) {
-  if constexpr (CoopBuilt<BF16, CW>::value) {
+static Pick coop_pick() {
+  if constexpr (tower_coop_built(BF16, CW)) {
     typedef CoopCfg<BF16, CW, HDR> Cfg;
-    hipLaunchKernelGGL((tower_coop_kernel<BF16, CW, HDR>), grid, dim3(Cfg::IPAR * Cfg::NWV * 64), Cfg::LDS, s, a.segs, a.tile_seg, a.B, ipb);
+    return HEP_PICK(Cfg::IPAR * Cfg::NWV * 64, Cfg::LDS, 159 * 1024, tower_coop_kernel, BF16, CW, HDR);
   }
-}
-
-template <bool BF16, int CW>
-static int prepare_coop() {
-  if constexpr (CoopBuilt<BF16, CW>::value) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(tower_coop_kernel<BF16, CW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(tower_coop_kernel<BF16, CW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) return -1;
-  }
-  return 0;
+  return Pick();
 }
 
 template <bool BF16, int CW, bool HDR>
-static void launch_one(const SepArgs& a, dim3 grid, hipStream_t s, int ipb) {
+static Pick one_pick() {
   typedef TowerCfg<BF16, CW, HDR> Cfg;
-  hipLaunchKernelGGL((tower_kernel<BF16, CW, HDR>), grid, dim3(Cfg::NW * 64), Cfg::LDS, s, a.segs, a.tile_seg, a.B, ipb);
+  return HEP_PICK(Cfg::NW * 64, Cfg::LDS, 159 * 1024, tower_kernel, BF16, CW, HDR);
 }
 
 template <int CW>
-static void launch_w(const SepArgs& a, dim3 grid, hipStream_t s, int ipb) {
+static Pick tower_pick_w(const SepArgs& a) {
   const bool hdr = a.direct == 2;
   if (a.coop) {
-    if (a.bf16) { if (hdr) launch_coop<true, CW, true>(a, grid, s, ipb); else launch_coop<true, CW, false>(a, grid, s, ipb); }
-    else { if (hdr) launch_coop<false, CW, true>(a, grid, s, ipb); else launch_coop<false, CW, false>(a, grid, s, ipb); }
-    return;
+    if (a.bf16) return hdr ? coop_pick<true, CW, true>() : coop_pick<true, CW, false>();
+    return hdr ? coop_pick<false, CW, true>() : coop_pick<false, CW, false>();
   }
-  if (a.bf16) { if (hdr) launch_one<true, CW, true>(a, grid, s, ipb); else launch_one<true, CW, false>(a, grid, s, ipb); }
-  else { if (hdr) launch_one<false, CW, true>(a, grid, s, ipb); else launch_one<false, CW, false>(a, grid, s, ipb); }
+  if (a.bf16) return hdr ? one_pick<true, CW, true>() : one_pick<true, CW, false>();
+  return hdr ? one_pick<false, CW, true>() : one_pick<false, CW, false>();
 }
 
-template <int CW>
-static int prepare_w() {
-  const void* fns[4] = {reinterpret_cast<const void*>(tower_kernel<true, CW, true>), reinterpret_cast<const void*>(tower_kernel<true, CW, false>),
-                        reinterpret_cast<const void*>(tower_kernel<false, CW, true>), reinterpret_cast<const void*>(tower_kernel<false, CW, false>)};
-  for (const void* f : fns)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) return -1;
-  return prepare_coop<true, CW>() | prepare_coop<false, CW>();
-}
-
-// raises the dynamic-LDS limit of every instantiation (call once per device)
-int tower_prepare(void) {
-  return prepare_w<64>() | prepare_w<88>() | prepare_w<112>() | prepare_w<160>() | prepare_w<224>() | prepare_w<288>() | prepare_w<384>();
+// the instantiation a head launch runs (hep_pick.h); empty for a width outside kTowerWidths or a cooperative form that is not built
+Pick tower_pick(const SepArgs& a) {
+  switch (a.C) {
+    case 64: return tower_pick_w<64>(a);
+    case 88: return tower_pick_w<88>(a);
+    case 112: return tower_pick_w<112>(a);
+    case 160: return tower_pick_w<160>(a);
+    case 224: return tower_pick_w<224>(a);
+    case 288: return tower_pick_w<288>(a);
+    case 384: return tower_pick_w<384>(a);
+    default: return Pick();
+  }
 }
 
 #ifdef HEP_TOWER_TRACE
@@ -779,14 +764,5 @@ void launch_tower(const SepArgs& a, hipStream_t s) {
   if (a.coop) { ipb = 8; while (ipb > 2 && (int64_t)a.total_tiles * ((a.B + ipb - 1) / ipb) < min_wgs) ipb /= 2; }
   ipb = std::min(ipb, a.B);
   const dim3 grid(a.total_tiles, (a.B + ipb - 1) / ipb);
-  switch (a.C) {
-    case 64: launch_w<64>(a, grid, s, ipb); break;
-    case 88: launch_w<88>(a, grid, s, ipb); break;
-    case 112: launch_w<112>(a, grid, s, ipb); break;
-    case 160: launch_w<160>(a, grid, s, ipb); break;
-    case 224: launch_w<224>(a, grid, s, ipb); break;
-    case 288: launch_w<288>(a, grid, s, ipb); break;
-    case 384: launch_w<384>(a, grid, s, ipb); break;
-    default: break;   // the planner only selects this kernel for tower_supports(C)
-  }
+  tower_pick(a).launch(grid, s, a.segs, a.tile_seg, a.B, ipb);
 }

@@ -31,8 +31,7 @@
 #include "k_xbf_impl.h"
 
 // k_xbf_shape.hip
-int xbf_shape_prepare(void);
-bool launch_xbf_shape(int id, const XbfArgs&, dim3 grid, hipStream_t);
+Pick xbf_shape_pick(int id, const XbfArgs&);
 void xbf_shape_trace_bind(unsigned long long* p);
 
 #ifdef HEP_XBF_TRACE
@@ -68,49 +67,29 @@ size_t xbf_layout(XbfArgs* a) {
   X(3, 2, 8, 8, 1, 32, 6) X(3, 1, 8, 16, 2, 96, 9) X(5, 2, 8, 8, 2, 144, 9) \
   X(3, 2, 8, 8, 2, 24, 9) X(3, 1, 8, 16, 2, 144, 12) X(3, 1, 8, 16, 2, 192, 12) X(5, 2, 8, 8, 2, 192, 12) X(5, 1, 8, 16, 3, 288, 18) X(3, 2, 8, 8, 3, 288, 18)
 
-template <bool BF16, int KS, int S, int TOH, int TOW, int NT1, int K1C, int NT2C>
-static int xprep1() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(xbf_kernel<BF16, KS, S, TOH, TOW, NT1, K1C, NT2C>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? 0 : -1;
-}
+#define XBF_PICK(...) HEP_PICK(XT, a.lds_bytes, 160 * 1024, xbf_kernel, BF16, __VA_ARGS__)
 template <bool BF16, int KS, int S, int TOH, int TOW>
-static int xprep() { return xprep1<BF16, KS, S, TOH, TOW, 1, 0, 0>() | xprep1<BF16, KS, S, TOH, TOW, 2, 0, 0>() | xprep1<BF16, KS, S, TOH, TOW, 3, 0, 0>(); }
-int xbf_prepare(void) {
-  int rc = xprep<true, 3, 1, 8, 16>() | xprep<true, 3, 2, 8, 8>() | xprep<true, 5, 1, 8, 16>() | xprep<true, 5, 2, 8, 8>() |
-           xprep<false, 3, 1, 8, 16>() | xprep<false, 3, 2, 8, 8>() | xprep<false, 5, 1, 8, 16>() | xprep<false, 5, 2, 8, 8>();
-#define X(k, s, th, tw, n1, k1, n2) rc |= xprep1<true, k, s, th, tw, n1, k1, n2>() | xprep1<false, k, s, th, tw, n1, k1, n2>();
-  XBF_SPECS(X)
-#undef X
-  return rc | xbf_shape_prepare();
-}
-
-template <bool BF16, int KS, int S, int TOH, int TOW>
-static void launch_xbf_n(const XbfArgs& a, dim3 grid, hipStream_t s) {
-  if (a.NT1 == 1) hipLaunchKernelGGL((xbf_kernel<BF16, KS, S, TOH, TOW, 1, 0, 0>), grid, dim3(XT), a.lds_bytes, s, a);
-  else if (a.NT1 == 2) hipLaunchKernelGGL((xbf_kernel<BF16, KS, S, TOH, TOW, 2, 0, 0>), grid, dim3(XT), a.lds_bytes, s, a);
-  else hipLaunchKernelGGL((xbf_kernel<BF16, KS, S, TOH, TOW, 3, 0, 0>), grid, dim3(XT), a.lds_bytes, s, a);
+static Pick xbf_pick_n(const XbfArgs& a) {
+  if (a.NT1 == 1) return XBF_PICK(KS, S, TOH, TOW, 1, 0, 0);
+  if (a.NT1 == 2) return XBF_PICK(KS, S, TOH, TOW, 2, 0, 0);
+  return XBF_PICK(KS, S, TOH, TOW, 3, 0, 0);
 }
 template <bool BF16>
-static void launch_xbf_t(const XbfArgs& a, dim3 grid, hipStream_t s) {
+static Pick xbf_pick_t(const XbfArgs& a) {
   const bool generic = a.generic == 1;           // A/B switch, parity test of the generic path (decided when the plan is built)
 #define X(k_, s_, th, tw, n1, k1, n2) \
-  if (!generic && a.k == k_ && a.s == s_ && a.NT1 == n1 && a.K1 == k1 && a.NT2 == n2) { hipLaunchKernelGGL((xbf_kernel<BF16, k_, s_, th, tw, n1, k1, n2>), grid, dim3(XT), a.lds_bytes, s, a); return; }
+  if (!generic && a.k == k_ && a.s == s_ && a.NT1 == n1 && a.K1 == k1 && a.NT2 == n2) return XBF_PICK(k_, s_, th, tw, n1, k1, n2);
   XBF_SPECS(X)
 #undef X
-  if (a.k == 3 && a.s == 1) launch_xbf_n<BF16, 3, 1, 8, 16>(a, grid, s);
-  else if (a.k == 3 && a.s == 2) launch_xbf_n<BF16, 3, 2, 8, 8>(a, grid, s);
-  else if (a.k == 5 && a.s == 1) launch_xbf_n<BF16, 5, 1, 8, 16>(a, grid, s);
-  else launch_xbf_n<BF16, 5, 2, 8, 8>(a, grid, s);
+  if (a.k == 3 && a.s == 1) return xbf_pick_n<BF16, 3, 1, 8, 16>(a);
+  if (a.k == 3 && a.s == 2) return xbf_pick_n<BF16, 3, 2, 8, 8>(a);
+  if (a.k == 5 && a.s == 1) return xbf_pick_n<BF16, 5, 1, 8, 16>(a);
+  return xbf_pick_n<BF16, 5, 2, 8, 8>(a);
 }
-int xbf_specialised(const XbfArgs& a) {
-  if (a.generic == 1) return 0;
-#define X(k_, s_, th, tw, n1, k1, n2) if (a.k == k_ && a.s == s_ && a.NT1 == n1 && a.K1 == k1 && a.NT2 == n2) return 1;
-  XBF_SPECS(X)
-#undef X
-  return 0;
-}
+#undef XBF_PICK
 // the row of XBF_SHAPES (k_xbf_impl.h) whose kernel runs this launch: every field the kernel folds must equal the row; 0 = xbf_kernel
 // (no such row, or the plan asked for it: HEP_XBF_GENERIC=1 the generic instantiation, =2 the width-specialised one).  Only fields the
-// planner sets are compared (hep_kernel_symbol asks before launch_xbf has filled the reciprocals, which follow from the compared ones).
+// planner sets are compared (xbf_pick is asked before launch_xbf has filled the reciprocals, which follow from the compared ones).
 int xbf_shape_id(const XbfArgs& a) {
   if (a.generic || !a.bf16) return 0;
 #define X(id, k_, s_, th, tw, n1, k1, n2, H_, W_, Ho_, Wo_, N1_, pt, pl, sq_, sqp_, sq2_, sqp2_, res_) { \
@@ -125,6 +104,11 @@ int xbf_shape_id(const XbfArgs& a) {
 #undef X
   return 0;
 }
+// the instantiation a launch runs (hep_pick.h): its shape row, else the width-specialised xbf_kernel, else the generic one
+Pick xbf_pick(const XbfArgs& a) {
+  if (const int id = xbf_shape_id(a)) return xbf_shape_pick(id, a);
+  return a.bf16 ? xbf_pick_t<true>(a) : xbf_pick_t<false>(a);
+}
 void launch_xbf(const XbfArgs& a_, hipStream_t s) {
   XbfArgs a = a_;
 #ifdef HEP_XBF_TRACE
@@ -137,7 +121,5 @@ void launch_xbf(const XbfArgs& a_, hipStream_t s) {
     a.sw_rcp = rcp_u32((uint32_t)((rv + 63) >> 6));
   }
   dim3 grid(wgs, a.B);
-  if (const int id = xbf_shape_id(a))
-    if (launch_xbf_shape(id, a, grid, s)) return;
-  if (a.bf16) launch_xbf_t<true>(a, grid, s); else launch_xbf_t<false>(a, grid, s);
+  xbf_pick(a).launch(grid, s, a);
 }

@@ -59,6 +59,16 @@ def test_variant_cover_entries_select_the_variants_they_are_listed_for(packs):
         assert not set(wanted) & others, (_fmt((phi, size, batch, dtype)), sorted(set(wanted) & others))
 
 
+def test_every_launch_of_the_support_matrix_names_an_instantiation(planned):
+    """No configuration of the matrix fails to plan (plan_matrix raises on a refusal, and plan_session refuses a launch whose pick
+    has no instantiation), and every line of every launch list names a device function of the form name<...>."""
+    import re
+    assert set(planned) == set(MATRIX)
+    form = re.compile(r"^[A-Za-z_][A-Za-z0-9_]*<[^<>]+>$")
+    bad = [(_fmt(c), sym, name) for c, launches in planned.items() for sym, name in launches if not form.match(sym) or not name]
+    assert all(planned.values()) and not bad, bad[:10]
+
+
 @pytest.mark.parametrize("size,batch", [(128, 1), (256, 16), (640, 3)])
 def test_phi7_plans_the_launch_list_of_phi6(packs, size, batch):
     """phi 6 and 7 share the backbone (EfficientNet-B6), the BiFPN width and depth and the heads: the inference planner selects
