@@ -10,7 +10,7 @@
 #include <type_traits>
 
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 
 #define GD_THREADS 256
 #define GD_BM 64

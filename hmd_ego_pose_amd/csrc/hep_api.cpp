@@ -1,7 +1,8 @@
 // hep_api.cpp - the session side of the C ABI of libhep.so (include/hep.h) and the forward executor:
 // eager stem launch (it reads the caller's input pointer) + one captured hipGraph for
-// everything behind it, replayed on the caller's stream.  The entry points that take no handle - the stateless
-// training side - are in hep_api_train.cpp.
+// everything behind it, replayed on the caller's stream.  The entry points that take no handle are in files of their
+// own: the evaluation and visualisation toolkit in hep_api_eval.cpp, the training side in hep_api_train.cpp.
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,7 +13,6 @@
 #include <fstream>
 #include <memory>
 
-#include "hep.h"
 #include "hep_api_util.h"
 #include "hep_plan.h"
 
@@ -404,17 +404,10 @@ int hep_preprocess_u8_device(hep_handle* h, const uint8_t* rgb_hwc, int batch, i
   if (!h || !rgb_hwc || !out_hwc || batch < 1 || height < 1 || width < 1) return fail(HEP_ERR_INVALID, "bad argument");
   Session& s = h->s;
   HIPRET(hipSetDevice(s.device));
+  ResizeGeom g;
+  if (!resize_geometry(height, width, s.size, &g)) return fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size");
   PreprocArgs a; a.in = rgb_hwc; a.out = out_hwc; a.B = batch; a.H = height; a.W = width; a.S = s.size;
-  // colibri_common.py:631-642: scale = image_size / longer side; that side becomes image_size, the other int(side * scale);
-  // cv2.resize(image, (resized_width, resized_height)): with an explicit size the per-axis inverse scale is src / dst
-  const int side = std::max(height, width);
-  a.resize = side != s.size;
-  const double scale = (double)s.size / side;
-  a.nh = height > width ? s.size : (int)(height * scale);
-  a.nw = height > width ? (int)(width * scale) : s.size;
-  if (!a.resize) { a.nh = height; a.nw = width; }
-  a.inv_scale_x = (double)width / std::max(a.nw, 1); a.inv_scale_y = (double)height / std::max(a.nh, 1);
-  if (a.nh > s.size || a.nw > s.size || a.nh < 1 || a.nw < 1) return fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size");
+  a.resize = g.resize; a.nh = g.nh; a.nw = g.nw; a.inv_scale_x = g.inv_scale_x; a.inv_scale_y = g.inv_scale_y;
   launch_preprocess(a, (hipStream_t)stream);
   HIPRET(hipGetLastError());
   return 0;
@@ -650,32 +643,28 @@ static int top1_locked(Session& s, const float* regression, const float* classif
   return 0;
 }
 
+// the body of hep_top1_device and hep_top_labels_device: `who` is the prefix of the entry point's messages
+static int top_device(const char* who, bool per_label, hep_handle* h, const float* regression, const float* classification, const float* rotation,
+                      const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
+                      uint32_t* records, void* stream) {
+  const Check c{who};
+  CHECKED(c.ptrs({{h, "handle"}, {camera, "camera"}, {records, "records"}}));      // (the handle is not read before the pointers are checked)
+  Session& s = h->s; CHECKED(c.range("batch", batch, 1, s.max_batch, HEP_ERR_INVALID, "max_batch"));
+  std::lock_guard<std::mutex> lk(s.mu);
+  HIPRET(hipSetDevice(s.device));
+  return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream, per_label);
+}
+
 int hep_top1_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
                     const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
                     uint32_t* records, void* stream) try {
-  if (!h) return fail(HEP_ERR_INVALID, "hep_top1_device: handle is NULL");
-  if (!camera) return fail(HEP_ERR_INVALID, "hep_top1_device: camera is NULL");
-  if (!records) return fail(HEP_ERR_INVALID, "hep_top1_device: records is NULL");
-  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_top1_device: batch outside 1..max_batch");      // (the handle is not read before the pointers are checked)
-  Session& s = h->s;
-  if (batch > s.max_batch) return fail(HEP_ERR_INVALID, "hep_top1_device: batch outside 1..max_batch");
-  std::lock_guard<std::mutex> lk(s.mu);
-  HIPRET(hipSetDevice(s.device));
-  return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream);
+  return top_device("hep_top1_device: ", false, h, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, stream);
 } HEP_CATCH_INT
 
 int hep_top_labels_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
                           const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
                           uint32_t* records, void* stream) try {
-  if (!h) return fail(HEP_ERR_INVALID, "hep_top_labels_device: handle is NULL");
-  if (!camera) return fail(HEP_ERR_INVALID, "hep_top_labels_device: camera is NULL");
-  if (!records) return fail(HEP_ERR_INVALID, "hep_top_labels_device: records is NULL");
-  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_top_labels_device: batch outside 1..max_batch");
-  Session& s = h->s;
-  if (batch > s.max_batch) return fail(HEP_ERR_INVALID, "hep_top_labels_device: batch outside 1..max_batch");
-  std::lock_guard<std::mutex> lk(s.mu);
-  HIPRET(hipSetDevice(s.device));
-  return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream, true);
+  return top_device("hep_top_labels_device: ", true, h, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, stream);
 } HEP_CATCH_INT
 
 namespace {
@@ -684,19 +673,12 @@ constexpr size_t kRecBytes = (size_t)HEP_POSE_RECORD_WORDS * 4;
 static_assert(HEP_POSE_RECORD_WORDS == POSE_RECORD_WORDS, "the record of include/hep.h is the kernel's");
 }  // namespace
 
-// what the two host entry points share, before any HIP call: NULL pointers and a batch below 1 without reading the handle (check_pose),
-// then - behind the frame geometry - the batch against the handle's max_batch (check_pose_batch)
-static int check_pose(const char* who, const hep_handle* h, const void* input, const char* input_name, int batch, const float* camera, const int32_t* found) {
-  if (!h) return fail(HEP_ERR_INVALID, std::string(who) + ": handle is NULL");
-  if (!input) return fail(HEP_ERR_INVALID, std::string(who) + ": " + input_name + " is NULL");
-  if (!camera) return fail(HEP_ERR_INVALID, std::string(who) + ": camera is NULL");
-  if (!found) return fail(HEP_ERR_INVALID, std::string(who) + ": found is NULL");
-  if (batch < 1) return fail(HEP_ERR_INVALID, std::string(who) + ": batch outside 1..max_batch given to hep_create");
-  return 0;
-}
-static int check_pose_batch(const char* who, const hep_handle* h, int batch) {
-  if (batch > h->s.max_batch) return fail(HEP_ERR_INVALID, std::string(who) + ": batch outside 1..max_batch given to hep_create");
-  return 0;
+// what the host entry points refuse first, without reading the handle: NULL pointers and a batch below 1 (check_pose); then, behind the frame
+// geometry where there is one, the batch against the handle's max_batch (check_pose_batch)
+static int check_pose_batch(const Check& c, int batch, int most) { return c.range("batch", batch, 1, most, HEP_ERR_INVALID, "max_batch given to hep_create"); }
+static int check_pose(const Check& c, const hep_handle* h, const void* input, const char* input_name, int batch, const float* camera, const int32_t* found) {
+  CHECKED(c.ptrs({{h, "handle"}, {input, input_name}, {camera, "camera"}, {found, "found"}}));
+  return check_pose_batch(c, batch, INT_MAX);
 }
 
 // Staging of one call: [camera rows, padded to cam_pad bytes | payload] on the device.  Direct (the default): two hipMemcpyAsync from
@@ -769,11 +751,11 @@ static int pose_finish(Session& s, int batch, float score_threshold, const PoseO
   return 0;
 }
 
-// the bodies of hep_pose_from_input / hep_poses_from_input and of hep_pose_from_i420 / hep_poses_from_i420: `who` names the entry point
+// the bodies of hep_pose_from_input / hep_poses_from_input and of hep_pose_from_i420 / hep_poses_from_i420: `who` is the prefix of the entry point's messages
 static int pose_from_input(const char* who, bool per_label, hep_handle* h, const float* input_nchw, int batch, const float* camera,
                            float score_threshold, const PoseOut& o) {
-  if (int rc = check_pose(who, h, input_nchw, "input_nchw", batch, camera, o.found)) return rc;
-  if (int rc = check_pose_batch(who, h, batch)) return rc;
+  const Check c{who};
+  CHECKED(check_pose(c, h, input_nchw, "input_nchw", batch, camera, o.found)); CHECKED(check_pose_batch(c, batch, h->s.max_batch));
   Session& s = h->s;
   std::lock_guard<std::mutex> lk(s.mu);
   HIPRET(hipSetDevice(s.device));
@@ -785,9 +767,8 @@ static int pose_from_input(const char* who, bool per_label, hep_handle* h, const
 }
 static int pose_from_i420(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop,
                           int resized, const float* camera, float score_threshold, const PoseOut& o) {
-  if (int rc = check_pose(who, h, yuv, "yuv", batch, camera, o.found)) return rc;
-  if (int rc = check_i420(height, width, crop, resized)) return rc;
-  if (int rc = check_pose_batch(who, h, batch)) return rc;
+  const Check c{who};
+  CHECKED(check_pose(c, h, yuv, "yuv", batch, camera, o.found)); CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_pose_batch(c, batch, h->s.max_batch));
   Session& s = h->s;
   {   // ResizeAndNormalizeMat's row count (preprocess_i420_locked computes the same): refused here, before any HIP call
     const int nh = (int)((float)resized * ((float)s.size / (float)resized));
@@ -809,14 +790,14 @@ static int pose_from_i420(const char* who, bool per_label, hep_handle* h, const 
 int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
                         int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
                         float* translation, float* hand) try {
-  return pose_from_input("hep_pose_from_input", false, h, input_nchw, batch, camera, score_threshold,
+  return pose_from_input("hep_pose_from_input: ", false, h, input_nchw, batch, camera, score_threshold,
                          PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
 } HEP_CATCH_INT
 
 int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
                        int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
-  return pose_from_i420("hep_pose_from_i420", false, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
+  return pose_from_i420("hep_pose_from_i420: ", false, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
                         PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
 } HEP_CATCH_INT
 
@@ -824,288 +805,15 @@ int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height,
 int hep_poses_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
                          int32_t* found, float* scores, int32_t* index, float* boxes, float* rotation, float* translation,
                          float* hand) try {
-  return pose_from_input("hep_poses_from_input", true, h, input_nchw, batch, camera, score_threshold,
+  return pose_from_input("hep_poses_from_input: ", true, h, input_nchw, batch, camera, score_threshold,
                          PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
 } HEP_CATCH_INT
 
 int hep_poses_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
                         const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
                         float* rotation, float* translation, float* hand) try {
-  return pose_from_i420("hep_poses_from_i420", true, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
+  return pose_from_i420("hep_poses_from_i420: ", true, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
                         PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-// ---- pose errors (evaluator) ----
-int hep_pose_errors_device(const float* points, int num_points, const float* rvec_gt, const float* t_gt, const float* rvec_pred,
-                           const float* t_pred, int num_pairs, int max_points, double* add, double* add_s, void* stream) try {
-  if (!points || !rvec_gt || !t_gt || !rvec_pred || !t_pred || !add || !add_s) return fail(HEP_ERR_INVALID, "bad argument");
-  if (num_points < 1 || num_pairs < 0) return fail(HEP_ERR_INVALID, "num_points must be >= 1 and num_pairs >= 0");
-  if (max_points < 1 || max_points > 1024) return fail(HEP_ERR_UNSUPPORTED, "max_points must be in 1..1024 (the reference uses 1000)");
-  if (num_pairs == 0) return 0;
-  PoseErrArgs a; a.points = points; a.rvec_gt = rvec_gt; a.t_gt = t_gt; a.rvec_pr = rvec_pred; a.t_pr = t_pred;
-  a.add = add; a.add_s = add_s; a.P = num_points; a.D = num_pairs; a.max_points = max_points;
-  launch_pose_errors(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-int hep_pose_errors(int device, const float* points, int num_points, const float* rvec_gt, const float* t_gt, const float* rvec_pred,
-                    const float* t_pred, int num_pairs, int max_points, double* add, double* add_s) try {
-  if (!points || !rvec_gt || !t_gt || !rvec_pred || !t_pred || !add || !add_s) return fail(HEP_ERR_INVALID, "bad argument");
-  if (num_points < 1 || num_pairs < 0) return fail(HEP_ERR_INVALID, "num_points must be >= 1 and num_pairs >= 0");
-  if (num_pairs == 0) return 0;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(HEP_ERR_DEVICE, "no HIP device visible: libhep has no CPU fallback");
-  if (device < 0 || device >= ndev) return fail(HEP_ERR_INVALID, "device index out of range");
-  HIPRET(hipSetDevice(device));
-  const size_t pb = (size_t)num_points * 12, db = (size_t)num_pairs * 12, ob = (size_t)num_pairs * 8;
-  unsigned char* buf = nullptr;
-  HIPRET(hipMalloc((void**)&buf, pb + 4 * db + 2 * ob + 64));
-  struct Free { unsigned char* p; ~Free() { hipFree(p); } } guard{buf};
-  float* d_pts = (float*)buf; float* d_rg = (float*)(buf + pb); float* d_tg = d_rg + 3 * num_pairs; float* d_rp = d_tg + 3 * num_pairs; float* d_tp = d_rp + 3 * num_pairs;
-  double* d_add = (double*)(buf + ((pb + 4 * db + 7) & ~(size_t)7)); double* d_adds = d_add + num_pairs;
-  HIPRET(hipMemcpy(d_pts, points, pb, hipMemcpyHostToDevice));
-  HIPRET(hipMemcpy(d_rg, rvec_gt, db, hipMemcpyHostToDevice)); HIPRET(hipMemcpy(d_tg, t_gt, db, hipMemcpyHostToDevice));
-  HIPRET(hipMemcpy(d_rp, rvec_pred, db, hipMemcpyHostToDevice)); HIPRET(hipMemcpy(d_tp, t_pred, db, hipMemcpyHostToDevice));
-  if (int rc = hep_pose_errors_device(d_pts, num_points, d_rg, d_tg, d_rp, d_tp, num_pairs, max_points, d_add, d_adds, nullptr)) return rc;
-  HIPRET(hipMemcpy(add, d_add, ob, hipMemcpyDeviceToHost));
-  HIPRET(hipMemcpy(add_s, d_adds, ob, hipMemcpyDeviceToHost));
-  return 0;
-} HEP_CATCH_INT
-
-// ---- evaluator: matching and pose metrics of a batch in one launch ----
-static_assert(HEP_SCORE_GT_DOUBLES == SCORE_GT_DOUBLES && HEP_SCORE_RECORD_DOUBLES == SCORE_RECORD_DOUBLES, "the tables of include/hep.h are the kernel's");
-int hep_score_detections_device(const float* det_boxes, const float* det_scores, const int32_t* det_labels, const float* det_rotation,
-                                const float* det_translation, const float* det_hand, int batch, int rows, const double* gt,
-                                const float* points, int num_points, int max_points, int label, float score_threshold,
-                                int max_detections, double iou_threshold, double* records, float* out_scores, int32_t* out_tp,
-                                void* stream) try {
-  // every check before any HIP call
-  const std::pair<const void*, const char*> ptrs[] = {{det_boxes, "det_boxes"}, {det_scores, "det_scores"}, {det_labels, "det_labels"},
-      {det_rotation, "det_rotation"}, {det_translation, "det_translation"}, {gt, "gt"}, {points, "points"}, {records, "records"},
-      {out_scores, "out_scores"}, {out_tp, "out_tp"}};
-  for (const auto& p : ptrs)
-    if (!p.first) return fail(HEP_ERR_INVALID, std::string("hep_score_detections_device: ") + p.second + " is NULL");
-  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_score_detections_device: batch must be >= 1");
-  if (rows < 1 || rows > SCORE_MAX_ROWS) return fail(HEP_ERR_INVALID, "hep_score_detections_device: rows outside 1..256");
-  if (max_detections < 1 || max_detections > rows) return fail(HEP_ERR_INVALID, "hep_score_detections_device: max_detections outside 1..rows");
-  if (num_points < 1) return fail(HEP_ERR_INVALID, "hep_score_detections_device: num_points must be >= 1");
-  if (max_points < 1 || max_points > 1024) return fail(HEP_ERR_INVALID, "hep_score_detections_device: max_points must be in 1..1024 (the reference uses 1000)");
-  ScoreArgs a;
-  a.boxes = det_boxes; a.scores = det_scores; a.labels = det_labels; a.rotation = det_rotation; a.translation = det_translation; a.hand = det_hand;
-  a.gt = gt; a.points = points; a.records = records; a.out_scores = out_scores; a.out_tp = out_tp;
-  a.B = batch; a.rows = rows; a.P = num_points; a.max_points = max_points; a.label = label; a.max_det = max_detections;
-  a.score_thr = score_threshold; a.iou_thr = iou_threshold;
-  launch_score(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-static_assert(HEP_SCORE_MAX_ANNOTATIONS == SCORE_MAX_ANN, "the annotation limit of include/hep.h is the kernel's");
-int hep_score_scene_device(const float* det_boxes, const float* det_scores, const int32_t* det_labels, const float* det_rotation,
-                           const float* det_translation, const float* det_hand, int batch, int rows, const double* gt, int amax,
-                           const float* points, const int32_t* point_offsets, int num_labels, int max_points, float score_threshold,
-                           int max_detections, double iou_threshold, double* records, float* out_scores, int32_t* out_tp,
-                           int32_t* out_labels, int32_t* out_count, void* stream) try {
-  // every check before any HIP call
-  const std::pair<const void*, const char*> ptrs[] = {{det_boxes, "det_boxes"}, {det_scores, "det_scores"}, {det_labels, "det_labels"},
-      {det_rotation, "det_rotation"}, {det_translation, "det_translation"}, {gt, "gt"}, {points, "points"}, {point_offsets, "point_offsets"},
-      {records, "records"}, {out_scores, "out_scores"}, {out_tp, "out_tp"}, {out_labels, "out_labels"}, {out_count, "out_count"}};
-  for (const auto& p : ptrs)
-    if (!p.first) return fail(HEP_ERR_INVALID, std::string("hep_score_scene_device: ") + p.second + " is NULL");
-  if (batch < 1) return fail(HEP_ERR_INVALID, "hep_score_scene_device: batch must be >= 1");
-  if (rows < 1 || rows > SCORE_MAX_ROWS) return fail(HEP_ERR_INVALID, "hep_score_scene_device: rows outside 1..256");
-  if (max_detections < 1 || max_detections > rows) return fail(HEP_ERR_INVALID, "hep_score_scene_device: max_detections outside 1..rows");
-  if (amax < 1 || amax > SCORE_MAX_ANN) return fail(HEP_ERR_INVALID, "hep_score_scene_device: amax outside 1..16");
-  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, "hep_score_scene_device: num_labels outside 1..63");
-  if (point_offsets[0] != 0) return fail(HEP_ERR_INVALID, "hep_score_scene_device: point_offsets[0] must be 0");
-  for (int l = 0; l < num_labels; l++)
-    if (point_offsets[l + 1] <= point_offsets[l])
-      return fail(HEP_ERR_INVALID, "hep_score_scene_device: point_offsets must increase (label " + std::to_string(l) + " has no point)");
-  if (max_points < 1 || max_points > 1024) return fail(HEP_ERR_INVALID, "hep_score_scene_device: max_points must be in 1..1024 (the reference uses 1000)");
-  SceneScoreArgs a;
-  a.boxes = det_boxes; a.scores = det_scores; a.labels = det_labels; a.rotation = det_rotation; a.translation = det_translation; a.hand = det_hand;
-  a.gt = gt; a.points = points; a.records = records; a.out_scores = out_scores; a.out_tp = out_tp; a.out_labels = out_labels; a.out_count = out_count;
-  a.B = batch; a.rows = rows; a.amax = amax; a.num_labels = num_labels; a.max_points = max_points; a.max_det = max_detections;
-  a.score_thr = score_threshold; a.iou_thr = iou_threshold;
-  for (int l = 0; l <= SCORE_MAX_LABELS; l++) a.offsets[l] = l <= num_labels ? point_offsets[l] : point_offsets[num_labels];
-  launch_score_scene(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// ---- pose overlays: annotations and kept detections drawn into the frames in one launch ----
-static_assert(HEP_DRAW_MAX_DETECTIONS == DRAW_MAX_DET && HEP_DRAW_BOX2D == DRAW_BOX2D && HEP_DRAW_CUBOID == DRAW_CUBOID && HEP_DRAW_HAND == DRAW_HAND,
-              "the limits and layer bits of include/hep.h are the kernel's");
-int hep_draw_poses_device(uint8_t* frames, int batch, int height, int width, const double* gt, int amax, const double* camera,
-                          const float* det_boxes, const float* det_scores, const int32_t* det_labels, const float* det_rotation,
-                          const float* det_translation, const float* det_hand, int rows, float score_threshold, int max_detections,
-                          const float* cuboids, const uint8_t* colours, int num_labels, int ann_layers, int det_layers, int thickness,
-                          void* stream) try {
-  // every check before any HIP call
-  const char* who = "hep_draw_poses_device: ";
-  const std::pair<const void*, const char*> ptrs[] = {{frames, "frames"}, {cuboids, "cuboids"}, {colours, "colours"}};
-  for (const auto& p : ptrs)
-    if (!p.first) return fail(HEP_ERR_INVALID, std::string(who) + p.second + " is NULL");
-  if (!gt && !camera) return fail(HEP_ERR_INVALID, std::string(who) + "gt and camera are both NULL (the camera comes from one of them)");
-  if (batch < 1) return fail(HEP_ERR_INVALID, std::string(who) + "batch must be >= 1");
-  if (gt && (amax < 1 || amax > SCORE_MAX_ANN)) return fail(HEP_ERR_INVALID, std::string(who) + "amax outside 1..16");
-  const int given = (det_boxes != nullptr) + (det_scores != nullptr) + (det_labels != nullptr) + (det_rotation != nullptr) + (det_translation != nullptr);
-  if (given != 0 && given != 5)
-    return fail(HEP_ERR_INVALID, std::string(who) + "det_boxes, det_scores, det_labels, det_rotation and det_translation must all be given or all be NULL");
-  if (given == 0 && det_hand) return fail(HEP_ERR_INVALID, std::string(who) + "det_hand without the other det_* arrays");
-  if (given == 5) {
-    if (rows < 1 || rows > SCORE_MAX_ROWS) return fail(HEP_ERR_INVALID, std::string(who) + "rows outside 1..256");
-    if (max_detections < 1 || max_detections > (rows < DRAW_MAX_DET ? rows : DRAW_MAX_DET))
-      return fail(HEP_ERR_INVALID, std::string(who) + "max_detections outside 1..min(rows, 64)");
-  }
-  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, std::string(who) + "num_labels outside 1..63");
-  if (thickness < 1 || thickness > 8) return fail(HEP_ERR_INVALID, std::string(who) + "thickness outside 1..8");
-  const int all_layers = DRAW_BOX2D | DRAW_CUBOID | DRAW_HAND;
-  if ((ann_layers & ~all_layers) || (det_layers & ~all_layers))
-    return fail(HEP_ERR_INVALID, std::string(who) + "layer bits outside HEP_DRAW_BOX2D | HEP_DRAW_CUBOID | HEP_DRAW_HAND");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, std::string(who) + "height and width must be in 16..4096");
-  DrawArgs a;
-  a.frames = frames; a.gt = gt; a.camera = camera;
-  a.boxes = det_boxes; a.scores = det_scores; a.labels = det_labels; a.rotation = det_rotation; a.translation = det_translation; a.hand = det_hand;
-  a.cuboids = cuboids;
-  a.B = batch; a.H = height; a.W = width; a.amax = gt ? amax : 0; a.rows = given ? rows : 0; a.max_det = given ? max_detections : 0;
-  a.num_labels = num_labels; a.ann_layers = ann_layers; a.det_layers = det_layers; a.thickness = thickness; a.score_thr = score_threshold;
-  memset(a.colours, 0, sizeof(a.colours));
-  memcpy(a.colours, colours, (size_t)num_labels * 3);
-  launch_draw(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// ---- object models under poses: mask, depth and filled overlays from one z-buffered rasteriser ----
-static_assert(HEP_RENDER_MAX_POSES == RENDER_MAX_POSES && HEP_RENDER_MAX_ELEMENTS == RENDER_MAX_ELEMS, "the limits of include/hep.h are the kernel's");
-static int render_range(int batch, int height, int width, int pmax, int num_vertices) {
-  const char* who = "hep_render_models_device: ";
-  if (batch < 1) return fail(HEP_ERR_INVALID, std::string(who) + "batch must be >= 1");
-  if (pmax < 1 || pmax > RENDER_MAX_POSES) return fail(HEP_ERR_INVALID, std::string(who) + "pmax outside 1..16");
-  if (num_vertices < 1 || num_vertices > RENDER_MAX_ELEMS) return fail(HEP_ERR_INVALID, std::string(who) + "num_vertices outside 1..16777216");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, std::string(who) + "height and width must be in 16..4096");
-  return 0;
-}
-
-int64_t hep_render_workspace_bytes(int batch, int height, int width, int pmax, int num_vertices) try {
-  if (int rc = render_range(batch, height, width, pmax, num_vertices)) return rc;
-  return (int64_t)batch * pmax * ((int64_t)num_vertices + 1) * (int64_t)sizeof(RenderVertex);      // the vertex records, then one bounding box per (image, slot)
-} HEP_CATCH_INT
-
-int hep_render_models_device(const double* poses, int batch, int pmax, const double* camera, const float* vertices, int num_vertices,
-                             const int32_t* faces, int num_faces, const int32_t* face_start, int num_labels, int height, int width,
-                             uint8_t* mask, float* depth, uint8_t* frames, const uint8_t* colours, int alpha,
-                             void* workspace, int64_t workspace_bytes, void* stream) try {
-  // every check before any HIP call
-  const char* who = "hep_render_models_device: ";
-  const std::pair<const void*, const char*> ptrs[] = {{poses, "poses"}, {camera, "camera"}, {vertices, "vertices"}, {faces, "faces"},
-                                                      {face_start, "face_start"}, {workspace, "workspace"}};
-  for (const auto& p : ptrs)
-    if (!p.first) return fail(HEP_ERR_INVALID, std::string(who) + p.second + " is NULL");
-  if (!mask && !depth && !frames) return fail(HEP_ERR_INVALID, std::string(who) + "mask, depth and frames are all NULL");
-  if (int rc = render_range(batch, height, width, pmax, num_vertices)) return rc;
-  if (num_faces < 1 || num_faces > RENDER_MAX_ELEMS) return fail(HEP_ERR_INVALID, std::string(who) + "num_faces outside 1..16777216");
-  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, std::string(who) + "num_labels outside 1..63");
-  if (face_start[0] < 0 || face_start[num_labels] > num_faces) return fail(HEP_ERR_INVALID, std::string(who) + "face_start leaves 0..num_faces");
-  for (int l = 0; l < num_labels; l++)
-    if (face_start[l] > face_start[l + 1]) return fail(HEP_ERR_INVALID, std::string(who) + "face_start decreases");
-  if (frames && !colours) return fail(HEP_ERR_INVALID, std::string(who) + "frames without colours");
-  if (frames && (alpha < 0 || alpha > 256)) return fail(HEP_ERR_INVALID, std::string(who) + "alpha outside 0..256");
-  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, std::string(who) + "workspace must be 16-byte aligned");
-  if (workspace_bytes < hep_render_workspace_bytes(batch, height, width, pmax, num_vertices))
-    return fail(HEP_ERR_INVALID, std::string(who) + "workspace too small (hep_render_workspace_bytes)");
-  RenderArgs a;
-  a.poses = poses; a.camera = camera; a.vertices = vertices; a.faces = faces; a.mask = mask; a.depth = depth; a.frames = frames;
-  a.ws = (RenderVertex*)workspace;
-  a.boxes = (int4*)(a.ws + (int64_t)batch * pmax * num_vertices);
-  a.B = batch; a.H = height; a.W = width; a.pmax = pmax; a.V = num_vertices; a.F = num_faces; a.num_labels = num_labels; a.alpha = frames ? alpha : 0;
-  memset(a.face_start, 0, sizeof(a.face_start));
-  memcpy(a.face_start, face_start, (size_t)(num_labels + 1) * sizeof(int32_t));
-  memset(a.colours, 0, sizeof(a.colours));
-  if (frames) memcpy(a.colours, colours, (size_t)num_labels * 3);
-  launch_render(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// ---- BOP pose errors of matched pairs: MSSD / MSPD and VSD ----
-static_assert(HEP_BOP_PAIR_DOUBLES == BOP_PAIR_DOUBLES && HEP_BOP_MAX_SYMMETRIES == BOP_MAX_SYM && HEP_BOP_MAX_TAUS == BOP_MAX_TAUS,
-              "the table and limits of include/hep.h are the kernel's");
-// a host start table [num_labels + 1]: starts at 0 or above, increases strictly, ends inside `count`, at most `most` entries per label (0: no limit)
-static int bop_start_table(const std::string& who, const char* name, const int32_t* start, int num_labels, int count, int most) {
-  if (start[0] < 0) return fail(HEP_ERR_INVALID, who + name + " starts below 0");
-  for (int l = 0; l < num_labels; l++) {
-    if (start[l + 1] <= start[l]) return fail(HEP_ERR_INVALID, who + name + " must increase (label " + std::to_string(l) + " has no entry)");
-    if (most && start[l + 1] - start[l] > most) return fail(HEP_ERR_INVALID, who + name + ": label " + std::to_string(l) + " has more than " + std::to_string(most) + " entries");
-  }
-  if (start[num_labels] > count) return fail(HEP_ERR_INVALID, who + name + " ends past the array");
-  return 0;
-}
-
-int hep_bop_point_errors_device(const double* pairs, int n, const float* vertices, int num_vertices, const int32_t* vertex_start,
-                                const double* symmetries, int num_symmetries, const int32_t* symmetry_start, int num_labels,
-                                double* errors, void* stream) try {
-  // every check before any HIP call
-  const std::string who = "hep_bop_point_errors_device: ";
-  const std::pair<const void*, const char*> ptrs[] = {{pairs, "pairs"}, {vertices, "vertices"}, {vertex_start, "vertex_start"}, {symmetries, "symmetries"},
-                                                      {symmetry_start, "symmetry_start"}, {errors, "errors"}};
-  for (const auto& p : ptrs)
-    if (!p.first) return fail(HEP_ERR_INVALID, who + p.second + " is NULL");
-  if (n < 1) return fail(HEP_ERR_INVALID, who + "n must be >= 1");
-  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, who + "num_labels outside 1..63");
-  if (num_vertices < 1 || num_symmetries < 1) return fail(HEP_ERR_INVALID, who + "num_vertices and num_symmetries must be >= 1");
-  if (int rc = bop_start_table(who, "vertex_start", vertex_start, num_labels, num_vertices, 0)) return rc;
-  if (int rc = bop_start_table(who, "symmetry_start", symmetry_start, num_labels, num_symmetries, BOP_MAX_SYM)) return rc;
-  BopPointArgs a;
-  a.pairs = pairs; a.vertices = vertices; a.sym = symmetries; a.out = errors; a.n = n; a.num_labels = num_labels;
-  for (int l = 0; l <= SCORE_MAX_LABELS; l++) {
-    a.vertex_start[l] = vertex_start[l <= num_labels ? l : num_labels];
-    a.sym_start[l] = symmetry_start[l <= num_labels ? l : num_labels];
-  }
-  launch_bop_points(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-static int bop_vsd_range(int n, int num_taus) {
-  const char* who = "hep_bop_vsd_device: ";
-  if (n < 1) return fail(HEP_ERR_INVALID, std::string(who) + "n must be >= 1");
-  if (num_taus < 1 || num_taus > BOP_MAX_TAUS) return fail(HEP_ERR_INVALID, std::string(who) + "num_taus outside 1..16");
-  return 0;
-}
-
-int64_t hep_bop_workspace_bytes(int n, int num_taus) try {
-  if (int rc = bop_vsd_range(n, num_taus)) return rc;
-  return ((int64_t)n * (2 + num_taus) * (int64_t)sizeof(int32_t) + 15) & ~(int64_t)15;      // the counters, rounded up to the alignment
-} HEP_CATCH_INT
-
-int hep_bop_vsd_device(const double* pairs, int n, int num_labels, const float* depth_gt, const float* depth_est, const float* depth_test,
-                       int num_images, int height, int width, double delta, const double* taus, int num_taus, double* vsd, int32_t* counts,
-                       void* workspace, int64_t workspace_bytes, void* stream) try {
-  // every check before any HIP call
-  const std::string who = "hep_bop_vsd_device: ";
-  const std::pair<const void*, const char*> ptrs[] = {{pairs, "pairs"}, {depth_gt, "depth_gt"}, {depth_est, "depth_est"}, {taus, "taus"}, {vsd, "vsd"},
-                                                      {counts, "counts"}, {workspace, "workspace"}};
-  for (const auto& p : ptrs)
-    if (!p.first) return fail(HEP_ERR_INVALID, who + p.second + " is NULL");
-  if (int rc = bop_vsd_range(n, num_taus)) return rc;
-  if (num_labels < 1 || num_labels > SCORE_MAX_LABELS) return fail(HEP_ERR_INVALID, who + "num_labels outside 1..63");
-  if (depth_test && num_images < 1) return fail(HEP_ERR_INVALID, who + "num_images must be >= 1 with a depth_test");
-  if (!(std::isfinite(delta) && delta > 0.0)) return fail(HEP_ERR_INVALID, who + "delta must be finite and positive");
-  for (int j = 0; j < num_taus; j++)
-    if (!(std::isfinite(taus[j]) && taus[j] > 0.0)) return fail(HEP_ERR_INVALID, who + "tau " + std::to_string(j) + " must be finite and positive");
-  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, who + "workspace must be 16-byte aligned");
-  if (workspace_bytes < hep_bop_workspace_bytes(n, num_taus)) return fail(HEP_ERR_INVALID, who + "workspace too small (hep_bop_workspace_bytes)");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, who + "height and width must be in 16..4096");
-  BopVsdArgs a;
-  a.pairs = pairs; a.depth_gt = depth_gt; a.depth_est = depth_est; a.depth_test = depth_test; a.ws = (int32_t*)workspace; a.vsd = vsd; a.counts = counts;
-  a.n = n; a.H = height; a.W = width; a.T = num_taus; a.images = depth_test ? num_images : 0; a.num_labels = num_labels; a.delta = delta;
-  for (int j = 0; j < BOP_MAX_TAUS; j++) a.taus[j] = j < num_taus ? taus[j] : 0.0;
-  launch_bop_vsd(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
 } HEP_CATCH_INT
 
 // ---- introspection ----

@@ -1,16 +1,15 @@
 // hep_api_train.cpp - the training side of the C ABI of libhep.so (include/hep.h): every entry point that takes no hep_handle.
 // Anchor targets, the losses and their backward, the three trainable parts (heads, neck, backbone), the augmentations, the
 // optimiser and the translation glue.  All of it is stateless: arguments are checked on the host, then the kernels are launched
-// on the caller's stream into the caller's buffers.  (Sessions and inference: hep_api.cpp.)
+// on the caller's stream into the caller's buffers.  (Sessions and inference: hep_api.cpp; evaluation and visualisation: hep_api_eval.cpp.)
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
 
-#include "hep.h"
 #include "hep_api_util.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 
 using namespace hep;
 
@@ -116,16 +115,16 @@ template <class Plan> int64_t workspace_bytes(const Part<Plan>& part, int phi, i
 // sync (the *_sync group): batch statistics over all replicas through the caller's hook, checked first; a hook that fails ends the launch (GDSyncFailed)
 template <class Plan, class Launch> int run(const Part<Plan>& part, int phi, int num_classes, int size, int batch, int bn_mode, float momentum, void* workspace,
                                             size_t workspace_bytes, Launch launch, const hep_sync* const* sync = nullptr) {
-  const std::string name = part.name;
-  if (sync && (!*sync || !(*sync)->sum)) return fail(HEP_ERR_INVALID, name + ": sync and sync->sum must not be NULL");
-  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return fail(HEP_ERR_INVALID, name + ": the BatchNorm momentum must be in [0, 1]");
+  const std::string name = part.name, prefix = name + ": "; const Check c{prefix.c_str()};
+  if (sync && (!*sync || !(*sync)->sum)) return c.fail(HEP_ERR_INVALID, "sync and sync->sum must not be NULL");
+  if (bn_mode == HEP_BN_BATCH && !(momentum >= 0.0f && momentum <= 1.0f)) return c.fail(HEP_ERR_INVALID, "the BatchNorm momentum must be in [0, 1]");
   Plan p; if (int rc = plan_part(part, phi, num_classes, size, batch, bn_mode, &p, false, sync != nullptr)) return rc;
-  if (((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, name + ": the workspace must be 16-byte aligned");
-  if (workspace_bytes < (size_t)p.ws_floats * sizeof(float)) return fail(HEP_ERR_INVALID, name + ": the workspace is smaller than hep_" + name + "_workspace_bytes");
+  CHECKED(c.aligned(workspace, 16, "the workspace"));
+  if (workspace_bytes < (size_t)p.ws_floats * sizeof(float)) return c.fail(HEP_ERR_INVALID, "the workspace is smaller than hep_" + name + "_workspace_bytes");
   try {
     launch(p, (float*)workspace);
   } catch (const GDSyncFailed& e) {
-    return fail(HEP_ERR_DEVICE, name + ": the sum hook (hep_sync.sum) returned " + std::to_string(e.rc) + ": nothing further was launched");
+    return c.fail(HEP_ERR_DEVICE, "the sum hook (hep_sync.sum) returned " + std::to_string(e.rc) + ": nothing further was launched");
   }
   HIPRET(hipGetLastError());
   return 0;
@@ -154,7 +153,7 @@ int64_t hep_heads_workspace_bytes(int phi, int num_classes, int size, int batch)
 int hep_heads_forward_device_bn(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch, float* const outs[5],
                                 void* workspace, size_t workspace_bytes, int bn_mode, float momentum, float* stats_out, void* stream) try {
   if (!params || !feats || !outs || !workspace || any_null(feats, 5) || any_null(outs, 5)) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  CHECKED(Check{"heads: "}.aligned(params, 16, "params"));
   return run(kHeads, phi, num_classes, size, batch, bn_mode, momentum, workspace, workspace_bytes,
              [&](const HGPlan& p, float* ws) { launch_heads_forward(p, params, feats, outs, ws, (hipStream_t)stream, momentum, stats_out); });
 } HEP_CATCH_INT
@@ -165,7 +164,7 @@ int hep_heads_forward_device(const float* params, const float* const feats[5], i
 int hep_heads_backward_device_bn(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch, float* grad_params,
                                  float* const grad_feats[5], void* workspace, size_t workspace_bytes, int bn_mode, void* stream) try {
   if (!params || !grad_outs || !grad_params || !workspace || any_null(grad_outs, 5) || (grad_feats && any_null(grad_feats, 5))) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  CHECKED(Check{"heads: "}.aligned(params, 16, "params"));
   return run(kHeads, phi, num_classes, size, batch, bn_mode, 0.0f, workspace, workspace_bytes,
              [&](const HGPlan& p, float* ws) { launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, ws, (hipStream_t)stream); });
 } HEP_CATCH_INT
@@ -178,14 +177,14 @@ int64_t hep_heads_workspace_bytes_sync(int phi, int num_classes, int size, int b
 int hep_heads_forward_device_sync(const float* params, const float* const feats[5], int phi, int num_classes, int size, int batch, float* const outs[5],
                                   void* workspace, size_t workspace_bytes, float momentum, float* stats_out, const hep_sync* sync, void* stream) try {
   if (!params || !feats || !outs || !workspace || any_null(feats, 5) || any_null(outs, 5)) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  CHECKED(Check{"heads: "}.aligned(params, 16, "params"));
   return run(kHeads, phi, num_classes, size, batch, HEP_BN_BATCH, momentum, workspace, workspace_bytes,
              [&](const HGPlan& p, float* ws) { launch_heads_forward(p, params, feats, outs, ws, (hipStream_t)stream, momentum, stats_out, sync); }, &sync);
 } HEP_CATCH_INT
 int hep_heads_backward_device_sync(const float* params, const float* const grad_outs[5], int phi, int num_classes, int size, int batch, float* grad_params,
                                    float* const grad_feats[5], void* workspace, size_t workspace_bytes, const hep_sync* sync, void* stream) try {
   if (!params || !grad_outs || !grad_params || !workspace || any_null(grad_outs, 5) || (grad_feats && any_null(grad_feats, 5))) return fail(HEP_ERR_INVALID, "bad argument");
-  if (((uintptr_t)params & 15) != 0) return fail(HEP_ERR_INVALID, "heads: params must be 16-byte aligned");
+  CHECKED(Check{"heads: "}.aligned(params, 16, "params"));
   return run(kHeads, phi, num_classes, size, batch, HEP_BN_BATCH, 0.0f, workspace, workspace_bytes,
              [&](const HGPlan& p, float* ws) { launch_heads_backward(p, params, grad_outs, grad_params, grad_feats, ws, (hipStream_t)stream, sync); }, &sync);
 } HEP_CATCH_INT
@@ -277,13 +276,6 @@ int hep_backbone_backward_device_sync(const float* params, const float* const gr
 } HEP_CATCH_INT
 
 // ---- training input: 6DoF augmentation + preprocess (k_augment.hip) ----
-static int augment_range(int batch, int height, int width, int size, int kmax) {
-  if (batch < 1) return fail(HEP_ERR_INVALID, "augment: batch must be >= 1");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, "augment: height and width must be in [16, 4096]");
-  if (size < 16 || size > 4096 || size % 4 != 0) return fail(HEP_ERR_UNSUPPORTED, "augment: size must be a multiple of 4 in [16, 4096]");
-  if (kmax < 1 || kmax > AUG_MAX_K) return fail(HEP_ERR_UNSUPPORTED, "augment: kmax must be in 1..16 annotations per image");
-  return 0;
-}
 static int64_t augment_partial_bytes(int batch, int height, int kmax) {
   const int64_t tiles = (height + AUG_TILE_ROWS - 1) / AUG_TILE_ROWS;
   return ((int64_t)batch * tiles * (4 * kmax + 1) * 4 + 255) & ~(int64_t)255;
@@ -291,7 +283,10 @@ static int64_t augment_partial_bytes(int batch, int height, int kmax) {
 
 // the box partials and the uint8 frame of the resize launch (counted whether or not this size needs it: the figure never shrinks as an argument grows)
 int64_t hep_augment_workspace_bytes(int batch, int height, int width, int size, int kmax) try {
-  if (int rc = augment_range(batch, height, width, size, kmax)) return rc;
+  const Check c{"augment: "};      // (hep_augment_6dof_device takes these refusals from here, with the figure)
+  CHECKED(c.at_least("batch", batch, 1)); CHECKED(c.frame(height, width, true));
+  if (size < 16 || size > 4096 || size % 4 != 0) return c.fail(HEP_ERR_UNSUPPORTED, "size must be a multiple of 4 in [16, 4096]");
+  if (kmax < 1 || kmax > AUG_MAX_K) return c.fail(HEP_ERR_UNSUPPORTED, "kmax must be in 1..16 annotations per image");
   return augment_partial_bytes(batch, height, kmax) + (((int64_t)batch * height * width * 3 + 255) & ~(int64_t)255);
 } HEP_CATCH_INT
 
@@ -300,29 +295,23 @@ int hep_augment_6dof_device(const uint8_t* rgb_hwc, const uint8_t* mask, const d
                             const int32_t* num_gt, int batch, int height, int width, int size, int kmax, float translation_scale_norm,
                             float* image_nchw, uint8_t* mask_out, float* camera, double* gt_boxes, int32_t* gt_labels, float* gt_transform,
                             int32_t* gt_num, int32_t* applied, void* workspace, int64_t workspace_bytes, void* stream) try {
+  const Check c{"augment: "};
   if (!rgb_hwc || !mask || !xform || !camera_k || !boxes || !labels || !mask_values || !rvec || !tvec || !extra || !num_gt)
-    return fail(HEP_ERR_INVALID, "augment: a required input pointer is NULL");
+    return c.fail(HEP_ERR_INVALID, "a required input pointer is NULL");
   if (!image_nchw || !camera || !gt_boxes || !gt_labels || !gt_transform || !gt_num || !applied)
-    return fail(HEP_ERR_INVALID, "augment: a required output pointer is NULL (only mask_out may be)");
-  if (!workspace) return fail(HEP_ERR_INVALID, "augment: workspace is NULL");
-  if (int rc = augment_range(batch, height, width, size, kmax)) return rc;
-  if (((uintptr_t)image_nchw & 15) != 0 || ((uintptr_t)workspace & 15) != 0) return fail(HEP_ERR_INVALID, "augment: image_nchw and workspace must be 16-byte aligned");
-  const int64_t need = hep_augment_workspace_bytes(batch, height, width, size, kmax);
-  if (workspace_bytes < need) return fail(HEP_ERR_INVALID, "augment: workspace too small (hep_augment_workspace_bytes)");
+    return c.fail(HEP_ERR_INVALID, "a required output pointer is NULL (only mask_out may be)");
+  CHECKED(c.ptrs({{workspace, "workspace"}}));
+  const int64_t need = hep_augment_workspace_bytes(batch, height, width, size, kmax); if (need < 0) return (int)need;
+  if (((uintptr_t)image_nchw & 15) != 0 || ((uintptr_t)workspace & 15) != 0) return c.fail(HEP_ERR_INVALID, "image_nchw and workspace must be 16-byte aligned");
+  CHECKED(c.workspace(workspace, workspace_bytes, need, "hep_augment_workspace_bytes"));
   AugmentArgs a;
   a.rgb = rgb_hwc; a.mask = mask; a.xform = xform; a.camera_k = camera_k; a.boxes = boxes; a.labels = labels; a.mask_values = mask_values;
   a.rvec = rvec; a.tvec = tvec; a.extra = extra; a.num_gt = num_gt;
   a.B = batch; a.H = height; a.W = width; a.S = size; a.kmax = kmax; a.tiles = (height + AUG_TILE_ROWS - 1) / AUG_TILE_ROWS;
   a.tsn = translation_scale_norm;
-  // preprocess_image (common.py:576-607), as hep_preprocess_u8_device: the longer side becomes size, the other int(side * scale)
-  const int side = std::max(height, width);
-  a.resize = side != size;
-  a.image_scale = (double)size / side;
-  a.nh = height > width ? size : (int)(height * a.image_scale);
-  a.nw = height > width ? (int)(width * a.image_scale) : size;
-  if (!a.resize) { a.nh = height; a.nw = width; }
-  if (a.nh > size || a.nw > size || a.nh < 1 || a.nw < 1) return fail(HEP_ERR_UNSUPPORTED, "augment: resized frame does not fit the network size");
-  a.inv_scale_x = (double)width / a.nw; a.inv_scale_y = (double)height / a.nh;
+  ResizeGeom g;      // preprocess_image, as hep_preprocess_u8_device
+  if (!resize_geometry(height, width, size, &g)) return c.fail(HEP_ERR_UNSUPPORTED, "resized frame does not fit the network size");
+  a.resize = g.resize; a.image_scale = g.scale; a.nh = g.nh; a.nw = g.nw; a.inv_scale_x = g.inv_scale_x; a.inv_scale_y = g.inv_scale_y;
   a.image = image_nchw; a.mask_out = mask_out; a.camera = camera; a.gt_boxes = gt_boxes; a.gt_labels = gt_labels; a.gt_transform = gt_transform;
   a.gt_num = gt_num; a.applied = applied;
   a.partials = (int32_t*)workspace; a.frame_u8 = (uint8_t*)workspace + augment_partial_bytes(batch, height, kmax);
@@ -332,31 +321,28 @@ int hep_augment_6dof_device(const uint8_t* rgb_hwc, const uint8_t* mask, const d
 } HEP_CATCH_INT
 
 // ---- training input: colour augmentation (k_colour.hip) ----
-static int colour_range(int batch, int height, int width) {
-  if (batch < 1) return fail(HEP_ERR_INVALID, "colour: batch must be >= 1");
-  if (height < 16 || height > 4096 || width < 16 || width > 4096) return fail(HEP_ERR_UNSUPPORTED, "colour: height and width must be in [16, 4096]");
-  if (batch > 65535) return fail(HEP_ERR_UNSUPPORTED, "colour: batch must be at most 65535");
-  return 0;
-}
 static int64_t colour_counter_bytes(int batch) { return ((int64_t)batch * 3 * COL_COUNTERS * 4 + 255) & ~(int64_t)255; }
 static int64_t colour_frame_bytes(int batch, int height, int width) { return ((int64_t)batch * height * width * 3 + 255) & ~(int64_t)255; }
 
 // the counters and the two frames the operations between an image's first and last go through
 int64_t hep_colour_workspace_bytes(int batch, int height, int width) try {
-  if (int rc = colour_range(batch, height, width)) return rc;
+  const Check c{"colour: "};      // (hep_colour_augment_device takes these refusals from here, with the figure)
+  CHECKED(c.at_least("batch", batch, 1)); CHECKED(c.frame(height, width, true));
+  if (batch > 65535) return c.fail(HEP_ERR_UNSUPPORTED, "batch must be at most 65535");
   return colour_counter_bytes(batch) + 2 * colour_frame_bytes(batch, height, width);
 } HEP_CATCH_INT
 
 int hep_colour_augment_device(const uint8_t* rgb_hwc, const int32_t* ops, const float* args, int batch, int height, int width,
                               uint8_t* out_hwc, void* workspace, int64_t workspace_bytes, void* stream) try {
-  if (!rgb_hwc || !ops || !args) return fail(HEP_ERR_INVALID, "colour: a required input pointer is NULL");
-  if (!out_hwc) return fail(HEP_ERR_INVALID, "colour: the output pointer is NULL");
-  if (!workspace) return fail(HEP_ERR_INVALID, "colour: workspace is NULL");
-  if (out_hwc == rgb_hwc) return fail(HEP_ERR_INVALID, "colour: out_hwc must not be rgb_hwc (the filters read neighbours)");
-  if (int rc = colour_range(batch, height, width)) return rc;
+  const Check c{"colour: "};
+  if (!rgb_hwc || !ops || !args) return c.fail(HEP_ERR_INVALID, "a required input pointer is NULL");
+  if (!out_hwc) return c.fail(HEP_ERR_INVALID, "the output pointer is NULL");
+  CHECKED(c.ptrs({{workspace, "workspace"}}));
+  if (out_hwc == rgb_hwc) return c.fail(HEP_ERR_INVALID, "out_hwc must not be rgb_hwc (the filters read neighbours)");
+  const int64_t need = hep_colour_workspace_bytes(batch, height, width); if (need < 0) return (int)need;
   if (((uintptr_t)workspace & 15) != 0 || ((uintptr_t)ops & 3) != 0 || ((uintptr_t)args & 3) != 0)
-    return fail(HEP_ERR_INVALID, "colour: workspace must be 16-byte, ops and args 4-byte aligned");
-  if (workspace_bytes < hep_colour_workspace_bytes(batch, height, width)) return fail(HEP_ERR_INVALID, "colour: workspace too small (hep_colour_workspace_bytes)");
+    return c.fail(HEP_ERR_INVALID, "workspace must be 16-byte, ops and args 4-byte aligned");
+  CHECKED(c.workspace(workspace, workspace_bytes, need, "hep_colour_workspace_bytes"));
   ColourArgs a;
   a.rgb = rgb_hwc; a.ops = ops; a.args = args; a.B = batch; a.H = height; a.W = width; a.out = out_hwc;
   a.counters = (uint32_t*)workspace;
@@ -369,16 +355,16 @@ int hep_colour_augment_device(const uint8_t* rgb_hwc, const int32_t* ops, const 
 } HEP_CATCH_INT
 
 // ---- the training step between the parts: optimiser, gradient norm, translation glue (k_train.hip) ----
-static int optim_check(const char* what, int64_t n, int optimizer, const void* const* ptrs, int count, const void* kind, const void* state) {
-  if (n <= 0) return fail(HEP_ERR_INVALID, std::string(what) + ": n must be > 0");
-  if (!kind || !state) return fail(HEP_ERR_INVALID, std::string(what) + ": kind or state is NULL");
+static int optim_check(const Check& c, int64_t n, int optimizer, const void* const* ptrs, int count, const void* kind, const void* state) {
+  if (n <= 0) return c.fail(HEP_ERR_INVALID, "n must be > 0");
+  if (!kind || !state) return c.fail(HEP_ERR_INVALID, "kind or state is NULL");
   for (int i = 0; i < count; i++) {
-    if (!ptrs[i]) return fail(HEP_ERR_INVALID, std::string(what) + ": a required pointer is NULL");
-    if (((uintptr_t)ptrs[i] & 15) != 0) return fail(HEP_ERR_INVALID, std::string(what) + ": the float buffers must be 16-byte aligned");
+    if (!ptrs[i]) return c.fail(HEP_ERR_INVALID, "a required pointer is NULL");
+    CHECKED(c.aligned(ptrs[i], 16, "the float buffers"));
   }
-  if (((uintptr_t)kind & 3) != 0 || ((uintptr_t)state & 15) != 0) return fail(HEP_ERR_INVALID, std::string(what) + ": kind must be 4-byte, state 16-byte aligned");
+  if (((uintptr_t)kind & 3) != 0 || ((uintptr_t)state & 15) != 0) return c.fail(HEP_ERR_INVALID, "kind must be 4-byte, state 16-byte aligned");
   if (optimizer != HEP_OPT_ADAM && optimizer != HEP_OPT_SGD_NESTEROV)
-    return fail(HEP_ERR_UNSUPPORTED, std::string(what) + ": optimizer " + std::to_string(optimizer) + " is not built (HEP_OPT_ADAM = 0, HEP_OPT_SGD_NESTEROV = 1)");
+    return c.fail(HEP_ERR_UNSUPPORTED, "optimizer " + std::to_string(optimizer) + " is not built (HEP_OPT_ADAM = 0, HEP_OPT_SGD_NESTEROV = 1)");
   return 0;
 }
 
@@ -390,8 +376,9 @@ int64_t hep_optim_workspace_bytes(int64_t n) try {
 int hep_optim_grad_norm_device(const float* grad, const uint8_t* kind, int64_t n, int optimizer, float beta1, float beta2, float max_norm,
                                void* state, void* workspace, size_t workspace_bytes, void* stream) try {
   const void* ptrs[2] = {grad, workspace};
-  if (int rc = optim_check("optim_grad_norm", n, optimizer, ptrs, 2, kind, state)) return rc;
-  if ((int64_t)workspace_bytes < hep_optim_workspace_bytes(n)) return fail(HEP_ERR_INVALID, "optim_grad_norm: workspace too small (hep_optim_workspace_bytes)");
+  const Check c{"optim_grad_norm: "};
+  CHECKED(optim_check(c, n, optimizer, ptrs, 2, kind, state));
+  CHECKED(c.workspace(workspace, (int64_t)workspace_bytes, hep_optim_workspace_bytes(n), "hep_optim_workspace_bytes"));
   OptimArgs a{};
   a.grad = grad; a.kind = kind; a.n = n; a.optimizer = optimizer; a.blocks = optim_grid(n); a.beta1 = beta1; a.beta2 = beta2; a.max_norm = max_norm;
   a.state = (OptimState*)state; a.partials = (double*)workspace;
@@ -403,8 +390,9 @@ int hep_optim_grad_norm_device(const float* grad, const uint8_t* kind, int64_t n
 int hep_optim_update_device(float* params, const float* grad, float* m, float* v, const float* stats, const uint8_t* kind, int64_t n,
                             int optimizer, float lr, float beta1, float beta2, float eps, const void* state, void* stream) try {
   const void* ptrs[4] = {params, grad, m, v};
-  if (int rc = optim_check("optim_update", n, optimizer, ptrs, optimizer == HEP_OPT_SGD_NESTEROV && !v ? 3 : 4, kind, state)) return rc;
-  if (stats && ((uintptr_t)stats & 15) != 0) return fail(HEP_ERR_INVALID, "optim_update: the float buffers must be 16-byte aligned");
+  const Check c{"optim_update: "};
+  CHECKED(optim_check(c, n, optimizer, ptrs, optimizer == HEP_OPT_SGD_NESTEROV && !v ? 3 : 4, kind, state));
+  CHECKED(c.aligned(stats, 16, "the float buffers"));      // (stats may be NULL)
   OptimArgs a{};
   a.params = params; a.grad = grad; a.m = m; a.v = v; a.stats = stats; a.kind = kind; a.n = n; a.optimizer = optimizer; a.blocks = optim_grid(n);
   a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.state = (OptimState*)state;

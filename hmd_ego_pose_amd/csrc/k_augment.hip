@@ -13,7 +13,7 @@
 //   nearest: rd = 512, source = X >> 10; bilinear: rd = 16, X >>= 5, source = X >> 5, fraction X & 31 (INTER_BITS = 5), int32
 //   weights (32-fy)(32-fx)32, (32-fy)fx 32, fy(32-fx)32, fy fx 32 (sum 32768), out = (sum w p + 16384) >> 15.
 // No atomics on global memory, no float atomics, no allocation: the partials have a fixed place per workgroup in the caller's workspace.
-#include "hep_internal.h"
+#include "hep_train.h"
 
 #include <cstdint>
 

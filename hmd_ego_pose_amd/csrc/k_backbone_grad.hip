@@ -31,7 +31,7 @@
 #include "hep.h"
 #include "grad_dev.h"
 #include "hep_host.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 
 #define BG_RED_JOBS 4        // reduce jobs of one launch: a weight, gamma, beta, statistics
 

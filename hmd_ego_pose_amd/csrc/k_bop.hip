@@ -21,7 +21,7 @@
 //   workgroup into the workspace with vector integer atomics - integer sums: the result does not depend on the order; one thread per
 //   pair then writes the counts and the T divisions.
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_eval.h"
 
 #define BOP_THREADS 256
 #define BOP_PPT 8                                                  // pixels of a thread in bop_vsd_kernel

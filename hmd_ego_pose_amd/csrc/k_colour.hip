@@ -10,7 +10,7 @@
 // An image's first operation reads rgb, its last writes out, the ones between ping-pong through two workspace frames; an image without an
 // operation is copied by the last launch.  Every rounding of the blend and of the autocontrast table is stated: this file is compiled with
 // -ffp-contract=off (Makefile).  No float atomics, no allocation, no host synchronisation.
-#include "hep_internal.h"
+#include "hep_train.h"
 
 #include <cstdint>
 

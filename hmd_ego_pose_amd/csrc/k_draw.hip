@@ -15,7 +15,7 @@
 // No atomics, no pixel has two writers, no floating point after step 3: the result is deterministic by construction.  The file is built
 // with -ffp-contract=off (Makefile), so the projection's statements round as tests/_draw.py's do.
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_eval.h"
 #include "eval_dev.h"
 
 #define DRAW_THREADS 256

@@ -12,7 +12,8 @@
 // order: results are bit-reproducible.  This is HBM/latency-trivial work (a pair is ~1 M distance evaluations) -
 // it exists so that the evaluator's metric loop (eval/common.py:866-1121) runs next to the detections it scores.
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_eval.h"
+#include "hep_train.h"
 #include "loss_dev.h"
 #include "eval_dev.h"
 

@@ -23,7 +23,7 @@
 // chain) plus a second pass that adds the partials in a fixed order in double: bit-reproducible, no float atomics.
 #include "hep.h"
 #include "grad_dev.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 
 static const int kFpnWidth[8] = {64, 88, 112, 160, 224, 288, 384, 384};
 static const int kHeadDepth[8] = {3, 3, 3, 4, 4, 4, 5, 5};

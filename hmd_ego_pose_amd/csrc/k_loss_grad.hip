@@ -20,7 +20,7 @@
 #include <atomic>
 
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 #include "loss_dev.h"
 
 #define LG_WAVE 64              // gfx950: wave64 (the ballots below are 64-bit)

@@ -31,7 +31,7 @@
 
 #include "hep.h"
 #include "grad_dev.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 
 #define NG_FUSION_EPS 1e-4f
 #define NG_RED_JOBS 6        // reduce jobs of one launch: pointwise weight, depthwise weight, gamma, beta, statistics, bias

@@ -29,7 +29,7 @@
 // winner is a minimum over a total order, so the result does not depend on where the list was cut.  Tiles that no face meets still write
 // the zeros of mask and depth.
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_eval.h"
 
 #define RENDER_THREADS 256
 #define RENDER_TW 32

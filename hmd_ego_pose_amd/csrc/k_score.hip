@@ -23,7 +23,7 @@
 // back end whatever a pragma says) - only then does the inlined pose_error_pair round like pose_error_kernel's.  The one
 // place where a fused product could flip a DECISION, the IoU, keeps its products out of the adder's reach with nofuse().
 #include "hep_dev.h"
-#include "hep_internal.h"
+#include "hep_eval.h"
 #include "eval_dev.h"
 
 // an opaque pass through a VGPR pair: the product is rounded before the sum sees it

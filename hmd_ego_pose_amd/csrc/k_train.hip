@@ -11,7 +11,7 @@
 // -ffp-contract=off (Makefile): every operation below rounds once, so the float32 restatement (tests/_optim.py) describes the rounding
 // of every step and the translation glue equals the torch ops it replaces bit for bit.
 #include "hep.h"
-#include "hep_internal.h"
+#include "hep_train.h"
 
 #include <cstdint>
 
