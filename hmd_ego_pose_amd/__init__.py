@@ -42,6 +42,9 @@ def __getattr__(name):   # torch custom-op registration happens on first use of 
     if name in ("render_models", "MeshSet", "load_ply_mesh", "poses_from_annotations", "poses_from_detections"):
         from . import render
         return getattr(render, name)
+    if name in ("synth_frames", "ShadedMeshSet", "load_ply_coloured_mesh", "draw_lights"):      # (synth.draw_poses: by its module, draw_poses is the overlay's)
+        from . import synth
+        return getattr(synth, name)
     if name in ("bop_errors", "pairs_from_scene", "symmetry_transforms", "SymmetrySet", "BopSettings"):
         from . import bop
         return getattr(bop, name)

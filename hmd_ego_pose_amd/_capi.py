@@ -66,6 +66,9 @@ SYMBOLS = {
     "hep_render_workspace_bytes": (c_int64, [c_int] * 5),
     "hep_render_models_device": (c_int, [_FP, c_int, c_int, _FP, _FP, c_int, _FP, c_int, POINTER(c_int32), c_int, c_int, c_int, c_void_p, _FP, c_void_p, c_void_p, c_int,
                                          c_void_p, c_int64, c_void_p]),
+    "hep_synth_workspace_bytes": (c_int64, [c_int] * 5),
+    "hep_synth_frames_device": (c_int, [_FP, c_int, c_int, _FP, _FP, c_void_p, c_int, _FP, _FP, c_int, POINTER(c_int32), c_int, _FP, c_int, c_int, c_void_p, c_int,
+                                        c_void_p, _FP, _FP, _FP, _FP, _FP, c_int] + [_FP] * 8 + [c_void_p, c_int64, c_void_p]),
     "hep_bop_point_errors_device": (c_int, [_FP, c_int, _FP, c_int, POINTER(c_int32), _FP, c_int, POINTER(c_int32), c_int, _FP, c_void_p]),
     "hep_bop_workspace_bytes": (c_int64, [c_int, c_int]),
     "hep_bop_vsd_device": (c_int, [_FP, c_int, c_int, _FP, _FP, _FP, c_int, c_int, c_int, c_double, POINTER(c_double), c_int, _FP, _FP, c_void_p, c_int64, c_void_p]),

@@ -141,11 +141,21 @@ int hep_draw_poses_device(uint8_t* frames, int batch, int height, int width, con
 
 // ---- object models under poses: mask, depth and filled overlays from one z-buffered rasteriser ----
 static_assert(HEP_RENDER_MAX_POSES == RENDER_MAX_POSES && HEP_RENDER_MAX_ELEMENTS == RENDER_MAX_ELEMS, "the limits of include/hep.h are the kernel's");
-int64_t hep_render_workspace_bytes(int batch, int height, int width, int pmax, int num_vertices) try {
-  const Check c{"hep_render_models_device: "};      // (hep_render_models_device takes these refusals from here, with the figure)
+// what both entry points of the rasteriser refuse, worded once (c: the entry point's prefix); the workspace holds the vertex records, then one bounding box per (image, slot)
+static int64_t render_workspace_bytes(const Check& c, int batch, int height, int width, int pmax, int num_vertices) {
   CHECKED(c.at_least("batch", batch, 1)); CHECKED(c.range("pmax", pmax, 1, RENDER_MAX_POSES));
   CHECKED(c.range("num_vertices", num_vertices, 1, RENDER_MAX_ELEMS)); CHECKED(c.frame(height, width));
-  return (int64_t)batch * pmax * ((int64_t)num_vertices + 1) * (int64_t)sizeof(RenderVertex);      // the vertex records, then one bounding box per (image, slot)
+  return (int64_t)batch * pmax * ((int64_t)num_vertices + 1) * (int64_t)sizeof(RenderVertex);
+}
+static int render_face_tables(const Check& c, int num_faces, const int32_t* face_start, int num_labels) {
+  CHECKED(c.range("num_faces", num_faces, 1, RENDER_MAX_ELEMS)); CHECKED(c.labels(num_labels));
+  if (face_start[0] < 0 || face_start[num_labels] > num_faces) return c.fail(HEP_ERR_INVALID, "face_start leaves 0..num_faces");
+  for (int l = 0; l < num_labels; l++) if (face_start[l] > face_start[l + 1]) return c.fail(HEP_ERR_INVALID, "face_start decreases");      // (a label without faces draws nothing)
+  return 0;
+}
+
+int64_t hep_render_workspace_bytes(int batch, int height, int width, int pmax, int num_vertices) try {
+  return render_workspace_bytes(Check{"hep_render_models_device: "}, batch, height, width, pmax, num_vertices);      // (hep_render_models_device takes these refusals from here, with the figure)
 } HEP_CATCH_INT
 
 int hep_render_models_device(const double* poses, int batch, int pmax, const double* camera, const float* vertices, int num_vertices,
@@ -156,10 +166,8 @@ int hep_render_models_device(const double* poses, int batch, int pmax, const dou
   CHECKED(c.ptrs({{poses, "poses"}, {camera, "camera"}, {vertices, "vertices"}, {faces, "faces"}, {face_start, "face_start"},
                        {workspace, "workspace"}}));
   if (!mask && !depth && !frames) return c.fail(HEP_ERR_INVALID, "mask, depth and frames are all NULL");
-  const int64_t need = hep_render_workspace_bytes(batch, height, width, pmax, num_vertices); if (need < 0) return (int)need;
-  CHECKED(c.range("num_faces", num_faces, 1, RENDER_MAX_ELEMS)); CHECKED(c.labels(num_labels));
-  if (face_start[0] < 0 || face_start[num_labels] > num_faces) return c.fail(HEP_ERR_INVALID, "face_start leaves 0..num_faces");
-  for (int l = 0; l < num_labels; l++) if (face_start[l] > face_start[l + 1]) return c.fail(HEP_ERR_INVALID, "face_start decreases");      // (a label without faces draws nothing)
+  const int64_t need = render_workspace_bytes(c, batch, height, width, pmax, num_vertices); if (need < 0) return (int)need;
+  CHECKED(render_face_tables(c, num_faces, face_start, num_labels));
   if (frames && !colours) return c.fail(HEP_ERR_INVALID, "frames without colours");
   if (frames) CHECKED(c.range("alpha", alpha, 0, 256));
   CHECKED(c.workspace(workspace, workspace_bytes, need, "hep_render_workspace_bytes"));
@@ -173,6 +181,55 @@ int hep_render_models_device(const double* poses, int batch, int pmax, const dou
   memset(a.colours, 0, sizeof(a.colours));
   if (frames) memcpy(a.colours, colours, (size_t)num_labels * 3);
   launch_render(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+// ---- synthetic training frames: shaded models composited over backgrounds, visible boxes and the padded annotations ----
+int64_t hep_synth_workspace_bytes(int batch, int height, int width, int pmax, int num_vertices) try {
+  return render_workspace_bytes(Check{"hep_synth_frames_device: "}, batch, height, width, pmax, num_vertices);
+} HEP_CATCH_INT
+
+int hep_synth_frames_device(const double* poses, int batch, int pmax, const double* camera, const float* vertices, const uint8_t* vertex_colours,
+                            int num_vertices, const int32_t* faces, const double* face_normals, int num_faces, const int32_t* face_start,
+                            int num_labels, const double* lights, int height, int width, uint8_t* frames, int alpha, uint8_t* mask, float* depth,
+                            int32_t* visible, const float* rvec, const float* tvec, const float* extra, int min_pixels, double* boxes,
+                            int32_t* labels, int32_t* mask_values, float* out_rvec, float* out_tvec, float* out_extra, int32_t* num_gt,
+                            int32_t* slot_of, void* workspace, int64_t workspace_bytes, void* stream) try {
+  const Check c{"hep_synth_frames_device: "};
+  CHECKED(c.ptrs({{poses, "poses"}, {camera, "camera"}, {vertices, "vertices"}, {vertex_colours, "vertex_colours"}, {faces, "faces"},
+                  {face_normals, "face_normals"}, {face_start, "face_start"}, {lights, "lights"}, {frames, "frames"}, {visible, "visible"},
+                  {workspace, "workspace"}}));
+  const void* group[11] = {rvec, tvec, extra, boxes, labels, mask_values, out_rvec, out_tvec, out_extra, num_gt, slot_of};
+  int given = 0;
+  for (const void* p : group) given += p != nullptr;
+  if (given != 0 && given != 11) return c.fail(HEP_ERR_INVALID, "the annotation group (rvec, tvec, extra and the eight outputs) is half given: all or none");
+  const int64_t need = render_workspace_bytes(c, batch, height, width, pmax, num_vertices); if (need < 0) return (int)need;
+  CHECKED(render_face_tables(c, num_faces, face_start, num_labels));
+  CHECKED(c.range("alpha", alpha, 0, 256)); CHECKED(c.at_least("min_pixels", min_pixels, 1));
+  CHECKED(c.aligned(poses, 8, "poses")); CHECKED(c.aligned(camera, 8, "camera")); CHECKED(c.aligned(face_normals, 8, "face_normals"));
+  CHECKED(c.aligned(lights, 8, "lights")); CHECKED(c.aligned(vertices, 4, "vertices")); CHECKED(c.aligned(faces, 4, "faces"));
+  CHECKED(c.aligned(depth, 4, "depth")); CHECKED(c.aligned(visible, 4, "visible"));
+  if (given) {
+    CHECKED(c.aligned(boxes, 8, "boxes"));
+    const std::pair<const void*, const char*> words[] = {{rvec, "rvec"}, {tvec, "tvec"}, {extra, "extra"}, {labels, "labels"}, {mask_values, "mask_values"},
+                                                          {out_rvec, "out_rvec"}, {out_tvec, "out_tvec"}, {out_extra, "out_extra"}, {num_gt, "num_gt"}, {slot_of, "slot_of"}};
+    for (const auto& w : words) CHECKED(c.aligned(w.first, 4, w.second));
+  }
+  CHECKED(c.workspace(workspace, workspace_bytes, need, "hep_synth_workspace_bytes"));
+  SynthArgs x;
+  RenderArgs& a = x.r;
+  a.poses = poses; a.camera = camera; a.vertices = vertices; a.faces = faces; a.mask = mask; a.depth = depth; a.frames = frames;
+  a.ws = (RenderVertex*)workspace;
+  a.boxes = (int4*)(a.ws + (int64_t)batch * pmax * num_vertices);
+  a.B = batch; a.H = height; a.W = width; a.pmax = pmax; a.V = num_vertices; a.F = num_faces; a.num_labels = num_labels; a.alpha = alpha;
+  memset(a.face_start, 0, sizeof(a.face_start));
+  memcpy(a.face_start, face_start, (size_t)(num_labels + 1) * sizeof(int32_t));
+  memset(a.colours, 0, sizeof(a.colours));
+  x.vertex_colours = vertex_colours; x.face_normals = face_normals; x.lights = lights; x.visible = visible;
+  x.rvec = rvec; x.tvec = tvec; x.extra = extra; x.out_boxes = boxes; x.out_labels = labels; x.out_mask_values = mask_values;
+  x.out_rvec = out_rvec; x.out_tvec = out_tvec; x.out_extra = out_extra; x.num_gt = num_gt; x.slot_of = slot_of; x.min_pixels = min_pixels;
+  launch_synth(x, (hipStream_t)stream);
   HIPRET(hipGetLastError());
   return 0;
 } HEP_CATCH_INT

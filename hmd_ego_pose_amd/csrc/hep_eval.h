@@ -80,6 +80,24 @@ struct RenderArgs {
 };
 void launch_render(const RenderArgs&, hipStream_t);
 
+// ---- synthetic training frames: the same rasteriser with the winning fragment shaded, composited and boxed (k_render.hip) ----
+#define SYNTH_LIGHT_DOUBLES 8        // lx, ly, lz, ambient, diffuse, gain0, gain1, gain2
+#define SYNTH_VISIBLE_INTS 5         // min_x, min_y, max_x, max_y, count
+struct SynthArgs {
+  RenderArgs r;                                                        // frames required, colours unused
+  const uint8_t* vertex_colours;                                       // [V][3]
+  const double* face_normals;                                          // [F][3], plain data: a zero vector is legal
+  const double* lights;                                                // [B][SYNTH_LIGHT_DOUBLES]
+  int32_t* visible;                                                    // [B][pmax][SYNTH_VISIBLE_INTS], initialised by the bounds launch
+  // the annotation group, all given or all NULL: gathered inputs [B][pmax][3|3|2] and the compacted outputs in augment.pad_annotations' layout
+  const float* rvec; const float* tvec; const float* extra;
+  double* out_boxes; int32_t* out_labels; int32_t* out_mask_values;    // [B][pmax][4], [B][pmax], [B][pmax]
+  float* out_rvec; float* out_tvec; float* out_extra;                  // [B][pmax][3|3|2]
+  int32_t* num_gt; int32_t* slot_of;                                   // [B], [B][pmax]
+  int min_pixels;
+};
+void launch_synth(const SynthArgs&, hipStream_t);
+
 // ---- BOP pose errors of matched pairs: MSSD / MSPD over vertices and symmetries, VSD over rendered depth maps (k_bop.hip) ----
 #define BOP_PAIR_DOUBLES 32          // HEP_BOP_PAIR_DOUBLES
 #define BOP_MAX_SYM 64               // HEP_BOP_MAX_SYMMETRIES

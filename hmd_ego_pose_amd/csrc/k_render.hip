@@ -28,6 +28,14 @@
 // the end, every thread shades ITS OWN pixels against the list and keeps its running winner in registers: no pixel has two writers.  The
 // winner is a minimum over a total order, so the result does not depend on where the list was cut.  Tiles that no face meets still write
 // the zeros of mask and depth.
+//
+// Synthetic frames (hep_synth_frames_device, launch_synth): the SAME launches with SynthArgs for RenderArgs - launches 2 and 3 are templates
+// over their argument, and the renderer's instantiation is the code it always was.  The shaded variant of launch 2 also writes the empty
+// visible record of its (image, slot); that of launch 3 shades each pixel's winner ONCE, after the face walk (synth_shade: float64, every
+// rounding stated in include/hep.h and tests/_synth.py), composites it and reduces min / max / count of the pixels each slot won - in LDS
+// first, then one integer atomicMin / atomicMax / atomicAdd set per (workgroup, slot that won a pixel): only commutative integer operations
+// cross workgroups, so the record does not depend on arrival order.  Launch 4 (synth_annotate_kernel): one thread per image compacts the
+// kept slots into the padded annotation tensors.
 #include "hep_dev.h"
 #include "hep_eval.h"
 
@@ -79,11 +87,23 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_project_kernel(RenderAr
   }
 }
 
-__global__ __launch_bounds__(RENDER_THREADS) void render_bounds_kernel(RenderArgs a) {
+// the kernel argument of a variant: RenderArgs itself, or SynthArgs around it (SHADE)
+__device__ __forceinline__ const RenderArgs& render_args(const RenderArgs& a) { return a; }
+__device__ __forceinline__ const RenderArgs& render_args(const SynthArgs& a) { return a.r; }
+template <class Args> struct RenderShades { static constexpr bool value = false; };
+template <> struct RenderShades<SynthArgs> { static constexpr bool value = true; };
+
+template <class Args>
+__global__ __launch_bounds__(RENDER_THREADS) void render_bounds_kernel(Args args) {
   __shared__ int s_box[4][RENDER_THREADS];
+  const RenderArgs& a = render_args(args);
   const int t = threadIdx.x, slot = blockIdx.x;
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     int lab;
+    if constexpr (RenderShades<Args>::value) {                      // the empty visible record of EVERY (image, slot), skipped rows included
+      if (t < SYNTH_VISIBLE_INTS)                                   // inside [0, B * pmax * 5): b < B, slot < pmax
+        args.visible[((int64_t)b * a.pmax + slot) * SYNTH_VISIBLE_INTS + t] = t < 2 ? INT_MAX : (t < 4 ? INT_MIN : 0);
+    }
     if (!render_row(a.poses + ((int64_t)b * a.pmax + slot) * 16, a.num_labels, lab)) continue;      // the same for every thread
     const RenderVertex* wsp = a.ws + ((int64_t)b * a.pmax + slot) * a.V;
     int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN;
@@ -134,7 +154,46 @@ __device__ __forceinline__ void render_shade(const int (*s_v)[8], const double (
   }
 }
 
-__global__ __launch_bounds__(RENDER_THREADS) void render_raster_kernel(RenderArgs a) {
+// SHADE: the winner of pixel (px, py) of image b shaded from its three vertex colours and its face's normal under the image's light -
+// once per pixel, after the face walk; include/hep.h (hep_synth_frames_device) states every rounding, tests/_synth.py in numpy
+__device__ __forceinline__ void synth_shade(const SynthArgs& x, int b, uint32_t key, int pcx, int pcy, int out[3]) {
+  const RenderArgs& a = x.r;
+  const int slot = (int)(key >> 24), f = (int)(key & 0xffffffu);  // a winner's face passed the index test of the walk: f < F, indices < V
+  const double* P = a.poses + ((int64_t)b * a.pmax + slot) * 16;
+  const RenderVertex* wsp = a.ws + ((int64_t)b * a.pmax + slot) * a.V;
+  const int i0 = a.faces[3 * (int64_t)f], i1 = a.faces[3 * (int64_t)f + 1], i2 = a.faces[3 * (int64_t)f + 2];
+  const RenderVertex A = wsp[i0], B = wsp[i1], C = wsp[i2];
+  const int64_t area = (int64_t)(B.sx - A.sx) * (C.sy - A.sy) - (int64_t)(B.sy - A.sy) * (C.sx - A.sx);
+  const int s = area < 0 ? -1 : 1;
+  const int64_t e0 = (int64_t)(s * (C.sx - B.sx)) * (pcy - B.sy) - (int64_t)(s * (C.sy - B.sy)) * (pcx - B.sx);
+  const int64_t e1 = (int64_t)(s * (A.sx - C.sx)) * (pcy - C.sy) - (int64_t)(s * (A.sy - C.sy)) * (pcx - C.sx);
+  const int64_t e2 = (int64_t)(s * (B.sx - A.sx)) * (pcy - A.sy) - (int64_t)(s * (B.sy - A.sy)) * (pcx - A.sx);
+  const double q0 = (double)e0 * A.w, q1 = (double)e1 * B.w, q2 = (double)e2 * C.w;
+  const double den = (q0 + q1) + q2;
+  const double b0 = q0 / den, b1 = q1 / den, b2 = q2 / den;
+  const double* n = x.face_normals + 3 * (int64_t)f;
+  const double n0 = n[0], n1 = n[1], n2 = n[2];
+  const double m0 = (P[4] * n0 + P[5] * n1) + P[6] * n2, m1 = (P[7] * n0 + P[8] * n1) + P[9] * n2, m2 = (P[10] * n0 + P[11] * n1) + P[12] * n2;
+  const double* L = x.lights + (int64_t)b * SYNTH_LIGHT_DOUBLES;
+  double d = (m0 * L[0] + m1 * L[1]) + m2 * L[2];
+  d = d < 0.0 ? -d : d;                                           // two-sided
+  const double sh = L[3] + L[4] * d;
+  const uint8_t* c0 = x.vertex_colours + 3 * (int64_t)i0;
+  const uint8_t* c1 = x.vertex_colours + 3 * (int64_t)i1;
+  const uint8_t* c2 = x.vertex_colours + 3 * (int64_t)i2;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double c = (b0 * (double)c0[k] + b1 * (double)c1[k]) + b2 * (double)c2[k];
+    const double v = (c * sh) * L[5 + k];
+    const double t = v + 0.5;
+    out[k] = !(t >= 0.0) ? 0 : (t >= 256.0 ? 255 : (int)floor(t));      // NaN: 0
+  }
+}
+
+template <class Args>
+__global__ __launch_bounds__(RENDER_THREADS) void render_raster_kernel(Args args) {
+  constexpr bool SHADE = RenderShades<Args>::value;
+  const RenderArgs& a = render_args(args);
   __shared__ __attribute__((aligned(16))) int s_v[RENDER_LIST][8];          // x0 y0 x1 y1 x2 y2, orientation << 31 | slot << 24 | face, 0
   __shared__ double s_w[RENDER_LIST][3];                                    // 1 / Z of the three vertices
   __shared__ int s_wcnt[2][RENDER_THREADS / 64];
@@ -146,7 +205,12 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_kernel(RenderArg
   const int px = tx0 + (t & (RENDER_TW - 1)), py0 = ty0 + t / RENDER_TW;      // the thread's pixel
   const int pcx = 16 * px + 8, pcy0 = 16 * py0 + 8;
 
+  __shared__ int s_vis[SHADE ? RENDER_MAX_POSES : 1][SYNTH_VISIBLE_INTS];    // SHADE: min_x, min_y, max_x, max_y, count of the tile's pixels each slot won
+
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
+    if constexpr (SHADE) {                                        // read back before the barrier that ends the previous image; the walk's barriers follow
+      if (t < RENDER_MAX_POSES * SYNTH_VISIBLE_INTS) s_vis[t / SYNTH_VISIBLE_INTS][t % SYNTH_VISIBLE_INTS] = t % SYNTH_VISIBLE_INTS < 2 ? INT_MAX : (t % SYNTH_VISIBLE_INTS < 4 ? INT_MIN : 0);
+    }
     double bz[RENDER_PPT];
     uint32_t bkey[RENDER_PPT];
 #pragma unroll
@@ -211,21 +275,80 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_kernel(RenderArg
       const double* P = a.poses + ((int64_t)b * a.pmax + (hit ? (bkey[k] >> 24) : 0)) * 16;
       if (a.mask) a.mask[o] = hit ? (uint8_t)(int)P[2] : (uint8_t)0;
       if (a.depth) a.depth[o] = hit ? (float)bz[k] : 0.0f;
-      if (a.frames && hit) {
+      if constexpr (SHADE) {
+        if (hit) {
+          int c[3];
+          synth_shade(args, b, bkey[k], 16 * qx + 8, 16 * py + 8, c);
+          uint8_t* q = a.frames + 3 * o;
+#pragma unroll
+          for (int ch = 0; ch < 3; ch++) q[ch] = (uint8_t)((a.alpha * c[ch] + (256 - a.alpha) * (int)q[ch] + 128) >> 8);
+          int* v = s_vis[bkey[k] >> 24];                          // slot < pmax <= RENDER_MAX_POSES
+          atomicMin(&v[0], qx); atomicMin(&v[1], py); atomicMax(&v[2], qx); atomicMax(&v[3], py); atomicAdd(&v[4], 1);
+        }
+      } else if (a.frames && hit) {
         const uint8_t* c = a.colours + 3 * (int)P[1];
         uint8_t* q = a.frames + 3 * o;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) q[ch] = (uint8_t)((a.alpha * (int)c[ch] + (256 - a.alpha) * (int)q[ch] + 128) >> 8);
       }
     }
+    if constexpr (SHADE) {
+      // the workgroup's pixels per slot are reduced; integer min / max / add commute, so the global record does not depend on which tile arrives first
+      __syncthreads();
+      if (t < a.pmax && s_vis[t][4] > 0) {
+        int32_t* g = args.visible + ((int64_t)b * a.pmax + t) * SYNTH_VISIBLE_INTS;      // inside [0, B * pmax * 5)
+        atomicMin(&g[0], s_vis[t][0]); atomicMin(&g[1], s_vis[t][1]); atomicMax(&g[2], s_vis[t][2]); atomicMax(&g[3], s_vis[t][3]); atomicAdd(&g[4], s_vis[t][4]);
+      }
+    }
     __syncthreads();                                              // the list is the next image's
   }
 }
 
-void launch_render(const RenderArgs& a, hipStream_t s) {
+// SHADE's last launch: one thread per image walks the slots in order and keeps a slot whose row is rendered and whose visible count reaches
+// min_pixels; the n-th kept slot becomes row n of the padded annotation tensors (augment.pad_annotations' layout), the rest is zeros
+__global__ __launch_bounds__(64) void synth_annotate_kernel(SynthArgs x) {
+  const RenderArgs& a = x.r;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= a.B) return;
+  int n = 0;                                                     // rows written so far: n <= slot < pmax, so every index below stays inside [B][pmax][.]
+  for (int slot = 0; slot < a.pmax; slot++) {
+    const int64_t src = (int64_t)b * a.pmax + slot, o = (int64_t)b * a.pmax + n;
+    const double* P = a.poses + src * 16;
+    const int32_t* vis = x.visible + src * SYNTH_VISIBLE_INTS;
+    int lab;
+    if (!render_row(P, a.num_labels, lab) || vis[4] < x.min_pixels) continue;
+    for (int k = 0; k < 4; k++) x.out_boxes[4 * o + k] = (double)vis[k];
+    x.out_labels[o] = lab;
+    x.out_mask_values[o] = (int)P[2];
+    for (int k = 0; k < 3; k++) { x.out_rvec[3 * o + k] = x.rvec[3 * src + k]; x.out_tvec[3 * o + k] = x.tvec[3 * src + k]; }
+    for (int k = 0; k < 2; k++) x.out_extra[2 * o + k] = x.extra[2 * src + k];
+    x.slot_of[o] = slot;
+    n++;
+  }
+  for (int r = n; r < a.pmax; r++) {                             // the padding: zeros, and no source slot
+    const int64_t o = (int64_t)b * a.pmax + r;
+    for (int k = 0; k < 4; k++) x.out_boxes[4 * o + k] = 0.0;
+    x.out_labels[o] = 0;
+    x.out_mask_values[o] = 0;
+    for (int k = 0; k < 3; k++) { x.out_rvec[3 * o + k] = 0.0f; x.out_tvec[3 * o + k] = 0.0f; }
+    for (int k = 0; k < 2; k++) x.out_extra[2 * o + k] = 0.0f;
+    x.slot_of[o] = -1;
+  }
+  x.num_gt[b] = n;
+}
+
+template <class Args>
+static void launch_raster(const Args& args, const RenderArgs& a, hipStream_t s) {
   const int B = a.B < 65535 ? a.B : 65535;
   hipLaunchKernelGGL(render_project_kernel, dim3((a.V + RENDER_THREADS - 1) / RENDER_THREADS, a.pmax, B), dim3(RENDER_THREADS), 0, s, a);
-  hipLaunchKernelGGL(render_bounds_kernel, dim3(a.pmax, B), dim3(RENDER_THREADS), 0, s, a);
+  hipLaunchKernelGGL(render_bounds_kernel<Args>, dim3(a.pmax, B), dim3(RENDER_THREADS), 0, s, args);
   const int tiles = ((a.W + RENDER_TW - 1) / RENDER_TW) * ((a.H + RENDER_TH - 1) / RENDER_TH);
-  hipLaunchKernelGGL(render_raster_kernel, dim3(tiles, B), dim3(RENDER_THREADS), 0, s, a);
+  hipLaunchKernelGGL(render_raster_kernel<Args>, dim3(tiles, B), dim3(RENDER_THREADS), 0, s, args);
+}
+
+void launch_render(const RenderArgs& a, hipStream_t s) { launch_raster(a, a, s); }
+
+void launch_synth(const SynthArgs& x, hipStream_t s) {
+  launch_raster(x, x.r, s);
+  if (x.num_gt) hipLaunchKernelGGL(synth_annotate_kernel, dim3((x.r.B + 63) / 64), dim3(64), 0, s, x);
 }

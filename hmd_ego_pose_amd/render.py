@@ -24,6 +24,12 @@ def load_ply_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
     """(vertices float32 [V,3], faces int32 [F,3]) of an ASCII or binary-little-endian PLY file: ``evaluate.load_ply_vertices`` plus the
     ``face`` element's ``vertex_indices`` / ``vertex_index`` list.  A face that is not a triangle, a file without faces and an index
     outside the vertices raise ValueError naming the file."""
+    return _read_ply(path, False)[:2]
+
+
+def _read_ply(path: str, want_colours: bool):
+    """The parser behind ``load_ply_mesh`` and ``synth.load_ply_coloured_mesh``: (vertices, faces, colours uint8 [V,3] or None).  With
+    ``want_colours`` the vertex element must have the uchar properties red, green and blue."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -54,6 +60,11 @@ def load_ply_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
         vnames = [p[0] for p in vprops]
         if any(len(p) != 2 for p in vprops) or not all(k in vnames for k in "xyz"):
             raise ValueError(f"{path}: vertex element has no plain x/y/z")
+        if want_colours:
+            for k in ("red", "green", "blue"):
+                if k not in vnames or _PLY_CODE.get(vprops[vnames.index(k)][1]) != "u1":
+                    raise ValueError(f"{path}: vertex element has no uchar property '{k}' (a coloured mesh needs red, green and blue)")
+        colours = None
         lists = [i for i, p in enumerate(fprops) if len(p) == 3]
         if len(lists) != 1 or fprops[lists[0]][0] not in ("vertex_indices", "vertex_index"):
             raise ValueError(f"{path}: face element needs exactly one list property, vertex_indices or vertex_index")
@@ -66,6 +77,8 @@ def load_ply_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
                 raise ValueError(f"{path}: truncated vertex element")
             rows = np.array(rows, dtype=np.float64).reshape(nv, len(vprops))
             vertices = np.stack([rows[:, vnames.index(k)] for k in "xyz"], axis=-1).astype(np.float32)
+            if want_colours:
+                colours = np.stack([rows[:, vnames.index(k)] for k in ("red", "green", "blue")], axis=-1).astype(np.uint8)
             faces = np.empty((nf, 3), np.int64)
             for i in range(nf):
                 tok = f.readline().split()
@@ -76,6 +89,8 @@ def load_ply_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
             vdt = np.dtype([(nm, "<" + _PLY_CODE[ty]) for nm, ty in vprops])
             v = np.frombuffer(f.read(nv * vdt.itemsize), dtype=vdt, count=nv)
             vertices = np.stack([v["x"], v["y"], v["z"]], axis=-1).astype(np.float32)
+            if want_colours:
+                colours = np.stack([v["red"], v["green"], v["blue"]], axis=-1).astype(np.uint8)
             fields = []
             for p in fprops:                                   # the record of a triangle; a face of another size breaks the count check
                 fields += [("_n", "<" + _PLY_CODE[p[1]]), ("_i", "<" + _PLY_CODE[p[2]], (3,))] if len(p) == 3 else [(p[0], "<" + _PLY_CODE[p[1]])]
@@ -92,7 +107,7 @@ def load_ply_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
             faces = rec["_i"].astype(np.int64)
     if faces.min() < 0 or faces.max() >= nv:
         raise ValueError(f"{path}: a face index lies outside the {nv} vertices")
-    return vertices, faces.astype(np.int32)
+    return vertices, faces.astype(np.int32), colours
 
 
 class MeshSet:
@@ -141,7 +156,7 @@ def _rodrigues(rv: torch.Tensor) -> torch.Tensor:
     R = torch.stack([c + v * kx * kx, v * kx * ky - s * kz, v * kx * kz + s * ky,
                      v * ky * kx + s * kz, c + v * ky * ky, v * ky * kz - s * kx,
                      v * kz * kx - s * ky, v * kz * ky + s * kx, c + v * kz * kz], dim=-1)
-    eye = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=rv.device)
+    eye = torch.eye(3, dtype=torch.float64, device=rv.device).reshape(9)      # made on the device: a host list would be a blocking upload
     return torch.where(small[..., None], eye.expand_as(R), R)
 
 

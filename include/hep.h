@@ -455,6 +455,56 @@ int hep_render_models_device(const double* poses, int batch, int pmax, const dou
                              const uint8_t* colours /* HOST [num_labels][3], or NULL without frames */, int alpha,
                              void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Synthetic training frames: the models of hep_render_models_device SHADED from per-vertex colours and one light per image, composited
+ * over the caller's backgrounds, and - in the same call - the labels hep_augment_6dof_device takes: the visible box of every pose slot from
+ * the pixels that slot actually won, and the padded annotation tensors with hidden and off-frame objects dropped.  The same rasteriser
+ * (one kernel, a compile-time switch), four launches (five with the annotation group).  Stateless like hep_render_models_device: no handle,
+ * no allocation, no host synchronisation, asynchronous on `stream`; the workspace is the caller's (hep_synth_workspace_bytes: the bytes
+ * and the refusals of hep_render_workspace_bytes; 16-byte aligned).  The definition is THIS library's own (tests/_synth.py states it in
+ * numpy and IS the definition; the kernels match it bit for bit).  No textures, smooth shading, shadows or anti-aliasing.
+ * poses, camera, vertices, faces, face_start, num_labels, height, width: those of hep_render_models_device, with the same row rule;
+ *   PROJECTION, COVERAGE, DEPTH and the WINNER per pixel are exactly its.  mask, depth: its outputs, bit for bit; each may be NULL.
+ * vertex_colours: device, uint8 [num_vertices][3].  face_normals: device, float64 [num_faces][3], indexed by the face's index in `faces`:
+ *   plain data, computed by the caller (hmd_ego_pose_amd.synth.ShadedMeshSet: cross(v1 - v0, v2 - v0) / length in float64); a zero vector
+ *   is legal.  lights: device, float64 [batch][8] = lx, ly, lz, ambient, diffuse, gain0, gain1, gain2; the direction is in the camera
+ *   frame and the CALLER normalises it: device code has only + - * /, floor and comparisons.
+ * SHADING of a pixel whose winner is face f of a slot, with vertices v0, v1, v2, the winner's edge values E0, E1, E2 at the pixel centre
+ *   (exact int64) and w_i = 1 / Z_i of the vertex records; float64, no contraction, in this order:
+ *   q_i = (double)E_i * w_i; den = (q0 + q1) + q2; b_i = q_i / den; c_k = (b0 C0k + b1 C1k) + b2 C2k, Cik the colour byte of vertex i
+ *   widened, k = 0, 1, 2; with R the pose row's matrix and n the face's normal m_r = (R[r][0] n0 + R[r][1] n1) + R[r][2] n2;
+ *   d = (m_0 lx + m_1 ly) + m_2 lz; d = d < 0 ? -d : d (two-sided: faces of either winding shade alike); s = ambient + diffuse * d;
+ *   v_k = (c_k * s) * gain_k; t = v_k + 0.5; byte = !(t >= 0) ? 0 : (t >= 256 ? 255 : (int)floor(t)) - a NaN gives 0.
+ * frames: uint8 [batch][height][width][3], REQUIRED, composited in place where something is rendered, per channel
+ *   out = (alpha * byte + (256 - alpha) * old + 128) >> 8, alpha an integer in 0..256; pixels that nothing covers keep their bytes.
+ * visible: int32 [batch][pmax][5], REQUIRED = min_x, min_y, max_x, max_y, count of the pixels slot k WON - the inclusive minimum and
+ *   maximum of the pixel indices, per slot, not per mask value.  A slot that won none - a skipped row included - has count 0, INT_MAX
+ *   in the two minima and INT_MIN in the two maxima.  Reduced in the workgroup, then by integer atomic min / max / add: the result does
+ *   not depend on the order of arrival.
+ * THE ANNOTATION GROUP, all eleven given or all NULL.  Inputs rvec, tvec float32 [batch][pmax][3], extra float32 [batch][pmax][2]: the
+ *   caller's padded tensors, slot k belonging to pose row k.  Per image the slots are walked in order; a slot is KEPT when its row is
+ *   rendered (the row rule) and count >= min_pixels (min_pixels >= 1); the n-th kept slot becomes row n of boxes float64 [batch][pmax][4]
+ *   (the four integers of visible widened), labels, mask_values int32 [batch][pmax] (the pose row's values truncated as the renderer
+ *   truncates them), out_rvec, out_tvec float32 [batch][pmax][3], out_extra float32 [batch][pmax][2] (gathered from slot k), slot_of
+ *   int32 [batch][pmax] (k; -1 in the padding); num_gt int32 [batch] the number kept.  All padding is zeros.  The outputs must not
+ *   overlap the inputs.
+ * Never writes outside frames [0 .. batch*height*width*3), mask / depth [0 .. batch*height*width), visible [0 .. batch*pmax*5), the
+ * annotation outputs' stated shapes and the workspace's stated bytes; never writes vertex_colours, face_normals, lights, rvec, tvec, extra.
+ * Checked before any HIP call, HEP_ERR_INVALID with the reason in hep_last_error: NULL poses, camera, vertices, vertex_colours, faces,
+ * face_normals, face_start, lights, frames, visible or workspace; a half-given annotation group; the ranges of hep_render_models_device
+ * (batch, pmax, num_vertices, num_faces, num_labels, face_start); alpha outside 0..256; min_pixels < 1; a pointer that is not aligned
+ * to its element; a workspace that is misaligned or too small.  height or width outside 16..4096: HEP_ERR_UNSUPPORTED. */
+int64_t hep_synth_workspace_bytes(int batch, int height, int width, int pmax, int num_vertices);
+int hep_synth_frames_device(const double* poses, int batch, int pmax, const double* camera,
+                            const float* vertices, const uint8_t* vertex_colours, int num_vertices,
+                            const int32_t* faces, const double* face_normals, int num_faces,
+                            const int32_t* face_start /* HOST [num_labels + 1], copied into the kernel argument */, int num_labels,
+                            const double* lights, int height, int width, uint8_t* frames, int alpha,
+                            uint8_t* mask /* or NULL */, float* depth /* or NULL */, int32_t* visible,
+                            const float* rvec, const float* tvec, const float* extra, int min_pixels,
+                            double* boxes, int32_t* labels, int32_t* mask_values, float* out_rvec, float* out_tvec, float* out_extra,
+                            int32_t* num_gt, int32_t* slot_of /* the annotation group: all or none */,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* BOP pose errors of matched (ground truth, estimate) pairs: MSSD and MSPD over a model's vertices and its set of symmetry transforms
  * from one entry point, VSD over rendered depth maps from a second.  Stateless like hep_render_models_device: no handle, no allocation, no
  * host synchronisation, asynchronous on `stream`.  This is BOP's mssd, mspd and vsd (bop19 visibility rule, step cost) RESTATED with this
