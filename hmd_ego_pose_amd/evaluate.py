@@ -205,16 +205,15 @@ def _model_cuboid(info: dict) -> Optional[np.ndarray]:
     return cuboid_corners(v[:3], v[3:])
 
 
-class LinemodFolder:
-    """One object of a Linemod-format dataset as the reference's ColibriGenerator reads it: ``<root>/data/<NN>/`` with
-    ``rgb/*.png``, ``mask/*.png``, ``gt_<fold>.yml``, ``info_<fold>.yml``, ``test_<fold>.txt`` and
-    ``<root>/models/obj_<NN>.ply`` + ``models_info.yml``."""
+class _Folder:
+    """What ``LinemodFolder`` and ``SceneFolder`` read alike of ``<root>/data/<NN>/`` and ``<root>/models/``: the split, ground-truth, camera
+    and model files, the frames of the split (``image_paths``), one camera matrix and one ``_annotation`` per frame.  The readers supply
+    ``_read_models`` (what they keep of models_info.yml and the PLY files) and ``_annotation`` (a frame's ground-truth entries -> its annotation)."""
 
-    def __init__(self, dataset_path: str, object_id: int = 1, fold: int = 0, split: str = "test", image_extension: str = ".png"):
+    def __init__(self, dataset_path: str, folder_id: int, fold: int, split: str, image_extension: str):
         import yaml
         loader = getattr(yaml, "CSafeLoader", yaml.SafeLoader)
-        self.object_id = object_id
-        self.object_path = os.path.join(dataset_path, "data", f"{object_id:02}")
+        self.object_path = os.path.join(dataset_path, "data", f"{folder_id:02}")
         self.model_path = os.path.join(dataset_path, "models")
         with open(os.path.join(self.object_path, f"{split}_{fold}.txt")) as f:
             examples = [e.strip() for e in f if e.strip()]
@@ -223,41 +222,33 @@ class LinemodFolder:
         with open(os.path.join(self.object_path, f"info_{fold}.yml")) as f:
             info = yaml.load(f, Loader=loader)
         with open(os.path.join(self.model_path, "models_info.yml")) as f:
-            models = yaml.load(f, Loader=loader)
-        self.diameter = float(models[object_id]["diameter"])
-        self.cuboid = _model_cuboid(models[object_id])                 # float32 [8,3], or None without min_* / size_*
-        self.points = load_ply_vertices(os.path.join(self.model_path, f"obj_{object_id:02}.ply"))
+            self._read_models(yaml.load(f, Loader=loader))
         names = sorted(n for n in os.listdir(os.path.join(self.object_path, "rgb"))
                        if n.endswith(image_extension) and n[:-len(image_extension)] in examples)
         self.image_paths = [os.path.join(self.object_path, "rgb", n) for n in names]
         self.annotations, self.camera = [], []
         for n in names:
             key = int(n.split(".")[0])
-            annos = [a for a in gt[key] if a["obj_id"] == object_id]
-            if not annos:
-                raise ValueError(f"no annotation of object {object_id} for frame {n}")
-            a = annos[0]
-            R = np.array(a["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
-            entry = {"rotation": matrix_to_axis_angle(R), "translation": np.array(a["cam_t_m2c"], dtype=np.float64),
-                     "drill_tip": np.array(a.get("drill_tip_transform", [0, 0, 0, 1]), dtype=np.float64)}
-            mask_path = os.path.join(self.object_path, "mask", n)
-            if os.path.exists(mask_path):
-                entry["bbox"] = self._bbox_from_mask(mask_path)
-            else:                                     # Linemod's own field: x, y, w, h
-                x, y, w, h = a["obj_bb"]
-                entry["bbox"] = np.array([x, y, x + w, y + h], dtype=np.float32)
-            hands_path = os.path.join(self.object_path, "hands", n[:-len(image_extension)] + "_coords_3d.npy")      # generators/colibri.py:430-436
-            if os.path.exists(hands_path):
-                entry["coords_3d"] = np.load(hands_path).astype(np.float64).reshape(21, 3)
-            self.annotations.append(entry)
+            self.annotations.append(self._annotation(n, gt[key], image_extension))
             self.camera.append(np.array(info[key]["cam_K"], dtype=np.float64).reshape(3, 3))
 
     @staticmethod
-    def _bbox_from_mask(path: str) -> np.ndarray:
-        """get_bbox_from_mask, colibri_common.py:540-561: (min_x, min_y, max_x, max_y) of the non-zero pixels."""
-        from PIL import Image
-        m = np.asarray(Image.open(path))
-        ys, xs = np.nonzero(m.reshape(m.shape[0], m.shape[1], -1).max(axis=2))
+    def _pose(a: dict) -> dict:
+        """The pose keys of an annotation from one ground-truth entry."""
+        R = np.array(a["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
+        return {"rotation": matrix_to_axis_angle(R), "translation": np.array(a["cam_t_m2c"], dtype=np.float64),
+                "drill_tip": np.array(a.get("drill_tip_transform", [0, 0, 0, 1]), dtype=np.float64)}
+
+    @staticmethod
+    def _obj_bb(a: dict) -> np.ndarray:
+        """Linemod's own field: x, y, w, h."""
+        x, y, w, h = a["obj_bb"]
+        return np.array([x, y, x + w, y + h], dtype=np.float32)
+
+    @staticmethod
+    def _mask_box(inside: np.ndarray) -> np.ndarray:
+        """get_bbox_from_mask, colibri_common.py:540-561: (min_x, min_y, max_x, max_y) of the pixels that are set."""
+        ys, xs = np.nonzero(inside)
         if ys.size == 0:
             return np.zeros(4, np.float32)
         return np.array([xs.min(), ys.min(), xs.max(), ys.max()], dtype=np.float32)
@@ -274,6 +265,41 @@ class LinemodFolder:
         """get_camera_parameter_input, colibri_common.py:658-678: [fx, fy, px, py, translation_scale_norm, image_scale]."""
         K = self.camera[i]
         return np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2], translation_scale_norm, image_scale], dtype=np.float32)
+
+
+class LinemodFolder(_Folder):
+    """One object of a Linemod-format dataset as the reference's ColibriGenerator reads it: ``<root>/data/<NN>/`` with
+    ``rgb/*.png``, ``mask/*.png``, ``gt_<fold>.yml``, ``info_<fold>.yml``, ``test_<fold>.txt`` and
+    ``<root>/models/obj_<NN>.ply`` + ``models_info.yml``."""
+
+    def __init__(self, dataset_path: str, object_id: int = 1, fold: int = 0, split: str = "test", image_extension: str = ".png"):
+        self.object_id = object_id
+        super().__init__(dataset_path, object_id, fold, split, image_extension)
+
+    def _read_models(self, models: dict) -> None:
+        self.diameter = float(models[self.object_id]["diameter"])
+        self.cuboid = _model_cuboid(models[self.object_id])            # float32 [8,3], or None without min_* / size_*
+        self.points = load_ply_vertices(os.path.join(self.model_path, f"obj_{self.object_id:02}.ply"))
+
+    def _annotation(self, n: str, entries: list, image_extension: str) -> dict:
+        """The FIRST entry of the folder's object; its box from the frame's mask where there is one."""
+        annos = [a for a in entries if a["obj_id"] == self.object_id]
+        if not annos:
+            raise ValueError(f"no annotation of object {self.object_id} for frame {n}")
+        entry = self._pose(annos[0])
+        mask_path = os.path.join(self.object_path, "mask", n)
+        entry["bbox"] = self._bbox_from_mask(mask_path) if os.path.exists(mask_path) else self._obj_bb(annos[0])
+        hands_path = os.path.join(self.object_path, "hands", n[:-len(image_extension)] + "_coords_3d.npy")      # generators/colibri.py:430-436
+        if os.path.exists(hands_path):
+            entry["coords_3d"] = np.load(hands_path).astype(np.float64).reshape(21, 3)
+        return entry
+
+    @classmethod
+    def _bbox_from_mask(cls, path: str) -> np.ndarray:
+        """The box of the non-zero pixels of a mask file, whichever channel they are in."""
+        from PIL import Image
+        m = np.asarray(Image.open(path))
+        return cls._mask_box(m.reshape(m.shape[0], m.shape[1], -1).max(axis=2))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -463,10 +489,10 @@ def _check_bop(who: str, bop, depth_test, frames, dev, num_labels: int):
     return check_settings(who, bop, depth_test, frames, dev, num_labels)
 
 
-def _score_bop(ev, bop, size, gt, d, records, diameters, depth_test, o: int, B: int, A: int) -> None:
-    """MSSD, MSPD and VSD of a batch's matched pairs into the evaluator's second buffer [capacity,A,2+T] at image offset ``o``."""
+def _score_bop(ev, bop, size, gt, d, records, diameters, depth_test, o: int) -> None:
+    """MSSD, MSPD and VSD of a batch's matched pairs (``records`` [B,A,16]) into the evaluator's second buffer [capacity,A,2+T] at image offset ``o``."""
     from .bop import score_batch
-    T = int(bop.tau_fractions.size)
+    B, A, T = int(records.shape[0]), int(records.shape[1]), int(bop.tau_fractions.size)
     if ev._bop_buf is None or ev._bop_buf.shape[2] != 2 + T:
         ev._bop_buf = torch.full((ev.capacity, A, 2 + T), float("nan"), dtype=torch.float64, device=ev.device)
     score_batch(bop, size, gt, dict(rotation=d[3], translation=d[4]), records, diameters, depth_test, ev._bop_buf[o:o + B])
@@ -482,7 +508,135 @@ def _bop_result(ev, who: str, rec: np.ndarray, diameters) -> Dict[str, dict]:
     return summarise_bop(rec, ev._bop_buf.cpu().numpy()[:ev.count], diameters, ev._bop_width)
 
 
-class DeviceEvaluator:
+def _matched_metrics(r: np.ndarray) -> Optional[dict]:
+    """``metric_summary``'s ``m`` from the matched records [n,16] of either scoring kernel, or None without a match."""
+    if not r.shape[0]:
+        return None
+    return dict(add=r[:, 5], add_s=r[:, 6], t_diff=r[:, 7], r_diff=r[:, 8], tip=r[:, 9], reproj=r[:, 10], hand=r[:, 11][~np.isnan(r[:, 11])])
+
+
+_DETECTION_KEYS = ("boxes", "scores", "labels", "rotation", "translation", "hand")
+_NUMPY = {torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32}          # the dtypes of the evaluators' buffer layouts
+
+
+class _Evaluator:
+    """What ``DeviceEvaluator`` and ``SceneEvaluator`` share: the settings, ONE allocation cut by a declared layout, and ``add`` - every
+    check, preprocess, ``model.detect``, the scoring launch, then BOP, the mesh blend and the draw.  A subclass supplies ``_gt_shape`` (the
+    per-image shape of ``gt``), ``num_labels``, ``_launch`` (its one library call), ``_bop_records`` and ``result``."""
+
+    def __init__(self, model, image_size: int, capacity: int, score_threshold: float, max_detections: int, iou_threshold: float,
+                 diameter_threshold: float, device: Optional[torch.device], max_points: int, draw_layers: int, draw_thickness: int):
+        self.model, self.image_size, self.capacity = model, int(image_size), int(capacity)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.diameter_threshold = float(diameter_threshold)
+        self.score_threshold, self.max_detections, self.iou_threshold = float(score_threshold), int(max_detections), float(iou_threshold)
+        self.max_points = int(max_points)
+        # ``add(..., draw_into=)``: the subclass's cuboids float32 [labels,8,3] on the device, the layers (HEP_DRAW_*) and line thickness of both
+        # annotations and detections
+        self._cuboids = None
+        self.draw_layers, self.draw_thickness = int(draw_layers), int(draw_thickness)
+        self.count = 0
+        self._bop_buf, self._bop_count, self._bop_width = None, 0, 0      # ``add(..., bop=)``: errors [C,amax,2+T] float64, allocated on first use
+
+    def _check_sizes(self, capacity: int, max_detections: int, max_points: int) -> None:
+        """A constructor's first refusal, ahead of the subclass's own."""
+        if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
+            raise ValueError(f"{type(self).__name__}: capacity and max_detections must be >= 1, max_points in 1..1024")
+
+    def _points(self, points, what: str) -> np.ndarray:
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+            raise ValueError(f"{type(self).__name__}: {what} must be [P,3] with P >= 1")
+        return pts
+
+    def _allocate(self, layout) -> None:
+        """ONE allocation, so that ``result`` is one copy.  ``layout``: (name, torch dtype, per-image shape) in byte order; ``_out[name]`` is the
+        device view [capacity, *shape] and ``_host()[name]`` the host view of the images added."""
+        self._layout = [(name, dt, (self.capacity, *shape)) for name, dt, shape in layout]
+        self._cut = np.cumsum([0] + [math.prod(shape) * dt.itemsize for _, dt, shape in self._layout]).tolist()
+        self._buf = torch.zeros((self._cut[-1],), dtype=torch.uint8, device=self.device)
+        self._out = {name: self._buf[a:b].view(dt).view(*shape) for (name, dt, shape), a, b in zip(self._layout, self._cut, self._cut[1:])}
+
+    def _host(self) -> Dict[str, np.ndarray]:
+        """The one device-to-host copy of an evaluation (which waits for the launches), cut like ``_out``, the images added only."""
+        host = self._buf.cpu().numpy()
+        return {name: host[a:b].view(_NUMPY[dt]).reshape(shape)[:self.count]
+                for (name, dt, shape), a, b in zip(self._layout, self._cut, self._cut[1:])}
+
+    def reset(self) -> None:
+        self.count = self._bop_count = 0
+
+    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None, bop=None,
+            depth_test: Optional[torch.Tensor] = None) -> None:
+        """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6]
+        (``LinemodFolder.camera_input``); ``gt`` float64 [B,88] (``gt_table``) for ``DeviceEvaluator``, [B,amax,88] (``gt_scene_table``) for
+        ``SceneEvaluator``; all on the evaluator's device.  Everything is checked on the host before the library sees a pointer; a batch that
+        does not fit the remaining capacity raises ValueError.
+        ``draw_into``: uint8 [B,H,W,3] on the device that already holds the original frames (it may be ``frames``): after scoring, the
+        ground truth - every valid annotation - and the kept detections are drawn into it from the same table and rows, each with its
+        label's cuboid, on the same stream (hep_draw_poses_device; needs the evaluator's ``cuboid`` / ``cuboids``).  The scores do not depend on it.
+        ``meshes``: a ``render.MeshSet`` next to ``draw_into``, one mesh per label: the filled models of the kept detections are blended in
+        first (hep_render_models_device, the labels' colours at half weight), then the lines are drawn on top.
+        ``bop``: a ``bop.BopSettings`` over the evaluator's labels (``DeviceEvaluator``: 0..``label``): MSSD, MSPD and VSD (tau = the
+        label's diameter times each tau fraction) of every matched (annotation, detection) pair go into a second buffer at the running
+        offset, and ``result`` gains a ``"bop"`` entry with one extra copy; ``depth_test``: float32 [B,H,W] measured depth in the model's
+        unit, one image per frame, for VSD's visibility.  Without ``bop`` nothing changes: same launches, same bytes."""
+        who, dev = type(self).__name__ + ".add", self.device
+        _check_draw_into(who, draw_into, frames, self._cuboids, dev, self.max_detections)
+        _check_meshes(who, meshes, draw_into, dev, self.max_detections)
+        bop_size = _check_bop(who, bop, depth_test, frames, dev, self.num_labels)
+        for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
+            if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
+                raise ValueError(f"{who}: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
+        if frames.dim() != 4 or frames.shape[0] < 1:
+            raise ValueError(f"{who}: frames must be uint8 [B,H,W,3] or float32 [B,3,S,S]")
+        B = int(frames.shape[0])
+        if frames.dtype == torch.uint8:
+            if frames.shape[3] != 3:
+                raise ValueError(f"{who}: uint8 frames must be [B,H,W,3]")
+        elif frames.dtype != torch.float32 or tuple(frames.shape[1:]) != (3, self.image_size, self.image_size):
+            raise ValueError(f"{who}: an image must be float32 [B,3,{self.image_size},{self.image_size}]")
+        gt_shape = (B, *self._gt_shape)
+        if tuple(camera.shape) != (B, 6) or tuple(gt.shape) != gt_shape:
+            raise ValueError(f"{who}: camera must be [{B},6] and gt [{','.join(map(str, gt_shape))}]")
+        if self.count + B > self.capacity:
+            raise ValueError(f"{who}: {self.count} + {B} images exceed the capacity of {self.capacity}")
+        x = self.model.model.session(self.image_size, B, dev).preprocess(frames) if frames.dtype == torch.uint8 else frames
+        det = self.model.detect(x, camera)
+        rows = int(det["scores"].shape[1]) if det["scores"].dim() == 2 else 0
+        for k, w, dt in (("boxes", 4, torch.float32), ("scores", None, torch.float32), ("labels", None, torch.int32), ("rotation", 3, torch.float32),
+                         ("translation", 3, torch.float32), ("hand", 63, torch.float32)):
+            t = det[k]
+            if tuple(t.shape) != ((B, rows) if w is None else (B, rows, w)) or t.dtype != dt or t.device != dev:
+                raise ValueError(f"{who}: detection rows '{k}' have shape {tuple(t.shape)} / {t.dtype} on {t.device}")
+        if not 1 <= rows <= 256 or self.max_detections > rows:
+            raise ValueError(f"{who}: {rows} detection rows: must be 1..256 and >= max_detections {self.max_detections}")
+        d = [det[k].contiguous() for k in _DETECTION_KEYS]
+        g = gt.contiguous()
+        o = self.count
+        _capi.check(self._launch([t.data_ptr() for t in d], B, rows, g.data_ptr(), {k: v[o:].data_ptr() for k, v in self._out.items()},
+                                 torch.cuda.current_stream(dev).cuda_stream))
+        self.count += B
+        scene = g.view(B, -1, GT_DOUBLES)                  # [B,amax,88]; row 0 carries the image's camera whichever the class
+        if bop is not None:
+            records, diameters = self._bop_records(self._out["records"][o:o + B])
+            _score_bop(self, bop, bop_size, scene, d, records, diameters, depth_test, o)
+        if meshes is not None:
+            _blend_models(draw_into, meshes, scene[:, 0], d, self.score_threshold, self.max_detections)
+        if draw_into is not None:
+            from .draw import draw_poses
+            draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(_DETECTION_KEYS, d)),
+                       score_threshold=self.score_threshold, max_detections=self.max_detections, ann_layers=self.draw_layers,
+                       det_layers=self.draw_layers, thickness=self.draw_thickness)
+
+    def _with_bop(self, out: dict, records: np.ndarray) -> dict:
+        """``result``'s ``"bop"`` entry, where ``add`` was given ``bop=``."""
+        if self._bop_count:
+            out["bop"] = _bop_result(self, type(self).__name__ + ".result", *self._bop_records(records))
+        return out
+
+
+class DeviceEvaluator(_Evaluator):
     """``evaluate`` with nothing on the host until the end: ``add`` runs preprocess (uint8 frames), ``model.detect`` and ONE launch of
     hep_score_detections_device per batch - per-image matching plus ADD, ADD-S, translation, rotation, tip, reprojection and hand
     errors of the matched pair - into device buffers of ``capacity`` images at a running offset, with no device-to-host copy and no
@@ -495,124 +649,67 @@ class DeviceEvaluator:
     Scope: one annotation per image and one evaluated ``label``, as ``evaluate`` has; several annotations per image and several
     labels in one pass: ``SceneEvaluator``."""
 
+    _gt_shape = (GT_DOUBLES,)
+
     def __init__(self, model, points, diameter: float, image_size: int, capacity: int, score_threshold: float = 0.05, max_detections: int = 10,
                  iou_threshold: float = 0.5, diameter_threshold: float = 0.1, label: int = 0, symmetric: bool = False,
                  device: Optional[torch.device] = None, max_points: int = 1000, cuboid=None, draw_layers: int = _capi.DRAW_CUBOID,
                  draw_thickness: int = 2):
-        if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
-            raise ValueError("DeviceEvaluator: capacity and max_detections must be >= 1, max_points in 1..1024")
-        self.model, self.image_size, self.capacity = model, int(image_size), int(capacity)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        # ``add(..., draw_into=)``: the model cuboid float32 [8,3] (``LinemodFolder.cuboid``) at every label up to ``label`` - the table's rows carry
-        # label 0, the detections theirs - and the layers (HEP_DRAW_*) and line thickness of both annotation and detections
-        self._cuboids = None
-        if cuboid is not None:
+        self._check_sizes(capacity, max_detections, max_points)
+        super().__init__(model, image_size, capacity, score_threshold, max_detections, iou_threshold, diameter_threshold, device, max_points,
+                         draw_layers, draw_thickness)
+        self.label, self.symmetric, self.diameter = int(label), bool(symmetric), float(diameter)
+        self.num_labels = self.label + 1                   # the labels its cuboids, ``meshes`` and ``bop`` sets hold: 0..``label``
+        if cuboid is not None:                             # ``LinemodFolder.cuboid``, at every label: the table's rows carry label 0, the detections theirs
             c = np.ascontiguousarray(cuboid, dtype=np.float32)
             if c.shape != (8, 3):
                 raise ValueError("DeviceEvaluator: cuboid must be [8,3]")
-            self._cuboids = torch.from_numpy(np.repeat(c[None], int(label) + 1, axis=0)).to(self.device)
-        self.draw_layers, self.draw_thickness = int(draw_layers), int(draw_thickness)
-        pts = np.ascontiguousarray(points, dtype=np.float32)
-        if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
-            raise ValueError("DeviceEvaluator: points must be [P,3] with P >= 1")
-        self.points = torch.from_numpy(pts).to(self.device)
-        self.diameter, self.diameter_threshold = float(diameter), float(diameter_threshold)
-        self.score_threshold, self.max_detections, self.iou_threshold = float(score_threshold), int(max_detections), float(iou_threshold)
-        self.label, self.symmetric, self.max_points = int(label), bool(symmetric), int(max_points)
-        # ONE allocation, so that ``result`` is one copy: records [capacity,16] float64 | scores [capacity,M] float32 | flags [capacity,M] int32
-        M, C = self.max_detections, self.capacity
-        self._buf = torch.zeros((C * (RECORD_DOUBLES * 8 + M * 8),), dtype=torch.uint8, device=self.device)
-        self._records = self._buf[:C * RECORD_DOUBLES * 8].view(torch.float64).view(C, RECORD_DOUBLES)
-        self._scores = self._buf[C * RECORD_DOUBLES * 8:C * (RECORD_DOUBLES * 8 + M * 4)].view(torch.float32).view(C, M)
-        self._tp = self._buf[C * (RECORD_DOUBLES * 8 + M * 4):].view(torch.int32).view(C, M)
-        self.count = 0
-        self._bop_buf, self._bop_count, self._bop_width = None, 0, 0      # ``add(..., bop=)``: errors [C,1,2+T] float64, allocated on first use
+            self._cuboids = torch.from_numpy(np.repeat(c[None], self.num_labels, axis=0)).to(self.device)
+        self.points = torch.from_numpy(self._points(points, "points")).to(self.device)
+        M = self.max_detections
+        self._allocate([("records", torch.float64, (RECORD_DOUBLES,)), ("scores", torch.float32, (M,)), ("tp", torch.int32, (M,))])
 
-    def reset(self) -> None:
-        self.count = self._bop_count = 0
+    def _launch(self, det, B, rows, gt, out, stream):
+        return _capi.lib().hep_score_detections_device(
+            *det, B, rows, gt, self.points.data_ptr(), int(self.points.shape[0]), self.max_points,
+            self.label, self.score_threshold, self.max_detections, self.iou_threshold, out["records"], out["scores"], out["tp"], stream)
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None, bop=None,
-            depth_test: Optional[torch.Tensor] = None) -> None:
-        """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6]
-        (``LinemodFolder.camera_input``); ``gt`` float64 [B,88] (``gt_table``); all on the evaluator's device.  Everything is checked on
-        the host before the library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.
-        ``draw_into``: uint8 [B,H,W,3] on the device that already holds the original frames (it may be ``frames``): after scoring, the
-        ground truth and the kept detections are drawn into it from the same table and rows, on the same stream
-        (hep_draw_poses_device; needs the evaluator's ``cuboid``).  The scores do not depend on it.
-        ``meshes``: a ``render.MeshSet`` next to ``draw_into``: the filled models of the kept detections are blended in first
-        (hep_render_models_device, the labels' colours at half weight), then the lines are drawn on top.
-        ``bop``: a ``bop.BopSettings`` (its sets hold labels 0..``label``): MSSD, MSPD and VSD of every matched pair go into a second
-        buffer at the running offset and ``result`` gains a ``"bop"`` entry; ``depth_test``: float32 [B,H,W] measured depth in the
-        model's unit for VSD's visibility.  Without ``bop`` nothing changes."""
-        dev = self.device
-        _check_draw_into("DeviceEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
-        _check_meshes("DeviceEvaluator.add", meshes, draw_into, dev, self.max_detections)
-        bop_size = _check_bop("DeviceEvaluator.add", bop, depth_test, frames, dev, self.label + 1)
-        for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
-            if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
-                raise ValueError(f"DeviceEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
-        if frames.dim() != 4 or frames.shape[0] < 1:
-            raise ValueError("DeviceEvaluator.add: frames must be uint8 [B,H,W,3] or float32 [B,3,S,S]")
-        B = int(frames.shape[0])
-        if frames.dtype == torch.uint8:
-            if frames.shape[3] != 3:
-                raise ValueError("DeviceEvaluator.add: uint8 frames must be [B,H,W,3]")
-        elif frames.dtype != torch.float32 or tuple(frames.shape[1:]) != (3, self.image_size, self.image_size):
-            raise ValueError(f"DeviceEvaluator.add: an image must be float32 [B,3,{self.image_size},{self.image_size}]")
-        if tuple(camera.shape) != (B, 6) or tuple(gt.shape) != (B, GT_DOUBLES):
-            raise ValueError(f"DeviceEvaluator.add: camera must be [{B},6] and gt [{B},{GT_DOUBLES}]")
-        if self.count + B > self.capacity:
-            raise ValueError(f"DeviceEvaluator.add: {self.count} + {B} images exceed the capacity of {self.capacity}")
-        x = self.model.model.session(self.image_size, B, dev).preprocess(frames) if frames.dtype == torch.uint8 else frames
-        det = self.model.detect(x, camera)
-        rows = int(det["scores"].shape[1]) if det["scores"].dim() == 2 else 0
-        for k, w, dt in (("boxes", 4, torch.float32), ("scores", None, torch.float32), ("labels", None, torch.int32), ("rotation", 3, torch.float32),
-                         ("translation", 3, torch.float32), ("hand", 63, torch.float32)):
-            t = det[k]
-            if tuple(t.shape) != ((B, rows) if w is None else (B, rows, w)) or t.dtype != dt or t.device != dev:
-                raise ValueError(f"DeviceEvaluator.add: detection rows '{k}' have shape {tuple(t.shape)} / {t.dtype} on {t.device}")
-        if not 1 <= rows <= 256 or self.max_detections > rows:
-            raise ValueError(f"DeviceEvaluator.add: {rows} detection rows: must be 1..256 and >= max_detections {self.max_detections}")
-        d = [det[k].contiguous() for k in ("boxes", "scores", "labels", "rotation", "translation", "hand")]
-        g = gt.contiguous()
-        o = self.count
-        _capi.check(_capi.lib().hep_score_detections_device(
-            *[t.data_ptr() for t in d], B, rows, g.data_ptr(), self.points.data_ptr(), int(self.points.shape[0]), self.max_points,
-            self.label, self.score_threshold, self.max_detections, self.iou_threshold,
-            self._records[o:].data_ptr(), self._scores[o:].data_ptr(), self._tp[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        self.count += B
-        if bop is not None:
-            # the scene layout of this evaluator's records: every image is an annotation of ``label``; slot 1 matched and 2 the row as they are
-            rec = self._records[o:o + B].clone()[:, None, :]
-            rec[..., 0], rec[..., 12] = 1.0, float(self.label)
-            _score_bop(self, bop, bop_size, g[:, None, :], d, rec, [self.diameter] * (self.label + 1), depth_test, o, B, 1)
-        if meshes is not None:
-            _blend_models(draw_into, meshes, g, d, self.score_threshold, self.max_detections)
-        if draw_into is not None:
-            from .draw import draw_poses
-            draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(("boxes", "scores", "labels", "rotation", "translation", "hand"), d)),
-                       score_threshold=self.score_threshold, max_detections=self.max_detections, ann_layers=self.draw_layers,
-                       det_layers=self.draw_layers, thickness=self.draw_thickness)
+    def _bop_records(self, records):
+        """Records [n,16], device or host, in the scene layout [n,1,16] BOP reads: every image is an annotation of ``label``; slot 1 matched
+        and 2 the row as they are.  With the diameter of every label up to it."""
+        scene = (records.clone() if isinstance(records, torch.Tensor) else records.copy())[:, None, :]
+        scene[..., 0], scene[..., 12] = 1.0, float(self.label)
+        return scene, [self.diameter] * self.num_labels
 
     def result(self) -> Dict[str, float]:
         """The metric dictionary of the images added since the last ``reset``: one device-to-host copy (which waits for the launches),
         then the host arithmetic of ``evaluate``'s tail."""
-        host = self._buf.cpu().numpy()
-        C, M, n = self.capacity, self.max_detections, self.count
-        rec = host[:C * RECORD_DOUBLES * 8].view(np.float64).reshape(C, RECORD_DOUBLES)[:n]
-        sc = host[C * RECORD_DOUBLES * 8:C * (RECORD_DOUBLES * 8 + M * 4)].view(np.float32).reshape(C, M)[:n]
-        tp = host[C * (RECORD_DOUBLES * 8 + M * 4):].view(np.int32).reshape(C, M)[:n]
-        keep = np.arange(M)[None, :] < rec[:, 0:1]                       # the considered detections, image by image, in row order
-        r = rec[rec[:, 1] == 1.0]
-        m = None
-        if r.shape[0]:
-            m = dict(add=r[:, 5], add_s=r[:, 6], t_diff=r[:, 7], r_diff=r[:, 8], tip=r[:, 9], reproj=r[:, 10], hand=r[:, 11][~np.isnan(r[:, 11])])
-        out = metric_summary(float(n), [float(v) for v in sc[keep]], tp[keep], m, self.diameter * self.diameter_threshold, symmetric=self.symmetric)
-        if self._bop_count:
-            scene = rec.copy()[:, None, :]
-            scene[..., 0], scene[..., 12] = 1.0, float(self.label)
-            out["bop"] = _bop_result(self, "DeviceEvaluator.result", scene, [self.diameter] * (self.label + 1))
-        return out
+        host = self._host()
+        rec, sc, tp = host["records"], host["scores"], host["tp"]
+        keep = np.arange(self.max_detections)[None, :] < rec[:, 0:1]      # the considered detections, image by image, in row order
+        out = metric_summary(float(self.count), [float(v) for v in sc[keep]], tp[keep], _matched_metrics(rec[rec[:, 1] == 1.0]),
+                             self.diameter * self.diameter_threshold, symmetric=self.symmetric)
+        return self._with_bop(out, rec)
+
+
+def _evaluate_folder(ev: _Evaluator, dataset, table, image_size: int, batch_size: int, save_path: Optional[str], meshes, **add_kw):
+    """The folder loop of ``evaluate_device`` and ``evaluate_scene_device``: batch by batch the frames, camera rows and
+    ``table(annotations, cameras, scale)`` uploaded and added to ``ev`` (with ``add_kw``), the drawn frames saved; returns ``ev.result()``."""
+    n, device = len(dataset), ev.device
+    for i0 in range(0, n, batch_size):
+        idx = list(range(i0, min(n, i0 + batch_size)))
+        frames = [dataset.load_image(i) for i in idx]
+        h, w = frames[0].shape[:2]
+        if any(f.shape[:2] != (h, w) for f in frames):
+            raise ValueError("frames of one batch must share a size")
+        scale = image_size / max(h, w)
+        u8 = torch.from_numpy(np.stack(frames)).to(device)
+        cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
+        gt = torch.from_numpy(table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale)).to(device)
+        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes, **add_kw)
+        if save_path is not None:
+            save_frames(save_path, idx, u8)
+    return ev.result()
 
 
 def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
@@ -627,30 +724,16 @@ def evaluate_device(dataset: LinemodFolder, model, image_size: int, score_thresh
     synchronisation per batch); the dictionary is the same with and without it.  ``draw_model`` (with ``save_path``): the filled model
     of every kept detection under its pose, blended in beneath the lines; the folder's PLY file must have triangle faces (ValueError)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    n = len(dataset)
     layers = _capi.DRAW_CUBOID | (_capi.DRAW_HAND if draw_hand else 0) | (_capi.DRAW_BOX2D if draw_bbox_2d else 0)
     if save_path is not None and dataset.cuboid is None:
         raise ValueError("evaluate_device: save_path needs the model cuboid (min_* / size_* in models_info.yml)")
     if draw_model and save_path is None:
         raise ValueError("evaluate_device: draw_model draws into the saved frames: it needs save_path")
     meshes = _folder_meshes("evaluate_device", dataset.model_path, [dataset.object_id], device) if draw_model else None
-    ev = DeviceEvaluator(model, dataset.points, dataset.diameter, image_size, max(n, 1), score_threshold, max_detections, iou_threshold,
+    ev = DeviceEvaluator(model, dataset.points, dataset.diameter, image_size, max(len(dataset), 1), score_threshold, max_detections, iou_threshold,
                          diameter_threshold, symmetric=symmetric, device=device, cuboid=dataset.cuboid if save_path is not None else None,
                          draw_layers=layers)
-    for i0 in range(0, n, batch_size):
-        idx = list(range(i0, min(n, i0 + batch_size)))
-        frames = [dataset.load_image(i) for i in idx]
-        h, w = frames[0].shape[:2]
-        if any(f.shape[:2] != (h, w) for f in frames):
-            raise ValueError("frames of one batch must share a size")
-        scale = image_size / max(h, w)
-        u8 = torch.from_numpy(np.stack(frames)).to(device)
-        cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
-        gt = torch.from_numpy(gt_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale)).to(device)
-        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes)
-        if save_path is not None:
-            save_frames(save_path, idx, u8)
-    return ev.result()
+    return _evaluate_folder(ev, dataset, gt_table, image_size, batch_size, save_path, meshes)
 
 
 def save_frames(save_path: str, indices: Sequence[int], frames: torch.Tensor) -> None:
@@ -724,7 +807,7 @@ def scene_mean(per_label: Dict[int, Dict[str, float]]) -> Dict[str, float]:
     return out
 
 
-class SceneEvaluator:
+class SceneEvaluator(_Evaluator):
     """``DeviceEvaluator`` for scenes: up to ``amax`` annotations per image over ``len(models)`` labels.  ``add`` runs preprocess,
     ``model.detect`` (ONE forward per batch, whatever the number of labels) and ONE launch of hep_score_scene_device per batch into
     ONE allocation at a running offset, with no device-to-host copy; ``result`` makes the one copy of an evaluation.
@@ -738,115 +821,44 @@ class SceneEvaluator:
     def __init__(self, model, models, image_size: int, capacity: int, amax: int, score_threshold: float = 0.05, max_detections: int = 10,
                  iou_threshold: float = 0.5, diameter_threshold: float = 0.1, device: Optional[torch.device] = None, max_points: int = 1000,
                  cuboids=None, draw_layers: int = _capi.DRAW_CUBOID, draw_thickness: int = 2):
-        if capacity < 1 or max_detections < 1 or not 1 <= max_points <= 1024:
-            raise ValueError("SceneEvaluator: capacity and max_detections must be >= 1, max_points in 1..1024")
+        self._check_sizes(capacity, max_detections, max_points)
         if not 1 <= amax <= MAX_ANNOTATIONS:
             raise ValueError(f"SceneEvaluator: amax must be in 1..{MAX_ANNOTATIONS}")
         if not 1 <= len(models) <= MAX_LABELS:
             raise ValueError(f"SceneEvaluator: 1..{MAX_LABELS} object models, one per label")
-        self.model, self.image_size, self.capacity, self.amax = model, int(image_size), int(capacity), int(amax)
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        # ``add(..., draw_into=)``: the model cuboids float32 [labels,8,3] (``SceneFolder.cuboids``), the layers (HEP_DRAW_*) and line thickness
-        self._cuboids = None
-        if cuboids is not None:
+        super().__init__(model, image_size, capacity, score_threshold, max_detections, iou_threshold, diameter_threshold, device, max_points,
+                         draw_layers, draw_thickness)
+        self.amax, self.num_labels = int(amax), len(models)
+        self._gt_shape = (self.amax, GT_DOUBLES)
+        if cuboids is not None:                            # ``SceneFolder.cuboids``
             c = np.ascontiguousarray(cuboids, dtype=np.float32)
             if c.shape != (len(models), 8, 3):
                 raise ValueError(f"SceneEvaluator: cuboids must be [{len(models)},8,3], one per label")
             self._cuboids = torch.from_numpy(c).to(self.device)
-        self.draw_layers, self.draw_thickness = int(draw_layers), int(draw_thickness)
-        clouds, self.diameters, self.symmetric = [], [], []
-        for l, (points, diameter, symmetric) in enumerate(models):
-            pts = np.ascontiguousarray(points, dtype=np.float32)
-            if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
-                raise ValueError(f"SceneEvaluator: the points of label {l} must be [P,3] with P >= 1")
-            clouds.append(pts); self.diameters.append(float(diameter)); self.symmetric.append(bool(symmetric))
-        self.num_labels = len(clouds)
+        clouds = [self._points(points, f"the points of label {l}") for l, (points, _, _) in enumerate(models)]
+        self.diameters, self.symmetric = [float(m[1]) for m in models], [bool(m[2]) for m in models]
         self._offsets = (ctypes.c_int32 * (self.num_labels + 1))(*np.concatenate(([0], np.cumsum([len(c) for c in clouds]))).tolist())
         self.points = torch.from_numpy(np.concatenate(clouds)).to(self.device)
-        self.diameter_threshold = float(diameter_threshold)
-        self.score_threshold, self.max_detections, self.iou_threshold = float(score_threshold), int(max_detections), float(iou_threshold)
-        self.max_points = int(max_points)
-        # ONE allocation, so that ``result`` is one copy: records [C,amax,16] float64 | scores [C,M] float32 | flags, labels [C,M] int32 | counts [C] int32
-        M, C, A = self.max_detections, self.capacity, self.amax
-        self._cut = np.cumsum([0, C * A * RECORD_DOUBLES * 8, C * M * 4, C * M * 4, C * M * 4, C * 4]).tolist()
-        self._buf = torch.zeros((self._cut[-1],), dtype=torch.uint8, device=self.device)
-        part = lambda k, dt, *shape: self._buf[self._cut[k]:self._cut[k + 1]].view(dt).view(*shape)
-        self._records, self._scores = part(0, torch.float64, C, A, RECORD_DOUBLES), part(1, torch.float32, C, M)
-        self._tp, self._labels, self._counts = part(2, torch.int32, C, M), part(3, torch.int32, C, M), part(4, torch.int32, C)
-        self.count = 0
-        self._bop_buf, self._bop_count, self._bop_width = None, 0, 0      # ``add(..., bop=)``: errors [C,amax,2+T] float64, allocated on first use
+        M = self.max_detections
+        self._allocate([("records", torch.float64, (self.amax, RECORD_DOUBLES)), ("scores", torch.float32, (M,)), ("tp", torch.int32, (M,)),
+                        ("labels", torch.int32, (M,)), ("counts", torch.int32, ())])
 
-    def reset(self) -> None:
-        self.count = self._bop_count = 0
+    def _launch(self, det, B, rows, gt, out, stream):
+        return _capi.lib().hep_score_scene_device(
+            *det, B, rows, gt, self.amax, self.points.data_ptr(), self._offsets, self.num_labels, self.max_points,
+            self.score_threshold, self.max_detections, self.iou_threshold, out["records"], out["scores"], out["tp"], out["labels"], out["counts"],
+            stream)
 
-    def add(self, frames, camera: torch.Tensor, gt: torch.Tensor, draw_into: Optional[torch.Tensor] = None, meshes=None, bop=None,
-            depth_test: Optional[torch.Tensor] = None) -> None:
-        """One batch: ``frames`` uint8 [B,H,W,3] (preprocessed here) or the network input float32 [B,3,S,S]; ``camera`` float32 [B,6];
-        ``gt`` float64 [B,amax,88] (``gt_scene_table``); all on the evaluator's device.  Everything is checked on the host before the
-        library sees a pointer; a batch that does not fit the remaining capacity raises ValueError.  ``draw_into``: as for
-        ``DeviceEvaluator.add`` - every valid annotation and every kept detection, each with its label's cuboid.  ``meshes``: as for
-        ``DeviceEvaluator.add``, one mesh per label.  ``bop``: a ``bop.BopSettings`` over the evaluator's labels: MSSD, MSPD and VSD
-        (tau = the label's diameter times each tau fraction) of every matched (annotation, detection) pair go into a second buffer at
-        the running offset, and ``result`` gains a ``"bop"`` entry with one extra copy; ``depth_test``: float32 [B,H,W] measured depth
-        in the model's unit, one image per frame, for VSD's visibility.  Without ``bop`` nothing changes: same launches, same bytes."""
-        dev = self.device
-        _check_draw_into("SceneEvaluator.add", draw_into, frames, self._cuboids, dev, self.max_detections)
-        _check_meshes("SceneEvaluator.add", meshes, draw_into, dev, self.max_detections)
-        bop_size = _check_bop("SceneEvaluator.add", bop, depth_test, frames, dev, self.num_labels)
-        for name, t, dt in (("frames", frames, None), ("camera", camera, torch.float32), ("gt", gt, torch.float64)):
-            if not isinstance(t, torch.Tensor) or t.device != dev or (dt is not None and t.dtype != dt):
-                raise ValueError(f"SceneEvaluator.add: {name} must be a {dt or 'uint8 or float32'} tensor on {dev}")
-        if frames.dim() != 4 or frames.shape[0] < 1:
-            raise ValueError("SceneEvaluator.add: frames must be uint8 [B,H,W,3] or float32 [B,3,S,S]")
-        B = int(frames.shape[0])
-        if frames.dtype == torch.uint8:
-            if frames.shape[3] != 3:
-                raise ValueError("SceneEvaluator.add: uint8 frames must be [B,H,W,3]")
-        elif frames.dtype != torch.float32 or tuple(frames.shape[1:]) != (3, self.image_size, self.image_size):
-            raise ValueError(f"SceneEvaluator.add: an image must be float32 [B,3,{self.image_size},{self.image_size}]")
-        if tuple(camera.shape) != (B, 6) or tuple(gt.shape) != (B, self.amax, GT_DOUBLES):
-            raise ValueError(f"SceneEvaluator.add: camera must be [{B},6] and gt [{B},{self.amax},{GT_DOUBLES}]")
-        if self.count + B > self.capacity:
-            raise ValueError(f"SceneEvaluator.add: {self.count} + {B} images exceed the capacity of {self.capacity}")
-        x = self.model.model.session(self.image_size, B, dev).preprocess(frames) if frames.dtype == torch.uint8 else frames
-        det = self.model.detect(x, camera)
-        rows = int(det["scores"].shape[1]) if det["scores"].dim() == 2 else 0
-        for k, w, dt in (("boxes", 4, torch.float32), ("scores", None, torch.float32), ("labels", None, torch.int32), ("rotation", 3, torch.float32),
-                         ("translation", 3, torch.float32), ("hand", 63, torch.float32)):
-            t = det[k]
-            if tuple(t.shape) != ((B, rows) if w is None else (B, rows, w)) or t.dtype != dt or t.device != dev:
-                raise ValueError(f"SceneEvaluator.add: detection rows '{k}' have shape {tuple(t.shape)} / {t.dtype} on {t.device}")
-        if not 1 <= rows <= 256 or self.max_detections > rows:
-            raise ValueError(f"SceneEvaluator.add: {rows} detection rows: must be 1..256 and >= max_detections {self.max_detections}")
-        d = [det[k].contiguous() for k in ("boxes", "scores", "labels", "rotation", "translation", "hand")]
-        g = gt.contiguous()
-        o = self.count
-        _capi.check(_capi.lib().hep_score_scene_device(
-            *[t.data_ptr() for t in d], B, rows, g.data_ptr(), self.amax, self.points.data_ptr(), self._offsets, self.num_labels, self.max_points,
-            self.score_threshold, self.max_detections, self.iou_threshold, self._records[o:].data_ptr(), self._scores[o:].data_ptr(),
-            self._tp[o:].data_ptr(), self._labels[o:].data_ptr(), self._counts[o:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
-        self.count += B
-        if bop is not None:
-            _score_bop(self, bop, bop_size, g, d, self._records[o:o + B], self.diameters, depth_test, o, B, self.amax)
-        if meshes is not None:
-            _blend_models(draw_into, meshes, g[:, 0], d, self.score_threshold, self.max_detections)
-        if draw_into is not None:
-            from .draw import draw_poses
-            draw_poses(draw_into, cuboids=self._cuboids, gt=g, detections=dict(zip(("boxes", "scores", "labels", "rotation", "translation", "hand"), d)),
-                       score_threshold=self.score_threshold, max_detections=self.max_detections, ann_layers=self.draw_layers,
-                       det_layers=self.draw_layers, thickness=self.draw_thickness)
+    def _bop_records(self, records):
+        return records, self.diameters
 
     def result(self) -> Dict[str, dict]:
         """``{"labels": {l: dict}, "mean": dict}`` of the images added since the last ``reset``: one device-to-host copy (which waits
         for the launches), then the host arithmetic."""
-        host = self._buf.cpu().numpy()
-        C, M, A, n = self.capacity, self.max_detections, self.amax, self.count
-        part = lambda k, dt, *shape: host[self._cut[k]:self._cut[k + 1]].view(dt).reshape(*shape)[:n]
-        out = summarise_scene(part(0, np.float64, C, A, RECORD_DOUBLES), part(1, np.float32, C, M), part(2, np.int32, C, M), part(3, np.int32, C, M),
-                              part(4, np.int32, C), self.diameters, self.symmetric, self.diameter_threshold)
-        if self._bop_count:
-            out["bop"] = _bop_result(self, "SceneEvaluator.result", part(0, np.float64, C, A, RECORD_DOUBLES), self.diameters)
-        return out
+        host = self._host()
+        out = summarise_scene(host["records"], host["scores"], host["tp"], host["labels"], host["counts"], self.diameters, self.symmetric,
+                              self.diameter_threshold)
+        return self._with_bop(out, host["records"])
 
 
 def summarise_scene(rec: np.ndarray, sc: np.ndarray, tp: np.ndarray, labels: np.ndarray, counts: np.ndarray, diameters: Sequence[float],
@@ -861,14 +873,11 @@ def summarise_scene(rec: np.ndarray, sc: np.ndarray, tp: np.ndarray, labels: np.
         r = flat[(flat[:, 0] == 1.0) & (flat[:, 12] == l)]
         num_ann = float(r.shape[0])
         r = r[r[:, 1] == 1.0]
-        m = None
-        if r.shape[0]:
-            m = dict(add=r[:, 5], add_s=r[:, 6], t_diff=r[:, 7], r_diff=r[:, 8], tip=r[:, 9], reproj=r[:, 10], hand=r[:, 11][~np.isnan(r[:, 11])])
-        per_label[l] = metric_summary(num_ann, [float(v) for v in sc[own]], tp[own], m, diameter * diameter_threshold, symmetric=sym)
+        per_label[l] = metric_summary(num_ann, [float(v) for v in sc[own]], tp[own], _matched_metrics(r), diameter * diameter_threshold, symmetric=sym)
     return {"labels": per_label, "mean": scene_mean(per_label)}
 
 
-class SceneFolder:
+class SceneFolder(_Folder):
     """One scene folder of a Linemod-format dataset (``<root>/data/<NN>/`` as ``LinemodFolder`` reads it) with EVERY ground-truth entry of
     a frame whose ``obj_id`` is in ``object_ids``; the label of an entry is the index of its object in that list.  ``scene_id``: the
     folder number (default: the first object id).  Boxes come from ``obj_bb`` (x, y, w, h) or, for the objects ``mask_values`` maps to
@@ -877,63 +886,40 @@ class SceneFolder:
 
     def __init__(self, dataset_path: str, object_ids: Sequence[int], scene_id: Optional[int] = None, fold: int = 0, split: str = "test",
                  mask_values: Optional[Dict[int, int]] = None, image_extension: str = ".png"):
-        import yaml
-        loader = getattr(yaml, "CSafeLoader", yaml.SafeLoader)
         self.object_ids = [int(o) for o in object_ids]
         if not self.object_ids or len(set(self.object_ids)) != len(self.object_ids):
             raise ValueError("SceneFolder: object_ids must be a non-empty list without repeats")
-        scene_id = self.object_ids[0] if scene_id is None else int(scene_id)
-        self.object_path = os.path.join(dataset_path, "data", f"{scene_id:02}")
-        self.model_path = os.path.join(dataset_path, "models")
-        with open(os.path.join(self.object_path, f"{split}_{fold}.txt")) as f:
-            examples = [e.strip() for e in f if e.strip()]
-        with open(os.path.join(self.object_path, f"gt_{fold}.yml")) as f:
-            gt = yaml.load(f, Loader=loader)
-        with open(os.path.join(self.object_path, f"info_{fold}.yml")) as f:
-            info = yaml.load(f, Loader=loader)
-        with open(os.path.join(self.model_path, "models_info.yml")) as f:
-            models = yaml.load(f, Loader=loader)
+        self._mask_values = mask_values or {}
+        super().__init__(dataset_path, self.object_ids[0] if scene_id is None else int(scene_id), fold, split, image_extension)
+        self.amax = max([len(e) for e in self.annotations] + [1])
+
+    def _read_models(self, models: dict) -> None:
         self.models = [(load_ply_vertices(os.path.join(self.model_path, f"obj_{o:02}.ply")), float(models[o]["diameter"]),
                         any(k.startswith("symmetries") for k in models[o])) for o in self.object_ids]
         self.models_info = [models[o] for o in self.object_ids]                              # ``bop.symmetry_transforms`` reads the symmetries
         boxes = [_model_cuboid(models[o]) for o in self.object_ids]
         self.cuboids = np.stack(boxes) if all(c is not None for c in boxes) else None      # float32 [labels,8,3], or None without min_* / size_*
-        names = sorted(n for n in os.listdir(os.path.join(self.object_path, "rgb"))
-                       if n.endswith(image_extension) and n[:-len(image_extension)] in examples)
-        self.image_paths = [os.path.join(self.object_path, "rgb", n) for n in names]
-        self.annotations, self.camera = [], []
-        mask_values = mask_values or {}
-        for n in names:
-            key = int(n.split(".")[0])
-            mask = None
-            entries = []
-            for a in gt[key]:
-                if a["obj_id"] not in self.object_ids:
-                    continue
-                R = np.array(a["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
-                entry = {"label": self.object_ids.index(a["obj_id"]), "rotation": matrix_to_axis_angle(R),
-                         "translation": np.array(a["cam_t_m2c"], dtype=np.float64),
-                         "drill_tip": np.array(a.get("drill_tip_transform", [0, 0, 0, 1]), dtype=np.float64)}
-                if a["obj_id"] in mask_values:
-                    if mask is None:
-                        from PIL import Image
-                        mask = np.asarray(Image.open(os.path.join(self.object_path, "mask", n)))
-                        mask = mask.reshape(mask.shape[0], mask.shape[1], -1)[:, :, 0]
-                    ys, xs = np.nonzero(mask == mask_values[a["obj_id"]])
-                    entry["bbox"] = np.array([xs.min(), ys.min(), xs.max(), ys.max()], dtype=np.float32) if ys.size else np.zeros(4, np.float32)
-                else:                                     # Linemod's own field: x, y, w, h
-                    x, y, w, h = a["obj_bb"]
-                    entry["bbox"] = np.array([x, y, x + w, y + h], dtype=np.float32)
-                entries.append(entry)
-            if len(entries) > MAX_ANNOTATIONS:
-                raise ValueError(f"SceneFolder: frame {n} holds {len(entries)} annotations, at most {MAX_ANNOTATIONS} are supported")
-            self.annotations.append(entries)
-            self.camera.append(np.array(info[key]["cam_K"], dtype=np.float64).reshape(3, 3))
-        self.amax = max([len(e) for e in self.annotations] + [1])
 
-    __len__ = LinemodFolder.__len__
-    load_image = LinemodFolder.load_image
-    camera_input = LinemodFolder.camera_input
+    def _annotation(self, n: str, entries: list, image_extension: str) -> List[dict]:
+        """EVERY entry of a listed object, in the file's order; the boxes of the objects ``mask_values`` names from the frame's merged mask."""
+        mask = None
+        out = []
+        for a in entries:
+            if a["obj_id"] not in self.object_ids:
+                continue
+            entry = {"label": self.object_ids.index(a["obj_id"]), **self._pose(a)}
+            if a["obj_id"] in self._mask_values:
+                if mask is None:
+                    from PIL import Image
+                    mask = np.asarray(Image.open(os.path.join(self.object_path, "mask", n)))
+                    mask = mask.reshape(mask.shape[0], mask.shape[1], -1)[:, :, 0]
+                entry["bbox"] = self._mask_box(mask == self._mask_values[a["obj_id"]])
+            else:
+                entry["bbox"] = self._obj_bb(a)
+            out.append(entry)
+        if len(out) > MAX_ANNOTATIONS:
+            raise ValueError(f"SceneFolder: frame {n} holds {len(out)} annotations, at most {MAX_ANNOTATIONS} are supported")
+        return out
 
 
 def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_threshold: float = 0.05, max_detections: int = 10,
@@ -947,7 +933,6 @@ def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_th
     and their average recalls as ``result()["bop"]`` (``bop.BopSettings`` built from the folder's ``models/``: the PLY meshes, which
     need triangle faces, and the symmetries of models_info.yml in steps of ``max_sym_disc_step``; no measured depth is read)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    n = len(dataset)
     settings = None
     if bop:
         from .bop import folder_settings
@@ -958,22 +943,10 @@ def evaluate_scene_device(dataset: SceneFolder, model, image_size: int, score_th
     if draw_model and save_path is None:
         raise ValueError("evaluate_scene_device: draw_model draws into the saved frames: it needs save_path")
     meshes = _folder_meshes("evaluate_scene_device", dataset.model_path, dataset.object_ids, device) if draw_model else None
-    ev = SceneEvaluator(model, dataset.models, image_size, max(n, 1), dataset.amax, score_threshold, max_detections, iou_threshold,
+    ev = SceneEvaluator(model, dataset.models, image_size, max(len(dataset), 1), dataset.amax, score_threshold, max_detections, iou_threshold,
                         diameter_threshold, device=device, cuboids=dataset.cuboids if save_path is not None else None, draw_layers=layers)
-    for i0 in range(0, n, batch_size):
-        idx = list(range(i0, min(n, i0 + batch_size)))
-        frames = [dataset.load_image(i) for i in idx]
-        h, w = frames[0].shape[:2]
-        if any(f.shape[:2] != (h, w) for f in frames):
-            raise ValueError("frames of one batch must share a size")
-        scale = image_size / max(h, w)
-        u8 = torch.from_numpy(np.stack(frames)).to(device)
-        cam = torch.from_numpy(np.stack([dataset.camera_input(i, scale) for i in idx])).to(device)
-        gt = torch.from_numpy(gt_scene_table([dataset.annotations[i] for i in idx], [dataset.camera[i] for i in idx], scale, dataset.amax)).to(device)
-        ev.add(u8, cam, gt, draw_into=u8 if save_path is not None else None, meshes=meshes, bop=settings)
-        if save_path is not None:
-            save_frames(save_path, idx, u8)
-    return ev.result()
+    return _evaluate_folder(ev, dataset, lambda annotations, cameras, scale: gt_scene_table(annotations, cameras, scale, dataset.amax),
+                            image_size, batch_size, save_path, meshes, bop=settings)
 
 
 def main(argv=None):
