@@ -9,7 +9,7 @@ from .weights import load_pack, pack_bytes, save_pack, seeded_state_dict, strip_
 
 
 def __getattr__(name):   # torch custom-op registration happens on first use of the model API
-    if name in ("HMDEgoPose", "TrainModelWithLoss", "Session"):
+    if name in ("HMDEgoPose", "TrainModelWithLoss", "Session", "tile_windows", "window_cameras", "window_from_box"):
         from . import model
         return getattr(model, name)
     if name == "TrainableHeads":

@@ -58,6 +58,15 @@ SYMBOLS = {
     "hep_top_labels_device": (c_int, [_P, _FP, _FP, _FP, _FP, _FP, _FP, c_int, c_float, c_void_p, c_void_p]),
     "hep_poses_from_i420": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7),
     "hep_poses_from_input": (c_int, [_P, _FP, c_int, _FP, c_float] + [_FP] * 7),
+    "hep_tile_windows": (c_int, [c_int] * 6 + [c_void_p]),
+    "hep_window_cameras": (c_int, [_FP, c_void_p, c_int, c_int, c_int, c_int, c_int, _FP]),
+    "hep_window_from_box": (c_int, [_FP, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
+    "hep_preprocess_i420_windows_device": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, _FP, c_void_p]),
+    "hep_best_window_device": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "hep_pose_from_i420_windows": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8),
+    "hep_poses_from_i420_windows": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7),
+    "hep_pose_from_i420_tiled": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8 + [c_void_p]),
+    "hep_poses_from_i420_tiled": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7 + [c_void_p]),
     "hep_pose_errors": (c_int, [c_int, _FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP]),
     "hep_pose_errors_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP, c_void_p]),
     "hep_score_detections_device": (c_int, [_FP] * 6 + [c_int, c_int, _FP, _FP, c_int, c_int, c_int, c_float, c_int, c_double, _FP, _FP, _FP, c_void_p]),

@@ -41,6 +41,7 @@ Session::~Session() {
   hipFree(d_keys); hipFree(d_det); hipFree(d_part);
   for (int i = 0; i < 5; i++) hipFree(d_stage[i]);
   hipFree(d_pose_in); hipFree(d_rec); hipHostFree(h_pose_in); hipHostFree(h_rec); hipFree(d_recs); hipHostFree(h_recs);
+  hipFree(d_best); hipHostFree(h_best);
   if (stream) hipStreamDestroy(stream);
 }
 
@@ -421,8 +422,10 @@ static int check_i420(int height, int width, int crop, int resized) {
 }
 
 // the launches of the frame path on `st`; s.mu is held (the two scratch buffers belong to the handle)
+// windows (hep_preprocess_i420_windows_device): a device table [batch][3] {frame, ox, oy} - output image i is that window of the frames at `yuv`
+// in place of the centre crop of frame i; everything behind the first launch is the same
 static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                                  float* out_hwc, hipStream_t st) {
+                                  float* out_hwc, hipStream_t st, const int32_t* windows = nullptr) {
   // The scratch frames are used ASYNCHRONOUSLY on the caller's stream and the mutex only covers the enqueue: a second call on
   // another stream (an in-flight pool) must not overwrite them while the first call's kernels still read them.  An event is
   // recorded behind the last launch of every call and the next call's stream waits for it first (device-side, no host stall).
@@ -442,15 +445,21 @@ static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int
   //  not for stream capture)
   {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return fail(HEP_ERR_UNSUPPORTED, "hep_preprocess_i420_device must not be called under stream capture");
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return fail(HEP_ERR_UNSUPPORTED, std::string(windows ? "hep_preprocess_i420_windows_device" : "hep_preprocess_i420_device") + " must not be called under stream capture");
   }
   if (s.pre_pending) HIPRET(hipStreamWaitEvent(st, s.pre_event, 0));
   // from the first launch on, EVERY return path leaves the event behind the scratch frames' last user
   struct Guard { Session& s; hipStream_t st; ~Guard() { if (hipEventRecord(s.pre_event, st) == hipSuccess) s.pre_pending = true; } } guard{s, st};
   // Program.cs:161 cvtColor + 383-397 CenterCropAndRescaleMat
-  Yv12Args ya; ya.in = yuv; ya.bgr = s.d_pre[0]; ya.B = batch; ya.H = height; ya.W = width; ya.crop = crop;
-  ya.ow = (width - crop) / 2; ya.oh = (height - crop) / 2;
-  launch_yv12_crop(ya, st);
+  if (windows) {
+    Yv12WinArgs wa; wa.in = yuv; wa.bgr = s.d_pre[0]; wa.windows = windows; wa.n = batch; wa.H = height; wa.W = width; wa.crop = crop;
+    launch_yv12_windows(wa, st);
+  } else {
+    Yv12Args ya; ya.in = yuv; ya.bgr = s.d_pre[0]; ya.B = batch; ya.H = height; ya.W = width; ya.crop = crop;
+    ya.ow = (width - crop) / 2; ya.oh = (height - crop) / 2;
+    launch_yv12_crop(ya, st);
+  }
   ResizeArgs r1; r1.in = s.d_pre[0]; r1.out = s.d_pre[1]; r1.B = batch; r1.H = crop; r1.W = crop; r1.nh = resized; r1.nw = resized; r1.S = resized; r1.norm = 0;
   r1.inv_scale_x = (double)crop / resized; r1.inv_scale_y = r1.inv_scale_x;
   launch_resize_u8(r1, st);
@@ -473,6 +482,18 @@ int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int
   HIPRET(hipSetDevice(s.device));
   std::lock_guard<std::mutex> lk(s.mu);
   return preprocess_i420_locked(s, yuv, batch, height, width, crop, resized, out_hwc, (hipStream_t)stream);
+} HEP_CATCH_INT
+
+int hep_preprocess_i420_windows_device(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n,
+                                       int crop, int resized, float* out_hwc, void* stream) try {
+  const Check c{"hep_preprocess_i420_windows_device: "};
+  CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {windows, "windows"}, {out_hwc, "out_hwc"}}));
+  CHECKED(c.at_least("frames", frames, 1)); CHECKED(check_i420(height, width, crop, resized));
+  Session& s = h->s;      // (the handle is read from here on)
+  CHECKED(c.range("n", n, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create"));
+  HIPRET(hipSetDevice(s.device));
+  std::lock_guard<std::mutex> lk(s.mu);
+  return preprocess_i420_locked(s, yuv, n, height, width, crop, resized, out_hwc, (hipStream_t)stream, windows);
 } HEP_CATCH_INT
 
 // ---- decode / filter ----
@@ -688,8 +709,8 @@ static int check_pose(const Check& c, const hep_handle* h, const void* input, co
 // 0.02 ms faster back to back and level at 60 Hz.  Buffers are sized for max_batch payloads of this call's per-image size and only
 // ever grown: a repeated shape allocates nothing.
 static size_t pose_cam_pad(const Session& s) { return ((size_t)s.max_batch * 24 + 255) & ~(size_t)255; }
-static int pose_stage(Session& s, const void* payload, size_t per_image, int batch, const float* camera) {
-  const size_t pad = pose_cam_pad(s), need = pad + per_image * (size_t)s.max_batch;
+// the buffers of a call that stages `need` bytes
+static int pose_reserve(Session& s, size_t need) {
   if (!s.d_rec) {
     const char* e = getenv("HEP_POSE_UPLOAD");
     s.pose_upload_pinned = e && !strcmp(e, "pinned");
@@ -707,6 +728,12 @@ static int pose_stage(Session& s, const void* payload, size_t per_image, int bat
     hipHostFree(s.h_pose_in); s.h_pose_in = nullptr; s.pose_pin_bytes = 0;
     HIPRET(hipHostMalloc((void**)&s.h_pose_in, need, hipHostMallocDefault)); s.pose_pin_bytes = need;
   }
+  return 0;
+}
+static int pose_stage(Session& s, const void* payload, size_t per_image, int batch, const float* camera) {
+  const size_t pad = pose_cam_pad(s);
+  if (int rc = pose_reserve(s, pad + per_image * (size_t)s.max_batch)) return rc;
+  const bool direct = !s.pose_upload_pinned;
   const size_t bytes = per_image * (size_t)batch;
   if (direct) {
     HIPRET(hipMemcpyAsync(s.d_pose_in, camera, (size_t)batch * 24, hipMemcpyHostToDevice, s.stream));
@@ -728,15 +755,8 @@ static int poses_buffers(Session& s) {
   return 0;
 }
 
-// top-detection launch on the handle's own head outputs, the records back through the pinned buffer, synchronise, scatter.
-// per_label (hep_poses_from_*): the launch of hep_top_labels_device, num_classes records per image, output row b * num_classes + c
-static int pose_finish(Session& s, int batch, float score_threshold, const PoseOut& o, bool per_label) {
-  uint32_t* d = per_label ? s.d_recs : s.d_rec;
-  uint32_t* hr = per_label ? s.h_recs : s.h_rec;
-  const int rows = per_label ? batch * s.num_classes : batch;
-  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, batch, score_threshold, d, s.stream, per_label)) return rc;
-  HIPRET(hipMemcpyAsync(hr, d, kRecBytes * rows, hipMemcpyDeviceToHost, s.stream));
-  HIPRET(hipStreamSynchronize(s.stream));
+// the records of a download -> the caller's arrays, row by row
+static void pose_scatter(const uint32_t* hr, int rows, const PoseOut& o) {
   for (int b = 0; b < rows; b++) {
     const uint32_t* r = hr + (size_t)b * HEP_POSE_RECORD_WORDS;
     memcpy(&o.found[b], r + 0, 4);
@@ -748,6 +768,18 @@ static int pose_finish(Session& s, int batch, float score_threshold, const PoseO
     if (o.translation) memcpy(o.translation + (size_t)b * 3, r + 12, 12);
     if (o.hand) memcpy(o.hand + (size_t)b * 63, r + 15, 63 * 4);
   }
+}
+
+// top-detection launch on the handle's own head outputs, the records back through the pinned buffer, synchronise, scatter.
+// per_label (hep_poses_from_*): the launch of hep_top_labels_device, num_classes records per image, output row b * num_classes + c
+static int pose_finish(Session& s, int batch, float score_threshold, const PoseOut& o, bool per_label) {
+  uint32_t* d = per_label ? s.d_recs : s.d_rec;
+  uint32_t* hr = per_label ? s.h_recs : s.h_rec;
+  const int rows = per_label ? batch * s.num_classes : batch;
+  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, batch, score_threshold, d, s.stream, per_label)) return rc;
+  HIPRET(hipMemcpyAsync(hr, d, kRecBytes * rows, hipMemcpyDeviceToHost, s.stream));
+  HIPRET(hipStreamSynchronize(s.stream));
+  pose_scatter(hr, rows, o);
   return 0;
 }
 
@@ -814,6 +846,192 @@ int hep_poses_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height
                         float* rotation, float* translation, float* hand) try {
   return pose_from_i420("hep_poses_from_i420: ", true, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
                         PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+// ---- whole-frame search: windows of a frame, best of the windows (include/hep.h) ----
+// a grid offset along one axis: span = side - crop; one cell sits at the centre (the frame path's crop), several reach both borders
+static int tile_offset(int i, int cells, int span) { return cells == 1 ? span / 2 : (int)(((int64_t)i * span) / (cells - 1)); }
+static void tile_windows(int height, int width, int crop, int nx, int ny, int frames, int32_t* w) {
+  for (int f = 0; f < frames; f++)
+    for (int r = 0; r < ny; r++)
+      for (int i = 0; i < nx; i++, w += 3) { w[0] = f; w[1] = tile_offset(i, nx, width - crop); w[2] = tile_offset(r, ny, height - crop); }
+}
+// camera row of window {frame, ox, oy}: the frame's row with the principal point moved by the window's offset from the centre crop, in pixels
+// of the resized image; every rounding stated (tests/_windows.py restates it)
+static void window_camera(const float* camera, const int32_t* w, int height, int width, int crop, int resized, float* out) {
+  const float* row = camera + (size_t)w[0] * 6;
+  memcpy(out, row, 24);
+  out[2] = (float)((double)row[2] - (double)(w[1] - (width - crop) / 2) * (double)resized / (double)crop);
+  out[3] = (float)((double)row[3] - (double)(w[2] - (height - crop) / 2) * (double)resized / (double)crop);
+}
+// a host table: every window inside its frame; frames < 0: the frame index has no upper limit to hold (hep_window_cameras)
+static int check_windows(const Check& c, const int32_t* windows, int n, int frames, int height, int width, int crop) {
+  for (int i = 0; i < n; i++) {
+    const int32_t* w = windows + (size_t)i * 3;
+    if (w[0] < 0 || (frames >= 0 && w[0] >= frames) || w[1] < 0 || w[1] > width - crop || w[2] < 0 || w[2] > height - crop)
+      return c.fail(HEP_ERR_INVALID, "window " + std::to_string(i) + " {" + std::to_string(w[0]) + ", " + std::to_string(w[1]) + ", " + std::to_string(w[2]) +
+                                     "} lies outside the frame (frame index or offsets)");
+  }
+  return 0;
+}
+
+int hep_tile_windows(int height, int width, int crop, int nx, int ny, int frames, int32_t* windows_out) try {
+  const Check c{"hep_tile_windows: "};
+  CHECKED(c.ptrs({{windows_out, "windows_out"}}));
+  CHECKED(c.at_least("nx", nx, 1)); CHECKED(c.at_least("ny", ny, 1)); CHECKED(c.at_least("frames", frames, 1));
+  CHECKED(check_i420(height, width, crop, 1));
+  tile_windows(height, width, crop, nx, ny, frames, windows_out);
+  return 0;
+} HEP_CATCH_INT
+
+int hep_window_cameras(const float* camera, const int32_t* windows, int n, int height, int width, int crop, int resized, float* camera_out) try {
+  const Check c{"hep_window_cameras: "};
+  CHECKED(c.ptrs({{camera, "camera"}, {windows, "windows"}, {camera_out, "camera_out"}}));
+  CHECKED(c.at_least("n", n, 1)); CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_windows(c, windows, n, -1, height, width, crop));
+  for (int i = 0; i < n; i++) window_camera(camera, windows + (size_t)i * 3, height, width, crop, resized, camera_out + (size_t)i * 6);
+  return 0;
+} HEP_CATCH_INT
+
+int hep_window_from_box(const float* box, int ox, int oy, int height, int width, int crop, int size, int32_t* ox_out, int32_t* oy_out) try {
+  const Check c{"hep_window_from_box: "};
+  CHECKED(c.ptrs({{box, "box"}, {ox_out, "ox_out"}, {oy_out, "oy_out"}}));
+  CHECKED(check_i420(height, width, crop, 1)); CHECKED(c.at_least("size", size, 1));
+  const int32_t w[3] = {0, ox, oy};
+  CHECKED(check_windows(c, w, 1, 1, height, width, crop));
+  // the centre of the box in frame pixels, then the window around it, kept inside the frame (compared in double: no cast of a value an int cannot hold)
+  auto around = [&](int o, float lo, float hi, int side) {
+    const double centre = (double)o + 0.5 * ((double)lo + (double)hi) * (double)crop / (double)size;
+    const double v = floor(centre - 0.5 * (double)crop + 0.5);
+    return !(v > 0.0) ? 0 : (v > (double)(side - crop) ? side - crop : (int)v);
+  };
+  *ox_out = around(ox, box[0], box[2], width); *oy_out = around(oy, box[1], box[3], height);
+  return 0;
+} HEP_CATCH_INT
+
+int hep_best_window_device(const uint32_t* records, int slots, const int32_t* windows, int n, int frames, uint32_t* out_records,
+                           int32_t* out_window, void* stream) try {
+  const Check c{"hep_best_window_device: "};
+  CHECKED(c.ptrs({{records, "records"}, {windows, "windows"}, {out_records, "out_records"}, {out_window, "out_window"}}));
+  CHECKED(c.range("slots", slots, 1, 63)); CHECKED(c.at_least("n", n, 1)); CHECKED(c.range("frames", frames, 1, INT_MAX / 64));
+  BestWindowArgs a; a.records = records; a.windows = windows; a.out_records = out_records; a.out_window = out_window; a.n = n; a.slots = slots; a.frames = frames;
+  launch_best_window(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
+// the handle's buffers for the winners of hep_pose(s)_from_i420_tiled: records and window indices of max_batch x num_classes rows, one size for both calls
+static int best_buffers(Session& s) {
+  const size_t need = (kRecBytes + 4) * s.max_batch * s.num_classes;
+  if (!s.d_best) HIPRET(hipMalloc((void**)&s.d_best, need));
+  if (!s.h_best) HIPRET(hipHostMalloc((void**)&s.h_best, need, hipHostMallocDefault));
+  return 0;
+}
+
+// The body of the windowed host calls; every argument has been checked and s.mu is held.  Staging: [camera rows of the windows, padded | table,
+// padded | frames] in the buffer hep_pose_from_i420 stages in, sized for max_batch frames of this geometry and only ever grown; then the
+// windowed preprocess, one forward at batch n and the top-detection launch.  window_out == NULL: the n (x num_classes) records come back as
+// they are.  Otherwise the best-of-windows launch follows and `frames` (x num_classes) winners with their window indices come back in one copy.
+static int pose_from_windows_locked(Session& s, bool per_label, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n,
+                                    int crop, int resized, const float* camera, float score_threshold, const PoseOut& o, int32_t* window_out) {
+  HIPRET(hipSetDevice(s.device));
+  const size_t in_floats = (size_t)3 * s.size * s.size;
+  if (!s.d_in) HIPRET(hipMalloc((void**)&s.d_in, in_floats * s.max_batch * 4));
+  if (per_label) if (int rc = poses_buffers(s)) return rc;
+  if (window_out) if (int rc = best_buffers(s)) return rc;
+  const size_t pad = pose_cam_pad(s), tpad = ((size_t)s.max_batch * 12 + 255) & ~(size_t)255, per_frame = (size_t)height * width * 3 / 2;
+  if (int rc = pose_reserve(s, pad + tpad + per_frame * (size_t)s.max_batch)) return rc;
+  if (!s.pose_upload_pinned) {
+    HIPRET(hipMemcpyAsync(s.d_pose_in, camera, (size_t)n * 24, hipMemcpyHostToDevice, s.stream));
+    HIPRET(hipMemcpyAsync(s.d_pose_in + pad, windows, (size_t)n * 12, hipMemcpyHostToDevice, s.stream));
+    HIPRET(hipMemcpyAsync(s.d_pose_in + pad + tpad, yuv, per_frame * frames, hipMemcpyHostToDevice, s.stream));
+  } else {
+    memcpy(s.h_pose_in, camera, (size_t)n * 24);
+    memcpy(s.h_pose_in + pad, windows, (size_t)n * 12);
+    memcpy(s.h_pose_in + pad + tpad, yuv, per_frame * frames);
+    HIPRET(hipMemcpyAsync(s.d_pose_in, s.h_pose_in, pad + tpad + per_frame * frames, hipMemcpyHostToDevice, s.stream));
+  }
+  const int32_t* d_table = (const int32_t*)(s.d_pose_in + pad);
+  if (int rc = preprocess_i420_locked(s, s.d_pose_in + pad + tpad, n, height, width, crop, resized, s.d_in, s.stream, d_table)) return rc;
+  const int64_t S = s.size; const int64_t nhwc[4] = {3 * S * S, 1, 3 * S, 3};      // the NCHW view of the [n,S,S,3] windows
+  std::string err;
+  if (int rc = run_forward(&s, s.d_in, nhwc, n, s.stream, &err)) return fail(rc, err);
+  if (!window_out) return pose_finish(s, n, score_threshold, o, per_label);
+  uint32_t* d = per_label ? s.d_recs : s.d_rec;
+  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, n, score_threshold, d, s.stream, per_label)) return rc;
+  const int slots = per_label ? s.num_classes : 1, rows = frames * slots;
+  BestWindowArgs a; a.records = d; a.windows = d_table; a.out_records = s.d_best; a.out_window = (int32_t*)(s.d_best + (size_t)rows * HEP_POSE_RECORD_WORDS);
+  a.n = n; a.slots = slots; a.frames = frames;
+  launch_best_window(a, s.stream);
+  HIPRET(hipGetLastError());
+  HIPRET(hipMemcpyAsync(s.h_best, s.d_best, (kRecBytes + 4) * rows, hipMemcpyDeviceToHost, s.stream));
+  HIPRET(hipStreamSynchronize(s.stream));
+  pose_scatter(s.h_best, rows, o);
+  memcpy(window_out, s.h_best + (size_t)rows * HEP_POSE_RECORD_WORDS, (size_t)rows * 4);
+  return 0;
+}
+// ResizeAndNormalizeMat's row count (preprocess_i420_locked computes the same): refused before any HIP call
+static int check_fits(const Session& s, int resized) {
+  const int nh = (int)((float)resized * ((float)s.size / (float)resized));
+  return nh < 1 || nh > s.size ? fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size") : 0;
+}
+
+static int pose_from_i420_windows(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int frames, int height, int width,
+                                  const int32_t* windows, int n, int crop, int resized, const float* camera, float score_threshold, const PoseOut& o) {
+  const Check c{who};
+  CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {windows, "windows"}, {camera, "camera"}, {o.found, "found"}}));
+  CHECKED(c.range("n", n, 1, INT_MAX, HEP_ERR_INVALID, "max_batch given to hep_create")); CHECKED(c.at_least("frames", frames, 1));
+  CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_windows(c, windows, n, frames, height, width, crop));
+  Session& s = h->s;      // (the handle is read from here on)
+  CHECKED(c.range("n", n, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create"));
+  CHECKED(c.range("frames", frames, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create")); CHECKED(check_fits(s, resized));
+  std::lock_guard<std::mutex> lk(s.mu);
+  return pose_from_windows_locked(s, per_label, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold, o, nullptr);
+}
+
+static int pose_from_i420_tiled(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop,
+                                int resized, int nx, int ny, const float* camera, float score_threshold, const PoseOut& o, int32_t* window) {
+  const Check c{who};
+  CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {camera, "camera"}, {o.found, "found"}, {window, "window"}}));
+  CHECKED(c.at_least("nx", nx, 1)); CHECKED(c.at_least("ny", ny, 1)); CHECKED(c.at_least("frames", frames, 1));
+  CHECKED(check_i420(height, width, crop, resized));
+  Session& s = h->s;      // (the handle is read from here on)
+  int64_t n = (int64_t)nx * ny;                     // (two factors at a time: neither product can pass int64)
+  if (n <= s.max_batch) n *= frames;
+  if (n > s.max_batch) return c.fail(HEP_ERR_INVALID, "frames * nx * ny outside 1..max_batch given to hep_create");
+  CHECKED(check_fits(s, resized));
+  std::lock_guard<std::mutex> lk(s.mu);
+  if (s.win_table.empty()) { s.win_table.resize((size_t)s.max_batch * 3); s.win_cam.resize((size_t)s.max_batch * 6); }
+  tile_windows(height, width, crop, nx, ny, frames, s.win_table.data());
+  for (int i = 0; i < (int)n; i++) window_camera(camera, s.win_table.data() + (size_t)i * 3, height, width, crop, resized, s.win_cam.data() + (size_t)i * 6);
+  return pose_from_windows_locked(s, per_label, yuv, frames, height, width, s.win_table.data(), (int)n, crop, resized, s.win_cam.data(), score_threshold, o, window);
+}
+
+int hep_pose_from_i420_windows(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                               int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                               int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
+  return pose_from_i420_windows("hep_pose_from_i420_windows: ", false, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
+                                PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+int hep_poses_from_i420_windows(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                                int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index,
+                                float* boxes, float* rotation, float* translation, float* hand) try {
+  return pose_from_i420_windows("hep_poses_from_i420_windows: ", true, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
+                                PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
+} HEP_CATCH_INT
+
+int hep_pose_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                             const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels, int32_t* index,
+                             float* boxes, float* rotation, float* translation, float* hand, int32_t* window) try {
+  return pose_from_i420_tiled("hep_pose_from_i420_tiled: ", false, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
+                              PoseOut{found, scores, labels, index, boxes, rotation, translation, hand}, window);
+} HEP_CATCH_INT
+
+int hep_poses_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                              const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
+                              float* rotation, float* translation, float* hand, int32_t* window) try {
+  return pose_from_i420_tiled("hep_poses_from_i420_tiled: ", true, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
+                              PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, window);
 } HEP_CATCH_INT
 
 // ---- introspection ----

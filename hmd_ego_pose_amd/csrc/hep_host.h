@@ -101,6 +101,10 @@ struct Session {
   uint32_t* d_rec = nullptr; uint32_t* h_rec = nullptr;
   // hep_poses_from_i420 / hep_poses_from_input: max_batch x num_classes records on both sides, allocated at the first of these calls
   uint32_t* d_recs = nullptr; uint32_t* h_recs = nullptr;
+  // hep_pose_from_i420_tiled / hep_poses_from_i420_tiled: the winners of the best-of-windows launch, [rows records | rows window indices] for up
+  // to max_batch x num_classes rows on both sides, allocated at the first of these calls
+  uint32_t* d_best = nullptr; uint32_t* h_best = nullptr;
+  std::vector<int32_t> win_table; std::vector<float> win_cam;      // their grid and its camera rows, built under the mutex: sized once, max_batch rows
   bool pose_upload_pinned = false;  // HEP_POSE_UPLOAD=pinned: the upload goes through h_pose_in (the measured alternative, hep_api.cpp pose_stage)
   unsigned* d_sync = nullptr;       // meeting counters of grouped launches (k_late.hip): an allocation of its own, zeroed once - never arena memory
   hipStream_t stream = nullptr;     // handle's own stream (host API, capture, profiling)

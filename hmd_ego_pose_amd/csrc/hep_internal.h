@@ -308,6 +308,11 @@ struct Yv12Args { const uint8_t* in; uint8_t* bgr; int B, H, W, crop, ow, oh; };
 struct ResizeArgs { const uint8_t* in; void* out; int B, H, W, nh, nw, S, norm; double inv_scale_x, inv_scale_y; };
 void launch_yv12_crop(const Yv12Args&, hipStream_t);
 void launch_resize_u8(const ResizeArgs&, hipStream_t);
+// the same conversion for n windows of a table in device memory, windows [n][3] int32 {frame, ox, oy}: window i is the crop x crop square of
+// frame `frame` whose top-left pixel is (ox, oy) - any parity; the chroma of a pixel is that of its place in the full frame.  The table is
+// trusted (the host entry points check theirs before the upload)
+struct Yv12WinArgs { const uint8_t* in; uint8_t* bgr; const int32_t* windows; int n, H, W, crop; };
+void launch_yv12_windows(const Yv12WinArgs&, hipStream_t);
 
 // ---- feature export: NHWC dtype -> NCHW fp32 ----
 struct ExportArgs { const void* in; float* out; int B, H, W, C, bf16; };
@@ -341,6 +346,11 @@ void launch_top1(const Top1Args&, hipStream_t);
 // the top detection of every label (k_post.hip toplabel_kernel): records [B][K][POSE_RECORD_WORDS], record (b, c) = the best candidate of
 // class c alone; class-specific by definition - any_class is not read
 void launch_toplabel(const Top1Args&, hipStream_t);
+// best of the windows of a frame (k_post.hip best_window_kernel): records [n][slots][POSE_RECORD_WORDS] of n windows {frame, ox, oy} ->
+// out_records [frames][slots] = the found record with the largest score among the windows of the frame (ties: the lowest window), copied
+// bit for bit, out_window [frames][slots] = that window or -1 with the not-found record of the two launches above
+struct BestWindowArgs { const uint32_t* records; const int32_t* windows; uint32_t* out_records; int32_t* out_window; int n, slots, frames; };
+void launch_best_window(const BestWindowArgs&, hipStream_t);
 
 // launch_X(args) finishes the arguments (reciprocals, grid) and launches X_pick(args): the pick reads only fields the planner sets, so it
 // can be asked for a launch's device function before any session exists (hep_kernel_symbol, plan_session's check of the plan)

@@ -582,3 +582,64 @@ void launch_amax_bf16(const void* x, int64_t n, unsigned* out, hipStream_t s) {
   const int blocks = (int)std::min<int64_t>(1024, (n + 255) / 256);
   hipLaunchKernelGGL(amax_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const uint16_t*>(x), n, out);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Whole-frame search (include/hep.h: hep_preprocess_i420_windows_device, hep_best_window_device).
+// yv12_windows_kernel: yv12_crop_kernel with the frame and the offsets of every output image read from a table {frame, ox, oy} - the
+// same per-pixel arithmetic, chroma at (sy / 2, sx / 2) of the full frame, so an odd offset needs nothing special.  One thread per pixel
+// of a window; the three table words of a workgroup's pixels are the same address for (almost) all of its lanes.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void yv12_windows_kernel(Yv12WinArgs a) {
+  const int64_t total = (int64_t)a.n * a.crop * a.crop;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int x = (int)(idx % a.crop), y = (int)((idx / a.crop) % a.crop), i = (int)(idx / ((int64_t)a.crop * a.crop));
+  const int32_t* w = a.windows + (int64_t)i * 3;
+  const int sx = w[1] + x, sy = w[2] + y, hw = a.H * a.W, q = (a.H / 2) * (a.W / 2);
+  const uint8_t* f = a.in + (int64_t)w[0] * (hw + 2 * q);
+  const int Y = f[(int64_t)sy * a.W + sx];
+  const int V = f[hw + (sy / 2) * (a.W / 2) + sx / 2], U = f[hw + q + (sy / 2) * (a.W / 2) + sx / 2];      // YV12: Y, V, U planes
+  const int yy = max(0, Y - 16) * 1220542, uu = U - 128, vv = V - 128, half = 1 << 19;
+  const int r = (yy + half + 1673527 * vv) >> 20, g = (yy + half - 852492 * vv - 409993 * uu) >> 20, bl = (yy + half + 2116026 * uu) >> 20;
+  uint8_t* o = a.bgr + idx * 3;
+  o[0] = (uint8_t)min(255, max(0, bl)); o[1] = (uint8_t)min(255, max(0, g)); o[2] = (uint8_t)min(255, max(0, r));
+}
+void launch_yv12_windows(const Yv12WinArgs& a, hipStream_t s) {
+  const int64_t total = (int64_t)a.n * a.crop * a.crop;
+  hipLaunchKernelGGL(yv12_windows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+}
+
+// best_window_kernel: one wave per (frame, slot).  Lane l looks at the windows l, l + 64, ... in rising order and keeps the first found
+// record of its frame, replaced only by a LARGER score (float32 comparison): its lowest window of the maximal score.  The 64 candidates
+// then meet by shuffles under the same order - larger score, then lower window - and the winner's 80 words are copied as they are.
+// (Scores are the network's sigmoid outputs: a NaN, which no comparison orders, does not occur in a record.)
+__global__ __launch_bounds__(64) void best_window_kernel(BestWindowArgs a) {
+  const int f = blockIdx.x / a.slots, c = blockIdx.x - f * a.slots, lane = threadIdx.x;
+  int best = -1;
+  float score = 0.f;
+  for (int i = lane; i < a.n; i += 64) {                     // (i < n guards the table and the records)
+    if (a.windows[(int64_t)i * 3] != f) continue;
+    const uint32_t* r = a.records + ((int64_t)i * a.slots + c) * POSE_RECORD_WORDS;
+    if (r[0] != 1u) continue;
+    const float sc = __uint_as_float(r[4]);
+    if (best < 0 || sc > score) { best = i; score = sc; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int ob = __shfl_xor(best, o, 64);
+    const float os = __shfl_xor(score, o, 64);
+    if (ob >= 0 && (best < 0 || os > score || (os == score && ob < best))) { best = ob; score = os; }
+  }
+  uint32_t* out = a.out_records + (int64_t)blockIdx.x * POSE_RECORD_WORDS;
+  const uint32_t* src = a.records + ((int64_t)(best < 0 ? 0 : best) * a.slots + c) * POSE_RECORD_WORDS;
+  for (int w = lane; w < POSE_RECORD_WORDS; w += 64) {
+    uint32_t v;
+    if (best >= 0) v = src[w];
+    else v = (w == 0 || w == 3 || w >= 78) ? 0u : (w < 3 ? 0xffffffffu : __float_as_uint(-1.f));   // the not-found record of top1_kernel
+    out[w] = v;
+  }
+  if (lane == 0) a.out_window[blockIdx.x] = best;
+}
+void launch_best_window(const BestWindowArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(best_window_kernel, dim3((unsigned)(a.frames * a.slots)), dim3(64), 0, s, a);
+}

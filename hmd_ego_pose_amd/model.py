@@ -232,7 +232,7 @@ class Session:
         return dict(found=rec[..., 0], index=rec[..., 2], score=f[..., 4], box=f[..., 5:9], rotation=f[..., 9:12],
                     translation=f[..., 12:15], hand=f[..., 15:78], record=rec)
 
-    def _pose_call(self, who, fn, lead, B, camera, score_threshold, per_label=False):
+    def _pose_call(self, who, fn, lead, B, camera, score_threshold, per_label=False, tail=()):
         import numpy as np
         cam = np.ascontiguousarray(camera, dtype=np.float32) if not isinstance(camera, torch.Tensor) else None
         if cam is None:
@@ -249,7 +249,7 @@ class Session:
                    rotation=e(np.float32, 3), translation=e(np.float32, 3), hand=e(np.float32, 63))
         if per_label:
             del out["label"]
-        _capi.check(fn(self.handle, *lead, cam.ctypes.data, float(score_threshold), *[out[k].ctypes.data for k in self._POSE_KEYS if k in out]))
+        _capi.check(fn(self.handle, *lead, cam.ctypes.data, float(score_threshold), *[out[k].ctypes.data for k in self._POSE_KEYS if k in out], *tail))
         return out
 
     @staticmethod
@@ -307,6 +307,99 @@ class Session:
         x = self._input_host("poses_from_input", x_host)
         return self._pose_call("poses_from_input", _capi.lib().hep_poses_from_input, (x.ctypes.data, x.shape[0]), x.shape[0], camera,
                                score_threshold, per_label=True)
+
+    # -- whole-frame search: windows of a frame, best of the windows ----------------------
+    def _windows_host(self, who, windows, frames, height, width, crop):
+        """a host table [n,3] int32 {frame, ox, oy}, every window inside its frame"""
+        import numpy as np
+        w = np.ascontiguousarray(windows.numpy() if isinstance(windows, torch.Tensor) else windows)
+        if w.dtype != np.int32 or w.ndim != 2 or w.shape[1] != 3 or not 1 <= w.shape[0] <= self.max_batch:
+            raise ValueError(f"{who}: windows must be int32 of shape (n, 3) with n in 1..{self.max_batch}, got {w.dtype} {w.shape}")
+        if ((w < 0).any() or (w[:, 0] >= frames).any() or (w[:, 1] > width - crop).any() or (w[:, 2] > height - crop).any()):
+            raise ValueError(f"{who}: a window lies outside the frame (frame index or offsets)")
+        return w
+
+    def preprocess_i420_windows(self, frames_u8: torch.Tensor, height: int, width: int, windows: torch.Tensor, crop: int = 256,
+                                resized: int = 512) -> torch.Tensor:
+        """``preprocess_i420`` for n windows of the frames (hep_preprocess_i420_windows_device): frames [F, height * width * 3 // 2] uint8
+        and ``windows`` [n,3] int32 {frame, ox, oy}, both on the device -> the NCHW view of [n, size, size, 3]; image i is the frame path's
+        arithmetic with the crop taken at (ox, oy) of frame ``frame``.  The table is trusted by the kernel: its shape and dtype are checked
+        here, its values are the caller's (``pose_from_i420_windows`` checks a host table)."""
+        if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 2 or frames_u8.shape[1] != height * width * 3 // 2:
+            raise ValueError("preprocess_i420_windows: expected a uint8 ROCm tensor [F, height * width * 3 // 2]")
+        if (not isinstance(windows, torch.Tensor) or windows.device != frames_u8.device or windows.dtype != torch.int32 or windows.dim() != 2
+                or windows.shape[1] != 3 or not 1 <= windows.shape[0] <= self.max_batch):
+            raise ValueError(f"preprocess_i420_windows: windows must be an int32 tensor (n, 3) on {frames_u8.device} with n in 1..{self.max_batch}")
+        x, w = frames_u8.contiguous(), windows.contiguous()
+        out = torch.empty((w.shape[0], self.size, self.size, 3), dtype=torch.float32, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _capi.check(_capi.lib().hep_preprocess_i420_windows_device(self.handle, x.data_ptr(), x.shape[0], height, width, w.data_ptr(), w.shape[0],
+                                                                   crop, resized, out.data_ptr(), stream))
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def best_window(records: torch.Tensor, windows: torch.Tensor, frames: int):
+        """Best of the windows of every frame in one launch (hep_best_window_device): ``records`` [n,80] (``top1``) or [n,K,80]
+        (``top_labels``) int32 and ``windows`` [n,3] int32 on the device -> (records [frames,80] or [frames,K,80], window [frames] or
+        [frames,K] int32): per frame and slot the found record with the largest score among the frame's windows, ties to the lowest window,
+        copied bit for bit; no such window: the not-found record and window -1."""
+        if (not isinstance(records, torch.Tensor) or not records.is_cuda or records.dtype != torch.int32 or records.dim() not in (2, 3)
+                or records.shape[-1] != _capi.POSE_RECORD_WORDS):
+            raise ValueError("best_window: records must be an int32 ROCm tensor [n,80] or [n,K,80]")
+        n, slots = records.shape[0], (records.shape[1] if records.dim() == 3 else 1)
+        if (not isinstance(windows, torch.Tensor) or windows.device != records.device or windows.dtype != torch.int32
+                or tuple(windows.shape) != (n, 3)):
+            raise ValueError(f"best_window: windows must be an int32 tensor ({n}, 3) on {records.device}")
+        if n < 1 or not 1 <= slots <= 63 or frames < 1:
+            raise ValueError("best_window: n and frames must be at least 1, slots in 1..63")
+        shape = (frames,) + tuple(records.shape[1:-1])
+        out = torch.empty(shape + (_capi.POSE_RECORD_WORDS,), dtype=torch.int32, device=records.device)
+        win = torch.empty(shape, dtype=torch.int32, device=records.device)
+        stream = torch.cuda.current_stream(records.device).cuda_stream
+        _capi.check(_capi.lib().hep_best_window_device(records.contiguous().data_ptr(), slots, windows.contiguous().data_ptr(), n, frames,
+                                                       out.data_ptr(), win.data_ptr(), stream))
+        return out, win
+
+    def pose_from_i420_windows(self, frames_u8_host, height: int, width: int, windows, camera, crop: int = 256, resized: int = 512,
+                               score_threshold=0.5, per_label=False):
+        """``pose_from_i420`` on n windows of the frames in one call (hep_pose_from_i420_windows; ``per_label``:
+        hep_poses_from_i420_windows): frames [F, height * width * 3 // 2] uint8, ``windows`` [n,3] int32 and ``camera`` [n,6] - one row PER
+        WINDOW, see ``window_cameras`` - in HOST memory -> the arrays of ``pose_from_i420`` (``poses_from_i420``) with one row per window."""
+        who = "pose_from_i420_windows"
+        x = self._i420_host(who, frames_u8_host, height, width, crop, resized)
+        if not 1 <= x.shape[0] <= self.max_batch:
+            raise ValueError(f"{who}: {x.shape[0]} frames are outside 1..{self.max_batch}")
+        w = self._windows_host(who, windows, x.shape[0], height, width, crop)
+        fn = _capi.lib().hep_poses_from_i420_windows if per_label else _capi.lib().hep_pose_from_i420_windows
+        return self._pose_call(who, fn, (x.ctypes.data, x.shape[0], height, width, w.ctypes.data, w.shape[0], crop, resized), w.shape[0], camera,
+                               score_threshold, per_label=per_label)
+
+    def _tiled(self, who, fn, per_label, frames_u8_host, height, width, camera, crop, resized, nx, ny, score_threshold):
+        import numpy as np
+        x = self._i420_host(who, frames_u8_host, height, width, crop, resized)
+        F = x.shape[0]
+        if nx < 1 or ny < 1 or not 1 <= F * nx * ny <= self.max_batch:
+            raise ValueError(f"{who}: frames * nx * ny = {F * nx * ny} is outside 1..{self.max_batch}")
+        window = np.empty((F, self.num_classes) if per_label else (F,), np.int32)
+        out = self._pose_call(who, fn, (x.ctypes.data, F, height, width, crop, resized, nx, ny), F, camera, score_threshold, per_label=per_label,
+                              tail=(window.ctypes.data,))
+        out["window"] = window
+        return out
+
+    def pose_from_i420_tiled(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, nx: int = 1, ny: int = 1,
+                             score_threshold=0.5):
+        """The whole frame in one call (hep_pose_from_i420_tiled): the ``nx`` x ``ny`` grid of ``tile_windows`` over every frame, the cameras
+        of ``window_cameras`` from ``camera`` [F,6] (the rows ``pose_from_i420`` takes), one forward at batch F * nx * ny, best window per
+        frame.  The arrays of ``pose_from_i420`` with one row per frame and ``window`` [F] int32: the winner's index in the grid's table or
+        -1.  Boxes are in the winning window's network-input pixels; a 1 x 1 grid is ``pose_from_i420`` bit for bit."""
+        return self._tiled("pose_from_i420_tiled", _capi.lib().hep_pose_from_i420_tiled, False, frames_u8_host, height, width, camera, crop, resized,
+                           nx, ny, score_threshold)
+
+    def poses_from_i420_tiled(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, nx: int = 1, ny: int = 1,
+                              score_threshold=0.5):
+        """``pose_from_i420_tiled`` for several objects (hep_poses_from_i420_tiled): arrays [F,K,...] as ``poses_from_i420``, ``window`` [F,K]."""
+        return self._tiled("poses_from_i420_tiled", _capi.lib().hep_poses_from_i420_tiled, True, frames_u8_host, height, width, camera, crop, resized,
+                           nx, ny, score_threshold)
 
     # -- introspection ------------------------------------------------------------------
     def stage(self, name: str, batch: int) -> torch.Tensor:
@@ -601,3 +694,44 @@ class TrainModelWithLoss(nn.Module):
         d = self.detect(imgs, camera_params)
         last = imgs.shape[0] - 1
         return [d[k][last].cpu() for k in ("boxes", "scores", "labels", "rotation", "translation", "hand")]
+
+
+# --------------------------------------------------------------------------------------
+# whole-frame search: the host arithmetic of include/hep.h (no handle, no HIP call)
+# --------------------------------------------------------------------------------------
+def tile_windows(height: int, width: int, crop: int, nx: int, ny: int, frames: int = 1):
+    """hep_tile_windows: the ``frames`` x ``ny`` x ``nx`` windows {frame, ox, oy} of a regular grid -> numpy int32 [frames * ny * nx, 3],
+    frame-major, then row, then column; the outer cells touch the frame's borders, a 1 x 1 grid is the centre crop."""
+    import numpy as np
+    if min(nx, ny, frames) < 1:
+        raise ValueError("tile_windows: nx, ny and frames must be at least 1")
+    out = np.empty((frames * ny * nx, 3), np.int32)
+    _capi.check(_capi.lib().hep_tile_windows(height, width, crop, nx, ny, frames, out.ctypes.data))
+    return out
+
+
+def window_cameras(camera, windows, height: int, width: int, crop: int, resized: int):
+    """hep_window_cameras: ``camera`` [F,6] (the rows of the CENTRE window of every frame) and ``windows`` [n,3] int32 -> numpy float32
+    [n,6]: the row of each window's frame with the principal point moved by the window's offset from the centre crop."""
+    import numpy as np
+    cam = np.ascontiguousarray(camera, dtype=np.float32)
+    w = np.ascontiguousarray(windows)
+    if w.dtype != np.int32 or w.ndim != 2 or w.shape[1] != 3 or w.shape[0] < 1:
+        raise ValueError(f"window_cameras: windows must be int32 of shape (n, 3), got {w.dtype} {w.shape}")
+    if cam.ndim != 2 or cam.shape[1] != 6 or (w[:, 0] < 0).any() or (w[:, 0] >= cam.shape[0]).any():
+        raise ValueError(f"window_cameras: camera must have shape (F, 6) with a row for every frame the windows name, got {cam.shape}")
+    out = np.empty((w.shape[0], 6), np.float32)
+    _capi.check(_capi.lib().hep_window_cameras(cam.ctypes.data, w.ctypes.data, w.shape[0], height, width, crop, resized, out.ctypes.data))
+    return out
+
+
+def window_from_box(box, ox: int, oy: int, height: int, width: int, crop: int, size: int):
+    """hep_window_from_box: the window centred on a detection -> (ox, oy).  ``box`` = xmin, ymin, xmax, ymax in network-input pixels
+    (``size``) of the window (ox, oy) it was found in."""
+    import numpy as np
+    b = np.ascontiguousarray(box, dtype=np.float32)
+    if b.shape != (4,):
+        raise ValueError(f"window_from_box: box must have 4 entries, got {b.shape}")
+    x, y = ctypes.c_int32(), ctypes.c_int32()
+    _capi.check(_capi.lib().hep_window_from_box(b.ctypes.data, ox, oy, height, width, crop, size, ctypes.byref(x), ctypes.byref(y)))
+    return x.value, y.value

@@ -28,7 +28,9 @@
  *   hep_top_labels_device, hep_poses_from_i420, hep_poses_from_input <- the same three for a model of several objects
  *                                 (num_classes > 1, backbone.py:14): the top detection of EVERY label, class-specific as the
  *                                 reference constructs its filter (train.py:78-81)
- *   hep_anchor_targets_device  <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
+ *   hep_pose_from_i420_tiled, hep_pose_from_i420_windows (and hep_poses_*) <- no twin: the callback's centre crop taken at several places of
+ *                                 the frame in one call, best window reported (WHOLE-FRAME SEARCH below)
+ *   hep_anchor_targets_device <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
  *   hep_heads_forward_device / hep_heads_backward_device <- the five head nets under those losses, trainable
@@ -257,6 +259,72 @@ int hep_poses_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height
 int hep_poses_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
                          int32_t* found, float* scores, int32_t* index, float* boxes, float* rotation, float* translation,
                          float* hand);
+
+/* WHOLE-FRAME SEARCH.  The frame path above shows the network the crop x crop square at the frame's centre, as the streaming app does;
+ * an object held elsewhere in the field of view is not found.  These calls cover the frame with several such squares in ONE upload, one
+ * forward at batch n and one download, and report the best of them.
+ * A WINDOW is three int32 {frame, ox, oy}: the crop x crop square of frame `frame` whose top-left pixel is (ox, oy), 0 <= ox <= width - crop,
+ * 0 <= oy <= height - crop, any parity.  Its pixels are converted exactly as the frame path converts the centre square (the chroma of a pixel
+ * is that of its place in the full frame), then resized and normalised by the same two launches.
+ * LIMITS: rotation is the network's output as the filter returns it, exactly as for the centre crop.  A window's camera differs from the
+ * caller's by the principal point only (hep_window_cameras); no correction for the viewing ray of an off-axis window is applied or claimed.
+ *
+ * The three functions below are host arithmetic: no handle, no HIP call.
+ *
+ * hep_tile_windows: the frames x ny x nx windows of a regular grid into windows_out [frames * ny * nx][3], frame-major, then row, then column.
+ * Column i has ox = nx == 1 ? (width - crop) / 2 : (i * (width - crop)) / (nx - 1) in integer division, row r the same with height and ny: the
+ * first and the last cell touch the frame's borders, and a 1 x 1 grid is the frame path's centre crop.  nx, ny or frames < 1, an odd height or
+ * width, a crop larger than the frame, NULL: HEP_ERR_INVALID. */
+int hep_tile_windows(int height, int width, int crop, int nx, int ny, int frames, int32_t* windows_out);
+/* hep_window_cameras: camera [frames,6] holds the rows the caller passes for the CENTRE window of every frame (fx, fy, px, py, tz_scale,
+ * image_scale); camera_out [n,6] gets, for window i, the row of its frame with
+ *   px' = (float)((double)px - (double)(ox - (width - crop) / 2) * (double)resized / (double)crop)          py' likewise from oy and height,
+ * the other four entries copied bit for bit.  hep_decode computes Tx = (cx / image_scale - px) * Tz / fx with cx / image_scale in pixels of the
+ * resized image, so this shift is the exact pinhole statement of moving the window; the centre window's row is unchanged bit for bit.
+ * camera must hold a row for every frame the table names.  NULL, n < 1, the frame geometry above, a window outside the frame: HEP_ERR_INVALID. */
+int hep_window_cameras(const float* camera, const int32_t* windows, int n, int height, int width, int crop, int resized, float* camera_out);
+/* hep_window_from_box: the window centred on a detection, for a loop that follows what it found.  box [4] = xmin, ymin, xmax, ymax in
+ * network-input pixels (`size` = the session's size) of the window (ox, oy) it was found in, as the records carry it.  In double:
+ *   cx = ox + 0.5 * (xmin + xmax) * crop / size;   *ox_out = clamp((int)floor(cx - 0.5 * crop + 0.5), 0, width - crop);   *oy_out likewise.
+ * NULL, size < 1, the frame geometry above, (ox, oy) outside the frame: HEP_ERR_INVALID. */
+int hep_window_from_box(const float* box, int ox, int oy, int height, int width, int crop, int size, int32_t* ox_out, int32_t* oy_out);
+
+/* Best of the windows of every frame, one launch, no handle.  records: device memory, [n][slots][HEP_POSE_RECORD_WORDS] as hep_top1_device
+ * (slots = 1) or hep_top_labels_device (slots = num_classes) writes them for a batch of n windows; windows [n][3] on the device.  For every
+ * frame f < frames and slot c: among the windows i with windows[i].frame == f whose record (i, c) has found == 1, the one with the largest
+ * score (float32 comparison) wins, ties to the lowest i; out_records [frames][slots] gets its record bit for bit and out_window [frames][slots]
+ * gets i.  Without such a window - none found, or a frame no window names - the record is the not-found record of the two launches (found 0,
+ * words 3, 78, 79 zero, the padding -1 / -1.0f elsewhere) and out_window is -1.  Windows of one frame need not be adjacent in the table.
+ * Asynchronous on `stream`, no allocation, no host synchronisation.  NULL, slots outside 1..63, n < 1, frames < 1: HEP_ERR_INVALID. */
+int hep_best_window_device(const uint32_t* records, int slots, const int32_t* windows, int n, int frames, uint32_t* out_records,
+                           int32_t* out_window, void* stream);
+
+/* hep_pose_from_i420 on n windows of `frames` frames in host memory: ONE upload (camera rows, table, frames), hep_preprocess_i420_windows_device's
+ * launches, one forward at batch n, the top-detection launch, one download.  yuv [frames][height * width * 3 / 2]; windows [n][3] and
+ * camera [n,6] on the host: one camera row PER WINDOW (hep_window_cameras makes them from per-frame rows).  Outputs as hep_pose_from_i420 with
+ * one row per window; boxes are in network-input pixels of their window.  hep_poses_from_i420_windows: the per-label launch, outputs
+ * [n][num_classes] as hep_poses_from_i420.  Mutex, pinned download and "allocated at first use, only ever grown" as for hep_pose_from_i420
+ * (the staging buffer is shared with it).  Checked before any HIP call, HEP_ERR_INVALID with the reason in hep_last_error: NULL handle / yuv /
+ * windows / camera / found, n or frames outside 1..max_batch, the frame geometry, a window whose frame index or offsets lie outside the frame. */
+int hep_pose_from_i420_windows(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                               int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                               int32_t* index, float* boxes, float* rotation, float* translation, float* hand);
+int hep_poses_from_i420_windows(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                                int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index,
+                                float* boxes, float* rotation, float* translation, float* hand);
+/* The whole frame in one call: the grid of hep_tile_windows (frames * nx * ny <= max_batch windows) with the cameras of hep_window_cameras from
+ * camera [frames,6] (the rows of the centre window, what hep_pose_from_i420 takes), the device work above, then hep_best_window_device and a
+ * download of `frames` records.  Outputs as hep_pose_from_i420, one row per FRAME, plus window [frames]: the index of the winning window in
+ * hep_tile_windows' order within the whole table (frame f's cell = window[f] - f * nx * ny; column = cell % nx, row = cell / nx), or -1.  Boxes
+ * stay in the winning window's network-input pixels; translation is in the camera frame through the shifted principal point.  A 1 x 1 grid is
+ * hep_pose_from_i420 bit for bit.  hep_poses_from_i420_tiled: per label, outputs and window are [frames][num_classes].  Checks as above, and
+ * nx or ny < 1, a NULL window, frames * nx * ny > max_batch: HEP_ERR_INVALID. */
+int hep_pose_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                             const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels, int32_t* index,
+                             float* boxes, float* rotation, float* translation, float* hand, int32_t* window);
+int hep_poses_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                              const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
+                              float* rotation, float* translation, float* hand, int32_t* window);
 
 /* ADD and ADD-S of num_pairs (ground truth, prediction) poses over one object model: points [num_points,3]; rotations
  * as axis-angle vectors in radians (what _get_detections hands on: network output * pi), translations in the model's
@@ -815,6 +883,14 @@ int hep_preprocess_u8_device(hep_handle* h, const uint8_t* rgb_hwc, int batch, i
  * when `stream` is capturing. */
 int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
                                float* out_hwc, void* stream);
+/* The same for n windows of a table (WHOLE-FRAME SEARCH above): yuv [frames][height * width * 3 / 2] and windows [n][3] int32
+ * {frame, ox, oy} on the device, out_hwc float32 [n, size, size, 3].  Image i is bit for bit the frame path's arithmetic with the crop
+ * taken at (ox, oy) of frame `frame`.  The table lives in device memory and is TRUSTED, as every device table of this ABI is (a window
+ * outside its frame reads outside the frames; the host calls check their table before the upload).  n <= max_batch: the handle's
+ * scratch frames, their event across streams and the refusal under stream capture are those of hep_preprocess_i420_device.
+ * NULL, frames < 1, the frame geometry, n outside 1..max_batch: HEP_ERR_INVALID before any HIP call. */
+int hep_preprocess_i420_windows_device(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n,
+                                       int crop, int resized, float* out_hwc, void* stream);
 
 /* Introspection used by tests, bench.py and DESIGN.md tables. */
 int hep_debug_tensor_count(const hep_handle* h);

@@ -27,6 +27,15 @@ path's spread.  With K = 1 a third child, "top1" (hep_pose_from_input / hep_pose
 same scores should be level.  No upload A/B in this mode.
 
     python tools/pose_call_time.py --labels 3 [--calls 300] [--warmup 20] [--json FILE]
+
+--tiles NXxNY: the whole-frame search on one 896 x 504 frame with crop 256, resized 512, phi 0 @ 512 and @ 256, fp32, seeded weights:
+  tiled    = one hep_pose_from_i420_tiled call (one upload, one forward at batch NX * NY, best-of-windows on the device, one download)
+  composed = what a caller could do without it: the same windows cut on the host into 256 x 256 I420 frames, one hep_pose_from_i420 each with
+             the window's camera row, the maximum taken on the host
+composed and tiled alternate, twice each per size, in child processes under the same limits.  No ratio is fixed in advance: the tool prints both
+medians, both run-to-run spreads, and whether the one call is faster than the composed path by more than the composed path's own spread.
+
+    python tools/pose_call_time.py --tiles 4x2 [--calls 300] [--warmup 20] [--json FILE]
 """
 import argparse
 import ctypes
@@ -138,34 +147,130 @@ def child(args):
             _capi.check(lib.hep_pose_from_i420(s.handle, frame.ctypes.data, 1, FH, FW, 256, 512, cam.ctypes.data, thr, *top_ptrs))
             row0["b"] = [(int(top["index"][0]), float(top["score"][0]))] if args.labels else (int(top["index"][0]), float(top["score"][0]))
 
-    def stats(ts):
-        ts = sorted(ts)
-        return {"p50_ms": round(ts[len(ts) // 2], 4), "p99_ms": round(ts[min(len(ts) - 1, int(len(ts) * 0.99))], 4), "min_ms": round(ts[0], 4)}
-
-    def back_to_back(fn):
-        for _ in range(args.warmup):
-            fn()
-        torch.cuda.synchronize(dev)
-        ts = []
-        for _ in range(args.calls):
-            t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
-        return stats(ts)
-
-    def paced(fn, hz):
-        ts, period = [], 1.0 / hz
-        nxt = time.perf_counter() + period
-        for _ in range(args.calls):
-            while time.perf_counter() < nxt:
-                time.sleep(max(0.0, min(0.002, nxt - time.perf_counter())))
-            nxt += period
-            t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
-        return stats(ts)
-
     out = {"path": args.child, "upload": os.environ.get("HEP_POSE_UPLOAD", "default"), "candidates": n_pass,
-           "a": back_to_back(call_a), "a_60hz": paced(call_a, 60.0), "b": back_to_back(call_b), "b_60hz": paced(call_b, 60.0),
+           "a": back_to_back(call_a, args), "a_60hz": paced(call_a, 60.0, args), "b": back_to_back(call_b, args), "b_60hz": paced(call_b, 60.0, args),
            "row0": row0, "forward_launches": lib.hep_kernel_count(s.handle, 1)}
     s.close()
     print("RESULT " + json.dumps(out), flush=True)
+
+
+def stats(ts):
+    ts = sorted(ts)
+    return {"p50_ms": round(ts[len(ts) // 2], 4), "p99_ms": round(ts[min(len(ts) - 1, int(len(ts) * 0.99))], 4), "min_ms": round(ts[0], 4)}
+
+
+def back_to_back(fn, args):
+    import torch
+    for _ in range(args.warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(args.calls):
+        t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+    return stats(ts)
+
+
+def paced(fn, hz, args):
+    ts, period = [], 1.0 / hz
+    nxt = time.perf_counter() + period
+    for _ in range(args.calls):
+        while time.perf_counter() < nxt:
+            time.sleep(max(0.0, min(0.002, nxt - time.perf_counter())))
+        nxt += period
+        t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
+    return stats(ts)
+
+
+def child_tiles(args):
+    """--tiles: one frame searched whole.  "tiled" = one hep_pose_from_i420_tiled call; "composed" = what a caller could do before it: every
+    window of the same grid cut out of the frame on the host into a crop x crop I420 frame (chroma planes at half offsets - an odd offset loses
+    its last chroma column: the composed path cannot express it), one hep_pose_from_i420 each with the window's camera, the maximum on the host."""
+    import numpy as np
+    import torch
+
+    import hmd_ego_pose_amd as H
+    from hmd_ego_pose_amd import _capi
+    from hmd_ego_pose_amd.model import Session
+    from hmd_ego_pose_amd.weights import seeded_state_dict
+    assert torch.cuda.is_available(), "needs the MI355X"
+    lib = _capi.lib()
+    nx, ny = args.tiles
+    S, T, thr = args.size, nx * ny, 0.0               # threshold 0: every window reports its best anchor, so the two paths' answers can be compared
+    FH, FW, crop, rs = 504, 896, 256, 512
+    s = Session(seeded_state_dict(0, 0), 0, S, T, "fp32", torch.device("cuda", 0))
+    rng = np.random.Generator(np.random.PCG64(5))
+    frame = rng.integers(0, 256, (1, FH * FW * 3 // 2), dtype=np.uint8)
+    cam = np.array([[480, 480, S / 2, S / 2, 1000, S / rs]], np.float32)
+    grid = H.tile_windows(FH, FW, crop, nx, ny, 1)
+    wcam = H.window_cameras(cam, grid, FH, FW, crop, rs)
+    top = {"found": np.empty(1, np.int32), "score": np.empty(1, np.float32), "label": np.empty(1, np.int32), "index": np.empty(1, np.int32),
+           "box": np.empty((1, 4), np.float32), "rotation": np.empty((1, 3), np.float32), "translation": np.empty((1, 3), np.float32),
+           "hand": np.empty((1, 63), np.float32)}
+    top_ptrs = [top[k].ctypes.data for k in Session._POSE_KEYS]
+    window = np.empty(1, np.int32)
+    answer = {}
+    if args.child == "tiled":
+        def call():
+            _capi.check(lib.hep_pose_from_i420_tiled(s.handle, frame.ctypes.data, 1, FH, FW, crop, rs, nx, ny, cam.ctypes.data, thr, *top_ptrs, window.ctypes.data))
+            answer["row"] = (int(window[0]), int(top["index"][0]), float(top["score"][0]))
+    else:
+        hw, q = FH * FW, (FH // 2) * (FW // 2)
+        yp, p1, p2 = frame[0, :hw].reshape(FH, FW), frame[0, hw:hw + q].reshape(FH // 2, FW // 2), frame[0, hw + q:].reshape(FH // 2, FW // 2)
+        sub = np.empty((1, crop * crop * 3 // 2), np.uint8)
+        c2 = crop // 2
+
+        def call():
+            best = (-1, -1, -1.0)
+            for i, (_f, ox, oy) in enumerate(grid):
+                sub[0, :crop * crop].reshape(crop, crop)[:] = yp[oy:oy + crop, ox:ox + crop]
+                sub[0, crop * crop:crop * crop + c2 * c2].reshape(c2, c2)[:] = p1[oy // 2:oy // 2 + c2, ox // 2:ox // 2 + c2]
+                sub[0, crop * crop + c2 * c2:].reshape(c2, c2)[:] = p2[oy // 2:oy // 2 + c2, ox // 2:ox // 2 + c2]
+                _capi.check(lib.hep_pose_from_i420(s.handle, sub.ctypes.data, 1, crop, crop, crop, rs, wcam[i:i + 1].ctypes.data, thr, *top_ptrs))
+                if top["found"][0] == 1 and float(top["score"][0]) > best[2]:
+                    best = (i, int(top["index"][0]), float(top["score"][0]))
+            answer["row"] = best
+    out = {"path": args.child, "size": S, "tiles": [nx, ny], "call": back_to_back(call, args), "call_60hz": paced(call, 60.0, args), "row": answer["row"],
+           "even_offsets": bool((grid[:, 1:] % 2 == 0).all()), "forward_launches": lib.hep_kernel_count(s.handle, T)}
+    s.close()
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def main_tiles(args):
+    """composed and tiled alternate, twice each, at phi 0 @ 512 and @ 256; medians and run-to-run spread of both, and whether the one call is
+    faster than the composed path by more than the composed path's own spread"""
+    runs, verdict = [], {}
+    for size in (512, 256):
+        for path in ("composed", "tiled") * 2:
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--calls", str(args.calls), "--warmup", str(args.warmup),
+                   "--tiles", f"{args.tiles[0]}x{args.tiles[1]}", "--size", str(size)]
+            r = subprocess.run(cmd, timeout=args.timeout, capture_output=True, text=True)
+            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+            if r.returncode != 0 or not line:
+                print(r.stdout[-2000:], r.stderr[-4000:], sep="\n")
+                sys.exit(f"the {path} child failed (exit status {r.returncode}): nothing further is started")
+            runs.append(json.loads(line[0][7:]))
+            d = runs[-1]
+            print(f"{path:<8} size {size}  " + "  ".join(f"{k}: p50 {d[k]['p50_ms']:.4f} p99 {d[k]['p99_ms']:.4f}" for k in ("call", "call_60hz")) +
+                  f"  (window, anchor, score) = {d['row']}", flush=True)
+        mine = [r for r in runs if r["size"] == size]
+        rows = {tuple(r["row"][:2]) for r in mine}
+        if mine[0]["even_offsets"]:                      # the composed path is exact only then
+            assert len(rows) == 1, [r["row"] for r in mine]
+        elif len(rows) != 1:
+            print(f"size {size}: the grid has odd offsets, which the host cut rounds down in the chroma planes - the two paths' answers differ: {sorted(rows)}")
+        for k in ("call", "call_60hz"):
+            c, t = ([r[k]["p50_ms"] for r in mine if r["path"] == p] for p in ("composed", "tiled"))
+            cs, ts = abs(c[0] - c[1]), abs(t[0] - t[1])
+            faster = max(t) < min(c) - cs
+            verdict[f"{size} {k}"] = {"composed_p50": c, "tiled_p50": t, "composed_spread": round(cs, 4), "tiled_spread": round(ts, 4), "tiled_faster_beyond_spread": bool(faster)}
+            print(f"size {size} {k:<9} composed p50 {c} (spread {cs:.4f})  tiled p50 {t} (spread {ts:.4f})  -> the one call is "
+                  f"{'faster than' if faster else 'NOT faster than'} the composed path by more than the composed path's spread ({min(c) / max(t):.2f} x)")
+    T = args.tiles[0] * args.tiles[1]
+    print(f"composed: per frame {T} host cuts, {T} x (H2D 2, preprocess 3 launches, forward at batch 1, top-1 1, D2H 1, synchronise)")
+    print(f"tiled:    per frame H2D 3 (cameras, table, frame), preprocess 3 launches at batch {T}, forward at batch {T}, top-1 1, best-of-windows 1, D2H 1, one synchronise")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"runs": runs, "verdict": verdict}, f, indent=1)
 
 
 # per call, beside the forward's own launches (hep_kernel_count; one eager stem launch + one graph replay)
@@ -184,10 +289,19 @@ def main():
     ap.add_argument("--json", default=None, help="also write every child's result to this file")
     ap.add_argument("--timeout", type=int, default=180, help="time limit of one measuring child process, seconds")
     ap.add_argument("--labels", type=int, default=0, help="K: time hep_poses_from_* with seeded K-class weights (see above)")
-    ap.add_argument("--child", default=None, choices=["old", "new", "top1"], help=argparse.SUPPRESS)
+    ap.add_argument("--tiles", default=None, help="NXxNY: time hep_pose_from_i420_tiled against the composed whole-frame search (see above)")
+    ap.add_argument("--size", type=int, default=512, help=argparse.SUPPRESS)
+    ap.add_argument("--child", default=None, choices=["old", "new", "top1", "composed", "tiled"], help=argparse.SUPPRESS)
     args = ap.parse_args()
     if not 0 <= args.labels <= 63:
         sys.exit("--labels must be in 1..63")
+    if args.tiles:
+        try:
+            args.tiles = tuple(int(v) for v in args.tiles.lower().split("x"))
+            assert len(args.tiles) == 2 and min(args.tiles) >= 1
+        except (ValueError, AssertionError):
+            sys.exit("--tiles takes NXxNY, e.g. 4x2")
+        return child_tiles(args) if args.child else main_tiles(args)
     if args.child:
         return child(args)
     runs = []
