@@ -9,7 +9,8 @@ from .weights import load_pack, pack_bytes, save_pack, seeded_state_dict, strip_
 
 
 def __getattr__(name):   # torch custom-op registration happens on first use of the model API
-    if name in ("HMDEgoPose", "TrainModelWithLoss", "Session", "tile_windows", "window_cameras", "window_from_box"):
+    if name in ("HMDEgoPose", "TrainModelWithLoss", "Session", "tile_windows", "window_cameras", "window_from_box",
+                "rectify_windows", "rectified_point_to_frame", "window_from_box_rectified"):
         from . import model
         return getattr(model, name)
     if name == "TrainableHeads":

@@ -19,6 +19,7 @@ HEP_F32, HEP_BF16, HEP_FP8 = 0, 1, 2
 FLAG_KEEP_INTERMEDIATES, FLAG_NO_GRAPH = 1, 2
 OUT_K = (4, 1, 3, 3, 63)
 POSE_RECORD_WORDS = 80                     # HEP_POSE_RECORD_WORDS
+RECTIFY_ROW_DOUBLES = 13                   # HEP_RECTIFY_ROW_DOUBLES
 SCORE_GT_DOUBLES, SCORE_RECORD_DOUBLES = 88, 16      # HEP_SCORE_GT_DOUBLES, HEP_SCORE_RECORD_DOUBLES
 SCORE_MAX_ANNOTATIONS, SCORE_MAX_LABELS = 16, 63     # HEP_SCORE_MAX_ANNOTATIONS; hep_score_scene_device's num_labels
 DRAW_BOX2D, DRAW_CUBOID, DRAW_HAND, DRAW_MAX_DETECTIONS = 1, 2, 4, 64      # HEP_DRAW_* of include/hep.h
@@ -67,6 +68,15 @@ SYMBOLS = {
     "hep_poses_from_i420_windows": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7),
     "hep_pose_from_i420_tiled": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8 + [c_void_p]),
     "hep_poses_from_i420_tiled": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7 + [c_void_p]),
+    "hep_rectify_windows": (c_int, [_FP, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "hep_rectified_point_to_frame": (c_int, [c_void_p, c_double, c_double, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "hep_window_from_box_rectified": (c_int, [c_void_p, _FP, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32)]),
+    "hep_preprocess_i420_rectified_device": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, _FP, c_void_p]),
+    "hep_derotate_records_device": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "hep_pose_from_i420_windows_rectified": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8),
+    "hep_poses_from_i420_windows_rectified": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7),
+    "hep_pose_from_i420_tiled_rectified": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 8 + [c_void_p]),
+    "hep_poses_from_i420_tiled_rectified": (c_int, [_P, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _FP, c_float] + [_FP] * 7 + [c_void_p]),
     "hep_pose_errors": (c_int, [c_int, _FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP]),
     "hep_pose_errors_device": (c_int, [_FP, c_int, _FP, _FP, _FP, _FP, c_int, c_int, _FP, _FP, c_void_p]),
     "hep_score_detections_device": (c_int, [_FP] * 6 + [c_int, c_int, _FP, _FP, c_int, c_int, c_int, c_float, c_int, c_double, _FP, _FP, _FP, c_void_p]),

@@ -2,6 +2,7 @@
 // eager stem launch (it reads the caller's input pointer) + one captured hipGraph for
 // everything behind it, replayed on the caller's stream.  The entry points that take no handle are in files of their
 // own: the evaluation and visualisation toolkit in hep_api_eval.cpp, the training side in hep_api_train.cpp.
+#include <float.h>
 #include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -424,8 +425,9 @@ static int check_i420(int height, int width, int crop, int resized) {
 // the launches of the frame path on `st`; s.mu is held (the two scratch buffers belong to the handle)
 // windows (hep_preprocess_i420_windows_device): a device table [batch][3] {frame, ox, oy} - output image i is that window of the frames at `yuv`
 // in place of the centre crop of frame i; everything behind the first launch is the same
+// rect (hep_preprocess_i420_rectified_device): a device table [batch][HEP_RECTIFY_ROW_DOUBLES] next to `windows` - image i is the rectified window
 static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                                  float* out_hwc, hipStream_t st, const int32_t* windows = nullptr) {
+                                  float* out_hwc, hipStream_t st, const int32_t* windows = nullptr, const double* rect = nullptr) {
   // The scratch frames are used ASYNCHRONOUSLY on the caller's stream and the mutex only covers the enqueue: a second call on
   // another stream (an in-flight pool) must not overwrite them while the first call's kernels still read them.  An event is
   // recorded behind the last launch of every call and the next call's stream waits for it first (device-side, no host stall).
@@ -446,13 +448,16 @@ static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int
   {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(HEP_ERR_UNSUPPORTED, std::string(windows ? "hep_preprocess_i420_windows_device" : "hep_preprocess_i420_device") + " must not be called under stream capture");
+      return fail(HEP_ERR_UNSUPPORTED, std::string(rect ? "hep_preprocess_i420_rectified_device" : windows ? "hep_preprocess_i420_windows_device" : "hep_preprocess_i420_device") + " must not be called under stream capture");
   }
   if (s.pre_pending) HIPRET(hipStreamWaitEvent(st, s.pre_event, 0));
   // from the first launch on, EVERY return path leaves the event behind the scratch frames' last user
   struct Guard { Session& s; hipStream_t st; ~Guard() { if (hipEventRecord(s.pre_event, st) == hipSuccess) s.pre_pending = true; } } guard{s, st};
   // Program.cs:161 cvtColor + 383-397 CenterCropAndRescaleMat
-  if (windows) {
+  if (rect) {
+    Yv12RectArgs ra; ra.in = yuv; ra.bgr = s.d_pre[0]; ra.windows = windows; ra.table = rect; ra.n = batch; ra.H = height; ra.W = width; ra.crop = crop; ra.resized = resized;
+    launch_yv12_rectified_windows(ra, st);
+  } else if (windows) {
     Yv12WinArgs wa; wa.in = yuv; wa.bgr = s.d_pre[0]; wa.windows = windows; wa.n = batch; wa.H = height; wa.W = width; wa.crop = crop;
     launch_yv12_windows(wa, st);
   } else {
@@ -494,6 +499,18 @@ int hep_preprocess_i420_windows_device(hep_handle* h, const uint8_t* yuv, int fr
   HIPRET(hipSetDevice(s.device));
   std::lock_guard<std::mutex> lk(s.mu);
   return preprocess_i420_locked(s, yuv, n, height, width, crop, resized, out_hwc, (hipStream_t)stream, windows);
+} HEP_CATCH_INT
+
+int hep_preprocess_i420_rectified_device(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows,
+                                         const double* table, int n, int crop, int resized, float* out_hwc, void* stream) try {
+  const Check c{"hep_preprocess_i420_rectified_device: "};
+  CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {windows, "windows"}, {table, "table"}, {out_hwc, "out_hwc"}}));
+  CHECKED(c.at_least("frames", frames, 1)); CHECKED(check_i420(height, width, crop, resized));
+  Session& s = h->s;      // (the handle is read from here on)
+  CHECKED(c.range("n", n, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create"));
+  HIPRET(hipSetDevice(s.device));
+  std::lock_guard<std::mutex> lk(s.mu);
+  return preprocess_i420_locked(s, yuv, n, height, width, crop, resized, out_hwc, (hipStream_t)stream, windows, table);
 } HEP_CATCH_INT
 
 // ---- decode / filter ----
@@ -919,6 +936,66 @@ int hep_best_window_device(const uint32_t* records, int slots, const int32_t* wi
   return 0;
 } HEP_CATCH_INT
 
+// rectified windows: the host arithmetic is hep_rectify.cpp's (built without contraction), the checks are here
+static_assert(HEP_RECTIFY_ROW_DOUBLES == RECTIFY_ROW_DOUBLES, "the table row of include/hep.h and of the kernels");
+// every window's frame has a camera row whose focal lengths are finite and positive
+static int check_rectify_camera(const Check& c, const float* camera, const int32_t* windows, int n) {
+  for (int i = 0; i < n; i++) {
+    const float* row = camera + (size_t)windows[(size_t)i * 3] * 6;
+    if (!(row[0] > 0.f && row[0] <= FLT_MAX && row[1] > 0.f && row[1] <= FLT_MAX))
+      return c.fail(HEP_ERR_INVALID, "camera row " + std::to_string(windows[(size_t)i * 3]) + ": fx and fy must be finite and positive");
+  }
+  return 0;
+}
+static int check_rectify_row(const Check& c, const double* row) {
+  return row[9] > 0.0 && row[9] <= DBL_MAX && row[10] > 0.0 && row[10] <= DBL_MAX ? 0 : c.fail(HEP_ERR_INVALID, "row: fx and fy must be finite and positive");
+}
+
+int hep_rectify_windows(const float* camera, int frames, const int32_t* windows, int n, int height, int width, int crop, int resized,
+                        double* table_out) try {
+  const Check c{"hep_rectify_windows: "};
+  CHECKED(c.ptrs({{camera, "camera"}, {windows, "windows"}, {table_out, "table_out"}}));
+  CHECKED(c.at_least("frames", frames, 1)); CHECKED(c.at_least("n", n, 1)); CHECKED(check_i420(height, width, crop, resized));
+  CHECKED(check_windows(c, windows, n, frames, height, width, crop)); CHECKED(check_rectify_camera(c, camera, windows, n));
+  for (int i = 0; i < n; i++)
+    rectify_row(camera + (size_t)windows[(size_t)i * 3] * 6, windows + (size_t)i * 3, height, width, crop, resized, table_out + (size_t)i * HEP_RECTIFY_ROW_DOUBLES);
+  return 0;
+} HEP_CATCH_INT
+
+int hep_rectified_point_to_frame(const double* row, double x, double y, int height, int width, int crop, int resized, int size, double* xy_out) try {
+  const Check c{"hep_rectified_point_to_frame: "};
+  CHECKED(c.ptrs({{row, "row"}, {xy_out, "xy_out"}}));
+  CHECKED(check_i420(height, width, crop, resized)); CHECKED(c.at_least("size", size, 1)); CHECKED(check_rectify_row(c, row));
+  rectified_point(row, x, y, height, width, crop, resized, size, xy_out);
+  return 0;
+} HEP_CATCH_INT
+
+int hep_window_from_box_rectified(const double* row, const float* box, int height, int width, int crop, int resized, int size, int32_t* ox_out,
+                                  int32_t* oy_out) try {
+  const Check c{"hep_window_from_box_rectified: "};
+  CHECKED(c.ptrs({{row, "row"}, {box, "box"}, {ox_out, "ox_out"}, {oy_out, "oy_out"}}));
+  CHECKED(check_i420(height, width, crop, resized)); CHECKED(c.at_least("size", size, 1)); CHECKED(check_rectify_row(c, row));
+  double xy[2];
+  rectified_point(row, 0.5 * ((double)box[0] + (double)box[2]), 0.5 * ((double)box[1] + (double)box[3]), height, width, crop, resized, size, xy);
+  // the window around that frame position, kept inside the frame as hep_window_from_box keeps it (a NaN - a ray that points backwards - gives 0)
+  auto around = [&](double centre, int side) {
+    const double v = floor(centre - 0.5 * (double)crop + 0.5);
+    return !(v > 0.0) ? 0 : (v > (double)(side - crop) ? side - crop : (int)v);
+  };
+  *ox_out = around(xy[0], width); *oy_out = around(xy[1], height);
+  return 0;
+} HEP_CATCH_INT
+
+int hep_derotate_records_device(uint32_t* records, int slots, const double* table, int n, void* stream) try {
+  const Check c{"hep_derotate_records_device: "};
+  CHECKED(c.ptrs({{records, "records"}, {table, "table"}}));
+  CHECKED(c.range("slots", slots, 1, 63)); CHECKED(c.range("n", n, 1, INT_MAX / 64));
+  DerotateArgs a; a.records = records; a.table = table; a.n = n; a.slots = slots;
+  launch_derotate_records(a, (hipStream_t)stream);
+  HIPRET(hipGetLastError());
+  return 0;
+} HEP_CATCH_INT
+
 // the handle's buffers for the winners of hep_pose(s)_from_i420_tiled: records and window indices of max_batch x num_classes rows, one size for both calls
 static int best_buffers(Session& s) {
   const size_t need = (kRecBytes + 4) * s.max_batch * s.num_classes;
@@ -931,34 +1008,54 @@ static int best_buffers(Session& s) {
 // padded | frames] in the buffer hep_pose_from_i420 stages in, sized for max_batch frames of this geometry and only ever grown; then the
 // windowed preprocess, one forward at batch n and the top-detection launch.  window_out == NULL: the n (x num_classes) records come back as
 // they are.  Otherwise the best-of-windows launch follows and `frames` (x num_classes) winners with their window indices come back in one copy.
+// rect != NULL (the *_rectified calls): the host table [n][HEP_RECTIFY_ROW_DOUBLES] goes up between the window table and the frames, the
+// rectified preprocess takes the place of the windowed one, `camera` holds every window's frame's CENTRE row and the back-rotation launch
+// follows the top-detection launch.
 static int pose_from_windows_locked(Session& s, bool per_label, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n,
-                                    int crop, int resized, const float* camera, float score_threshold, const PoseOut& o, int32_t* window_out) {
+                                    int crop, int resized, const float* camera, float score_threshold, const PoseOut& o, int32_t* window_out,
+                                    const double* rect = nullptr) {
   HIPRET(hipSetDevice(s.device));
   const size_t in_floats = (size_t)3 * s.size * s.size;
   if (!s.d_in) HIPRET(hipMalloc((void**)&s.d_in, in_floats * s.max_batch * 4));
   if (per_label) if (int rc = poses_buffers(s)) return rc;
   if (window_out) if (int rc = best_buffers(s)) return rc;
   const size_t pad = pose_cam_pad(s), tpad = ((size_t)s.max_batch * 12 + 255) & ~(size_t)255, per_frame = (size_t)height * width * 3 / 2;
-  if (int rc = pose_reserve(s, pad + tpad + per_frame * (size_t)s.max_batch)) return rc;
+  const size_t row_bytes = HEP_RECTIFY_ROW_DOUBLES * sizeof(double), rpad = rect ? ((size_t)s.max_batch * row_bytes + 255) & ~(size_t)255 : 0;
+  if (int rc = pose_reserve(s, pad + tpad + rpad + per_frame * (size_t)s.max_batch)) return rc;
   if (!s.pose_upload_pinned) {
     HIPRET(hipMemcpyAsync(s.d_pose_in, camera, (size_t)n * 24, hipMemcpyHostToDevice, s.stream));
     HIPRET(hipMemcpyAsync(s.d_pose_in + pad, windows, (size_t)n * 12, hipMemcpyHostToDevice, s.stream));
-    HIPRET(hipMemcpyAsync(s.d_pose_in + pad + tpad, yuv, per_frame * frames, hipMemcpyHostToDevice, s.stream));
+    if (rect) HIPRET(hipMemcpyAsync(s.d_pose_in + pad + tpad, rect, (size_t)n * row_bytes, hipMemcpyHostToDevice, s.stream));
+    HIPRET(hipMemcpyAsync(s.d_pose_in + pad + tpad + rpad, yuv, per_frame * frames, hipMemcpyHostToDevice, s.stream));
   } else {
     memcpy(s.h_pose_in, camera, (size_t)n * 24);
     memcpy(s.h_pose_in + pad, windows, (size_t)n * 12);
-    memcpy(s.h_pose_in + pad + tpad, yuv, per_frame * frames);
-    HIPRET(hipMemcpyAsync(s.d_pose_in, s.h_pose_in, pad + tpad + per_frame * frames, hipMemcpyHostToDevice, s.stream));
+    if (rect) memcpy(s.h_pose_in + pad + tpad, rect, (size_t)n * row_bytes);
+    memcpy(s.h_pose_in + pad + tpad + rpad, yuv, per_frame * frames);
+    HIPRET(hipMemcpyAsync(s.d_pose_in, s.h_pose_in, pad + tpad + rpad + per_frame * frames, hipMemcpyHostToDevice, s.stream));
   }
   const int32_t* d_table = (const int32_t*)(s.d_pose_in + pad);
-  if (int rc = preprocess_i420_locked(s, s.d_pose_in + pad + tpad, n, height, width, crop, resized, s.d_in, s.stream, d_table)) return rc;
+  const double* d_rect = rect ? (const double*)(s.d_pose_in + pad + tpad) : nullptr;      // (256-byte aligned)
+  if (int rc = preprocess_i420_locked(s, s.d_pose_in + pad + tpad + rpad, n, height, width, crop, resized, s.d_in, s.stream, d_table, d_rect)) return rc;
   const int64_t S = s.size; const int64_t nhwc[4] = {3 * S * S, 1, 3 * S, 3};      // the NCHW view of the [n,S,S,3] windows
   std::string err;
   if (int rc = run_forward(&s, s.d_in, nhwc, n, s.stream, &err)) return fail(rc, err);
-  if (!window_out) return pose_finish(s, n, score_threshold, o, per_label);
+  if (!window_out && !rect) return pose_finish(s, n, score_threshold, o, per_label);
   uint32_t* d = per_label ? s.d_recs : s.d_rec;
   if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, n, score_threshold, d, s.stream, per_label)) return rc;
   const int slots = per_label ? s.num_classes : 1, rows = frames * slots;
+  if (rect) {
+    DerotateArgs da; da.records = d; da.table = d_rect; da.n = n; da.slots = slots;
+    launch_derotate_records(da, s.stream);
+    HIPRET(hipGetLastError());
+  }
+  if (!window_out) {                                  // the rectified windows call: the n (x num_classes) back-rotated records as they are
+    uint32_t* hr = per_label ? s.h_recs : s.h_rec;
+    HIPRET(hipMemcpyAsync(hr, d, kRecBytes * n * slots, hipMemcpyDeviceToHost, s.stream));
+    HIPRET(hipStreamSynchronize(s.stream));
+    pose_scatter(hr, n * slots, o);
+    return 0;
+  }
   BestWindowArgs a; a.records = d; a.windows = d_table; a.out_records = s.d_best; a.out_window = (int32_t*)(s.d_best + (size_t)rows * HEP_POSE_RECORD_WORDS);
   a.n = n; a.slots = slots; a.frames = frames;
   launch_best_window(a, s.stream);
@@ -975,21 +1072,43 @@ static int check_fits(const Session& s, int resized) {
   return nh < 1 || nh > s.size ? fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size") : 0;
 }
 
+// the host tables of the tiled and of the rectified calls, built under the mutex: sized once, max_batch rows
+static void win_buffers(Session& s) {
+  if (s.win_table.empty()) { s.win_table.resize((size_t)s.max_batch * 3); s.win_cam.resize((size_t)s.max_batch * 6); s.win_rect.resize((size_t)s.max_batch * HEP_RECTIFY_ROW_DOUBLES); }
+}
+// the rectified calls' host side: s.win_cam = every window's frame's centre row as it is, s.win_rect = the table of hep_rectify_windows
+static void rectify_tables(Session& s, const float* camera, const int32_t* windows, int n, int height, int width, int crop, int resized) {
+  for (int i = 0; i < n; i++) {
+    const float* row = camera + (size_t)windows[(size_t)i * 3] * 6;
+    memcpy(s.win_cam.data() + (size_t)i * 6, row, 24);
+    rectify_row(row, windows + (size_t)i * 3, height, width, crop, resized, s.win_rect.data() + (size_t)i * HEP_RECTIFY_ROW_DOUBLES);
+  }
+}
+
+// rectified: camera is [frames,6], the centre rows
 static int pose_from_i420_windows(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int frames, int height, int width,
-                                  const int32_t* windows, int n, int crop, int resized, const float* camera, float score_threshold, const PoseOut& o) {
+                                  const int32_t* windows, int n, int crop, int resized, const float* camera, float score_threshold, const PoseOut& o,
+                                  bool rectified = false) {
   const Check c{who};
   CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {windows, "windows"}, {camera, "camera"}, {o.found, "found"}}));
   CHECKED(c.range("n", n, 1, INT_MAX, HEP_ERR_INVALID, "max_batch given to hep_create")); CHECKED(c.at_least("frames", frames, 1));
   CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_windows(c, windows, n, frames, height, width, crop));
+  if (rectified) CHECKED(check_rectify_camera(c, camera, windows, n));
   Session& s = h->s;      // (the handle is read from here on)
   CHECKED(c.range("n", n, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create"));
   CHECKED(c.range("frames", frames, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create")); CHECKED(check_fits(s, resized));
   std::lock_guard<std::mutex> lk(s.mu);
+  if (rectified) {
+    win_buffers(s);
+    rectify_tables(s, camera, windows, n, height, width, crop, resized);
+    return pose_from_windows_locked(s, per_label, yuv, frames, height, width, windows, n, crop, resized, s.win_cam.data(), score_threshold, o, nullptr, s.win_rect.data());
+  }
   return pose_from_windows_locked(s, per_label, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold, o, nullptr);
 }
 
 static int pose_from_i420_tiled(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop,
-                                int resized, int nx, int ny, const float* camera, float score_threshold, const PoseOut& o, int32_t* window) {
+                                int resized, int nx, int ny, const float* camera, float score_threshold, const PoseOut& o, int32_t* window,
+                                bool rectified = false) {
   const Check c{who};
   CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {camera, "camera"}, {o.found, "found"}, {window, "window"}}));
   CHECKED(c.at_least("nx", nx, 1)); CHECKED(c.at_least("ny", ny, 1)); CHECKED(c.at_least("frames", frames, 1));
@@ -999,9 +1118,16 @@ static int pose_from_i420_tiled(const char* who, bool per_label, hep_handle* h, 
   if (n <= s.max_batch) n *= frames;
   if (n > s.max_batch) return c.fail(HEP_ERR_INVALID, "frames * nx * ny outside 1..max_batch given to hep_create");
   CHECKED(check_fits(s, resized));
+  if (rectified)
+    for (int f = 0; f < frames; f++) { const int32_t w[3] = {f, 0, 0}; CHECKED(check_rectify_camera(c, camera, w, 1)); }
   std::lock_guard<std::mutex> lk(s.mu);
-  if (s.win_table.empty()) { s.win_table.resize((size_t)s.max_batch * 3); s.win_cam.resize((size_t)s.max_batch * 6); }
+  win_buffers(s);
   tile_windows(height, width, crop, nx, ny, frames, s.win_table.data());
+  if (rectified) {
+    rectify_tables(s, camera, s.win_table.data(), (int)n, height, width, crop, resized);
+    return pose_from_windows_locked(s, per_label, yuv, frames, height, width, s.win_table.data(), (int)n, crop, resized, s.win_cam.data(), score_threshold, o, window,
+                                    s.win_rect.data());
+  }
   for (int i = 0; i < (int)n; i++) window_camera(camera, s.win_table.data() + (size_t)i * 3, height, width, crop, resized, s.win_cam.data() + (size_t)i * 6);
   return pose_from_windows_locked(s, per_label, yuv, frames, height, width, s.win_table.data(), (int)n, crop, resized, s.win_cam.data(), score_threshold, o, window);
 }
@@ -1032,6 +1158,35 @@ int hep_poses_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int
                               float* rotation, float* translation, float* hand, int32_t* window) try {
   return pose_from_i420_tiled("hep_poses_from_i420_tiled: ", true, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
                               PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, window);
+} HEP_CATCH_INT
+
+// the rectified forms of the four calls above (include/hep.h): camera is [frames,6], the centre rows, for all four
+int hep_pose_from_i420_windows_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                                         int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                                         int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
+  return pose_from_i420_windows("hep_pose_from_i420_windows_rectified: ", false, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
+                                PoseOut{found, scores, labels, index, boxes, rotation, translation, hand}, true);
+} HEP_CATCH_INT
+
+int hep_poses_from_i420_windows_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                                          int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index,
+                                          float* boxes, float* rotation, float* translation, float* hand) try {
+  return pose_from_i420_windows("hep_poses_from_i420_windows_rectified: ", true, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
+                                PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, true);
+} HEP_CATCH_INT
+
+int hep_pose_from_i420_tiled_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels, int32_t* index,
+                                       float* boxes, float* rotation, float* translation, float* hand, int32_t* window) try {
+  return pose_from_i420_tiled("hep_pose_from_i420_tiled_rectified: ", false, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
+                              PoseOut{found, scores, labels, index, boxes, rotation, translation, hand}, window, true);
+} HEP_CATCH_INT
+
+int hep_poses_from_i420_tiled_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
+                                        float* rotation, float* translation, float* hand, int32_t* window) try {
+  return pose_from_i420_tiled("hep_poses_from_i420_tiled_rectified: ", true, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
+                              PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, window, true);
 } HEP_CATCH_INT
 
 // ---- introspection ----

@@ -105,6 +105,7 @@ struct Session {
   // to max_batch x num_classes rows on both sides, allocated at the first of these calls
   uint32_t* d_best = nullptr; uint32_t* h_best = nullptr;
   std::vector<int32_t> win_table; std::vector<float> win_cam;      // their grid and its camera rows, built under the mutex: sized once, max_batch rows
+  std::vector<double> win_rect;     // the rectified tiled calls: the grid's table of hep_rectify_windows, max_batch rows, built under the mutex
   bool pose_upload_pinned = false;  // HEP_POSE_UPLOAD=pinned: the upload goes through h_pose_in (the measured alternative, hep_api.cpp pose_stage)
   unsigned* d_sync = nullptr;       // meeting counters of grouped launches (k_late.hip): an allocation of its own, zeroed once - never arena memory
   hipStream_t stream = nullptr;     // handle's own stream (host API, capture, profiling)
@@ -124,5 +125,10 @@ void launch_op(const Session& s, const Op& op, int batch, hipStream_t st, const 
 Pick op_pick(const Op& op);          // the device function launch_op runs for `op` (hep_pick.h); empty: none is built - plan_session refuses such a plan
 int run_forward(Session* s, const float* in_dev, const int64_t* strides, int batch, hipStream_t st, std::string* err);
 int host_anchors(int size, std::vector<float>* anchors, std::vector<float>* tanchors);
+// rectified windows, host arithmetic (hep_rectify.cpp, built without contraction; tests/_rectify.py states every rounding).
+// rectify_row: the table row (R_w row-major, fx, fy, px, py) of window w = {frame, ox, oy} from its frame's centre camera row.
+// rectified_point: pixel (x, y) of a rectified image of side x side pixels -> frame coordinates xy[2]; false (xy = NaN) where the ray points backwards
+void rectify_row(const float* camera_row, const int32_t* w, int height, int width, int crop, int resized, double* row);
+bool rectified_point(const double* row, double x, double y, int height, int width, int crop, int resized, int side, double* xy);
 
 }  // namespace hep

@@ -313,6 +313,12 @@ void launch_resize_u8(const ResizeArgs&, hipStream_t);
 // trusted (the host entry points check theirs before the upload)
 struct Yv12WinArgs { const uint8_t* in; uint8_t* bgr; const int32_t* windows; int n, H, W, crop; };
 void launch_yv12_windows(const Yv12WinArgs&, hipStream_t);
+// rectified windows (k_rectify.hip, include/hep.h): the crop x crop image of window i is the frame resampled into the view of the camera
+// rotated to look along the window's ray; table [n][RECTIFY_ROW_DOUBLES] = R_w row-major, fx, fy, px, py in device memory.  Every tap is
+// clamped to the frame, so no value of `table` reads outside it; the frame index of `windows` is trusted as above (ox, oy are not read)
+#define RECTIFY_ROW_DOUBLES 13    // HEP_RECTIFY_ROW_DOUBLES of include/hep.h
+struct Yv12RectArgs { const uint8_t* in; uint8_t* bgr; const int32_t* windows; const double* table; int n, H, W, crop, resized; };
+void launch_yv12_rectified_windows(const Yv12RectArgs&, hipStream_t);
 
 // ---- feature export: NHWC dtype -> NCHW fp32 ----
 struct ExportArgs { const void* in; float* out; int B, H, W, C, bf16; };
@@ -351,6 +357,10 @@ void launch_toplabel(const Top1Args&, hipStream_t);
 // bit for bit, out_window [frames][slots] = that window or -1 with the not-found record of the two launches above
 struct BestWindowArgs { const uint32_t* records; const int32_t* windows; uint32_t* out_records; int32_t* out_window; int n, slots, frames; };
 void launch_best_window(const BestWindowArgs&, hipStream_t);
+// back-rotation of the records of n rectified windows (k_rectify.hip derotate_records_kernel): records [n][slots][POSE_RECORD_WORDS] in place,
+// table as above - rotation, translation and the 21 hand joints of every found record go from the virtual camera's frame to the real one's
+struct DerotateArgs { uint32_t* records; const double* table; int n, slots; };
+void launch_derotate_records(const DerotateArgs&, hipStream_t);
 
 // launch_X(args) finishes the arguments (reciprocals, grid) and launches X_pick(args): the pick reads only fields the planner sets, so it
 // can be asked for a launch's device function before any session exists (hep_kernel_symbol, plan_session's check of the plan)

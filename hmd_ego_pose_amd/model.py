@@ -232,15 +232,15 @@ class Session:
         return dict(found=rec[..., 0], index=rec[..., 2], score=f[..., 4], box=f[..., 5:9], rotation=f[..., 9:12],
                     translation=f[..., 12:15], hand=f[..., 15:78], record=rec)
 
-    def _pose_call(self, who, fn, lead, B, camera, score_threshold, per_label=False, tail=()):
+    def _pose_call(self, who, fn, lead, B, camera, score_threshold, per_label=False, tail=(), cam_rows=None):
         import numpy as np
         cam = np.ascontiguousarray(camera, dtype=np.float32) if not isinstance(camera, torch.Tensor) else None
         if cam is None:
             if camera.is_cuda:
                 raise ValueError(f"{who}: camera must live in host memory")
             cam = np.ascontiguousarray(camera.numpy(), dtype=np.float32)
-        if cam.shape != (B, 6):
-            raise ValueError(f"{who}: camera must have shape ({B}, 6), got {cam.shape}")
+        if cam.shape != (B if cam_rows is None else cam_rows, 6):      # cam_rows: the rectified windows call - a row per frame, B windows
+            raise ValueError(f"{who}: camera must have shape ({B if cam_rows is None else cam_rows}, 6), got {cam.shape}")
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"{who}: batch {B} is outside 1..{self.max_batch}")
         lead_shape = (B, self.num_classes) if per_label else (B,)       # per_label (poses_from_*): slot c is label c, no label array
@@ -337,6 +337,45 @@ class Session:
                                                                    crop, resized, out.data_ptr(), stream))
         return out.permute(0, 3, 1, 2)
 
+    def preprocess_i420_rectified(self, frames_u8: torch.Tensor, height: int, width: int, windows: torch.Tensor, table: torch.Tensor,
+                                  crop: int = 256, resized: int = 512) -> torch.Tensor:
+        """``preprocess_i420_windows`` on RECTIFIED windows (hep_preprocess_i420_rectified_device): ``table`` [n,13] float64 on the device, the
+        rows of ``rectify_windows`` for ``windows`` -> the NCHW view of [n, size, size, 3]; image i is the frame resampled into the view of the
+        camera rotated to look along window i's ray.  Every tap is clamped to the frame: no table value reads outside it."""
+        who = "preprocess_i420_rectified"
+        if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 2 or frames_u8.shape[1] != height * width * 3 // 2:
+            raise ValueError(f"{who}: expected a uint8 ROCm tensor [F, height * width * 3 // 2]")
+        if (not isinstance(windows, torch.Tensor) or windows.device != frames_u8.device or windows.dtype != torch.int32 or windows.dim() != 2
+                or windows.shape[1] != 3 or not 1 <= windows.shape[0] <= self.max_batch):
+            raise ValueError(f"{who}: windows must be an int32 tensor (n, 3) on {frames_u8.device} with n in 1..{self.max_batch}")
+        if (not isinstance(table, torch.Tensor) or table.device != frames_u8.device or table.dtype != torch.float64
+                or tuple(table.shape) != (windows.shape[0], _capi.RECTIFY_ROW_DOUBLES)):
+            raise ValueError(f"{who}: table must be a float64 tensor ({windows.shape[0]}, {_capi.RECTIFY_ROW_DOUBLES}) on {frames_u8.device}")
+        x, w, t = frames_u8.contiguous(), windows.contiguous(), table.contiguous()
+        out = torch.empty((w.shape[0], self.size, self.size, 3), dtype=torch.float32, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _capi.check(_capi.lib().hep_preprocess_i420_rectified_device(self.handle, x.data_ptr(), x.shape[0], height, width, w.data_ptr(), t.data_ptr(),
+                                                                     w.shape[0], crop, resized, out.data_ptr(), stream))
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def derotate_records(records: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+        """Back-rotation of the records of n rectified windows IN PLACE, one launch (hep_derotate_records_device): ``records`` [n,80]
+        (``top1``) or [n,K,80] (``top_labels``) int32, contiguous, and ``table`` [n,13] float64 on the device.  Rotation, translation and hand
+        of every found record go from the rectified camera's frame to the real camera's; everything else stays.  Returns ``records``."""
+        if (not isinstance(records, torch.Tensor) or not records.is_cuda or records.dtype != torch.int32 or records.dim() not in (2, 3)
+                or records.shape[-1] != _capi.POSE_RECORD_WORDS or not records.is_contiguous()):
+            raise ValueError("derotate_records: records must be a contiguous int32 ROCm tensor [n,80] or [n,K,80]")
+        n, slots = records.shape[0], (records.shape[1] if records.dim() == 3 else 1)
+        if (not isinstance(table, torch.Tensor) or table.device != records.device or table.dtype != torch.float64
+                or tuple(table.shape) != (n, _capi.RECTIFY_ROW_DOUBLES)):
+            raise ValueError(f"derotate_records: table must be a float64 tensor ({n}, {_capi.RECTIFY_ROW_DOUBLES}) on {records.device}")
+        if n < 1 or not 1 <= slots <= 63:
+            raise ValueError("derotate_records: n must be at least 1, slots in 1..63")
+        stream = torch.cuda.current_stream(records.device).cuda_stream
+        _capi.check(_capi.lib().hep_derotate_records_device(records.data_ptr(), slots, table.contiguous().data_ptr(), n, stream))
+        return records
+
     @staticmethod
     def best_window(records: torch.Tensor, windows: torch.Tensor, frames: int):
         """Best of the windows of every frame in one launch (hep_best_window_device): ``records`` [n,80] (``top1``) or [n,K,80]
@@ -361,18 +400,25 @@ class Session:
         return out, win
 
     def pose_from_i420_windows(self, frames_u8_host, height: int, width: int, windows, camera, crop: int = 256, resized: int = 512,
-                               score_threshold=0.5, per_label=False):
+                               score_threshold=0.5, per_label=False, rectified=False):
         """``pose_from_i420`` on n windows of the frames in one call (hep_pose_from_i420_windows; ``per_label``:
         hep_poses_from_i420_windows): frames [F, height * width * 3 // 2] uint8, ``windows`` [n,3] int32 and ``camera`` [n,6] - one row PER
-        WINDOW, see ``window_cameras`` - in HOST memory -> the arrays of ``pose_from_i420`` (``poses_from_i420``) with one row per window."""
+        WINDOW, see ``window_cameras`` - in HOST memory -> the arrays of ``pose_from_i420`` (``poses_from_i420``) with one row per window.
+        ``rectified=True`` (hep_pose_from_i420_windows_rectified / hep_poses_from_...): every window is rectified - resampled into the view
+        of the camera rotated to look along its ray - and the poses are rotated back into the real camera's frame; ``camera`` is then [F,6],
+        the CENTRE rows of the frames, and boxes are in network-input pixels of the rectified window (``rectified_point_to_frame``)."""
         who = "pose_from_i420_windows"
         x = self._i420_host(who, frames_u8_host, height, width, crop, resized)
         if not 1 <= x.shape[0] <= self.max_batch:
             raise ValueError(f"{who}: {x.shape[0]} frames are outside 1..{self.max_batch}")
         w = self._windows_host(who, windows, x.shape[0], height, width, crop)
-        fn = _capi.lib().hep_poses_from_i420_windows if per_label else _capi.lib().hep_pose_from_i420_windows
+        l = _capi.lib()
+        if rectified:
+            fn = l.hep_poses_from_i420_windows_rectified if per_label else l.hep_pose_from_i420_windows_rectified
+        else:
+            fn = l.hep_poses_from_i420_windows if per_label else l.hep_pose_from_i420_windows
         return self._pose_call(who, fn, (x.ctypes.data, x.shape[0], height, width, w.ctypes.data, w.shape[0], crop, resized), w.shape[0], camera,
-                               score_threshold, per_label=per_label)
+                               score_threshold, per_label=per_label, cam_rows=x.shape[0] if rectified else None)
 
     def _tiled(self, who, fn, per_label, frames_u8_host, height, width, camera, crop, resized, nx, ny, score_threshold):
         import numpy as np
@@ -387,18 +433,23 @@ class Session:
         return out
 
     def pose_from_i420_tiled(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, nx: int = 1, ny: int = 1,
-                             score_threshold=0.5):
+                             score_threshold=0.5, rectified=False):
         """The whole frame in one call (hep_pose_from_i420_tiled): the ``nx`` x ``ny`` grid of ``tile_windows`` over every frame, the cameras
         of ``window_cameras`` from ``camera`` [F,6] (the rows ``pose_from_i420`` takes), one forward at batch F * nx * ny, best window per
         frame.  The arrays of ``pose_from_i420`` with one row per frame and ``window`` [F] int32: the winner's index in the grid's table or
-        -1.  Boxes are in the winning window's network-input pixels; a 1 x 1 grid is ``pose_from_i420`` bit for bit."""
-        return self._tiled("pose_from_i420_tiled", _capi.lib().hep_pose_from_i420_tiled, False, frames_u8_host, height, width, camera, crop, resized,
+        -1.  Boxes are in the winning window's network-input pixels; a 1 x 1 grid is ``pose_from_i420`` bit for bit.
+        ``rectified=True`` (hep_pose_from_i420_tiled_rectified): the grid's windows are rectified and the winner's pose is in the real camera's
+        frame, exact off the optical axis; the box is in network-input pixels of the RECTIFIED window (``window_from_box_rectified``)."""
+        l = _capi.lib()
+        return self._tiled("pose_from_i420_tiled", l.hep_pose_from_i420_tiled_rectified if rectified else l.hep_pose_from_i420_tiled, False, frames_u8_host, height, width, camera, crop, resized,
                            nx, ny, score_threshold)
 
     def poses_from_i420_tiled(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, nx: int = 1, ny: int = 1,
-                              score_threshold=0.5):
-        """``pose_from_i420_tiled`` for several objects (hep_poses_from_i420_tiled): arrays [F,K,...] as ``poses_from_i420``, ``window`` [F,K]."""
-        return self._tiled("poses_from_i420_tiled", _capi.lib().hep_poses_from_i420_tiled, True, frames_u8_host, height, width, camera, crop, resized,
+                              score_threshold=0.5, rectified=False):
+        """``pose_from_i420_tiled`` for several objects (hep_poses_from_i420_tiled; ``rectified``: hep_poses_from_i420_tiled_rectified): arrays
+        [F,K,...] as ``poses_from_i420``, ``window`` [F,K]."""
+        l = _capi.lib()
+        return self._tiled("poses_from_i420_tiled", l.hep_poses_from_i420_tiled_rectified if rectified else l.hep_poses_from_i420_tiled, True, frames_u8_host, height, width, camera, crop, resized,
                            nx, ny, score_threshold)
 
     # -- introspection ------------------------------------------------------------------
@@ -734,4 +785,50 @@ def window_from_box(box, ox: int, oy: int, height: int, width: int, crop: int, s
         raise ValueError(f"window_from_box: box must have 4 entries, got {b.shape}")
     x, y = ctypes.c_int32(), ctypes.c_int32()
     _capi.check(_capi.lib().hep_window_from_box(b.ctypes.data, ox, oy, height, width, crop, size, ctypes.byref(x), ctypes.byref(y)))
+    return x.value, y.value
+
+
+def rectify_windows(camera, windows, height: int, width: int, crop: int, resized: int):
+    """hep_rectify_windows: ``camera`` [F,6] (the CENTRE rows) and ``windows`` [n,3] int32 -> numpy float64 [n,13]: per window the rotation R_w
+    (row-major) that takes the optical axis to the window's viewing ray, then fx, fy, px, py.  The centre window's R_w is the identity."""
+    import numpy as np
+    cam = np.ascontiguousarray(camera, dtype=np.float32)
+    w = np.ascontiguousarray(windows)
+    if w.dtype != np.int32 or w.ndim != 2 or w.shape[1] != 3 or w.shape[0] < 1:
+        raise ValueError(f"rectify_windows: windows must be int32 of shape (n, 3), got {w.dtype} {w.shape}")
+    if cam.ndim != 2 or cam.shape[1] != 6 or cam.shape[0] < 1:
+        raise ValueError(f"rectify_windows: camera must have shape (F, 6), got {cam.shape}")
+    out = np.empty((w.shape[0], _capi.RECTIFY_ROW_DOUBLES), np.float64)
+    _capi.check(_capi.lib().hep_rectify_windows(cam.ctypes.data, cam.shape[0], w.ctypes.data, w.shape[0], height, width, crop, resized, out.ctypes.data))
+    return out
+
+
+def _rectify_row(who, row):
+    import numpy as np
+    r = np.ascontiguousarray(row, dtype=np.float64)
+    if r.shape != (_capi.RECTIFY_ROW_DOUBLES,):
+        raise ValueError(f"{who}: row must have {_capi.RECTIFY_ROW_DOUBLES} entries (a row of rectify_windows), got {r.shape}")
+    return r
+
+
+def rectified_point_to_frame(row, x: float, y: float, height: int, width: int, crop: int, resized: int, size: int):
+    """hep_rectified_point_to_frame: pixel (x, y) of the network input (``size``) of the rectified window ``row`` -> the frame position
+    (X_f, Y_f) it looks at; (nan, nan) when the ray points backwards.  Boxes of the rectified calls go back to the frame through this."""
+    import numpy as np
+    r = _rectify_row("rectified_point_to_frame", row)
+    xy = np.empty(2, np.float64)
+    _capi.check(_capi.lib().hep_rectified_point_to_frame(r.ctypes.data, float(x), float(y), height, width, crop, resized, size, xy.ctypes.data))
+    return float(xy[0]), float(xy[1])
+
+
+def window_from_box_rectified(row, box, height: int, width: int, crop: int, resized: int, size: int):
+    """hep_window_from_box_rectified: the plain window (ox, oy) centred on a detection of the rectified window ``row``; ``box`` = xmin, ymin,
+    xmax, ymax in network-input pixels of that rectified window."""
+    import numpy as np
+    r = _rectify_row("window_from_box_rectified", row)
+    b = np.ascontiguousarray(box, dtype=np.float32)
+    if b.shape != (4,):
+        raise ValueError(f"window_from_box_rectified: box must have 4 entries, got {b.shape}")
+    x, y = ctypes.c_int32(), ctypes.c_int32()
+    _capi.check(_capi.lib().hep_window_from_box_rectified(r.ctypes.data, b.ctypes.data, height, width, crop, resized, size, ctypes.byref(x), ctypes.byref(y)))
     return x.value, y.value

@@ -30,6 +30,8 @@
  *                                 reference constructs its filter (train.py:78-81)
  *   hep_pose_from_i420_tiled, hep_pose_from_i420_windows (and hep_poses_*) <- no twin: the callback's centre crop taken at several places of
  *                                 the frame in one call, best window reported (WHOLE-FRAME SEARCH below)
+ *   hep_pose_from_i420_tiled_rectified, hep_pose_from_i420_windows_rectified (and hep_poses_*) <- no twin: the same search on windows resampled
+ *                                 into the view of a camera rotated to look along their ray, poses rotated back (RECTIFIED WINDOWS below)
  *   hep_anchor_targets_device <- anchor_targets_bbox, pytorch-sandbox/generators/utils/anchors.py:69-221 (training side)
  *   hep_losses_device          <- batch_iterate, pytorch-sandbox/hmdegopose/loss.py:54-428 (training side, forward values)
  *   hep_losses_backward_device <- loss.backward() through batch_iterate (training side, gradients of the predictions)
@@ -266,8 +268,9 @@ int hep_poses_from_input(hep_handle* h, const float* input_nchw, int batch, cons
  * A WINDOW is three int32 {frame, ox, oy}: the crop x crop square of frame `frame` whose top-left pixel is (ox, oy), 0 <= ox <= width - crop,
  * 0 <= oy <= height - crop, any parity.  Its pixels are converted exactly as the frame path converts the centre square (the chroma of a pixel
  * is that of its place in the full frame), then resized and normalised by the same two launches.
- * LIMITS: rotation is the network's output as the filter returns it, exactly as for the centre crop.  A window's camera differs from the
- * caller's by the principal point only (hep_window_cameras); no correction for the viewing ray of an off-axis window is applied or claimed.
+ * LIMITS of the plain (unrectified) calls: rotation is the network's output as the filter returns it, exactly as for the centre crop.  A
+ * window's camera differs from the caller's by the principal point only (hep_window_cameras); no correction for the viewing ray of an off-axis
+ * window is applied or claimed by them.  The RECTIFIED WINDOWS further below apply that correction exactly.
  *
  * The three functions below are host arithmetic: no handle, no HIP call.
  *
@@ -325,6 +328,66 @@ int hep_pose_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int 
 int hep_poses_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
                               const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
                               float* rotation, float* translation, float* hand, int32_t* window);
+
+/* RECTIFIED WINDOWS.  A plain window is a square cut out of the frame: 30 degrees off the optical axis it shows the object as a camera looking
+ * along the axis sees it from the side, while the network - trained on crops whose principal point sits near their centre - reports the rotation
+ * as if the camera looked straight at it.  The rectified window of {frame, ox, oy} is the frame RESAMPLED into the picture that a camera with the
+ * caller's own intrinsics, rotated about the same centre to look along the window's viewing ray, would have taken (a pure rotation is a
+ * homography: exact up to resampling).  The network sees a centre view with the centre camera row; its rotation, translation and hand joints are
+ * then rotated back into the real camera's frame.  tests/_rectify.py states every rounding of what follows in numpy; all of it is float64.
+ * CLAIMED: the geometry, up to resampling.  NOT MODELLED: lens distortion.  NOT MEASURED AND NOT CLAIMED: accuracy on trained weights.
+ *
+ * With s = resized / crop, ox_c = (width - crop) / 2, oy_c = (height - crop) / 2 (integer division) and (fx, fy, px, py) the frame's CENTRE camera
+ * row (float32 widened): a = (ox - ox_c) s / fx, b = (oy - oy_c) s / fy, d = (a, b, 1) / sqrt(a a + b b + 1), k = 1 / (1 + d_z),
+ *   R_w = [1 - d_x d_x k, -d_x d_y k, d_x;  -d_x d_y k, 1 - d_y d_y k, d_y;  -d_x, -d_y, d_z]
+ * - the rotation about e_z x d that takes e_z to d, from + - * / sqrt alone; a point X_v of the virtual camera's frame is X_c = R_w X_v in the
+ * real camera's.  The centre window gives the identity exactly.  A TABLE ROW is HEP_RECTIFY_ROW_DOUBLES doubles: R_w row-major, fx, fy, px, py.
+ * Pixel (x, y) of the rectified crop: u = s (x + 0.5) - 0.5, v alike; q = ((u - px) / fx, (v - py) / fy, 1); p = R_w q; p_z <= 0 or not finite:
+ * black.  Otherwise u' = fx p_x / p_z + px, X_f = (u' + 0.5) / s - 0.5 + ox_c (Y_f alike), sampled from the converted frame at 1/32 pixel with
+ * integer bilinear weights that sum to 32768 and the four taps CLAMPED to the frame (replicate border).  The two resize launches of the frame path
+ * follow unchanged.  The centre window's crop is the plain crop bit for bit.
+ *
+ * hep_rectify_windows (host arithmetic, no handle, no HIP call): camera [frames,6] = the centre rows, windows [n][3] -> table_out
+ * [n][HEP_RECTIFY_ROW_DOUBLES].  NULL, n or frames < 1, the frame geometry, a window outside the frame or naming a frame >= frames, an fx or fy
+ * that is not finite and positive: HEP_ERR_INVALID. */
+#define HEP_RECTIFY_ROW_DOUBLES 13
+int hep_rectify_windows(const float* camera, int frames, const int32_t* windows, int n, int height, int width, int crop, int resized,
+                        double* table_out);
+/* Going back to the frame (host arithmetic): pixel (x, y) of the network input (`size` pixels a side) of the rectified window `row` looks at
+ * frame position xy_out[2] = (X_f, Y_f) - the chain above with size in place of crop in u = (resized / size) (x + 0.5) - 0.5; both NaN when the
+ * ray points backwards.  BOXES OF THE RECTIFIED CALLS LIVE IN THE RECTIFIED WINDOW: map their corners or centre with this function, not with the
+ * window's offsets.  hep_window_from_box_rectified: the plain window centred on a detection of a rectified window, for the follow loop - the
+ * centre (0.5 (xmin + xmax), 0.5 (ymin + ymax)) of box [4] goes through the map above, then *ox_out = clamp((int)floor(X_f - 0.5 crop + 0.5), 0,
+ * width - crop) and *oy_out likewise (a NaN gives 0).  NULL, size < 1, the frame geometry, a row whose fx or fy is not finite and positive:
+ * HEP_ERR_INVALID. */
+int hep_rectified_point_to_frame(const double* row, double x, double y, int height, int width, int crop, int resized, int size, double* xy_out);
+int hep_window_from_box_rectified(const double* row, const float* box, int height, int width, int crop, int resized, int size, int32_t* ox_out,
+                                  int32_t* oy_out);
+/* Back-rotation of the records of n rectified windows, in place, one launch, no handle: records [n][slots][HEP_POSE_RECORD_WORDS] and table
+ * [n][HEP_RECTIFY_ROW_DOUBLES] on the device.  For every record with found == 1, in double, each result rounded once to float32: the rotation
+ * words hold the axis-angle vector in units of pi (the network's output), so R_out = R_w Rodrigues(pi rotation) and rotation' = Rodrigues^-1(R_out)
+ * / pi; translation' = R_w translation; every hand joint' = R_w joint.  Words 0-8 (found, label, index, score, box - the box stays in
+ * network-input pixels of the rectified window) and 78-79 are untouched; a record with found != 1 is untouched bit for bit, and so is every
+ * record of a row whose R_w is exactly the identity.  Asynchronous on `stream`.  NULL, slots outside 1..63, n < 1: HEP_ERR_INVALID. */
+int hep_derotate_records_device(uint32_t* records, int slots, const double* table, int n, void* stream);
+/* The four one-call forms on rectified windows: ONE upload (camera rows, window table, the float64 table computed on the host, frames), the
+ * rectified preprocess, one forward at batch n, the top-detection launch with every window's frame's CENTRE camera row unshifted, the
+ * back-rotation launch, for the tiled calls hep_best_window_device, one download.  Arguments, outputs and checks as for the calls above, except:
+ * camera is [frames,6] - the centre rows - for ALL FOUR, and an fx or fy that is not finite and positive is HEP_ERR_INVALID.  Boxes are in
+ * network-input pixels of the RECTIFIED window; rotation, translation and hand are in the real camera's frame.  A 1 x 1 grid is
+ * hep_pose_from_i420 bit for bit. */
+int hep_pose_from_i420_windows_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                                         int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
+                                         int32_t* index, float* boxes, float* rotation, float* translation, float* hand);
+int hep_poses_from_i420_windows_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
+                                          int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index,
+                                          float* boxes, float* rotation, float* translation, float* hand);
+int hep_pose_from_i420_tiled_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels, int32_t* index,
+                                       float* boxes, float* rotation, float* translation, float* hand, int32_t* window);
+int hep_poses_from_i420_tiled_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
+                                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
+                                        float* rotation, float* translation, float* hand, int32_t* window);
 
 /* ADD and ADD-S of num_pairs (ground truth, prediction) poses over one object model: points [num_points,3]; rotations
  * as axis-angle vectors in radians (what _get_detections hands on: network output * pi), translations in the model's
@@ -891,6 +954,13 @@ int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int
  * NULL, frames < 1, the frame geometry, n outside 1..max_batch: HEP_ERR_INVALID before any HIP call. */
 int hep_preprocess_i420_windows_device(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n,
                                        int crop, int resized, float* out_hwc, void* stream);
+
+/* The same for n RECTIFIED windows (RECTIFIED WINDOWS above): table [n][HEP_RECTIFY_ROW_DOUBLES] on the device next to windows [n][3], of which
+ * only the frame index is read.  Both tables are trusted device memory; every tap is clamped to its frame, so no value of `table` - a NaN row
+ * included - reads outside it.  Scratch frames, event, refusal under stream capture and the n <= max_batch rule as above.
+ * NULL, frames < 1, the frame geometry, n outside 1..max_batch: HEP_ERR_INVALID before any HIP call. */
+int hep_preprocess_i420_rectified_device(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows,
+                                         const double* table, int n, int crop, int resized, float* out_hwc, void* stream);
 
 /* Introspection used by tests, bench.py and DESIGN.md tables. */
 int hep_debug_tensor_count(const hep_handle* h);

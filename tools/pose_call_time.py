@@ -36,6 +36,15 @@ composed and tiled alternate, twice each per size, in child processes under the 
 medians, both run-to-run spreads, and whether the one call is faster than the composed path by more than the composed path's own spread.
 
     python tools/pose_call_time.py --tiles 4x2 [--calls 300] [--warmup 20] [--json FILE]
+
+--tiles NXxNY --rectified: the same frame and sessions, the one call on RECTIFIED windows against the one call on plain windows:
+  tiled     = hep_pose_from_i420_tiled, as above (unchanged code: its figures show that nothing else moved)
+  rectified = hep_pose_from_i420_tiled_rectified (the table computed on the host and uploaded with the rest, four clamped taps and a float64
+              chain per crop pixel where the plain kernel reads one pixel, and the back-rotation launch)
+tiled and rectified alternate, twice each per size.  The tool prints both medians, both run-to-run spreads, and whether the rectified call costs
+more than the plain call's own spread.
+
+    python tools/pose_call_time.py --tiles 4x2 --rectified [--calls 300] [--warmup 20] [--json FILE]
 """
 import argparse
 import ctypes
@@ -209,7 +218,12 @@ def child_tiles(args):
     top_ptrs = [top[k].ctypes.data for k in Session._POSE_KEYS]
     window = np.empty(1, np.int32)
     answer = {}
-    if args.child == "tiled":
+    if args.child == "rectified":
+        def call():
+            _capi.check(lib.hep_pose_from_i420_tiled_rectified(s.handle, frame.ctypes.data, 1, FH, FW, crop, rs, nx, ny, cam.ctypes.data, thr, *top_ptrs,
+                                                               window.ctypes.data))
+            answer["row"] = (int(window[0]), int(top["index"][0]), float(top["score"][0]))
+    elif args.child == "tiled":
         def call():
             _capi.check(lib.hep_pose_from_i420_tiled(s.handle, frame.ctypes.data, 1, FH, FW, crop, rs, nx, ny, cam.ctypes.data, thr, *top_ptrs, window.ctypes.data))
             answer["row"] = (int(window[0]), int(top["index"][0]), float(top["score"][0]))
@@ -235,23 +249,52 @@ def child_tiles(args):
     print("RESULT " + json.dumps(out), flush=True)
 
 
+def tiles_child(args, path, size):
+    """one measuring child of the --tiles modes: its result, printed; a child that fails ends the run"""
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--calls", str(args.calls), "--warmup", str(args.warmup),
+           "--tiles", f"{args.tiles[0]}x{args.tiles[1]}", "--size", str(size)]
+    r = subprocess.run(cmd, timeout=args.timeout, capture_output=True, text=True)
+    line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+    if r.returncode != 0 or not line:
+        print(r.stdout[-2000:], r.stderr[-4000:], sep="\n")
+        sys.exit(f"the {path} child failed (exit status {r.returncode}): nothing further is started")
+    d = json.loads(line[0][7:])
+    print(f"{path:<9} size {size}  " + "  ".join(f"{k}: p50 {d[k]['p50_ms']:.4f} p99 {d[k]['p99_ms']:.4f}" for k in ("call", "call_60hz")) +
+          f"  (window, anchor, score) = {d['row']}", flush=True)
+    return d
+
+
+def main_tiles_rectified(args):
+    """tiled and rectified alternate, twice each, at phi 0 @ 512 and @ 256; medians and run-to-run spread of both, and what the rectification costs"""
+    runs, verdict = [], {}
+    for size in (512, 256):
+        for path in ("tiled", "rectified") * 2:
+            runs.append(tiles_child(args, path, size))
+        mine = [r for r in runs if r["size"] == size]
+        for k in ("call", "call_60hz"):
+            t, c = ([r[k]["p50_ms"] for r in mine if r["path"] == p] for p in ("tiled", "rectified"))
+            ts, cs = abs(t[0] - t[1]), abs(c[0] - c[1])
+            cost = sum(c) / 2 - sum(t) / 2
+            beyond = min(c) > max(t) + ts
+            verdict[f"{size} {k}"] = {"tiled_p50": t, "rectified_p50": c, "tiled_spread": round(ts, 4), "rectified_spread": round(cs, 4),
+                                      "cost_ms": round(cost, 4), "cost_beyond_spread": bool(beyond)}
+            print(f"size {size} {k:<9} tiled p50 {t} (spread {ts:.4f})  rectified p50 {c} (spread {cs:.4f})  -> the rectification costs {cost:+.4f} ms, "
+                  f"{'more' if beyond else 'NOT more'} than the plain call's run-to-run spread")
+    T = args.tiles[0] * args.tiles[1]
+    print(f"tiled:     per frame H2D 3 (cameras, table, frame), preprocess 3 launches at batch {T}, forward at batch {T}, top-1 1, best-of-windows 1, D2H 1")
+    print(f"rectified: per frame H2D 4 (cameras, table, float64 table, frame), the same launches with the warp in place of the crop, back-rotation 1, D2H 1")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"runs": runs, "verdict": verdict}, f, indent=1)
+
+
 def main_tiles(args):
     """composed and tiled alternate, twice each, at phi 0 @ 512 and @ 256; medians and run-to-run spread of both, and whether the one call is
     faster than the composed path by more than the composed path's own spread"""
     runs, verdict = [], {}
     for size in (512, 256):
         for path in ("composed", "tiled") * 2:
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--calls", str(args.calls), "--warmup", str(args.warmup),
-                   "--tiles", f"{args.tiles[0]}x{args.tiles[1]}", "--size", str(size)]
-            r = subprocess.run(cmd, timeout=args.timeout, capture_output=True, text=True)
-            line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
-            if r.returncode != 0 or not line:
-                print(r.stdout[-2000:], r.stderr[-4000:], sep="\n")
-                sys.exit(f"the {path} child failed (exit status {r.returncode}): nothing further is started")
-            runs.append(json.loads(line[0][7:]))
-            d = runs[-1]
-            print(f"{path:<8} size {size}  " + "  ".join(f"{k}: p50 {d[k]['p50_ms']:.4f} p99 {d[k]['p99_ms']:.4f}" for k in ("call", "call_60hz")) +
-                  f"  (window, anchor, score) = {d['row']}", flush=True)
+            runs.append(tiles_child(args, path, size))
         mine = [r for r in runs if r["size"] == size]
         rows = {tuple(r["row"][:2]) for r in mine}
         if mine[0]["even_offsets"]:                      # the composed path is exact only then
@@ -290,8 +333,9 @@ def main():
     ap.add_argument("--timeout", type=int, default=180, help="time limit of one measuring child process, seconds")
     ap.add_argument("--labels", type=int, default=0, help="K: time hep_poses_from_* with seeded K-class weights (see above)")
     ap.add_argument("--tiles", default=None, help="NXxNY: time hep_pose_from_i420_tiled against the composed whole-frame search (see above)")
+    ap.add_argument("--rectified", action="store_true", help="with --tiles: time hep_pose_from_i420_tiled_rectified against hep_pose_from_i420_tiled")
     ap.add_argument("--size", type=int, default=512, help=argparse.SUPPRESS)
-    ap.add_argument("--child", default=None, choices=["old", "new", "top1", "composed", "tiled"], help=argparse.SUPPRESS)
+    ap.add_argument("--child", default=None, choices=["old", "new", "top1", "composed", "tiled", "rectified"], help=argparse.SUPPRESS)
     args = ap.parse_args()
     if not 0 <= args.labels <= 63:
         sys.exit("--labels must be in 1..63")
@@ -301,7 +345,9 @@ def main():
             assert len(args.tiles) == 2 and min(args.tiles) >= 1
         except (ValueError, AssertionError):
             sys.exit("--tiles takes NXxNY, e.g. 4x2")
-        return child_tiles(args) if args.child else main_tiles(args)
+        return child_tiles(args) if args.child else (main_tiles_rectified if args.rectified else main_tiles)(args)
+    if args.rectified:
+        sys.exit("--rectified goes with --tiles")
     if args.child:
         return child(args)
     runs = []

@@ -1,6 +1,7 @@
-/* The whole-frame search's host side as a stand-alone program: the argument checks of its nine entry points - every call below must return
+/* The whole-frame search's host side as a stand-alone program: the argument checks of its entry points, plain and rectified, - every call below must return
  * before any HIP call, so it runs without a device - and the host arithmetic of hep_tile_windows / hep_window_cameras / hep_window_from_box on
- * exactly sized heap blocks.  It suits a host sanitizer build:
+ * exactly sized heap blocks (hep_rectify_windows, hep_rectified_point_to_frame and hep_window_from_box_rectified likewise).  It suits a host
+ * sanitizer build:
  *   make -C hmd_ego_pose_amd/csrc OUT=$PWD/build_san/libhep_san.so OBJDIR=$PWD/build_san/obj \
  *        EXTRA="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer"
  *   clang -fsanitize=address,undefined -Iinclude tools/windows_abi_check.c -o build_san/windows_abi_check -Lbuild_san -lhep_san -Wl,-rpath,$PWD/build_san
@@ -89,6 +90,8 @@ int main(void) {
 #define WINS(h, y, fr, hh, ww, wi, n, c, cm, fo) hep_poses_from_i420_windows(h, y, fr, hh, ww, wi, n, c, R, cm, .5f, fo, NULL, NULL, NULL, NULL, NULL, NULL)
 #define TIL(h, y, fr, hh, ww, c, nx, ny, cm, fo, wo) hep_pose_from_i420_tiled(h, y, fr, hh, ww, c, R, nx, ny, cm, .5f, fo, NULL, NULL, NULL, NULL, NULL, NULL, NULL, wo)
 #define TILS(h, y, fr, hh, ww, c, nx, ny, cm, fo, wo) hep_poses_from_i420_tiled(h, y, fr, hh, ww, c, R, nx, ny, cm, .5f, fo, NULL, NULL, NULL, NULL, NULL, NULL, wo)
+#define WINR(h, y, fr, hh, ww, wi, n, c, cm, fo) hep_pose_from_i420_windows_rectified(h, y, fr, hh, ww, wi, n, c, R, cm, .5f, fo, NULL, NULL, NULL, NULL, NULL, NULL, NULL)
+#define TILR(h, y, fr, hh, ww, c, nx, ny, cm, fo, wo) hep_pose_from_i420_tiled_rectified(h, y, fr, hh, ww, c, R, nx, ny, cm, .5f, fo, NULL, NULL, NULL, NULL, NULL, NULL, NULL, wo)
   const int32_t frame1[3] = {1, 0, 0};
   REFUSED(WIN(NULL, yuv, 1, H, W, grid, 1, C, cam, found), "hep_pose_from_i420_windows: handle is NULL");
   REFUSED(WINS(NULL, yuv, 1, H, W, grid, 1, C, cam, found), "hep_poses_from_i420_windows: handle is NULL");
@@ -118,7 +121,47 @@ int main(void) {
   REFUSED(TIL(fake, yuv, 1, H, W, C, 4, 2, cam, found, found), "frames * nx * ny outside 1..max_batch");      /* the zeroed handle: max_batch 0 */
   REFUSED(TIL(fake, yuv, 2147483647, H, W, C, 2147483647, 2147483647, cam, found, found), "frames * nx * ny outside 1..max_batch");      /* no overflow on the way */
 
-  free(fake); free(cam); free(f); free(found); free(yuv); free(rec); free(grid); free(wcam);
+  /* rectified windows: the host arithmetic into exactly sized blocks, then the refusals */
+  double* table = malloc(16 * HEP_RECTIFY_ROW_DOUBLES * sizeof(double));
+  EXPECT(hep_rectify_windows(cam, 2, grid, 16, H, W, C, R, table), 0);
+  EXPECT(table[0 * 13 + 2] < 0 && table[3 * 13 + 2] > 0 && table[3 * 13 + 8] > 0 && table[15 * 13 + 9] == 481. && table[12] == 66., 1);
+  double* id = malloc(HEP_RECTIFY_ROW_DOUBLES * sizeof(double));
+  EXPECT(hep_rectify_windows(cam, 1, one, 1, H, W, C, R, id), 0);
+  EXPECT(id[0] == 1. && id[4] == 1. && id[8] == 1. && id[1] == 0. && id[2] == 0. && id[5] == 0. && id[6] == 0., 1);
+  double* xy = malloc(2 * sizeof(double));
+  EXPECT(hep_rectified_point_to_frame(id, 255.5, 255.5, H, W, C, R, 512, xy), 0);
+  EXPECT(xy[0] == 320. + 127.5 && xy[1] == 124. + 127.5, 1);      /* the identity row: the centre crop's own pixel */
+  EXPECT(hep_window_from_box_rectified(table + 3 * 13, box, H, W, C, R, 512, &ox, &oy), 0);
+  EXPECT(ox >= 0 && ox <= W - C && oy >= 0 && oy <= H - C, 1);
+  EXPECT(hep_window_from_box_rectified(table, far_box, H, W, C, R, 512, &ox, &oy), 0);
+  EXPECT(ox >= 0 && ox <= W - C && oy >= 0 && oy <= H - C, 1);
+  REFUSED(hep_rectify_windows(NULL, 2, grid, 16, H, W, C, R, table), "camera is NULL");
+  REFUSED(hep_rectify_windows(cam, 2, grid, 16, H, W, C, R, NULL), "table_out is NULL");
+  REFUSED(hep_rectify_windows(cam, 2, grid, 0, H, W, C, R, table), "n must be >= 1");
+  REFUSED(hep_rectify_windows(cam, 1, grid, 16, H, W, C, R, table), "outside the frame");      /* the grid names frame 1: no camera row */
+  REFUSED(hep_rectify_windows(cam, 2, outside, 1, H, W, C, R, table), "outside the frame");
+  REFUSED(hep_rectify_windows(cam, 2, grid, 16, H + 1, W, C, R, table), "even");
+  cam[0] = 0.f;
+  REFUSED(hep_rectify_windows(cam, 2, grid, 16, H, W, C, R, table), "fx and fy must be finite and positive");
+  REFUSED(WINR(fake, yuv, 2, H, W, grid, 16, C, cam, found), "hep_pose_from_i420_windows_rectified: camera row 0: fx and fy must be finite and positive");
+  cam[0] = 480.f;
+  id[10] = -1.;
+  REFUSED(hep_rectified_point_to_frame(id, 1., 1., H, W, C, R, 512, xy), "fx and fy must be finite and positive");
+  REFUSED(hep_window_from_box_rectified(id, box, H, W, C, R, 512, &ox, &oy), "fx and fy must be finite and positive");
+  REFUSED(hep_rectified_point_to_frame(NULL, 1., 1., H, W, C, R, 512, xy), "row is NULL");
+  REFUSED(hep_window_from_box_rectified(table, box, H, W, C, R, 0, &ox, &oy), "size must be >= 1");
+  REFUSED(hep_preprocess_i420_rectified_device(fake, yuv, 1, H, W, grid, NULL, 1, C, R, f, NULL), "table is NULL");
+  REFUSED(hep_preprocess_i420_rectified_device(fake, yuv, 1, H, W, grid, table, 1, C, R, f, NULL), "n outside 1..max_batch");
+  REFUSED(hep_derotate_records_device(NULL, 1, table, 1, NULL), "records is NULL");
+  REFUSED(hep_derotate_records_device(rec, 1, NULL, 1, NULL), "table is NULL");
+  REFUSED(hep_derotate_records_device(rec, 64, table, 1, NULL), "slots outside 1..63");
+  REFUSED(WINR(NULL, yuv, 1, H, W, grid, 1, C, cam, found), "hep_pose_from_i420_windows_rectified: handle is NULL");
+  REFUSED(WINR(fake, yuv, 1, H, W, frame1, 1, C, cam, found), "outside the frame");
+  REFUSED(WINR(fake, yuv, 2, H, W, grid, 16, C, cam, found), "n outside 1..max_batch");
+  REFUSED(TILR(fake, yuv, 1, H, W, C, 4, 2, cam, found, NULL), "window is NULL");
+  REFUSED(TILR(fake, yuv, 1, H, W, C, 4, 2, cam, found, found), "hep_pose_from_i420_tiled_rectified: frames * nx * ny outside 1..max_batch");
+
+  free(fake); free(cam); free(f); free(found); free(yuv); free(rec); free(grid); free(wcam); free(table); free(id); free(xy);
   printf(failures ? "%d check(s) failed\n" : "all argument checks returned as documented\n", failures);
   return failures != 0;
 }
