@@ -1,9 +1,8 @@
 // hep_api.cpp - the session side of the C ABI of libhep.so (include/hep.h) and the forward executor:
 // eager stem launch (it reads the caller's input pointer) + one captured hipGraph for
-// everything behind it, replayed on the caller's stream.  The entry points that take no handle are in files of their
-// own: the evaluation and visualisation toolkit in hep_api_eval.cpp, the training side in hep_api_train.cpp.
-#include <float.h>
-#include <limits.h>
+// everything behind it, replayed on the caller's stream.  Frame to pose (top detection, the hep_pose(s)_from_* host calls, whole-frame
+// search) is in hep_api_pose.cpp.  The entry points that take no handle are in files of their own: the evaluation and visualisation
+// toolkit in hep_api_eval.cpp, the training side in hep_api_train.cpp.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,30 +20,7 @@ using namespace hep;
 
 thread_local std::string hep::g_err;      // the message behind hep_last_error(): the one definition (hep_api_util.h)
 
-struct hep_handle { Session s; };
-
 namespace hep {
-
-Session::~Session() {
-  if (!realised) return;            // planned on the host only (hep_plan_launch_list): no device object exists and no HIP call is made
-  for (auto& g : graphs) for (hipGraphExec_t ge : g.second) hipGraphExecDestroy(ge);
-  for (auto& lo : lane_ops) for (Op& o : lo) {
-    if (o.kind == OP_SEP) { hipFree((void*)o.sep.segs); hipFree((void*)o.sep.tile_seg); }
-    if (o.kind == OP_CHAIN) hipFree((void*)o.chain.nodes);
-  }
-  for (hipStream_t st : lane_streams) hipStreamDestroy(st);
-  for (hipEvent_t ev : lane_events) hipEventDestroy(ev);
-  if (fork_event) hipEventDestroy(fork_event);
-  if (pre_event) hipEventDestroy(pre_event);
-  hipFree(d_sync); hipFree(d_weights); hipFree(d_arena); hipFree(d_pre[0]); hipFree(d_pre[1]);
-  for (int i = 0; i < 5; i++) { hipFree(d_out[i]); hipFree(d_feat_nchw[i]); }
-  hipFree(d_in); hipFree(d_anchors); hipFree(d_tanchors); hipFree(d_boxes); hipFree(d_trans); hipFree(d_cam);
-  hipFree(d_keys); hipFree(d_det); hipFree(d_part);
-  for (int i = 0; i < 5; i++) hipFree(d_stage[i]);
-  hipFree(d_pose_in); hipFree(d_rec); hipHostFree(h_pose_in); hipHostFree(h_rec); hipFree(d_recs); hipHostFree(h_recs);
-  hipFree(d_best); hipHostFree(h_best);
-  if (stream) hipStreamDestroy(stream);
-}
 
 void launch_op(const Session& s, const Op& op, int batch, hipStream_t st, const float* in, const int64_t* strides) {
   switch (op.kind) {
@@ -415,19 +391,30 @@ int hep_preprocess_u8_device(hep_handle* h, const uint8_t* rgb_hwc, int batch, i
   return 0;
 } HEP_CATCH_INT
 
-// the frame geometry both I420 entry points refuse (host arithmetic only)
-static int check_i420(int height, int width, int crop, int resized) {
+}  // extern "C"
+
+namespace hep {      // the frame path, shared with hep_api_pose.cpp (declared in hep_host.h)
+
+// the frame geometry every I420 entry point refuses (host arithmetic only)
+int check_i420(int height, int width, int crop, int resized) {
   if (height < 2 || width < 2 || (height & 1) || (width & 1)) return fail(HEP_ERR_INVALID, "4:2:0 frames have even sides");
   if (crop < 1 || crop > height || crop > width || resized < 1) return fail(HEP_ERR_INVALID, "crop must fit the frame, resized must be positive");
   return 0;
+}
+// Program.cs:399-445 ResizeAndNormalizeMat on the square resized x resized frame: scale = (float)img_size / image_width, and the rows that
+// gives (*nh) have to fit the network size.  The host calls refuse it before any HIP call, the device entry points where the launch needs it.
+int check_fits(const Session& s, int resized, int* nh) {
+  const int rows = (int)((float)resized * ((float)s.size / (float)resized));
+  if (nh) *nh = rows;
+  return rows < 1 || rows > s.size ? fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size") : 0;
 }
 
 // the launches of the frame path on `st`; s.mu is held (the two scratch buffers belong to the handle)
 // windows (hep_preprocess_i420_windows_device): a device table [batch][3] {frame, ox, oy} - output image i is that window of the frames at `yuv`
 // in place of the centre crop of frame i; everything behind the first launch is the same
 // rect (hep_preprocess_i420_rectified_device): a device table [batch][HEP_RECTIFY_ROW_DOUBLES] next to `windows` - image i is the rectified window
-static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                                  float* out_hwc, hipStream_t st, const int32_t* windows = nullptr, const double* rect = nullptr) {
+int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
+                           float* out_hwc, hipStream_t st, const int32_t* windows, const double* rect) {
   // The scratch frames are used ASYNCHRONOUSLY on the caller's stream and the mutex only covers the enqueue: a second call on
   // another stream (an in-flight pool) must not overwrite them while the first call's kernels still read them.  An event is
   // recorded behind the last launch of every call and the next call's stream waits for it first (device-side, no host stall).
@@ -468,16 +455,17 @@ static int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int
   ResizeArgs r1; r1.in = s.d_pre[0]; r1.out = s.d_pre[1]; r1.B = batch; r1.H = crop; r1.W = crop; r1.nh = resized; r1.nw = resized; r1.S = resized; r1.norm = 0;
   r1.inv_scale_x = (double)crop / resized; r1.inv_scale_y = r1.inv_scale_x;
   launch_resize_u8(r1, st);
-  // Program.cs:399-445 ResizeAndNormalizeMat on the square resized x resized frame: scale = (float)img_size / image_width
-  const float scale = (float)s.size / (float)resized;
   ResizeArgs r2; r2.in = s.d_pre[1]; r2.out = out_hwc; r2.B = batch; r2.H = resized; r2.W = resized; r2.S = s.size; r2.norm = 1;
-  r2.nw = s.size; r2.nh = (int)((float)resized * scale);
-  if (r2.nh < 1 || r2.nh > s.size) return fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size");
+  r2.nw = s.size; CHECKED(check_fits(s, resized, &r2.nh));
   r2.inv_scale_x = (double)resized / r2.nw; r2.inv_scale_y = (double)resized / r2.nh;
   launch_resize_u8(r2, st);
   HIPRET(hipGetLastError());
   return 0;
 }
+
+}  // namespace hep
+
+extern "C" {
 
 int hep_preprocess_i420_device(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
                                float* out_hwc, void* stream) try {
@@ -660,533 +648,6 @@ int hep_filter(hep_handle* h, const float* boxes, const float* classification, c
   HIPRET(hipMemcpyAsync(det_count, ct_, (size_t)batch * 4, hipMemcpyDeviceToHost, s.stream));
   HIPRET(hipStreamSynchronize(s.stream));
   return 0;
-} HEP_CATCH_INT
-
-// ---- top detection / frame to pose ----
-static int top1_locked(Session& s, const float* regression, const float* classification, const float* rotation,
-                       const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
-                       uint32_t* records, hipStream_t st, bool per_label = false) {
-  Top1Args a;
-  a.regression = regression ? regression : s.d_out[0];         // NULL = the handle's own last outputs
-  a.scores = classification ? classification : s.d_out[1];
-  a.rotation = rotation ? rotation : s.d_out[2];
-  a.translation_raw = translation_raw ? translation_raw : s.d_out[3];
-  a.hand = hand ? hand : s.d_out[4];
-  a.camera = camera; a.anchors = s.d_anchors; a.t_anchors = s.d_tanchors;
-  a.B = batch; a.N = s.num_anchors; a.K = s.num_classes; a.any_class = s.class_specific_filter ? 0 : 1;
-  a.score_thr = score_threshold; a.clip_max = (float)(s.size - 1);
-  a.records = records;                                         // per_label: [batch][num_classes] records, class-specific whatever the handle's mode
-  if (per_label) launch_toplabel(a, st); else launch_top1(a, st);
-  HIPRET(hipGetLastError());
-  return 0;
-}
-
-// the body of hep_top1_device and hep_top_labels_device: `who` is the prefix of the entry point's messages
-static int top_device(const char* who, bool per_label, hep_handle* h, const float* regression, const float* classification, const float* rotation,
-                      const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
-                      uint32_t* records, void* stream) {
-  const Check c{who};
-  CHECKED(c.ptrs({{h, "handle"}, {camera, "camera"}, {records, "records"}}));      // (the handle is not read before the pointers are checked)
-  Session& s = h->s; CHECKED(c.range("batch", batch, 1, s.max_batch, HEP_ERR_INVALID, "max_batch"));
-  std::lock_guard<std::mutex> lk(s.mu);
-  HIPRET(hipSetDevice(s.device));
-  return top1_locked(s, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, (hipStream_t)stream, per_label);
-}
-
-int hep_top1_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
-                    const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
-                    uint32_t* records, void* stream) try {
-  return top_device("hep_top1_device: ", false, h, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, stream);
-} HEP_CATCH_INT
-
-int hep_top_labels_device(hep_handle* h, const float* regression, const float* classification, const float* rotation,
-                          const float* translation_raw, const float* hand, const float* camera, int batch, float score_threshold,
-                          uint32_t* records, void* stream) try {
-  return top_device("hep_top_labels_device: ", true, h, regression, classification, rotation, translation_raw, hand, camera, batch, score_threshold, records, stream);
-} HEP_CATCH_INT
-
-namespace {
-struct PoseOut { int32_t* found; float* scores; int32_t* labels; int32_t* index; float* boxes; float* rotation; float* translation; float* hand; };
-constexpr size_t kRecBytes = (size_t)HEP_POSE_RECORD_WORDS * 4;
-static_assert(HEP_POSE_RECORD_WORDS == POSE_RECORD_WORDS, "the record of include/hep.h is the kernel's");
-}  // namespace
-
-// what the host entry points refuse first, without reading the handle: NULL pointers and a batch below 1 (check_pose); then, behind the frame
-// geometry where there is one, the batch against the handle's max_batch (check_pose_batch)
-static int check_pose_batch(const Check& c, int batch, int most) { return c.range("batch", batch, 1, most, HEP_ERR_INVALID, "max_batch given to hep_create"); }
-static int check_pose(const Check& c, const hep_handle* h, const void* input, const char* input_name, int batch, const float* camera, const int32_t* found) {
-  CHECKED(c.ptrs({{h, "handle"}, {input, input_name}, {camera, "camera"}, {found, "found"}}));
-  return check_pose_batch(c, batch, INT_MAX);
-}
-
-// Staging of one call: [camera rows, padded to cam_pad bytes | payload] on the device.  Direct (the default): two hipMemcpyAsync from
-// the caller's pageable memory.  Pinned (HEP_POSE_UPLOAD=pinned, kept for the A/B of tools/pose_call_time.py): camera and payload are
-// copied into a pinned buffer of the handle and go up as ONE hipMemcpyAsync.  Measured twice (NOTEBOOK.md section 24): the 3 MB float
-// blob is 0.05 ms faster direct (the host copy into the pinned buffer costs more than the runtime's own staging), the 1.4 MB frame
-// 0.02 ms faster back to back and level at 60 Hz.  Buffers are sized for max_batch payloads of this call's per-image size and only
-// ever grown: a repeated shape allocates nothing.
-static size_t pose_cam_pad(const Session& s) { return ((size_t)s.max_batch * 24 + 255) & ~(size_t)255; }
-// the buffers of a call that stages `need` bytes
-static int pose_reserve(Session& s, size_t need) {
-  if (!s.d_rec) {
-    const char* e = getenv("HEP_POSE_UPLOAD");
-    s.pose_upload_pinned = e && !strcmp(e, "pinned");
-    HIPRET(hipMalloc((void**)&s.d_rec, kRecBytes * s.max_batch));
-  }
-  const bool direct = !s.pose_upload_pinned;
-  if (!s.h_rec) HIPRET(hipHostMalloc((void**)&s.h_rec, kRecBytes * s.max_batch, hipHostMallocDefault));
-  if (s.pose_in_bytes < need) {
-    HIPRET(hipStreamSynchronize(s.stream));
-    hipFree(s.d_pose_in); s.d_pose_in = nullptr; s.pose_in_bytes = 0;
-    HIPRET(hipMalloc((void**)&s.d_pose_in, need)); s.pose_in_bytes = need;
-  }
-  if (!direct && s.pose_pin_bytes < need) {
-    HIPRET(hipStreamSynchronize(s.stream));
-    hipHostFree(s.h_pose_in); s.h_pose_in = nullptr; s.pose_pin_bytes = 0;
-    HIPRET(hipHostMalloc((void**)&s.h_pose_in, need, hipHostMallocDefault)); s.pose_pin_bytes = need;
-  }
-  return 0;
-}
-static int pose_stage(Session& s, const void* payload, size_t per_image, int batch, const float* camera) {
-  const size_t pad = pose_cam_pad(s);
-  if (int rc = pose_reserve(s, pad + per_image * (size_t)s.max_batch)) return rc;
-  const bool direct = !s.pose_upload_pinned;
-  const size_t bytes = per_image * (size_t)batch;
-  if (direct) {
-    HIPRET(hipMemcpyAsync(s.d_pose_in, camera, (size_t)batch * 24, hipMemcpyHostToDevice, s.stream));
-    HIPRET(hipMemcpyAsync(s.d_pose_in + pad, payload, bytes, hipMemcpyHostToDevice, s.stream));
-  } else {
-    memcpy(s.h_pose_in, camera, (size_t)batch * 24);
-    memcpy(s.h_pose_in + pad, payload, bytes);
-    HIPRET(hipMemcpyAsync(s.d_pose_in, s.h_pose_in, pad + bytes, hipMemcpyHostToDevice, s.stream));
-  }
-  return 0;
-}
-
-// the handle's buffers for num_classes records per image (hep_poses_from_*): allocated at the first such call for max_batch images - the
-// size never changes for a handle, so nothing is allocated or freed afterwards
-static int poses_buffers(Session& s) {
-  const size_t need = kRecBytes * s.max_batch * s.num_classes;
-  if (!s.d_recs) HIPRET(hipMalloc((void**)&s.d_recs, need));
-  if (!s.h_recs) HIPRET(hipHostMalloc((void**)&s.h_recs, need, hipHostMallocDefault));
-  return 0;
-}
-
-// the records of a download -> the caller's arrays, row by row
-static void pose_scatter(const uint32_t* hr, int rows, const PoseOut& o) {
-  for (int b = 0; b < rows; b++) {
-    const uint32_t* r = hr + (size_t)b * HEP_POSE_RECORD_WORDS;
-    memcpy(&o.found[b], r + 0, 4);
-    if (o.labels) memcpy(&o.labels[b], r + 1, 4);
-    if (o.index) memcpy(&o.index[b], r + 2, 4);
-    if (o.scores) memcpy(&o.scores[b], r + 4, 4);
-    if (o.boxes) memcpy(o.boxes + (size_t)b * 4, r + 5, 16);
-    if (o.rotation) memcpy(o.rotation + (size_t)b * 3, r + 9, 12);
-    if (o.translation) memcpy(o.translation + (size_t)b * 3, r + 12, 12);
-    if (o.hand) memcpy(o.hand + (size_t)b * 63, r + 15, 63 * 4);
-  }
-}
-
-// top-detection launch on the handle's own head outputs, the records back through the pinned buffer, synchronise, scatter.
-// per_label (hep_poses_from_*): the launch of hep_top_labels_device, num_classes records per image, output row b * num_classes + c
-static int pose_finish(Session& s, int batch, float score_threshold, const PoseOut& o, bool per_label) {
-  uint32_t* d = per_label ? s.d_recs : s.d_rec;
-  uint32_t* hr = per_label ? s.h_recs : s.h_rec;
-  const int rows = per_label ? batch * s.num_classes : batch;
-  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, batch, score_threshold, d, s.stream, per_label)) return rc;
-  HIPRET(hipMemcpyAsync(hr, d, kRecBytes * rows, hipMemcpyDeviceToHost, s.stream));
-  HIPRET(hipStreamSynchronize(s.stream));
-  pose_scatter(hr, rows, o);
-  return 0;
-}
-
-// the bodies of hep_pose_from_input / hep_poses_from_input and of hep_pose_from_i420 / hep_poses_from_i420: `who` is the prefix of the entry point's messages
-static int pose_from_input(const char* who, bool per_label, hep_handle* h, const float* input_nchw, int batch, const float* camera,
-                           float score_threshold, const PoseOut& o) {
-  const Check c{who};
-  CHECKED(check_pose(c, h, input_nchw, "input_nchw", batch, camera, o.found)); CHECKED(check_pose_batch(c, batch, h->s.max_batch));
-  Session& s = h->s;
-  std::lock_guard<std::mutex> lk(s.mu);
-  HIPRET(hipSetDevice(s.device));
-  if (per_label) if (int rc = poses_buffers(s)) return rc;
-  if (int rc = pose_stage(s, input_nchw, (size_t)3 * s.size * s.size * 4, batch, camera)) return rc;
-  std::string err;
-  if (int rc = run_forward(&s, (const float*)(s.d_pose_in + pose_cam_pad(s)), nullptr, batch, s.stream, &err)) return fail(rc, err);
-  return pose_finish(s, batch, score_threshold, o, per_label);
-}
-static int pose_from_i420(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop,
-                          int resized, const float* camera, float score_threshold, const PoseOut& o) {
-  const Check c{who};
-  CHECKED(check_pose(c, h, yuv, "yuv", batch, camera, o.found)); CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_pose_batch(c, batch, h->s.max_batch));
-  Session& s = h->s;
-  {   // ResizeAndNormalizeMat's row count (preprocess_i420_locked computes the same): refused here, before any HIP call
-    const int nh = (int)((float)resized * ((float)s.size / (float)resized));
-    if (nh < 1 || nh > s.size) return fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size");
-  }
-  std::lock_guard<std::mutex> lk(s.mu);
-  HIPRET(hipSetDevice(s.device));
-  const size_t in_floats = (size_t)3 * s.size * s.size;
-  if (!s.d_in) HIPRET(hipMalloc((void**)&s.d_in, in_floats * s.max_batch * 4));
-  if (per_label) if (int rc = poses_buffers(s)) return rc;
-  if (int rc = pose_stage(s, yuv, (size_t)height * width * 3 / 2, batch, camera)) return rc;
-  if (int rc = preprocess_i420_locked(s, s.d_pose_in + pose_cam_pad(s), batch, height, width, crop, resized, s.d_in, s.stream)) return rc;
-  const int64_t S = s.size; const int64_t nhwc[4] = {3 * S * S, 1, 3 * S, 3};      // the NCHW view of the [batch,S,S,3] frames
-  std::string err;
-  if (int rc = run_forward(&s, s.d_in, nhwc, batch, s.stream, &err)) return fail(rc, err);
-  return pose_finish(s, batch, score_threshold, o, per_label);
-}
-
-int hep_pose_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
-                        int32_t* found, float* scores, int32_t* labels, int32_t* index, float* boxes, float* rotation,
-                        float* translation, float* hand) try {
-  return pose_from_input("hep_pose_from_input: ", false, h, input_nchw, batch, camera, score_threshold,
-                         PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-int hep_pose_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
-                       int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
-  return pose_from_i420("hep_pose_from_i420: ", false, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
-                        PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-// several objects: [batch][num_classes] rows per output, slot c = label c (no labels array)
-int hep_poses_from_input(hep_handle* h, const float* input_nchw, int batch, const float* camera, float score_threshold,
-                         int32_t* found, float* scores, int32_t* index, float* boxes, float* rotation, float* translation,
-                         float* hand) try {
-  return pose_from_input("hep_poses_from_input: ", true, h, input_nchw, batch, camera, score_threshold,
-                         PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-int hep_poses_from_i420(hep_handle* h, const uint8_t* yuv, int batch, int height, int width, int crop, int resized,
-                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
-                        float* rotation, float* translation, float* hand) try {
-  return pose_from_i420("hep_poses_from_i420: ", true, h, yuv, batch, height, width, crop, resized, camera, score_threshold,
-                        PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-// ---- whole-frame search: windows of a frame, best of the windows (include/hep.h) ----
-// a grid offset along one axis: span = side - crop; one cell sits at the centre (the frame path's crop), several reach both borders
-static int tile_offset(int i, int cells, int span) { return cells == 1 ? span / 2 : (int)(((int64_t)i * span) / (cells - 1)); }
-static void tile_windows(int height, int width, int crop, int nx, int ny, int frames, int32_t* w) {
-  for (int f = 0; f < frames; f++)
-    for (int r = 0; r < ny; r++)
-      for (int i = 0; i < nx; i++, w += 3) { w[0] = f; w[1] = tile_offset(i, nx, width - crop); w[2] = tile_offset(r, ny, height - crop); }
-}
-// camera row of window {frame, ox, oy}: the frame's row with the principal point moved by the window's offset from the centre crop, in pixels
-// of the resized image; every rounding stated (tests/_windows.py restates it)
-static void window_camera(const float* camera, const int32_t* w, int height, int width, int crop, int resized, float* out) {
-  const float* row = camera + (size_t)w[0] * 6;
-  memcpy(out, row, 24);
-  out[2] = (float)((double)row[2] - (double)(w[1] - (width - crop) / 2) * (double)resized / (double)crop);
-  out[3] = (float)((double)row[3] - (double)(w[2] - (height - crop) / 2) * (double)resized / (double)crop);
-}
-// a host table: every window inside its frame; frames < 0: the frame index has no upper limit to hold (hep_window_cameras)
-static int check_windows(const Check& c, const int32_t* windows, int n, int frames, int height, int width, int crop) {
-  for (int i = 0; i < n; i++) {
-    const int32_t* w = windows + (size_t)i * 3;
-    if (w[0] < 0 || (frames >= 0 && w[0] >= frames) || w[1] < 0 || w[1] > width - crop || w[2] < 0 || w[2] > height - crop)
-      return c.fail(HEP_ERR_INVALID, "window " + std::to_string(i) + " {" + std::to_string(w[0]) + ", " + std::to_string(w[1]) + ", " + std::to_string(w[2]) +
-                                     "} lies outside the frame (frame index or offsets)");
-  }
-  return 0;
-}
-
-int hep_tile_windows(int height, int width, int crop, int nx, int ny, int frames, int32_t* windows_out) try {
-  const Check c{"hep_tile_windows: "};
-  CHECKED(c.ptrs({{windows_out, "windows_out"}}));
-  CHECKED(c.at_least("nx", nx, 1)); CHECKED(c.at_least("ny", ny, 1)); CHECKED(c.at_least("frames", frames, 1));
-  CHECKED(check_i420(height, width, crop, 1));
-  tile_windows(height, width, crop, nx, ny, frames, windows_out);
-  return 0;
-} HEP_CATCH_INT
-
-int hep_window_cameras(const float* camera, const int32_t* windows, int n, int height, int width, int crop, int resized, float* camera_out) try {
-  const Check c{"hep_window_cameras: "};
-  CHECKED(c.ptrs({{camera, "camera"}, {windows, "windows"}, {camera_out, "camera_out"}}));
-  CHECKED(c.at_least("n", n, 1)); CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_windows(c, windows, n, -1, height, width, crop));
-  for (int i = 0; i < n; i++) window_camera(camera, windows + (size_t)i * 3, height, width, crop, resized, camera_out + (size_t)i * 6);
-  return 0;
-} HEP_CATCH_INT
-
-int hep_window_from_box(const float* box, int ox, int oy, int height, int width, int crop, int size, int32_t* ox_out, int32_t* oy_out) try {
-  const Check c{"hep_window_from_box: "};
-  CHECKED(c.ptrs({{box, "box"}, {ox_out, "ox_out"}, {oy_out, "oy_out"}}));
-  CHECKED(check_i420(height, width, crop, 1)); CHECKED(c.at_least("size", size, 1));
-  const int32_t w[3] = {0, ox, oy};
-  CHECKED(check_windows(c, w, 1, 1, height, width, crop));
-  // the centre of the box in frame pixels, then the window around it, kept inside the frame (compared in double: no cast of a value an int cannot hold)
-  auto around = [&](int o, float lo, float hi, int side) {
-    const double centre = (double)o + 0.5 * ((double)lo + (double)hi) * (double)crop / (double)size;
-    const double v = floor(centre - 0.5 * (double)crop + 0.5);
-    return !(v > 0.0) ? 0 : (v > (double)(side - crop) ? side - crop : (int)v);
-  };
-  *ox_out = around(ox, box[0], box[2], width); *oy_out = around(oy, box[1], box[3], height);
-  return 0;
-} HEP_CATCH_INT
-
-int hep_best_window_device(const uint32_t* records, int slots, const int32_t* windows, int n, int frames, uint32_t* out_records,
-                           int32_t* out_window, void* stream) try {
-  const Check c{"hep_best_window_device: "};
-  CHECKED(c.ptrs({{records, "records"}, {windows, "windows"}, {out_records, "out_records"}, {out_window, "out_window"}}));
-  CHECKED(c.range("slots", slots, 1, 63)); CHECKED(c.at_least("n", n, 1)); CHECKED(c.range("frames", frames, 1, INT_MAX / 64));
-  BestWindowArgs a; a.records = records; a.windows = windows; a.out_records = out_records; a.out_window = out_window; a.n = n; a.slots = slots; a.frames = frames;
-  launch_best_window(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// rectified windows: the host arithmetic is hep_rectify.cpp's (built without contraction), the checks are here
-static_assert(HEP_RECTIFY_ROW_DOUBLES == RECTIFY_ROW_DOUBLES, "the table row of include/hep.h and of the kernels");
-// every window's frame has a camera row whose focal lengths are finite and positive
-static int check_rectify_camera(const Check& c, const float* camera, const int32_t* windows, int n) {
-  for (int i = 0; i < n; i++) {
-    const float* row = camera + (size_t)windows[(size_t)i * 3] * 6;
-    if (!(row[0] > 0.f && row[0] <= FLT_MAX && row[1] > 0.f && row[1] <= FLT_MAX))
-      return c.fail(HEP_ERR_INVALID, "camera row " + std::to_string(windows[(size_t)i * 3]) + ": fx and fy must be finite and positive");
-  }
-  return 0;
-}
-static int check_rectify_row(const Check& c, const double* row) {
-  return row[9] > 0.0 && row[9] <= DBL_MAX && row[10] > 0.0 && row[10] <= DBL_MAX ? 0 : c.fail(HEP_ERR_INVALID, "row: fx and fy must be finite and positive");
-}
-
-int hep_rectify_windows(const float* camera, int frames, const int32_t* windows, int n, int height, int width, int crop, int resized,
-                        double* table_out) try {
-  const Check c{"hep_rectify_windows: "};
-  CHECKED(c.ptrs({{camera, "camera"}, {windows, "windows"}, {table_out, "table_out"}}));
-  CHECKED(c.at_least("frames", frames, 1)); CHECKED(c.at_least("n", n, 1)); CHECKED(check_i420(height, width, crop, resized));
-  CHECKED(check_windows(c, windows, n, frames, height, width, crop)); CHECKED(check_rectify_camera(c, camera, windows, n));
-  for (int i = 0; i < n; i++)
-    rectify_row(camera + (size_t)windows[(size_t)i * 3] * 6, windows + (size_t)i * 3, height, width, crop, resized, table_out + (size_t)i * HEP_RECTIFY_ROW_DOUBLES);
-  return 0;
-} HEP_CATCH_INT
-
-int hep_rectified_point_to_frame(const double* row, double x, double y, int height, int width, int crop, int resized, int size, double* xy_out) try {
-  const Check c{"hep_rectified_point_to_frame: "};
-  CHECKED(c.ptrs({{row, "row"}, {xy_out, "xy_out"}}));
-  CHECKED(check_i420(height, width, crop, resized)); CHECKED(c.at_least("size", size, 1)); CHECKED(check_rectify_row(c, row));
-  rectified_point(row, x, y, height, width, crop, resized, size, xy_out);
-  return 0;
-} HEP_CATCH_INT
-
-int hep_window_from_box_rectified(const double* row, const float* box, int height, int width, int crop, int resized, int size, int32_t* ox_out,
-                                  int32_t* oy_out) try {
-  const Check c{"hep_window_from_box_rectified: "};
-  CHECKED(c.ptrs({{row, "row"}, {box, "box"}, {ox_out, "ox_out"}, {oy_out, "oy_out"}}));
-  CHECKED(check_i420(height, width, crop, resized)); CHECKED(c.at_least("size", size, 1)); CHECKED(check_rectify_row(c, row));
-  double xy[2];
-  rectified_point(row, 0.5 * ((double)box[0] + (double)box[2]), 0.5 * ((double)box[1] + (double)box[3]), height, width, crop, resized, size, xy);
-  // the window around that frame position, kept inside the frame as hep_window_from_box keeps it (a NaN - a ray that points backwards - gives 0)
-  auto around = [&](double centre, int side) {
-    const double v = floor(centre - 0.5 * (double)crop + 0.5);
-    return !(v > 0.0) ? 0 : (v > (double)(side - crop) ? side - crop : (int)v);
-  };
-  *ox_out = around(xy[0], width); *oy_out = around(xy[1], height);
-  return 0;
-} HEP_CATCH_INT
-
-int hep_derotate_records_device(uint32_t* records, int slots, const double* table, int n, void* stream) try {
-  const Check c{"hep_derotate_records_device: "};
-  CHECKED(c.ptrs({{records, "records"}, {table, "table"}}));
-  CHECKED(c.range("slots", slots, 1, 63)); CHECKED(c.range("n", n, 1, INT_MAX / 64));
-  DerotateArgs a; a.records = records; a.table = table; a.n = n; a.slots = slots;
-  launch_derotate_records(a, (hipStream_t)stream);
-  HIPRET(hipGetLastError());
-  return 0;
-} HEP_CATCH_INT
-
-// the handle's buffers for the winners of hep_pose(s)_from_i420_tiled: records and window indices of max_batch x num_classes rows, one size for both calls
-static int best_buffers(Session& s) {
-  const size_t need = (kRecBytes + 4) * s.max_batch * s.num_classes;
-  if (!s.d_best) HIPRET(hipMalloc((void**)&s.d_best, need));
-  if (!s.h_best) HIPRET(hipHostMalloc((void**)&s.h_best, need, hipHostMallocDefault));
-  return 0;
-}
-
-// The body of the windowed host calls; every argument has been checked and s.mu is held.  Staging: [camera rows of the windows, padded | table,
-// padded | frames] in the buffer hep_pose_from_i420 stages in, sized for max_batch frames of this geometry and only ever grown; then the
-// windowed preprocess, one forward at batch n and the top-detection launch.  window_out == NULL: the n (x num_classes) records come back as
-// they are.  Otherwise the best-of-windows launch follows and `frames` (x num_classes) winners with their window indices come back in one copy.
-// rect != NULL (the *_rectified calls): the host table [n][HEP_RECTIFY_ROW_DOUBLES] goes up between the window table and the frames, the
-// rectified preprocess takes the place of the windowed one, `camera` holds every window's frame's CENTRE row and the back-rotation launch
-// follows the top-detection launch.
-static int pose_from_windows_locked(Session& s, bool per_label, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n,
-                                    int crop, int resized, const float* camera, float score_threshold, const PoseOut& o, int32_t* window_out,
-                                    const double* rect = nullptr) {
-  HIPRET(hipSetDevice(s.device));
-  const size_t in_floats = (size_t)3 * s.size * s.size;
-  if (!s.d_in) HIPRET(hipMalloc((void**)&s.d_in, in_floats * s.max_batch * 4));
-  if (per_label) if (int rc = poses_buffers(s)) return rc;
-  if (window_out) if (int rc = best_buffers(s)) return rc;
-  const size_t pad = pose_cam_pad(s), tpad = ((size_t)s.max_batch * 12 + 255) & ~(size_t)255, per_frame = (size_t)height * width * 3 / 2;
-  const size_t row_bytes = HEP_RECTIFY_ROW_DOUBLES * sizeof(double), rpad = rect ? ((size_t)s.max_batch * row_bytes + 255) & ~(size_t)255 : 0;
-  if (int rc = pose_reserve(s, pad + tpad + rpad + per_frame * (size_t)s.max_batch)) return rc;
-  if (!s.pose_upload_pinned) {
-    HIPRET(hipMemcpyAsync(s.d_pose_in, camera, (size_t)n * 24, hipMemcpyHostToDevice, s.stream));
-    HIPRET(hipMemcpyAsync(s.d_pose_in + pad, windows, (size_t)n * 12, hipMemcpyHostToDevice, s.stream));
-    if (rect) HIPRET(hipMemcpyAsync(s.d_pose_in + pad + tpad, rect, (size_t)n * row_bytes, hipMemcpyHostToDevice, s.stream));
-    HIPRET(hipMemcpyAsync(s.d_pose_in + pad + tpad + rpad, yuv, per_frame * frames, hipMemcpyHostToDevice, s.stream));
-  } else {
-    memcpy(s.h_pose_in, camera, (size_t)n * 24);
-    memcpy(s.h_pose_in + pad, windows, (size_t)n * 12);
-    if (rect) memcpy(s.h_pose_in + pad + tpad, rect, (size_t)n * row_bytes);
-    memcpy(s.h_pose_in + pad + tpad + rpad, yuv, per_frame * frames);
-    HIPRET(hipMemcpyAsync(s.d_pose_in, s.h_pose_in, pad + tpad + rpad + per_frame * frames, hipMemcpyHostToDevice, s.stream));
-  }
-  const int32_t* d_table = (const int32_t*)(s.d_pose_in + pad);
-  const double* d_rect = rect ? (const double*)(s.d_pose_in + pad + tpad) : nullptr;      // (256-byte aligned)
-  if (int rc = preprocess_i420_locked(s, s.d_pose_in + pad + tpad + rpad, n, height, width, crop, resized, s.d_in, s.stream, d_table, d_rect)) return rc;
-  const int64_t S = s.size; const int64_t nhwc[4] = {3 * S * S, 1, 3 * S, 3};      // the NCHW view of the [n,S,S,3] windows
-  std::string err;
-  if (int rc = run_forward(&s, s.d_in, nhwc, n, s.stream, &err)) return fail(rc, err);
-  if (!window_out && !rect) return pose_finish(s, n, score_threshold, o, per_label);
-  uint32_t* d = per_label ? s.d_recs : s.d_rec;
-  if (int rc = top1_locked(s, nullptr, nullptr, nullptr, nullptr, nullptr, (const float*)s.d_pose_in, n, score_threshold, d, s.stream, per_label)) return rc;
-  const int slots = per_label ? s.num_classes : 1, rows = frames * slots;
-  if (rect) {
-    DerotateArgs da; da.records = d; da.table = d_rect; da.n = n; da.slots = slots;
-    launch_derotate_records(da, s.stream);
-    HIPRET(hipGetLastError());
-  }
-  if (!window_out) {                                  // the rectified windows call: the n (x num_classes) back-rotated records as they are
-    uint32_t* hr = per_label ? s.h_recs : s.h_rec;
-    HIPRET(hipMemcpyAsync(hr, d, kRecBytes * n * slots, hipMemcpyDeviceToHost, s.stream));
-    HIPRET(hipStreamSynchronize(s.stream));
-    pose_scatter(hr, n * slots, o);
-    return 0;
-  }
-  BestWindowArgs a; a.records = d; a.windows = d_table; a.out_records = s.d_best; a.out_window = (int32_t*)(s.d_best + (size_t)rows * HEP_POSE_RECORD_WORDS);
-  a.n = n; a.slots = slots; a.frames = frames;
-  launch_best_window(a, s.stream);
-  HIPRET(hipGetLastError());
-  HIPRET(hipMemcpyAsync(s.h_best, s.d_best, (kRecBytes + 4) * rows, hipMemcpyDeviceToHost, s.stream));
-  HIPRET(hipStreamSynchronize(s.stream));
-  pose_scatter(s.h_best, rows, o);
-  memcpy(window_out, s.h_best + (size_t)rows * HEP_POSE_RECORD_WORDS, (size_t)rows * 4);
-  return 0;
-}
-// ResizeAndNormalizeMat's row count (preprocess_i420_locked computes the same): refused before any HIP call
-static int check_fits(const Session& s, int resized) {
-  const int nh = (int)((float)resized * ((float)s.size / (float)resized));
-  return nh < 1 || nh > s.size ? fail(HEP_ERR_UNSUPPORTED, "preprocess: resized frame does not fit the network size") : 0;
-}
-
-// the host tables of the tiled and of the rectified calls, built under the mutex: sized once, max_batch rows
-static void win_buffers(Session& s) {
-  if (s.win_table.empty()) { s.win_table.resize((size_t)s.max_batch * 3); s.win_cam.resize((size_t)s.max_batch * 6); s.win_rect.resize((size_t)s.max_batch * HEP_RECTIFY_ROW_DOUBLES); }
-}
-// the rectified calls' host side: s.win_cam = every window's frame's centre row as it is, s.win_rect = the table of hep_rectify_windows
-static void rectify_tables(Session& s, const float* camera, const int32_t* windows, int n, int height, int width, int crop, int resized) {
-  for (int i = 0; i < n; i++) {
-    const float* row = camera + (size_t)windows[(size_t)i * 3] * 6;
-    memcpy(s.win_cam.data() + (size_t)i * 6, row, 24);
-    rectify_row(row, windows + (size_t)i * 3, height, width, crop, resized, s.win_rect.data() + (size_t)i * HEP_RECTIFY_ROW_DOUBLES);
-  }
-}
-
-// rectified: camera is [frames,6], the centre rows
-static int pose_from_i420_windows(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int frames, int height, int width,
-                                  const int32_t* windows, int n, int crop, int resized, const float* camera, float score_threshold, const PoseOut& o,
-                                  bool rectified = false) {
-  const Check c{who};
-  CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {windows, "windows"}, {camera, "camera"}, {o.found, "found"}}));
-  CHECKED(c.range("n", n, 1, INT_MAX, HEP_ERR_INVALID, "max_batch given to hep_create")); CHECKED(c.at_least("frames", frames, 1));
-  CHECKED(check_i420(height, width, crop, resized)); CHECKED(check_windows(c, windows, n, frames, height, width, crop));
-  if (rectified) CHECKED(check_rectify_camera(c, camera, windows, n));
-  Session& s = h->s;      // (the handle is read from here on)
-  CHECKED(c.range("n", n, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create"));
-  CHECKED(c.range("frames", frames, 1, s.max_batch, HEP_ERR_INVALID, "max_batch given to hep_create")); CHECKED(check_fits(s, resized));
-  std::lock_guard<std::mutex> lk(s.mu);
-  if (rectified) {
-    win_buffers(s);
-    rectify_tables(s, camera, windows, n, height, width, crop, resized);
-    return pose_from_windows_locked(s, per_label, yuv, frames, height, width, windows, n, crop, resized, s.win_cam.data(), score_threshold, o, nullptr, s.win_rect.data());
-  }
-  return pose_from_windows_locked(s, per_label, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold, o, nullptr);
-}
-
-static int pose_from_i420_tiled(const char* who, bool per_label, hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop,
-                                int resized, int nx, int ny, const float* camera, float score_threshold, const PoseOut& o, int32_t* window,
-                                bool rectified = false) {
-  const Check c{who};
-  CHECKED(c.ptrs({{h, "handle"}, {yuv, "yuv"}, {camera, "camera"}, {o.found, "found"}, {window, "window"}}));
-  CHECKED(c.at_least("nx", nx, 1)); CHECKED(c.at_least("ny", ny, 1)); CHECKED(c.at_least("frames", frames, 1));
-  CHECKED(check_i420(height, width, crop, resized));
-  Session& s = h->s;      // (the handle is read from here on)
-  int64_t n = (int64_t)nx * ny;                     // (two factors at a time: neither product can pass int64)
-  if (n <= s.max_batch) n *= frames;
-  if (n > s.max_batch) return c.fail(HEP_ERR_INVALID, "frames * nx * ny outside 1..max_batch given to hep_create");
-  CHECKED(check_fits(s, resized));
-  if (rectified)
-    for (int f = 0; f < frames; f++) { const int32_t w[3] = {f, 0, 0}; CHECKED(check_rectify_camera(c, camera, w, 1)); }
-  std::lock_guard<std::mutex> lk(s.mu);
-  win_buffers(s);
-  tile_windows(height, width, crop, nx, ny, frames, s.win_table.data());
-  if (rectified) {
-    rectify_tables(s, camera, s.win_table.data(), (int)n, height, width, crop, resized);
-    return pose_from_windows_locked(s, per_label, yuv, frames, height, width, s.win_table.data(), (int)n, crop, resized, s.win_cam.data(), score_threshold, o, window,
-                                    s.win_rect.data());
-  }
-  for (int i = 0; i < (int)n; i++) window_camera(camera, s.win_table.data() + (size_t)i * 3, height, width, crop, resized, s.win_cam.data() + (size_t)i * 6);
-  return pose_from_windows_locked(s, per_label, yuv, frames, height, width, s.win_table.data(), (int)n, crop, resized, s.win_cam.data(), score_threshold, o, window);
-}
-
-int hep_pose_from_i420_windows(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
-                               int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
-                               int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
-  return pose_from_i420_windows("hep_pose_from_i420_windows: ", false, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
-                                PoseOut{found, scores, labels, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-int hep_poses_from_i420_windows(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
-                                int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index,
-                                float* boxes, float* rotation, float* translation, float* hand) try {
-  return pose_from_i420_windows("hep_poses_from_i420_windows: ", true, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
-                                PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand});
-} HEP_CATCH_INT
-
-int hep_pose_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
-                             const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels, int32_t* index,
-                             float* boxes, float* rotation, float* translation, float* hand, int32_t* window) try {
-  return pose_from_i420_tiled("hep_pose_from_i420_tiled: ", false, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
-                              PoseOut{found, scores, labels, index, boxes, rotation, translation, hand}, window);
-} HEP_CATCH_INT
-
-int hep_poses_from_i420_tiled(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
-                              const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
-                              float* rotation, float* translation, float* hand, int32_t* window) try {
-  return pose_from_i420_tiled("hep_poses_from_i420_tiled: ", true, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
-                              PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, window);
-} HEP_CATCH_INT
-
-// the rectified forms of the four calls above (include/hep.h): camera is [frames,6], the centre rows, for all four
-int hep_pose_from_i420_windows_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
-                                         int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels,
-                                         int32_t* index, float* boxes, float* rotation, float* translation, float* hand) try {
-  return pose_from_i420_windows("hep_pose_from_i420_windows_rectified: ", false, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
-                                PoseOut{found, scores, labels, index, boxes, rotation, translation, hand}, true);
-} HEP_CATCH_INT
-
-int hep_poses_from_i420_windows_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, const int32_t* windows, int n, int crop,
-                                          int resized, const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index,
-                                          float* boxes, float* rotation, float* translation, float* hand) try {
-  return pose_from_i420_windows("hep_poses_from_i420_windows_rectified: ", true, h, yuv, frames, height, width, windows, n, crop, resized, camera, score_threshold,
-                                PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, true);
-} HEP_CATCH_INT
-
-int hep_pose_from_i420_tiled_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
-                                       const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* labels, int32_t* index,
-                                       float* boxes, float* rotation, float* translation, float* hand, int32_t* window) try {
-  return pose_from_i420_tiled("hep_pose_from_i420_tiled_rectified: ", false, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
-                              PoseOut{found, scores, labels, index, boxes, rotation, translation, hand}, window, true);
-} HEP_CATCH_INT
-
-int hep_poses_from_i420_tiled_rectified(hep_handle* h, const uint8_t* yuv, int frames, int height, int width, int crop, int resized, int nx, int ny,
-                                        const float* camera, float score_threshold, int32_t* found, float* scores, int32_t* index, float* boxes,
-                                        float* rotation, float* translation, float* hand, int32_t* window) try {
-  return pose_from_i420_tiled("hep_poses_from_i420_tiled_rectified: ", true, h, yuv, frames, height, width, crop, resized, nx, ny, camera, score_threshold,
-                              PoseOut{found, scores, nullptr, index, boxes, rotation, translation, hand}, window, true);
 } HEP_CATCH_INT
 
 // ---- introspection ----

@@ -1,5 +1,6 @@
-// hep_api_util.h - what the three files of the C ABI share (hep_api.cpp: everything that takes a hep_handle; hep_api_eval.cpp: the stateless
-// evaluation and visualisation toolkit; hep_api_train.cpp: the stateless training side).  hep_last_error() returns the message of the calling
+// hep_api_util.h - what the four files of the C ABI share (hep_api.cpp: sessions and everything else that takes a hep_handle; hep_api_pose.cpp:
+// frame to pose - top detection, the hep_pose(s)_from_* host calls, whole-frame search; hep_api_eval.cpp: the stateless evaluation and
+// visualisation toolkit; hep_api_train.cpp: the stateless training side).  hep_last_error() returns the message of the calling
 // thread's last failing call, whichever file the call lives in: the string behind it has ONE definition (hep_api.cpp) and is only declared here.
 #pragma once
 #include <algorithm>

@@ -95,8 +95,9 @@ struct Session {
   int32_t* d_part = nullptr;        // per-class survivors of the detection filter (num_classes > 1)
   float* d_det = nullptr; size_t det_floats = 0;   // staging for host-buffer filter
   float* d_stage[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // host-side inputs of hep_decode / hep_filter (never the forward's outputs)
-  // hep_pose_from_i420 / hep_pose_from_input: [camera rows, padded | frame bytes or input floats] on the device and its pinned
-  // twin on the host (when the upload goes through it), the records on both sides; allocated at first use, only ever grown
+  // the hep_pose(s)_from_* calls (hep_api_pose.cpp pose_run_locked): [camera rows | window table | float64 table | frame bytes or input
+  // floats], the sections a call has, on the device and its pinned twin on the host (when the upload goes through it), the records on both
+  // sides; allocated at first use, only ever grown
   unsigned char* d_pose_in = nullptr; unsigned char* h_pose_in = nullptr; size_t pose_in_bytes = 0, pose_pin_bytes = 0;
   uint32_t* d_rec = nullptr; uint32_t* h_rec = nullptr;
   // hep_poses_from_i420 / hep_poses_from_input: max_batch x num_classes records on both sides, allocated at the first of these calls
@@ -106,7 +107,7 @@ struct Session {
   uint32_t* d_best = nullptr; uint32_t* h_best = nullptr;
   std::vector<int32_t> win_table; std::vector<float> win_cam;      // their grid and its camera rows, built under the mutex: sized once, max_batch rows
   std::vector<double> win_rect;     // the rectified tiled calls: the grid's table of hep_rectify_windows, max_batch rows, built under the mutex
-  bool pose_upload_pinned = false;  // HEP_POSE_UPLOAD=pinned: the upload goes through h_pose_in (the measured alternative, hep_api.cpp pose_stage)
+  bool pose_upload_pinned = false;  // HEP_POSE_UPLOAD=pinned: the upload goes through h_pose_in (the measured alternative, hep_api_pose.cpp pose_run_locked)
   unsigned* d_sync = nullptr;       // meeting counters of grouped launches (k_late.hip): an allocation of its own, zeroed once - never arena memory
   hipStream_t stream = nullptr;     // handle's own stream (host API, capture, profiling)
   std::map<int, std::vector<hipGraphExec_t>> graphs;   // per batch size: one graph per lane
@@ -124,6 +125,13 @@ int build_session(Session* s, const Pack& pack, std::string* err);
 void launch_op(const Session& s, const Op& op, int batch, hipStream_t st, const float* in, const int64_t* strides);   // batch frames starting at `in`
 Pick op_pick(const Op& op);          // the device function launch_op runs for `op` (hep_pick.h); empty: none is built - plan_session refuses such a plan
 int run_forward(Session* s, const float* in_dev, const int64_t* strides, int batch, hipStream_t st, std::string* err);
+// the frame path (hep_api.cpp), shared by the preprocess entry points and the frame-to-pose calls (hep_api_pose.cpp); a refusal sets the message.
+// check_i420: the frame geometry; check_fits: the rows of the resized frame (*nh) fit the network size; preprocess_i420_locked: the launches
+// on `st` with s.mu held - windows / rect are DEVICE tables (centre crop / windowed / rectified windows)
+int check_i420(int height, int width, int crop, int resized);
+int check_fits(const Session& s, int resized, int* nh = nullptr);
+int preprocess_i420_locked(Session& s, const uint8_t* yuv, int batch, int height, int width, int crop, int resized, float* out_hwc, hipStream_t st,
+                           const int32_t* windows = nullptr, const double* rect = nullptr);
 int host_anchors(int size, std::vector<float>* anchors, std::vector<float>* tanchors);
 // rectified windows, host arithmetic (hep_rectify.cpp, built without contraction; tests/_rectify.py states every rounding).
 // rectify_row: the table row (R_w row-major, fx, fy, px, py) of window w = {frame, ox, oy} from its frame's centre camera row.
@@ -132,3 +140,5 @@ void rectify_row(const float* camera_row, const int32_t* w, int height, int widt
 bool rectified_point(const double* row, double x, double y, int height, int width, int crop, int resized, int side, double* xy);
 
 }  // namespace hep
+
+struct hep_handle { hep::Session s; };      // the handle of include/hep.h (hep_api.cpp, hep_api_pose.cpp)

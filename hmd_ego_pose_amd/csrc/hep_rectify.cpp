@@ -1,5 +1,5 @@
 // hep_rectify.cpp - the host arithmetic of the rectified windows (include/hep.h: hep_rectify_windows, hep_rectified_point_to_frame,
-// hep_window_from_box_rectified; their argument checks live with the other whole-frame entry points in hep_api.cpp).  Built with
+// hep_window_from_box_rectified; their argument checks live with the other whole-frame entry points in hep_api_pose.cpp).  Built with
 // -ffp-contract=off (Makefile): tests/_rectify.py states every product and sum in this order and is reproduced bit for bit.
 #include <math.h>
 #include <stdint.h>

@@ -9,6 +9,28 @@
 
 namespace hep {
 
+// everything build_session and the entry points (hep_api.cpp, hep_api_pose.cpp) allocated for the handle, at first use or before
+Session::~Session() {
+  if (!realised) return;            // planned on the host only (hep_plan_launch_list): no device object exists and no HIP call is made
+  for (auto& g : graphs) for (hipGraphExec_t ge : g.second) hipGraphExecDestroy(ge);
+  for (auto& lo : lane_ops) for (Op& o : lo) {
+    if (o.kind == OP_SEP) { hipFree((void*)o.sep.segs); hipFree((void*)o.sep.tile_seg); }
+    if (o.kind == OP_CHAIN) hipFree((void*)o.chain.nodes);
+  }
+  for (hipStream_t st : lane_streams) hipStreamDestroy(st);
+  for (hipEvent_t ev : lane_events) hipEventDestroy(ev);
+  if (fork_event) hipEventDestroy(fork_event);
+  if (pre_event) hipEventDestroy(pre_event);
+  hipFree(d_sync); hipFree(d_weights); hipFree(d_arena); hipFree(d_pre[0]); hipFree(d_pre[1]);
+  for (int i = 0; i < 5; i++) { hipFree(d_out[i]); hipFree(d_feat_nchw[i]); }
+  hipFree(d_in); hipFree(d_anchors); hipFree(d_tanchors); hipFree(d_boxes); hipFree(d_trans); hipFree(d_cam);
+  hipFree(d_keys); hipFree(d_det); hipFree(d_part);
+  for (int i = 0; i < 5; i++) hipFree(d_stage[i]);
+  hipFree(d_pose_in); hipFree(d_rec); hipHostFree(h_pose_in); hipHostFree(h_rec); hipFree(d_recs); hipHostFree(h_recs);
+  hipFree(d_best); hipHostFree(h_best);
+  if (stream) hipStreamDestroy(stream);
+}
+
 size_t sync_lane_words(const Session& s, const Plan& plan) {
   // per lane: 16 words per image for the grouped late kernel, then ntails blocks of one 128-byte line per image (arrival tickets of the fronts' tails)
   return (size_t)s.lane_batch * 16 + (size_t)plan.ntails * s.lane_batch * 32;

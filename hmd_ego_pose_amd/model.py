@@ -325,55 +325,57 @@ class Session:
         and ``windows`` [n,3] int32 {frame, ox, oy}, both on the device -> the NCHW view of [n, size, size, 3]; image i is the frame path's
         arithmetic with the crop taken at (ox, oy) of frame ``frame``.  The table is trusted by the kernel: its shape and dtype are checked
         here, its values are the caller's (``pose_from_i420_windows`` checks a host table)."""
-        if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 2 or frames_u8.shape[1] != height * width * 3 // 2:
-            raise ValueError("preprocess_i420_windows: expected a uint8 ROCm tensor [F, height * width * 3 // 2]")
-        if (not isinstance(windows, torch.Tensor) or windows.device != frames_u8.device or windows.dtype != torch.int32 or windows.dim() != 2
-                or windows.shape[1] != 3 or not 1 <= windows.shape[0] <= self.max_batch):
-            raise ValueError(f"preprocess_i420_windows: windows must be an int32 tensor (n, 3) on {frames_u8.device} with n in 1..{self.max_batch}")
-        x, w = frames_u8.contiguous(), windows.contiguous()
-        out = torch.empty((w.shape[0], self.size, self.size, 3), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _capi.check(_capi.lib().hep_preprocess_i420_windows_device(self.handle, x.data_ptr(), x.shape[0], height, width, w.data_ptr(), w.shape[0],
-                                                                   crop, resized, out.data_ptr(), stream))
-        return out.permute(0, 3, 1, 2)
+        return self._preprocess_windows("preprocess_i420_windows", frames_u8, height, width, windows, None, crop, resized)
 
     def preprocess_i420_rectified(self, frames_u8: torch.Tensor, height: int, width: int, windows: torch.Tensor, table: torch.Tensor,
                                   crop: int = 256, resized: int = 512) -> torch.Tensor:
         """``preprocess_i420_windows`` on RECTIFIED windows (hep_preprocess_i420_rectified_device): ``table`` [n,13] float64 on the device, the
         rows of ``rectify_windows`` for ``windows`` -> the NCHW view of [n, size, size, 3]; image i is the frame resampled into the view of the
         camera rotated to look along window i's ray.  Every tap is clamped to the frame: no table value reads outside it."""
-        who = "preprocess_i420_rectified"
+        return self._preprocess_windows("preprocess_i420_rectified", frames_u8, height, width, windows, (table,), crop, resized)
+
+    def _preprocess_windows(self, who, frames_u8, height, width, windows, table, crop, resized):
+        """the two calls above: device frames and device windows checked, ``table`` = None or (the rectified call's device table,)"""
         if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 2 or frames_u8.shape[1] != height * width * 3 // 2:
             raise ValueError(f"{who}: expected a uint8 ROCm tensor [F, height * width * 3 // 2]")
         if (not isinstance(windows, torch.Tensor) or windows.device != frames_u8.device or windows.dtype != torch.int32 or windows.dim() != 2
                 or windows.shape[1] != 3 or not 1 <= windows.shape[0] <= self.max_batch):
             raise ValueError(f"{who}: windows must be an int32 tensor (n, 3) on {frames_u8.device} with n in 1..{self.max_batch}")
-        if (not isinstance(table, torch.Tensor) or table.device != frames_u8.device or table.dtype != torch.float64
-                or tuple(table.shape) != (windows.shape[0], _capi.RECTIFY_ROW_DOUBLES)):
-            raise ValueError(f"{who}: table must be a float64 tensor ({windows.shape[0]}, {_capi.RECTIFY_ROW_DOUBLES}) on {frames_u8.device}")
-        x, w, t = frames_u8.contiguous(), windows.contiguous(), table.contiguous()
+        x, w = frames_u8.contiguous(), windows.contiguous()
+        t = () if table is None else (self._device_table(who, table[0], w.shape[0], x.device).data_ptr(),)
         out = torch.empty((w.shape[0], self.size, self.size, 3), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _capi.check(_capi.lib().hep_preprocess_i420_rectified_device(self.handle, x.data_ptr(), x.shape[0], height, width, w.data_ptr(), t.data_ptr(),
-                                                                     w.shape[0], crop, resized, out.data_ptr(), stream))
+        fn = _capi.lib().hep_preprocess_i420_windows_device if table is None else _capi.lib().hep_preprocess_i420_rectified_device
+        _capi.check(fn(self.handle, x.data_ptr(), x.shape[0], height, width, w.data_ptr(), *t, w.shape[0], crop, resized, out.data_ptr(),
+                       torch.cuda.current_stream(x.device).cuda_stream))
         return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def _device_table(who, table, n, device):
+        """the table [n,13] float64 of ``rectify_windows`` on ``device``, next to n windows or records there -> contiguous"""
+        if (not isinstance(table, torch.Tensor) or table.device != device or table.dtype != torch.float64
+                or tuple(table.shape) != (n, _capi.RECTIFY_ROW_DOUBLES)):
+            raise ValueError(f"{who}: table must be a float64 tensor ({n}, {_capi.RECTIFY_ROW_DOUBLES}) on {device}")
+        return table.contiguous()
+
+    @staticmethod
+    def _device_records(who, records, in_place=False):
+        """device records [n,80] or [n,K,80] int32 (``in_place``: written where they lie, so contiguous) -> (n, slots)"""
+        if (not isinstance(records, torch.Tensor) or not records.is_cuda or records.dtype != torch.int32 or records.dim() not in (2, 3)
+                or records.shape[-1] != _capi.POSE_RECORD_WORDS or (in_place and not records.is_contiguous())):
+            raise ValueError(f"{who}: records must be {'a contiguous' if in_place else 'an'} int32 ROCm tensor [n,80] or [n,K,80]")
+        return records.shape[0], (records.shape[1] if records.dim() == 3 else 1)
 
     @staticmethod
     def derotate_records(records: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
         """Back-rotation of the records of n rectified windows IN PLACE, one launch (hep_derotate_records_device): ``records`` [n,80]
         (``top1``) or [n,K,80] (``top_labels``) int32, contiguous, and ``table`` [n,13] float64 on the device.  Rotation, translation and hand
         of every found record go from the rectified camera's frame to the real camera's; everything else stays.  Returns ``records``."""
-        if (not isinstance(records, torch.Tensor) or not records.is_cuda or records.dtype != torch.int32 or records.dim() not in (2, 3)
-                or records.shape[-1] != _capi.POSE_RECORD_WORDS or not records.is_contiguous()):
-            raise ValueError("derotate_records: records must be a contiguous int32 ROCm tensor [n,80] or [n,K,80]")
-        n, slots = records.shape[0], (records.shape[1] if records.dim() == 3 else 1)
-        if (not isinstance(table, torch.Tensor) or table.device != records.device or table.dtype != torch.float64
-                or tuple(table.shape) != (n, _capi.RECTIFY_ROW_DOUBLES)):
-            raise ValueError(f"derotate_records: table must be a float64 tensor ({n}, {_capi.RECTIFY_ROW_DOUBLES}) on {records.device}")
+        n, slots = Session._device_records("derotate_records", records, in_place=True)
+        t = Session._device_table("derotate_records", table, n, records.device)
         if n < 1 or not 1 <= slots <= 63:
             raise ValueError("derotate_records: n must be at least 1, slots in 1..63")
         stream = torch.cuda.current_stream(records.device).cuda_stream
-        _capi.check(_capi.lib().hep_derotate_records_device(records.data_ptr(), slots, table.contiguous().data_ptr(), n, stream))
+        _capi.check(_capi.lib().hep_derotate_records_device(records.data_ptr(), slots, t.data_ptr(), n, stream))
         return records
 
     @staticmethod
@@ -382,10 +384,7 @@ class Session:
         (``top_labels``) int32 and ``windows`` [n,3] int32 on the device -> (records [frames,80] or [frames,K,80], window [frames] or
         [frames,K] int32): per frame and slot the found record with the largest score among the frame's windows, ties to the lowest window,
         copied bit for bit; no such window: the not-found record and window -1."""
-        if (not isinstance(records, torch.Tensor) or not records.is_cuda or records.dtype != torch.int32 or records.dim() not in (2, 3)
-                or records.shape[-1] != _capi.POSE_RECORD_WORDS):
-            raise ValueError("best_window: records must be an int32 ROCm tensor [n,80] or [n,K,80]")
-        n, slots = records.shape[0], (records.shape[1] if records.dim() == 3 else 1)
+        n, slots = Session._device_records("best_window", records)
         if (not isinstance(windows, torch.Tensor) or windows.device != records.device or windows.dtype != torch.int32
                 or tuple(windows.shape) != (n, 3)):
             raise ValueError(f"best_window: windows must be an int32 tensor ({n}, 3) on {records.device}")
@@ -412,16 +411,17 @@ class Session:
         if not 1 <= x.shape[0] <= self.max_batch:
             raise ValueError(f"{who}: {x.shape[0]} frames are outside 1..{self.max_batch}")
         w = self._windows_host(who, windows, x.shape[0], height, width, crop)
-        l = _capi.lib()
-        if rectified:
-            fn = l.hep_poses_from_i420_windows_rectified if per_label else l.hep_pose_from_i420_windows_rectified
-        else:
-            fn = l.hep_poses_from_i420_windows if per_label else l.hep_pose_from_i420_windows
-        return self._pose_call(who, fn, (x.ctypes.data, x.shape[0], height, width, w.ctypes.data, w.shape[0], crop, resized), w.shape[0], camera,
-                               score_threshold, per_label=per_label, cam_rows=x.shape[0] if rectified else None)
+        return self._pose_call(who, self._search_fn("windows", per_label, rectified),
+                               (x.ctypes.data, x.shape[0], height, width, w.ctypes.data, w.shape[0], crop, resized), w.shape[0], camera, score_threshold, per_label=per_label, cam_rows=x.shape[0] if rectified else None)
 
-    def _tiled(self, who, fn, per_label, frames_u8_host, height, width, camera, crop, resized, nx, ny, score_threshold):
+    @staticmethod
+    def _search_fn(form, per_label, rectified):
+        """the C call of the "windows" or "tiled" form: hep_pose(s)_from_i420_<form>[_rectified]"""
+        return getattr(_capi.lib(), f"hep_{'poses' if per_label else 'pose'}_from_i420_{form}{'_rectified' if rectified else ''}")
+
+    def _tiled(self, who, per_label, rectified, frames_u8_host, height, width, camera, crop, resized, nx, ny, score_threshold):
         import numpy as np
+        fn = self._search_fn("tiled", per_label, rectified)
         x = self._i420_host(who, frames_u8_host, height, width, crop, resized)
         F = x.shape[0]
         if nx < 1 or ny < 1 or not 1 <= F * nx * ny <= self.max_batch:
@@ -440,17 +440,13 @@ class Session:
         -1.  Boxes are in the winning window's network-input pixels; a 1 x 1 grid is ``pose_from_i420`` bit for bit.
         ``rectified=True`` (hep_pose_from_i420_tiled_rectified): the grid's windows are rectified and the winner's pose is in the real camera's
         frame, exact off the optical axis; the box is in network-input pixels of the RECTIFIED window (``window_from_box_rectified``)."""
-        l = _capi.lib()
-        return self._tiled("pose_from_i420_tiled", l.hep_pose_from_i420_tiled_rectified if rectified else l.hep_pose_from_i420_tiled, False, frames_u8_host, height, width, camera, crop, resized,
-                           nx, ny, score_threshold)
+        return self._tiled("pose_from_i420_tiled", False, rectified, frames_u8_host, height, width, camera, crop, resized, nx, ny, score_threshold)
 
     def poses_from_i420_tiled(self, frames_u8_host, height: int, width: int, camera, crop: int = 256, resized: int = 512, nx: int = 1, ny: int = 1,
                               score_threshold=0.5, rectified=False):
         """``pose_from_i420_tiled`` for several objects (hep_poses_from_i420_tiled; ``rectified``: hep_poses_from_i420_tiled_rectified): arrays
         [F,K,...] as ``poses_from_i420``, ``window`` [F,K]."""
-        l = _capi.lib()
-        return self._tiled("poses_from_i420_tiled", l.hep_poses_from_i420_tiled_rectified if rectified else l.hep_poses_from_i420_tiled, True, frames_u8_host, height, width, camera, crop, resized,
-                           nx, ny, score_threshold)
+        return self._tiled("poses_from_i420_tiled", True, rectified, frames_u8_host, height, width, camera, crop, resized, nx, ny, score_threshold)
 
     # -- introspection ------------------------------------------------------------------
     def stage(self, name: str, batch: int) -> torch.Tensor:

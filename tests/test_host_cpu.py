@@ -288,7 +288,7 @@ def test_corrupt_pack_is_refused_without_reading_out_of_bounds():
 
 
 def test_no_cpp_exception_crosses_the_c_abi():
-    """include/hep.h: "never throws".  Every extern "C" entry point is a function-try-block (csrc/hep_api.cpp): a std::bad_alloc /
+    """include/hep.h: "never throws".  Every extern "C" entry point is a function-try-block (csrc/hep_api*.cpp): a std::bad_alloc /
     length_error raised while a hostile pack is copied, or anything else a C++ body could throw, comes back as HEP_ERR_INTERNAL
     with a message instead of unwinding into a ctypes / P/Invoke caller (which terminates the process).  Truncated tables and
     oversized headers are plain HEP_ERR_PACK."""

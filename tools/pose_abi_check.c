@@ -28,7 +28,8 @@ int main(void) {
   uint8_t* yuv = calloc(64, 1);
   int32_t* found = calloc(4, sizeof(int32_t));
   uint32_t* rec = calloc(HEP_POSE_RECORD_WORDS, sizeof(uint32_t));
-  hep_handle* h = (hep_handle*)yuv;               /* a stand-in: the checks walked with it come before the handle is read */
+  hep_handle* h = calloc(1, 1 << 16);             /* a stand-in, zeroed: the checks walked with it come before the handle is read, but for
+                                                     the batch of the two device calls, whose one range check reads max_batch (here 0) */
 
   REFUSED(hep_top1_device(NULL, NULL, NULL, NULL, NULL, NULL, f, 1, 0.5f, rec, NULL), "handle is NULL");
   REFUSED(hep_top1_device(h, NULL, NULL, NULL, NULL, NULL, NULL, 1, 0.5f, rec, NULL), "camera is NULL");
@@ -81,7 +82,7 @@ int main(void) {
   REFUSED(I420S(h, yuv, 1, 480, 640, 0, 512, f, found), "crop");
   REFUSED(I420S(h, yuv, 1, 480, 640, 256, 0, f, found), "resized");
 
-  free(f); free(yuv); free(found); free(rec);
+  free(f); free(yuv); free(found); free(rec); free(h);
   printf(failures ? "%d check(s) failed\n" : "all argument checks returned as documented\n", failures);
   return failures != 0;
 }
